@@ -23,8 +23,11 @@ N = 1 with --mode decomposed [--shares S]: the partitioned code path on ONE GPU 
 (the plan an S-GPU run would use), the shares are eroded one after the other with the same masks, merged, and checked against
 the oracle's CRC; the line reports the time of every share (what each of S GPUs would spend) next to the sequential total.
 
-Prints ONE JSON line on rank 0 with the `roofline` (dominant kernel family, HIP-event timed) and
-`cpu_baseline` (the CPU oracle on a bounded sample of the same workload, rank 0, N=1 only) objects.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps, writes the last step's field if
+--dump-outputs DIR is given and prints the line.  Everything else is measured only with --full: the oracle CRC check
+(`parity`), the `roofline` (dominant kernel family, HIP-event timed), `cpu_baseline` (the CPU oracle on a bounded sample of
+the same workload), `new_terrain`, `with_transfers`, `relaxed_mode`, `ensemble_in_flight` (N = 1), the D2D copy rate,
+`ensemble_seeds` and the `one_planet` leg (N > 1).
 """
 from __future__ import annotations
 
@@ -441,6 +444,18 @@ def parity_crc(pl, cells: int, iters: int, seed: int = 1):
     return out
 
 
+DUMP_BYTES = 60_000_000          # --dump-outputs writes at most this many bytes of data (under 64 MB with the .npy header)
+
+
+def dump_outputs(out_dir: Path, field: np.ndarray):
+    """--dump-outputs: the elevation field a caller of the timed path receives, float32.  A field larger than DUMP_BYTES is written as
+    cells 0, k, 2k, ... (k fixed by the cell count), so two runs with the same arguments write the same cells."""
+    field = np.ascontiguousarray(field, dtype=np.float32)
+    k = -(-field.nbytes // DUMP_BYTES)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / ("elevation.npy" if k == 1 else f"elevation_every_{k}.npy"), field[::k])
+
+
 def with_transfers_ms(pl, seed, params):
     """the same step through the JS call surface's entry points, which take and return HOST arrays (every call
     copies r_elevation in and out and r_isOcean in: 2 x 4 B + 1 B per cell per call over PCIe).  One step, wall time in ms."""
@@ -588,13 +603,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cells", type=int, default=10_000_000)
     ap.add_argument("--iters", type=int, default=200, help="composite iterations per step (200 = BASELINE config)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every supplementary measurement and check (oracle CRC, roofline, "
+                                                         "CPU baseline, new terrains, transfers, relaxed mode, planets in flight, D2D copy rate; N > 1: "
+                                                         "per-seed CRCs and the one-planet leg); the --no-* options below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the field of the last timed step (rank 0) to DIR/elevation.npy (float32; "
+                                                                        "above 60 MB, every k-th cell to DIR/elevation_every_<k>.npy)")
     ap.add_argument("--cpu-iters", type=int, default=4)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-relaxed", action="store_true", help="skip the relaxed-mode measurement (N = 1)")
     ap.add_argument("--no-transfers", action="store_true", help="skip the step through the host-array entry points (value_with_transfers)")
-    ap.add_argument("--timed-only", action="store_true", help="nothing but warm-up and the timed steps (what a rocprofv3 trace of the timed region wants): "
-                                                               "= --no-cpu --no-profile --no-relaxed --no-transfers --in-flight 0")
+    ap.add_argument("--timed-only", action="store_true", help="nothing but warm-up and the timed steps (what a rocprofv3 trace of the timed region wants), "
+                                                               "even with --full; the same as a run without --full")
     ap.add_argument("--in-flight", type=int, default=6, help="planets in flight for the supplementary ensemble figure (0 = skip)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl", help="gloo + --share-gpu: rehearse the multi-rank path on a one-GPU box (not a measurement)")
     ap.add_argument("--share-gpu", action="store_true", help="all ranks use device 0")
@@ -616,7 +636,10 @@ def main():
     ap.add_argument("--one-planet-parity-iters", type=int, default=20, help="one extra untimed step at this iteration count, whose CRC the committed oracle checksum covers (0 = skip)")
     ap.add_argument("--one-planet-warmup", type=int, default=1)
     args = ap.parse_args()
-    if args.timed_only:
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    full = args.full and not args.timed_only
+    if not full:
         args.no_cpu = args.no_profile = args.no_relaxed = args.no_transfers = True
         args.in_flight = 0
 
@@ -749,10 +772,12 @@ def main():
     wall = dist_max(dist, wall, "cuda" if args.backend == "nccl" else "cpu")
     stats = pl.last_erode_stats()
     stages = pl.last_stage_timing()
-    crc = parity_crc(pl, args.cells, max(params["hIters"], params["tIters"], params["gIters"])) if (rank == 0 and seed == 1) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), fleet[(args.steps - 1) % len(fleet)].download())
+    crc = parity_crc(pl, args.cells, max(params["hIters"], params["tIters"], params["gIters"])) if (full and rank == 0 and seed == 1) else None
     # config 5: which seeds this job ran, and for each the CRC of its field against the oracle's where tests/golden/crc_config3.json has one
     seeds_run = None
-    if world > 1 and not decomposed_mode:
+    if full and world > 1 and not decomposed_mode:
         it_ = max(params["hIters"], params["tIters"], params["gIters"])
         mine = [dict(rank=rank, seed=sk, steps=len([i for i in range(args.steps) if i % len(fleet) == j]), **parity_crc(q, args.cells, it_, sk))
                 for j, (q, sk) in enumerate(zip(fleet, fleet_seeds))]
@@ -768,7 +793,7 @@ def main():
     # mirror, flood tables, land lists, launch-count prediction) are cached after the first step.  Three other terrains on the same mesh, one step each,
     # with those tables rebuilt inside the clock; then the benched terrain again (untimed) for the legs below.
     new_terrain = None
-    if rank == 0 and world == 1 and not virt and not args.timed_only:
+    if full and rank == 0 and world == 1 and not virt:
         ms_new = []
         for s2 in (seed + 101, seed + 102, seed + 103):
             pl.synthetic_terrain(s2); pl.save_state(); pl.sync()
@@ -923,7 +948,7 @@ def main():
         relaxed = relaxed_mode_leg(pl, seed, params, pl.download(), N)
     # everything the line needs is worked out HERE, before the one-planet leg: its watchdog may only print (no torch / GPU call from the
     # timer thread: a collective that never gets its peers would block a device synchronisation for ever)
-    d2d_GBs = round(d2d_bandwidth_GBs(local_rank), 1) if rank == 0 else None
+    d2d_GBs = round(d2d_bandwidth_GBs(local_rank), 1) if (full and rank == 0) else None
     host_threads = host_thread_usage()
 
     def build_line(one_planet):
@@ -960,7 +985,7 @@ def main():
             sys.stdout.flush()
 
     one_planet = None
-    if world > 1 and not decomposed_mode and args.mode == "auto" and args.one_planet_cells > 0:
+    if full and world > 1 and not decomposed_mode and args.mode == "auto" and args.one_planet_cells > 0:
         pl.close()
         # The one-planet leg exchanges between ranks inside the flood stage (a path that has never had real peers on this pool): should it not
         # come back, the ensemble measurement above must not be lost with it — after the timeout rank 0 prints the line without the leg and
