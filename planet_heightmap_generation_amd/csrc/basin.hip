@@ -82,7 +82,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_basin_jump(const int32_t* __restri
     }
 }
 // thread i: the i-th cell in processing order (largest rank first)
-// scramble (test hook, WO_BASIN_SCRAMBLE=1): every third cell is sent to the neighbouring group, so groups are no longer closed under
+// scramble (test hook basin_scramble): every third cell is sent to the neighbouring group, so groups are no longer closed under
 // the dependencies and the launch leaves tasks pending — the k_solve_patch launches that finish them must give the same bits
 __global__ __launch_bounds__(WO_BLOCK) void k_basin_keys(const int32_t* __restrict__ land, const uint32_t* __restrict__ keyOfCell, int32_t L,
                                                           uint32_t* __restrict__ keys, int32_t* __restrict__ vals, int32_t scramble, int32_t* rangeStart, int32_t nRangeWords) {
@@ -214,7 +214,7 @@ __device__ inline SolveOut solve_apply_recip(const SolveTask& T, double factor, 
 }
 
 // Waves per range: TWO (measured at 10 M cells, solve launches per step: 1 wave 66.7 ms, 2 waves 45.5, 4 waves 48.2, 8 waves 77.7; lag 1 / 2 / 6
-// super-chunks with two waves: 45.6 / 45.5 / 52.5).  A wave spends ~2 000 clocks in a pass that holds a turn (WO_BASIN_STATS: 80 % of the
+// super-chunks with two waves: 45.6 / 45.5 / 52.5).  A wave spends ~2 000 clocks in a pass that holds a turn (k_solve_flowing<..., true>: 80 % of the
 // slowest range's time is inside turns, 75 % of its passes hold one) and a hand-off to another wave costs about as much again, so fewer,
 // fuller waves win until one wave has to take every level alone.
 template <int NW, bool STATS, int LAG_ = 2>
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(64 * NW, (NW <= 4 ? 4 : 2)) void k_solve_flowing(Fi
     static_assert(LOOKBACK + LAG + 1 <= RCHUNKS, "ring too small for the lag");
     __shared__ unsigned long long s_ring[2 * RING];
     __shared__ int32_t s_prog[NW];                     // super-chunks each wave has finished
-    __shared__ int32_t s_level[STATS ? RING : 1];      // WO_BASIN_STATS (diagnostic): depth of every task in the dependency DAG
+    __shared__ int32_t s_level[STATS ? RING : 1];      // STATS (diagnostic): depth of every task in the dependency DAG
     __shared__ int32_t s_maxLevel;
     __shared__ unsigned long long s_passes[STATS ? NW : 1], s_readyPasses[STATS ? NW : 1], s_clk[4];
     unsigned long long myPasses = 0, myReady = 0, cRead = 0, cTurn = 0, cRest = 0, cWait = 0;
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(64 * NW, (NW <= 4 ? 4 : 2)) void k_solve_flowing(Fi
         }
         // The polling loop as straight-line code: a single wave issues one instruction every few clocks, and the loop the
         // compiler made of the nested conditions above was ~250 instructions per pass (~2 000 clocks per level of the DAG,
-        // WO_BASIN_STATS, profiles/r04e_*).  Here a pass reads the three ring words (a predecessor already in hand reads the
+        // k_solve_flowing<..., true>, profiles/r04e_*).  Here a pass reads the three ring words (a predecessor already in hand reads the
         // task's own word), tests the tags with integer compares, and — only when some lane is ready — runs the turn for the
         // whole wave without a branch (solve_apply_flat: the same operations on the same values, selected at the end).  Tags
         // do not change once written (the ring slot is reused LAG super-chunks later at the earliest), so nothing is latched.
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(64 * NW, (NW <= 4 ? 4 : 2)) void k_solve_flowing(Fi
             }
             const long long c2 = STATS ? clock64() : 0;
             if (STATS) { cRead += (unsigned long long)(c1 - c0); cTurn += (unsigned long long)(c2 - c1); }
-            if (__any(open & bad)) {                                     // a predecessor is blocked (never on real layouts: WO_BASIN_SCRAMBLE)
+            if (__any(open & bad)) {                                     // a predecessor is blocked (never on real layouts: hook basin_scramble)
                 if (open & bad) { blocked = true; ring_put(myWord, 0.0f, -(q + 1)); ring_put(myWord + 1, 0.0f, -(q + 1)); open = false; }
             }
         }

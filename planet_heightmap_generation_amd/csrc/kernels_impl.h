@@ -264,7 +264,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_flow_climb(Fields F, const int32_t
     }
 }
 // ---------------------------------------------------------------------------------------------------------------------
-// Flow accumulation in two levels (default under the land-first mirror; WO_FLOW=climb: k_flow_climb alone).
+// Flow accumulation in two levels (default under the land-first mirror; on the planet's own cell order, WO_LAYOUT=index: k_flow_climb alone).
 // k_flow_climb pays one returning device-scope atomic — a round trip to the memory side, ~0.5 us under load — per cell of the longest
 // flow path (a few hundred cells at 10 M: ~200 us per launch with the chip idle).  The land cells are numbered in Morton order, so a TILE
 // of FT_CELLS consecutive ids is a compact patch and ~95 % of the forward edges stay inside one.  Hence:
@@ -1183,7 +1183,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_mirror_rows(const int32_t* off, co
 }
 
 // {serial, value} of a device counter into a host-mapped word: the host polls the word instead of paying a copy, a stream
-// synchronisation and its wake-up for one integer (planet.hip: publish_and_wait)
+// synchronisation and its wake-up for one integer (planet.hip: read_count)
 __global__ void k_publish_count(const int32_t* __restrict__ src, unsigned long long* hostWord, uint32_t serial) {
     if (threadIdx.x == 0 && blockIdx.x == 0)
         __hip_atomic_store(hostWord, ((unsigned long long)serial << 32) | (unsigned long long)(uint32_t)*src, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -122,14 +122,13 @@ static void refresh_host_ocean(wo_planet* p) {
 // One device integer for the host, through a host-mapped word the host polls: ~10 us from the producing kernel's end to the next
 // launch instead of ~30 (copy kernel, stream synchronisation, wake-up).  Falls back to the copy when the word is not there or the
 // poll outlasts 2 s (a faulted stream must surface as an error, not as a hang).
-static int32_t publish_and_wait(wo_planet* p, const int32_t* d_ptr) {
-    const bool poll = true;
+static int32_t read_count(wo_planet* p, const int32_t* d_ptr) {
     hipStream_t s = p->ctx->stream;
-    if (poll && !p->h_word) {
+    if (!p->h_word) {
         if (hipHostMalloc((void**)&p->h_word, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&p->d_word, p->h_word, 0) != hipSuccess) { p->h_word = nullptr; p->d_word = nullptr; (void)hipGetLastError(); }
         else *p->h_word = 0;
     }
-    if (poll && p->h_word) {
+    if (p->h_word) {
         const uint32_t serial = ++p->wordSerial;
         hipLaunchKernelGGL(k_publish_count, dim3(1), dim3(1), 0, s, d_ptr, p->d_word, serial);
         const auto t0 = std::chrono::steady_clock::now();
@@ -148,25 +147,21 @@ static int32_t publish_and_wait(wo_planet* p, const int32_t* d_ptr) {
     return p->h_count[0];
 }
 
-int32_t read_count(wo_planet* p, const int32_t* d_ptr) { return publish_and_wait(p, d_ptr); }
-
-// Patch-local solve driver: launches k_solve_patch until no task is pending.  Returns the number of launches.
-// basin: the store order is the group-major one of basin_layout() and the first launch of the pass is k_solve_basin, which
-// normally leaves nothing pending; whatever it does leave (layout off: see basin.hip) is finished by k_solve_patch launches.
-static int64_t run_solve_patches(wo_planet* p, const Fields& F, double K, double m, double dt, bool basin, bool countersCleared = false, bool deferCheck = false, int32_t passTag = 1) {
+// Basin solve driver (basin.hip): the first launch of the pass is k_solve_basin on the group-major store order of basin_layout(), which
+// normally leaves nothing pending; whatever it does leave (layout off: see basin.hip) is finished by k_solve_patch launches until no task
+// is pending.  Returns the number of launches.  The pass's setup launch (k_solve_setup_batched) has cleared the patch counters and the
+// pending totals: one slot per launch, cleared once per pass (a memset per launch was 13.6 k fill kernels per step).
+static int64_t run_solve_patches(wo_planet* p, const Fields& F, double K, double m, double dt, bool deferCheck, int32_t passTag) {
     hipStream_t s = p->ctx->stream;
     const int np = p->numPatches;
-    if (basin && deferCheck && countersCleared) {
+    if (deferCheck) {
         // the one launch of the basin solve, and no look at what it left: tasks left pending are counted into a word that is not
         // cleared during the call and looked at where the host synchronises anyway (erode_composite: RedoWithChecks)
         basin_solve_launch(p, F, passTag, p->d_pendingEver);
         p->lastPatchLaunches = 1;
         return 1;
     }
-    if (!countersCleared) launch(p, FAM_MISC, k_fill_i32, blocks_for(np, 64), WO_BLOCK, p->d_patchPending, basin ? 0 : 1, (int32_t)np);
-    // one pending-total slot per launch, cleared once per pass (a memset per launch was 13.6 k fill kernels per step)
     int32_t* tot = p->d_patchTotals;
-    if (!countersCleared) WO_HIP(hipMemsetAsync(tot, 0, (size_t)WO_PATCH_TOTAL_SLOTS * sizeof(int32_t), s));
     int64_t launches = 0;
     // polling passes per visit (kernels_impl.h); launches from lateFrom on (few patches still open: no queue of visits behind a
     // long one) may poll longer
@@ -185,18 +180,18 @@ static int64_t run_solve_patches(wo_planet* p, const Fields& F, double K, double
                 if (b > 0) break;
                 WO_HIP(hipMemsetAsync(tot, 0, (size_t)WO_PATCH_TOTAL_SLOTS * sizeof(int32_t), s));   // wrapped: every earlier slot has been read back
             }
-            if (basin && tag == 1) basin_solve_launch(p, F, tag, tot + 1);
+            if (tag == 1) basin_solve_launch(p, F, tag, tot + 1);
             else {
-            // the first k_solve_patch launch after a lean setup: its blocker hints are made from the records now (only tasks the basin
-            // launch left pending get one; normally there is no such launch at all)
-            if (basin && tag == 2 && F.solveLean) launch(p, FAM_MISC, k_solve_blk_init, blocks_for(p->L, 4096), WO_BLOCK, F, p->L);
-            launch(p, FAM_SOLVE_PATCH, k_solve_patch, np, WO_PATCH_THREADS, F, p->L, tag, p->d_patchPending, tot + (tag % WO_PATCH_TOTAL_SLOTS), K, m, dt,
-                   (int32_t*)nullptr, (int32_t)(tag >= lateFrom ? lateCap : spinCap));
+                // the first k_solve_patch launch after a lean setup: its blocker hints are made from the records now (only tasks the basin
+                // launch left pending get one; normally there is no such launch at all)
+                if (tag == 2 && F.solveLean) launch(p, FAM_MISC, k_solve_blk_init, blocks_for(p->L, 4096), WO_BLOCK, F, p->L);
+                launch(p, FAM_SOLVE_PATCH, k_solve_patch, np, WO_PATCH_THREADS, F, p->L, tag, p->d_patchPending, tot + (tag % WO_PATCH_TOTAL_SLOTS), K, m, dt,
+                       (int32_t*)nullptr, (int32_t)(tag >= lateFrom ? lateCap : spinCap));
             }
             ++launches;
         }
-        if (basin && first == 1 && tag == 2) {                     // the usual case: the one launch of the basin solve, one total to look at
-            if (publish_and_wait(p, tot + 1) == 0) need = 1;
+        if (first == 1 && tag == 2) {                     // the usual case: the one launch of the basin solve, one total to look at
+            if (read_count(p, tot + 1) == 0) need = 1;
         } else {
             WO_HIP(hipMemcpyAsync(p->h_patchTotals, tot, (size_t)WO_PATCH_TOTAL_SLOTS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
             WO_HIP(hipStreamSynchronize(s));
@@ -205,8 +200,14 @@ static int64_t run_solve_patches(wo_planet* p, const Fields& F, double K, double
         if (need) break;
         if (launches > 4 * (int64_t)p->N + 1024) throw HipError{"patch solve does not converge"};
     }
-    p->lastPatchLaunches = basin ? need : need + 1;      // basin: the first burst is exactly what the last pass needed (one launch)
+    p->lastPatchLaunches = need;      // the first burst is exactly what the last pass needed (its first launch is the basin one)
     return need;
+}
+
+// The stage brackets of an earlier call, never asked for: their events back to the pool
+static void release_stage_brackets(wo_planet* p) {
+    for (auto& b : p->stageBrackets) { p->eventPool.push_back(b.a); p->eventPool.push_back(b.b); }
+    p->stageBrackets.clear(); p->stageSeen.clear(); p->stagePending = false;
 }
 
 // Stage timings (wo_last_stage_timing, the reference's _postTiming).  A pair of event records costs ~10 us of stream time, and the
@@ -226,16 +227,12 @@ struct StageClock {
         hipEvent_t a = profile_event(p), b = profile_event(p); WO_HIP(hipEventRecord(a, p->ctx->stream)); ev.push_back({name, {a, b}});
     }
     void end() { if (open) WO_HIP(hipEventRecord(ev.back().second.second, p->ctx->stream)); open = false; }
-    void count_only(const char* name) { ++seen[name].first; }       // an occurrence that is not bracketed (an iteration replayed from the graph)
     void finish() {
         // the brackets are handed to the planet as they are; wo_last_stage_timing turns them into milliseconds when somebody asks
-        for (auto& b : p->stageBrackets) { p->eventPool.push_back(b.a); p->eventPool.push_back(b.b); }      // (an earlier call's, never asked for)
-        p->stageBrackets.clear(); p->stageSeen.clear();
+        release_stage_brackets(p);          // (an earlier call's, never asked for)
         std::vector<std::string> order;
         for (auto& e : ev) {
-            bool known = false;
-            for (auto& n : order) if (n == e.first) { known = true; break; }
-            if (!known) order.push_back(e.first);
+            if (std::find(order.begin(), order.end(), e.first) == order.end()) order.push_back(e.first);
             p->stageBrackets.push_back({e.first, e.second.first, e.second.second});
         }
         for (auto& n : order) p->stageSeen.push_back({n, seen[n]});
@@ -254,8 +251,7 @@ struct StageClock {
 // Which pass 1 runs is read from the environment at every call: WO_FLOOD=device selects the device formulation; the
 // default is the host heap walk (the reference's own order, and at 10^7 cells still the faster of the two: see
 // DESIGN.md).  The device result is the reference's whenever no decision hinged on two EQUAL keys (the heap orders
-// those by its array mechanics); the decisions that did are counted and, unless WO_FLOOD_TIES=id accepts the cell-id
-// order, pass 1 is redone on the host.
+// those by its array mechanics); the decisions that did are counted and, if there are any, pass 1 is redone on the host.
 // ---------------------------------------------------------------------------------------------------
 struct FloodRun { double deviceMs = 0; int64_t rounds = 0, epochs = 0, evals = 0, ties = 0; bool usedDevice = false, fellBack = false; FloodHostStats host; };
 
@@ -369,24 +365,39 @@ static bool flood_device_pass1(wo_planet* p, FloodRun& R) {
 static const int32_t* morton_if_known(const wo_planet* p) {
     return (!p->h_xyz.empty() && p->mirror.h_morton.size() == (size_t)p->N) ? p->mirror.h_morton.data() : nullptr;
 }
+static const float* host_xyz(const wo_planet* p) { return p->h_xyz.empty() ? nullptr : p->h_xyz.data(); }
+// the flood's tables for the planet's current mask
+static void ensure_flood_static(wo_planet* p) {
+    FloodScratch& S = p->flood;
+    if (!S.staticValid || S.staticN != p->N)
+        flood_build_static(p->N, p->h_off.data(), p->h_adj.data(), host_xyz(p), p->h_ocean.data(), S, morton_if_known(p));
+}
+static void flood_exchange(wo_planet* p, double carveStrength, FloodHostStats* stats) {
+    const int rc = flood_host_passes_exchange(p->N, p->h_off.data(), p->h_adj.data(), host_xyz(p), p->h_pinned, carveStrength, p->flood, stats, p->floodX);
+    if (rc) throw HipError{"flood exchange: the host's exchange function failed (status " + std::to_string(rc) + ")"};
+}
+// WO_FLOOD_TIMING: one stderr line per step of a host-side stage, "[tag] what  ms since the previous line"
+struct HostLap {
+    const char* tag; int width; bool on;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void operator()(const char* what) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "[%s] %-*s %8.1f ms\n", tag, width, what, std::chrono::duration<double, std::milli>(now - t0).count());
+        t0 = now;
+    }
+};
 static void flood_stage(wo_planet* p, double carveStrength, FloodRun& R) {
     hipStream_t s = p->ctx->stream;
     const size_t bytes = (size_t)p->N * sizeof(float);
     const bool timing = p->opt.floodTiming;
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[flood stage] %-12s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t0).count());
-        t0 = now;
-    };
+    HostLap lap{"flood stage", 12, timing};
     if (timing) { WO_HIP(hipStreamSynchronize(s)); lap("drain gpu"); }
     refresh_host_ocean(p);
     lap("ocean mask");
-    FloodScratch& S = p->flood;
-    if (!S.staticValid || S.staticN != p->N)
-        flood_build_static(p->N, p->h_off.data(), p->h_adj.data(), p->h_xyz.empty() ? nullptr : p->h_xyz.data(), p->h_ocean.data(), S, morton_if_known(p));
+    ensure_flood_static(p);
     lap("static");
+    FloodScratch& S = p->flood;
     if (S.L == 0 && !p->floodX.on) return;       // (a share without land still takes part in the exchange)
     const bool hostOnly = p->floodX.on || !p->opt.floodDevice;
     WO_HIP(hipMemcpyAsync(p->h_pinned, p->d_e, bytes, hipMemcpyDeviceToHost, s));
@@ -399,8 +410,7 @@ static void flood_stage(wo_planet* p, double carveStrength, FloodRun& R) {
         flood_pass23_host(p->h_pinned, carveStrength, S);
     } else if (p->floodX.on) {
         if (p->floodX.trueOcean.size() != (size_t)p->N) throw HipError{"flood exchange: the true ocean mask does not fit the planet"};
-        const int rc = flood_host_passes_exchange(p->N, p->h_off.data(), p->h_adj.data(), p->h_xyz.empty() ? nullptr : p->h_xyz.data(), p->h_pinned, carveStrength, S, &R.host, p->floodX);
-        if (rc) throw HipError{"flood exchange: the host's exchange function failed (status " + std::to_string(rc) + ")"};
+        flood_exchange(p, carveStrength, &R.host);
     } else {
         flood_host_passes(p->h_pinned, carveStrength, S, &R.host);
     }
@@ -429,13 +439,7 @@ static void flood_stage_land(wo_planet* p, double carveStrength, FloodRun& R) {
     FloodScratch& S = p->flood;
     const size_t bytes = (size_t)S.L * sizeof(float);
     const bool timing = p->opt.floodTiming;
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[flood stage] %-12s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t0).count());
-        t0 = now;
-    };
+    HostLap lap{"flood stage", 12, timing};
     if (timing) { WO_HIP(hipStreamSynchronize(s)); lap("drain gpu"); }
     // The land heights travel through the planet's own hipHostMalloc'ed buffer (allocated once per planet, N floats).  Round 5 page-locked the flood's
     // own array instead (hipHostRegister of a THP-advised heap block, 0.5 ms of a 312 ms step): user-pointer registrations of transparent-huge-page memory
@@ -487,13 +491,7 @@ static void mirror_build(wo_planet* p, const uint8_t* mask = nullptr) {
     if (M.built && ownMask && M.h_mask.size() == (size_t)N && p->mirrorMaskVersion == p->oceanVersion) return;
     if (M.built && (!mask || (M.h_mask.size() == (size_t)N && std::memcmp(M.h_mask.data(), mask, (size_t)N) == 0))) { if (ownMask) p->mirrorMaskVersion = p->oceanVersion; return; }
     hipStream_t s = p->ctx->stream;
-    auto tLap = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {          // WO_FLOOD_TIMING: what a new terrain's tables cost (bench.py: new_terrain_step_ms)
-        if (!p->opt.floodTiming) return;
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[mirror] %-18s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - tLap).count());
-        tLap = now;
-    };
+    HostLap lap{"mirror", 18, p->opt.floodTiming};          // WO_FLOOD_TIMING: what a new terrain's tables cost (bench.py: new_terrain_step_ms)
     if (M.h_morton.empty()) { morton_order_cells(N, p->h_xyz.data(), M.h_morton); lap("morton order"); }
     M.h_perm.resize(N);
     if (mask) {
@@ -608,419 +606,421 @@ static void ensure_side_stream(wo_planet* p) {
 // the caller restores the field and runs the call again with the check after every pass (erode_composite_checked).
 struct RedoWithChecks {};
 
-static void erode_composite(wo_planet* p, int32_t hIters, double K, double m, double dt, int32_t tIters, double talus,
-                            double kThermal, int32_t gIters, double gStrength, bool checkEveryPass = true) {
-    if (gIters < 0) gIters = 0;
-    if (gStrength != gStrength) gStrength = 0;
-    const int32_t total = std::max(hIters, std::max(tIters, gIters));
-    for (auto& b : p->stageBrackets) { p->eventPool.push_back(b.a); p->eventPool.push_back(b.b); }
-    p->stageBrackets.clear(); p->stageSeen.clear(); p->stagePending = false;
-    p->stageTiming.clear(); p->erodeStats.clear();
-    p->floodX.calls = 0; p->floodX.gathers = 0; p->floodX.globalFloods = 0; p->floodX.received = 0;       // per call (the stats of a step, not of the planet's life)
-    if (total <= 0) return;
-    ensure_scratch(p);
-    hipStream_t s = p->ctx->stream;
-    if (hIters > 0) WO_HIP(hipMemsetAsync(p->d_flowCnt, 0, (size_t)p->N * sizeof(int32_t), s));   // k_flow_final keeps it zero between iterations; a call that was cut short may not have
-    if (hIters > 0 && p->d_ftInflow) { WO_HIP(hipMemsetAsync(p->d_ftInflow, 0, (size_t)p->N * 4, s)); WO_HIP(hipMemsetAsync(p->d_ftExtCnt, 0, (size_t)p->N * 4, s)); }   // (k_flow_tiles<true> keeps them zero)
-    const int32_t N = p->N;
-    const int gridN = xcd_grid(N);
-    StageClock clk(p);
-    int64_t carveFlowLeft = 0, maxSolve = 0, iceRounds = 0, carveRounds = 0, sorts = 0, patchLaunches = 0;
+// One erodeComposite call: its parameters, the constants that follow from them, and what its stages count (wo_last_erode_stats)
+struct ErodeCall {
+    wo_planet* p;
+    int32_t hIters; double K, m, dt; int32_t tIters; double talus, kThermal; int32_t gIters; double gStrength; bool checkEveryPass;
+    int32_t total, midIter; double gCarve, gConv, gDep, gFjord;
+    int gridN, gridL = 0;                   // gridL: index-order passes over the ascending land list (set by erode_setup)
+    StageClock clk; MirrorScope mir; FloodRun floodRun;
+    int64_t sorts = 0, maxSolve = 0, patchLaunches = 0, basinPasses = 0, basinLeftoverPasses = 0, iceRounds = 0, carveRounds = 0, carveActive = 0, carveFlowLeft = 0;
     double floodHostMs = 0;
-
-    clk.begin("setup");
+    ErodeCall(wo_planet* pl, int32_t h, double K_, double m_, double dt_, int32_t t, double talus_, double kT, int32_t g, double gs, bool check)
+        : p(pl), hIters(h), K(K_), m(m_), dt(dt_), tIters(t), talus(talus_), kThermal(kT), gIters(std::max(g, 0)), gStrength(gs != gs ? 0 : gs),
+          checkEveryPass(check), total(std::max(hIters, std::max(tIters, gIters))), midIter((int32_t)std::floor(total * 0.75 + 0.5)),
+          gridN(xcd_grid(pl->N)), clk(pl), mir(pl) {
+        const double gScale = gIters > 0 ? 1.0 / gIters : 0;
+        gCarve = 0.02 * gScale; gConv = 0.01 * gScale; gDep = 0.005 * gScale; gFjord = 0.015 * gScale;
+    }
+    void stats(bool mirrored) const {
+        p->erodeStats = {{"land_cells", (double)p->L}, {"mirror_layout", mirrored ? 1.0 : 0.0}, {"iterations", (double)total}, {"sorts", (double)sorts},
+                         {"solve_launches_max_per_pass", (double)maxSolve}, {"solve_patch_launches_total", (double)patchLaunches},
+                         {"solve_basin_passes", (double)basinPasses}, {"solve_basin_passes_with_leftovers", (double)basinLeftoverPasses},
+                         {"flow_two_level", (p->d_ftLr && p->landIdentity && hIters > 0) ? 1.0 : 0.0}, {"ice_rounds_total", (double)iceRounds},
+                         {"carve_rounds_total", (double)carveRounds}, {"carve_active_total", (double)carveActive}, {"carve_flow_launches_with_leftovers", (double)carveFlowLeft}, {"solve_check_every_pass", checkEveryPass ? 1.0 : 0.0}, {"calls_run_again_with_checks", (double)p->redoCalls}, {"flood_stage_ms", floodHostMs},
+                         {"flood_device_pass1_ms", floodRun.deviceMs}, {"flood_device_rounds", (double)floodRun.rounds}, {"flood_device_epochs", (double)floodRun.epochs},
+                         {"flood_device_evaluations", (double)floodRun.evals}, {"flood_equal_key_decisions", (double)floodRun.ties}, {"flood_pass1_on_host", (floodRun.usedDevice && !floodRun.fellBack) ? 0.0 : 1.0},
+                         {"flood_host_calls", (double)floodRun.host.calls}, {"flood_host_serial_pass1", (double)floodRun.host.serialPass1}, {"flood_host_tie_groups", (double)floodRun.host.tieGroups}, {"flood_host_contested", (double)floodRun.host.contested},
+                         {"flood_host_open_parents", (double)floodRun.host.openParents}, {"flood_host_unresolved", (double)floodRun.host.unresolved},
+                         {"flood_host_path_redo", (double)floodRun.host.pathRedo}, {"flood_host_replays", (double)floodRun.host.replays}, {"flood_host_replayed_landmasses", (double)floodRun.host.replayedLandmasses}, {"flood_host_pass1_ms", floodRun.host.pass1Ms},
+                         {"flood_host_pass23_ms", floodRun.host.pass23Ms},
+                         {"relaxed_sort_every", (double)p->opt.relaxedSortEvery}, {"relaxed_full", p->opt.relaxedFull ? 1.0 : 0.0}, {"flood_exchange_calls", (double)p->floodX.calls}, {"flood_exchange_gathers", (double)p->floodX.gathers}, {"flood_exchange_whole_planet_floods", (double)p->floodX.globalFloods}, {"flood_exchange_received", (double)p->floodX.received}};
+    }
+};
+// The indices i in [0, n) whose cell cell(i) is land, ascending, into out (on the host's workers); returns their number
+template <class Cell>
+static int32_t compact_land(int64_t n, const uint8_t* ocean, Cell cell, int32_t* out) {
+    std::vector<int64_t> cnt(host_threads() + 2, 0);
+    parallel_ranges(n, [&](int64_t b, int64_t e, int t) { int64_t c = 0; for (int64_t i = b; i < e; ++i) c += ocean[cell(i)] ? 0 : 1; cnt[t + 1] = c; });
+    for (size_t t = 1; t < cnt.size(); ++t) cnt[t] += cnt[t - 1];
+    parallel_ranges(n, [&](int64_t b, int64_t e, int t) { int64_t o = cnt[t]; for (int64_t i = b; i < e; ++i) if (!ocean[cell(i)]) out[o++] = (int32_t)i; });
+    return (int32_t)cnt.back();
+}
+// A share without land (landmass decomposition of a small planet) still answers the other shares' flood exchanges; then the call is over
+static void erode_without_land(ErodeCall& c) {
+    wo_planet* p = c.p;
+    if (p->floodX.on) {
+        hipStream_t s = p->ctx->stream;
+        const int calls = (c.hIters > 0 ? 1 : 0) + (c.midIter < c.total ? 1 : 0);
+        WO_HIP(hipMemcpyAsync(p->h_pinned, c.mir.on ? p->mirror.o_e : p->d_e, (size_t)p->N * sizeof(float), hipMemcpyDeviceToHost, s));
+        WO_HIP(hipStreamSynchronize(s));
+        ensure_flood_static(p);
+        for (int k = 0; k < calls; ++k) flood_exchange(p, 0.5, nullptr);
+    }
+    c.mir.finish();
+    c.clk.end(); c.clk.finish();
+}
+// The "setup" stage: the field into the land-first mirror, the land lists, the ranks, the solve's patch order and the ocean cells'
+// constants.  Returns false for a share without land (the call is over then).
+static bool erode_setup(ErodeCall& c) {
+    wo_planet* p = c.p; hipStream_t s = p->ctx->stream;
+    const int32_t N = p->N;
+    c.clk.begin("setup");
     refresh_host_ocean(p);          // the planet's own mask, before the pointers move
-    MirrorScope mir(p);
-    mir.enter(p->h_ocean.data());          // land first (mirror_build)
-    p->landIdentity = mir.on && p->mirror.h_mask.size() == (size_t)N;      // land cells are the ids 0 .. L-1: the index-order passes skip the land list
+    c.mir.enter(p->h_ocean.data());          // land first (mirror_build)
+    p->landIdentity = c.mir.on && p->mirror.h_mask.size() == (size_t)N;      // land cells are the ids 0 .. L-1: the index-order passes skip the land list
     coast_flags(p);
     // landCells in ascending r (js/terrain-post.js:384-390): host-side compaction of the ocean mask
-    {
-        int32_t* hl = reinterpret_cast<int32_t*>(p->h_pinned);
-        int32_t L = 0;
-        // both lists only depend on the mask (and on whether the call runs on the mirror): a call with the mask of the previous one takes them as they are
-        const bool listsKept = p->d_landInit && p->landListsOcean == p->oceanVersion && p->landListsMirror == mir.on && p->landListsL >= 0;
-        if (listsKept) L = p->landListsL;
-        else {
-            const uint8_t* oc = p->h_ocean.data();
-            std::vector<int64_t> cnt(host_threads() + 2, 0);
-            parallel_ranges(N, [&](int64_t b, int64_t e, int t) { int64_t c = 0; for (int64_t r = b; r < e; ++r) c += oc[r] ? 0 : 1; cnt[t + 1] = c; });
-            for (size_t t = 1; t < cnt.size(); ++t) cnt[t] += cnt[t - 1];
-            parallel_ranges(N, [&](int64_t b, int64_t e, int t) { int64_t o = cnt[t]; for (int64_t r = b; r < e; ++r) if (!oc[r]) hl[o++] = (int32_t)r; });
-            L = (int32_t)cnt.back();
-        }
-        p->L = L;
-        if (L == 0) {
-            // a share without land (landmass decomposition of a small planet) still answers the other shares' flood exchanges
-            if (p->floodX.on) {
-                const int32_t midIter0 = (int32_t)std::floor(total * 0.75 + 0.5);
-                const int calls = (hIters > 0 ? 1 : 0) + (midIter0 < total ? 1 : 0);
-                WO_HIP(hipMemcpyAsync(p->h_pinned, mir.on ? p->mirror.o_e : p->d_e, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, s));
-                WO_HIP(hipStreamSynchronize(s));
-                if (!p->flood.staticValid || p->flood.staticN != N)
-                    flood_build_static(N, p->h_off.data(), p->h_adj.data(), p->h_xyz.empty() ? nullptr : p->h_xyz.data(), p->h_ocean.data(), p->flood, morton_if_known(p));
-                for (int k = 0; k < calls; ++k) {
-                    const int rc = flood_host_passes_exchange(N, p->h_off.data(), p->h_adj.data(), p->h_xyz.empty() ? nullptr : p->h_xyz.data(), p->h_pinned, 0.5, p->flood, nullptr, p->floodX);
-                    if (rc) throw HipError{"flood exchange: the host's exchange function failed (status " + std::to_string(rc) + ")"};
-                }
-            }
-            mir.finish();
-            clk.end(); clk.finish(); return;
-        }
-        if (listsKept) {
-            WO_HIP(hipMemcpyAsync(p->d_land[0], p->d_landInit, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        } else if (mir.on) {
-            // initial landCells: the same cells in the same (ascending-r) order, under their mirror names
-            WO_HIP(hipMemcpyAsync(p->d_listA, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            launch(p, FAM_MISC, k_mirror_map_i32, blocks_for(L, 4096), WO_BLOCK, (const int32_t*)p->d_listA, (const int32_t*)p->mirror.inv, p->d_land[0], L);
-            WO_HIP(hipStreamSynchronize(s));
-            // the list the index-order passes iterate: land cells in ascending mirror id
-            const int32_t* perm = p->mirror.h_perm.data();
-            const uint8_t* oc = p->h_ocean.data();
-            std::vector<int64_t> cnt(host_threads() + 2, 0);
-            parallel_ranges(N, [&](int64_t b, int64_t e, int t) { int64_t c = 0; for (int64_t i = b; i < e; ++i) c += oc[perm[i]] ? 0 : 1; cnt[t + 1] = c; });
-            for (size_t t = 1; t < cnt.size(); ++t) cnt[t] += cnt[t - 1];
-            parallel_ranges(N, [&](int64_t b, int64_t e, int t) { int64_t o = cnt[t]; for (int64_t i = b; i < e; ++i) if (!oc[perm[i]]) hl[o++] = (int32_t)i; });
-            WO_HIP(hipMemcpyAsync(p->d_landIdx, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        } else {
-            WO_HIP(hipMemcpyAsync(p->d_landIdx, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            WO_HIP(hipMemcpyAsync(p->d_land[0], p->d_landIdx, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        }
-        if (!listsKept) {
-            if (!p->d_landInit) p->d_landInit = dalloc<int32_t>((size_t)N);
-            WO_HIP(hipMemcpyAsync(p->d_landInit, p->d_land[0], (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-            p->landListsOcean = p->oceanVersion; p->landListsMirror = mir.on; p->landListsL = L;
-        }
-        WO_HIP(hipStreamSynchronize(s));       // h_pinned is reused by the flood stage
-        p->landCur = 0;
-        launch(p, FAM_MISC, k_init_rank, gridN, WO_BLOCK, p->d_rank, N);
-        rank_from_land(p);      // thermal-only runs never sort: landCells stays in ascending-r order
-        // spatial patches for the patch-local solve: land cells in Morton order (shared with the host flood's layout)
-        if (hIters > 0) {
-            if (!p->flood.staticValid || p->flood.staticN != N)
-                flood_build_static(N, p->h_off.data(), p->h_adj.data(), p->h_xyz.data(), p->h_ocean.data(), p->flood, morton_if_known(p));
-            if (p->patchVersion != p->flood.staticVersion || p->patchMirror != mir.on) {
-                p->patchMirror = mir.on;
-                if (mir.on) WO_HIP(hipMemcpyAsync(p->d_patchOrder, p->d_landIdx, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));   // ascending mirror id IS Morton order
-                else WO_HIP(hipMemcpyAsync(p->d_patchOrder, p->flood.landCell.data(), (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                launch(p, FAM_MISC, k_fill_i32, gridN, WO_BLOCK, p->d_slotOf, -1, N);
-                launch(p, FAM_MISC, k_slot_scatter, blocks_for(L, 4096), WO_BLOCK, (const int32_t*)p->d_patchOrder, p->d_slotOf, L);
-                WO_HIP(hipStreamSynchronize(s));
-                p->patchVersion = p->flood.staticVersion;
-                p->lastPatchLaunches = 1;
-                p->numPatches = (L + WO_PATCH - 1) / WO_PATCH;
-            }
-        } else {
-            p->patchVersion = -1;
-        }
+    int32_t* hl = reinterpret_cast<int32_t*>(p->h_pinned);
+    const uint8_t* oc = p->h_ocean.data();
+    // both lists only depend on the mask (and on whether the call runs on the mirror): a call with the mask of the previous one takes them as they are
+    const bool listsKept = p->d_landInit && p->landListsOcean == p->oceanVersion && p->landListsMirror == c.mir.on && p->landListsL >= 0;
+    const int32_t L = listsKept ? p->landListsL : compact_land(N, oc, [](int64_t r) { return r; }, hl);
+    p->L = L;
+    if (L == 0) { erode_without_land(c); return false; }
+    if (listsKept) {
+        WO_HIP(hipMemcpyAsync(p->d_land[0], p->d_landInit, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    } else if (c.mir.on) {
+        // initial landCells: the same cells in the same (ascending-r) order, under their mirror names
+        WO_HIP(hipMemcpyAsync(p->d_listA, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        launch(p, FAM_MISC, k_mirror_map_i32, blocks_for(L, 4096), WO_BLOCK, (const int32_t*)p->d_listA, (const int32_t*)p->mirror.inv, p->d_land[0], L);
+        WO_HIP(hipStreamSynchronize(s));
+        // the list the index-order passes iterate: land cells in ascending mirror id
+        const int32_t* perm = p->mirror.h_perm.data();
+        compact_land(N, oc, [perm](int64_t i) { return perm[i]; }, hl);
+        WO_HIP(hipMemcpyAsync(p->d_landIdx, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    } else {
+        WO_HIP(hipMemcpyAsync(p->d_landIdx, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        WO_HIP(hipMemcpyAsync(p->d_land[0], p->d_landIdx, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     }
-    const int32_t L = p->L;
-    const int gridL = xcd_grid(L);              // index-order passes over the ascending land list
-    if (hIters > 0 || tIters > 0) {
+    if (!listsKept) {
+        if (!p->d_landInit) p->d_landInit = dalloc<int32_t>((size_t)N);
+        WO_HIP(hipMemcpyAsync(p->d_landInit, p->d_land[0], (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        p->landListsOcean = p->oceanVersion; p->landListsMirror = c.mir.on; p->landListsL = L;
+    }
+    WO_HIP(hipStreamSynchronize(s));       // h_pinned is reused by the flood stage
+    p->landCur = 0;
+    launch(p, FAM_MISC, k_init_rank, c.gridN, WO_BLOCK, p->d_rank, N);
+    rank_from_land(p);      // thermal-only runs never sort: landCells stays in ascending-r order
+    // spatial patches for the patch-local solve: land cells in Morton order (shared with the host flood's layout)
+    if (c.hIters > 0) {
+        ensure_flood_static(p);
+        if (p->patchVersion != p->flood.staticVersion || p->patchMirror != c.mir.on) {
+            p->patchMirror = c.mir.on;
+            if (c.mir.on) WO_HIP(hipMemcpyAsync(p->d_patchOrder, p->d_landIdx, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));   // ascending mirror id IS Morton order
+            else WO_HIP(hipMemcpyAsync(p->d_patchOrder, p->flood.landCell.data(), (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            launch(p, FAM_MISC, k_fill_i32, c.gridN, WO_BLOCK, p->d_slotOf, -1, N);
+            launch(p, FAM_MISC, k_slot_scatter, blocks_for(L, 4096), WO_BLOCK, (const int32_t*)p->d_patchOrder, p->d_slotOf, L);
+            WO_HIP(hipStreamSynchronize(s));
+            p->patchVersion = p->flood.staticVersion;
+            p->lastPatchLaunches = 1;
+            p->numPatches = (L + WO_PATCH - 1) / WO_PATCH;
+        }
+    } else p->patchVersion = -1;
+    c.gridL = xcd_grid(L);
+    if (c.hIters > 0 || c.tIters > 0) {
         // ocean cells keep these values through the whole call: both elevation buffers hold them, and the per-ocean-cell
         // constants of the land passes are written once
         WO_HIP(hipMemcpyAsync(p->d_e2, p->d_e, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));
         launch(p, FAM_MISC, k_erode_ocean_init, blocks_for(N, 4096), WO_BLOCK, p->fields());
     }
-    clk.end();
-
-    FloodRun floodRun;
-    auto leftovers_so_far = [&]() {
-        if (checkEveryPass || !p->d_pendingEver) return;
-        if (read_count(p, p->d_pendingEver) != 0) {
-            if (p->opt.floodTiming) {          // (diagnostic runs only) which of the two reasons: a splitter-sort bucket that did not fit, or a basin launch with leftovers
-                int32_t h[8] = {0};
-                WO_HIP(hipMemcpy(h, p->d_pendingEver, sizeof(h), hipMemcpyDeviceToHost));
-                std::fprintf(stderr, "[erode] call runs again with checks: %d basin-solve tasks were left pending\n", h[0]);
-            }
-            throw RedoWithChecks{};
+    c.clk.end();
+    return true;
+}
+// The host is about to read the field: an unchecked basin launch of this call that left tasks pending sends the call back to run again with checks
+static void leftovers_so_far(ErodeCall& c) {
+    wo_planet* p = c.p;
+    if (c.checkEveryPass || !p->d_pendingEver || read_count(p, p->d_pendingEver) == 0) return;
+    if (p->opt.floodTiming) {          // (diagnostic runs only) which of the two reasons: a splitter-sort bucket that did not fit, or a basin launch with leftovers
+        int32_t h[8] = {0};
+        WO_HIP(hipMemcpy(h, p->d_pendingEver, sizeof(h), hipMemcpyDeviceToHost));
+        std::fprintf(stderr, "[erode] call runs again with checks: %d basin-solve tasks were left pending\n", h[0]);
+    }
+    throw RedoWithChecks{};
+}
+static void erode_flood(ErodeCall& c, double carveStrength) {
+    wo_planet* p = c.p;
+    leftovers_so_far(c);
+    c.clk.begin("priority_flood");
+    const auto t0 = std::chrono::steady_clock::now();
+    // inside the land-first mirror, with the mask and the flood's tables in place: the land heights straight from the mirrored field
+    const bool landOnly = c.mir.on && p->landIdentity && !p->floodX.on && !p->opt.floodDevice && p->h_ocean_valid && p->flood.staticValid &&
+                          p->flood.staticN == p->N && p->flood.L > 0 && flood_land_is_mirror_prefix(p);
+    if (landOnly) flood_stage_land(p, carveStrength, c.floodRun);
+    else { c.mir.suspend(); flood_stage(p, carveStrength, c.floodRun); c.mir.resume(); }
+    c.floodHostMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c.clk.end();
+}
+static void erode_sort(ErodeCall& c) { c.clk.begin("sort"); sort_land_by_elevation(c.p); ++c.sorts; c.clk.end(); }
+// ice accumulation: the receivers, then one launch in which the last donor to arrive runs its receiver's task (k_ice_climb)
+static void ice_flow(ErodeCall& c, const Fields& F) {
+    launch(c.p, FAM_ICE_RECV, k_ice_receivers, c.gridN, WO_BLOCK, F);
+    launch(c.p, FAM_ICE_ROUND, k_ice_climb, c.gridL, WO_BLOCK, F, F.blocker); ++c.iceRounds;
+}
+// RELAXED glacial step: the carve from a snapshot of the heights, one sweep
+static void glacial_step_relaxed(ErodeCall& c) {
+    wo_planet* p = c.p;
+    c.clk.begin("glacial");
+    const Fields F = p->fields();
+    ice_flow(c, F);
+    launch(p, FAM_CARVE_ROUND, k_carve_jacobi, c.gridL, WO_BLOCK, F, (const float*)p->d_e, p->d_e2, c.gCarve, c.gConv, c.gStrength);
+    swap_elev(p);
+    launch(p, FAM_MORAINE, k_moraine_fjord, c.gridN, WO_BLOCK, p->fields(), c.gDep, c.gFjord);
+    c.clk.end();
+}
+// the carve's per-task buffers, for at least `active` tasks
+static void ensure_carve_capacity(wo_planet* p, int32_t active) {
+    if ((int64_t)active <= p->carveCap) return;
+    dfree(p->d_carveDeps); dfree(p->d_carveDepCnt); dfree(p->d_carveDepPos); dfree(p->d_carveRecs); dfree(p->d_carveSlotDone); dfree(p->d_carveExpect);
+    p->carveCap = (int64_t)active + active / 4 + 1024;
+    p->d_carveDeps = dalloc<int32_t>((size_t)p->carveCap * WO_CARVE_DEPS);
+    p->d_carveDepCnt = dalloc<int32_t>((size_t)p->carveCap); p->d_carveDepPos = dalloc<int32_t>((size_t)p->carveCap);
+    p->d_carveRecs = dalloc<CarveRec>((size_t)p->carveCap); p->d_carveSlotDone = dalloc<int32_t>((size_t)p->carveCap); p->d_carveExpect = dalloc<CarveExpect>((size_t)p->carveCap);
+}
+// k_carve_granules' grid, every task in one launch: what is certainly resident at once, the occupancy query's blocks per CU less one
+// (the query is known to answer one too many near register-file edges).  Asked once per process.
+static int carve_granule_blocks() {
+    static int blocks = 0;
+    if (!blocks) {
+        int perCu = 0, dev = 0; hipDeviceProp_t prop;
+        WO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_carve_granules, WO_BLOCK, 0));
+        WO_HIP(hipGetDevice(&dev)); WO_HIP(hipGetDeviceProperties(&prop, dev));
+        blocks = std::max(1, std::min(perCu, 8) - 1) * prop.multiProcessorCount;
+    }
+    return blocks;
+}
+// The carve of the active tasks (> 0): the one launch (k_carve_granules), then — for whatever it leaves — rounds over the static activation list
+// (k_carve_round_static): every launch covers all active tasks, a finished one leaves after one load, an open one issues its loads at once; the
+// number of finished tasks is read back after a burst.  Returns the number of carve launches.  (Round 2 also tried all rounds in ONE cooperative
+// launch with a grid barrier: slower, profiles/r02f_*; the done-word form of the one launch, k_carve_flow, and the rounds-only route were removed in round 6.)
+static int64_t carve_launches(ErodeCall& c, const Fields& F, int32_t active) {
+    wo_planet* p = c.p;
+    const int32_t* const count = p->d_counters + 3; int32_t* const done = p->d_counters + 4;
+    // (the dependency lists — a two-hop walk per task — are for the rounds: the granule launch waits on the heights themselves and the lists are only
+    // made if it leaves tasks to the rounds)
+    launch(p, FAM_CARVE_SETUP, k_carve_records, blocks_for(active), WO_BLOCK, F, (const int32_t*)p->d_listB, count, p->d_carveRecs, p->d_carveSlotDone, c.gCarve, c.gConv, c.gStrength,
+           (int32_t)0, (int32_t)1);
+    WO_HIP(hipMemsetAsync(done, 0, sizeof(int32_t), p->ctx->stream));
+    const int grid = blocks_for(active);
+    // hook carve_blocks=<n>: at most n workgroups, so that every thread takes many tasks in turn
+    const int blocksNow = p->opt.carveBlocks > 0 ? std::max(1, std::min(carve_granule_blocks(), p->opt.carveBlocks)) : carve_granule_blocks();
+    const long long flowBudget = p->opt.carveBudgetMs * 100000ll;   // 100 MHz ticks
+    if (!p->d_carveG) p->d_carveG = dalloc<unsigned long long>((size_t)p->N);
+    launch(p, FAM_CARVE_SETUP, k_carve_expect, grid, WO_BLOCK, F, (const CarveRec*)p->d_carveRecs, count, p->d_carveExpect);
+    launch(p, FAM_CARVE_SETUP, k_carve_pack, blocks_for(p->N, 4096), WO_BLOCK, (const float*)F.e, p->d_carveG, p->N);
+    launch(p, FAM_CARVE_ROUND, k_carve_granules, std::min(grid, blocksNow), WO_BLOCK, F, (const CarveRec*)p->d_carveRecs, (const CarveExpect*)p->d_carveExpect, p->d_carveG,
+           p->d_carveSlotDone, count, done, flowBudget);
+    launch(p, FAM_CARVE_SETUP, k_carve_unpack, blocks_for(p->N, 4096), WO_BLOCK, (const unsigned long long*)p->d_carveG, F.e, p->N);
+    int64_t k = 2;          // the number of the next launch
+    if (read_count(p, done) >= active) return k - 1;
+    // the rounds want the dependency lists after all
+    ++c.carveFlowLeft;
+    launch(p, FAM_CARVE_SETUP, k_carve_deps, grid, WO_BLOCK, F, (const int32_t*)p->d_listB, count, p->d_carveSlot);
+    launch(p, FAM_CARVE_SETUP, k_carve_records, grid, WO_BLOCK, F, (const int32_t*)p->d_listB, count, p->d_carveRecs, p->d_carveSlotDone, c.gCarve, c.gConv, c.gStrength, (int32_t)1, (int32_t)0);
+    // the depth of the carve DAG falls from one glacial iteration to the next (the ice smooths its bed), so the count of
+    // finished tasks is read back every 32 rounds (a read-back costs about as much as three empty rounds)
+    constexpr int burst = 32;
+    for (;;) {
+        for (int b = 0; b < burst; ++b, ++k)
+            launch(p, FAM_CARVE_ROUND, k_carve_round_static, grid, WO_BLOCK, F, (const CarveRec*)p->d_carveRecs, p->d_carveSlotDone, count, (int32_t)k, c.gCarve, c.gConv, c.gStrength, done);
+        if (read_count(p, done) >= active) return k - 1;
+        if (k > 4 * (int64_t)p->N + 1024) throw HipError{"carve rounds do not converge"};
+    }
+}
+// Exact glacial step: ice accumulation, the active carve tasks in landCells order, their carve, moraines and fjords
+static void glacial_step_exact(ErodeCall& c) {
+    wo_planet* p = c.p;
+    c.clk.begin("glacial");
+    Fields F = p->fields();
+    ice_flow(c, F);
+    launch(p, FAM_CARVE_SETUP, k_carve_setup_cells, c.gridN, WO_BLOCK, F);
+    select_active_by_rank(p, F.arank, p->d_listB, p->d_counters + 3);     // the active tasks in landCells order
+    const int32_t active = read_count(p, p->d_counters + 3);
+    c.carveActive += active; ensure_carve_capacity(p, active);
+    F.carveDeps = p->d_carveDeps; F.carveDepCnt = p->d_carveDepCnt; F.carveDepPos = p->d_carveDepPos;
+    if (active > 0) c.carveRounds += carve_launches(c, F, active);
+    launch(p, FAM_MORAINE, k_moraine_fjord, c.gridN, WO_BLOCK, F, c.gDep, c.gFjord);
+    c.clk.end();
+}
+// The two-level flow accumulation's buffers (k_flow_tiles)
+static FlowTiles flow_tiles_buffers(wo_planet* p) {
+    const size_t N = (size_t)p->N;
+    if (!p->d_ftLr) {
+        p->d_ftLr = dalloc<int32_t>(N); p->d_ftParent = dalloc<int32_t>(N); p->d_ftExtCnt = dalloc<int32_t>(N); p->d_ftInflow = dalloc<uint32_t>(N); p->d_ftRootAcc = dalloc<unsigned long long>(N);
+        WO_HIP(hipMemsetAsync(p->d_ftInflow, 0, N * 4, p->ctx->stream)); WO_HIP(hipMemsetAsync(p->d_ftExtCnt, 0, N * 4, p->ctx->stream));
+    }
+    FlowTiles FT{};
+    FT.lr = p->d_ftLr; FT.parent = p->d_ftParent; FT.rootAcc = p->d_ftRootAcc; FT.inflow = p->d_ftInflow; FT.extCnt = p->d_ftExtCnt;
+    return FT;
+}
+static int flow_tile_count(int32_t L) { return (int)(((int64_t)L + FT_CELLS - 1) / FT_CELLS); }
+// The receivers pass (+ the flow's start state and donor counts, + the start state of the basin layout's search), then the layout's fork
+static void erode_receivers(ErodeCall& c, const Fields& F, const FlowTiles& FT, int32_t* donorCnt, bool basin, bool slotIdentity, bool tilesBeforeFork) {
+    wo_planet* p = c.p; hipStream_t s = p->ctx->stream;
+    Fields Fr = F; if (basin) Fr.basinJ = p->d_basinJ;          // (the layout's start state)
+    c.clk.begin("receivers");
+    launch(p, FAM_RECEIVERS, k_receivers_flow_init, c.gridL, WO_BLOCK, Fr, donorCnt);
+    c.clk.end();
+    if (!basin) return;
+    // basin-local solve (basin.hip): this pass's store order groups every drainage component with everything it depends on.
+    // The layout needs the receivers only and touches none of the flow accumulation's arrays: it runs on the planet's side stream
+    // beside the flow accumulation and the solve's setup waits for both.  (A third stream for the solve's event lists was measured in
+    // round 3 and a side stream for the elevation sort in round 6 — profiles/r03bc_*, r06d_*: no faster, a launch of these sizes already
+    // occupies the chip's workgroup slots and two side by side take turns; both removed.)
+    ensure_side_stream(p);
+    if (tilesBeforeFork) {
+        // (the root links too before the fork: beside the layout's first kernel — high-priority stream — they took 33 us instead of 15; flow stage 45.9 -> 43.8 ms per step, profiles/r05h_*)
+        launch(p, FAM_FLOW_TILES, k_flow_tiles<false>, flow_tile_count(p->L), FT_THREADS, F, FT);
+        launch(p, FAM_FLOW_TILES, k_flow_root_links, blocks_for(p->L, 4096), WO_BLOCK, F, FT);
+    }
+    WO_HIP(hipEventRecord(p->evFork, s));
+    WO_HIP(hipStreamWaitEvent(p->side, p->evFork, 0));
+    p->onSide = true;
+    try { basin_layout(p, slotIdentity); } catch (...) { p->onSide = false; throw; }
+    p->onSide = false;
+    WO_HIP(hipEventRecord(p->evJoin, p->side));
+}
+// Flow accumulation = subtree sizes of the forward forest (integers: any order of the additions is exact): in two levels under the mirror
+// (kernels_impl.h: k_flow_tiles), else one launch in which every leaf hands its total to its receiver and the thread that completes a
+// receiver carries on with it (k_flow_climb).  Every cell with a forward receiver is retired either way; k_flow_final reads the packed totals.
+// (10 M cells, flow stage per step: round 2's rake rounds + pointer doubling 108 ms, the climb 45, two levels 29: profiles/r02r_*, r05g_*.)
+static void erode_flow(ErodeCall& c, const Fields& F, const FlowTiles& FT, int32_t* donorCnt, bool flowTiles, bool tilesBeforeFork, bool clearOut) {
+    wo_planet* p = c.p;
+    c.clk.begin("flow");
+    if (flowTiles) {
+        const int tiles = flow_tile_count(p->L);
+        if (!tilesBeforeFork) {
+            launch(p, FAM_FLOW_TILES, k_flow_tiles<false>, tiles, FT_THREADS, F, FT);
+            launch(p, FAM_FLOW_TILES, k_flow_root_links, blocks_for(p->L, 4096), WO_BLOCK, F, FT);
         }
-    };
-    auto flood = [&](double cs) {
-        leftovers_so_far();                    // the host is about to read the field
-        clk.begin("priority_flood");
-        auto t0 = std::chrono::steady_clock::now();
-        // inside the land-first mirror, with the mask and the flood's tables in place: the land heights straight from the mirrored field
-        const bool landOnly = mir.on && p->landIdentity && !p->floodX.on && !p->opt.floodDevice && p->h_ocean_valid && p->flood.staticValid &&
-                              p->flood.staticN == p->N && p->flood.L > 0 && flood_land_is_mirror_prefix(p);
-        if (landOnly) flood_stage_land(p, cs, floodRun);
-        else {
-            mir.suspend();
-            flood_stage(p, cs, floodRun);
-            mir.resume();
-        }
-        floodHostMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        clk.end();
-    };
-    if (hIters > 0) flood(0.5);
+        launch(p, FAM_FLOW_TILES, k_flow_root_climb, blocks_for(p->L, 4096), WO_BLOCK, F, FT);
+        launch(p, FAM_FLOW_TILES, k_flow_tiles<true>, tiles, FT_THREADS, F, FT);
+    } else
+        launch(p, FAM_FLOW_SNAP, k_flow_climb, c.gridL, WO_BLOCK, F, (const int32_t*)p->d_flowCnt, (int32_t)0x7fffffff);
+    Fields Ff = F;
+    if (p->opt.relaxedFull) Ff.ev = nullptr;                // (no event lists: the relaxed solve has no order)
+    // the solve's outputs are cleared (tags 0) only for a pass whose result is checked on the spot (k_solve_patch / k_solve_final read
+    // the tags as launch numbers); the unchecked pass stamps them with a tag of its own instead (erode_solve_basin): 16 B per land cell less to write
+    launch(p, FAM_FLOW_FINAL, k_flow_final, c.gridL, WO_BLOCK, Ff, donorCnt, clearOut ? p->d_out : (SolveOut*)nullptr);
+    c.clk.end();
+}
+// Exact mode: the basin-local solve, once the layout on the side stream has joined
+static void erode_solve_basin(ErodeCall& c, Fields F, int32_t iter) {
+    wo_planet* p = c.p; hipStream_t s = p->ctx->stream;
+    WO_HIP(hipStreamWaitEvent(s, p->evJoin, 0));
+    F.slotOf = p->d_basinSlot; F.solveLean = 1;
+    // (the outputs' tags were cleared by k_flow_final: one coalesced sweep instead of one scattered 16-byte write per task)
+    // an unchecked pass: the solve launch writes the final heights itself (SolveTask finality flags) and no k_solve_final then
+    const bool unchecked = !c.checkEveryPass; F.solveFinals = unchecked ? 1 : 0;
+    // (the setup launch also clears the counters and pending totals of the solve launches: run_solve_patches)
+    launch(p, FAM_SOLVE_SETUP, k_solve_setup_batched<true>, c.gridL, WO_BLOCK, F, p->d_patchPending, (int32_t)p->numPatches, p->d_patchTotals, (int32_t)WO_PATCH_TOTAL_SLOTS);
+    // the unchecked pass's one launch tags what it produces with a number no earlier pass of this planet used
+    int32_t passTag = 1;
+    if (unchecked) {
+        if (p->solvePassSerial >= 0x3ff00000) { WO_HIP(hipMemsetAsync(p->d_out, 0, (size_t)p->N * sizeof(SolveOut), s)); p->solvePassSerial = 0; }
+        passTag = (1 << 20) + (int32_t)(++p->solvePassSerial);
+    }
+    const int64_t r = run_solve_patches(p, F, c.K, c.m, c.dt, unchecked, passTag);
+    ++c.basinPasses; if (r > 1) ++c.basinLeftoverPasses;
+    c.patchLaunches += r; c.maxSolve = std::max(c.maxSolve, r);
+    if (!unchecked) launch(p, FAM_SOLVE_FINAL, k_solve_final, c.gridL, WO_BLOCK, F, p->d_e2, (iter < c.tIters) ? p->d_me : (float*)nullptr);
+}
+// RELAXED: h' = a + b h'(receiver) composed by pointer jumping (12 doublings cover chains of 4 096 cells), then heights + deposits in one sweep
+static void erode_solve_affine(ErodeCall& c, const Fields& F) {
+    wo_planet* p = c.p;
+    if (!p->d_affine[0]) { p->d_affine[0] = dalloc<Affine>((size_t)p->N); p->d_affine[1] = dalloc<Affine>((size_t)p->N); }
+    launch(p, FAM_SOLVE_SETUP, k_affine_init, c.gridL, WO_BLOCK, F, p->d_affine[0]);
+    int cur = 0;
+    for (int q = 0; q < 12; ++q, cur ^= 1) launch(p, FAM_SOLVE_ROUND, k_affine_jump, c.gridL, WO_BLOCK, F, (const Affine*)p->d_affine[cur], p->d_affine[cur ^ 1]);
+    launch(p, FAM_SOLVE_FINAL, k_affine_apply, c.gridL, WO_BLOCK, F, (const Affine*)p->d_affine[cur], p->d_e2);
+}
+// The hydraulic step: receivers, flow accumulation, the implicit solve (exact: basin-local, basin.hip; relaxed: the affine recurrence)
+static void hydraulic_step(ErodeCall& c, int32_t iter) {
+    wo_planet* p = c.p;
+    Fields F = p->fields();
+    F.solveK = c.K; F.solveM = c.m; F.solveDt = c.dt;
+    const bool basin = !p->opt.relaxedFull;
+    const bool slotIdentity = c.mir.on && p->mirror.h_mask.size() == (size_t)p->N;          // land-first mirror: a land cell's Morton slot is its id
+    if (basin) { basin_alloc(p); F.basinMslot = slotIdentity ? nullptr : p->d_slotOf; }
+    // two-level accumulation (k_flow_tiles): needs the land cells to be the ids 0 .. L-1 in Morton order (land-first mirror); on the planet's
+    // own cell order (WO_LAYOUT=index) the one-launch climb over all cells (k_flow_climb)
+    const bool flowTiles = p->landIdentity;
+    FlowTiles FT = flowTiles ? flow_tiles_buffers(p) : FlowTiles{};
+    // the two-level accumulation's first kernel also shortens the layout's start state inside every tile (k_flow_tiles<false>: J[c] <- an
+    // ancestor at most a tile away), so it runs before the fork and the layout's component search starts from chains of tiles instead of cells
+    const bool tilesBeforeFork = basin && flowTiles && slotIdentity;
+    if (tilesBeforeFork) FT.basinJ = p->d_basinJ;
+    int32_t* const donorCnt = flowTiles ? (int32_t*)nullptr : p->d_flowCnt;
+    erode_receivers(c, F, FT, donorCnt, basin, slotIdentity, tilesBeforeFork);
+    erode_flow(c, F, FT, donorCnt, flowTiles, tilesBeforeFork, basin && c.checkEveryPass);
+    c.clk.begin("solve");
+    if (basin) erode_solve_basin(c, F, iter); else erode_solve_affine(c, F);
+    swap_elev(p);
+    c.clk.end();
+}
+static void thermal_step(ErodeCall& c, bool afterSolve) {
+    wo_planet* p = c.p;
+    c.clk.begin("thermal");
+    const Fields F = p->fields();
+    if (!afterSolve) launch(p, FAM_THERMAL_EXCESS, k_masked_elev, c.gridL, WO_BLOCK, F);      // else written by the solve
+    launch(p, FAM_THERMAL_EXCESS, k_thermal_excess, c.gridL, WO_BLOCK, F, c.talus);
+    if (p->maxDeg <= 12) launch(p, FAM_THERMAL_APPLY, k_thermal_apply_reg<12>, c.gridL, WO_BLOCK, F, p->d_e2, c.talus, c.kThermal);
+    else if (p->maxDeg <= 16) launch(p, FAM_THERMAL_APPLY, k_thermal_apply_reg<16>, c.gridL, WO_BLOCK, F, p->d_e2, c.talus, c.kThermal);
+    else launch_shmem(p, FAM_THERMAL_APPLY, k_thermal_apply, c.gridL, WO_BLOCK, (size_t)p->maxDeg * WO_BLOCK * 12, F, p->d_e2, c.talus, c.kThermal, (int32_t)p->maxDeg);
+    swap_elev(p);
+    c.clk.end();
+}
 
-    const bool glacial = gIters > 0 && gStrength > 0;
-    if (glacial) launch(p, FAM_GLAC_INDEX, k_glac_index, gridN, WO_BLOCK, p->fields(), gStrength);
-    const double gScale = gIters > 0 ? 1.0 / gIters : 0;
-    const double gCarve = 0.02 * gScale, gConv = 0.01 * gScale, gDep = 0.005 * gScale, gFjord = 0.015 * gScale;
-    const int32_t midIter = (int32_t)std::floor(total * 0.75 + 0.5);
-    bool midDone = false;
+static void erode_composite(wo_planet* p, int32_t hIters, double K, double m, double dt, int32_t tIters, double talus,
+                            double kThermal, int32_t gIters, double gStrength, bool checkEveryPass = true) {
+    ErodeCall c(p, hIters, K, m, dt, tIters, talus, kThermal, gIters, gStrength, checkEveryPass);
+    release_stage_brackets(p);
+    p->stageTiming.clear(); p->erodeStats.clear();
+    p->floodX.calls = 0; p->floodX.gathers = 0; p->floodX.globalFloods = 0; p->floodX.received = 0;       // per call (the stats of a step, not of the planet's life)
+    if (c.total <= 0) return;
+    ensure_scratch(p);
+    hipStream_t s = p->ctx->stream;
+    if (hIters > 0) WO_HIP(hipMemsetAsync(p->d_flowCnt, 0, (size_t)p->N * sizeof(int32_t), s));   // k_flow_final keeps it zero between iterations; a call that was cut short may not have
+    if (hIters > 0 && p->d_ftInflow) { WO_HIP(hipMemsetAsync(p->d_ftInflow, 0, (size_t)p->N * 4, s)); WO_HIP(hipMemsetAsync(p->d_ftExtCnt, 0, (size_t)p->N * 4, s)); }   // (k_flow_tiles<true> keeps them zero)
+    if (!erode_setup(c)) return;
+    if (hIters > 0) erode_flood(c, 0.5);
+
+    const bool glacial = c.gIters > 0 && c.gStrength > 0;
+    if (glacial) launch(p, FAM_GLAC_INDEX, k_glac_index, c.gridN, WO_BLOCK, p->fields(), c.gStrength);
     // (round 2's river-aligned patch lists, WO_RIVER_PATCHES, were measured and dropped: profiles/r02c_river_patch_experiment.txt)
-    int64_t basinPasses = 0, basinLeftoverPasses = 0, carveActive = 0;
-
-    const bool stageAll = p->opt.stageTimingAll;
     // (one composite iteration as a hipGraph — captured once per call, replayed 167 times — was built and measured in round 4: 499.5 ms per step against 384.1 with
     // plain launches, profiles/r04j_*: a graph launch costs more than the ~25 stream launches it replaces; removed in round 6)
-    bool sortAfterFlood = false;
-    for (int32_t iter = 0; iter < total; ++iter) {
-        clk.on = true;
-        if (!midDone && iter >= midIter) { midDone = true; flood(0.85); sortAfterFlood = true; }
-        clk.on = stageAll || p->profiling || total <= 16 || iter % 8 == 0;
-        const bool gNow = iter < gIters && glacial, hNow = iter < hIters;
+    const bool relaxedFull = p->opt.relaxedFull;           // RELAXED MODE, not parity (kernels_impl.h): one sort per flood, affine solve, Jacobi carve
+    bool midDone = false, sortAfterFlood = false;
+    for (int32_t iter = 0; iter < c.total; ++iter) {
+        c.clk.on = true;
+        if (!midDone && iter >= c.midIter) { midDone = true; erode_flood(c, 0.85); sortAfterFlood = true; }
+        c.clk.on = p->opt.stageTimingAll || p->profiling || c.total <= 16 || iter % 8 == 0;
+        const bool gNow = iter < c.gIters && glacial, hNow = iter < hIters;
         // WO_RELAXED_SORT_EVERY=K (relaxed mode, NOT the reference's semantics: SURVEY 7.3): landCells is re-sorted only every K-th
         // iteration; in between the passes run with a stale visiting order (still a consistent order: every pass compares ranks
         // pairwise, so the dataflow is well defined, it is just not the reference's).  Measured, never reported as parity.
-        const bool relaxedFull = p->opt.relaxedFull;           // RELAXED MODE, not parity (kernels_impl.h): one sort per flood, affine solve, Jacobi carve
         const bool sortNow = relaxedFull ? (iter == 0 || sortAfterFlood) : (p->opt.relaxedSortEvery <= 1 || iter % p->opt.relaxedSortEvery == 0);
-        if ((gNow || hNow) && sortNow) sortAfterFlood = false;
-        if ((gNow || hNow) && sortNow) { clk.begin("sort"); sort_land_by_elevation(p); ++sorts; clk.end(); }
-
-        if (gNow) {
-            clk.begin("glacial");
-            Fields F = p->fields();
-            launch(p, FAM_ICE_RECV, k_ice_receivers, gridN, WO_BLOCK, F);
-            // ice accumulation: one launch in which the last donor to arrive runs its receiver's task (k_ice_climb)
-            launch(p, FAM_ICE_ROUND, k_ice_climb, gridL, WO_BLOCK, F, F.blocker); ++iceRounds;
-            if (relaxedFull) {          // RELAXED: the carve from a snapshot of the heights, one sweep
-                launch(p, FAM_CARVE_ROUND, k_carve_jacobi, gridL, WO_BLOCK, F, (const float*)p->d_e, p->d_e2, gCarve, gConv, gStrength);
-                swap_elev(p);
-                launch(p, FAM_MORAINE, k_moraine_fjord, gridN, WO_BLOCK, p->fields(), gDep, gFjord);
-                clk.end();
-            } else {
-            launch(p, FAM_CARVE_SETUP, k_carve_setup_cells, gridN, WO_BLOCK, F);
-            select_active_by_rank(p, F.arank, p->d_listB, p->d_counters + 3);     // the active tasks in landCells order
-            int32_t activeTasks = 0;
-            {   // dependency lists of the active tasks (once per glacial step)
-                const int32_t active = read_count(p, p->d_counters + 3);
-                activeTasks = active;
-                carveActive += active;
-                if ((int64_t)active > p->carveCap) {
-                    dfree(p->d_carveDeps); dfree(p->d_carveDepCnt); dfree(p->d_carveDepPos); dfree(p->d_carveRecs); dfree(p->d_carveSlotDone); dfree(p->d_carveExpect);
-                    p->carveCap = (int64_t)active + active / 4 + 1024;
-                    p->d_carveDeps = dalloc<int32_t>((size_t)p->carveCap * WO_CARVE_DEPS);
-                    p->d_carveDepCnt = dalloc<int32_t>((size_t)p->carveCap); p->d_carveDepPos = dalloc<int32_t>((size_t)p->carveCap);
-                    p->d_carveRecs = dalloc<CarveRec>((size_t)p->carveCap); p->d_carveSlotDone = dalloc<int32_t>((size_t)p->carveCap); p->d_carveExpect = dalloc<CarveExpect>((size_t)p->carveCap);
-                }
-                F.carveDeps = p->d_carveDeps; F.carveDepCnt = p->d_carveDepCnt; F.carveDepPos = p->d_carveDepPos;
-                // (the dependency lists — a two-hop walk per task — are for the rounds: the granule launch waits on the heights themselves and the lists are only
-                // made if it leaves tasks to the rounds)
-                if (active > 0)
-                    launch(p, FAM_CARVE_SETUP, k_carve_records, blocks_for(active), WO_BLOCK, F, (const int32_t*)p->d_listB, (const int32_t*)(p->d_counters + 3), p->d_carveRecs, p->d_carveSlotDone, gCarve, gConv, gStrength,
-                           (int32_t)0, (int32_t)1);
-            }
-            {
-                int32_t* c = p->d_counters;
-                const int32_t count = activeTasks;
-                int64_t k = 1;
-                // The one launch (k_carve_granules), then — for whatever it leaves — rounds over the static activation list (k_carve_round_static): every
-                // launch covers all active tasks, a finished one leaves after one load, an open one issues its loads at once; the number of finished tasks
-                // is read back after a burst.  (Round 2 also tried all rounds in ONE cooperative launch with a grid barrier: slower,
-                // profiles/r02f_persistent_rounds_grid.txt; the done-word form of the one launch, k_carve_flow, and the rounds-only route were removed in round 6.)
-                if (count > 0) {
-                    const int32_t active = count;
-                    int32_t* done = c + 4;
-                    WO_HIP(hipMemsetAsync(done, 0, sizeof(int32_t), s));
-                    const int grid = blocks_for(active);
-                    // the depth of the carve DAG falls from one glacial iteration to the next (the ice smooths its bed), so the count of
-                    // finished tasks is read back every 32 rounds (a read-back costs about as much as three empty rounds)
-                    constexpr int burst = 32;
-                    bool allDone = false;
-                    {
-                        // every task in one launch; the grid is what is certainly resident at once: the occupancy query's blocks per CU less one
-                        // (the query is known to answer one too many near register-file edges)
-                        static int flowBlocks = 0;
-                        if (!flowBlocks) {
-                            int perCu = 0, dev = 0; hipDeviceProp_t prop;
-                            WO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_carve_granules, WO_BLOCK, 0));
-                            WO_HIP(hipGetDevice(&dev)); WO_HIP(hipGetDeviceProperties(&prop, dev));
-                            flowBlocks = std::max(1, std::min(perCu, 8) - 1) * prop.multiProcessorCount;
-                        }
-                        // hook carve_blocks=<n>: at most n workgroups, so that every thread takes many tasks in turn
-                        const int blocksNow = p->opt.carveBlocks > 0 ? std::max(1, std::min(flowBlocks, p->opt.carveBlocks)) : flowBlocks;
-                        const long long flowBudget = p->opt.carveBudgetMs * 100000ll;   // 100 MHz ticks
-                        if (!p->d_carveG) p->d_carveG = dalloc<unsigned long long>((size_t)N);
-                        launch(p, FAM_CARVE_SETUP, k_carve_expect, grid, WO_BLOCK, F, (const CarveRec*)p->d_carveRecs, (const int32_t*)(c + 3), p->d_carveExpect);
-                        launch(p, FAM_CARVE_SETUP, k_carve_pack, blocks_for(N, 4096), WO_BLOCK, (const float*)F.e, p->d_carveG, N);
-                        launch(p, FAM_CARVE_ROUND, k_carve_granules, std::min(grid, blocksNow), WO_BLOCK, F, (const CarveRec*)p->d_carveRecs, (const CarveExpect*)p->d_carveExpect, p->d_carveG,
-                               p->d_carveSlotDone, (const int32_t*)(c + 3), done, flowBudget);
-                        launch(p, FAM_CARVE_SETUP, k_carve_unpack, blocks_for(N, 4096), WO_BLOCK, (const unsigned long long*)p->d_carveG, F.e, N);
-                        ++k;
-                        const int32_t fin = read_count(p, done);
-                        allDone = fin >= active;
-                        if (!allDone) {          // the rounds want the dependency lists after all
-                            ++carveFlowLeft;
-                            launch(p, FAM_CARVE_SETUP, k_carve_deps, grid, WO_BLOCK, F, (const int32_t*)p->d_listB, (const int32_t*)(c + 3), p->d_carveSlot);
-                            launch(p, FAM_CARVE_SETUP, k_carve_records, grid, WO_BLOCK, F, (const int32_t*)p->d_listB, (const int32_t*)(c + 3), p->d_carveRecs, p->d_carveSlotDone, gCarve, gConv, gStrength, (int32_t)1, (int32_t)0);
-                        }
-                    }
-                    for (; !allDone;) {
-                        for (int b = 0; b < burst; ++b, ++k)
-                            launch(p, FAM_CARVE_ROUND, k_carve_round_static, grid, WO_BLOCK, F, (const CarveRec*)p->d_carveRecs, p->d_carveSlotDone, (const int32_t*)(c + 3), (int32_t)k, gCarve, gConv, gStrength, done);
-                        if (read_count(p, done) >= active) break;
-                        if (k > 4 * (int64_t)p->N + 1024) throw HipError{"carve rounds do not converge"};
-                    }
-                }
-                carveRounds += k - 1;
-            }
-            launch(p, FAM_MORAINE, k_moraine_fjord, gridN, WO_BLOCK, F, gDep, gFjord);
-            clk.end();
-            }
-        }
-
+        if ((gNow || hNow) && sortNow) { sortAfterFlood = false; erode_sort(c); }
+        if (gNow) { if (relaxedFull) glacial_step_relaxed(c); else glacial_step_exact(c); }
         if (hNow) {
-            if (gNow && sortNow) { clk.begin("sort"); sort_land_by_elevation(p); ++sorts; clk.end(); }
-            Fields F = p->fields();
-            F.solveK = K; F.solveM = m; F.solveDt = dt;
-            const bool basin = !relaxedFull;           // exact mode: the basin-local solve (basin.hip); relaxed mode: the affine recurrence below
-            const bool slotIdentity = mir.on && p->mirror.h_mask.size() == (size_t)N;          // land-first mirror: a land cell's Morton slot is its id
-            // the receivers pass also leaves the start state of the layout's component search
-            if (basin) { basin_alloc(p); F.basinJ = p->d_basinJ; F.basinMslot = slotIdentity ? nullptr : p->d_slotOf; }
-            // two-level accumulation (k_flow_tiles): needs the land cells to be the ids 0 .. L-1 in Morton order (land-first mirror); on the planet's
-            // own cell order (WO_LAYOUT=index) the one-launch climb over all cells (k_flow_climb)
-            const bool flowTiles = p->landIdentity;
-            FlowTiles FT{};
-            if (flowTiles) {
-                if (!p->d_ftLr) {
-                    p->d_ftLr = dalloc<int32_t>((size_t)N); p->d_ftParent = dalloc<int32_t>((size_t)N); p->d_ftExtCnt = dalloc<int32_t>((size_t)N); p->d_ftInflow = dalloc<uint32_t>((size_t)N); p->d_ftRootAcc = dalloc<unsigned long long>((size_t)N);
-                    WO_HIP(hipMemsetAsync(p->d_ftInflow, 0, (size_t)N * 4, s)); WO_HIP(hipMemsetAsync(p->d_ftExtCnt, 0, (size_t)N * 4, s));
-                }
-                FT.lr = p->d_ftLr; FT.parent = p->d_ftParent; FT.rootAcc = p->d_ftRootAcc; FT.inflow = p->d_ftInflow; FT.extCnt = p->d_ftExtCnt;
-            }
-            int32_t* const donorCnt = flowTiles ? (int32_t*)nullptr : p->d_flowCnt;
-            bool tilesFirstDone = false, linksDone = false;
-            // unchecked basin pass: its one launch tags what it produces with a number no earlier pass of this planet used
-            const bool passTagged = basin && !checkEveryPass;
-            clk.begin("receivers");
-            launch(p, FAM_RECEIVERS, k_receivers_flow_init, gridL, WO_BLOCK, F, donorCnt);        // + flow start state and donor counts
-            clk.end();
-            F.basinJ = nullptr;
-            // basin-local solve (basin.hip): this pass's store order groups every drainage component with everything it depends on.
-            // The layout needs the receivers only and touches none of the flow accumulation's arrays: it runs on the planet's side stream
-            // beside the flow accumulation and the solve's setup waits for both.  (A third stream for the solve's event lists was measured in
-            // round 3 and a side stream for the elevation sort in round 6 — profiles/r03bc_*, r06d_*: no faster, a launch of these sizes already
-            // occupies the chip's workgroup slots and two side by side take turns; both removed.)
-            if (basin) {
-                ensure_side_stream(p);
-                // two-level flow accumulation: its first kernel also shortens the layout's start state inside every tile (k_flow_tiles<false>:
-                // J[c] <- an ancestor at most a tile away), so the layout's component search starts after it, from chains of tiles instead of cells
-                const bool tilesFeedLayout = flowTiles && slotIdentity;
-                if (tilesFeedLayout) {
-                    FT.basinJ = p->d_basinJ;
-                    launch(p, FAM_FLOW_TILES, k_flow_tiles<false>, (int)(((int64_t)L + FT_CELLS - 1) / FT_CELLS), FT_THREADS, F, FT);
-                    tilesFirstDone = true;
-                    // (the root links too before the fork: beside the layout's first kernel — high-priority stream — they took 33 us instead of 15; flow stage 45.9 -> 43.8 ms per step, profiles/r05h_*)
-                    launch(p, FAM_FLOW_TILES, k_flow_root_links, blocks_for(L, 4096), WO_BLOCK, F, FT);
-                    linksDone = true;
-                }
-                WO_HIP(hipEventRecord(p->evFork, s));
-                WO_HIP(hipStreamWaitEvent(p->side, p->evFork, 0));
-                p->onSide = true;
-                try { basin_layout(p, slotIdentity); } catch (...) { p->onSide = false; throw; }
-                p->onSide = false;
-                WO_HIP(hipEventRecord(p->evJoin, p->side));
-            }
-            clk.begin("flow");
-            // Flow accumulation = subtree sizes of the forward forest (integers: any order of the additions is exact): in two levels under the mirror
-            // (kernels_impl.h: k_flow_tiles), else one launch in which every leaf hands its total to its receiver and the thread that completes a
-            // receiver carries on with it (k_flow_climb).  Every cell with a forward receiver is retired either way; k_flow_final reads the packed totals.
-            // (10 M cells, flow stage per step: round 2's rake rounds + pointer doubling 108 ms, the climb 45, two levels 29: profiles/r02r_*, r05g_*.)
-            if (flowTiles) {
-                const int tiles = (int)(((int64_t)L + FT_CELLS - 1) / FT_CELLS);
-                if (!tilesFirstDone) launch(p, FAM_FLOW_TILES, k_flow_tiles<false>, tiles, FT_THREADS, F, FT);
-                if (!linksDone) launch(p, FAM_FLOW_TILES, k_flow_root_links, blocks_for(L, 4096), WO_BLOCK, F, FT);
-                launch(p, FAM_FLOW_TILES, k_flow_root_climb, blocks_for(L, 4096), WO_BLOCK, F, FT);
-                launch(p, FAM_FLOW_TILES, k_flow_tiles<true>, tiles, FT_THREADS, F, FT);
-            } else
-                launch(p, FAM_FLOW_SNAP, k_flow_climb, gridL, WO_BLOCK, F, (const int32_t*)p->d_flowCnt, (int32_t)0x7fffffff);
-            {
-                Fields Ff = F;
-                if (relaxedFull) Ff.ev = nullptr;                // (no event lists: the relaxed solve has no order)
-                // the solve's outputs are cleared (tags 0) only for a pass whose result is checked on the spot (k_solve_patch / k_solve_final read
-                // the tags as launch numbers); the unchecked pass stamps them with a tag of its own instead (passTag below): 16 B per land cell less to write
-                launch(p, FAM_FLOW_FINAL, k_flow_final, gridL, WO_BLOCK, Ff, donorCnt, (basin && !passTagged) ? p->d_out : (SolveOut*)nullptr);
-            }
-            clk.end();
-            clk.begin("solve");
-            if (relaxedFull) {
-                // RELAXED: h' = a + b h'(receiver) composed by pointer jumping (12 doublings cover chains of 4 096 cells), then heights + deposits in one sweep
-                if (!p->d_affine[0]) { p->d_affine[0] = dalloc<Affine>((size_t)N); p->d_affine[1] = dalloc<Affine>((size_t)N); }
-                launch(p, FAM_SOLVE_SETUP, k_affine_init, gridL, WO_BLOCK, F, p->d_affine[0]);
-                int cur = 0;
-                for (int q = 0; q < 12; ++q, cur ^= 1) launch(p, FAM_SOLVE_ROUND, k_affine_jump, gridL, WO_BLOCK, F, (const Affine*)p->d_affine[cur], p->d_affine[cur ^ 1]);
-                launch(p, FAM_SOLVE_FINAL, k_affine_apply, gridL, WO_BLOCK, F, (const Affine*)p->d_affine[cur], p->d_e2);
-                swap_elev(p);
-                clk.end();
-            } else {
-                WO_HIP(hipStreamWaitEvent(s, p->evJoin, 0));
-                F.slotOf = p->d_basinSlot;
-                F.solveLean = 1;
-                // (the outputs' tags were cleared by k_flow_final: one coalesced sweep instead of one scattered 16-byte write per task)
-                // the solve launch writes the final heights itself (SolveTask finality flags) when its result is not looked at pass by pass and
-                // no k_solve_final then
-                const bool solveFinals = !checkEveryPass;
-                F.solveFinals = solveFinals ? 1 : 0;
-                // (the setup launch also clears the counters of the solve launch: run_solve_patches' countersCleared)
-                launch(p, FAM_SOLVE_SETUP, k_solve_setup_batched<true>, gridL, WO_BLOCK, F, p->d_patchPending, (int32_t)p->numPatches, p->d_patchTotals, (int32_t)WO_PATCH_TOTAL_SLOTS);
-                int32_t passTag = 1;
-                if (passTagged) {
-                    if (p->solvePassSerial >= 0x3ff00000) { WO_HIP(hipMemsetAsync(p->d_out, 0, (size_t)N * sizeof(SolveOut), s)); p->solvePassSerial = 0; }
-                    passTag = (1 << 20) + (int32_t)(++p->solvePassSerial);
-                }
-                const int64_t r = run_solve_patches(p, F, K, m, dt, true, true, !checkEveryPass, passTag);
-                ++basinPasses; if (r > 1) ++basinLeftoverPasses;
-                patchLaunches += r; maxSolve = std::max(maxSolve, r);
-                if (!solveFinals) launch(p, FAM_SOLVE_FINAL, k_solve_final, gridL, WO_BLOCK, F, p->d_e2, (iter < tIters) ? p->d_me : (float*)nullptr);
-                swap_elev(p);
-                clk.end();
-            }
+            if (gNow && sortNow) erode_sort(c);
+            hydraulic_step(c, iter);
         }
-
-        if (iter < tIters) {
-            clk.begin("thermal");
-            Fields F = p->fields();
-            if (!hNow) launch(p, FAM_THERMAL_EXCESS, k_masked_elev, gridL, WO_BLOCK, F);      // else written by k_solve_final
-            launch(p, FAM_THERMAL_EXCESS, k_thermal_excess, gridL, WO_BLOCK, F, talus);
-            if (p->maxDeg <= 12)
-                launch(p, FAM_THERMAL_APPLY, k_thermal_apply_reg<12>, gridL, WO_BLOCK, F, p->d_e2, talus, kThermal);
-            else if (p->maxDeg <= 16)
-                launch(p, FAM_THERMAL_APPLY, k_thermal_apply_reg<16>, gridL, WO_BLOCK, F, p->d_e2, talus, kThermal);
-            else
-                launch_shmem(p, FAM_THERMAL_APPLY, k_thermal_apply, gridL, WO_BLOCK, (size_t)p->maxDeg * WO_BLOCK * 12, F, p->d_e2, talus, kThermal,
-                             (int32_t)p->maxDeg);
-            swap_elev(p);
-            clk.end();
-        }
+        if (iter < tIters) thermal_step(c, hNow);
     }
-    clk.on = true;
-    leftovers_so_far();
+    c.clk.on = true;
+    leftovers_so_far(c);
     if (glacial) {
-        clk.begin("glacial_blend");
-        launch(p, FAM_GLAC_BLEND, k_glacial_blend, gridN, WO_BLOCK, p->fields(), (const float*)p->d_e, p->d_e2);
+        c.clk.begin("glacial_blend");
+        launch(p, FAM_GLAC_BLEND, k_glacial_blend, c.gridN, WO_BLOCK, p->fields(), (const float*)p->d_e, p->d_e2);
         swap_elev(p);
-        clk.end();
+        c.clk.end();
     }
-    const bool mirrored = mir.on;
-    if (mir.on) { clk.begin("setup"); mir.finish(); clk.end(); }
-    clk.finish();
-    p->erodeStats = {{"land_cells", (double)L}, {"mirror_layout", mirrored ? 1.0 : 0.0}, {"iterations", (double)total}, {"sorts", (double)sorts},
-                     {"solve_launches_max_per_pass", (double)maxSolve}, {"solve_patch_launches_total", (double)patchLaunches},
-                     {"solve_basin_passes", (double)basinPasses}, {"solve_basin_passes_with_leftovers", (double)basinLeftoverPasses},
-                     {"flow_two_level", (p->d_ftLr && p->landIdentity && hIters > 0) ? 1.0 : 0.0}, {"ice_rounds_total", (double)iceRounds},
-                     {"carve_rounds_total", (double)carveRounds}, {"carve_active_total", (double)carveActive}, {"carve_flow_launches_with_leftovers", (double)carveFlowLeft}, {"solve_check_every_pass", checkEveryPass ? 1.0 : 0.0}, {"calls_run_again_with_checks", (double)p->redoCalls}, {"flood_stage_ms", floodHostMs},
-                     {"flood_device_pass1_ms", floodRun.deviceMs}, {"flood_device_rounds", (double)floodRun.rounds}, {"flood_device_epochs", (double)floodRun.epochs},
-                     {"flood_device_evaluations", (double)floodRun.evals}, {"flood_equal_key_decisions", (double)floodRun.ties},
-                     {"flood_pass1_on_host", (floodRun.usedDevice && !floodRun.fellBack) ? 0.0 : 1.0},
-                     {"flood_host_calls", (double)floodRun.host.calls}, {"flood_host_serial_pass1", (double)floodRun.host.serialPass1},
-                     {"flood_host_tie_groups", (double)floodRun.host.tieGroups}, {"flood_host_contested", (double)floodRun.host.contested},
-                     {"flood_host_open_parents", (double)floodRun.host.openParents}, {"flood_host_unresolved", (double)floodRun.host.unresolved},
-                     {"flood_host_path_redo", (double)floodRun.host.pathRedo}, {"flood_host_replays", (double)floodRun.host.replays}, {"flood_host_replayed_landmasses", (double)floodRun.host.replayedLandmasses}, {"flood_host_pass1_ms", floodRun.host.pass1Ms},
-                     {"flood_host_pass23_ms", floodRun.host.pass23Ms},
-                     {"relaxed_sort_every", (double)p->opt.relaxedSortEvery}, {"relaxed_full", p->opt.relaxedFull ? 1.0 : 0.0}, {"flood_exchange_calls", (double)p->floodX.calls}, {"flood_exchange_gathers", (double)p->floodX.gathers}, {"flood_exchange_whole_planet_floods", (double)p->floodX.globalFloods}, {"flood_exchange_received", (double)p->floodX.received}};
+    const bool mirrored = c.mir.on;
+    if (mirrored) { c.clk.begin("setup"); c.mir.finish(); c.clk.end(); }
+    c.clk.finish();
+    c.stats(mirrored);
 }
 
 static void jacobi(wo_planet* p, int kind, int32_t iterations, double strength) {
@@ -1128,14 +1128,14 @@ static bool check_planet(wo_planet* p, const char* fn) {
 // the host never got ahead of the device).  No real layout has ever left a task pending, so the look is deferred: the launches add
 // into one word per call, the word is read where the host synchronises anyway (before the second flood, at the end), and if it is
 // not zero the field is restored from a copy taken at entry and the call runs again with the check after every pass — the form
-// that finishes pending tasks with k_solve_patch launches.  WO_SOLVE_CHECK=pass: always that form.
+// that finishes pending tasks with k_solve_patch launches.
 static void erode_composite_checked(wo_planet* p, int32_t hIters, double K, double m, double dt, int32_t tIters, double talus,
                                     double kThermal, int32_t gIters, double gStrength) {
-    if (hIters <= 0) { erode_composite(p, hIters, K, m, dt, tIters, talus, kThermal, gIters, gStrength, true); return; }
-    // With a flood exchange set (shares of one planet) every flood call of this rank is a pair of collectives with its peers: a rank that
-    // ran the call a second time would repeat them alone (its peers are past them and no longer hold that call's heights).  Such a call is
-    // therefore checked pass by pass from the start — pending tasks are finished where they arise and nothing is ever run again.
-    if (p->floodX.on) { erode_composite(p, hIters, K, m, dt, tIters, talus, kThermal, gIters, gStrength, true); return; }
+    // (no hydraulic passes: nothing to check.)  With a flood exchange set (shares of one planet) every flood call of this rank is a pair of
+    // collectives with its peers: a rank that ran the call a second time would repeat them alone (its peers are past them and no longer hold
+    // that call's heights).  Such a call is therefore checked pass by pass from the start — pending tasks are finished where they arise and
+    // nothing is ever run again.
+    if (hIters <= 0 || p->floodX.on) { erode_composite(p, hIters, K, m, dt, tIters, talus, kThermal, gIters, gStrength, true); return; }
     hipStream_t s = p->ctx->stream;
     if (!p->d_redoE) p->d_redoE = dalloc<float>((size_t)p->N);
     if (!p->d_pendingEver) p->d_pendingEver = dalloc<int32_t>(16);
@@ -1146,7 +1146,7 @@ static void erode_composite_checked(wo_planet* p, int32_t hIters, double K, doub
     } catch (const RedoWithChecks&) {
         WO_HIP(hipStreamSynchronize(s));
         if (p->side) WO_HIP(hipStreamSynchronize(p->side));
-            WO_HIP(hipMemcpyAsync(p->d_e, p->d_redoE, (size_t)p->N * sizeof(float), hipMemcpyDeviceToDevice, s));
+        WO_HIP(hipMemcpyAsync(p->d_e, p->d_redoE, (size_t)p->N * sizeof(float), hipMemcpyDeviceToDevice, s));
         ++p->redoCalls;
         erode_composite(p, hIters, K, m, dt, tIters, talus, kThermal, gIters, gStrength, true);
     }
@@ -1974,8 +1974,7 @@ static void assign_elevation(wo_planet* p, const int32_t* r_plate, const wo_plat
     if (d_super) (void)hipFree(d_super);
     if (d_dl) (void)hipFree(d_dl);
     dT.release(); dTS.release(); cS.release(); cP.release();
-    for (auto& b : p->stageBrackets) { p->eventPool.push_back(b.a); p->eventPool.push_back(b.b); }
-    p->stageBrackets.clear(); p->stageSeen.clear(); p->stagePending = false;
+    release_stage_brackets(p);
     p->stageTiming = timing;
 }
 
