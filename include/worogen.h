@@ -79,6 +79,9 @@ int wo_neighbor_dist(int32_t numRegions, const int32_t* adjOffset, const int32_t
 /* computeTriangleElevations: js/planet-worker.js:29-37 */
 int wo_triangle_elevations(int32_t numTriangles, const int32_t* triangles, const float* r_elevation,
                            float* t_elevation);
+/* generateTriangleCenters: js/sphere-mesh.js:206-219.  t_xyz[3t+k] = (a + b + c) / 3 of the corners' coordinate k, summed
+ * left to right in double and stored as float32.  t_xyz has 3*numTriangles floats. */
+int wo_triangle_centers(int32_t numTriangles, const int32_t* triangles, const float* r_xyz, float* t_xyz);
 
 /* ------------------------------------------------ SimplexNoise (js/simplex-noise.js:5-54) ----- */
 /* constructor: perm[512] and permMod12[512] for makeRng(seed) (js/simplex-noise.js:8-14) */
@@ -248,6 +251,25 @@ int wo_planet_set_flood_exchange_comm(wo_planet* planet, const uint8_t* r_isOcea
  * (concurrent union-find); needs no GPU. */
 int wo_land_components(int32_t numRegions, const int32_t* adjOffset, const int32_t* adjList, const uint8_t* r_isOcean,
                        int32_t* label);
+
+/* ------------------------------------------------ heightmap import (js/planet-worker.js:682-940) */
+/* handleImportHeightmap's three stages that only import uses, on the planet's resident field (csrc/heightmap.hip; the per-cell
+ * bodies and their exactness contract are in csrc/import_ops.h).  All three are bit-identical to the reference.
+ * sampleHeightmap(mesh, r_xyz, imageData, imgW, imgH) with sampleBilinear / grayscaleToElevation   js/planet-worker.js:682-727
+ *   gray: imgW*imgH bytes, row-major, row 0 at the north pole.  Sets the resident r_elevation to the sampled field and the
+ *   resident r_isOcean to r_elevation <= 0 (as wo_planet_ocean_from_elevation); r_elevation_out (numRegions floats) may be
+ *   NULL (resident only).  lat = asin(clamp(y)), lon = atan2(x, z) are fdlibm ports (V8's Math.asin / Math.atan2), not libm.
+ *   Fails on a NULL image, imgW or imgH <= 0, or imgW*imgH > INT32_MAX. */
+int wo_sample_heightmap(wo_planet* p, const uint8_t* gray, int32_t imgW, int32_t imgH, float* r_elevation_out);
+/* deriveSyntheticPlates(mesh, r_elevation) on the resident field                                   js/planet-worker.js:733-769
+ *   r_plate[r] = smallest region id of r's component (cells joined along mesh edges whose endpoints share e <= 0; NaN is land);
+ *   seeds = the cells with r_plate[r] == r in ascending id (the Set's insertion order), seedIsOcean[i] = (e <= 0) of seeds[i]
+ *   (NULL: not wanted), *nSeeds their number.  r_plate, seeds and seedIsOcean are sized by numRegions. */
+int wo_synthetic_plates(wo_planet* p, int32_t* r_plate, int32_t* seeds, uint8_t* seedIsOcean, int32_t* nSeeds);
+/* The import's region classification on the resident (final) field                                 js/planet-worker.js:811-831
+ *   ocean_r: e <= 0; mountain_r: e > 0.5; coastline_r: e > 0 with a neighbour e <= 0.  Each list in ascending id (the Sets'
+ *   insertion order), sized by numRegions; counts[3] = their lengths (mountain, coastline, ocean). */
+int wo_classify_regions(wo_planet* p, int32_t* mountain, int32_t* coastline, int32_t* ocean, int32_t* counts);
 
 /* ------------------------------------------------ climate-util --------------- */
 /* smoothField(mesh, field, passes)                                       js/climate-util.js:5-25

@@ -37,6 +37,7 @@ SIGNATURES = {
     "wo_mesh_csr": (C.c_int, [_c_i32, _c_i32, _p, _p, _p, _p, _p]),
     "wo_neighbor_dist": (C.c_int, [_c_i32, _p, _p, _p, _p]),
     "wo_triangle_elevations": (C.c_int, [_c_i32, _p, _p, _p]),
+    "wo_triangle_centers": (C.c_int, [_c_i32, _p, _p, _p]),
     "wo_noise_tables": (C.c_int, [_c_f64, _p, _p]),
     "wo_noise_point": (C.c_int, [_p, _p, _c_i32, _c_i32, _c_f64, _c_f64, _c_f64, _c_f64, _c_f64, _c_f64, _p]),
     "wo_noise_eval": (C.c_int, [_p, _c_f64, _c_i32, _c_i32, _c_f64, _c_f64, _c_f64, _c_i64, _p, _p]),
@@ -52,6 +53,9 @@ SIGNATURES = {
     "wo_soil_creep": (C.c_int, [_p, _p, _p, _c_i32, _c_f64]),
     "wo_assign_elevation": (C.c_int, [_p, _p, _p, _p, _c_i32, _p, _p, _p, _p, _c_f64, _c_f64, _c_f64, _p, _p, _p, _p, _p, _p, _p]),
     "wo_smooth_field": (C.c_int, [_p, _p, _c_i32]),
+    "wo_sample_heightmap": (C.c_int, [_p, _p, _c_i32, _c_i32, _p]),
+    "wo_synthetic_plates": (C.c_int, [_p, _p, _p, _p, _p]),
+    "wo_classify_regions": (C.c_int, [_p, _p, _p, _p, _p]),
     "wo_project_coarse_plates": (C.c_int, [_p, _c_i32, _p, _p, _p, _p, _c_f64, _c_i32, _p]),
     "wo_smooth_reconnect_plates": (C.c_int, [_c_i32, _p, _p, _p, _p, _c_i32, _c_i32]),
     "wo_land_components": (C.c_int, [_c_i32, _p, _p, _p, _p]),

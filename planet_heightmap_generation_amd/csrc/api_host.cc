@@ -62,6 +62,22 @@ int wo_triangle_elevations(int32_t numTriangles, const int32_t* triangles, const
     return 0;
 }
 
+int wo_triangle_centers(int32_t numTriangles, const int32_t* triangles, const float* r_xyz, float* t_xyz) {
+    if (numTriangles < 0 || !triangles || !r_xyz || !t_xyz) { wo::set_error("wo_triangle_centers: bad arguments"); return 1; }
+    wo::parallel_ranges(numTriangles, [&](int64_t b, int64_t e, int) {
+        for (int64_t t = b; t < e; ++t) {
+            const int64_t a = triangles[3 * t], c1 = triangles[3 * t + 1], c2 = triangles[3 * t + 2];
+            for (int k = 0; k < 3; ++k) {
+                // (r_xyz[3a+k] + r_xyz[3b+k] + r_xyz[3c+k]) / 3 in double, stored as float32 (js/sphere-mesh.js:214-216)
+                double s = (double)r_xyz[3 * a + k] + (double)r_xyz[3 * c1 + k];
+                s = s + (double)r_xyz[3 * c2 + k];
+                t_xyz[3 * t + k] = (float)(s / 3.0);
+            }
+        }
+    });
+    return 0;
+}
+
 int wo_noise_tables(double seed, uint8_t* perm512, uint8_t* pm12_512) {
     if (!perm512 || !pm12_512) { wo::set_error("wo_noise_tables: null pointer"); return 1; }
     wo::noise_tables(seed, perm512, pm12_512);

@@ -159,6 +159,17 @@ struct wo_planet {
     int landCur = 0;                    // which of d_land[] holds the current order
     int32_t L = 0;
 
+    // heightmap import scratch (heightmap.hip), allocated on first use and grown when needed; freed by wo_planet_destroy
+    struct Import {
+        uint8_t* img = nullptr; int64_t imgCap = 0;          // the uploaded grayscale image
+        int32_t* label = nullptr;                           // union-find parents, then the component labels
+        uint8_t* flags = nullptr;                           // classification + seed bits per cell (import_ops.h: CLS_*)
+        int32_t* lists = nullptr;                           // 4 x N: plateSeeds, mountain_r, coastline_r, ocean_r
+        uint8_t* seedOcean = nullptr;                       // plateIsOcean.has(seed), parallel to the seed list
+        int32_t* blockCounts = nullptr;                     // [blocks][4] counts, scanned in place into offsets
+        int32_t* totals = nullptr; int32_t* h_totals = nullptr;   // the four list lengths (device, pinned host)
+    } imp;
+
     // Patch-major mirror of the mesh for erodeComposite (planet.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
     // d_e2, d_ocean, d_coast) point at the mirror and the o_* members hold the planet's own buffers.
@@ -244,5 +255,7 @@ void basin_alloc(wo_planet* p);
 void basin_layout(wo_planet* p, bool slotIdentity);
 void basin_solve_launch(wo_planet* p, const Fields& F, int32_t launchTag, int32_t* totalPending);
 void basin_free(wo_planet* p);
+// heightmap.hip: frees the import scratch
+void import_free(wo_planet* p);
 
 }  // namespace wo

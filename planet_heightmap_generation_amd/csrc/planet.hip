@@ -1255,6 +1255,7 @@ void wo_planet_destroy(wo_planet* p) {
     if (p->floodLink && p->floodLinkFree) p->floodLinkFree(p->floodLink);
     p->floodLink = nullptr;
     basin_free(p);
+    import_free(p);
     if (p->side) { (void)hipStreamSynchronize(p->side); (void)hipStreamDestroy(p->side); p->side = nullptr; }
     if (p->evFork) { (void)hipEventDestroy(p->evFork); p->evFork = nullptr; }
     if (p->evJoin) { (void)hipEventDestroy(p->evJoin); p->evJoin = nullptr; }

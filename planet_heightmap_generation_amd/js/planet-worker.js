@@ -11,6 +11,12 @@
 //                  elevations; the climate stages are not run here (skipClimate is reported as true, the reference's own
 //                  behaviour above 300 k cells).  Same result message as the reference, typed arrays transferred:
 //                  -> { type: 'reapplyDone', skipClimate: true, r_elevation, t_elevation, erosionDelta, _reapplyTiming, _postTiming }
+//   cmd 'importHeightmap' { N, jitter, grayscale, imageWidth, imageHeight, sliders, seed? }   (:771-940)
+//                  the reference's handler with every stage native: mesh, neighbour distances, triangle centres, the sampler
+//                  (device), runPostProcessing resident, synthetic plates and region classification (device), triangle
+//                  elevations.  The sampled field is kept as W.prePostElev on the device, so a following `reapply` works on the
+//                  imported planet.  Climate is not run (skipClimate is reported as true, as for reapply); the result is the
+//                  reference's `done` message with the climate fields null, buffers transferred as the reference does.
 //   cmd 'dispose'  frees the retained state -> { type: 'disposed' }
 //   progress / errors exactly as the reference posts them: { type: 'progress', pct, label }, { type: 'error', message, stack };
 //   an unknown command answers `Unknown command: <cmd>` (:952).
@@ -20,6 +26,8 @@ import { parentPort } from 'worker_threads';
 import { performance } from 'perf_hooks';
 import addon, { defaultContext } from './native.js';
 import { runPostProcessingResident } from './post-processing.js';
+import { buildSphere, computeNeighborDist, generateTriangleCenters } from './sphere-mesh.js';
+import { platesFromDevice } from './heightmap-import.js';
 
 let W = null;          // retained state (js/planet-worker.js:22)
 
@@ -81,13 +89,85 @@ function handleReapply(data) {
     }
 }
 
+const CLIMATE_NULLS = ['r_wind_east_summer', 'r_wind_north_summer', 'r_wind_east_winter', 'r_wind_north_winter', 'itczLons', 'itczLatsSummer',
+    'itczLatsWinter', 'r_ocean_current_east_summer', 'r_ocean_current_north_summer', 'r_ocean_current_east_winter', 'r_ocean_current_north_winter',
+    'r_ocean_speed_summer', 'r_ocean_speed_winter', 'r_ocean_warmth_summer', 'r_ocean_warmth_winter', 'r_precip_summer', 'r_precip_winter',
+    'r_temperature_summer', 'r_temperature_winter'];           // buildClimateFields(null, ...) (:112-134)
+
+function handleImportHeightmap(data) {
+    const { N, jitter, grayscale, imageWidth, imageHeight, smoothing, hydraulicErosion, thermalErosion, ridgeSharpening, glacialErosion, terrainWarp, seed: overrideSeed } = data;
+    const timing = [];
+    try {
+        if (!(grayscale instanceof Uint8Array) && !(grayscale instanceof Uint8ClampedArray)) throw new TypeError('importHeightmap: grayscale must be a Uint8Array or Uint8ClampedArray');
+        if (!(imageWidth >= 1 && imageHeight >= 1) || grayscale.length !== imageWidth * imageHeight) throw new RangeError('importHeightmap: grayscale length must be imageWidth*imageHeight');
+        const tTotal0 = performance.now();
+        progress(0, 'Building sphere mesh\u2026');
+        const seed = (overrideSeed !== undefined && overrideSeed !== null) ? overrideSeed : Math.floor(Math.random() * 16777216);
+        let t0 = performance.now();
+        const { mesh, r_xyz } = buildSphere(N, jitter, seed);
+        timing.push({ stage: 'Sphere mesh', ms: performance.now() - t0 });
+        t0 = performance.now();
+        const neighborDist = computeNeighborDist(mesh, r_xyz);
+        timing.push({ stage: 'Neighbor distances', ms: performance.now() - t0 });
+        t0 = performance.now();
+        const t_xyz = generateTriangleCenters(mesh, r_xyz);
+        timing.push({ stage: 'Triangle centers', ms: performance.now() - t0 });
+
+        progress(20, 'Sampling heightmap\u2026');
+        t0 = performance.now();
+        releaseRetained();
+        const planet = addon.planetCreate(defaultContext(), mesh.numRegions, mesh.adjOffset, mesh.adjList, r_xyz, neighborDist);
+        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles, seed, hasHotspot: false };
+        const prePostElev = addon.sampleHeightmap(planet, grayscale, imageWidth, imageHeight, true);
+        addon.planetSaveState(planet);                  // W.prePostElev, device copy
+        timing.push({ stage: 'Sample heightmap', ms: performance.now() - t0 });
+
+        progress(35, 'Processing terrain\u2026');
+        t0 = performance.now();
+        const r_elevation = new Float32Array(mesh.numRegions);
+        const { dl_erosionDelta, postTiming } = runPostProcessingResident(planet, mesh.numRegions, r_elevation,
+            { smoothing, glacialErosion, hydraulicErosion, thermalErosion, ridgeSharpening, terrainWarp }, seed, false);
+        timing.push({ stage: 'Terrain post-processing', ms: performance.now() - t0 });
+
+        progress(50, 'Deriving plates\u2026');
+        t0 = performance.now();
+        const { r_plate, plateSeeds, plateIsOcean, plateVec } = platesFromDevice(addon.syntheticPlates(planet));
+        timing.push({ stage: 'Synthetic plates', ms: performance.now() - t0 });
+        const regions = addon.classifyRegions(planet);
+
+        progress(75, 'Computing triangle elevations\u2026');
+        t0 = performance.now();
+        const t_elevation = addon.triangleElevations(mesh.triangles, r_elevation);
+        timing.push({ stage: 'Triangle elevations', ms: performance.now() - t0 });
+        t0 = performance.now();
+        const r_stress = new Float32Array(mesh.numRegions);
+        timing.push({ stage: 'Clone state for retention', ms: performance.now() - t0 });
+
+        const climate = {};
+        for (const k of CLIMATE_NULLS) climate[k] = null;
+        const result = {
+            type: 'done', triangles: mesh.triangles, halfedges: mesh.halfedges, numRegions: mesh.numRegions, r_xyz, t_xyz, r_plate,
+            plateSeeds: Array.from(plateSeeds), plateVec, plateIsOcean: Array.from(plateIsOcean), originalPlateIsOcean: Array.from(plateIsOcean),
+            plateDensity: {}, plateDensityLand: {}, plateDensityOcean: {}, prePostElev, r_elevation, t_elevation,
+            mountain_r: Array.from(regions.mountain_r), coastline_r: Array.from(regions.coastline_r), ocean_r: Array.from(regions.ocean_r),
+            r_stress, ...climate, skipClimate: true, seed, nMag: 0, debugLayers: { erosionDelta: dl_erosionDelta },
+            _timing: [], _pipelineTiming: timing, _postTiming: postTiming, _workerTotal: performance.now() - tTotal0,
+            _params: { N, P: 0, jitter, nMag: 0, numContinents: 0, smoothing, terrainWarp, hydraulicErosion, thermalErosion, ridgeSharpening, glacialErosion, seed }
+        };
+        parentPort.postMessage(result, [r_xyz.buffer, t_xyz.buffer, r_plate.buffer, prePostElev.buffer, r_elevation.buffer, t_elevation.buffer, r_stress.buffer]);
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
 parentPort.on('message', (data) => {
     const { cmd } = data;
     switch (cmd) {
         case 'retain': handleRetain(data); break;
         case 'reapply': handleReapply(data); break;
+        case 'importHeightmap': handleImportHeightmap(data); break;
         case 'dispose': releaseRetained(); parentPort.postMessage({ type: 'disposed' }); break;
-        case 'generate': case 'editRecompute': case 'computeClimate': case 'importHeightmap':
+        case 'generate': case 'editRecompute': case 'computeClimate':
             parentPort.postMessage({ type: 'error', message: `Command not served by the device worker (host stages of the reference): ${cmd}` });
             break;
         default: parentPort.postMessage({ type: 'error', message: `Unknown command: ${cmd}` });

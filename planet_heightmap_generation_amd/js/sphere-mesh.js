@@ -54,3 +54,7 @@ export function computeNeighborDist(mesh, r_xyz) {
 export function computeTriangleElevations(mesh, r_elevation) {       // js/planet-worker.js:29-37
     return addon.triangleElevations(mesh.triangles, r_elevation);
 }
+
+export function generateTriangleCenters(mesh, r_xyz) {                // js/sphere-mesh.js:206-219
+    return addon.triangleCenters(mesh.triangles, r_xyz);
+}

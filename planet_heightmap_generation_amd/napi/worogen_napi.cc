@@ -484,6 +484,66 @@ napi_value SmoothAndReconnectPlates(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
+// ---- heightmap import (include/worogen.h: wo_sample_heightmap / wo_synthetic_plates / wo_classify_regions / wo_triangle_centers) ----
+// The image (Uint8Array or Uint8ClampedArray of imgW*imgH pixels) is checked before the planet handle is looked at.
+napi_value SampleHeightmap(napi_env env, napi_callback_info info) {            // (planet, gray, imgW, imgH, download) -> Float32Array | undefined
+    Args a(env, info);
+    bool is = false; napi_typedarray_type t = napi_int8_array; size_t n = 0; void* data = nullptr; napi_value ab; size_t off;
+    if (a.argc > 1 && napi_is_typedarray(env, a.argv[1], &is) == napi_ok && is) napi_get_typedarray_info(env, a.argv[1], &t, &n, &data, &ab, &off);
+    if (!is || (t != napi_uint8_array && t != napi_uint8_clamped_array)) { napi_throw_type_error(env, nullptr, "sampleHeightmap: the image must be a Uint8Array or Uint8ClampedArray"); return nullptr; }
+    const double W = a.num(2), H = a.num(3);
+    if (!(W >= 1 && H >= 1 && W == (double)(int64_t)W && H == (double)(int64_t)H) || W * H > 2147483647.0) { napi_throw_range_error(env, nullptr, "sampleHeightmap: imgW and imgH must be positive integers with imgW*imgH < 2^31"); return nullptr; }
+    if ((double)n != W * H) { napi_throw_range_error(env, nullptr, "sampleHeightmap: the image length must be imgW*imgH"); return nullptr; }
+    wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    bool download = false; if (a.argc > 4) napi_get_value_bool(env, a.argv[4], &download);
+    void* d = nullptr; napi_value out = nullptr;
+    if (download) { out = make_ta(env, napi_float32_array, (size_t)wo_planet_num_regions(p), 4, &d); if (!out) return nullptr; }
+    if (wo_sample_heightmap(p, (const uint8_t*)data, (int32_t)W, (int32_t)H, (float*)d)) return throw_wo(env, "sampleHeightmap");
+    return out;
+}
+napi_value SyntheticPlates(napi_env env, napi_callback_info info) {            // (planet) -> {r_plate, seeds Int32Array, seedIsOcean Uint8Array}
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    const size_t n = (size_t)wo_planet_num_regions(p);
+    void *rp, *sd, *so; napi_value vrp = make_ta(env, napi_int32_array, n, 4, &rp);
+    std::vector<int32_t> seeds(n); std::vector<uint8_t> isOc(n); int32_t k = 0;
+    if (!vrp) return nullptr;
+    if (wo_synthetic_plates(p, (int32_t*)rp, seeds.data(), isOc.data(), &k)) return throw_wo(env, "syntheticPlates");
+    napi_value vs = make_ta(env, napi_int32_array, (size_t)k, 4, &sd), vo = make_ta(env, napi_uint8_array, (size_t)k, 1, &so);
+    if (!vs || !vo) return nullptr;
+    if (k) { std::memcpy(sd, seeds.data(), (size_t)k * 4); std::memcpy(so, isOc.data(), (size_t)k); }
+    napi_value o; napi_create_object(env, &o);
+    set_prop(env, o, "r_plate", vrp); set_prop(env, o, "seeds", vs); set_prop(env, o, "seedIsOcean", vo);
+    return o;
+}
+napi_value ClassifyRegions(napi_env env, napi_callback_info info) {            // (planet) -> {mountain_r, coastline_r, ocean_r} Int32Arrays
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    const size_t n = (size_t)wo_planet_num_regions(p);
+    std::vector<int32_t> l[3] = {std::vector<int32_t>(n), std::vector<int32_t>(n), std::vector<int32_t>(n)};
+    int32_t counts[3] = {0, 0, 0};
+    if (wo_classify_regions(p, l[0].data(), l[1].data(), l[2].data(), counts)) return throw_wo(env, "classifyRegions");
+    napi_value o; napi_create_object(env, &o);
+    const char* names[3] = {"mountain_r", "coastline_r", "ocean_r"};
+    for (int j = 0; j < 3; ++j) {
+        void* d; napi_value v = make_ta(env, napi_int32_array, (size_t)counts[j], 4, &d); if (!v) return nullptr;
+        if (counts[j]) std::memcpy(d, l[j].data(), (size_t)counts[j] * 4);
+        set_prop(env, o, names[j], v);
+    }
+    return o;
+}
+napi_value TriangleCenters(napi_env env, napi_callback_info info) {            // (triangles, r_xyz) -> Float32Array(numSides)
+    Args a(env, info);
+    size_t ns, nx; int32_t* tri = (int32_t*)a.ta(0, napi_int32_array, &ns); if (!a.ok) return nullptr;
+    float* xyz = (float*)a.ta(1, napi_float32_array, &nx); if (!a.ok) return nullptr;
+    for (size_t i = 0; i < ns; ++i) if (tri[i] < 0 || 3 * (size_t)tri[i] + 2 >= nx) { napi_throw_range_error(env, nullptr, "triangleCenters: corner out of range"); return nullptr; }
+    void* d; napi_value out = make_ta(env, napi_float32_array, 3 * (ns / 3), 4, &d);
+    if (!out) return nullptr;
+    if (wo_triangle_centers((int32_t)(ns / 3), tri, xyz, (float*)d)) return throw_wo(env, "triangleCenters");
+    return out;
+}
+
 // ---- multi-GPU exchange over RCCL (include/worogen.h: wo_comm_*; one worker thread per GPU holds one communicator) -------
 void FinalizeComm(napi_env, void* data, void*) { wo_comm_destroy((wo_comm*)data); }
 napi_value CommUniqueId(napi_env env, napi_callback_info) {                   // () -> Uint8Array(128): rank 0 makes it, the host posts it to every worker
@@ -562,7 +622,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"lastStageTiming", LastStageTiming}, {"lastErodeStats", LastErodeStats}, {"assignElevation", AssignElevation},
         {"projectCoarsePlates", ProjectCoarsePlates}, {"smoothField", SmoothField}, {"smoothAndReconnectPlates", SmoothAndReconnectPlates},
         {"diffuseOceanWarmth", DiffuseOceanWarmth}, {"computeWindConvergence", WindConvergence}, {"advectMoisture", AdvectMoisture},
-        {"landComponents", LandComponents},
+        {"landComponents", LandComponents}, {"sampleHeightmap", SampleHeightmap}, {"syntheticPlates", SyntheticPlates},
+        {"classifyRegions", ClassifyRegions}, {"triangleCenters", TriangleCenters},
         {"commUniqueId", CommUniqueId}, {"commCreate", CommCreate}, {"planetSetHalo", PlanetSetHalo},
         {"planetExchangeAllgather", PlanetExchangeAllgather}, {"planetExchangeNeighbors", PlanetExchangeNeighbors}, {"planetSetFloodExchange", PlanetSetFloodExchange},
     };

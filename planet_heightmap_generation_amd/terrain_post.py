@@ -396,26 +396,45 @@ def run_post_processing(planet: Planet, r_elevation, params: dict, seed, r_hotsp
     """Counterpart of runPostProcessing (js/planet-worker.js:40-102): slider -> argument mapping, ocean mask
     taken after the warp, fixed soil creep.  Mutates r_elevation in place; returns (r_isOcean, erosionDelta)."""
     e = _f32(r_elevation, planet.numRegions)
-    g = lambda k: float(params.get(k, 0.0))  # noqa: E731
-    warp_s, smoothing, glac, hyd, therm, ridge = g("terrainWarp"), g("smoothing"), g("glacialErosion"), g("hydraulicErosion"), g("thermalErosion"), g("ridgeSharpening")
     planet.upload(e)
     if r_hotspot is not None:
         planet.upload_hotspot(r_hotspot)
+    out, delta, _ = run_post_processing_resident(planet, params, seed, r_hotspot is not None)
+    e[:] = out
+    return planet.download_ocean(), delta
+
+
+def run_post_processing_resident(planet: Planet, params: dict, seed, use_hotspot=False):
+    """The same passes on the field that is ALREADY resident (the worker's reapply / import): returns (r_elevation,
+    erosionDelta, postTiming) with postTiming the reference's [{stage, ms}] list (js/planet-worker.js:40-102)."""
+    import time
+    g = lambda k: float(params.get(k, 0.0))  # noqa: E731
+    warp_s, smoothing, glac, hyd, therm, ridge = g("terrainWarp"), g("smoothing"), g("glacialErosion"), g("hydraulicErosion"), g("thermalErosion"), g("ridgeSharpening")
+    timing = []
+
+    def timed(stage, fn):
+        t0 = time.perf_counter()
+        fn()
+        planet.sync()
+        timing.append(dict(stage=stage, ms=(time.perf_counter() - t0) * 1e3))
+
     if warp_s > 0:
-        planet.warp_terrain_resident(seed, warp_s, r_hotspot is not None)
+        timed(f"Terrain warp (strength={warp_s:.2f})", lambda: planet.warp_terrain_resident(seed, warp_s, use_hotspot))
     planet.ocean_from_elevation()
     pre = planet.download()
     if smoothing > 0:
-        planet.smooth_elevation_resident(_js_round(1 + smoothing * 4), 0.2 + smoothing * 0.5)
+        it, st = _js_round(1 + smoothing * 4), 0.2 + smoothing * 0.5
+        timed(f"Smoothing ({it} iters, str={st:.2f})", lambda: planet.smooth_elevation_resident(it, st))
     if glac > 0 or hyd > 0 or therm > 0:
-        planet.erode_composite_resident(_js_round(hyd * 20), 0.0006 * hyd, 0.5, 1.0, _js_round(therm * 10), 1.2 - therm * 0.4,
-                                        therm * 0.15, _js_round(glac * 10), glac)
+        h, t, gi = _js_round(hyd * 20), _js_round(therm * 10), _js_round(glac * 10)
+        timed(f"Erosion composite (h={h}, t={t}, g={gi})",
+              lambda: planet.erode_composite_resident(h, 0.0006 * hyd, 0.5, 1.0, t, 1.2 - therm * 0.4, therm * 0.15, gi, glac))
     if ridge > 0:
-        planet.sharpen_ridges_resident(_js_round(1 + ridge * 3), ridge * 0.08)
-    planet.apply_soil_creep_resident(3, 0.1125)
+        it = _js_round(1 + ridge * 3)
+        timed(f"Ridge sharpening ({it} iters)", lambda: planet.sharpen_ridges_resident(it, ridge * 0.08))
+    timed("Soil creep (3 iters)", lambda: planet.apply_soil_creep_resident(3, 0.1125))
     out = planet.download()
-    e[:] = out
-    return planet.download_ocean(), (out.astype(np.float64) - pre.astype(np.float64)).astype(np.float32)
+    return out, (out.astype(np.float64) - pre.astype(np.float64)).astype(np.float32), timing
 
 
 def _js_round(x: float) -> int:
