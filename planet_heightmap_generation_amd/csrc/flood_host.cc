@@ -15,7 +15,7 @@
 //    40-240 MB arrays.  In the compact Morton layout a cell, its row and its neighbours' state share a few lines
 //    in arrays 4x smaller.  Orders the reference defines by cell id (seed order, pass-2 order, pass-3 tie
 //    order, the noise hash) still use the original ids.
-//  * pass 1 is serial (heap order); the rows of the next few heap entries are prefetched.
+//  * pass 1 keeps the heap order: one heap per landmass, the single heap replayed where equal keys matter (serial route: one heap).
 //  * passes 2 and 3 are separable per drainage tree (every path, carve window and drain target lies inside
 //    one tree), so trees run on a few host cores while each tree keeps the reference's order.
 #include <algorithm>
@@ -269,97 +269,93 @@ constexpr int32_t UNVISITED = -2, TO_OCEAN = -3, NO_TARGET = -1;
 }  // namespace
 int64_t flood_queues_differ(int64_t ops, uint64_t seed) { return queues_differ(ops, seed); }
 
-// Everything that depends only on (mesh, positions, r_isOcean): Morton order, compact land numbering and CSR, the
-// open-ocean component (largest, first wins ties, js/terrain-post.js:66-94) and the seed list (land cells whose
-// first open-ocean neighbour in adjacency order exists, ascending r, :118-128).  Shared by both flood calls of
-// an erodeComposite and kept across calls while the ocean mask is unchanged.
-void flood_build_static(int32_t N, const int32_t* off, const int32_t* adj, const float* xyz, const uint8_t* ocean, FloodScratch& S, const int32_t* mortonAll) {
-    const bool timing = std::getenv("WO_FLOOD_TIMING") != nullptr;
-    auto tp = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[flood static] %-12s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - tp).count());
+namespace {
+using Clock = std::chrono::steady_clock;
+double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+struct FloodTimer {             // WO_FLOOD_TIMING: laps -> stderr
+    bool on; const char* tag; int width;
+    explicit FloodTimer(const FloodScratch& S) : on(S.hooks.timing), tag("[flood]"), width(10) {}
+    FloodTimer(bool on_, const char* tag_, int width_) : on(on_), tag(tag_), width(width_) {}
+    Clock::time_point tp = Clock::now();
+    void lap(const char* what) {
+        const auto now = Clock::now();
+        if (on) std::fprintf(stderr, "%s %-*s %8.1f ms\n", tag, width, what, ms_between(tp, now));
         tp = now;
-    };
-    // Ocean components (:66-94).  The reference labels them by a stack walk in ascending r and keeps the largest, the
-    // first label winning ties — i.e. among the largest components the one holding the smallest cell id.  Only that
-    // choice is observable, so the components come from a concurrent union-find whose roots are the smallest id of
-    // each component (link the larger root under the smaller with a CAS; path halving on the way up).
-    hvec<int32_t> parentStore((size_t)N);               // (not zero-filled: mesh_components writes every entry)
-    int32_t* parent = parentStore.data();
-    mesh_components(N, off, adj, [&](int32_t r) { return ocean[r] != 0; }, [](int32_t, int32_t) { return true; }, parent);
+    }
+};
+// out := value(i) of every i < n with keep(i), ascending i: per range of parallel_ranges the count, their scan, then every range writes behind the ranges before it
+template <class Keep, class Value>
+void filter_ranges(int64_t n, hvec<int32_t>& out, Keep keep, Value value) {
+    std::vector<int64_t> cnt(host_threads() + 2, 0);
+    parallel_ranges(n, [&](int64_t b, int64_t e, int t) { int64_t c = 0; for (int64_t i = b; i < e; ++i) c += keep(i) ? 1 : 0; cnt[t + 1] = c; });
+    for (size_t t = 1; t < cnt.size(); ++t) cnt[t] += cnt[t - 1];
+    out.resize(cnt.back());
+    parallel_ranges(n, [&](int64_t b, int64_t e, int t) { int64_t o = cnt[t]; for (int64_t i = b; i < e; ++i) if (keep(i)) out[o++] = value(i); });
+}
+// emit(root, count) for every run of equal comp[] among the members of [b, e)
+template <class Member, class Emit>
+void for_runs(int64_t b, int64_t e, const int32_t* comp, Member member, Emit emit) {
+    int32_t last = -1; int64_t cnt = 0;
+    for (int64_t r = b; r < e; ++r) {
+        if (!member(r)) continue;
+        if (comp[r] == last) { ++cnt; continue; }
+        if (cnt) emit(last, cnt);
+        last = comp[r]; cnt = 1;
+    }
+    if (cnt) emit(last, cnt);
+}
+inline uint32_t morton_key(const float* xyz, int32_t r) {
+    auto q = [](float v) { int32_t t = (int32_t)((v + 1.0f) * 511.5f); return (uint32_t)(t < 0 ? 0 : (t > 1023 ? 1023 : t)); };
+    return spread3(q(xyz[3 * r])) | (spread3(q(xyz[3 * r + 1])) << 1) | (spread3(q(xyz[3 * r + 2])) << 2);
+}
+// Ocean components (:66-94).  The reference labels them by a stack walk in ascending r and keeps the largest, the
+// first label winning ties — i.e. among the largest components the one holding the smallest cell id.  Only that
+// choice is observable, so the components come from a concurrent union-find whose roots are the smallest id of
+// each component (link the larger root under the smaller with a CAS; path halving on the way up).
+// label: the root of every ocean cell; returns the open ocean's root.
+int32_t main_ocean_label(int32_t N, const int32_t* off, const int32_t* adj, const uint8_t* ocean, int32_t* label) {
+    mesh_components(N, off, adj, [&](int32_t r) { return ocean[r] != 0; }, [](int32_t, int32_t) { return true; }, label);
     // component sizes per thread as (root, count) runs, merged afterwards
     std::vector<std::vector<std::pair<int32_t, int64_t>>> runs(host_threads() + 1);
-    parallel_ranges(N, [&](int64_t b, int64_t e, int t) {
-        auto& out = runs[t];
-        int32_t last = -1; int64_t cnt = 0;
-        for (int64_t r = b; r < e; ++r) {
-            if (!ocean[r]) continue;
-            const int32_t root = parent[r];
-            if (root == last) { ++cnt; continue; }
-            if (cnt) out.push_back({last, cnt});
-            last = root; cnt = 1;
-        }
-        if (cnt) out.push_back({last, cnt});
-    });
-    int32_t mainLab = -1;
-    {
-        std::vector<std::pair<int32_t, int64_t>> all;
-        for (auto& v : runs) all.insert(all.end(), v.begin(), v.end());
-        std::sort(all.begin(), all.end());
-        int64_t best = 0;
-        for (size_t i = 0; i < all.size();) {
-            size_t j = i; int64_t sz = 0;
-            while (j < all.size() && all[j].first == all[i].first) sz += all[j++].second;
-            if (sz > best) { best = sz; mainLab = all[i].first; }      // ascending roots: the first of the largest wins
-            i = j;
-        }
+    parallel_ranges(N, [&](int64_t b, int64_t e, int t) { for_runs(b, e, label, [&](int64_t r) { return ocean[r] != 0; }, [&](int32_t root, int64_t cnt) { runs[t].push_back({root, cnt}); }); });
+    std::vector<std::pair<int32_t, int64_t>> all;
+    for (auto& v : runs) all.insert(all.end(), v.begin(), v.end());
+    std::sort(all.begin(), all.end());
+    int32_t mainLab = -1; int64_t best = 0;
+    for (size_t i = 0; i < all.size();) {
+        size_t j = i; int64_t sz = 0;
+        while (j < all.size() && all[j].first == all[i].first) sz += all[j++].second;
+        if (sz > best) { best = sz; mainLab = all[i].first; }      // ascending roots: the first of the largest wins
+        i = j;
     }
-    const int32_t* label = parent;
-    lap("ocean labels");
-    // land cells in Morton order of their positions (identity order when no positions are given)
-    hvec<int32_t> landCells;
+    return mainLab;
+}
+// land cells in Morton order of their positions (identity order when no positions are given)
+void build_land_list(int32_t N, const float* xyz, const uint8_t* ocean, const int32_t* mortonAll, hvec<int32_t>& landCells) {
     if (xyz && mortonAll) {
         // the caller has ALL cells in that order already (morton_order_cells: same keys, same stable sort, so the land cells appear in it in the order the sort
         // below would give them): a new mask on a known mesh is a filter, not a sort (32 -> 3 ms of a new terrain's set-up at 10 M cells)
-        std::vector<int64_t> cnt(host_threads() + 2, 0);
-        parallel_ranges(N, [&](int64_t b, int64_t e, int t) { int64_t c = 0; for (int64_t i = b; i < e; ++i) c += ocean[mortonAll[i]] ? 0 : 1; cnt[t + 1] = c; });
-        for (size_t t = 1; t < cnt.size(); ++t) cnt[t] += cnt[t - 1];
-        landCells.resize(cnt.back());
-        parallel_ranges(N, [&](int64_t b, int64_t e, int t) { int64_t o = cnt[t]; for (int64_t i = b; i < e; ++i) { const int32_t r = mortonAll[i]; if (!ocean[r]) landCells[o++] = r; } });
-    } else {
-        std::vector<int64_t> cnt(host_threads() + 2, 0);
-        parallel_ranges(N, [&](int64_t b, int64_t e, int t) { int64_t c = 0; for (int64_t r = b; r < e; ++r) c += ocean[r] ? 0 : 1; cnt[t + 1] = c; });
-        for (size_t t = 1; t < cnt.size(); ++t) cnt[t] += cnt[t - 1];
-        landCells.resize(cnt.back());
-        parallel_ranges(N, [&](int64_t b, int64_t e, int t) { int64_t o = cnt[t]; for (int64_t r = b; r < e; ++r) if (!ocean[r]) landCells[o++] = (int32_t)r; });
+        filter_ranges(N, landCells, [&](int64_t i) { return !ocean[mortonAll[i]]; }, [&](int64_t i) { return mortonAll[i]; });
+        return;
     }
+    filter_ranges(N, landCells, [&](int64_t r) { return !ocean[r]; }, [](int64_t r) { return (int32_t)r; });
     const int32_t L = (int32_t)landCells.size();
-    if (xyz && L > 1 && !mortonAll) {
+    if (xyz && L > 1) {
         std::vector<uint32_t> keys(L);
-        parallel_ranges(L, [&](int64_t b, int64_t e, int) {
-            for (int64_t i = b; i < e; ++i) {
-                const int32_t r = landCells[i];
-                auto q = [](float v) { int32_t t = (int32_t)((v + 1.0f) * 511.5f); return (uint32_t)(t < 0 ? 0 : (t > 1023 ? 1023 : t)); };
-                keys[i] = spread3(q(xyz[3 * r])) | (spread3(q(xyz[3 * r + 1])) << 1) | (spread3(q(xyz[3 * r + 2])) << 2);
-            }
-        });
+        parallel_ranges(L, [&](int64_t b, int64_t e, int) { for (int64_t i = b; i < e; ++i) keys[i] = morton_key(xyz, landCells[i]); });
         radix_sort_u32(keys, landCells);
     }
-    lap("morton sort");
-    S.L = L;
-    S.landCell.swap(landCells);
+}
+// landIndex (cell id -> land index, -1 for ocean) and landByR (land indices in ascending original id: the order passes 2 and 3 are defined in)
+void build_land_index(int32_t N, const uint8_t* ocean, FloodScratch& S) {
     S.landIndex.resize(N);
     parallel_ranges(N, [&](int64_t b, int64_t e, int) { for (int64_t r = b; r < e; ++r) S.landIndex[r] = -1; });
-    parallel_ranges(L, [&](int64_t b, int64_t e, int) { for (int64_t i = b; i < e; ++i) S.landIndex[S.landCell[i]] = (int32_t)i; });
-    {   // land indices in ascending original id (the order passes 2 and 3 are defined in)
-        std::vector<int64_t> cnt(host_threads() + 2, 0);
-        parallel_ranges(N, [&](int64_t b, int64_t e, int t) { int64_t c = 0; for (int64_t r = b; r < e; ++r) c += ocean[r] ? 0 : 1; cnt[t + 1] = c; });
-        for (size_t t = 1; t < cnt.size(); ++t) cnt[t] += cnt[t - 1];
-        S.landByR.resize(L);
-        parallel_ranges(N, [&](int64_t b, int64_t e, int t) { int64_t o = cnt[t]; for (int64_t r = b; r < e; ++r) if (!ocean[r]) S.landByR[o++] = S.landIndex[r]; });
-    }
+    parallel_ranges(S.L, [&](int64_t b, int64_t e, int) { for (int64_t i = b; i < e; ++i) S.landIndex[S.landCell[i]] = (int32_t)i; });
+    filter_ranges(N, S.landByR, [&](int64_t r) { return !ocean[r]; }, [&](int64_t r) { return S.landIndex[r]; });
+}
+// the land cells' own CSR in land indices (ocean neighbours dropped)
+void build_compact_csr(const int32_t* off, const int32_t* adj, const uint8_t* ocean, FloodScratch& S) {
+    const int32_t L = S.L;
     S.offL.assign(L + 1, 0);
     parallel_ranges(L, [&](int64_t b, int64_t e, int) {
         for (int64_t i = b; i < e; ++i) {
@@ -378,93 +374,106 @@ void flood_build_static(int32_t N, const int32_t* off, const int32_t* adj, const
             for (int32_t j = off[r]; j < off[r + 1]; ++j) { const int32_t nb = adj[j]; if (!ocean[nb]) S.adjL[o++] = S.landIndex[nb]; }
         }
     });
-    lap("compact csr");
-    S.seedCell.clear();                     // land index of each seed, in ascending original id
-    {
-        std::vector<std::vector<int32_t>> part(host_threads() + 1);
-        parallel_ranges(N, [&](int64_t b, int64_t e, int t) {
-            for (int64_t r = b; r < e; ++r) {
-                if (ocean[r]) continue;
-                for (int32_t j = off[r]; j < off[r + 1]; ++j) {
-                    const int32_t nb = adj[j];
-                    if (ocean[nb] && label[nb] == mainLab) { part[t].push_back(S.landIndex[r]); break; }
-                }
+}
+// seedCell: the land index of each seed (a land cell with an open-ocean neighbour, :118-128), in ascending original id
+void find_seeds(int32_t N, const int32_t* off, const int32_t* adj, const uint8_t* ocean, const int32_t* label, int32_t mainLab, FloodScratch& S) {
+    S.seedCell.clear();
+    std::vector<std::vector<int32_t>> part(host_threads() + 1);
+    parallel_ranges(N, [&](int64_t b, int64_t e, int t) {
+        for (int64_t r = b; r < e; ++r) {
+            if (ocean[r]) continue;
+            for (int32_t j = off[r]; j < off[r + 1]; ++j) {
+                const int32_t nb = adj[j];
+                if (ocean[nb] && label[nb] == mainLab) { part[t].push_back(S.landIndex[r]); break; }
             }
-        });
-        for (auto& v : part) S.seedCell.insert(S.seedCell.end(), v.begin(), v.end());      // ranges ascend with the thread index
+        }
+    });
+    for (auto& v : part) S.seedCell.insert(S.seedCell.end(), v.begin(), v.end());      // ranges ascend with the thread index
+}
+// compCells: per seeded landmass its cells in ascending original id (the order pass 2 is defined in); compIndex: by component root the
+// landmass's number, -1 for an unseeded one.  As filter_ranges, with one output per landmass.
+void build_landmass_cells(const int32_t* comp, const int32_t* compIndex, FloodScratch& S) {
+    const int32_t nComp = (int32_t)S.compSize.size();
+    S.compCellStart.assign(nComp + 1, 0);
+    for (int32_t k = 0; k < nComp; ++k) S.compCellStart[k + 1] = S.compCellStart[k] + S.compSize[k];
+    S.compCells.resize(S.compCellStart[nComp]);
+    const int nt = host_threads() + 2;
+    std::vector<int32_t> cnt((size_t)nt * (size_t)std::max(nComp, 1), 0);
+    int usedRanges = 0;
+    parallel_ranges(S.L, [&](int64_t b, int64_t e, int t) {
+        int32_t* c = cnt.data() + (size_t)t * (size_t)nComp;
+        for (int64_t q = b; q < e; ++q) { const int32_t k = compIndex[comp[S.landByR[q]]]; if (k >= 0) ++c[k]; }
+        int cur = usedRanges; while (cur < t + 1 && !__atomic_compare_exchange_n(&usedRanges, &cur, t + 1, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    });
+    for (int32_t k = 0; k < nComp; ++k) {                // exclusive scan over the ranges, per landmass
+        int32_t at = S.compCellStart[k];
+        for (int t = 0; t < usedRanges; ++t) { int32_t& c = cnt[(size_t)t * (size_t)nComp + k]; const int32_t n = c; c = at; at += n; }
     }
+    parallel_ranges(S.L, [&](int64_t b, int64_t e, int t) {
+        int32_t* c = cnt.data() + (size_t)t * (size_t)nComp;
+        for (int64_t q = b; q < e; ++q) { const int32_t i = S.landByR[q]; const int32_t k = compIndex[comp[i]]; if (k >= 0) S.compCells[c[k]++] = i; }
+    });
+}
+// Landmasses: connected components of the compact land graph.  The flood never crosses water (ocean cells are
+// "visited" from the start, :119), so every landmass floods from its own seeds and pass 1 can give each its own
+// heap (walk_landmass).  Seeds are grouped by landmass (ascending original id inside, the order the
+// reference pushes them in); landmasses are taken largest first.
+void build_landmasses(FloodScratch& S) {
+    const int32_t L = S.L;
+    hvec<int32_t> comp((size_t)L);
+    mesh_components(L, S.offL.data(), S.adjL.data(), [](int32_t) { return true; }, [](int32_t, int32_t) { return true; }, comp.data());
+    // cells per component root: runs of equal roots (Morton order keeps a landmass's cells together) added with one atomic each
+    hvec<int32_t> size((size_t)L);
+    parallel_ranges(L, [&](int64_t b, int64_t e, int) { std::memset(size.data() + b, 0, sizeof(int32_t) * (size_t)(e - b)); });
+    parallel_ranges(L, [&](int64_t b, int64_t e, int) { for_runs(b, e, comp.data(), [](int64_t) { return true; }, [&](int32_t root, int64_t cnt) { __atomic_fetch_add(&size[root], (int32_t)cnt, __ATOMIC_RELAXED); }); });
+    const int32_t nS = (int32_t)S.seedCell.size();
+    std::vector<int32_t> ord(nS);
+    for (int32_t k = 0; k < nS; ++k) ord[k] = k;
+    std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) {
+        const int32_t ca = comp[S.seedCell[a]], cb = comp[S.seedCell[b]];
+        return size[ca] != size[cb] ? size[ca] > size[cb] : ca < cb;
+    });
+    S.compSeeds.assign(ord.begin(), ord.end());
+    S.compSeedStart.clear(); S.compSize.clear();
+    for (int32_t k = 0; k < nS; ++k)
+        if (k == 0 || comp[S.seedCell[ord[k]]] != comp[S.seedCell[ord[k - 1]]]) { S.compSeedStart.push_back(k); S.compSize.push_back(size[comp[S.seedCell[ord[k]]]]); }
+    S.compSeedStart.push_back(nS);
+    S.stamp.resize(L);
+    // each seed's position among its landmass's seeds (= local tree number)
+    const int32_t nComp = (int32_t)S.compSize.size();
+    hvec<int32_t>& compIndex = size;                     // by component root (the sizes are in compSize now)
+    parallel_ranges(L, [&](int64_t b, int64_t e, int) { for (int64_t i = b; i < e; ++i) compIndex[i] = -1; });
+    S.seedLocal.assign(nS, 0);
+    for (int32_t k = 0; k < nComp; ++k) {
+        compIndex[comp[S.seedCell[ord[S.compSeedStart[k]]]]] = k;
+        for (int32_t q = S.compSeedStart[k]; q < S.compSeedStart[k + 1]; ++q) S.seedLocal[ord[q]] = q - S.compSeedStart[k];
+    }
+    build_landmass_cells(comp.data(), compIndex.data(), S);
+}
+}  // namespace
+
+// Everything that depends only on (mesh, positions, r_isOcean): Morton order, compact land numbering and CSR, the
+// open-ocean component (largest, first wins ties, js/terrain-post.js:66-94) and the seed list (land cells whose
+// first open-ocean neighbour in adjacency order exists, ascending r, :118-128).  Shared by both flood calls of
+// an erodeComposite and kept across calls while the ocean mask is unchanged.
+void flood_build_static(int32_t N, const int32_t* off, const int32_t* adj, const float* xyz, const uint8_t* ocean, FloodScratch& S, const int32_t* mortonAll) {
+    FloodTimer T(std::getenv("WO_FLOOD_TIMING") != nullptr, "[flood static]", 12);
+    hvec<int32_t> label((size_t)N);                     // (not zero-filled: mesh_components writes every entry)
+    const int32_t mainLab = main_ocean_label(N, off, adj, ocean, label.data());
+    T.lap("ocean labels");
+    build_land_list(N, xyz, ocean, mortonAll, S.landCell);
+    T.lap("morton sort");
+    const int32_t L = S.L = (int32_t)S.landCell.size();
+    build_land_index(N, ocean, S);
+    build_compact_csr(off, adj, ocean, S);
+    T.lap("compact csr");
+    find_seeds(N, off, adj, ocean, label.data(), mainLab, S);
     S.surface.resize(L); S.state.resize(L); S.root.resize(L); S.eL.resize(L); S.localIdx.resize(L);
     S.order.resize(L); S.order2.resize(L); S.bits.resize(L); S.bits2.resize(L); S.list2.resize(L);
-    lap("seeds+alloc");
-    {   // Landmasses: connected components of the compact land graph.  The flood never crosses water (ocean cells are
-        // "visited" from the start, :119), so every landmass floods from its own seeds and pass 1 can give each its own
-        // heap (flood_pass1_landmasses).  Seeds are grouped by landmass (ascending original id inside, the order the
-        // reference pushes them in); landmasses are taken largest first.
-        hvec<int32_t> comp((size_t)L);
-        mesh_components(L, S.offL.data(), S.adjL.data(), [](int32_t) { return true; }, [](int32_t, int32_t) { return true; }, comp.data());
-        // cells per component root: runs of equal roots (Morton order keeps a landmass's cells together) added with one atomic each
-        hvec<int32_t> size((size_t)L);
-        parallel_ranges(L, [&](int64_t b, int64_t e, int) { std::memset(size.data() + b, 0, sizeof(int32_t) * (size_t)(e - b)); });
-        parallel_ranges(L, [&](int64_t b, int64_t e, int) {
-            int32_t last = -1, run = 0;
-            for (int64_t i = b; i < e; ++i) {
-                const int32_t c = comp[i];
-                if (c == last) { ++run; continue; }
-                if (run) __atomic_fetch_add(&size[last], run, __ATOMIC_RELAXED);
-                last = c; run = 1;
-            }
-            if (run) __atomic_fetch_add(&size[last], run, __ATOMIC_RELAXED);
-        });
-        const int32_t nS = (int32_t)S.seedCell.size();
-        std::vector<int32_t> ord(nS);
-        for (int32_t k = 0; k < nS; ++k) ord[k] = k;
-        std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) {
-            const int32_t ca = comp[S.seedCell[a]], cb = comp[S.seedCell[b]];
-            return size[ca] != size[cb] ? size[ca] > size[cb] : ca < cb;
-        });
-        S.compSeeds.assign(ord.begin(), ord.end());
-        S.compSeedStart.clear(); S.compSize.clear();
-        for (int32_t k = 0; k < nS; ++k)
-            if (k == 0 || comp[S.seedCell[ord[k]]] != comp[S.seedCell[ord[k - 1]]]) { S.compSeedStart.push_back(k); S.compSize.push_back(size[comp[S.seedCell[ord[k]]]]); }
-        S.compSeedStart.push_back(nS);
-        S.stamp.resize(L);
-        // per seeded landmass: its cells in ascending original id (the order pass 2 is defined in), and each seed's position
-        // among its landmass's seeds (= local tree number)
-        const int32_t nComp = (int32_t)S.compSize.size();
-        hvec<int32_t>& compIndex = size;                     // by component root: the landmass's number, -1 for an unseeded one (the sizes are in compSize now)
-        parallel_ranges(L, [&](int64_t b, int64_t e, int) { for (int64_t i = b; i < e; ++i) compIndex[i] = -1; });
-        S.seedLocal.assign(nS, 0);
-        for (int32_t k = 0; k < nComp; ++k) {
-            compIndex[comp[S.seedCell[ord[S.compSeedStart[k]]]]] = k;
-            for (int32_t q = S.compSeedStart[k]; q < S.compSeedStart[k + 1]; ++q) S.seedLocal[ord[q]] = q - S.compSeedStart[k];
-        }
-        S.compCellStart.assign(nComp + 1, 0);
-        for (int32_t k = 0; k < nComp; ++k) S.compCellStart[k + 1] = S.compCellStart[k] + S.compSize[k];
-        S.compCells.resize(S.compCellStart[nComp]);
-        // the cells of every landmass in ascending original id: per range of that order the count per landmass, then every range writes behind the ranges before it
-        {
-            const int nt = host_threads() + 2;
-            std::vector<int32_t> cnt((size_t)nt * (size_t)std::max(nComp, 1), 0);
-            int usedRanges = 0;
-            parallel_ranges(L, [&](int64_t b, int64_t e, int t) {
-                int32_t* c = cnt.data() + (size_t)t * (size_t)nComp;
-                for (int64_t q = b; q < e; ++q) { const int32_t k = compIndex[comp[S.landByR[q]]]; if (k >= 0) ++c[k]; }
-                int cur = usedRanges; while (cur < t + 1 && !__atomic_compare_exchange_n(&usedRanges, &cur, t + 1, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-            });
-            for (int32_t k = 0; k < nComp; ++k) {                // exclusive scan over the ranges, per landmass
-                int32_t at = S.compCellStart[k];
-                for (int t = 0; t < usedRanges; ++t) { int32_t& c = cnt[(size_t)t * (size_t)nComp + k]; const int32_t n = c; c = at; at += n; }
-            }
-            parallel_ranges(L, [&](int64_t b, int64_t e, int t) {
-                int32_t* c = cnt.data() + (size_t)t * (size_t)nComp;
-                for (int64_t q = b; q < e; ++q) { const int32_t i = S.landByR[q]; const int32_t k = compIndex[comp[i]]; if (k >= 0) S.compCells[c[k]++] = i; }
-            });
-        }
-    }
-    lap("landmasses");
-    S.staticValid = true;
-    S.staticN = N;
-    ++S.staticVersion;
+    T.lap("seeds+alloc");
+    build_landmasses(S);
+    T.lap("landmasses");
+    S.staticValid = true; S.staticN = N; ++S.staticVersion;
 }
 
 // All cells in Morton order of their positions, ties in ascending id: the same keys and the same stable sort as the land list
@@ -472,13 +481,7 @@ void flood_build_static(int32_t N, const int32_t* off, const int32_t* adj, const
 void morton_order_cells(int32_t N, const float* xyz, hvec<int32_t>& cells) {
     cells.resize(N);
     std::vector<uint32_t> keys(N);
-    parallel_ranges(N, [&](int64_t b, int64_t e, int) {
-        for (int64_t r = b; r < e; ++r) {
-            auto q = [](float v) { int32_t t = (int32_t)((v + 1.0f) * 511.5f); return (uint32_t)(t < 0 ? 0 : (t > 1023 ? 1023 : t)); };
-            cells[r] = (int32_t)r;
-            keys[r] = spread3(q(xyz[3 * r])) | (spread3(q(xyz[3 * r + 1])) << 1) | (spread3(q(xyz[3 * r + 2])) << 2);
-        }
-    });
+    parallel_ranges(N, [&](int64_t b, int64_t e, int) { for (int64_t r = b; r < e; ++r) { cells[r] = (int32_t)r; keys[r] = morton_key(xyz, (int32_t)r); } });
     radix_sort_u32(keys, cells);
 }
 
@@ -486,20 +489,6 @@ void morton_order_cells(int32_t N, const float* xyz, hvec<int32_t>& cells) {
 void flood_cell_noise(const FloodScratch& S, double* out) {
     parallel_ranges(S.L, [&](int64_t b, int64_t en, int) { for (int64_t i = b; i < en; ++i) out[i] = cell_noise(S.landCell[i]); });
 }
-
-namespace {
-struct FloodTimer {
-    bool on;
-    explicit FloodTimer(const FloodScratch& S) : on(S.hooks.timing) {}
-    std::chrono::steady_clock::time_point tp = std::chrono::steady_clock::now();
-    void lap(const char* what) {
-        if (!on) return;
-        auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[flood] %-10s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - tp).count());
-        tp = now;
-    }
-};
-}  // namespace
 
 void FloodHooks::read() {
     // test hooks (host_util.h: WO_TEST_HOOKS), then the two documented switches
@@ -612,8 +601,9 @@ void flood_pass1_host(FloodScratch& S) {
 //  * a contested cell whose surface (hence key) is the same under either claimant and whose key is above the
 //    group's level pops after the group either way: only its drainTo is open.  It is reported in rep.alt and
 //    passes 2/3 decide whether the elevations depend on it (flood_pass23_host).
-//  * anything else (a claimant would change a surface, or the cell cascades inside the group)  ->  return false,
-//    the caller runs the serial walk (flood_pass1_host), the reference's order by construction.
+//  * anything else (a claimant would change a surface, or the cell cascades inside the group)  ->  the landmass is UNDECIDED:
+//    it is walked again inside a replay of the single heap (replay_dirty_landmasses); the two-phase route runs the serial
+//    walk (flood_pass1_host) instead, the reference's order by construction.
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 struct TieGroup { float level; int32_t firstFam, fam; };
@@ -626,7 +616,7 @@ struct Contest { int32_t cell, other; float level; };
 // in the same state whatever the order inside it).  The replay of the single heap treats them like cells of a decided landmass.
 struct PopLog { std::vector<int32_t> cells; int32_t n = 0, outerOpen = 0, prefix = -1; };
 struct WalkStats { int64_t pops = 0, descending = 0, raised = 0, heapSum = 0, heapMax = 0; };     // WO_FLOOD_TIMING: the largest landmass's walk
-template <class Heap, bool STATS = false>
+template <class Heap, bool STATS = false> __attribute__((noinline))      // a function per queue: all of them inlined into one dispatcher cost the second flood's walk 4-6 ms of 34-39 (the queue's own calls no longer inline)
 void walk_landmass_h(FloodScratch& S, const int32_t* seeds, int32_t nSeeds, hvec<FloodHeapItem>& store,
                    std::vector<Contest>& contests, int64_t& nGroups, int64_t& nNested, WalkStats* ws = nullptr,
                    const FloodHeapItem* resume = nullptr, size_t nResume = 0, PopLog* log = nullptr) {
@@ -720,53 +710,85 @@ void walk_landmass_h(FloodScratch& S, const int32_t* seeds, int32_t nSeeds, hvec
     }
     if (logCells) log->prefix = log->n;                     // no contested cell at all
 }
-// landmasses of at least WO_FLOOD_RING_MIN cells (default 4096; FloodHooks: the tests run both queues) walk on the ring queue
-inline bool walk_on_ring(const FloodScratch& S, int32_t nCells) { return nCells >= S.hooks.ringMin; }
-void walk_landmass_with_stats(FloodScratch& S, const int32_t* seeds, int32_t nSeeds, int32_t nCells, hvec<FloodHeapItem>& store,
-                              std::vector<Contest>& contests, int64_t& nGroups, int64_t& nNested, WalkStats& ws, PopLog* log = nullptr) {
-    if (log && (int32_t)log->cells.size() < nCells) log->cells.resize(nCells);
-    if (walk_on_ring(S, nCells)) walk_landmass_h<RingQueue, true>(S, seeds, nSeeds, store, contests, nGroups, nNested, &ws, nullptr, 0, log);
-    else walk_landmass_h<KeyHeap4, true>(S, seeds, nSeeds, store, contests, nGroups, nNested, &ws, nullptr, 0, log);
+// One walk: from the landmass's seeds or, when the replay of the single heap began it, from the frontier that heap held for it.
+struct Walk {
+    const int32_t* seeds = nullptr; int32_t nSeeds = 0; const FloodHeapItem* frontier = nullptr; size_t nFrontier = 0;
+    int32_t nCells = 0;                                  // of the landmass: picks the queue, sizes the log
+    hvec<FloodHeapItem>* store = nullptr; std::vector<Contest>* contests = nullptr; int64_t* nGroups = nullptr; int64_t* nNested = nullptr;
+    WalkStats* stats = nullptr; PopLog* log = nullptr;   // optional (stats: WO_FLOOD_TIMING, the largest landmass)
+};
+template <class Heap>
+void walk_landmass_on(FloodScratch& S, const Walk& w) {
+    if (w.stats) walk_landmass_h<Heap, true>(S, w.seeds, w.nSeeds, *w.store, *w.contests, *w.nGroups, *w.nNested, w.stats, w.frontier, w.nFrontier, w.log);
+    else walk_landmass_h<Heap, false>(S, w.seeds, w.nSeeds, *w.store, *w.contests, *w.nGroups, *w.nNested, nullptr, w.frontier, w.nFrontier, w.log);
 }
-void walk_landmass_resume(FloodScratch& S, const std::vector<FloodHeapItem>& frontier, int32_t nCells, hvec<FloodHeapItem>& store,
-                          std::vector<Contest>& contests, int64_t& nGroups, int64_t& nNested) {
-    if (walk_on_ring(S, nCells)) walk_landmass_h<RingQueue>(S, nullptr, 0, store, contests, nGroups, nNested, nullptr, frontier.data(), frontier.size());
-    else walk_landmass_h<KeyHeap4>(S, nullptr, 0, store, contests, nGroups, nNested, nullptr, frontier.data(), frontier.size());
+// Where a walk's time goes (round 4, the 402 k-cell landmass of the bench planet; research/flood_walk_bench.py replays the walk's op log
+// on the queue alone and the recorded pop order on the expansion alone).  FIRST flood of a step (fresh terrain): heap 11 600 entries on
+// average, 88 % of the pops in ascending order, 86 % of the pushes carry the cell's own key (height + noise); queue 20-24 ms and
+// expansion 15-20 ms in the build container; 27-31 ms for the walk on the GPU box with either queue.  SECOND flood (after 150 erosion
+// iterations): 86 % of the pushes carry a RAISED key (level + EPS + noise) and wait for the level to pass their noise — 100 000 entries on
+// average, 170 000 at most, 44 % of the pops below the level already reached: 44.6-46.7 ms on the 4-ary heap, 34.1-36.9 ms on the ring
+// (GPU box, bucket widths 2^-15 ... 2^-18 alike; no difference in the build container, whose cores have twice the L2).  The binary heap
+// was slower than the 4-ary one (35 against 31-32 ms).  Built, measured and removed in round 4: the ranks of the cells' OWN keys sorted on the
+// device before the stage (4 radix passes + 3 copies: 0.8 ms), the frontier of those keys a bitmap over the ranks and only the raised keys in
+// the ring — exact (device keys and ranks == the host's arithmetic on every cell, fields == oracle), 8.7 against 20 ms on the queue-only replay
+// with ranks per landmass, but with ranks over the whole planet (a landmass's bits are sparse in it) the first flood's walk went 27.6-28.8 ->
+// 25-26 ms and the second flood's, whose keys are mostly raised, 34 -> 41-50 ms: a loss per step.
+// (Measured and dropped in round 3: a bucket queue — 2^16 buckets of width 2^-14 behind a two-level bitmap — instead of the binary heap for
+// the walks, which do not depend on the order of equal keys: 83-130 ms against 45-60 ms for the largest landmass in the build container; the
+// heap of one landmass stays in cache, the buckets' vectors do not.)
+// Landmasses of at least WO_FLOOD_RING_MIN cells (default 4096; FloodHooks: the tests run both queues) walk on the ring queue.
+void walk_landmass(FloodScratch& S, const Walk& w) {
+    if (w.log && (int32_t)w.log->cells.size() < w.nCells) w.log->cells.resize(w.nCells);
+    if (w.nCells >= S.hooks.ringMin) walk_landmass_on<RingQueue>(S, w);
+    else walk_landmass_on<KeyHeap4>(S, w);
 }
-void walk_landmass(FloodScratch& S, const int32_t* seeds, int32_t nSeeds, int32_t nCells, hvec<FloodHeapItem>& store,
-                   std::vector<Contest>& contests, int64_t& nGroups, int64_t& nNested, PopLog* log = nullptr) {
-    // Where a walk's time goes (round 4, the 402 k-cell landmass of the bench planet; research/flood_walk_bench.py replays the walk's op log
-    // on the queue alone and the recorded pop order on the expansion alone).  FIRST flood of a step (fresh terrain): heap 11 600 entries on
-    // average, 88 % of the pops in ascending order, 86 % of the pushes carry the cell's own key (height + noise); queue 20-24 ms and
-    // expansion 15-20 ms in the build container; 27-31 ms for the walk on the GPU box with either queue.  SECOND flood (after 150 erosion
-    // iterations): 86 % of the pushes carry a RAISED key (level + EPS + noise) and wait for the level to pass their noise — 100 000 entries on
-    // average, 170 000 at most, 44 % of the pops below the level already reached: 44.6-46.7 ms on the 4-ary heap, 34.1-36.9 ms on the ring
-    // (GPU box, bucket widths 2^-15 ... 2^-18 alike; no difference in the build container, whose cores have twice the L2).  The binary heap
-    // was slower than the 4-ary one (35 against 31-32 ms).  Built, measured and removed in round 4: the ranks of the cells' OWN keys sorted on the
-    // device before the stage (4 radix passes + 3 copies: 0.8 ms), the frontier of those keys a bitmap over the ranks and only the raised keys in
-    // the ring — exact (device keys and ranks == the host's arithmetic on every cell, fields == oracle), 8.7 against 20 ms on the queue-only replay
-    // with ranks per landmass, but with ranks over the whole planet (a landmass's bits are sparse in it) the first flood's walk went 27.6-28.8 ->
-    // 25-26 ms and the second flood's, whose keys are mostly raised, 34 -> 41-50 ms: a loss per step.
-    if (log && (int32_t)log->cells.size() < nCells) log->cells.resize(nCells);
-    if (walk_on_ring(S, nCells)) walk_landmass_h<RingQueue>(S, seeds, nSeeds, store, contests, nGroups, nNested, nullptr, nullptr, 0, log);
-    else walk_landmass_h<KeyHeap4>(S, seeds, nSeeds, store, contests, nGroups, nNested, nullptr, nullptr, 0, log);
+// the walk of seeded landmass k from its seeds
+Walk seeded_walk(const FloodScratch& S, int32_t k, hvec<FloodHeapItem>& store, std::vector<Contest>& contests, int64_t& nGroups, int64_t& nNested) {
+    return Walk{S.compSeeds.data() + S.compSeedStart[k], S.compSeedStart[k + 1] - S.compSeedStart[k], nullptr, 0, S.compSize[k], &store, &contests, &nGroups, &nNested};
 }
-int flood_workers(int64_t items) {
+template <class W>
+void run_on_threads(int nt, W worker) {  // worker(0 .. nt - 1); a single one runs on the caller
+    if (nt == 1) { worker(0); return; }
+    std::vector<std::thread> th;
+    for (int w = 0; w < nt; ++w) th.emplace_back(worker, w);
+    for (auto& t : th) t.join();
+}
+int flood_workers(int64_t items) {      // WO_FLOOD_THREADS: read once per process
     static const int capThreads = [] { const char* e = std::getenv("WO_FLOOD_THREADS"); const int v = e ? std::atoi(e) : 0; return v >= 1 ? v : 24; }();
     return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(host_threads(), capThreads), items));
 }
-}  // namespace
-
+// What the landmass walks report (contested cells: see TieGroup above)
+struct FloodTieReport {
+    int64_t groups = 0, nested = 0, contested = 0, openParents = 0, unresolved = 0;
+    int32_t landmasses = 0, workers = 0, replayed = 0;   // replayed: landmasses decided by the replay of the single heap
+    std::vector<std::pair<int32_t, int32_t>> alt;      // (cell, alternative parent) where only drainTo is undecided
+};
+// The judgement of a contested cell with a known other claimant (ct.other >= 0): open() when only its parent is undecided — its
+// surface (hence key) is the same under either claimant, its key is above the group's level (it pops after the group either way)
+// and both possible targets are final when pass 3, which visits cells by ascending surface, reaches it.
+struct ContestJudgement { float kx, altSurface; bool aboveGroup, sameSurface, ordered; bool open() const { return aboveGroup && sameSurface && ordered; } };
+ContestJudgement judge_contest(const FloodScratch& S, const Contest& ct) {
+    const FloodCell* st = S.state.data(); const FloodCell& x = st[ct.cell];
+    const double limO = (double)st[ct.other].surface + 1e-7;          // (EPS)
+    ContestJudgement j;
+    j.kx = (float)((double)x.surface + cell_noise(S.landCell[ct.cell]));
+    j.altSurface = ((double)x.e < limO) ? (float)limO : x.e;
+    j.aboveGroup = j.kx > ct.level;
+    j.sameSurface = std::memcmp(&j.altSurface, &x.surface, 4) == 0;
+    j.ordered = x.drain >= 0 && st[x.drain].surface < x.surface && st[ct.other].surface < x.surface;
+    return j;
+}
+// The two-phase route's pass 1 (WO_FLOOD_HOST=two-phase): every landmass walked, one heap each, landmasses concurrently; then all
+// contests judged.  Returns false when one of them is undecided: the caller redoes pass 1 serially (flood_pass1_host).
 bool flood_pass1_landmasses(FloodScratch& S, FloodTieReport& rep) {
-    const double EPS = 1e-7;
     FloodTimer T(S);
     const int32_t nComp = (int32_t)S.compSize.size();
+    const int nt = flood_workers(nComp);
     rep = FloodTieReport{};
-    rep.landmasses = nComp;
+    rep.landmasses = nComp; rep.workers = nt;
     if (nComp == 0) return true;
     parallel_ranges(S.L, [&](int64_t b, int64_t en, int) { std::memset(S.stamp.data() + b, 0, sizeof(int32_t) * (size_t)(en - b)); });
-    const int nt = flood_workers(nComp);
-    rep.workers = nt;
     if ((int)S.workerHeaps.size() < nt) S.workerHeaps.resize(nt);
     std::vector<std::vector<Contest>> contests(nt);
     std::vector<int64_t> ng(nt, 0), nn(nt, 0);
@@ -775,29 +797,17 @@ bool flood_pass1_landmasses(FloodScratch& S, FloodTieReport& rep) {
         for (;;) {
             const int32_t k = next.fetch_add(1);
             if (k >= nComp) break;
-            walk_landmass(S, S.compSeeds.data() + S.compSeedStart[k], S.compSeedStart[k + 1] - S.compSeedStart[k], S.compSize[k], S.workerHeaps[w], contests[w], ng[w], nn[w]);
+            walk_landmass(S, seeded_walk(S, k, S.workerHeaps[w], contests[w], ng[w], nn[w]));
         }
     };
-    if (nt == 1) worker(0);
-    else {
-        std::vector<std::thread> th;
-        for (int w = 0; w < nt; ++w) th.emplace_back(worker, w);
-        for (auto& t : th) t.join();
-    }
-    const FloodCell* st = S.state.data();
+    run_on_threads(nt, worker);
     for (int w = 0; w < nt; ++w) {
         rep.groups += ng[w]; rep.nested += nn[w];
         for (const Contest& ct : contests[w]) {
             ++rep.contested;
-            if (ct.other < 0) { ++rep.unresolved; continue; }
-            const FloodCell& x = st[ct.cell];
-            const float kx = (float)((double)x.surface + cell_noise(S.landCell[ct.cell]));
-            const double limO = (double)st[ct.other].surface + EPS;
-            const float altSurface = ((double)x.e < limO) ? (float)limO : x.e;
-            const bool sameSurface = std::memcmp(&altSurface, &x.surface, 4) == 0;
-            // pass 3 visits cells by ascending surface: both possible targets must be final when the cell's turn comes
-            const bool ordered = x.drain >= 0 && st[x.drain].surface < x.surface && st[ct.other].surface < x.surface;
-            if (kx > ct.level && sameSurface && ordered) { ++rep.openParents; rep.alt.push_back({ct.cell, ct.other}); }
+            // an open parent counts as soon as it is seen (this route has no verdict per landmass: one undecided cell sends the whole call to the
+            // serial walk); the pipeline withdraws those of an undecided landmass (walk_and_judge), so the two routes' openParents differ on ties
+            if (ct.other >= 0 && judge_contest(S, ct).open()) { ++rep.openParents; rep.alt.push_back({ct.cell, ct.other}); }
             else ++rep.unresolved;
         }
     }
@@ -806,6 +816,7 @@ bool flood_pass1_landmasses(FloodScratch& S, FloodTieReport& rep) {
                            rep.landmasses, rep.workers, (long long)rep.groups, (long long)rep.nested, (long long)rep.contested, (long long)rep.openParents, (long long)rep.unresolved);
     return rep.unresolved == 0;
 }
+}  // namespace
 
 // results of the device pass 1 (flood_kernels.h) into the host state of passes 2 and 3: parent in land-index space
 // (FL_NONE = -1 unreached, FL_SEED = -2 drains to the open ocean), surface, tree id (position of the tree's seed)
@@ -1032,116 +1043,111 @@ void tree_pass23(const TreeCtx& X, int32_t* cells, int32_t n, std::vector<int32_
         if ((double)eL[c] <= te) eL[c] = (float)(te + EPS);
     }
 }
+// Consecutive trees (cells of tree t: cnt[t] .. cnt[t + 1]) into chunks of at least `budget` cells each; the last may hold fewer.
+void cut_chunks(const std::vector<int32_t>& cnt, int32_t nTrees, int64_t budget, std::vector<int32_t>& chunkStart) {
+    chunkStart.assign(1, 0);
+    for (int32_t t = 0, last = 0; t < nTrees; ++t)
+        if (cnt[t + 1] - cnt[last] >= budget) { chunkStart.push_back(t + 1); last = t + 1; }
+    if (chunkStart.back() != nTrees) chunkStart.push_back(nTrees);
+}
+// An open parent x (pass 1 left the choice between st[x].drain and p1 open: equal keys, same surface under either).  The elevations
+// do not depend on the choice when (i) no carve path ran through the cell — a path exists only below a deficit cell, so then the
+// cell kept its height through pass 2 and both parents saw the same carves — and (ii) pass 3 leaves the cell alone under either
+// parent (it stands above both parents' final heights).  Asked after pass 3 of a landmass whose carve tracked S.onPath.
+bool open_parent_is_harmless(const FloodScratch& S, int32_t x, int32_t p1) {
+    const FloodCell* st = S.state.data(); const float* eL = S.eL.data();
+    const int32_t p0 = st[x].drain;
+    const bool untouched = !S.onPath[x] && std::memcmp(&eL[x], &st[x].e, 4) == 0;
+    const double h = (double)st[x].e;
+    return untouched && p0 >= 0 && h > (double)eL[p0] && h > (double)eL[p1];
+}
+// the land elevations back into the caller's array
+void write_back(float* e, const FloodScratch& S) {
+    const int32_t* landCell = S.landCell.data(); const float* eL = S.eL.data();
+    if (S.landOrder) parallel_ranges(S.L, [&](int64_t b, int64_t en, int) { std::memcpy(e + b, eL + b, sizeof(float) * (size_t)(en - b)); });
+    else parallel_ranges(S.L, [&](int64_t b, int64_t en, int) { for (int64_t i = b; i < en; ++i) e[landCell[i]] = eL[i]; });
+}
+// All cells of each tree into S.list2 (tree t: cnt2[t] .. cnt2[t + 1]), ascending ORIGINAL id inside.  (Not just the cells with an
+// initial deficit: a carve lowers other cells of the path below their flood surface, and the reference tests `deficit > EPS`
+// against the current height when it reaches them, :154-155.)  A stable counting sort of the ascending-id land list by tree, in
+// parallel: per-worker counts per tree ([tree][worker] so the prefix runs sequentially), then every worker scatters its own
+// contiguous share.
+void group_land_by_tree(FloodScratch& S, std::vector<int32_t>& cnt2) {
+    const int32_t L = S.L, nTrees = (int32_t)S.seedCell.size();
+    const int32_t* root = S.root.data(); const int32_t* byR = S.landByR.data(); int32_t* list2 = S.list2.data();
+    cnt2.assign(nTrees + 1, 0);
+    const int T = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)host_threads(), 16, (int64_t)L / 65536 + 1}));
+    std::vector<int32_t> cw((size_t)nTrees * T, 0);
+    auto share = [&](int t, int64_t& b, int64_t& e) { b = (int64_t)L * t / T; e = (int64_t)L * (t + 1) / T; };
+    std::vector<std::thread> th;
+    for (int t = 0; t < T; ++t) th.emplace_back([&, t]() {
+        int64_t b, e; share(t, b, e);
+        for (int64_t k = b; k < e; ++k) { const int32_t r = root[byR[k]]; if (r >= 0) ++cw[(size_t)r * T + t]; }
+    });
+    for (auto& x : th) x.join();
+    int32_t run = 0;
+    for (int32_t tr = 0; tr < nTrees; ++tr) {
+        cnt2[tr] = run;
+        for (int t = 0; t < T; ++t) { const int32_t c = cw[(size_t)tr * T + t]; cw[(size_t)tr * T + t] = run; run += c; }
+    }
+    cnt2[nTrees] = run; th.clear();
+    for (int t = 0; t < T; ++t) th.emplace_back([&, t]() {
+        int64_t b, e; share(t, b, e);
+        for (int64_t k = b; k < e; ++k) { const int32_t i = byR[k]; const int32_t r = root[i]; if (r >= 0) list2[cw[(size_t)r * T + t]++] = i; }
+    });
+    for (auto& x : th) x.join();
+}
+// body(tree) for every non-empty tree, on threads.  Trees are numbered by their seed's original id, i.e. along the Fibonacci
+// spiral: consecutive ids are spatial neighbours, so workers take contiguous chunks.  Measured on the 2-socket EPYC GPU box with
+// the packed records and huge pages: 6 workers 199 ms, 12 -> 136, 24 -> 102, 48 -> 91 ms for the two calls of a step; 24 is the
+// default (WO_FLOOD_THREADS overrides), which leaves room for several ranks / planets per socket.
+template <class Body>
+void for_trees(const std::vector<int32_t>& cnt, int32_t nTrees, Body body) {
+    const int nt = flood_workers(nTrees);
+    std::vector<int32_t> chunkStart;
+    cut_chunks(cnt, nTrees, std::max<int64_t>(2048, (int64_t)cnt[nTrees] / (nt * 16)), chunkStart);
+    const size_t nChunks = chunkStart.size() - 1; std::atomic<size_t> next{0};
+    run_on_threads(nt, [&](int) {
+        for (size_t c; (c = next.fetch_add(1)) < nChunks;)
+            for (int32_t t = chunkStart[c]; t < chunkStart[c + 1]; ++t) if (cnt[t + 1] > cnt[t]) body(t);
+    });
+}
 }  // namespace
 
-// passes 2 and 3 (:152-214) on the state pass 1 left, then the land elevations back into e
+// passes 2 and 3 (:152-214) on the state pass 1 left, then the land elevations back into e.
+// --- pass 2 (:152-196) and pass 3 (:200-214).  Both are sequential in the reference, but every cell a turn
+// reads or writes (the drain path of r, the carve window on it, r itself; in pass 3 the cell and its
+// drain target) lies inside r's drainage tree, and trees share no land cell.  So trees are processed
+// concurrently while each tree keeps the reference's order (ascending r in pass 2, ascending (surface, r)
+// in pass 3): identical results, no relaxation.
 bool flood_pass23_host(float* e, double carveStrength, FloodScratch& S, const std::vector<std::pair<int32_t, int32_t>>* openAlt) {
     FloodTimer T(S);
-    // Cells whose parent pass 1 left open (equal keys, same surface under either parent).  The elevations do not depend
-    // on the choice when (i) no carve path runs through the cell — a path exists only below a deficit cell, so then the
-    // cell keeps its height through pass 2 and both parents see the same carves — and (ii) pass 3 leaves the cell alone
-    // under either parent (it stands above both parents' final heights).  Checked after pass 3; otherwise: false.
+    // cells whose parent pass 1 left open are checked after pass 3 (open_parent_is_harmless); their landmass's carve marks its paths
     const bool track = openAlt && !openAlt->empty();
     uint8_t* onPath = nullptr;
     if (track) {
-        S.onPath.resize(S.L);
-        onPath = S.onPath.data();
+        S.onPath.resize(S.L); onPath = S.onPath.data();
         parallel_ranges(S.L, [&](int64_t b, int64_t en, int) { std::memset(onPath + b, 0, (size_t)(en - b)); });
     }
-    const bool timing = T.on;
-    const int32_t L = S.L;
-    const int32_t* landCell = S.landCell.data();
-    float* eL = S.eL.data();
-    FloodCell* st = S.state.data();
-    // passes 2 and 3 stream over surface / tree id: give them compact arrays again
-    float* surface = S.surface.data();
-    int32_t* root = S.root.data();
-    parallel_ranges(L, [&](int64_t b, int64_t en, int) { for (int64_t i = b; i < en; ++i) { surface[i] = st[i].surface; root[i] = st[i].root; } });
-    // --- pass 2 (:152-196) and pass 3 (:200-214).  Both are sequential in the reference, but every cell a turn
-    // reads or writes (the drain path of r, the carve window on it, r itself; in pass 3 the cell and its
-    // drain target) lies inside r's drainage tree, and trees share no land cell.  So trees are processed
-    // concurrently while each tree keeps the reference's order (ascending r in pass 2, ascending (surface, r)
-    // in pass 3): identical results, no relaxation.
-    const int32_t nTrees = (int32_t)S.seedCell.size();
-    std::vector<int32_t> cnt2(nTrees + 1, 0);
-    // all cells of each tree, ascending ORIGINAL id inside.  (Not just the cells with an initial deficit: a carve
-    // lowers other cells of the path below their flood surface, and the reference tests `deficit > EPS` against
-    // the current height when it reaches them, :154-155.)
-    int32_t* list2 = S.list2.data();
-    {   // stable counting sort of the ascending-id land list by tree, in parallel: per-worker counts per tree
-        // ([tree][worker] so the prefix runs sequentially), then every worker scatters its own contiguous share
-        const int32_t* byR = S.landByR.data();
-        const int T = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)host_threads(), 16, (int64_t)L / 65536 + 1}));
-        std::vector<int32_t> cw((size_t)nTrees * T, 0);
-        auto share = [&](int t, int64_t& b, int64_t& e) { b = (int64_t)L * t / T; e = (int64_t)L * (t + 1) / T; };
-        std::vector<std::thread> th;
-        for (int t = 0; t < T; ++t) th.emplace_back([&, t]() {
-            int64_t b, e; share(t, b, e);
-            for (int64_t k = b; k < e; ++k) { const int32_t r = root[byR[k]]; if (r >= 0) ++cw[(size_t)r * T + t]; }
-        });
-        for (auto& x : th) x.join();
-        int32_t run = 0;
-        for (int32_t tr = 0; tr < nTrees; ++tr) {
-            cnt2[tr] = run;
-            for (int t = 0; t < T; ++t) { const int32_t c = cw[(size_t)tr * T + t]; cw[(size_t)tr * T + t] = run; run += c; }
-        }
-        cnt2[nTrees] = run;
-        th.clear();
-        for (int t = 0; t < T; ++t) th.emplace_back([&, t]() {
-            int64_t b, e; share(t, b, e);
-            for (int64_t k = b; k < e; ++k) { const int32_t i = byR[k]; const int32_t r = root[i]; if (r >= 0) list2[cw[(size_t)r * T + t]++] = i; }
-        });
-        for (auto& x : th) x.join();
-    }
-    // Trees are numbered by their seed's original id, i.e. along the Fibonacci spiral: consecutive ids are spatial
-    // neighbours, so workers take contiguous chunks.  Measured on the 2-socket EPYC GPU box with the packed records and
-    // huge pages: 6 workers 199 ms, 12 -> 136, 24 -> 102, 48 -> 91 ms for the two calls of a step; 24 is the default
-    // (WO_FLOOD_THREADS overrides), which leaves room for several ranks / planets per socket.
-    auto for_trees = [&](const std::vector<int32_t>& cnt, auto body) {
-        static const int capThreads = [] { const char* e = std::getenv("WO_FLOOD_THREADS"); const int v = e ? std::atoi(e) : 0; return v >= 1 ? v : 24; }();
-        const int nt = std::max(1, std::min<int>(std::min(host_threads(), capThreads), nTrees));
-        const int64_t total = cnt[nTrees];
-        const int64_t perChunk = std::max<int64_t>(2048, total / (nt * 16));
-        std::vector<int32_t> chunkStart;
-        chunkStart.push_back(0);
-        for (int32_t t = 0, last = 0; t < nTrees; ++t)
-            if (cnt[t + 1] - cnt[last] >= perChunk) { chunkStart.push_back(t + 1); last = t + 1; }
-        if (chunkStart.back() != nTrees) chunkStart.push_back(nTrees);
-        const size_t nChunks = chunkStart.size() - 1;
-        std::atomic<size_t> next{0};
-        auto worker = [&]() {
-            for (;;) {
-                const size_t c = next.fetch_add(1);
-                if (c >= nChunks) break;
-                for (int32_t t = chunkStart[c]; t < chunkStart[c + 1]; ++t) if (cnt[t + 1] > cnt[t]) body(t);
-            }
-        };
-        if (nt == 1) { worker(); return; }
-        std::vector<std::thread> th;
-        for (int i = 0; i < nt; ++i) th.emplace_back(worker);
-        for (auto& t : th) t.join();
-    };
+    const FloodCell* st = S.state.data();
+    float* surface = S.surface.data(); int32_t* root = S.root.data();      // passes 2 and 3 stream over surface / tree id: give them compact arrays again
+    parallel_ranges(S.L, [&](int64_t b, int64_t en, int) { for (int64_t i = b; i < en; ++i) { surface[i] = st[i].surface; root[i] = st[i].root; } });
+    const int32_t nTrees = (int32_t)S.seedCell.size(); std::vector<int32_t> cnt2;
+    group_land_by_tree(S, cnt2);
     T.lap("group2");
     std::atomic<int64_t> nDeficit{0}, totLen{0};
-    const TreeCtx ctx{st, eL, surface, carveStrength, onPath, S.localIdx.data(), S.hooks.chainsMin};
-    for_trees(cnt2, [&](int32_t tree) {
+    int32_t* list2 = S.list2.data();
+    const TreeCtx ctx{st, S.eL.data(), surface, carveStrength, onPath, S.localIdx.data(), S.hooks.chainsMin};
+    for_trees(cnt2, nTrees, [&](int32_t tree) {
         static thread_local std::vector<int32_t> path;
         int64_t myLen = 0, myDef = 0;
         tree_pass23(ctx, list2 + cnt2[tree], cnt2[tree + 1] - cnt2[tree], path, myLen, myDef);
-        if (timing) { totLen += myLen; nDeficit += myDef; }
+        if (T.on) { totLen += myLen; nDeficit += myDef; }
     });
-    if (timing) std::fprintf(stderr, "[flood] pass2: %lld deficit cells in %d trees, total path length %lld\n", (long long)nDeficit.load(), nTrees, (long long)totLen.load());
+    if (T.on) std::fprintf(stderr, "[flood] pass2: %lld deficit cells in %d trees, total path length %lld\n", (long long)nDeficit.load(), nTrees, (long long)totLen.load());
     T.lap("pass2+3");
-    if (track) {
-        for (const auto& oa : *openAlt) {
-            const int32_t x = oa.first, p0 = st[x].drain, p1 = oa.second;
-            const bool untouched = !onPath[x] && std::memcmp(&eL[x], &st[x].e, 4) == 0;
-            const double h = (double)st[x].e;
-            if (!(untouched && p0 >= 0 && h > (double)eL[p0] && h > (double)eL[p1])) return false;
-        }
-    }
-    if (S.landOrder) parallel_ranges(L, [&](int64_t b, int64_t en, int) { std::memcpy(e + b, eL + b, sizeof(float) * (size_t)(en - b)); });
-    else parallel_ranges(L, [&](int64_t b, int64_t en, int) { for (int64_t i = b; i < en; ++i) e[landCell[i]] = eL[i]; });
+    if (track) for (const auto& oa : *openAlt) if (!open_parent_is_harmless(S, oa.first, oa.second)) return false;
+    write_back(e, S);
     T.lap("writeback");
     return true;
 }
@@ -1157,26 +1163,18 @@ bool flood_pass23_host(float* e, double carveStrength, FloodScratch& S, const st
 // reference's, in the same order, so its array — and with it every choice between equal keys — is the reference's.
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
-// stopLevel: the replay ends as soon as the heap's smallest key exceeds it (+inf: runs to the end); then `frontier[k]` receives the
-// entries the heap still holds for dirty landmass k, in array order, and true is returned.  See flood_landmass_pipeline.
-// prefix[k]: the cells of dirty landmass k that its own walk popped before its first tie group with a contested cell (PopLog) — they, and
-// the claims they made, are kept and they push like clean cells (dirty == 2); only the rest of the landmass is walked for real (dirty == 1).
-bool replay_dirty_landmasses(FloodScratch& S, const std::vector<uint8_t>& dirtyComp, const float* e, float stopLevel,
-                             std::vector<std::vector<FloodHeapItem>>* frontier, const std::vector<std::vector<int32_t>>* prefix) {
-    const double EPS = 1e-7;
-    FloodTimer T(S);
-    const int32_t L = S.L;
-    const int32_t* landCell = S.landCell.data();
-    const int32_t* offL = S.offL.data();
-    const int32_t* adjL = S.adjL.data();
-    float* eL = S.eL.data();
-    FloodCell* st = S.state.data();
-    S.replayDirty.resize(L);
+// An entry of the replay's heap carries "walked for real" in the top bit of its cell (the heap compares keys only): the heap loop never has
+// to look the popped cell up to know which of the two kinds it is, nor to decide what to pull in for the cells about to pop.
+constexpr int32_t REAL = INT32_MIN, CELL = INT32_MAX;
+// S.replayDirty: 1 = cell of a dirty landmass, walked for real; 2 = such a cell that belongs to its landmass's decided prefix.  The cells
+// of the dirty landmasses go back to the start state of pass 1, except what a prefix popped or claimed.  Returns the number of prefix cells.
+int64_t replay_reset_dirty(FloodScratch& S, const std::vector<uint8_t>& dirtyComp, const std::vector<std::vector<int32_t>>* prefix) {
+    float* eL = S.eL.data(); FloodCell* st = S.state.data();
+    S.replayDirty.resize(S.L);
     uint8_t* dirty = S.replayDirty.data();
-    parallel_ranges(L, [&](int64_t b, int64_t en, int) { std::memset(dirty + b, 0, (size_t)(en - b)); });
-    const int32_t nComp = (int32_t)S.compSize.size();
+    parallel_ranges(S.L, [&](int64_t b, int64_t en, int) { std::memset(dirty + b, 0, (size_t)(en - b)); });
     int64_t prefixLeft = 0;
-    for (int32_t k = 0; k < nComp; ++k) {
+    for (int32_t k = 0; k < (int32_t)S.compSize.size(); ++k) {
         if (!dirtyComp[k]) continue;
         const int32_t* cells = S.compCells.data() + S.compCellStart[k];
         const int32_t n = S.compCellStart[k + 1] - S.compCellStart[k];
@@ -1198,7 +1196,13 @@ bool replay_dirty_landmasses(FloodScratch& S, const std::vector<uint8_t>& dirtyC
             }
         });
     }
-    // children of the clean cells, in the order their claimant pushed them (adjacency order), with their keys
+    return prefixLeft;
+}
+// S.childStart / S.childItem: the children of the clean cells, in the order their claimant pushed them (adjacency order), with their keys
+void replay_child_lists(FloodScratch& S) {
+    const int32_t L = S.L;
+    const int32_t* landCell = S.landCell.data(); const int32_t* offL = S.offL.data(); const int32_t* adjL = S.adjL.data();
+    const FloodCell* st = S.state.data(); const uint8_t* dirty = S.replayDirty.data();
     S.childStart.resize((size_t)L + 1);
     int32_t* cs = S.childStart.data();
     parallel_ranges(L, [&](int64_t b, int64_t en, int) {
@@ -1208,19 +1212,10 @@ bool replay_dirty_landmasses(FloodScratch& S, const std::vector<uint8_t>& dirtyC
             cs[i + 1] = c;
         }
     });
-    {   // exclusive scan, in parallel: per-range sums, then offsets
-        const int nt = host_threads();
-        std::vector<int64_t> part(nt + 2, 0);
-        parallel_ranges(L, [&](int64_t b, int64_t en, int t) { int64_t a = 0; for (int64_t i = b; i < en; ++i) a += cs[i + 1]; part[t + 1] = a; });
-        for (int t = 1; t <= nt + 1; ++t) part[t] += part[t - 1];
-        cs[0] = 0;
-        parallel_ranges(L, [&](int64_t b, int64_t en, int t) { int64_t run = part[t]; for (int64_t i = b; i < en; ++i) { run += cs[i + 1]; cs[i + 1] = (int32_t)run; } });
-    }
+    cs[0] = 0;
+    inclusive_scan_parallel(cs + 1, L);
     S.childItem.resize((size_t)cs[L] + 1);
     FloodHeapItem* ci = S.childItem.data();
-    // An entry of this heap carries "walked for real" in the top bit of its cell (the heap compares keys only): the loop below never has
-    // to look the popped cell up to know which of the two kinds it is, nor to decide what to pull in for the cells about to pop.
-    constexpr int32_t REAL = INT32_MIN, CELL = INT32_MAX;
     parallel_ranges(L, [&](int64_t b, int64_t en, int) {
         for (int64_t i = b; i < en; ++i) {
             if (cs[i + 1] == cs[i]) continue;
@@ -1231,6 +1226,21 @@ bool replay_dirty_landmasses(FloodScratch& S, const std::vector<uint8_t>& dirtyC
             }
         }
     });
+}
+// stopLevel: the replay ends as soon as the heap's smallest key exceeds it (+inf: runs to the end); then `frontier[k]` receives the
+// entries the heap still holds for dirty landmass k, in array order, and true is returned.  See PipelineCall::replay.
+// prefix[k]: the cells of dirty landmass k that its own walk popped before its first tie group with a contested cell (PopLog) — they, and
+// the claims they made, are kept and they push like clean cells (dirty == 2); only the rest of the landmass is walked for real (dirty == 1).
+bool replay_dirty_landmasses(FloodScratch& S, const std::vector<uint8_t>& dirtyComp, float stopLevel,
+                             std::vector<std::vector<FloodHeapItem>>* frontier, const std::vector<std::vector<int32_t>>* prefix) {
+    const double EPS = 1e-7;
+    FloodTimer T(S);
+    const int32_t L = S.L;
+    const int32_t* landCell = S.landCell.data(); const int32_t* offL = S.offL.data(); const int32_t* adjL = S.adjL.data();
+    FloodCell* st = S.state.data();
+    int64_t prefixLeft = replay_reset_dirty(S, dirtyComp, prefix);
+    replay_child_lists(S);
+    const uint8_t* dirty = S.replayDirty.data(); const int32_t* cs = S.childStart.data(); const FloodHeapItem* ci = S.childItem.data();
     T.lap("replay prep");
     if (S.heapStore.size() < 4096) S.heapStore.resize(4096);
     KeyHeap heap(S.heapStore);
@@ -1294,7 +1304,6 @@ bool replay_dirty_landmasses(FloodScratch& S, const std::vector<uint8_t>& dirtyC
                            stopped ? "stopped" : "ran to the end", (long long)pops, (double)stopLevel, heap.n);
     return stopped;
 }
-}  // namespace
 
 // Pass 1 + passes 2/3, pipelined per landmass.  A landmass's trees, carve paths and fix-ups stay inside it, so its passes
 // 2/3 need only its own pass 1.  Workers take landmasses largest first; after the walk of one they resolve its contested
@@ -1302,314 +1311,351 @@ bool replay_dirty_landmasses(FloodScratch& S, const std::vector<uint8_t>& dirtyC
 // that has run out of landmasses helps.  While the largest landmass (14 % of the land on the bench planet) is still in
 // its walk, the carving of all the others is already done.  Landmasses whose walk met an equal-key decision that matters
 // are left out of the first round, re-walked inside the replay of the single heap (above) and carved in a second round.
-// On return e holds the reference's result; FloodScratch is consumed (the caller gathers again before another call).
-bool flood_landmass_pipeline(float* e, double carveStrength, FloodScratch& S, FloodTieReport& rep, int64_t& pathRedo, bool replayAllowed) {
-    const double EPS = 1e-7;
-    FloodTimer T(S);
-    const int32_t nComp = (int32_t)S.compSize.size();
-    const int32_t L = S.L;
-    rep = FloodTieReport{};
-    rep.landmasses = nComp;
-    // (stamp and onPath start at zero: flood_gather, which every caller runs first)
-    const int nt = std::min(flood_workers(std::max(nComp, 1)), std::max(1, L / 16384));    // small planets: a thread costs more than it saves
-    rep.workers = nt;
-    if ((int)S.workerHeaps.size() < nt) S.workerHeaps.resize(nt);
-    FloodCell* st = S.state.data();
-    float* eL = S.eL.data();
-    int32_t* list2 = S.list2.data();
-    constexpr int32_t BIG = 32768, CHUNK = 4096;
-    const int32_t chainsMin = S.hooks.chainsMin;
-    struct BigJob {
-        int32_t k = -1; std::vector<int32_t> cnt, chunkStart, chunkOrder; bool track = false;
-        std::atomic<int> ready{0}; std::atomic<size_t> nextChunk{0}, doneChunks{0};
-    };
-    struct Local { std::vector<Contest> contests; std::vector<std::pair<int32_t, int32_t>> alt; std::vector<int32_t> altComp; int64_t groups = 0, nested = 0, contested = 0, unresolved = 0; float maxLevel = -INFINITY; bool noLevel = false; };
-    std::vector<Local> loc(nt);
-    std::vector<uint8_t> dirty(std::max(nComp, 1), 0);
-    const int forceDirty = S.hooks.forceDirty;     // test hook: treat this landmass (by rank in size) as undecided
-    // the pops of a landmass with a contested cell up to its first such tie group (PopLog): bare pushes in the replay, like a decided landmass
-    std::vector<std::vector<int32_t>> prefix(S.hooks.replayPrefix ? std::max(nComp, 1) : 0);
-    // One round over a list of landmasses.  walked: pass 1 of these landmasses is already there (the replay's).
-    const auto tRound0 = std::chrono::steady_clock::now();
-    auto run_round = [&](const std::vector<int32_t>& list, bool walked) {
-        const int32_t nList = (int32_t)list.size();
-        int32_t nBig = 0;
-        while (nBig < nList && S.compSize[list[nBig]] >= BIG) ++nBig;             // lists are in descending size
-        std::vector<BigJob> big(nBig);
-        std::atomic<int32_t> next{0}, bigLeft{nBig};
-        auto run_chunks = [&](BigJob& J, std::vector<int32_t>& path) {
-            const TreeCtx ctx{st, eL, nullptr, carveStrength, J.track ? S.onPath.data() : nullptr, S.localIdx.data(), chainsMin};
-            const size_t nChunks = J.chunkStart.size() - 1;
-            const int32_t base = S.compCellStart[J.k];
-            for (;;) {
-                const size_t cq = J.nextChunk.fetch_add(1);
-                if (cq >= nChunks) break;
-                const size_t c = (size_t)J.chunkOrder[cq];
-                int64_t a = 0, b = 0;
-                for (int32_t t = J.chunkStart[c]; t < J.chunkStart[c + 1]; ++t)
-                    if (J.cnt[t + 1] > J.cnt[t]) {
-                        const int32_t nT = J.cnt[t + 1] - J.cnt[t];
-                        const bool timed = T.on && nT >= 16384;
-                        const auto tt0 = timed ? std::chrono::steady_clock::now() : tRound0;
-                        const int64_t a0 = a, b0 = b;
-                        tree_pass23(ctx, list2 + base + J.cnt[t], nT, path, a, b);
-                        if (timed) {
-                            const auto now = std::chrono::steady_clock::now();
-                            std::fprintf(stderr, "[flood] landmass %d: tree of %d cells, passes 2+3 %.2f ms (%lld deficit cells, %lld path steps), done at %.1f ms\n", J.k, nT,
-                                         std::chrono::duration<double, std::milli>(now - tt0).count(), (long long)(b - b0), (long long)(a - a0), std::chrono::duration<double, std::milli>(now - tRound0).count());
-                        }
-                    }
-                if (J.doneChunks.fetch_add(1) + 1 == nChunks) bigLeft.fetch_sub(1);
-            }
-        };
-        // The walk of the largest landmass is the critical path of the call, one thread for 27-40 ms, and its working set (~20 MB) lives in the
-        // last-level cache of the core it runs on.  That thread stays on the CPU it is on and every other worker of the round keeps off the
-        // CPUs that share its L3 (an EPYC CCD) until it is done (WO_FLOOD_PIN=0: nobody's affinity is touched).
+constexpr int32_t BIG = 32768, CHUNK = 4096;        // a landmass of at least BIG cells hands its trees out in chunks of at least CHUNK cells
+struct BigJob {
+    int32_t k = -1; std::vector<int32_t> cnt, chunkStart, chunkOrder; bool track = false;
+    std::atomic<int> ready{0}; std::atomic<size_t> nextChunk{0}, doneChunks{0};
+};
+// One round over a list of landmasses (descending size).  walked: pass 1 of these landmasses is already there (the replay's).
+struct Round {
+    const std::vector<int32_t>& list; const bool walked; const int32_t nBig;
+    std::vector<BigJob> big; std::atomic<int32_t> next{0}, bigLeft;     // big: the first nBig of the list
+    bool pinning = false; std::atomic<int> reservedGroup{-1};     // WO_FLOOD_PIN: see PipelineCall::place_worker
+    Round(const std::vector<int32_t>& l, bool w, int32_t nb) : list(l), walked(w), nBig(nb), big(nb), bigLeft(nb) {}
+};
+// what one worker's walks found
+struct WorkerFindings { std::vector<Contest> contests; std::vector<std::pair<int32_t, int32_t>> alt; std::vector<int32_t> altComp; int64_t groups = 0, nested = 0, contested = 0, unresolved = 0; float maxLevel = -INFINITY; bool noLevel = false; };
+struct PipelineCall {
+    FloodScratch& S; const double carveStrength; FloodTieReport& rep; FloodTimer T; int nt;
+    std::vector<WorkerFindings> loc;
+    std::vector<uint8_t> dirty;                          // per landmass: undecided, goes through the replay
+    std::vector<std::vector<int32_t>> prefix;            // the pops of a landmass with a contested cell up to its first such tie group (PopLog): bare pushes in the replay, like a decided landmass
+    Clock::time_point tRound0;
+    static double ms_since(Clock::time_point t0) { return ms_between(t0, Clock::now()); }
+    PipelineCall(double cs, FloodScratch& S_, FloodTieReport& rep_) : S(S_), carveStrength(cs), rep(rep_), T(S_) {
+        const int32_t nComp = (int32_t)S.compSize.size();
+        // (stamp and onPath start at zero: flood_gather, which every caller runs first)
+        nt = std::min(flood_workers(std::max(nComp, 1)), std::max(1, S.L / 16384));    // small planets: a thread costs more than it saves
+        rep = FloodTieReport{};
+        rep.landmasses = nComp; rep.workers = nt;
+        if ((int)S.workerHeaps.size() < nt) S.workerHeaps.resize(nt);
+        loc.resize(nt); dirty.assign(std::max(nComp, 1), 0); prefix.resize(S.hooks.replayPrefix ? std::max(nComp, 1) : 0);
+        tRound0 = Clock::now();
+    }
+    TreeCtx tree_ctx(bool track) const { return TreeCtx{S.state.data(), S.eL.data(), nullptr, carveStrength, track ? S.onPath.data() : nullptr, S.localIdx.data(), S.hooks.chainsMin}; }
+    // The walk of the largest landmass is the critical path of the call, one thread for 27-40 ms, and its working set (~20 MB) lives in the
+    // last-level cache of the core it runs on.  That thread stays on the CPU it is on and every other worker of the round keeps off the
+    // CPUs that share its L3 (an EPYC CCD) until it is done (WO_FLOOD_PIN=0: nobody's affinity is touched).
+    void place_worker(Round& R, int32_t q, AffinityScope& affinity, bool& placed) {
         const CpuGroups& cpus = CpuGroups::get();
-        const bool pinning = S.hooks.pin && !walked && nBig > 0 && !cpus.groups.empty() && nt > 1;
-        std::atomic<int> reservedGroup{-1};
-        auto worker = [&](int w) {
-            Local& me = loc[w];
-            std::vector<int32_t> path, cnt;
-            static thread_local PopLog popLog;
-            PopLog* const log = prefix.empty() ? nullptr : &popLog;
-            AffinityScope affinity;
-            bool placed = false;
-            for (;;) {
-                const int32_t q = next.fetch_add(1);
-                if (q >= nList) break;
-                const int32_t k = list[q];
-                bool track = false, undecided = false;
-                if (pinning && !placed) {
-                    if (q == 0) {
-                        const int cpu = sched_getcpu();
-                        const int g = cpu >= 0 && cpu < (int)cpus.groupOf.size() ? cpus.groupOf[cpu] : -1;
-                        if (g >= 0 && affinity.only(cpu)) reservedGroup.store(g, std::memory_order_release);
-                        else reservedGroup.store(-2, std::memory_order_release);
-                        if (T.on) std::fprintf(stderr, "[flood] the largest walk stays on cpu %d; the other workers keep off its L3 (group %d of %zu)\n", cpu, g, cpus.groups.size());
-                        placed = true;
-                    } else {
-                        const int g = reservedGroup.load(std::memory_order_acquire);
-                        if (g >= 0) { (void)affinity.all_but_group(cpus, g); placed = true; }
-                        else if (g == -2) placed = true;
-                    }
-                }
-                if (!walked) {
-                    // --- pass 1 of landmass k
-                    me.contests.clear();
-                    const auto tw0 = std::chrono::steady_clock::now();
-                    WalkStats ws;
-                    if (T.on && q == 0) walk_landmass_with_stats(S, S.compSeeds.data() + S.compSeedStart[k], S.compSeedStart[k + 1] - S.compSeedStart[k], S.compSize[k], S.workerHeaps[w], me.contests, me.groups, me.nested, ws, log);
-                    else walk_landmass(S, S.compSeeds.data() + S.compSeedStart[k], S.compSeedStart[k + 1] - S.compSeedStart[k], S.compSize[k], S.workerHeaps[w], me.contests, me.groups, me.nested, log);
-                    if (log && (!me.contests.empty() || q == forceDirty)) {
-                        // (the test hook's landmass has no contested cell: every cut of its pops is as good as any; WO_FLOOD_FORCE_PREFIX permille of them)
-                        const int32_t len = q == forceDirty && me.contests.empty() ? (int32_t)((int64_t)log->n * S.hooks.forcePrefixPermille / 1000) : log->prefix;
-                        prefix[k].assign(log->cells.begin(), log->cells.begin() + len);
-                        if (T.on) std::fprintf(stderr, "[flood] landmass %d (%d cells): %d pops before its first tie group with a contested cell\n", k, S.compSize[k], len);
-                    }
-                    // (measured and dropped in round 3: a bucket queue — 2^16 buckets of width 2^-14 behind a two-level bitmap — instead of the
-                    // binary heap for the walks, which do not depend on the order of equal keys: 83-130 ms against 45-60 ms for this landmass in
-                    // the build container; the heap of one landmass stays in cache, the buckets' vectors do not)
-                    if (T.on && q == 0) std::fprintf(stderr, "[flood] walk of the largest landmass (%d cells): %.1f ms; heap mean %lld max %lld entries, %lld pops below the level reached, %lld raised keys, %d seeds\n", S.compSize[k], std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count(),
-                                                     (long long)(ws.heapSum / std::max<int64_t>(ws.pops, 1)), (long long)ws.heapMax, (long long)ws.descending, (long long)ws.raised, S.compSeedStart[k + 1] - S.compSeedStart[k]);
-                    const size_t alt0 = me.alt.size();
-                    for (const Contest& ct : me.contests) {
-                        ++me.contested;
-                        bool open = false;
-                        if (ct.other < 0) me.noLevel = true; else if (ct.level > me.maxLevel) me.maxLevel = ct.level;
-                        if (ct.other >= 0) {
-                            const FloodCell& x = st[ct.cell];
-                            const float kx = (float)((double)x.surface + cell_noise(S.landCell[ct.cell]));
-                            const double limO = (double)st[ct.other].surface + EPS;
-                            const float altSurface = ((double)x.e < limO) ? (float)limO : x.e;
-                            const bool sameSurface = std::memcmp(&altSurface, &x.surface, 4) == 0;
-                            const bool ordered = x.drain >= 0 && st[x.drain].surface < x.surface && st[ct.other].surface < x.surface;
-                            open = kx > ct.level && sameSurface && ordered;
-                            if (!open && T.on) std::fprintf(stderr, "[flood] undecided contested cell %d (other %d): %s%s%s level %.9g key %.9g surface %.9g / %.9g e %.9g\n", S.landCell[ct.cell], S.landCell[ct.other],
-                                                            kx > ct.level ? "" : "cascades-inside-the-group ", sameSurface ? "" : "surface-differs ", ordered ? "" : "pass3-order ", (double)ct.level, (double)kx,
-                                                            (double)x.surface, (double)altSurface, (double)x.e);
-                        }
-                        if (open) { me.alt.push_back({ct.cell, ct.other}); me.altComp.push_back(k); track = true; }
-                        else { ++me.unresolved; undecided = true; }
-                    }
-                    if (q == forceDirty) undecided = true;
-                    if (undecided) { me.alt.resize(alt0); me.altComp.resize(alt0); dirty[k] = 1; }
-                }
-                // --- its cells grouped by tree (stable: ascending original id inside a tree); an undecided landmass waits for the replay
-                const bool isBig = q < nBig;
-                const int32_t base = S.compCellStart[k], n = S.compCellStart[k + 1] - base, nTrees = S.compSeedStart[k + 1] - S.compSeedStart[k];
-                std::vector<int32_t>& c = isBig ? big[q].cnt : cnt;
-                if (undecided) {
-                    if (isBig) { BigJob& J = big[q]; J.k = k; J.chunkStart.assign(1, 0); J.ready.store(1, std::memory_order_release); bigLeft.fetch_sub(1); }
-                    continue;
-                }
-                const int32_t* cells = S.compCells.data() + base;
-                c.assign((size_t)nTrees + 1, 0);
-                for (int32_t qq = 0; qq < n; ++qq) ++c[S.seedLocal[st[cells[qq]].root] + 1];
-                for (int32_t t = 0; t < nTrees; ++t) c[t + 1] += c[t];
-                {
-                    static thread_local std::vector<int32_t> pos;
-                    pos.assign(c.begin(), c.end() - 1);
-                    for (int32_t qq = 0; qq < n; ++qq) { const int32_t i = cells[qq]; list2[base + pos[S.seedLocal[st[i].root]]++] = i; }
-                }
-                if (T.on && q == 0) std::fprintf(stderr, "[flood] largest landmass: walk + contests + tree lists done at %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tRound0).count());
-                if (isBig) {                                  // hand the trees out in chunks
-                    BigJob& J = big[q];
-                    J.k = k; J.track = track;
-                    J.chunkStart.clear(); J.chunkStart.push_back(0);
-                    for (int32_t t = 0, last = 0; t < nTrees; ++t) if (c[t + 1] - c[last] >= CHUNK) { J.chunkStart.push_back(t + 1); last = t + 1; }
-                    if (J.chunkStart.back() != nTrees) J.chunkStart.push_back(nTrees);
-                    // biggest chunks first: the largest tree (41 k of this landmass's 402 k cells on the bench planet) is the longest single job of the tail
-                    J.chunkOrder.resize(J.chunkStart.size() - 1);
-                    for (size_t x = 0; x < J.chunkOrder.size(); ++x) J.chunkOrder[x] = (int32_t)x;
-                    std::stable_sort(J.chunkOrder.begin(), J.chunkOrder.end(), [&](int32_t x, int32_t y) { return c[J.chunkStart[x + 1]] - c[J.chunkStart[x]] > c[J.chunkStart[y + 1]] - c[J.chunkStart[y]]; });
-                    J.ready.store(1, std::memory_order_release);
-                    run_chunks(J, path);
-                } else {
-                    const TreeCtx ctx{st, eL, nullptr, carveStrength, track ? S.onPath.data() : nullptr, S.localIdx.data(), chainsMin};
-                    int64_t a = 0, b = 0;
-                    for (int32_t t = 0; t < nTrees; ++t) if (c[t + 1] > c[t]) tree_pass23(ctx, list2 + base + c[t], c[t + 1] - c[t], path, a, b);
-                }
+        if (q == 0) {
+            const int cpu = sched_getcpu();
+            const int g = cpu >= 0 && cpu < (int)cpus.groupOf.size() ? cpus.groupOf[cpu] : -1;
+            R.reservedGroup.store(g >= 0 && affinity.only(cpu) ? g : -2, std::memory_order_release);
+            if (T.on) std::fprintf(stderr, "[flood] the largest walk stays on cpu %d; the other workers keep off its L3 (group %d of %zu)\n", cpu, g, cpus.groups.size());
+            placed = true;
+        } else {
+            const int g = R.reservedGroup.load(std::memory_order_acquire);
+            if (g >= 0) { (void)affinity.all_but_group(cpus, g); placed = true; }
+            else if (g == -2) placed = true;
+        }
+    }
+    // Pass 1 of landmass k (q: its rank in size) and the judgement of its contests.  track: it has open parents, its carve marks its
+    // paths.  Returns true when it is undecided (dirty[k]): it waits for the replay.
+    bool walk_and_judge(int w, int32_t q, int32_t k, bool& track) {
+        WorkerFindings& me = loc[w];
+        static thread_local PopLog popLog;
+        PopLog* const log = prefix.empty() ? nullptr : &popLog;
+        const int32_t forceDirty = S.hooks.forceDirty;     // test hook: treat this landmass (by rank in size) as undecided
+        const bool largest = T.on && q == 0;
+        me.contests.clear();
+        const auto tw0 = Clock::now();
+        WalkStats ws;
+        Walk walk = seeded_walk(S, k, S.workerHeaps[w], me.contests, me.groups, me.nested);
+        walk.log = log; walk.stats = largest ? &ws : nullptr;
+        walk_landmass(S, walk);
+        if (log && (!me.contests.empty() || q == forceDirty)) {
+            // (the test hook's landmass has no contested cell: every cut of its pops is as good as any; WO_FLOOD_FORCE_PREFIX permille of them)
+            const int32_t len = q == forceDirty && me.contests.empty() ? (int32_t)((int64_t)log->n * S.hooks.forcePrefixPermille / 1000) : log->prefix;
+            prefix[k].assign(log->cells.begin(), log->cells.begin() + len);
+            if (T.on) std::fprintf(stderr, "[flood] landmass %d (%d cells): %d pops before its first tie group with a contested cell\n", k, S.compSize[k], len);
+        }
+        if (largest) std::fprintf(stderr, "[flood] walk of the largest landmass (%d cells): %.1f ms; heap mean %lld max %lld entries, %lld pops below the level reached, %lld raised keys, %d seeds\n", S.compSize[k], ms_since(tw0),
+                                  (long long)(ws.heapSum / std::max<int64_t>(ws.pops, 1)), (long long)ws.heapMax, (long long)ws.descending, (long long)ws.raised, walk.nSeeds);
+        // Open parents count per landmass: an undecided one withdraws those it has reported (alt0; the replay walks it again and leaves nothing
+        // open).  The two-phase route counts every one it sees (flood_pass1_landmasses): on tie-heavy input the two figures differ, on purpose.
+        const size_t alt0 = me.alt.size();
+        bool undecided = false;
+        for (const Contest& ct : me.contests) {
+            ++me.contested;
+            bool open = false;
+            if (ct.other < 0) me.noLevel = true;
+            else {
+                if (ct.level > me.maxLevel) me.maxLevel = ct.level;
+                const ContestJudgement j = judge_contest(S, ct);
+                open = j.open();
+                if (!open && T.on) std::fprintf(stderr, "[flood] undecided contested cell %d (other %d): %s%s%s level %.9g key %.9g surface %.9g / %.9g e %.9g\n", S.landCell[ct.cell], S.landCell[ct.other],
+                                                j.aboveGroup ? "" : "cascades-inside-the-group ", j.sameSurface ? "" : "surface-differs ", j.ordered ? "" : "pass3-order ", (double)ct.level, (double)j.kx,
+                                                (double)S.state[ct.cell].surface, (double)j.altSurface, (double)S.state[ct.cell].e);
             }
-            // --- no landmass left to start: help with the big ones until all of them are through
-            while (bigLeft.load() > 0) {
-                bool did = false;
-                for (int32_t q = 0; q < nBig; ++q) {
-                    BigJob& J = big[q];
-                    if (J.ready.load(std::memory_order_acquire) && J.nextChunk.load() < J.chunkStart.size() - 1) { run_chunks(J, path); did = true; }
+            if (open) { me.alt.push_back({ct.cell, ct.other}); me.altComp.push_back(k); track = true; }
+            else { ++me.unresolved; undecided = true; }
+        }
+        if (q == forceDirty) undecided = true;
+        if (undecided) { me.alt.resize(alt0); me.altComp.resize(alt0); dirty[k] = 1; }
+        return undecided;
+    }
+    // The cells of landmass k grouped by tree into its stretch of S.list2 (tree t: c[t] .. c[t + 1]); stable, so ascending original id inside a tree
+    void group_by_tree(int32_t k, std::vector<int32_t>& c) {
+        const FloodCell* st = S.state.data(); int32_t* list2 = S.list2.data();
+        const int32_t base = S.compCellStart[k], n = S.compCellStart[k + 1] - base, nTrees = S.compSeedStart[k + 1] - S.compSeedStart[k];
+        const int32_t* cells = S.compCells.data() + base;
+        c.assign((size_t)nTrees + 1, 0);
+        for (int32_t qq = 0; qq < n; ++qq) ++c[S.seedLocal[st[cells[qq]].root] + 1];
+        for (int32_t t = 0; t < nTrees; ++t) c[t + 1] += c[t];
+        static thread_local std::vector<int32_t> pos;
+        pos.assign(c.begin(), c.end() - 1);
+        for (int32_t qq = 0; qq < n; ++qq) { const int32_t i = cells[qq]; list2[base + pos[S.seedLocal[st[i].root]]++] = i; }
+    }
+    // A big landmass (its tree offsets are in J.cnt) hands its trees out in chunks, biggest chunks first: the largest tree (41 k of the
+    // largest landmass's 402 k cells on the bench planet) is the longest single job of the tail
+    void publish_big_job(BigJob& J, int32_t k, bool track) {
+        const std::vector<int32_t>& c = J.cnt; J.k = k; J.track = track;
+        cut_chunks(c, S.compSeedStart[k + 1] - S.compSeedStart[k], CHUNK, J.chunkStart);
+        J.chunkOrder.resize(J.chunkStart.size() - 1);
+        for (size_t x = 0; x < J.chunkOrder.size(); ++x) J.chunkOrder[x] = (int32_t)x;
+        std::stable_sort(J.chunkOrder.begin(), J.chunkOrder.end(), [&](int32_t x, int32_t y) { return c[J.chunkStart[x + 1]] - c[J.chunkStart[x]] > c[J.chunkStart[y + 1]] - c[J.chunkStart[y]]; });
+        J.ready.store(1, std::memory_order_release);
+    }
+    void run_chunks(Round& R, BigJob& J, std::vector<int32_t>& path) {
+        const TreeCtx ctx = tree_ctx(J.track);
+        const size_t nChunks = J.chunkStart.size() - 1;
+        int32_t* trees = S.list2.data() + S.compCellStart[J.k];
+        for (;;) {
+            const size_t cq = J.nextChunk.fetch_add(1);
+            if (cq >= nChunks) break;
+            const size_t c = (size_t)J.chunkOrder[cq];
+            int64_t a = 0, b = 0;
+            for (int32_t t = J.chunkStart[c]; t < J.chunkStart[c + 1]; ++t)
+                if (J.cnt[t + 1] > J.cnt[t]) {
+                    const int32_t nT = J.cnt[t + 1] - J.cnt[t];
+                    const bool timed = T.on && nT >= 16384;
+                    const auto tt0 = timed ? Clock::now() : tRound0;
+                    const int64_t a0 = a, b0 = b;
+                    tree_pass23(ctx, trees + J.cnt[t], nT, path, a, b);
+                    if (timed) std::fprintf(stderr, "[flood] landmass %d: tree of %d cells, passes 2+3 %.2f ms (%lld deficit cells, %lld path steps), done at %.1f ms\n", J.k, nT,
+                                            ms_since(tt0), (long long)(b - b0), (long long)(a - a0), ms_since(tRound0));
                 }
-                if (!did) std::this_thread::sleep_for(std::chrono::microseconds(25));      // not a busy wait: the walk of the largest landmass is the critical path and may share a core
+            if (J.doneChunks.fetch_add(1) + 1 == nChunks) R.bigLeft.fetch_sub(1);
+        }
+    }
+    // no landmass left to start: help with the big ones until all of them are through
+    void help_until_done(Round& R, std::vector<int32_t>& path) {
+        while (R.bigLeft.load() > 0) {
+            bool did = false;
+            for (BigJob& J : R.big)
+                if (J.ready.load(std::memory_order_acquire) && J.nextChunk.load() < J.chunkStart.size() - 1) { run_chunks(R, J, path); did = true; }
+            if (!did) std::this_thread::sleep_for(std::chrono::microseconds(25));      // not a busy wait: the walk of the largest landmass is the critical path and may share a core
+        }
+    }
+    void worker(Round& R, int w) {
+        std::vector<int32_t> path, cnt;
+        AffinityScope affinity; bool placed = false;
+        for (;;) {
+            const int32_t q = R.next.fetch_add(1);
+            if (q >= (int32_t)R.list.size()) break;
+            const int32_t k = R.list[q];
+            if (R.pinning && !placed) place_worker(R, q, affinity, placed);
+            bool track = false;
+            const bool undecided = !R.walked && walk_and_judge(w, q, k, track);
+            const bool isBig = q < R.nBig;
+            if (undecided) {                                  // waits for the replay
+                if (isBig) { BigJob& J = R.big[q]; J.k = k; J.chunkStart.assign(1, 0); J.ready.store(1, std::memory_order_release); R.bigLeft.fetch_sub(1); }
+                continue;
             }
-        };
+            std::vector<int32_t>& c = isBig ? R.big[q].cnt : cnt;
+            group_by_tree(k, c);
+            if (T.on && q == 0) std::fprintf(stderr, "[flood] largest landmass: walk + contests + tree lists done at %.1f ms\n", ms_since(tRound0));
+            if (isBig) { publish_big_job(R.big[q], k, track); run_chunks(R, R.big[q], path); }
+            else {
+                const TreeCtx ctx = tree_ctx(track);
+                int32_t* trees = S.list2.data() + S.compCellStart[k]; int64_t a = 0, b = 0;
+                for (size_t t = 0; t + 1 < c.size(); ++t) if (c[t + 1] > c[t]) tree_pass23(ctx, trees + c[t], c[t + 1] - c[t], path, a, b);
+            }
+        }
+        help_until_done(R, path);
+    }
+    void run_round(const std::vector<int32_t>& list, bool walked) {
+        const int32_t nList = (int32_t)list.size(); int32_t nBig = 0;
+        while (nBig < nList && S.compSize[list[nBig]] >= BIG) ++nBig;             // lists are in descending size
+        Round R(list, walked, nBig);
+        R.pinning = S.hooks.pin && !walked && nBig > 0 && nt > 1 && !CpuGroups::get().groups.empty();
         const int use = std::min(nt, std::max(1, nList));
-        if (T.on) std::fprintf(stderr, "[flood] round setup done at %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tRound0).count());
-        if (use == 1 && nBig == 0) worker(0);
+        if (T.on) std::fprintf(stderr, "[flood] round setup done at %.1f ms\n", ms_since(tRound0));
+        if (use == 1 && nBig == 0) worker(R, 0);
         else {
             const int th_n = nBig > 0 ? nt : use;                  // chunks of a big landmass are worth every worker
             // on the persistent host workers (host_util.h: HostPool; threads of its own when the pool is busy with another planet)
-            parallel_ranges((int64_t)th_n, [&](int64_t b, int64_t en, int) { for (int64_t w = b; w < en; ++w) worker((int)w); }, 1);
+            parallel_ranges((int64_t)th_n, [&](int64_t b, int64_t en, int) { for (int64_t w = b; w < en; ++w) worker(R, (int)w); }, 1);
         }
-        if (T.on) std::fprintf(stderr, "[flood] round joined at %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tRound0).count());
-    };
-    std::vector<int32_t> all(nComp);
-    for (int32_t k = 0; k < nComp; ++k) all[k] = k;
-    run_round(all, false);
-    T.lap("pipeline");
-    // open parents (see flood_pass23_host): the elevations must not depend on the choice; a landmass where they do is undecided after all
-    for (const Local& l : loc)
-        for (size_t a = 0; a < l.alt.size(); ++a) {
-            const int32_t x = l.alt[a].first, p0 = st[x].drain, p1 = l.alt[a].second;
-            const bool untouched = !S.onPath[x] && std::memcmp(&eL[x], &st[x].e, 4) == 0;
-            const double h = (double)st[x].e;
-            if (!(untouched && p0 >= 0 && h > (double)eL[p0] && h > (double)eL[p1])) { if (!dirty[l.altComp[a]]) { dirty[l.altComp[a]] = 1; ++pathRedo; } }
-        }
-    for (const Local& l : loc) { rep.groups += l.groups; rep.nested += l.nested; rep.contested += l.contested; rep.unresolved += l.unresolved; rep.openParents += (int64_t)l.alt.size(); }
-    std::vector<int32_t> redo;
-    for (int32_t k = 0; k < nComp; ++k) if (dirty[k]) redo.push_back(k);
-    if (!redo.empty()) {
-        // A replay is going to run.  A landmass that is otherwise decided but holds an open parent x (claimants p0, p1 with equal
-        // keys) would push x when the walk's claimant p0 pops; the reference may push it when p1 pops — same result for the
-        // landmass, but a different heap array from then on, i.e. possibly a different choice between equal keys elsewhere.
-        // Such landmasses are walked for real inside the replay as well (they are rare and the replay's cost is the bare heap's).
-        bool added = false;
-        for (const Local& l : loc) for (int32_t k : l.altComp) if (!dirty[k]) { dirty[k] = 1; added = true; }
-        if (added) { redo.clear(); for (int32_t k = 0; k < nComp; ++k) if (dirty[k]) redo.push_back(k); }
+        if (T.on) std::fprintf(stderr, "[flood] round joined at %.1f ms\n", ms_since(tRound0));
     }
+    // After round 1.  Open parents (open_parent_is_harmless): a landmass where the elevations depend on the choice is undecided after all.
+    void recheck_open_parents(int64_t& pathRedo) {
+        for (const WorkerFindings& l : loc)
+            for (size_t a = 0; a < l.alt.size(); ++a)
+                if (!open_parent_is_harmless(S, l.alt[a].first, l.alt[a].second) && !dirty[l.altComp[a]]) { dirty[l.altComp[a]] = 1; ++pathRedo; }
+        for (const WorkerFindings& l : loc) { rep.groups += l.groups; rep.nested += l.nested; rep.contested += l.contested; rep.unresolved += l.unresolved; rep.openParents += (int64_t)l.alt.size(); }
+    }
+    // The landmasses that go through the replay, if any does.  A landmass that is otherwise decided but holds an open parent x (claimants
+    // p0, p1 with equal keys) would push x when the walk's claimant p0 pops; the reference may push it when p1 pops — same result for the
+    // landmass, but a different heap array from then on, i.e. possibly a different choice between equal keys elsewhere.
+    // Such landmasses are walked for real inside the replay as well (they are rare and the replay's cost is the bare heap's).
+    std::vector<int32_t> landmasses_to_replay() {
+        if (std::find(dirty.begin(), dirty.end(), 1) != dirty.end()) for (const WorkerFindings& l : loc) for (int32_t k : l.altComp) dirty[k] = 1;
+        std::vector<int32_t> redo;
+        for (int32_t k = 0; k < (int32_t)S.compSize.size(); ++k) if (dirty[k]) redo.push_back(k);
+        return redo;
+    }
+    // The replay has to reproduce the reference's heap only up to the last equal-key decision that matters: every contested cell of
+    // the first round (open parents included: they change the array) belongs to a tie group, and once the heap's smallest key has
+    // passed the highest of those groups' levels no decision is left that the landmass walks could not vouch for themselves.
+    float replay_stop_level() const {
+        float stopLevel = -INFINITY;
+        bool toTheEnd = S.hooks.forceDirty >= 0;             // (the test hook has no level: its landmass is replayed in full)
+        for (const WorkerFindings& l : loc) { if (l.noLevel) toTheEnd = true; if (l.maxLevel > stopLevel) stopLevel = l.maxLevel; }
+        if (toTheEnd) stopLevel = INFINITY;
+        return S.hooks.hasReplayStop ? S.hooks.replayStop : stopLevel;      // (test hook)
+    }
+    // Pass 1 of the undecided landmasses.  From the stop level each goes on alone, on a queue of its own seeded with the entries the single
+    // heap held for it — concurrently, with the tie bookkeeping of a first-round walk; should that meet a contested cell after all (the
+    // history below the level may differ from the first round's), the replay is run again, to the end.
+    void replay(const std::vector<int32_t>& redo) {
+        const float stopLevel = replay_stop_level();
+        const std::vector<std::vector<int32_t>>* pre = prefix.empty() ? nullptr : &prefix;
+        std::vector<std::vector<FloodHeapItem>> frontier(S.compSize.size());
+        if (!replay_dirty_landmasses(S, dirty, stopLevel, &frontier, pre)) return;
+        std::atomic<int> contestedAgain{0};
+        const FloodCell* st = S.state.data(); uint8_t* seen = S.seen.data(); int32_t* stamp = S.stamp.data();
+        parallel_ranges((int64_t)redo.size(), [&](int64_t b, int64_t en, int) {
+            for (int64_t q = b; q < en; ++q) {
+                const int32_t k = redo[q];
+                const int32_t* cells = S.compCells.data() + S.compCellStart[k];
+                const int32_t n = S.compCellStart[k + 1] - S.compCellStart[k];
+                for (int32_t x = 0; x < n; ++x) { const int32_t i = cells[x]; seen[i] = st[i].drain != UNVISITED; stamp[i] = 0; }
+                static thread_local hvec<FloodHeapItem> store;
+                std::vector<Contest> contests; int64_t g = 0, nn = 0;
+                walk_landmass(S, Walk{nullptr, 0, frontier[k].data(), frontier[k].size(), n, &store, &contests, &g, &nn});
+                if (!contests.empty()) contestedAgain.fetch_add(1);
+            }
+        }, 1);
+        T.lap("resumed");
+        if (T.on) std::fprintf(stderr, "[flood] %zu landmasses resumed on their own queues above level %.9g%s\n", redo.size(), (double)stopLevel, contestedAgain.load() ? "; a contested cell turned up: full replay" : "");
+        if (contestedAgain.load()) replay_dirty_landmasses(S, dirty, INFINITY, nullptr, pre);
+    }
+};
+// On return e holds the reference's result; FloodScratch's per-call arrays are consumed (flood_gather() before the next use).
+// replayAllowed == false: a call that would need the replay returns false instead and leaves e untouched (the caller has a
+// better heap to replay: flood_host_passes_exchange)
+bool flood_landmass_pipeline(float* e, double carveStrength, FloodScratch& S, FloodTieReport& rep, int64_t& pathRedo, bool replayAllowed = true) {
+    PipelineCall P(carveStrength, S, rep);
+    std::vector<int32_t> all(S.compSize.size());
+    for (size_t k = 0; k < all.size(); ++k) all[k] = (int32_t)k;
+    P.run_round(all, false);
+    P.T.lap("pipeline");
+    P.recheck_open_parents(pathRedo);
+    const std::vector<int32_t> redo = P.landmasses_to_replay();
     rep.replayed = (int32_t)redo.size();
     if (!redo.empty() && !replayAllowed) return false;
-    if (T.on) std::fprintf(stderr, "[flood] landmasses %d, workers %d, tie groups %lld (nested %lld), contested %lld, open parents %lld, undecided %lld -> %d landmasses through the replay\n",
-                           rep.landmasses, rep.workers, (long long)rep.groups, (long long)rep.nested, (long long)rep.contested, (long long)rep.openParents, (long long)rep.unresolved, rep.replayed);
+    if (P.T.on) std::fprintf(stderr, "[flood] landmasses %d, workers %d, tie groups %lld (nested %lld), contested %lld, open parents %lld, undecided %lld -> %d landmasses through the replay\n",
+                             rep.landmasses, rep.workers, (long long)rep.groups, (long long)rep.nested, (long long)rep.contested, (long long)rep.openParents, (long long)rep.unresolved, rep.replayed);
     if (!redo.empty()) {
-        // The replay has to reproduce the reference's heap only up to the last equal-key decision that matters: every contested cell of
-        // the first round (open parents included: they change the array) belongs to a tie group, and once the heap's smallest key has
-        // passed the highest of those groups' levels no decision is left that the landmass walks could not vouch for themselves.  From
-        // there each undecided landmass goes on alone, on a queue of its own seeded with the entries the single heap held for it —
-        // concurrently, with the tie bookkeeping of a first-round walk; should that meet a contested cell after all (the history below
-        // the level may differ from the first round's), the replay is run again, to the end.
-        float stopLevel = -INFINITY;
-        bool toTheEnd = forceDirty >= 0;                     // (the test hook has no level: its landmass is replayed in full)
-        for (const Local& l : loc) { if (l.noLevel) toTheEnd = true; if (l.maxLevel > stopLevel) stopLevel = l.maxLevel; }
-        if (toTheEnd) stopLevel = INFINITY;
-        if (S.hooks.hasReplayStop) stopLevel = S.hooks.replayStop;      // test hook
-        std::vector<std::vector<FloodHeapItem>> frontier(nComp);
-        if (replay_dirty_landmasses(S, dirty, e, stopLevel, &frontier, prefix.empty() ? nullptr : &prefix)) {
-            std::atomic<int> contestedAgain{0};
-            uint8_t* seen = S.seen.data();
-            int32_t* stamp = S.stamp.data();
-            parallel_ranges((int64_t)redo.size(), [&](int64_t b, int64_t en, int) {
-                for (int64_t q = b; q < en; ++q) {
-                    const int32_t k = redo[q];
-                    const int32_t* cells = S.compCells.data() + S.compCellStart[k];
-                    const int32_t n = S.compCellStart[k + 1] - S.compCellStart[k];
-                    for (int32_t x = 0; x < n; ++x) { const int32_t i = cells[x]; seen[i] = st[i].drain != UNVISITED; stamp[i] = 0; }
-                    static thread_local hvec<FloodHeapItem> store;
-                    std::vector<Contest> contests; int64_t g = 0, nn = 0;
-                    walk_landmass_resume(S, frontier[k], n, store, contests, g, nn);
-                    if (!contests.empty()) contestedAgain.fetch_add(1);
-                }
-            }, 1);
-            T.lap("resumed");
-            if (T.on) std::fprintf(stderr, "[flood] %zu landmasses resumed on their own queues above level %.9g%s\n", redo.size(), (double)stopLevel, contestedAgain.load() ? "; a contested cell turned up: full replay" : "");
-            if (contestedAgain.load()) replay_dirty_landmasses(S, dirty, e, INFINITY, nullptr, prefix.empty() ? nullptr : &prefix);
-        }
-        run_round(redo, true);
-        T.lap("round 2");
+        P.replay(redo);
+        P.run_round(redo, true);
+        P.T.lap("round 2");
     }
-    const int32_t* landCell = S.landCell.data();
-    if (S.landOrder) parallel_ranges(L, [&](int64_t b, int64_t en, int) { std::memcpy(e + b, eL + b, sizeof(float) * (size_t)(en - b)); });
-    else parallel_ranges(L, [&](int64_t b, int64_t en, int) { for (int64_t i = b; i < en; ++i) e[landCell[i]] = eL[i]; });
-    T.lap("writeback");
+    write_back(e, S);
+    P.T.lap("writeback");
     return true;
 }
+
+void count_ties(FloodHostStats& st, const FloodTieReport& rep) { st.tieGroups += rep.groups; st.contested += rep.contested; st.openParents += rep.openParents; st.unresolved += rep.unresolved; }
+// the pipeline on gathered state, with its time (pass 1 and passes 2/3 overlap: one figure) and its replay in the statistics
+bool timed_pipeline(float* e, double carveStrength, FloodScratch& S, FloodHostStats& st, FloodTieReport& rep, bool replayAllowed) {
+    const auto t0 = Clock::now();
+    const bool done = flood_landmass_pipeline(e, carveStrength, S, rep, st.pathRedo, replayAllowed);
+    st.pass1Ms += ms_between(t0, Clock::now());
+    if (replayAllowed && rep.replayed) { ++st.replays; st.replayedLandmasses += rep.replayed; }
+    return done;
+}
+// The positions of this share's land cells among the planet's land cells in ascending id (true mask): what the flooding rank hands back
+void exchange_own_positions(int32_t N, const FloodScratch& S, FloodExchange& X) {
+    X.ownPos.resize((size_t)S.L);
+    const uint8_t* toc = X.trueOcean.data(); const int32_t* li = S.landIndex.data();
+    int32_t cnt = 0, lowest = -1, placed = 0;
+    for (int32_t r = 0; r < N; ++r) if (!toc[r]) { if (li[r] >= 0) { X.ownPos[(size_t)li[r]] = cnt; ++placed; if (lowest < 0) lowest = r; } ++cnt; }
+    // every land cell of the resident (this rank's) mask must be land in the planet's true mask: a cell that is not has no place among the planet's
+    // land heights (its ownPos entry would stay unset) and the election has no bid for a rank without one
+    if (placed != S.L) throw std::runtime_error("flood exchange: the resident ocean mask has land cells that the planet's true mask (wo_planet_set_flood_exchange) calls ocean");
+    X.landTotal = cnt; X.minOwnCell = lowest; X.posVersion = S.staticVersion;
+}
+
+// undecided, and the one to do it: the whole planet from the pooled heights `snap`, as the unpartitioned run floods it; its land heights into `pack`
+void exchange_flood_planet(int32_t N, const int32_t* off, const int32_t* adj, const float* xyz, float* snap, float* pack, double carveStrength, FloodHostStats& st, FloodExchange& X) {
+    ++X.globalFloods;
+    FloodScratch& G = X.global;
+    if (!G.staticValid || G.staticN != N) flood_build_static(N, off, adj, xyz, X.trueOcean.data(), G);
+    flood_gather(snap, G);
+    FloodTieReport rep;
+    timed_pipeline(snap, carveStrength, G, st, rep, true);
+    const int32_t* gCell = G.landCell.data(); const int32_t* byR = G.landByR.data();
+    parallel_ranges(G.L, [&](int64_t b, int64_t en, int) { for (int64_t q = b; q < en; ++q) pack[q] = snap[gCell[byR[q]]]; });
+}
+enum class HostRoute { Pipeline, TwoPhase, Serial };
+}  // namespace
 
 // gather + pass 1 + passes 2/3 on the host.  Pass 1 runs one heap per landmass on the tree workers; landmasses where that
 // cannot vouch for the single heap's result (FloodTieReport) are decided by the replay of the single heap
 // (replay_dirty_landmasses).  WO_FLOOD_HOST=serial: the plain serial walk; =two-phase: all walks, then all trees, serial
-// walk when undecided (round 2's form, kept for comparison).
+// walk when undecided (round 2's form, kept for comparison).  The variable is read once per process.
 void flood_host_passes(float* e, double carveStrength, FloodScratch& S, FloodHostStats* stats) {
-    static const bool serialOnly = [] { const char* v = std::getenv("WO_FLOOD_HOST"); return v && std::string(v) == "serial"; }();
-    using clock = std::chrono::steady_clock;
-    auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    static const HostRoute route = [] {
+        const char* v = std::getenv("WO_FLOOD_HOST"); const std::string r = v ? v : "";
+        return r == "serial" ? HostRoute::Serial : r == "two-phase" ? HostRoute::TwoPhase : HostRoute::Pipeline;
+    }();
     FloodHostStats local;
     FloodHostStats& st = stats ? *stats : local;
     ++st.calls;
     flood_gather(e, S);
     bool done = false;
-    if (!serialOnly) {
-        static const bool twoPhase = [] { const char* v = std::getenv("WO_FLOOD_HOST"); return v && std::string(v) == "two-phase"; }();
+    if (route != HostRoute::Serial) {
         FloodTieReport rep;
-        auto t0 = clock::now();
-        if (twoPhase) {                                     // all walks first, then all trees (kept for comparison)
+        if (route == HostRoute::TwoPhase) {                 // all walks first, then all trees (kept for comparison)
+            const auto t0 = Clock::now();
             const bool exact = flood_pass1_landmasses(S, rep);
-            auto t1 = clock::now();
-            st.pass1Ms += ms(t0, t1);
+            const auto t1 = Clock::now();
+            st.pass1Ms += ms_between(t0, t1);
             if (exact) {
                 done = flood_pass23_host(e, carveStrength, S, &rep.alt);
-                st.pass23Ms += ms(t1, clock::now());
+                st.pass23Ms += ms_between(t1, Clock::now());
                 if (!done) ++st.pathRedo;
             }
-        } else {
-            done = flood_landmass_pipeline(e, carveStrength, S, rep, st.pathRedo);
-            st.pass1Ms += ms(t0, clock::now());             // pass 1 and passes 2/3 overlap: one figure
-            if (rep.replayed) { ++st.replays; st.replayedLandmasses += rep.replayed; }
-        }
-        st.tieGroups += rep.groups; st.contested += rep.contested; st.openParents += rep.openParents; st.unresolved += rep.unresolved;
+        } else done = timed_pipeline(e, carveStrength, S, st, rep, true);
+        count_ties(st, rep);
         if (!done) flood_gather(e, S);
     }
     if (!done) {
-        auto t0 = clock::now();
+        const auto t0 = Clock::now();
         flood_pass1_host(S);
-        auto t1 = clock::now();
+        const auto t1 = Clock::now();
         flood_pass23_host(e, carveStrength, S);
-        st.pass1Ms += ms(t0, t1); st.pass23Ms += ms(t1, clock::now());
+        st.pass1Ms += ms_between(t0, t1); st.pass23Ms += ms_between(t1, Clock::now());
         ++st.serialPass1;
     }
 }
 
 int flood_host_passes_exchange(int32_t N, const int32_t* off, const int32_t* adj, const float* xyz, float* e, double carveStrength,
                                FloodScratch& S, FloodHostStats* stats, FloodExchange& X) {
-    using clock = std::chrono::steady_clock;
-    auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     FloodHostStats local;
     FloodHostStats& st = stats ? *stats : local;
     ++st.calls; ++X.calls;
@@ -1617,33 +1663,19 @@ int flood_host_passes_exchange(int32_t N, const int32_t* off, const int32_t* adj
     X.snapshot.resize((size_t)N);
     float* snap = X.snapshot.data();
     parallel_ranges(N, [&](int64_t b, int64_t en, int) { std::memcpy(snap + b, e + b, sizeof(float) * (size_t)(en - b)); });
-    int32_t flag = 0;
+    bool mine = false;                                      // this share is undecided on its own
     if (S.L > 0) {
         flood_gather(e, S);
         FloodTieReport rep;
-        auto t0 = clock::now();
-        const bool done = flood_landmass_pipeline(e, carveStrength, S, rep, st.pathRedo, false);
-        st.pass1Ms += ms(t0, clock::now());
-        st.tieGroups += rep.groups; st.contested += rep.contested; st.openParents += rep.openParents; st.unresolved += rep.unresolved;
-        flag = done ? 0 : 1;
+        mine = !timed_pipeline(e, carveStrength, S, st, rep, false);
+        count_ties(st, rep);
     }
     // Who floods the whole planet when a call is undecided: ONE rank — the undecided one that owns the land cell with the smallest id (the
     // ranks' cells are disjoint, so "INT32_MAX - that id" under the max picks it and every rank can tell whether it is the one).  It hands
     // the planet's land heights back (phase 2: it sends; phase 3: the others receive) and the other undecided ranks keep their own cells.
-    const bool mine = flag != 0;
-    if (S.L > 0 && (X.posVersion != S.staticVersion || X.ownPos.size() != (size_t)S.L)) {
-        X.ownPos.resize((size_t)S.L);
-        const uint8_t* toc = X.trueOcean.data();
-        const int32_t* li = S.landIndex.data();
-        int32_t cnt = 0, lowest = -1, placed = 0;
-        for (int32_t r = 0; r < N; ++r) if (!toc[r]) { if (li[r] >= 0) { X.ownPos[(size_t)li[r]] = cnt; ++placed; if (lowest < 0) lowest = r; } ++cnt; }
-        // every land cell of the resident (this rank's) mask must be land in the planet's true mask: a cell that is not has no place among the planet's
-        // land heights (its ownPos entry would stay unset) and the election below has no bid for a rank without one
-        if (placed != S.L) throw std::runtime_error("flood exchange: the resident ocean mask has land cells that the planet's true mask (wo_planet_set_flood_exchange) calls ocean");
-        X.landTotal = cnt; X.minOwnCell = lowest; X.posVersion = S.staticVersion;
-    }
+    if (S.L > 0 && (X.posVersion != S.staticVersion || X.ownPos.size() != (size_t)S.L)) exchange_own_positions(N, S, X);
     const int32_t bid = mine ? INT32_MAX - X.minOwnCell : 0;
-    flag = bid;
+    int32_t flag = bid;
     if (int rc = X.fn(X.user, 0, &flag, 1)) return rc;
     if (!flag) return 0;
     ++X.gathers;
@@ -1652,27 +1684,14 @@ int flood_host_passes_exchange(int32_t N, const int32_t* off, const int32_t* adj
     X.landPack.resize((size_t)std::max<int64_t>(X.landTotal, 1));
     float* pack = X.landPack.data();
     if (mine && flag == bid) {
-        // undecided, and the one to do it: the whole planet, as the unpartitioned run floods it
-        ++X.globalFloods;
-        FloodScratch& G = X.global;
-        if (!G.staticValid || G.staticN != N) flood_build_static(N, off, adj, xyz, X.trueOcean.data(), G);
-        flood_gather(snap, G);
-        FloodTieReport rep;
-        auto t0 = clock::now();
-        flood_landmass_pipeline(snap, carveStrength, G, rep, st.pathRedo, true);
-        st.pass1Ms += ms(t0, clock::now());
-        if (rep.replayed) { ++st.replays; st.replayedLandmasses += rep.replayed; }
-        const int32_t* gCell = G.landCell.data();
-        const int32_t* byR = G.landByR.data();
-        parallel_ranges(G.L, [&](int64_t b, int64_t en, int) { for (int64_t q = b; q < en; ++q) pack[q] = snap[gCell[byR[q]]]; });
+        exchange_flood_planet(N, off, adj, xyz, snap, pack, carveStrength, st, X);
         if (int rc = X.fn(X.user, 2, pack, X.landTotal)) return rc;
     } else {
         if (int rc = X.fn(X.user, 3, pack, X.landTotal)) return rc;
         if (mine) ++X.received;
     }
     if (mine) {
-        const int32_t* landCell = S.landCell.data();
-        const int32_t* pos = X.ownPos.data();
+        const int32_t* landCell = S.landCell.data(); const int32_t* pos = X.ownPos.data();
         parallel_ranges(S.L, [&](int64_t b, int64_t en, int) { for (int64_t i = b; i < en; ++i) e[landCell[i]] = pack[pos[i]]; });
     }
     return 0;

@@ -58,7 +58,7 @@ struct FloodScratch {
     hvec<int32_t> root, order, order2, list2;
     hvec<uint32_t> bits, bits2;
     hvec<FloodHeapItem> heapStore;
-    // landmasses of the compact land graph (static per mask): pass 1 walks them concurrently (flood_pass1_landmasses)
+    // landmasses of the compact land graph (static per mask): pass 1 walks them concurrently, one heap each (flood_host.cc: walk_landmass)
     hvec<int32_t> compSeeds;                 // seed positions (indices into seedCell) grouped by landmass, ascending inside
     std::vector<int32_t> compSeedStart;      // compSeeds range per seeded landmass, landmasses in descending size
     std::vector<int32_t> compSize;
@@ -74,14 +74,6 @@ struct FloodScratch {
     hvec<int32_t> childStart;                // per clean cell: its claimed children in childItem, in the order it pushed them
     hvec<FloodHeapItem> childItem;
 };
-// What the landmass-parallel pass 1 reports.  A cell is "contested" when two cells with EQUAL keys that sat in the heap
-// together (and their sub-key cascades) both reached it: which one claims it is decided by the array history of the
-// reference's single heap, which separate heaps cannot know.
-struct FloodTieReport {
-    int64_t groups = 0, nested = 0, contested = 0, openParents = 0, unresolved = 0;
-    int32_t landmasses = 0, workers = 0, replayed = 0;   // replayed: landmasses decided by the replay of the single heap
-    std::vector<std::pair<int32_t, int32_t>> alt;      // (cell, alternative parent) where only drainTo is undecided
-};
 // (re)builds the mask-dependent tables (Morton-ordered land list `landCell`, compact CSR, seeds)
 // mortonAll (nullable): every cell in the order of morton_order_cells(N, xyz) — the land list is then a filter of it instead of a sort
 void flood_build_static(int32_t N, const int32_t* off, const int32_t* adj, const float* xyz, const uint8_t* ocean, FloodScratch& S, const int32_t* mortonAll = nullptr);
@@ -95,18 +87,7 @@ int64_t flood_queues_differ(int64_t ops, uint64_t seed);            // test supp
 void flood_cell_noise(const FloodScratch& S, double* out);            // cellNoise per land cell, compact order
 void flood_gather(const float* e, FloodScratch& S);                   // land elevations -> compact arrays, pass-1 start state
 void flood_pass1_host(FloodScratch& S);                               // serial heap walk (reference order incl. heap tie mechanics)
-// One heap per landmass, landmasses concurrently; equal-key decisions that could differ from the single heap's are
-// detected (FloodTieReport).  Returns false when one of them changes surfaces/keys: the caller redoes pass 1 serially.
-bool flood_pass1_landmasses(FloodScratch& S, FloodTieReport& rep);
-// The same per landmass, with passes 2/3 of a landmass starting as soon as its own pass 1 is over (the largest landmass
-// bounds pass 1; the others' carving runs beside it).  Landmasses where an equal-key decision matters are walked again
-// inside a replay of the reference's single heap (bare heap operations for everything else) and carved afterwards, so the
-// call always ends with the reference's result in e.  FloodScratch's per-call arrays are consumed: flood_gather() before
-// the next use.
-// replayAllowed == false: a call that would need the replay returns false instead and leaves e untouched (the caller has a
-// better heap to replay: flood_host_passes_exchange)
-bool flood_landmass_pipeline(float* e, double carveStrength, FloodScratch& S, FloodTieReport& rep, int64_t& pathRedo, bool replayAllowed = true);
-// pass 1 (landmass-parallel when exact, else the serial walk) + passes 2/3; stats: see flood_host.cc
+// gather + pass 1 + passes 2/3: e ends with the reference's result.  The routes (landmass pipeline + replay of the single heap; WO_FLOOD_HOST) and the statistics: flood_host.cc
 struct FloodHostStats { int64_t calls = 0, serialPass1 = 0, tieGroups = 0, contested = 0, openParents = 0, unresolved = 0, pathRedo = 0, replays = 0, replayedLandmasses = 0; double pass1Ms = 0, pass23Ms = 0; };
 void flood_host_passes(float* e, double carveStrength, FloodScratch& S, FloodHostStats* stats);
 // The flood of ONE SHARE of a planet (landmass decomposition, decomposed.py: the other shares' landmasses are ocean to S).  A share's

@@ -1,9 +1,9 @@
-"""priorityFloodCarve's host stage, pass 1 with one heap per landmass (csrc/flood_host.cc: flood_pass1_landmasses)
-against the oracle's single-heap walk (reference: js/terrain-post.js:59-215).
+"""priorityFloodCarve's host stage, pass 1 with one heap per landmass (csrc/flood_host.cc: flood_landmass_pipeline, the default
+route; flood_pass1_landmasses is the two-phase route's) against the oracle's single-heap walk (reference: js/terrain-post.js:59-215).
 
 The landmass route must give the reference's elevations bit for bit whatever the reference's heap does with equal
-keys: it either proves that no equal-key decision can matter (tie groups / contested cells / open parents) or hands
-pass 1 to the serial walk.  These tests drive it through the test-only emulator library (the same flood_host.cc the
+keys: it either proves that no equal-key decision can matter (tie groups / contested cells / open parents) or walks the
+undecided landmasses again inside a replay of the single heap (the two-phase route: hands pass 1 to the serial walk).  These tests drive it through the test-only emulator library (the same flood_host.cc the
 product links) on CPU: ordinary terrain (no fallback expected), islands and lakes, and terrain quantised so that
 thousands of keys collide (contested cells, fallbacks)."""
 import ctypes as C
