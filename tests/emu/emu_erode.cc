@@ -572,7 +572,25 @@ void emu_bfs_fields(const ElevMesh& M, const ElevInputs& I, ElevHostState& H, co
     run(BFS_ARC, seeds_of([&](int32_t r) { return H.btype[r] == 1 && H.bothOcean[r] && (double)H.subduct[r] < 0.45; }), H.arcDist.data(), (float)(Q.maxArcDist + 1),
         H.arcStress.data(), nullptr, nullptr, Q.maxArcDist);
 }
+// The largest frontier of each BFS field (coast, rift, ridge, fracture, back-arc, arc) in the last emu_assign_elevation call: the
+// frontier of level L is the cells at distance L - 1, for L = 1 .. the field's reach, whichever formulation filled the field.
+int32_t g_frontier[6] = {0, 0, 0, 0, 0, 0};
+void record_frontiers(int32_t N, const ElevHostState& H, const ElevParams& Q, int32_t maxCD) {
+    const float* dist[6] = {H.dBdry.data(), H.riftDist.data(), H.ridgeDist.data(), H.fractureDist.data(), H.backArcDist.data(), H.arcDist.data()};
+    const int32_t reach[6] = {maxCD, Q.riftHalfWidth, Q.ridgeHalfWidth, Q.fractureHalfWidth, Q.baEnd, Q.maxArcDist};
+    for (int f = 0; f < 6; ++f) {
+        std::vector<int32_t> count(reach[f] > 0 ? reach[f] : 0, 0);
+        for (int32_t r = 0; r < N; ++r) {
+            const float d = dist[f][r];
+            if (d >= 0 && d < (float)reach[f]) ++count[(size_t)d];
+        }
+        g_frontier[f] = 0;
+        for (int32_t c : count) if (c > g_frontier[f]) g_frontier[f] = c;
+    }
+}
 }  // namespace
+
+extern "C" void emu_bfs_largest_frontiers(int32_t* out6) { for (int f = 0; f < 6; ++f) out6[f] = g_frontier[f]; }
 
 extern "C" int emu_assign_elevation(int32_t N, const int32_t* off, const int32_t* adj, const float* xyz, const int32_t* r_plate,
                                     int32_t numIds, const uint8_t* hasVec, const double* pole, const double* omega, const uint8_t* isOcean,
@@ -605,9 +623,9 @@ extern "C" int emu_assign_elevation(int32_t N, const int32_t* off, const int32_t
     ElevHostState H; ElevParams Q{}; std::vector<Dome> domes;
     if (g_bfsDevice)
         elevation_host_stage(M, I, hS, hasSuper ? &hP : nullptr, H, Q, domes,
-                             [&](const ElevParams& Qs, int32_t maxCD, double maxStress) { emu_bfs_fields(M, I, H, Qs, maxCD, maxStress); });
+                             [&](const ElevParams& Qs, int32_t maxCD, double maxStress) { emu_bfs_fields(M, I, H, Qs, maxCD, maxStress); record_frontiers(N, H, Qs, maxCD); });
     else elevation_host_stage(M, I, hS, hasSuper ? &hP : nullptr, H, Q, domes,
-                              [&](const ElevParams& Qs, int32_t maxCD, double maxStress) { fifo_bfs_fields(M, I, H, Qs, maxCD, maxStress); });
+                              [&](const ElevParams& Qs, int32_t maxCD, double maxStress) { fifo_bfs_fields(M, I, H, Qs, maxCD, maxStress); record_frontiers(N, H, Qs, maxCD); });
     ElevFields F{};
     F.xyz = xyz; F.plate = r_plate; F.isOcean = H.isOcean.data(); F.stress = H.stress.data(); F.subduct = H.subduct.data(); F.btype = H.btype.data();
     F.distMountain = H.distMountain.data(); F.distOcean = H.distOcean.data(); F.distCoastline = H.distCoastline.data(); F.distCoast = H.distCoast.data();

@@ -1,0 +1,105 @@
+"""assignElevation on gfx950 cell by cell against the emulator (tests/emu, bfs_device = 0: the product's host stage, the reference's
+FIFO BFS and the kernel bodies of csrc/elevation_ops.h with glibc's libm) at the sizes and on the meshes the golden vectors do not
+reach: 1 M cells of realistic plates, 4 M cells of 3 000 plates (a coast frontier longer than one grid of the BFS kernels, so the
+grid-stride second pass and the atomics of many workgroups in k_bfs_push run), a mesh with hubs of degree 24, a relabelled mesh
+with shuffled rows, the 250 k golden, debug layers off, and two plate layouts on one Planet.
+
+Only the libm calls differ between the two (ocml's instead of glibc's).  test_elevation_libm.py shows that moving every one of
+them by 4 double ulps changes no cell of any output, and by 2^20 ulps changes a few cells by at most 1.8e-7.  So (elev_inputs.compare):
+the Sets and stress bit for bit; elevation and every debug layer within 4 * 2^-23 * max(1, |ref|) in every cell, and at most
+max(8, N / 10^4) cells different at all."""
+from functools import lru_cache
+
+import numpy as np
+import pytest
+
+import elev_inputs as EI
+
+pytestmark = pytest.mark.gpu
+GRID_THREADS = 512 * 256            # k_bfs_push / count / assign: grid 512 x WO_BLOCK 256 (planet.hip, run_field)
+
+
+@pytest.fixture(scope="module")
+def emu():
+    return EI.load_emulator(False)
+
+
+BUILDERS = {
+    "realistic_N1000000": lambda: EI.realistic_case(1_000_000),
+    "hub_N200000_deg24": lambda: EI.hub_case(200_000),
+    "relabelled_N200000": lambda: EI.relabelled_case(200_000),
+    "elev_N250000_s4_large": EI.large_golden_case,
+}
+
+
+@lru_cache(maxsize=None)
+def _case(name):
+    return BUILDERS[name]()
+
+
+def _planet(case):
+    from planet_heightmap_generation_amd import terrain_post as TP
+    return TP.Planet(case.mesh, case.xyz, case.nd)
+
+
+@pytest.mark.parametrize("name", list(BUILDERS))
+def test_matches_emulator(emu, name):
+    case = _case(name)
+    ref = EI.emulate(emu, case)
+    print(f"{name}: largest BFS frontiers {ref['frontiers']}")
+    pl = _planet(case)
+    try:
+        got = EI.on_device(case, pl)
+    finally:
+        pl.close()
+    EI.compare(name, got, ref, case.N)
+
+
+@pytest.mark.isolated
+def test_many_plates_4m(emu):
+    """3 000 plates on 4 M cells: the coast field's first frontier (its boundary cells) is longer than the 131 072 threads of one
+    grid of the BFS kernels, so every level runs the grid-stride second pass, and thousands of workgroups race on pushPos / attrKey."""
+    case = EI.many_plates_case(4_000_000, 3000)
+    ref = EI.emulate(emu, case)
+    print(f"{case.name}: largest BFS frontiers {ref['frontiers']}")
+    assert ref["frontiers"]["coast"] > GRID_THREADS, ref["frontiers"]
+    pl = _planet(case)
+    try:
+        got = EI.on_device(case, pl)
+    finally:
+        pl.close()
+    EI.compare(case.name, got, ref, case.N)
+
+
+def test_debug_layers_off_changes_nothing(emu):
+    """debug = False: no layer buffer on the device (DL_COASTAL is read, modified and written only when layers exist); elevation,
+    stress and the Sets equal the debug = True call bit for bit, and that call equals the emulator."""
+    case = _case("realistic_N1000000")
+    pl = _planet(case)
+    try:
+        on = EI.on_device(case, pl, debug=True)
+        off = EI.on_device(case, pl, debug=False)
+    finally:
+        pl.close()
+    assert off["debugLayers"] == {}
+    for k in ("mountain_r", "coastline_r", "ocean_r"):
+        assert off[k] == on[k], k
+    print(f"debug off vs on: elevation {int((off['r_elevation'] != on['r_elevation']).sum())} cells differ, "
+          f"stress {int((off['r_stress'] != on['r_stress']).sum())}")
+    assert np.array_equal(off["r_elevation"], on["r_elevation"]) and np.array_equal(off["r_stress"], on["r_stress"])
+    EI.compare("debug on", on, EI.emulate(emu, case), case.N)
+
+
+def test_two_layouts_one_planet(emu):
+    """Realistic plates, then 400 Voronoi plates, then the realistic plates again on one Planet: nothing of an earlier call leaks
+    into a later one, and each equals its own reference."""
+    a = EI.realistic_case(200_000, seed=1)
+    b = EI.many_plates_case(200_000, 400, seed=1)
+    assert np.array_equal(a.xyz, b.xyz) and np.array_equal(a.mesh.adjList, b.mesh.adjList)
+    refs = [EI.emulate(emu, c) for c in (a, b)]
+    pl = _planet(a)
+    try:
+        for i, (c, ref) in enumerate(((a, refs[0]), (b, refs[1]), (a, refs[0]))):
+            EI.compare(f"call {i + 1} ({c.name})", EI.on_device(c, pl), ref, c.N)
+    finally:
+        pl.close()
