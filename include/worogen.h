@@ -277,6 +277,31 @@ int wo_classify_regions(wo_planet* p, int32_t* mountain, int32_t* coastline, int
  * rewritten in place); the planet's resident elevation is untouched. */
 int wo_smooth_field(wo_planet* p, float* field, int32_t passes);
 
+/* ------------------------------------------------ seasonal pressure and wind (js/wind.js) ------ */
+/* computeWind(mesh, r_xyz, r_elevation, plateIsOcean, r_plate, noise, axialTilt)                   js/wind.js:394-687
+ *   on the planet's resident mesh (csrc/wind.hip; the per-cell bodies and their exactness contract are in csrc/wind_ops.h).
+ *   numRegions must equal the planet's (the arrays are sized by it).  r_elevation: numRegions floats, or NULL for the planet's
+ *   resident field.  r_plate: numRegions ids.  oceanPlates / nOceanPlates: the ids in the reference's plateIsOcean Set (any
+ *   order, duplicates allowed; NULL only with length 0).  seed: the seed of the SimplexNoise instance the reference is handed.
+ *   axialTilt (degrees): converted and never read again by the reference (:397); it must be a number.
+ *   The results stay on the device in a wind block the planet owns (a later call replaces them); wo_wind_download copies one
+ *   field to the host by the reference's result key:
+ *     numRegions floats   r_pressure_{summer,winter} r_wind_east_* r_wind_north_* r_wind_speed_*  r_lat r_lon r_sinLat
+ *                         r_continentality r_plateContinentality  r_eastX r_eastY r_eastZ r_northX r_northY r_northZ
+ *     numRegions int32    r_coastDistLand          numRegions bytes   r_isLand
+ *     360 floats          itczLons itczLatsSummer itczLatsWinter
+ *   outBytes is the size of `out`; it must be at least the field's; an unknown key fails.  bfsLevels2 (may be NULL):
+ *   [0] / [1] = levels the coast / plate distance field took (for profiles).  No CPU fallback: without a device there is
+ *   no planet. */
+int wo_compute_wind(wo_planet* p, int32_t numRegions, const float* r_elevation, const int32_t* r_plate, const int32_t* oceanPlates,
+                    int32_t nOceanPlates, double seed, double axialTilt, int32_t* bfsLevels2);
+int wo_wind_download(wo_planet* p, const char* field, void* out, int64_t outBytes);
+/* computeGradients(mesh, r_xyz, r_pressure, r_east*, r_north*, r_gradE, r_gradN)                   js/wind.js:306-339
+ *   on caller arrays: r_pressure numRegions floats; east3 / north3 the x, y and z arrays one after another (3 * numRegions
+ *   floats each); r_gradE / r_gradN numRegions floats, written. */
+int wo_compute_gradients(wo_planet* p, int32_t numRegions, const float* r_pressure, const float* east3, const float* north3,
+                         float* r_gradE, float* r_gradN);
+
 /* ------------------------------------------------ device-resident variants -------------------- */
 /* The "reapply" pattern (js/planet-worker.js:341-440): fields stay in HBM, only scalars arrive.
  * wo_planet_upload sets the resident r_elevation (and r_isOcean when not NULL); the *_resident

@@ -170,6 +170,10 @@ struct wo_planet {
         int32_t* totals = nullptr; int32_t* h_totals = nullptr;   // the four list lengths (device, pinned host)
     } imp;
 
+    // seasonal pressure and wind (wind.hip): the wind block — results and scratch of wo_compute_wind, allocated on its first
+    // call; freed by wo_planet_destroy
+    struct wo_wind_block* wind = nullptr;
+
     // Patch-major mirror of the mesh for erodeComposite (planet.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
     // d_e2, d_ocean, d_coast) point at the mirror and the o_* members hold the planet's own buffers.
@@ -257,5 +261,10 @@ void basin_solve_launch(wo_planet* p, const Fields& F, int32_t launchTag, int32_
 void basin_free(wo_planet* p);
 // heightmap.hip: frees the import scratch
 void import_free(wo_planet* p);
+// wind.hip: frees the wind block; planet.hip: smoothField on a resident field (returns the buffer that holds the result)
+void wind_free(wo_planet* p);
+// planet.hip: the entry points' handle check (refreshes p->opt from the environment, selects the device)
+bool check_planet(wo_planet* p, const char* fn);
+float* smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passes);
 
 }  // namespace wo

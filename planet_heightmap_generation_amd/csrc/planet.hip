@@ -1116,7 +1116,18 @@ Options Options::from_env() {
     return o;
 }
 
-static bool check_planet(wo_planet* p, const char* fn) {
+// smoothField (js/climate-util.js:5-25) on a device-resident field, no host round trip: `passes` Jacobi passes from a into b and
+// back; returns the buffer that holds the result (wind.hip)
+float* wo::smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passes) {
+    Fields F = p->fields();
+    for (int32_t pass = 0; pass < passes; ++pass) {
+        launch(p, FAM_SMOOTH_FIELD, k_smooth_field, xcd_grid(p->N), WO_BLOCK, F, (const float*)a, b);
+        std::swap(a, b);
+    }
+    return a;
+}
+
+bool wo::check_planet(wo_planet* p, const char* fn) {
     if (!p) { set_error(std::string(fn) + ": null planet handle"); return false; }
     p->opt = Options::from_env();
     hipError_t e = hipSetDevice(p->ctx->device);
@@ -1256,6 +1267,7 @@ void wo_planet_destroy(wo_planet* p) {
     p->floodLink = nullptr;
     basin_free(p);
     import_free(p);
+    wind_free(p);
     if (p->side) { (void)hipStreamSynchronize(p->side); (void)hipStreamDestroy(p->side); p->side = nullptr; }
     if (p->evFork) { (void)hipEventDestroy(p->evFork); p->evFork = nullptr; }
     if (p->evJoin) { (void)hipEventDestroy(p->evJoin); p->evJoin = nullptr; }
@@ -1548,12 +1560,7 @@ int wo_smooth_field(wo_planet* p, float* field, int32_t passes) {
         const size_t bytes = (size_t)p->N * sizeof(float);
         a = dalloc<float>(p->N); b = dalloc<float>(p->N);
         WO_HIP(hipMemcpyAsync(a, field, bytes, hipMemcpyHostToDevice, s));
-        Fields F = p->fields();
-        for (int32_t pass = 0; pass < passes; ++pass) {
-            launch(p, FAM_SMOOTH_FIELD, k_smooth_field, xcd_grid(p->N), WO_BLOCK, F, (const float*)a, b);
-            std::swap(a, b);
-        }
-        WO_HIP(hipMemcpyAsync(field, a, bytes, hipMemcpyDeviceToHost, s));
+        WO_HIP(hipMemcpyAsync(field, smooth_field_resident(p, a, b, passes), bytes, hipMemcpyDeviceToHost, s));
         WO_HIP(hipStreamSynchronize(s));
         dfree(a); dfree(b);
         return 0;

@@ -441,6 +441,44 @@ napi_value AdvectMoisture(napi_env env, napi_callback_info info) {
     if (wo_advect_moisture(p, hk, land, we, wn, x, y, z, w, cd, a.i32(10), (float*)d)) return throw_wo(env, "advectMoisture");
     return out;
 }
+// computeWind(planet, r_elevation | null, r_plate, oceanPlates Int32Array, seed, axialTilt) -> the reference's result object
+// (js/wind.js:649-683, without _windTiming); null elevation: the planet's resident field
+napi_value ComputeWind(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* e = (float*)opt_regions(a, 1, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    int32_t* plate = (int32_t*)opt_regions(a, 2, napi_int32_array, p, "computeWind: r_plate must be an Int32Array", true); if (!a.ok) return nullptr;
+    size_t nOcean = 0; int32_t* ocean = (int32_t*)a.ta(3, napi_int32_array, &nOcean); if (!a.ok) return nullptr;
+    const int32_t n = wo_planet_num_regions(p);
+    if (wo_compute_wind(p, n, e, plate, nOcean ? ocean : nullptr, (int32_t)nOcean, a.num(4), a.num(5), nullptr)) return throw_wo(env, "computeWind");
+    static const char* const f32[] = {"r_pressure_summer", "r_wind_east_summer", "r_wind_north_summer", "r_wind_speed_summer",
+                                      "r_pressure_winter", "r_wind_east_winter", "r_wind_north_winter", "r_wind_speed_winter",
+                                      "itczLons", "itczLatsSummer", "itczLatsWinter", "r_lat", "r_lon", "r_sinLat", "r_isLand",
+                                      "r_continentality", "r_coastDistLand", "r_plateContinentality",
+                                      "r_eastX", "r_eastY", "r_eastZ", "r_northX", "r_northY", "r_northZ"};
+    napi_value o; napi_create_object(env, &o);
+    for (const char* k : f32) {
+        const bool itcz = k[0] == 'i', land = std::strcmp(k, "r_isLand") == 0, dist = std::strcmp(k, "r_coastDistLand") == 0;
+        const size_t len = itcz ? 360 : (size_t)n, elem = land ? 1 : 4;
+        void* d; napi_value v = make_ta(env, land ? napi_uint8_array : dist ? napi_int32_array : napi_float32_array, len, elem, &d);
+        if (!v) return nullptr;
+        if (wo_wind_download(p, k, d, (int64_t)(len * elem))) return throw_wo(env, "computeWind");
+        set_prop(env, o, k, v);
+    }
+    return o;
+}
+// computeGradients(planet, r_pressure, r_eastX, r_eastY, r_eastZ, r_northX, r_northY, r_northZ, r_gradE, r_gradN): the last two are written
+napi_value ComputeGradients(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* q[9];
+    for (int i = 0; i < 9; ++i) { q[i] = (float*)opt_regions(a, (size_t)i + 1, napi_float32_array, p, "computeGradients: nine Float32Arrays of numRegions entries", true); if (!a.ok) return nullptr; }
+    const size_t n = (size_t)wo_planet_num_regions(p);
+    std::vector<float> east(3 * n), north(3 * n);
+    for (int c = 0; c < 3; ++c) { std::memcpy(east.data() + c * n, q[1 + c], n * 4); std::memcpy(north.data() + c * n, q[4 + c], n * 4); }
+    if (wo_compute_gradients(p, (int32_t)n, q[0], east.data(), north.data(), q[7], q[8])) return throw_wo(env, "computeGradients");
+    return nullptr;
+}
 // landComponents(numRegions, adjOffset, adjList, r_isOcean) -> Int32Array (label = smallest id of the landmass, -1 for ocean)
 napi_value LandComponents(napi_env env, napi_callback_info info) {
     Args a(env, info);
@@ -623,7 +661,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"projectCoarsePlates", ProjectCoarsePlates}, {"smoothField", SmoothField}, {"smoothAndReconnectPlates", SmoothAndReconnectPlates},
         {"diffuseOceanWarmth", DiffuseOceanWarmth}, {"computeWindConvergence", WindConvergence}, {"advectMoisture", AdvectMoisture},
         {"landComponents", LandComponents}, {"sampleHeightmap", SampleHeightmap}, {"syntheticPlates", SyntheticPlates},
-        {"classifyRegions", ClassifyRegions}, {"triangleCenters", TriangleCenters},
+        {"classifyRegions", ClassifyRegions}, {"triangleCenters", TriangleCenters}, {"computeWind", ComputeWind}, {"computeGradients", ComputeGradients},
         {"commUniqueId", CommUniqueId}, {"commCreate", CommCreate}, {"planetSetHalo", PlanetSetHalo},
         {"planetExchangeAllgather", PlanetExchangeAllgather}, {"planetExchangeNeighbors", PlanetExchangeNeighbors}, {"planetSetFloodExchange", PlanetSetFloodExchange},
     };
