@@ -302,6 +302,34 @@ int wo_wind_download(wo_planet* p, const char* field, void* out, int64_t outByte
 int wo_compute_gradients(wo_planet* p, int32_t numRegions, const float* r_pressure, const float* east3, const float* north3,
                          float* r_gradE, float* r_gradN);
 
+/* wo_wind_upload sets one field of the planet's wind block from the host by its result key (the keys and sizes of
+ *   wo_wind_download; `bytes` must be the field's size exactly); it allocates the block if there is none.  It serves a caller
+ *   that brings its own windResult to a later stage.  A block filled only by uploads is no wind result: wo_wind_download of a
+ *   field that was never set still fails. */
+int wo_wind_upload(wo_planet* p, const char* field, const void* data, int64_t bytes);
+
+/* ------------------------------------------------ ocean surface currents (js/ocean.js) --------- */
+/* computeOceanCurrents(mesh, r_xyz, r_elevation, windResult)                                       js/ocean.js:204-382
+ *   on the planet's resident mesh (csrc/ocean.hip; the per-cell bodies and their exactness contract are in csrc/ocean_ops.h).
+ *   windResult is the planet's wind block: left there by wo_compute_wind, or filled by wo_wind_upload with at least r_lat r_lon
+ *   r_isLand r_eastX r_eastY r_eastZ itczLons itczLatsSummer itczLatsWinter, the fields the stage reads; otherwise the call
+ *   fails with "no wind result".  r_elevation is not read by the reference and is no argument here.  numRegions must equal the
+ *   planet's.  All eight outputs are the reference's bit for bit.
+ *   The results stay on the device in an ocean block the planet owns (a later call replaces them); wo_ocean_download copies one
+ *   field (numRegions floats) to the host by the reference's result key:
+ *     r_ocean_current_east_{summer,winter} r_ocean_current_north_* r_ocean_speed_* r_ocean_warmth_*
+ *   outBytes is the size of `out`; it must be at least the field's; an unknown key fails.  info (may be NULL) receives what the
+ *   reference logs (:243, :371) and the pass counts, for profiles and checks.  No CPU fallback. */
+typedef struct wo_ocean_info {
+    int32_t circumpolarNH, circumpolarSH;              /* an open ocean channel at 60 +- 5 degrees north / south */
+    int32_t coastThreshold, warmthRange;               /* hops; the distance fields are built to warmthRange - 1 */
+    int32_t currentSmoothPasses, warmthSmoothPasses;
+    int32_t oceanCells[2];                             /* ocean cells with a speed > 0, summer / winter */
+    float p95[2];                                      /* their 95th percentile, summer / winter */
+} wo_ocean_info;
+int wo_compute_ocean_currents(wo_planet* p, int32_t numRegions, wo_ocean_info* info);
+int wo_ocean_download(wo_planet* p, const char* field, void* out, int64_t outBytes);
+
 /* ------------------------------------------------ device-resident variants -------------------- */
 /* The "reapply" pattern (js/planet-worker.js:341-440): fields stay in HBM, only scalars arrive.
  * wo_planet_upload sets the resident r_elevation (and r_isOcean when not NULL); the *_resident

@@ -96,6 +96,7 @@ struct Options {
     bool basinScramble = false;        // basin_scramble=1         a deliberately wrong basin layout (leftovers for the patch finisher)
     long long carveBudgetMs = 200;     // carve_budget_ms=<n>      spin budget of the one-launch carve (0: it gives up at once and the rounds finish)
     int  carveBlocks = 0;              // carve_blocks=<n>         at most this many workgroups for the one-launch carve
+    bool oceanSplitSmooth = false;     // ocean_split_smooth=1     ocean currents: the masked smoothing field by field instead of one interleaved gather (the A/B of DESIGN section 8.3)
     static Options from_env();
 };
 }  // namespace wo
@@ -173,6 +174,9 @@ struct wo_planet {
     // seasonal pressure and wind (wind.hip): the wind block — results and scratch of wo_compute_wind, allocated on its first
     // call; freed by wo_planet_destroy
     struct wo_wind_block* wind = nullptr;
+    // ocean surface currents (ocean.hip): the ocean block — results and scratch of wo_compute_ocean_currents, allocated on its
+    // first call; freed by wo_planet_destroy
+    struct wo_ocean_block* ocean = nullptr;
 
     // Patch-major mirror of the mesh for erodeComposite (planet.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
@@ -263,6 +267,8 @@ void basin_free(wo_planet* p);
 void import_free(wo_planet* p);
 // wind.hip: frees the wind block; planet.hip: smoothField on a resident field (returns the buffer that holds the result)
 void wind_free(wo_planet* p);
+// ocean.hip: frees the ocean block
+void ocean_free(wo_planet* p);
 // planet.hip: the entry points' handle check (refreshes p->opt from the environment, selects the device)
 bool check_planet(wo_planet* p, const char* fn);
 float* smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passes);

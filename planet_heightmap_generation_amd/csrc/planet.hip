@@ -1113,6 +1113,7 @@ Options Options::from_env() {
     o.basinScramble = test_hook_int("basin_scramble", 0) != 0;
     o.carveBudgetMs = test_hook_int("carve_budget_ms", 200);
     o.carveBlocks = (int)std::max<long long>(0, test_hook_int("carve_blocks", 0));
+    o.oceanSplitSmooth = test_hook_int("ocean_split_smooth", 0) != 0;
     return o;
 }
 
@@ -1267,6 +1268,7 @@ void wo_planet_destroy(wo_planet* p) {
     p->floodLink = nullptr;
     basin_free(p);
     import_free(p);
+    ocean_free(p);
     wind_free(p);
     if (p->side) { (void)hipStreamSynchronize(p->side); (void)hipStreamDestroy(p->side); p->side = nullptr; }
     if (p->evFork) { (void)hipEventDestroy(p->evFork); p->evFork = nullptr; }

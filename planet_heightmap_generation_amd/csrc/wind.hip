@@ -24,35 +24,10 @@
 
 #include "../../include/worogen.h"
 #include "device.h"
+#include "wind_block.h"
 #include "wind_ops.h"
 
 namespace W = wo::wind;
-
-// the wind block of a planet
-struct wo_wind_block {
-    bool valid = false;
-    // results (device): the eight season arrays, then the per-cell geography
-    float* season[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // pressure, east, north, speed
-    float *lat = nullptr, *lon = nullptr, *sinLat = nullptr, *cosLat = nullptr;
-    uint8_t* isLand = nullptr;
-    float *cont = nullptr, *plateCont = nullptr;
-    int32_t* coastDist = nullptr;
-    float* frame[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    float itcz[3][W::ITCZ_SAMPLES];                           // host: itczLons, itczLatsSummer, itczLatsWinter
-    // scratch
-    float *e = nullptr, *tmpA = nullptr, *tmpB = nullptr, *gradE = nullptr, *gradN = nullptr;
-    int32_t *label = nullptr, *compSize = nullptr, *plateDist = nullptr, *plate = nullptr, *oceanIds = nullptr; int64_t oceanIdCap = 0; int32_t nOceanIds = 0;   // ascending ocean plate ids: capacity, count in use
-    uint8_t* plateOcean = nullptr;
-    uint32_t* keys[2] = {nullptr, nullptr}; int32_t* vals[2] = {nullptr, nullptr}; uint32_t* sortScratch = nullptr; int sortFlip = 0;
-    int32_t* binOffset = nullptr;
-    int32_t* frontier[2] = {nullptr, nullptr}; int32_t* counts = nullptr;      // 3 rotating frontier lengths
-    unsigned long long* mainKey = nullptr;
-    W::SampleSpec* specs = nullptr; W::SampleAcc* acc = nullptr; W::Spline* splines = nullptr;
-    uint32_t* selHist = nullptr; W::SelState* selState = nullptr; float* maxSpeed = nullptr;
-    // pinned host
-    W::SampleAcc* h_acc = nullptr; int32_t* h_count = nullptr;
-    int32_t bfsLevels[2] = {0, 0};
-};
 
 namespace wo {
 
@@ -140,17 +115,6 @@ __global__ __launch_bounds__(WO_BLOCK) void k_wind_cc_main(const int32_t* __rest
     WIND_CELLS(r, N) if (!isLand[r] && label[r] == r) atomicMax(mainKey, W::main_ocean_key(compSize[r], r));
 }
 
-// append the flagged lanes' values with one atomic per wave; every lane of the wave calls it together
-__device__ inline void wind_append(bool flag, int32_t value, int32_t* list, int32_t* counter) {
-    const unsigned long long m = __ballot(flag);
-    if (m == 0) return;
-    const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
-    int32_t base = 0;
-    if (lane == leader) base = atomicAdd(counter, (int32_t)__popcll(m));
-    base = __shfl(base, leader);
-    if (flag) list[base + (int32_t)__popcll(m & ((1ull << lane) - 1ull))] = value;
-}
-
 // level 0 of a distance field: mode 0 coast (land cells that touch the main ocean), mode 1 plates
 __global__ __launch_bounds__(WO_BLOCK) void k_wind_bfs_seed(int32_t mode, const uint8_t* __restrict__ isLand, const int32_t* __restrict__ label,
                                                             const unsigned long long* __restrict__ mainKey, const uint8_t* __restrict__ plateOcean,
@@ -236,12 +200,9 @@ __global__ __launch_bounds__(WO_BLOCK) void k_wind_finish(float* __restrict__ sp
     WIND_CELLS(r, N) { speed[r] = W::normalise_speed_cell(speed[r], m); pressureDev[r] = W::pressure_dev_cell(pressure[r]); }
 }
 
-template <class T> static void walloc(T*& q, size_t n) { WO_HIP(hipMalloc((void**)&q, std::max<size_t>(n, 1) * sizeof(T))); }
-template <class T> static void wfree(T*& q) { if (q) { (void)hipFree(q); q = nullptr; } }
-
 void wind_free(wo_planet* p);
 static void wind_alloc_buffers(wo_planet* p, wo_wind_block* B);
-static void wind_alloc(wo_planet* p) {
+void wind_alloc(wo_planet* p) {
     if (p->wind) return;
     auto* B = new wo_wind_block();
     p->wind = B;
@@ -314,7 +275,7 @@ static void wind_run(wo_planet* p, double seed) {
     auto* B = p->wind;
     const int32_t N = p->N, g = blocks_for(N);
     hipStream_t s = p->ctx->stream;
-    B->valid = false;
+    B->valid = false; B->have = 0;
     // step 0 and the geo index
     W::CellGeo G{B->lat, B->lon, B->sinLat, B->cosLat, B->isLand, B->frame[0], B->frame[1], B->frame[2], B->frame[3], B->frame[4], B->frame[5]};
     launch(p, FAM_CLIMATE, k_wind_precompute, g, WO_BLOCK, (const float*)p->d_xyz, (const float*)B->e, G, B->keys[0], B->vals[0], N);
@@ -369,7 +330,7 @@ static void wind_run(wo_planet* p, double seed) {
         launch(p, FAM_CLIMATE, k_wind_finish, g, WO_BLOCK, out[3], (const float*)B->maxSpeed, pressure, out[0], N);
     }
     WO_HIP(hipStreamSynchronize(s));                                        // sel0 is read by the copies above
-    B->valid = true;
+    B->valid = true; B->have = WF_ALL;
 }
 
 }  // namespace wo
@@ -380,8 +341,7 @@ using namespace wo;
     catch (const HipError& e) { set_error(std::string(fn) + ": " + e.msg); return 2; }   \
     catch (const std::exception& e) { set_error(std::string(fn) + ": " + e.what()); return 3; }
 
-// the downloadable fields: the reference's result keys in the order it sets them (js/wind.js:649-683)
-enum WindField : int { WF_SEASON0 = 0, WF_ITCZ0 = 8, WF_LAT = 11, WF_LON, WF_SINLAT, WF_ISLAND, WF_CONT, WF_COASTDIST, WF_PLATECONT, WF_FRAME0, WF_COUNT = WF_FRAME0 + 6 };
+// the downloadable fields: the reference's result keys in the order it sets them (js/wind.js:649-683; wind_block.h: WindField)
 static const char* const kWindFields[WF_COUNT] = {
     "r_pressure_summer", "r_wind_east_summer", "r_wind_north_summer", "r_wind_speed_summer",
     "r_pressure_winter", "r_wind_east_winter", "r_wind_north_winter", "r_wind_speed_winter",
@@ -404,7 +364,7 @@ int wo_compute_wind(wo_planet* p, int32_t numRegions, const float* r_elevation, 
     try {
         wind_alloc(p);
         auto* B = p->wind;
-        B->valid = false;
+        B->valid = false; B->have = 0;
         hipStream_t s = p->ctx->stream;
         const size_t N = (size_t)p->N;
         std::vector<int32_t> ids(oceanPlates, oceanPlates + nOceanPlates);
@@ -424,31 +384,58 @@ int wo_compute_wind(wo_planet* p, int32_t numRegions, const float* r_elevation, 
     } WO_WIND_CATCH("wo_compute_wind")
 }
 
+// where field f lives and how large it is (the ITCZ arrays are host arrays of the block)
+static void* wind_field_ptr(wo_wind_block* B, int f, size_t N, size_t* bytes) {
+    const bool itcz = f >= WF_ITCZ0 && f < WF_LAT;
+    *bytes = itcz ? sizeof(float) * W::ITCZ_SAMPLES : f == WF_ISLAND ? N : N * 4;
+    if (itcz) return B->itcz[f - WF_ITCZ0];
+    if (f < WF_ITCZ0) return B->season[f / 4][f % 4];
+    switch (f) {
+        case WF_LAT: return B->lat;           case WF_LON: return B->lon;             case WF_SINLAT: return B->sinLat;
+        case WF_ISLAND: return B->isLand;     case WF_CONT: return B->cont;           case WF_COASTDIST: return B->coastDist;
+        case WF_PLATECONT: return B->plateCont;
+        default: return B->frame[f - WF_FRAME0];
+    }
+}
+
 int wo_wind_download(wo_planet* p, const char* field, void* out, int64_t outBytes) {
     if (!check_planet(p, "wo_wind_download")) return 1;
     if (!field || !out) { set_error("wo_wind_download: null pointer"); return 1; }
     auto* B = p->wind;
-    if (!B || !B->valid) { set_error("wo_wind_download: no wind result on this planet (call wo_compute_wind first)"); return 1; }
+    if (!B || !(B->valid || B->have)) { set_error("wo_wind_download: no wind result on this planet (call wo_compute_wind first)"); return 1; }
     const int f = wind_field_index(field);
     if (f < 0) { set_error(std::string("wo_wind_download: unknown field '") + field + "'"); return 1; }
+    if (!B->valid && !((B->have >> f) & 1u)) { set_error(std::string("wo_wind_download: no wind result on this planet: ") + field + " was never set (call wo_compute_wind first)"); return 1; }
     try {
-        const size_t N = (size_t)p->N;
-        const void* src = nullptr;
-        const bool itcz = f >= WF_ITCZ0 && f < WF_LAT;
-        const size_t bytes = itcz ? sizeof(float) * W::ITCZ_SAMPLES : f == WF_ISLAND ? N : N * 4;
+        size_t bytes = 0;
+        const void* src = wind_field_ptr(B, f, (size_t)p->N, &bytes);
         if (outBytes < (int64_t)bytes) { set_error(std::string("wo_wind_download: ") + field + " needs " + std::to_string(bytes) + " bytes, out has " + std::to_string(outBytes)); return 1; }
-        if (itcz) { std::memcpy(out, B->itcz[f - WF_ITCZ0], bytes); return 0; }
-        if (f < WF_ITCZ0) src = B->season[f / 4][f % 4];
-        else switch (f) {
-            case WF_LAT: src = B->lat; break;           case WF_LON: src = B->lon; break;             case WF_SINLAT: src = B->sinLat; break;
-            case WF_ISLAND: src = B->isLand; break;     case WF_CONT: src = B->cont; break;           case WF_COASTDIST: src = B->coastDist; break;
-            case WF_PLATECONT: src = B->plateCont; break;
-            default: src = B->frame[f - WF_FRAME0];
-        }
+        if (f >= WF_ITCZ0 && f < WF_LAT) { std::memcpy(out, src, bytes); return 0; }
         WO_HIP(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, p->ctx->stream));
         WO_HIP(hipStreamSynchronize(p->ctx->stream));
         return 0;
     } WO_WIND_CATCH("wo_wind_download")
+}
+
+int wo_wind_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) {
+    if (!check_planet(p, "wo_wind_upload")) return 1;
+    if (!field || !data) { set_error("wo_wind_upload: null pointer"); return 1; }
+    const int f = wind_field_index(field);
+    if (f < 0) { set_error(std::string("wo_wind_upload: unknown field '") + field + "'"); return 1; }
+    try {
+        wind_alloc(p);
+        auto* B = p->wind;
+        size_t want = 0;
+        void* dst = wind_field_ptr(B, f, (size_t)p->N, &want);
+        if (bytes != (int64_t)want) { set_error(std::string("wo_wind_upload: ") + field + " takes " + std::to_string(want) + " bytes, data has " + std::to_string(bytes)); return 1; }
+        if (f >= WF_ITCZ0 && f < WF_LAT) std::memcpy(dst, data, want);
+        else {
+            WO_HIP(hipMemcpyAsync(dst, data, want, hipMemcpyHostToDevice, p->ctx->stream));
+            WO_HIP(hipStreamSynchronize(p->ctx->stream));     // `data` is the caller's, and pageable
+        }
+        B->have |= 1u << f;
+        return 0;
+    } WO_WIND_CATCH("wo_wind_upload")
 }
 
 int wo_compute_gradients(wo_planet* p, int32_t numRegions, const float* r_pressure, const float* east3, const float* north3, float* r_gradE, float* r_gradN) {

@@ -1,0 +1,61 @@
+// The wind block of a planet: results and scratch of wo_compute_wind (wind.hip).  The ocean-current stage (ocean.hip) reads
+// its results and borrows its scratch, so the block, its field keys and the wave-convergent append live here.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "device.h"
+#include "wind_ops.h"
+
+struct wo_wind_block {
+    bool valid = false;                                       // a whole result of wo_compute_wind
+    uint32_t have = 0;                                        // bit f: field f (WindField) was set, by wo_compute_wind or by wo_wind_upload
+    // results (device): the eight season arrays, then the per-cell geography
+    float* season[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // pressure, east, north, speed
+    float *lat = nullptr, *lon = nullptr, *sinLat = nullptr, *cosLat = nullptr;
+    uint8_t* isLand = nullptr;
+    float *cont = nullptr, *plateCont = nullptr;
+    int32_t* coastDist = nullptr;
+    float* frame[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float itcz[3][wo::wind::ITCZ_SAMPLES];                    // host: itczLons, itczLatsSummer, itczLatsWinter
+    // scratch
+    float *e = nullptr, *tmpA = nullptr, *tmpB = nullptr, *gradE = nullptr, *gradN = nullptr;
+    int32_t *label = nullptr, *compSize = nullptr, *plateDist = nullptr, *plate = nullptr, *oceanIds = nullptr; int64_t oceanIdCap = 0; int32_t nOceanIds = 0;   // ascending ocean plate ids: capacity, count in use
+    uint8_t* plateOcean = nullptr;
+    uint32_t* keys[2] = {nullptr, nullptr}; int32_t* vals[2] = {nullptr, nullptr}; uint32_t* sortScratch = nullptr; int sortFlip = 0;
+    int32_t* binOffset = nullptr;
+    int32_t* frontier[2] = {nullptr, nullptr}; int32_t* counts = nullptr;      // 3 rotating frontier lengths
+    unsigned long long* mainKey = nullptr;
+    wo::wind::SampleSpec* specs = nullptr; wo::wind::SampleAcc* acc = nullptr; wo::wind::Spline* splines = nullptr;
+    uint32_t* selHist = nullptr; wo::wind::SelState* selState = nullptr; float* maxSpeed = nullptr;
+    // pinned host
+    wo::wind::SampleAcc* h_acc = nullptr; int32_t* h_count = nullptr;
+    int32_t bfsLevels[2] = {0, 0};
+};
+
+namespace wo {
+
+// the fields of the block by the reference's result keys, in the order it sets them (js/wind.js:649-683)
+enum WindField : int { WF_SEASON0 = 0, WF_ITCZ0 = 8, WF_LAT = 11, WF_LON, WF_SINLAT, WF_ISLAND, WF_CONT, WF_COASTDIST, WF_PLATECONT, WF_FRAME0, WF_COUNT = WF_FRAME0 + 6 };
+constexpr uint32_t WF_ALL = (1u << WF_COUNT) - 1u;
+
+// wind.hip: allocates the planet's wind block if there is none
+void wind_alloc(wo_planet* p);
+
+template <class T> inline void walloc(T*& q, size_t n) { WO_HIP(hipMalloc((void**)&q, std::max<size_t>(n, 1) * sizeof(T))); }
+template <class T> inline void wfree(T*& q) { if (q) { (void)hipFree(q); q = nullptr; } }
+
+// append the flagged lanes' values with one atomic per wave; every lane of the wave calls it together
+__device__ inline void wind_append(bool flag, int32_t value, int32_t* list, int32_t* counter) {
+    const unsigned long long m = __ballot(flag);
+    if (m == 0) return;
+    const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
+    int32_t base = 0;
+    if (lane == leader) base = atomicAdd(counter, (int32_t)__popcll(m));
+    base = __shfl(base, leader);
+    if (flag) list[base + (int32_t)__popcll(m & ((1ull << lane) - 1ull))] = value;
+}
+
+}  // namespace wo

@@ -479,6 +479,53 @@ napi_value ComputeGradients(napi_env env, napi_callback_info info) {
     if (wo_compute_gradients(p, (int32_t)n, q[0], east.data(), north.data(), q[7], q[8])) return throw_wo(env, "computeGradients");
     return nullptr;
 }
+// windUpload(planet, key, typedArray): one field of the planet's wind block by its result key (the C ABI checks key and size)
+static bool key_at(Args& a, size_t i, char (&key)[64]) {
+    size_t n = 0;
+    if (i < a.argc && napi_get_value_string_utf8(a.env, a.argv[i], key, sizeof(key), &n) == napi_ok) return true;
+    napi_throw_type_error(a.env, nullptr, "expected a result key (string)");
+    return false;
+}
+napi_value WindUpload(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    char key[64]; if (!key_at(a, 1, key)) return nullptr;
+    bool is = false;
+    if (a.argc < 3 || napi_is_typedarray(env, a.argv[2], &is) != napi_ok || !is) { napi_throw_type_error(env, nullptr, "windUpload: expected a typed array"); return nullptr; }
+    napi_typedarray_type t; size_t n; void* data; napi_value ab; size_t off;
+    napi_get_typedarray_info(env, a.argv[2], &t, &n, &data, &ab, &off);
+    const size_t elem = (t == napi_uint8_array || t == napi_int8_array || t == napi_uint8_clamped_array) ? 1 : (t == napi_float32_array || t == napi_int32_array || t == napi_uint32_array) ? 4 : 0;
+    if (!elem) { napi_throw_type_error(env, nullptr, "windUpload: expected a Float32Array, Int32Array or Uint8Array"); return nullptr; }
+    if (wo_wind_upload(p, key, data, (int64_t)(n * elem))) return throw_wo(env, "windUpload");
+    return nullptr;
+}
+// computeOceanCurrents(planet) -> {circumpolarNH, circumpolarSH, coastThreshold, warmthRange, ...}: the stage on the planet's wind block;
+// the results stay on the device (oceanDownload)
+napi_value ComputeOceanCurrents(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    wo_ocean_info oi;
+    if (wo_compute_ocean_currents(p, wo_planet_num_regions(p), &oi)) return throw_wo(env, "computeOceanCurrents");
+    napi_value o, v; napi_create_object(env, &o);
+    napi_get_boolean(env, oi.circumpolarNH != 0, &v); set_prop(env, o, "circumpolarNH", v);
+    napi_get_boolean(env, oi.circumpolarSH != 0, &v); set_prop(env, o, "circumpolarSH", v);
+    const struct { const char* k; double x; } nums[] = {{"coastThreshold", (double)oi.coastThreshold}, {"warmthRange", (double)oi.warmthRange},
+        {"currentSmoothPasses", (double)oi.currentSmoothPasses}, {"warmthSmoothPasses", (double)oi.warmthSmoothPasses}, {"oceanCellsSummer", (double)oi.oceanCells[0]},
+        {"oceanCellsWinter", (double)oi.oceanCells[1]}, {"p95Summer", (double)oi.p95[0]}, {"p95Winter", (double)oi.p95[1]}};
+    for (const auto& e : nums) { napi_create_double(env, e.x, &v); set_prop(env, o, e.k, v); }
+    return o;
+}
+// oceanDownload(planet, key) -> Float32Array: one field of the planet's ocean block by the reference's result key
+napi_value OceanDownload(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    char key[64]; if (!key_at(a, 1, key)) return nullptr;
+    const size_t n = (size_t)wo_planet_num_regions(p);
+    void* d; napi_value out = make_ta(env, napi_float32_array, n, 4, &d);
+    if (!out) return nullptr;
+    if (wo_ocean_download(p, key, d, (int64_t)(n * 4))) return throw_wo(env, "oceanDownload");
+    return out;
+}
 // landComponents(numRegions, adjOffset, adjList, r_isOcean) -> Int32Array (label = smallest id of the landmass, -1 for ocean)
 napi_value LandComponents(napi_env env, napi_callback_info info) {
     Args a(env, info);
@@ -662,6 +709,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"diffuseOceanWarmth", DiffuseOceanWarmth}, {"computeWindConvergence", WindConvergence}, {"advectMoisture", AdvectMoisture},
         {"landComponents", LandComponents}, {"sampleHeightmap", SampleHeightmap}, {"syntheticPlates", SyntheticPlates},
         {"classifyRegions", ClassifyRegions}, {"triangleCenters", TriangleCenters}, {"computeWind", ComputeWind}, {"computeGradients", ComputeGradients},
+        {"windUpload", WindUpload}, {"computeOceanCurrents", ComputeOceanCurrents}, {"oceanDownload", OceanDownload},
         {"commUniqueId", CommUniqueId}, {"commCreate", CommCreate}, {"planetSetHalo", PlanetSetHalo},
         {"planetExchangeAllgather", PlanetExchangeAllgather}, {"planetExchangeNeighbors", PlanetExchangeNeighbors}, {"planetSetFloodExchange", PlanetSetFloodExchange},
     };

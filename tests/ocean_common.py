@@ -1,0 +1,129 @@
+"""Shared pieces of the ocean-current tests: the golden cases with their inputs, the host emulator of csrc/ocean_ops.h
+(tests/emu_ocean, built on first use) and the comparison.  The bar is bit equality on all eight outputs, with no tolerance: the
+stage reads only wind outputs that are exact, calls no libm function but sqrt, and its distance fields are hop counts."""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import re
+import subprocess
+from functools import lru_cache
+
+import numpy as np
+
+import wind_common as WC
+from conftest import GOLDEN, REPO
+
+EMU_DIR = REPO / "tests" / "emu_ocean"
+GOLDEN_CASES = ("ocean_config1_N10000_s1", "ocean_import_N10000_s1", "ocean_N2000_ocean_s1", "ocean_N2000_land_s1", "ocean_N10000_wedge_s1",
+                "ocean_N250000_s4")
+WIND_INPUTS = ("r_lat", "r_lon", "r_isLand", "r_eastX", "r_eastY", "r_eastZ", "itczLons", "itczLatsSummer", "itczLatsWinter")
+_emu = []
+ptr, crc, same_bits, Mesh = WC.ptr, WC.crc, WC.same_bits, WC.Mesh
+
+
+def result_fields():
+    from planet_heightmap_generation_amd import ocean as OC
+    return OC.RESULT_FIELDS
+
+
+def emu():
+    if not _emu:
+        subprocess.run(["make", "-s", "-C", str(EMU_DIR)], check=True)
+        _emu.append(C.CDLL(str(EMU_DIR / "_build" / "libemu_ocean.so")))
+    return _emu[0]
+
+
+def logged(meta):
+    """The numbers the reference logged during the call (js/ocean.js:243, :371), in the form of ocean.info; p95 stays the logged
+    text (toExponential(3))."""
+    text = "\n".join(meta["log"])
+    m = re.search(r"Circumpolar: NH=(true|false), SH=(true|false)", text)
+    out = dict(circumpolarNH=m.group(1) == "true", circumpolarSH=m.group(2) == "true")
+    for s in ("summer", "winter"):
+        m = re.search(rf"\[Ocean {s}\] coastThreshold=(\d+), warmthRange=(\d+), p95=(\S+), oceanCells=(\d+)", text)
+        out["coastThreshold"], out["warmthRange"] = int(m.group(1)), int(m.group(2))
+        out[f"p95{s.capitalize()}"], out[f"oceanCells{s.capitalize()}"] = m.group(3), int(m.group(4))
+    return out
+
+
+def to_exponential3(v: float) -> str:
+    """Number.prototype.toExponential(3) of a positive f32 value"""
+    mant, exp = f"{float(v):.3e}".split("e")
+    return f"{mant}e{'+' if int(exp) >= 0 else '-'}{abs(int(exp))}"
+
+
+def info_matches_log(info, meta):
+    want = logged(meta)
+    got = dict(info, p95Summer=to_exponential3(info["p95Summer"]), p95Winter=to_exponential3(info["p95Winter"]))
+    return {k: (got[k], v) for k, v in want.items() if got[k] != v}
+
+
+@lru_cache(maxsize=None)
+def golden_case(name):
+    """A wind_common case (mesh, positions, terrain, plates, seed) with ref (the eight outputs: every meta['stride']-th cell
+    unless the fixture keeps them whole), meta, and wind (the nine wind outputs the stage reads, whole).  The sparse fixture
+    keeps only the checksums of the per-cell wind inputs: they are rebuilt by the wind emulator, which reproduces these fields
+    bit for bit (tests/test_wind.py), and checked against the checksums."""
+    g = np.load(GOLDEN / f"{name}.npz")
+    meta = json.loads(bytes(g["meta_json"]).decode())
+    if meta["planet"] is not None:
+        base = WC.golden_case(meta["planet"])
+    else:
+        m = np.load(GOLDEN / "mesh_N10000_s1.npz")
+        base = WC.make_case(name, WC.Mesh(m["ref_adjOffset"], m["ref_adjList"]), m["xyz"], g["in_e"], g["in_plate"], g["in_ocean"], seed=meta["seed"])
+    wind = {k: g[f"win_{k}"] for k in WIND_INPUTS if f"win_{k}" in g.files}
+    if len(wind) < len(WIND_INPUTS):
+        own = WC.emulate(base)
+        for k in WIND_INPUTS:
+            wind.setdefault(k, own[k])
+    for k in WIND_INPUTS:
+        assert crc(wind[k]) == meta["crc_inputs"][k], f"{name}: {k} is not the reference's"
+    ref = {k[4:]: g[k] for k in g.files if k.startswith("ref_")}
+    return dict(base, name=name, ref=ref, meta=meta, wind=wind)
+
+
+def emulate(case, wind=None, max_depth="truncated", order_seed=0):
+    """The whole stage on the host from the nine wind inputs (default: the case's own).  max_depth: 'truncated' builds the
+    distance fields to warmthRange - 1 as the device does, None runs them to exhaustion as the reference does.  Returns the eight
+    arrays plus _info (as ocean.info) and _dist (west, east)."""
+    wind = case["wind"] if wind is None else wind
+    N = case["N"]
+    c32 = lambda k, ty=np.float32: np.ascontiguousarray(wind[k], ty)  # noqa: E731
+    w = {k: c32(k) for k in WIND_INPUTS if k != "r_isLand"}
+    land = c32("r_isLand", np.uint8)
+    if max_depth == "truncated":
+        max_depth = 2 * max(5, int(np.floor(np.sqrt(float(N)) * 0.035 + 0.5))) - 1
+    out = {k: np.zeros(N, ty) for k, ty in result_fields()}
+    arr = (C.c_void_p * len(out))(*[ptr(a) for a in out.values()])
+    info, p95, dist = np.zeros(8, np.int32), np.zeros(2, np.float32), np.zeros(2 * N, np.int32)
+    emu().emu_ocean(C.c_int32(N), ptr(case["off"]), ptr(case["adj"]), ptr(case["xyz"]), ptr(w["r_lat"]), ptr(w["r_lon"]), ptr(land), ptr(w["r_eastX"]),
+                    ptr(w["r_eastY"]), ptr(w["r_eastZ"]), ptr(w["itczLatsSummer"]), ptr(w["itczLatsWinter"]), C.c_int32(-1 if max_depth is None else max_depth),
+                    C.c_uint64(order_seed), arr, ptr(info), ptr(p95), ptr(dist))
+    from planet_heightmap_generation_amd import ocean as OC
+    out["_info"] = dict(zip(OC.INFO_FIELDS, [bool(info[0]), bool(info[1])] + [int(v) for v in info[2:]] + [float(p95[0]), float(p95[1])]))
+    out["_dist"] = (dist[:N].copy(), dist[N:].copy())
+    return out
+
+
+def differing(got, ref, stride=1, crcs=None):
+    """{key: cells that differ} over the eight outputs (or 'crc' where only the checksum of the whole array differs)"""
+    bad = {}
+    for k, _ in result_fields():
+        g = got[k] if ref[k].size == got[k].size else got[k][::stride]
+        if not same_bits(g, ref[k]):
+            bad[k] = int((np.ascontiguousarray(g).view(np.uint32) != np.ascontiguousarray(ref[k]).view(np.uint32)).sum()) if g.shape == ref[k].shape else "shape"
+        elif crcs is not None and crc(got[k]) != crcs[k]:
+            bad[k] = "crc"
+    return bad
+
+
+def assert_equal(label, got, ref, stride=1, crcs=None):
+    bad = differing(got, ref, stride, crcs)
+    print(f"{label}: " + ("all eight outputs equal bit for bit" if not bad else f"cells that differ: {bad}"))
+    assert not bad, f"{label}: {bad}"
+
+
+def assert_golden(label, got, case):
+    m = case["meta"]
+    assert_equal(label, got, case["ref"], m["stride"], m["crc"] if m["stride"] > 1 else None)

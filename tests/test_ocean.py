@@ -1,0 +1,119 @@
+"""computeOceanCurrents (js/ocean.js:204-382) without a GPU: the host emulator of csrc/ocean_ops.h (tests/emu_ocean drives the very
+bodies the kernels of csrc/ocean.hip run) against the reference's goldens, bit for bit; what the reference logged; the licence for
+building the distance fields only to depth warmthRange - 1; the order independence of those fields; the Python argument checks.
+
+The device itself is held to the same goldens in test_gpu_ocean.py."""
+import numpy as np
+import pytest
+
+import ocean_common as OC
+
+
+@pytest.mark.parametrize("name", OC.GOLDEN_CASES)
+def test_emulator_matches_reference(name):
+    """All eight outputs bit for bit (the sparse case on the stored cells and on the checksums of the whole arrays), and the flags,
+    threshold, range, ocean counts and p95 the reference logged."""
+    case = OC.golden_case(name)
+    assert set(case["ref"]) == {k for k, _ in OC.result_fields()} == set(case["meta"]["keys"]) - {"_oceanTiming"}
+    assert case["meta"]["exports"] == ["computeOceanCurrents"]
+    out = OC.emulate(case)
+    print(f"{name}: {out['_info']}")
+    OC.assert_golden(name, out, case)
+    assert not OC.info_matches_log(out["_info"], case["meta"])
+
+
+def test_goldens_cover_the_branches():
+    """What each case is there for."""
+    flags = {n: (OC.logged(OC.golden_case(n)["meta"])["circumpolarNH"], OC.logged(OC.golden_case(n)["meta"])["circumpolarSH"]) for n in OC.GOLDEN_CASES}
+    assert flags["ocean_config1_N10000_s1"] == (True, True) and flags["ocean_import_N10000_s1"] == (False, False)
+    assert flags["ocean_N10000_wedge_s1"] == (True, False)
+    assert OC.logged(OC.golden_case("ocean_N250000_s4")["meta"])["coastThreshold"] == 18
+    assert OC.logged(OC.golden_case("ocean_config1_N10000_s1")["meta"])["oceanCellsSummer"] == 7320
+    wedge = OC.golden_case("ocean_N10000_wedge_s1")
+    assert int((wedge["e"] > 0).sum()) == 74
+    # no coast at all: no seed, every distance -1, warmth all 0, and at 2 001 cells not every 5-degree bin holds a cell
+    sea = OC.golden_case("ocean_N2000_ocean_s1")
+    out = OC.emulate(sea, max_depth=None)
+    assert (out["_dist"][0] == -1).all() and (out["_dist"][1] == -1).all()
+    assert not sea["ref"]["r_ocean_warmth_summer"].any() and not sea["ref"]["r_ocean_warmth_winter"].any()
+    assert flags["ocean_N2000_ocean_s1"] == (False, False) and np.abs(sea["ref"]["r_ocean_current_east_summer"]).max() > 0.5
+    # no ocean cell: the percentile's empty-array branch, every output 0
+    land = OC.golden_case("ocean_N2000_land_s1")
+    assert OC.logged(land["meta"])["oceanCellsSummer"] == 0 and OC.logged(land["meta"])["p95Summer"] == "1.000e+0"
+    assert all(not land["ref"][k].any() for k, _ in OC.result_fields())
+
+
+@pytest.mark.parametrize("name", ["ocean_config1_N10000_s1", "ocean_N250000_s4"])
+def test_truncated_distance_fields_change_nothing(name):
+    """The distance fields run to exhaustion (the reference) and built only to depth warmthRange - 1 (the device) give the same
+    eight outputs: a distance is only compared with coastThreshold and with warmthRange."""
+    case = OC.golden_case(name)
+    full, cut = OC.emulate(case, max_depth=None), OC.emulate(case)
+    rng = cut["_info"]["warmthRange"]
+    for f, c in zip(full["_dist"], cut["_dist"]):
+        assert f.max() >= rng, "the complete field should reach beyond the truncation depth"
+        assert c.max() == rng - 1 and np.array_equal(c, np.where(f < rng, f, -1))
+    OC.assert_equal(f"{name}: truncated against complete", cut, full)
+    assert cut["_info"] == full["_info"]
+
+
+def _irregular_case(which):
+    import elev_inputs as EI
+    import wind_common as WC
+    ec = {"hub": lambda: EI.hub_case(20_000), "row_shuffled": lambda: EI.relabelled_case(20_000)}[which]()
+    case = WC.case_from_elev(ec, WC.plate_mask_elevation(ec, seed=11))
+    return dict(case, wind=WC.emulate(case))
+
+
+@pytest.mark.parametrize("which", ["ocean_config1_N10000_s1", "ocean_import_N10000_s1", "ocean_N10000_wedge_s1", "hub", "row_shuffled"])
+def test_distance_fields_are_order_independent(which):
+    """Seed lists and frontiers in three drawn orders (the interleavings of the device's threads) against the reference's FIFO
+    queue: the same distances, complete and truncated, and so the same outputs."""
+    case = OC.golden_case(which) if which.startswith("ocean_") else _irregular_case(which)
+    for depth in (None, "truncated"):
+        base = OC.emulate(case, max_depth=depth)
+        assert (base["_dist"][0] >= 0).any() and (base["_dist"][1] >= 0).any()
+        for seed in (1, 2, 3):
+            got = OC.emulate(case, max_depth=depth, order_seed=seed)
+            assert np.array_equal(got["_dist"][0], base["_dist"][0]) and np.array_equal(got["_dist"][1], base["_dist"][1]), f"distances differ under order {seed}"
+            OC.assert_equal(f"{which}: order {seed}", got, base)
+
+
+class _NoDevicePlanet:
+    """Stands where a Planet would: any use of its handle is a use of the device."""
+    numRegions = 100
+
+    @property
+    def handle(self):
+        raise AssertionError("device work was started")
+
+
+def test_python_argument_checks_refuse_before_device_work():
+    from planet_heightmap_generation_amd import ocean as OD
+    p, n = _NoDevicePlanet(), 100
+    xyz, e = np.zeros(3 * n, np.float32), np.zeros(n, np.float32)
+    wind = {k: np.zeros(360 if k.startswith("itcz") else n, np.uint8 if k == "r_isLand" else np.float32) for k in OD.WIND_INPUTS}
+    with pytest.raises(ValueError, match="r_xyz"):
+        OD.compute_ocean_currents(p, xyz[:-3], e)
+    with pytest.raises(ValueError, match="r_elevation"):
+        OD.compute_ocean_currents(p, xyz, e[:-1])
+    with pytest.raises(ValueError, match="r_lon"):
+        OD.compute_ocean_currents(p, xyz, e, {k: v for k, v in wind.items() if k != "r_lon"})
+    with pytest.raises(ValueError, match="r_eastX has 99 values"):
+        OD.compute_ocean_currents(p, xyz, e, dict(wind, r_eastX=np.zeros(n - 1, np.float32)))
+    with pytest.raises(KeyError):
+        OD.download(p, "_oceanTiming")
+    with pytest.raises(KeyError):
+        OD.upload_wind(p, "r_cosLat", e)
+    assert OD.WIND_INPUTS == OC.WIND_INPUTS
+    assert [k for k, _ in OD.RESULT_FIELDS] == [k for k in OC.golden_case("ocean_config1_N10000_s1")["meta"]["keys"] if k != "_oceanTiming"]
+
+
+def test_c_abi_refuses_null_planet():
+    """Status 1 and a message that names the entry point, never a dereference."""
+    from planet_heightmap_generation_amd import capi
+    L = capi.lib()
+    a = np.zeros(8, np.float32)
+    assert L.wo_compute_ocean_currents(None, 8, None) != 0 and "wo_compute_ocean_currents" in capi.last_error()
+    assert L.wo_ocean_download(None, b"r_ocean_speed_summer", capi.ptr(a), 32) != 0 and "wo_ocean_download" in capi.last_error()
+    assert L.wo_wind_upload(None, b"r_lat", capi.ptr(a), 32) != 0 and "wo_wind_upload" in capi.last_error()
