@@ -871,6 +871,11 @@ bool tree_pass2_chains(const TreeCtx& X, const int32_t* cells, int32_t n, int64_
         else { C.par[q] = -1; rootQ = q; ++nRoots; }
     }
     if (nRoots != 1) return false;
+    // The peak search below stops early because "a height never exceeds its cell's flood surface".  The carve's clamp at 0 (:189) keeps that
+    // only where no surface is negative: a cell of land below sea level (a mask that is not `elevation <= 0`) is LIFTED to 0 by the clamp, above
+    // its surface.  The seed cell has the lowest surface of the tree (pass 1: a claimed cell's surface is at least its claimant's): a tree
+    // whose seed lies below 0 takes the plain form.
+    if (surf(cells[rootQ]) < 0) return false;
     for (int32_t q = 0; q < n; ++q) C.kidStart[q + 1] += C.kidStart[q];
     C.kids.resize(n); C.order.resize(n);
     {   // children lists, then breadth-first order from the seed cell (parents before children)

@@ -16,7 +16,7 @@ from conftest import GOLDEN, REPO
 
 EMU_DIR = REPO / "tests" / "emu_ocean"
 GOLDEN_CASES = ("ocean_config1_N10000_s1", "ocean_import_N10000_s1", "ocean_N2000_ocean_s1", "ocean_N2000_land_s1", "ocean_N10000_wedge_s1",
-                "ocean_N250000_s4")
+                "ocean_N250000_s4", "ocean_N2000_edges_s1", "ocean_N63_shape_s1", "ocean_N255_shape_s1", "ocean_N256_shape_s1", "ocean_N4096_shape_s1")
 WIND_INPUTS = ("r_lat", "r_lon", "r_isLand", "r_eastX", "r_eastY", "r_eastZ", "itczLons", "itczLatsSummer", "itczLatsWinter")
 _emu = []
 ptr, crc, same_bits, Mesh = WC.ptr, WC.crc, WC.same_bits, WC.Mesh
@@ -70,8 +70,9 @@ def golden_case(name):
     if meta["planet"] is not None:
         base = WC.golden_case(meta["planet"])
     else:
-        m = np.load(GOLDEN / "mesh_N10000_s1.npz")
-        base = WC.make_case(name, WC.Mesh(m["ref_adjOffset"], m["ref_adjList"]), m["xyz"], g["in_e"], g["in_plate"], g["in_ocean"], seed=meta["seed"])
+        m = np.load(GOLDEN / f"{meta.get('mesh', 'mesh_N10000_s1')}.npz")          # a planet of its own: the mesh fixture it names, positions if it moves any
+        xyz = g["in_xyz"] if "in_xyz" in g.files else m["xyz"]
+        base = WC.make_case(name, WC.Mesh(m["ref_adjOffset"], m["ref_adjList"]), xyz, g["in_e"], g["in_plate"], g["in_ocean"], seed=meta["seed"])
     wind = {k: g[f"win_{k}"] for k in WIND_INPUTS if f"win_{k}" in g.files}
     if len(wind) < len(WIND_INPUTS):
         own = WC.emulate(base)

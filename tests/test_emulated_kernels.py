@@ -68,6 +68,34 @@ def test_emulated_ties_and_flats(emu, oracle):
         assert rc == 0 and np.array_equal(e, ref), (h, t, g_, int((e != ref).sum()))
 
 
+@pytest.mark.parametrize("land", [12000, 15000])
+def test_flood_and_erosion_of_land_below_sea_level(emu, oracle, land):
+    """A mask that is not `elevation <= 0`: land is the `land` highest of 20 001 cells, thousands of them below 0.  The carve's clamp
+    at 0 (js/terrain-post.js:189) then LIFTS a height, above its flood surface; the chain form of pass 2 (flood_host.cc:
+    tree_pass2_chains) ends its peak search on the strength of "no height exceeds its surface" and must leave such trees to the plain
+    form.  Both pass-1 routes of the host flood and the whole emulated erodeComposite against the oracle (which equals the reference
+    under Node on this planet), bit for bit."""
+    from planet_heightmap_generation_amd import sphere_mesh as S
+    mesh, xyz, nd = S.build_sphere(20000, 0.75, 4)
+    eq = (np.round(oracle.synthetic_terrain(xyz, 4) * 64) / 64).astype(np.float32)
+    oc = np.ones(eq.size, np.uint8)
+    oc[np.argsort(-eq, kind="stable")[:land]] = 0
+    assert int(((oc == 0) & (eq < 0)).sum()) > 5000
+    om = oracle.Mesh(mesh.adjOffset, mesh.adjList)
+    emu.emu_flood_host.argtypes = [C.c_int32] + [C.c_void_p] * 5 + [C.c_double, C.c_int32, C.c_int32, C.c_void_p]
+    ref = oracle.priority_flood_carve(om, eq, oc, 0.5)
+    assert (ref[oc == 0] != eq[oc == 0]).sum() > 1000
+    for mode in (0, 1):
+        e, stats = eq.copy(), np.zeros(11)
+        emu.emu_flood_host(mesh.numRegions, P(mesh.adjOffset), P(mesh.adjList), P(xyz), P(e), P(oc), 0.5, mode, 1, P(stats))
+        assert np.array_equal(e, ref), (mode, int((e != ref).sum()))
+    for h, t in ((1, 0), (0, 3), (3, 3)):                      # the mid-loop flood runs without hydraulic iterations too
+        ref = oracle.erode_composite(om, eq, xyz, oc, h, 3e-4, 0.5, 1.0, t, 1.16, 0.015, 0, 0.0, nd)
+        e, stats = eq.copy(), np.zeros(8)
+        rc = emu.emu_erode_composite(mesh.numRegions, P(mesh.adjOffset), P(mesh.adjList), P(e), P(xyz), P(oc), h, 3e-4, 0.5, 1.0, t, 1.16, 0.015, 0, 0.0, P(nd), P(stats))
+        assert rc == 0 and np.array_equal(e, ref), (h, t, int((e != ref).sum()))
+
+
 def test_flood_open_ocean_choice(emu, oracle):
     """The flood seeds only from the largest ocean component, the first one in cell order winning ties
     (js/terrain-post.js:66-94).  Masks with two equal oceans, with inland seas and with one ocean cell."""

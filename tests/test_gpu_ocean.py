@@ -97,6 +97,24 @@ def test_matches_emulator(which):
     OC.assert_equal(which, got, ref)
 
 
+@pytest.mark.parametrize("cells", WC.BOUNDARY_CELLS)
+def test_matches_emulator_at_sort_boundaries(cells):
+    """The planets of test_gpu_wind.py's test of this name (4 096, 131 072 and 131 073 cells): the device against the emulator fed
+    the device's own wind result."""
+    case = WC.boundary_case(cells)
+    pl = _planet(case)
+    try:
+        wind = _wind(pl, case, fields=OC.WIND_INPUTS)
+        got, info = _ocean(pl, case)
+    finally:
+        pl.close()
+    ref = OC.emulate(case, wind)
+    print(f"{cells} cells: device {info}, reached by the west / east field {int((ref['_dist'][0] >= 0).sum())} / {int((ref['_dist'][1] >= 0).sum())} cells")
+    assert info == ref["_info"]
+    assert (ref["_dist"][0] >= 0).sum() > cells // 100 and (ref["_dist"][1] >= 0).sum() > cells // 100 and np.abs(ref["r_ocean_warmth_summer"]).max() > 0.05
+    OC.assert_equal(f"{cells} cells", got, ref)
+
+
 def test_second_call_equals_fresh_planet():
     """Another terrain through computeWind on the same planet, then the stage again: what a fresh planet gives.  A repeat of the
     first pair of calls gives the first result."""

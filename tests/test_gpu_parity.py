@@ -940,6 +940,50 @@ def test_land_count_shrinks_and_grows_on_one_planet(TP, oracle):
     pl.close()
 
 
+@pytest.mark.parametrize("cells,counts", [(20000, (2049, 4097, 2048, 4096)), (200000, (131072, 131073, 131072, 131073))])
+def test_sorts_at_tile_and_group_boundaries(TP, oracle, cells, counts):
+    """The land count L is the pair count of both sorts of an iteration.  L exactly one tile of select_active_by_rank (2 048) and of
+    the radix sort (4 096: csrc/radix.hip), exactly one group of 32 radix tiles (131 072), and one pair more than each; the
+    field is quantised to 1/64, so runs of equal keys cross the tile seams.  All counts of a mesh run on one planet, up, down and
+    up again, which also crosses the rule that a sort starts on the group totals its predecessor cleared.  Bit for bit the C
+    oracle without the glacial passes; with them (L = 4 097) on the RMS bar of this file.  At 200 k cells the 131 072 highest
+    cells reach below sea level (56 181 lie above it): the mask is not `elevation <= 0` there, and the flood's clamp at 0 lifts
+    heights; this case found the chain form of the flood's pass 2 wrong on such land (46 014 cells off the oracle, fixed in
+    flood_host.cc: tree_pass2_chains; without a GPU: test_emulated_kernels.py)."""
+    from planet_heightmap_generation_amd import sphere_mesh as S
+    mesh, xyz, nd = S.build_sphere(cells, 0.75, 4)
+    om = oracle.Mesh(mesh.adjOffset, mesh.adjList)
+    eq = (np.round(oracle.synthetic_terrain(xyz, 4) * 64) / 64).astype(np.float32)
+    highest = np.argsort(-eq, kind="stable")
+    assert np.unique(eq).size < 200, "thousands of equal keys"
+    args = (3, 3e-4, 0.5, 1.0, 3, 1.16, 0.015, 0, 0.0)
+    refs = {}
+    pl = TP.Planet(mesh, xyz, nd)
+    try:
+        for L in counts:
+            oc = np.ones(eq.size, np.uint8)
+            oc[highest[:L]] = 0                                   # land is exactly the L highest cells
+            assert int((oc == 0).sum()) == L
+            if L not in refs:
+                refs[L] = oracle.erode_composite(om, eq, xyz, oc, *args, nd)
+                assert not np.array_equal(refs[L], eq)
+            got = eq.copy()
+            pl.erode_composite(got, oc, *args)
+            print(f"{eq.size} cells, L = {L}: cells that differ from the oracle {int((got != refs[L]).sum())}")
+            assert np.array_equal(got, refs[L]), (L, int((got != refs[L]).sum()))
+        if 4097 in counts:
+            glacial = args[:7] + (2, 0.5)
+            oc = np.ones(eq.size, np.uint8)
+            oc[highest[:4097]] = 0
+            ref = oracle.erode_composite(om, eq, xyz, oc, *glacial, nd)
+            got = eq.copy()
+            pl.erode_composite(got, oc, *glacial)
+            print(f"{eq.size} cells, L = 4097, two glacial passes: rms {rms(got, ref):.3e}, cells that differ {int((got != ref).sum())}")
+            assert rms(got, ref) < RMS_TOL
+    finally:
+        pl.close()
+
+
 def test_decomposed_shares_when_some_shares_have_no_land(TP, oracle):
     """More shares than landmasses: the land-less shares' erodeComposite calls do nothing but answer the flood exchange (the same
     number of calls as everybody else).  Merged == oracle."""

@@ -75,6 +75,43 @@ def test_matches_emulator(which):
     WC.compare(which, got, ref, case["N"])
 
 
+@pytest.mark.parametrize("cells", WC.BOUNDARY_CELLS)
+def test_matches_emulator_at_sort_boundaries(cells):
+    """Planets whose cell count, the launch shape of every kernel and the pair count of the geo index's radix sort, is exactly one
+    tile (4 096), exactly one group of 32 tiles (131 072), and one pair more."""
+    from planet_heightmap_generation_amd import wind as WD
+    case = WC.boundary_case(cells)
+    ref = WC.emulate(case)
+    pl = _planet(case)
+    try:
+        got = _device(pl, case)
+        levels = WD.bfs_levels(pl)
+    finally:
+        pl.close()
+    print(f"{cells} cells: land {(case['e'] > 0).mean():.3f}, BFS levels device {levels} emulator {ref['_levels']}")
+    assert levels == ref["_levels"]
+    WC.compare(f"{cells} cells", got, ref, case["N"])
+
+
+def test_edge_planet_values_need_no_reference():
+    """The check of test_wind.py's test of this name on the device's own outputs (all downloaded through wind_download): the poles,
+    the date line, lon = +-pi/2, the fallback frame, finite fields, the coast distance of a plain host BFS; then the ocean stage on
+    the resident block: every output finite."""
+    from planet_heightmap_generation_amd import ocean as OD, wind as WD
+    case = WC.golden_case("wind_N2000_edges_s1")
+    pl = _planet(case)
+    try:
+        _device(pl, case, e="host")
+        got = {k: WD.download(pl, k) for k, _ in WC.result_fields()}
+        sea = OD.compute_ocean_currents(pl, case["xyz"], case["e"])
+    finally:
+        pl.close()
+    WC.check_edge_values("device", got, case)
+    for k, v in sea.items():
+        assert np.isfinite(v).all(), k
+    assert np.abs(sea["r_ocean_current_east_summer"]).max() > 0.5
+
+
 def test_libm_sensitivity_1m():
     """The perturbed emulator at 1 M cells (K = 4 double ulps; all up, all down, two hashed draws): cells of any output that change,
     against a tenth of the cap.  DESIGN section 3 records the counts."""

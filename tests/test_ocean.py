@@ -43,7 +43,23 @@ def test_goldens_cover_the_branches():
     assert all(not land["ref"][k].any() for k, _ in OC.result_fields())
 
 
-@pytest.mark.parametrize("name", ["ocean_config1_N10000_s1", "ocean_N250000_s4"])
+def test_edge_planet_outputs_are_finite():
+    """Ocean cells on the date line (lon = -pi is half a step before the first ITCZ sample: the lookup wraps, js/climate-util.js:35)
+    and at a pole: every output finite, from the reference's wind inputs and from the wind emulator's."""
+    import wind_common as WC
+    case = OC.golden_case("ocean_N2000_edges_s1")
+    c = WC.edge_cells(case)
+    sea = case["e"] <= 0
+    assert sea[c["north"]].all() and sea[c["date_line"]].sum() == 3 and (np.signbit(case["xyz"].reshape(-1, 3)[c["date_line"], 0]) & sea[c["date_line"]]).any()
+    for label, wind in (("the reference's wind", case["wind"]), ("the emulator's wind", WC.emulate(case))):
+        out = OC.emulate(case, wind)
+        for k, _ in OC.result_fields():
+            assert np.isfinite(out[k]).all(), (label, k)
+        assert np.abs(out["r_ocean_current_east_summer"][c["date_line"]][sea[c["date_line"]]]).max() > 0
+        OC.assert_golden(f"edge planet from {label}", out, case)
+
+
+@pytest.mark.parametrize("name", ["ocean_config1_N10000_s1", "ocean_N250000_s4", "ocean_N2000_edges_s1", "ocean_N4096_shape_s1"])
 def test_truncated_distance_fields_change_nothing(name):
     """The distance fields run to exhaustion (the reference) and built only to depth warmthRange - 1 (the device) give the same
     eight outputs: a distance is only compared with coastThreshold and with warmthRange."""

@@ -16,10 +16,33 @@ def test_emulator_matches_reference(name):
     ref = case["ref"]
     assert set(ref) == {k for k, _ in WC.result_fields()} == set(case["meta"]["keys"]) - {"_windTiming"}
     if "ocean" not in name and "land" not in name:
-        assert np.ptp(ref["r_pressure_summer"]) > 10 and ref["r_wind_speed_winter"].max() == 1.0 and ref["r_coastDistLand"].max() >= 8
+        far = 8 if case["N"] >= 10_000 else 0               # a planet of 64 cells has no land eight hops from the sea: there, a coast at all
+        assert np.ptp(ref["r_pressure_summer"]) > 10 and ref["r_wind_speed_winter"].max() == 1.0 and ref["r_coastDistLand"].max() >= far
     out = WC.emulate(case)
     print(f"{name}: BFS levels (coast, plates) {out['_levels']}")
     WC.compare_golden(name, out, case)
+
+
+def test_edge_planet_values_need_no_reference():
+    """Cells exactly at the poles, on the date line and at lon = +-pi/2 (no Fibonacci planet has one): latitude, longitude and the
+    fallback frame from f64 numpy, every output finite, the coast distance from a plain host BFS.  The same check runs on the
+    device in test_gpu_wind.py."""
+    case = WC.golden_case("wind_N2000_edges_s1")
+    WC.check_edge_values("emulator", WC.emulate(case), case)
+    # the fixture reaches what it is there for: the bins before their clamp (js/wind.js:95-100) are 36 and 72 at the north pole and at
+    # lon = +pi, and -1 at the south pole and at lon = -pi (fl32(pi) lies above pi)
+    lat, lon = case["ref"]["r_lat"].astype(np.float64), case["ref"]["r_lon"].astype(np.float64)
+    assert np.floor((lat + np.pi / 2) / np.pi * 36).max() == 36 and np.floor((lon + np.pi) / (2 * np.pi) * 72).max() == 72
+    assert np.floor((lat + np.pi / 2) / np.pi * 36).min() == -1 and np.floor((lon + np.pi) / (2 * np.pi) * 72).min() == -1
+    land = case["e"] > 0
+    c = WC.edge_cells(case)
+    moved = np.unique(np.concatenate(list(c.values())))
+    assert land[moved].any() and not land[moved].all() and abs(land.mean() - 0.315) < 0.002, "the moved cells lie on both sides of the coast"
+
+
+def test_shape_planets_sit_on_the_launch_boundaries():
+    """64, 256, 257 and 4 097 cells: one wave, one 256-thread block, one block and a cell, one 4 096-pair radix tile and a pair."""
+    assert [WC.golden_case(f"wind_N{n}_shape_s1")["N"] for n in (63, 255, 256, 4096)] == [64, 256, 257, 4097]
 
 
 def test_degenerate_planets():

@@ -19,7 +19,8 @@ import numpy as np
 from conftest import GOLDEN, REPO
 
 EMU_DIR = REPO / "tests" / "emu_wind"
-GOLDEN_CASES = ("wind_config1_N10000_s1", "wind_import_N10000_s1", "wind_N2000_ocean_s1", "wind_N2000_land_s1", "wind_N250000_s4")
+GOLDEN_CASES = ("wind_config1_N10000_s1", "wind_import_N10000_s1", "wind_N2000_ocean_s1", "wind_N2000_land_s1", "wind_N250000_s4",
+                "wind_N2000_edges_s1", "wind_N63_shape_s1", "wind_N255_shape_s1", "wind_N256_shape_s1", "wind_N4096_shape_s1")
 SEASON_FIELDS = tuple(f"r_{k}_{s}" for s in ("summer", "winter") for k in ("pressure", "wind_east", "wind_north", "wind_speed"))
 ULP_BOUND = 4 * 2.0 ** -23
 HOOK_K = 4                          # double ulps: twice the 2-ulp bound of ocml's double exp / sin / cos
@@ -73,7 +74,13 @@ def golden_case(name):
         off, adj, xyz, e, plate, ocean = m["ref_adjOffset"], m["ref_adjList"], m["xyz"], s["done_r_elevation"], s["done_r_plate"], s["done_plateIsOcean"]
     elif name.startswith("wind_N2000_"):
         m = np.load(GOLDEN / "mesh_N2000_s1.npz")
-        off, adj, xyz, e, plate, ocean = m["ref_adjOffset"], m["ref_adjList"], m["xyz"], g["in_e"], g["in_plate"], g["in_ocean"]
+        xyz = g["in_xyz"] if "in_xyz" in g.files else m["xyz"]      # the edge planet moves twelve cells of the mesh
+        off, adj, e, plate, ocean = m["ref_adjOffset"], m["ref_adjList"], g["in_e"], g["in_plate"], g["in_ocean"]
+    elif name.endswith("_shape_s1"):
+        from plates_common import reference_mesh
+        mesh, xyz = reference_mesh(meta["mesh_N"], 0.75, meta["seed"])      # keeps no mesh: rebuilt, checksums checked
+        assert crc(np.asarray(xyz, np.float32)) == meta["crc_xyz"] and crc(mesh.adjOffset) == meta["crc_adjOffset"] and crc(mesh.adjList) == meta["crc_adjList"]
+        off, adj, e, plate, ocean = mesh.adjOffset, mesh.adjList, g["in_e"], g["in_plate"], g["in_ocean"]
     else:
         from plates_common import reference_mesh
         s = np.load(GOLDEN / "elev_N250000_s4_large.npz")           # keeps no mesh: rebuilt the way the reference harness did, checksums checked
@@ -217,3 +224,90 @@ def synthetic_case(N, seed=3, e=None, poles=48):
     for s in range(0, P.shape[0], 1 << 20):
         plate[s:s + (1 << 20)] = np.argmax(P[s:s + (1 << 20)] @ pole.T.astype(np.float32), axis=1)
     return make_case(f"synthetic_N{N}", mesh, xyz, e, plate * 1000 + 7, np.arange(0, poles, 3, dtype=np.int32) * 1000 + 7, seed=seed)
+
+
+def host_coast_distance(case):
+    """r_coastDistLand restated plainly (js/wind.js:485-541): the ocean components over non-land cells, the largest one (the
+    first found among equals, scanning the cells in ascending order) is the main ocean, land cells that touch it are at distance 0,
+    and a FIFO queue walks the land from them."""
+    from collections import deque
+    N, off, adj = case["N"], case["off"], case["adj"]
+    land = case["e"] > 0
+    label, best, main = np.full(N, -1, np.int64), 0, -1
+    for r in range(N):
+        if land[r] or label[r] >= 0:
+            continue
+        label[r], size, q = r, 0, deque([r])
+        while q:
+            c = q.popleft()
+            size += 1
+            for nb in adj[off[c]:off[c + 1]]:
+                if not land[nb] and label[nb] < 0:
+                    label[nb] = r
+                    q.append(nb)
+        if size > best:
+            best, main = size, r
+    dist, q = np.full(N, -1, np.int32), deque()
+    for r in np.flatnonzero(land):
+        if main >= 0 and any(not land[nb] and label[nb] == main for nb in adj[off[r]:off[r + 1]]):
+            dist[r] = 0
+            q.append(r)
+    while q:
+        c = q.popleft()
+        for nb in adj[off[c]:off[c + 1]]:
+            if land[nb] and dist[nb] < 0:
+                dist[nb] = dist[c] + 1
+                q.append(nb)
+    return dist
+
+
+def edge_cells(case):
+    """The cells of the edge planet by what their f32 position is: dict of index arrays."""
+    x, y, z = case["xyz"].reshape(-1, 3).T
+    return dict(north=np.flatnonzero((y == 1) & (x == 0) & (z == 0)), south=np.flatnonzero(y == -1), near_pole=np.flatnonzero((y == 1) & (x != 0)),
+                equator=np.flatnonzero(y == 0), date_line=np.flatnonzero((x == 0) & (z < 0)), quarter=np.flatnonzero((z == 0) & (x != 0)))
+
+
+def check_edge_values(label, got, case):
+    """What the outputs must be at the poles, on the date line and at lon = +-pi/2, from f64 numpy rounded to f32 and from the
+    fallback of the tangent frame (js/wind.js:430-433); no reference output is read.  `got`: wind outputs (all of RESULT_FIELDS)."""
+    c = edge_cells(case)
+    x, y, z = case["xyz"].reshape(-1, 3).T
+    assert [c[k].size for k in ("north", "south", "near_pole", "equator", "date_line", "quarter")] == [1, 1, 1, 4, 6, 3], {k: v.tolist() for k, v in c.items()}
+    half_pi, pi = np.float32(np.pi / 2), np.float32(np.pi)
+    lat, lon = got["r_lat"], got["r_lon"]
+    poles = np.concatenate([c["north"], c["south"]])
+    assert same_bits(lat[poles], np.array([half_pi, -half_pi], np.float32)), lat[poles]
+    assert same_bits(lat[c["near_pole"]], np.array([half_pi], np.float32))
+    assert same_bits(lat[c["equator"]], np.zeros(4, np.float32)), lat[c["equator"]]                    # +0, not -0: asin(+0)
+    d = c["date_line"]
+    assert np.signbit(x[d]).sum() == 3, "the date-line cells should have x = -0 and x = +0"
+    assert same_bits(lon[d], np.where(np.signbit(x[d]), -pi, pi).astype(np.float32)), lon[d]
+    q = c["quarter"]
+    assert np.signbit(z[q]).any() and not np.signbit(z[q]).all(), "z = -0 and z = +0"
+    assert same_bits(lon[q], np.where(x[q] > 0, half_pi, -half_pi).astype(np.float32)), lon[q]
+    assert same_bits(lon[c["north"]], np.zeros(1, np.float32))
+    everywhere = np.arctan2(x.astype(np.float64), z.astype(np.float64)).astype(np.float32), np.arcsin(y.astype(np.float64)).astype(np.float32)
+    off = [int((np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64)) > 1).sum()) for a, b in zip((lon, lat), everywhere)]
+    print(f"{label}: cells whose r_lon / r_lat is more than one f32 step from numpy's f64 atan2 / asin: {off}")
+    assert off == [0, 0]
+    for k, want in (("r_eastX", 1), ("r_eastY", 0), ("r_eastZ", 0)):
+        assert same_bits(got[k][poles], np.full(2, want, np.float32)), (k, got[k][poles])
+    for k, want in (("r_northX", np.zeros(2, np.float32)), ("r_northY", z[poles]), ("r_northZ", -y[poles])):     # north = p x (1, 0, 0) = (0, z, -y), of length 1 in f64
+        assert np.array_equal(got[k][poles], want), (k, got[k][poles])
+    n = c["near_pole"]                                                                                 # (1e-10, 1, 1e-10): the frame proper, east = (z, 0, -x) / |.|
+    assert abs(float(got["r_eastX"][n[0]]) - np.sqrt(0.5)) < 1e-6 and abs(float(got["r_eastZ"][n[0]]) + np.sqrt(0.5)) < 1e-6
+    for k, _ in result_fields():
+        assert np.isfinite(got[k]).all(), f"{label}: {k} is not finite in {np.flatnonzero(~np.isfinite(got[k]))[:8]}"
+    assert np.array_equal(got["r_coastDistLand"], host_coast_distance(case))
+
+
+BOUNDARY_CELLS = (4096, 131072, 131073)     # one radix tile of 4 096 pairs exactly; one group of 32 tiles exactly; one group and a pair
+
+
+@lru_cache(maxsize=None)
+def boundary_case(cells):
+    """synthetic_case with exactly `cells` cells (build_sphere adds the closing cell to the count it is given)."""
+    case = synthetic_case(cells - 1)
+    assert case["N"] == cells
+    return case

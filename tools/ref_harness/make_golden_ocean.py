@@ -15,6 +15,8 @@ Cases (the planet of a wind fixture is not stored twice; `planet` in the metadat
   ocean_N2000_land_s1       planet of wind_N2000_land_s1: no ocean cell, the percentile's empty-array branch
   ocean_N10000_wedge_s1     mesh_N10000_s1, every cell at -0.5 except a land wedge at +0.25 where -72 deg < lat < -48 deg and
                             0 deg < lon < 25 deg (74 cells); one plate, oceanic.  The circumpolar flags differ per hemisphere.
+  ocean_N2000_edges_s1      planet of wind_N2000_edges_s1: cells at both poles, on the date line and at lon = +-pi/2
+  ocean_N{63,255,256,4096}_shape_s1   planets of wind_N{...}_shape_s1: 64, 256, 257 and 4 097 cells
   ocean_N250000_s4          planet of wind_N250000_s4, the only one with coastThreshold 18; stored sparse as that fixture is:
                             every 16th cell plus the CRC32 of each whole array (the ITCZ arrays in full; the per-cell wind
                             inputs as CRC32 only: wind_N250000_s4 holds their samples)
@@ -64,14 +66,15 @@ def wedge_case():
 def cases(only=None):
     out = []
     want = lambda name: only in (None, name)  # noqa: E731
-    wind = {c["name"]: c for c in MW.cases()} if only != "ocean_N10000_wedge_s1" else {}
+    wind = {c["name"]: c for c in MW.cases(None if only is None else "wind_" + only[len("ocean_"):])} if only != "ocean_N10000_wedge_s1" else {}
     for k, c in wind.items():
         name = "ocean_" + k[len("wind_"):]
         if want(name):
             out.append(dict(c, name=name, planet=k, store=()))
     if want("ocean_N10000_wedge_s1"):
         out.append(wedge_case())
-    order = ["ocean_config1_N10000_s1", "ocean_import_N10000_s1", "ocean_N2000_ocean_s1", "ocean_N2000_land_s1", "ocean_N10000_wedge_s1", "ocean_N250000_s4"]
+    order = ["ocean_config1_N10000_s1", "ocean_import_N10000_s1", "ocean_N2000_ocean_s1", "ocean_N2000_land_s1", "ocean_N10000_wedge_s1", "ocean_N250000_s4",
+             "ocean_N2000_edges_s1"] + [f"ocean_N{n}_shape_s1" for n in MW.SHAPE_SIZES]
     return sorted(out, key=lambda c: order.index(c["name"]))
 
 

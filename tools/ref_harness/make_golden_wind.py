@@ -11,6 +11,10 @@ Cases (inputs that another fixture already holds are not stored twice):
   wind_N2000_land_s1       mesh_N2000_s1, every cell at 0.25, four plates, none oceanic
   wind_N250000_s4          the planet of elev_N250000_s4_large.npz (mesh rebuilt, checksums checked); r_coastDistLand and the
                            ITCZ arrays in full, every other output as its CRC32 plus every 16th cell
+  wind_N2000_edges_s1      mesh_N2000_s1 with twelve cells moved (by less than a cell spacing) onto the poles, the date line and
+                           lon = +-pi/2 (EDGE_TARGETS), the terrain and plates of rule_terrain / band_plates; positions stored
+  wind_N{63,255,256,4096}_shape_s1   reference_mesh(N, 0.75, 1): 64, 256, 257 and 4 097 cells (one wave, one block, one block and a
+                           cell, one radix tile and a pair), the same terrain and plate rule; the mesh is not stored, its CRC32s are
 
 Usage:  python tools/ref_harness/make_golden_wind.py [--ref /root/reference] [--only NAME] [--time-cells N]
   --time-cells N   no fixture is written: the reference's wall time of computeWind on the N-cell planet of
@@ -43,8 +47,76 @@ def crc(a) -> int:
     return zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
 
 
-def cases():
+def _f32(v) -> float:
+    return float(np.float32(v))
+
+
+def edge_targets():
+    """Positions (f64 values of exact f32 numbers) that no Fibonacci planet has: both poles (the south one through the tangent
+    frame's fallback with non-zero x and z), one just outside the fallback, one at the largest |y| below 1, lon = +-pi/2 with
+    z = +-0, and six cells on the date line whose x alternates between -0 and +0."""
+    t = [(0.0, 1.0, 0.0), (1e-11, -1.0, -5e-11), (1.0, 0.0, 0.0), (-1.0, 0.0, -0.0)]
+    for i, deg in enumerate((-60, -30, 0, 30, 60, 80)):
+        y = _f32(np.sin(np.radians(deg)))
+        t.append((-0.0 if i % 2 == 0 else 0.0, y, -_f32(np.sqrt(1 - y * y))))
+    y = float(np.nextafter(np.float32(1), np.float32(0)))
+    t.append((_f32(np.sqrt(1 - y * y)), y, 0.0))                    # |y| one f32 step under 1, z = +0 in the northern cap
+    t.append((1e-10, 1.0, 1e-10))                                    # |(x, z)| = 1.41e-10: the first frame past the fallback
+    return np.array(t, np.float64).astype(np.float32)
+
+
+def snap_to_targets(xyz, targets):
+    """For each target in turn, the nearest cell not used yet and not the closing cell (0, 0, 1) is moved onto it."""
+    P = np.array(xyz, np.float32).reshape(-1, 3)
+    closing = np.flatnonzero((P == np.array([0, 0, 1], np.float32)).all(axis=1))
+    used, moved = set(closing.tolist()), []
+    for t in targets:
+        d = np.linalg.norm(P.astype(np.float64) - t.astype(np.float64), axis=1)
+        d[list(used)] = np.inf
+        r = int(np.argmin(d))
+        moved.append((r, float(d[r])))
+        used.add(r)
+        P[r] = t
+    return P.reshape(-1), moved
+
+
+def rule_terrain(xyz):
+    """Land (+0.25) where sin(3 lon + 1) cos(2 lat) > 0.25 or lat < -70 degrees, ocean (-0.5) elsewhere."""
+    P = np.asarray(xyz, np.float32).reshape(-1, 3).astype(np.float64)
+    lat, lon = np.arcsin(np.clip(P[:, 1], -1, 1)), np.arctan2(P[:, 0], P[:, 2])
+    land = (np.sin(3 * lon + 1) * np.cos(2 * lat) > 0.25) | (lat < np.radians(-70))
+    return np.where(land, 0.25, -0.5).astype(np.float32)
+
+
+def band_plates(n):
+    """Plate ids 0, 7, 14, 21 in four bands of cells; 0 and 14 are oceanic."""
+    return (np.arange(n, dtype=np.int32) * 4 // n).astype(np.int32) * 7, np.array([0, 14], np.int32)
+
+
+SHAPE_SIZES = (63, 255, 256, 4096)
+
+
+def cases(only=None):
     out = []
+    want = lambda name: only in (None, name)  # noqa: E731
+    if want("wind_N2000_edges_s1"):
+        m = np.load(GOLD / "mesh_N2000_s1.npz")
+        xyz, moved = snap_to_targets(m["xyz"], edge_targets())
+        print("wind_N2000_edges_s1: cells moved (cell, distance): " + ", ".join(f"{r} {d:.3f}" for r, d in moved))
+        assert max(d for _, d in moved) < 0.07
+        plate, ocean = band_plates(xyz.size // 3)
+        out.append(dict(name="wind_N2000_edges_s1", off=m["ref_adjOffset"], adj=m["ref_adjList"], xyz=xyz, e=rule_terrain(xyz), plate=plate, ocean=ocean, seed=1,
+                        store=("xyz", "e", "plate", "ocean"), sparse=False, extra=dict(mesh="mesh_N2000_s1", moved=[r for r, _ in moved])))
+    for n in SHAPE_SIZES:
+        if want(f"wind_N{n}_shape_s1"):
+            from plates_common import reference_mesh
+            mesh, xyz = reference_mesh(n, 0.75, 1)
+            plate, ocean = band_plates(mesh.numRegions)
+            out.append(dict(name=f"wind_N{n}_shape_s1", off=mesh.adjOffset, adj=mesh.adjList, xyz=xyz, e=rule_terrain(xyz), plate=plate, ocean=ocean, seed=1,
+                            store=("e", "plate", "ocean"), sparse=False,
+                            extra=dict(mesh_N=n, crc_xyz=crc(np.asarray(xyz, np.float32)), crc_adjOffset=crc(mesh.adjOffset), crc_adjList=crc(mesh.adjList))))
+    if only is not None and out:
+        return out
     g = np.load(GOLD / "elev_config1_N10000_s1.npz")
     out.append(dict(name="wind_config1_N10000_s1", off=g["adjOffset"], adj=g["adjList"], xyz=g["xyz"], e=g["ref_final_elevation"], plate=g["r_plate"],
                     ocean=g["plateSeeds"][g["plateIsOcean"] == 1], seed=1, store=(), sparse=False))
@@ -98,7 +170,7 @@ def run(ref: Path, cs, write: bool):
                 continue
             data = {}
             info = dict(exports=meta["exports"], keys=cm["keys"], arrays=cm["arrays"], seed=c["seed"], axialTilt=23.5, numRegions=int(len(c["off"]) - 1),
-                        ref_ms=cm["ms"], stride=STRIDE if c["sparse"] else 1, crc={})
+                        ref_ms=cm["ms"], stride=STRIDE if c["sparse"] else 1, crc={}, **c.get("extra", {}))
             for name, ty in cm["arrays"].items():
                 a = np.fromfile(work / f"{k}_o_{name}.bin", TYPES[ty])
                 info["crc"][name] = crc(a)
@@ -121,7 +193,7 @@ def main():
     if args.time_cells:
         run(Path(args.ref), [timing_case(args.time_cells)], write=False)
         return
-    cs = [c for c in cases() if args.only in (None, c["name"])]
+    cs = [c for c in cases(args.only) if args.only in (None, c["name"])]
     run(Path(args.ref), cs, write=True)
 
 
