@@ -61,6 +61,10 @@ int         wo_abi_version(void);
 const char* wo_last_error(void);
 /* number of usable HIP devices (0 when none / no driver); never fails */
 int         wo_device_count(void);
+/* What the library holds at this moment, over all contexts and planets of the process: bytes of device memory, bytes of
+ * pinned host memory, and the number of allocations it has made so far (a call that leaves this number as it was
+ * allocated nothing).  Any pointer may be NULL; returns 0. */
+int         wo_memory_in_use(int64_t* deviceBytes, int64_t* pinnedBytes, int64_t* allocCalls);
 
 /* ------------------------------------------------ host-side input producers (no GPU needed) --- */
 /* generateFibonacciSphere + pole append: js/sphere-mesh.js:9-37,179-181.  r_xyz has 3*(N+1) floats;

@@ -32,6 +32,7 @@ SIGNATURES = {
     "wo_abi_version": (C.c_int, []),
     "wo_last_error": (C.c_char_p, []),
     "wo_device_count": (C.c_int, []),
+    "wo_memory_in_use": (C.c_int, [_p, _p, _p]),
     "wo_fib_sphere_points": (C.c_int, [_c_i32, _c_f64, _c_f64, _p]),
     "wo_sphere_delaunay": (C.c_int, [_c_i32, _p, _p, _p]),
     "wo_mesh_csr": (C.c_int, [_c_i32, _c_i32, _p, _p, _p, _p, _p]),

@@ -386,12 +386,15 @@ void basin_alloc(wo_planet* p) {
     const int32_t N = p->N;
     hipStream_t s = cur_stream(p);
     if (!p->d_basinJ) {
-        WO_HIP(hipMalloc((void**)&p->d_basinJ, (size_t)N * 4));
-        WO_HIP(hipMalloc((void**)&p->d_basinSlot, (size_t)N * 4));
-        WO_HIP(hipMalloc((void**)&p->d_basinKey, (size_t)N * 4));
-        WO_HIP(hipMalloc((void**)&p->d_basinVals[0], (size_t)N * 4)); WO_HIP(hipMalloc((void**)&p->d_basinVals[1], (size_t)N * 4));   // own buffers: the layout runs beside the flow accumulation, whose rounds use the planet's lists
-        WO_HIP(hipMalloc((void**)&p->d_basinRange, ((size_t)N / 64 + 8 + WO_LONG_MAX) * 4));        // range starts, then {count, long ranges}
-        WO_HIP(hipMalloc((void**)&p->d_basinLong, (size_t)N / 64 + 8));
+        // built in an arena of its own and handed to the planet's whole; basinJ, assigned last, says that the buffers are there
+        DeviceArena a;
+        int32_t* J = a.dev<int32_t>(N);
+        p->d_basinSlot = a.dev<int32_t>(N);
+        p->d_basinKey = a.dev<uint32_t>(N);
+        p->d_basinVals[0] = a.dev<int32_t>(N); p->d_basinVals[1] = a.dev<int32_t>(N);   // own buffers: the layout runs beside the flow accumulation, whose rounds use the planet's lists
+        p->d_basinRange = a.dev<int32_t>((size_t)N / 64 + 8 + WO_LONG_MAX);        // range starts, then {count, long ranges}
+        p->d_basinLong = a.dev<uint8_t>((size_t)N / 64 + 8);
+        p->mem.adopt(a); p->d_basinJ = J;
         WO_HIP(hipMemsetAsync(p->d_basinSlot, 0xff, (size_t)N * 4, s));
     }
 }
@@ -429,17 +432,6 @@ void basin_solve_launch(wo_planet* p, const Fields& F, int32_t launchTag, int32_
     launch(p, FAM_SOLVE_BASIN, k_solve_flowing<2, false>, grid, 128, F, p->L, (const int32_t*)p->d_basinRange, (int32_t)nRanges, launchTag, p->d_patchPending, totalPending, big, flag, (unsigned long long*)nullptr);
     // (k_solve_flowing<2, true>: the same kernel with phase clocks and the depth of the slowest range's dependency DAG written to its last argument — the
     // diagnostic build behind DESIGN.md's "clocks per level" figures, profiles/r04c_*; not instantiated in the product)
-}
-
-void basin_free(wo_planet* p) {
-    if (p->d_basinJ) (void)hipFree(p->d_basinJ);
-    if (p->d_basinSlot) (void)hipFree(p->d_basinSlot);
-    if (p->d_basinKey) (void)hipFree(p->d_basinKey);
-    for (auto& v : p->d_basinVals) { if (v) (void)hipFree(v); v = nullptr; }
-    if (p->d_basinRange) (void)hipFree(p->d_basinRange);
-    if (p->d_basinLong) (void)hipFree(p->d_basinLong);
-    p->d_basinLong = nullptr;
-    p->d_basinJ = nullptr; p->d_basinSlot = nullptr; p->d_basinKey = nullptr; p->d_basinRange = nullptr;
 }
 
 }  // namespace wo

@@ -23,6 +23,7 @@
 #include "device.h"
 
 struct wo_comm {
+    wo::DeviceArena mem;
     ncclComm_t comm = nullptr;
     int32_t nranks = 0, rank = 0, device = 0;
     float* gather = nullptr; size_t gatherCap = 0;      // [nranks][maxPerRank] landing buffer of the all-gather
@@ -98,6 +99,7 @@ struct GroupGuard {
 
 // RCCL form of the landmass decomposition's flood exchange (wo_planet_set_flood_exchange_comm)
 struct FloodLink {
+    wo::DeviceArena mem;
     wo_planet* planet = nullptr; wo_comm* comm = nullptr;
     std::vector<int32_t> counts, cells;              // cells: every rank's land cells, concatenated in rank order
     std::vector<int64_t> start;
@@ -106,18 +108,7 @@ struct FloodLink {
     float *d_send = nullptr, *d_all = nullptr, *h_send = nullptr, *h_all = nullptr;
     float* d_land = nullptr; size_t landCap = 0;     // the flooded land heights on their way through ncclBroadcast
 };
-void flood_link_free(void* v) {
-    FloodLink* k = (FloodLink*)v;
-    if (!k) return;
-    if (k->d_flag) (void)hipFree(k->d_flag);
-    if (k->h_flag) (void)hipHostFree(k->h_flag);
-    if (k->d_send) (void)hipFree(k->d_send);
-    if (k->d_all) (void)hipFree(k->d_all);
-    if (k->d_land) (void)hipFree(k->d_land);
-    if (k->h_send) (void)hipHostFree(k->h_send);
-    if (k->h_all) (void)hipHostFree(k->h_all);
-    delete k;
-}
+void flood_link_free(void* v) { delete (FloodLink*)v; }
 int flood_link_exchange(void* user, int32_t phase, void* buf, int64_t n) {
     FloodLink* k = (FloodLink*)user;
     if (phase == -1) {                                   // handshake (include/worogen.h): this link implements protocol 2 (phases 0-3)
@@ -153,9 +144,8 @@ int flood_link_exchange(void* user, int32_t phase, void* buf, int64_t n) {
             if (root < 0 || root >= c->nranks) { wo::set_error("flood exchange: no rank sent the flooded heights"); return 1; }
             const size_t need = (size_t)std::max<int64_t>(n, 1);
             if (need > k->landCap) {
-                if (k->d_land) (void)hipFree(k->d_land);
-                k->d_land = nullptr; k->landCap = 0;
-                WO_HIP(hipMalloc((void**)&k->d_land, need * sizeof(float)));
+                k->mem.release(k->d_land); k->landCap = 0;
+                k->d_land = k->mem.dev<float>(need);
                 k->landCap = need;
             }
             if (sender) WO_HIP(hipMemcpyAsync(k->d_land, buf, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
@@ -166,11 +156,11 @@ int flood_link_exchange(void* user, int32_t phase, void* buf, int64_t n) {
         }
         float* field = (float*)buf;
         const size_t M = (size_t)k->maxCount;
-        if (!k->d_send) {
-            WO_HIP(hipMalloc((void**)&k->d_send, M * sizeof(float)));
-            WO_HIP(hipMalloc((void**)&k->d_all, M * (size_t)c->nranks * sizeof(float)));
-            WO_HIP(hipHostMalloc((void**)&k->h_send, M * sizeof(float)));
-            WO_HIP(hipHostMalloc((void**)&k->h_all, M * (size_t)c->nranks * sizeof(float)));
+        if (!k->d_send) {                                // (send, which says that the four are there, last)
+            if (!k->d_all) k->d_all = k->mem.dev<float>(M * (size_t)c->nranks);
+            if (!k->h_send) k->h_send = k->mem.pinned<float>(M);
+            if (!k->h_all) k->h_all = k->mem.pinned<float>(M * (size_t)c->nranks);
+            k->d_send = k->mem.dev<float>(M);
         }
         const int32_t* mine = k->cells.data() + k->start[c->rank];
         const int32_t nMine = k->counts[c->rank];
@@ -190,11 +180,12 @@ int flood_link_exchange(void* user, int32_t phase, void* buf, int64_t n) {
     } catch (const wo::HipError& e) { wo::set_error(std::string("flood exchange: ") + e.msg); return 1; }
 }
 
-template <class T> void grow(T*& p, size_t& cap, size_t need) {
+// a buffer of the communicator for at least `need` floats; a failure leaves it empty (nullptr, capacity 0) for the caller to report
+void grow(wo_comm* c, float*& q, size_t& cap, size_t need) {
     if (need <= cap) return;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    if (hipMalloc((void**)&p, need * sizeof(T)) == hipSuccess) cap = need;
+    c->mem.release(q); cap = 0;
+    q = c->mem.try_dev<float>(need);
+    if (q) cap = need;
 }
 }  // namespace
 
@@ -227,8 +218,6 @@ int wo_comm_destroy(wo_comm* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
     if (c->comm) (void)rccl().CommDestroy(c->comm);
-    if (c->gather) (void)hipFree(c->gather);
-    if (c->send) (void)hipFree(c->send);
     delete c;
     return 0;
 }
@@ -246,8 +235,8 @@ int wo_planet_exchange_allgather(wo_planet* p, wo_comm* c, const int32_t* counts
     if (counts[c->rank] != p->nHaloSend || others != p->nHaloRecv) { wo::set_error("wo_planet_exchange_allgather: counts do not match the planet's halo lists (wo_planet_set_halo)"); return 1; }
     try {
         hipStream_t s = p->ctx->stream;
-        grow(c->send, c->sendCap, (size_t)maxCount);
-        grow(c->gather, c->gatherCap, (size_t)maxCount * (size_t)c->nranks);
+        grow(c, c->send, c->sendCap, (size_t)maxCount);
+        grow(c, c->gather, c->gatherCap, (size_t)maxCount * (size_t)c->nranks);
         if (!c->send || !c->gather) { wo::set_error("wo_planet_exchange_allgather: out of device memory"); return 1; }
         if (p->nHaloSend > 0) wo::launch(p, wo::FAM_MISC, k_comm_pack, wo::blocks_for(p->nHaloSend), wo::WO_BLOCK, (const float*)p->d_e, (const int32_t*)p->d_haloSend, p->nHaloSend, c->send);
         if (p->nHaloSend < maxCount) WO_HIP(hipMemsetAsync(c->send + p->nHaloSend, 0, (size_t)(maxCount - p->nHaloSend) * sizeof(float), s));
@@ -276,7 +265,7 @@ int wo_planet_exchange_neighbors(wo_planet* p, wo_comm* c, int32_t nToPrev, int3
     }
     try {
         hipStream_t s = p->ctx->stream;
-        grow(c->send, c->sendCap, (size_t)std::max(p->nHaloSend, 1));
+        grow(c, c->send, c->sendCap, (size_t)std::max(p->nHaloSend, 1));
         if (!c->send) { wo::set_error("wo_planet_exchange_neighbors: out of device memory"); return 1; }
         if (p->nHaloSend > 0) wo::launch(p, wo::FAM_MISC, k_comm_pack, wo::blocks_for(p->nHaloSend), wo::WO_BLOCK, (const float*)p->d_e, (const int32_t*)p->d_haloSend, p->nHaloSend, c->send);
         GroupGuard group;
@@ -307,7 +296,7 @@ int wo_planet_set_flood_exchange_comm(wo_planet* p, const uint8_t* trueOcean, wo
     }
     k->cells.assign(cellsByRank, cellsByRank + k->start[c->nranks]);
     for (int32_t v : k->cells) if (v < 0 || v >= p->N) { delete k; wo::set_error("wo_planet_set_flood_exchange_comm: cell id out of range"); return 1; }
-    if (hipMalloc((void**)&k->d_flag, sizeof(int32_t)) != hipSuccess || hipHostMalloc((void**)&k->h_flag, sizeof(int32_t)) != hipSuccess) {
+    if (!(k->d_flag = k->mem.try_dev<int32_t>(1)) || !(k->h_flag = k->mem.try_pinned<int32_t>(1))) {
         flood_link_free(k); wo::set_error("wo_planet_set_flood_exchange_comm: out of memory"); return 1;
     }
     if (wo_planet_set_flood_exchange(p, trueOcean, flood_link_exchange, k) != 0) { flood_link_free(k); return 1; }     // (frees a previous link)

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "device_mem.h"
 #include "host_util.h"
 
 #include "erode_ops.h"
@@ -17,15 +18,11 @@
 
 namespace wo {
 
-struct HipError { std::string msg; };
-
-#define WO_HIP(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            throw ::wo::HipError{std::string(#call) + " -> " + hipGetErrorString(e_) + " (" + __FILE__ + ":" + \
-                                 std::to_string(__LINE__) + ")"};                                      \
-    } while (0)
+// The entry points' try / catch pair: WO_TRY body WO_CATCH("wo_name") turns a HipError into status 2 and any other exception into 3
+#define WO_TRY try {
+#define WO_CATCH(fn)                                                                                   \
+    } catch (const ::wo::HipError& e) { ::wo::set_error(std::string(fn) + ": " + e.msg); return 2; }   \
+      catch (const std::exception& e) { ::wo::set_error(std::string(fn) + ": " + e.what()); return 3; }
 
 constexpr int WO_BLOCK = 256;
 inline int blocks_for(int64_t n, int maxBlocks = 1 << 20) {
@@ -68,6 +65,7 @@ struct wo_ctx {
 
 // device state of the flood's pass 1 (flood_kernels.h); static part per land mask, the rest per call
 struct wo_flood_gpu {
+    wo::DeviceArena mem;                 // owns every buffer below
     int64_t version = -1; int32_t L = 0, cap = 0, nSeeds = 0;
     int32_t *off = nullptr, *adj = nullptr, *cell = nullptr, *seedIdx = nullptr, *seeds = nullptr; double* nz = nullptr;
     float* e = nullptr;
@@ -105,6 +103,7 @@ struct wo_planet {
     wo_ctx* ctx = nullptr;
     wo::Options opt;
     int32_t N = 0, E = 0, maxDeg = 0;
+    wo::DeviceArena mem;                 // owns the planet's own device and pinned buffers (device_mem.h); the members below are views
     // host copies kept for the host-resident flood stage
     wo::hvec<int32_t> h_off, h_adj;          // host mirrors walked in data-dependent order: huge-page advised (host_util.h)
     wo::hvec<float> h_xyz;
@@ -112,8 +111,10 @@ struct wo_planet {
     bool h_ocean_valid = false;
     float* h_pinned = nullptr;          // N floats, pinned
     int32_t* h_count = nullptr;         // pinned scalar(s) for round-count read-back
-    float* d_redoE = nullptr; int32_t* d_pendingEver = nullptr; int64_t redoCalls = 0;   // erode_composite_checked: the field at entry, tasks any basin launch of the call left pending, calls that had to run again
-    unsigned long long *h_word = nullptr, *d_word = nullptr; uint32_t wordSerial = 0;   // host-mapped {serial, value} word the host polls (planet.hip: read_count)
+    // erode_composite_checked: the field at entry, tasks any basin launch of the call left pending, calls that had to run again
+    float* d_redoE = nullptr; int32_t* d_pendingEver = nullptr; int64_t redoCalls = 0;
+    // host-mapped {serial, value} word the host polls (planet.hip: read_count)
+    unsigned long long *h_word = nullptr, *d_word = nullptr; uint32_t wordSerial = 0;
     wo::FloodScratch flood;
     wo::FloodExchange floodX;           // landmass decomposition: the shares pool their heights when a flood call needs the whole planet's heap (wo_planet_set_flood_exchange)
     void* floodLink = nullptr; void (*floodLinkFree)(void*) = nullptr;   // comm.hip: state of the RCCL form of that exchange
@@ -140,28 +141,43 @@ struct wo_planet {
     int32_t* d_landInit = nullptr; int64_t oceanVersion = 0, landListsOcean = -1; bool landListsMirror = false; int32_t landListsL = -1;
     uint32_t* d_keys[2] = {nullptr, nullptr};
     float *d_cellDist = nullptr, *d_flow = nullptr;
-    wo::SolveTask* d_task = nullptr; wo::SolveOut* d_out = nullptr; int32_t *d_haloSend = nullptr, *d_haloRecv = nullptr; float *d_haloBuf = nullptr, *h_haloBuf = nullptr; int32_t nHaloSend = 0, nHaloRecv = 0;   // banded Jacobi passes
+    wo::SolveTask* d_task = nullptr; wo::SolveOut* d_out = nullptr;
+    // banded Jacobi passes
+    int32_t *d_haloSend = nullptr, *d_haloRecv = nullptr; float *d_haloBuf = nullptr, *h_haloBuf = nullptr; int32_t nHaloSend = 0, nHaloRecv = 0;
     int32_t* d_flowCnt = nullptr; wo::TargetRank* d_tr = nullptr; wo::EventList* d_ev = nullptr; float* d_me = nullptr;
-    int32_t *d_carveSlot = nullptr, *d_carveDeps = nullptr, *d_carveDepCnt = nullptr, *d_carveDepPos = nullptr; uint32_t* d_rs[2] = {nullptr, nullptr}; int rsFlip[2] = {0, 0};   /* radix.hip scratch: elevation sort, basin sort */ wo::CarveRec* d_carveRecs = nullptr; wo::CarveExpect* d_carveExpect = nullptr; unsigned long long* d_carveG = nullptr;   /* k_carve_granules: expected tags per task, height granules per cell */ int32_t* d_carveSlotDone = nullptr; int64_t carveCap = 0;   // carve dependency lists
+    // carve dependency lists
+    int32_t *d_carveSlot = nullptr, *d_carveDeps = nullptr, *d_carveDepCnt = nullptr, *d_carveDepPos = nullptr;
+    // radix.hip scratch: elevation sort, basin sort
+    uint32_t* d_rs[2] = {nullptr, nullptr}; int rsFlip[2] = {0, 0};
+    // k_carve_granules: expected tags per task, height granules per cell
+    wo::CarveRec* d_carveRecs = nullptr; wo::CarveExpect* d_carveExpect = nullptr; unsigned long long* d_carveG = nullptr;
+    int32_t* d_carveSlotDone = nullptr; int64_t carveCap = 0;
     unsigned long long* d_accCnt = nullptr;
-    int32_t *d_ftLr = nullptr, *d_ftParent = nullptr, *d_ftExtCnt = nullptr; uint32_t* d_ftInflow = nullptr; unsigned long long* d_ftRootAcc = nullptr;      // two-level flow accumulation (kernels_impl.h: FlowTiles)
+    // two-level flow accumulation (kernels_impl.h: FlowTiles)
+    int32_t *d_ftLr = nullptr, *d_ftParent = nullptr, *d_ftExtCnt = nullptr; uint32_t* d_ftInflow = nullptr; unsigned long long* d_ftRootAcc = nullptr;
     int32_t *d_jump = nullptr, *d_nj = nullptr;
     int32_t* d_doneAt = nullptr;
     double* d_totalExcess = nullptr;
     float *d_glac = nullptr, *d_iceFlow = nullptr;
     int32_t *d_iceTarget = nullptr, *d_arank = nullptr;
     uint8_t* d_iceUp = nullptr;
-    int32_t *d_patchOrder = nullptr, *d_slotOf = nullptr, *d_patchPending = nullptr, *d_patchTotals = nullptr, *d_patchBlk = nullptr; int64_t patchVersion = -1; bool patchMirror = false; int32_t numPatches = 0; int64_t lastPatchLaunches = 1; int64_t solveCalls = 0;
+    int32_t *d_patchOrder = nullptr, *d_slotOf = nullptr, *d_patchPending = nullptr, *d_patchTotals = nullptr, *d_patchBlk = nullptr;
+    int64_t patchVersion = -1; bool patchMirror = false; int32_t numPatches = 0; int64_t lastPatchLaunches = 1; int64_t solveCalls = 0;
     hipStream_t side = nullptr; hipEvent_t evFork = nullptr, evJoin = nullptr; bool onSide = false;
-    uint32_t* d_basinKey = nullptr; int32_t* d_basinVals[2] = {nullptr, nullptr}; int32_t *d_basinJ = nullptr, *d_basinSlot = nullptr, *d_basinRange = nullptr; uint8_t* d_basinLong = nullptr; int64_t basinLaunches = 0; wo::Affine* d_affine[2] = {nullptr, nullptr};   /* relaxed mode: the affine recurrence, ping-pong */ int64_t solvePassSerial = 0;   /* unchecked basin passes so far (their output tag: planet.hip, passTag) */   // basin.hip: component roots (Morton slot space), group-major store order of the pass
+    // basin.hip: component roots (Morton slot space), group-major store order of the pass
+    uint32_t* d_basinKey = nullptr; int32_t* d_basinVals[2] = {nullptr, nullptr}; int32_t *d_basinJ = nullptr, *d_basinSlot = nullptr, *d_basinRange = nullptr;
+    uint8_t* d_basinLong = nullptr; int64_t basinLaunches = 0;
+    wo::Affine* d_affine[2] = {nullptr, nullptr};      // relaxed mode: the affine recurrence, ping-pong
+    int64_t solvePassSerial = 0;                       // unchecked basin passes so far (their output tag: planet.hip, passTag)
     int32_t* h_patchTotals = nullptr;      // pinned: the pending totals of a burst of k_solve_patch launches (run_solve_patches)
     int32_t *d_listA = nullptr, *d_listB = nullptr, *d_counters = nullptr;   // round lists + 4 counters
     void* d_sortTemp = nullptr; size_t sortTempBytes = 0;
     int landCur = 0;                    // which of d_land[] holds the current order
     int32_t L = 0;
 
-    // heightmap import scratch (heightmap.hip), allocated on first use and grown when needed; freed by wo_planet_destroy
+    // heightmap import scratch (heightmap.hip), allocated on first use and grown when needed
     struct Import {
+        wo::DeviceArena mem;
         uint8_t* img = nullptr; int64_t imgCap = 0;          // the uploaded grayscale image
         int32_t* label = nullptr;                           // union-find parents, then the component labels
         uint8_t* flags = nullptr;                           // classification + seed bits per cell (import_ops.h: CLS_*)
@@ -172,16 +188,17 @@ struct wo_planet {
     } imp;
 
     // seasonal pressure and wind (wind.hip): the wind block — results and scratch of wo_compute_wind, allocated on its first
-    // call; freed by wo_planet_destroy
+    // call; deleted by wo_planet_destroy (wind_free)
     struct wo_wind_block* wind = nullptr;
     // ocean surface currents (ocean.hip): the ocean block — results and scratch of wo_compute_ocean_currents, allocated on its
-    // first call; freed by wo_planet_destroy
+    // first call; deleted by wo_planet_destroy (ocean_free)
     struct wo_ocean_block* ocean = nullptr;
 
     // Patch-major mirror of the mesh for erodeComposite (planet.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
     // d_e2, d_ocean, d_coast) point at the mirror and the o_* members hold the planet's own buffers.
     struct Mirror {
+        wo::DeviceArena mem;
         bool built = false, active = false;
         int32_t *perm = nullptr, *inv = nullptr, *off = nullptr, *adj = nullptr;       // perm: mirror id -> cell id
         float *dist = nullptr, *xyz = nullptr, *e = nullptr, *e2 = nullptr, *hot = nullptr;
@@ -262,15 +279,12 @@ void select_active_by_rank(wo_planet* p, const int32_t* arank, int32_t* out, int
 void basin_alloc(wo_planet* p);
 void basin_layout(wo_planet* p, bool slotIdentity);
 void basin_solve_launch(wo_planet* p, const Fields& F, int32_t launchTag, int32_t* totalPending);
-void basin_free(wo_planet* p);
-// heightmap.hip: frees the import scratch
-void import_free(wo_planet* p);
-// wind.hip: frees the wind block; planet.hip: smoothField on a resident field (returns the buffer that holds the result)
+// wind.hip, ocean.hip: drop the wind block / the ocean block (and with it its memory)
 void wind_free(wo_planet* p);
-// ocean.hip: frees the ocean block
 void ocean_free(wo_planet* p);
 // planet.hip: the entry points' handle check (refreshes p->opt from the environment, selects the device)
 bool check_planet(wo_planet* p, const char* fn);
+// planet.hip: smoothField on a resident field (returns the buffer that holds the result)
 float* smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passes);
 
 }  // namespace wo

@@ -132,32 +132,20 @@ __global__ __launch_bounds__(WO_BLOCK) void k_import_scatter(const uint8_t* __re
     }
 }
 
-template <class T> static void grow(T*& q, int64_t& cap, int64_t n) {
-    if (q && cap >= n) return;
-    if (q) { WO_HIP(hipFree(q)); q = nullptr; cap = 0; }
-    WO_HIP(hipMalloc((void**)&q, (size_t)std::max<int64_t>(n, 1) * sizeof(T)));
-    cap = n;
-}
-
+// Built in an arena of its own and handed to the import scratch whole; h_totals, assigned last, says that the buffers are there
 static void import_alloc(wo_planet* p) {
     auto& I = p->imp;
-    if (I.label) return;
+    if (I.h_totals) return;
     const size_t N = (size_t)p->N, nB = (N + WO_BLOCK - 1) / WO_BLOCK;
-    WO_HIP(hipMalloc((void**)&I.label, N * 4));
-    WO_HIP(hipMalloc((void**)&I.flags, N));
-    WO_HIP(hipMalloc((void**)&I.lists, (size_t)IMP_LISTS * N * 4));
-    WO_HIP(hipMalloc((void**)&I.seedOcean, N));
-    WO_HIP(hipMalloc((void**)&I.blockCounts, nB * IMP_LISTS * 4));
-    WO_HIP(hipMalloc((void**)&I.totals, IMP_LISTS * 4));
-    WO_HIP(hipHostMalloc((void**)&I.h_totals, 64));
-}
-
-void import_free(wo_planet* p) {
-    auto& I = p->imp;
-    for (void* q : {(void*)I.img, (void*)I.label, (void*)I.flags, (void*)I.lists, (void*)I.seedOcean, (void*)I.blockCounts, (void*)I.totals})
-        if (q) (void)hipFree(q);
-    if (I.h_totals) (void)hipHostFree(I.h_totals);
-    I = wo_planet::Import{};
+    DeviceArena a;
+    I.label = a.dev<int32_t>(N);
+    I.flags = a.dev<uint8_t>(N);
+    I.lists = a.dev<int32_t>((size_t)IMP_LISTS * N);
+    I.seedOcean = a.dev<uint8_t>(N);
+    I.blockCounts = a.dev<int32_t>(nB * IMP_LISTS);
+    I.totals = a.dev<int32_t>(IMP_LISTS);
+    int32_t* h_totals = a.pinned<int32_t>(16);
+    I.mem.adopt(a); I.h_totals = h_totals;
 }
 
 // count / scan / scatter on the resident field; returns the four list lengths (the one synchronisation)
@@ -185,10 +173,6 @@ static bool check_import_planet(wo_planet* p, const char* fn) {
 
 using namespace wo;
 
-#define WO_IMP_CATCH(fn)                                                                \
-    catch (const HipError& e) { set_error(std::string(fn) + ": " + e.msg); return 2; }   \
-    catch (const std::exception& e) { set_error(std::string(fn) + ": " + e.what()); return 3; }
-
 extern "C" {
 
 int wo_sample_heightmap(wo_planet* p, const uint8_t* gray, int32_t W, int32_t H, float* r_elevation_out) {
@@ -197,9 +181,13 @@ int wo_sample_heightmap(wo_planet* p, const uint8_t* gray, int32_t W, int32_t H,
     if (W <= 0 || H <= 0) { set_error("wo_sample_heightmap: image width and height must be positive"); return 1; }
     const int64_t px = (int64_t)W * (int64_t)H;
     if (px > INT32_MAX) { set_error("wo_sample_heightmap: image of more than 2^31 - 1 pixels"); return 1; }
-    try {
+    WO_TRY
         hipStream_t s = p->ctx->stream;
-        grow(p->imp.img, p->imp.imgCap, px);
+        auto& I = p->imp;
+        if (!I.img || I.imgCap < px) {                       // the old image goes first; the capacity is set once the new one is there
+            I.mem.release(I.img); I.imgCap = 0;
+            I.img = I.mem.dev<uint8_t>((size_t)px); I.imgCap = px;
+        }
         WO_HIP(hipMemcpyAsync(p->imp.img, gray, (size_t)px, hipMemcpyHostToDevice, s));
         launch(p, FAM_MISC, k_sample_heightmap, (int)((p->N + WO_BLOCK - 1) / WO_BLOCK), WO_BLOCK, (const float*)p->d_xyz, (const uint8_t*)p->imp.img,
                W, H, p->d_e, p->d_ocean, p->N);
@@ -207,13 +195,13 @@ int wo_sample_heightmap(wo_planet* p, const uint8_t* gray, int32_t W, int32_t H,
         if (r_elevation_out) WO_HIP(hipMemcpyAsync(r_elevation_out, p->d_e, (size_t)p->N * 4, hipMemcpyDeviceToHost, s));
         WO_HIP(hipStreamSynchronize(s));                     // the caller's image is borrowed for the call only
         return 0;
-    } WO_IMP_CATCH("wo_sample_heightmap")
+    WO_CATCH("wo_sample_heightmap")
 }
 
 int wo_synthetic_plates(wo_planet* p, int32_t* r_plate, int32_t* seeds, uint8_t* seedIsOcean, int32_t* nSeeds) {
     if (!check_import_planet(p, "wo_synthetic_plates")) return 1;
     if (!r_plate || !seeds || !nSeeds) { set_error("wo_synthetic_plates: null pointer"); return 1; }
-    try {
+    WO_TRY
         import_alloc(p);
         auto& I = p->imp;
         const int32_t N = p->N, g = (int32_t)((N + WO_BLOCK - 1) / WO_BLOCK);
@@ -229,13 +217,13 @@ int wo_synthetic_plates(wo_planet* p, int32_t* r_plate, int32_t* seeds, uint8_t*
         WO_HIP(hipStreamSynchronize(s));
         *nSeeds = len[0];
         return 0;
-    } WO_IMP_CATCH("wo_synthetic_plates")
+    WO_CATCH("wo_synthetic_plates")
 }
 
 int wo_classify_regions(wo_planet* p, int32_t* mountain, int32_t* coastline, int32_t* ocean, int32_t* counts) {
     if (!check_import_planet(p, "wo_classify_regions")) return 1;
     if (!mountain || !coastline || !ocean || !counts) { set_error("wo_classify_regions: null pointer"); return 1; }
-    try {
+    WO_TRY
         import_alloc(p);
         auto& I = p->imp;
         const int64_t N = p->N;
@@ -247,7 +235,7 @@ int wo_classify_regions(wo_planet* p, int32_t* mountain, int32_t* coastline, int
         WO_HIP(hipStreamSynchronize(s));
         for (int j = 0; j < 3; ++j) counts[j] = len[j + 1];
         return 0;
-    } WO_IMP_CATCH("wo_classify_regions")
+    WO_CATCH("wo_classify_regions")
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 
 #include <cstddef>
 #include <cstring>
+#include <memory>
 #include <string>
 
 #include "../../include/worogen.h"
@@ -48,6 +49,7 @@ constexpr size_t OCEAN_CTL_HEAD = offsetof(OceanCtl, bins);
 
 // the ocean block of a planet
 struct wo_ocean_block {
+    wo::DeviceArena mem;                                      // owns every device and pinned buffer of the block
     bool valid = false;
     float* out[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // per season: east, north, speed, warmth
     uint8_t* isOcean = nullptr;
@@ -262,29 +264,20 @@ __global__ __launch_bounds__(WO_BLOCK) void k_ocean_finish(float* __restrict__ s
     warmS[r] = g.v[0]; warmW[r] = g.v[1];
 }
 
-void ocean_free(wo_planet* p) {
-    auto* B = p->ocean;
-    if (!B) return;
-    for (auto& a : B->out) wfree(a);
-    wfree(B->isOcean); wfree(B->group[0]); wfree(B->group[1]); wfree(B->itcz); wfree(B->ctl);
-    if (B->h_ctl) (void)hipHostFree(B->h_ctl);
-    delete B;
-    p->ocean = nullptr;
-}
+void ocean_free(wo_planet* p) { delete p->ocean; p->ocean = nullptr; }
 
 static void ocean_alloc(wo_planet* p) {
     if (p->ocean) return;
-    auto* B = new wo_ocean_block();
-    p->ocean = B;
-    try {
-        const size_t N = (size_t)p->N;
-        for (auto& a : B->out) walloc(a, N);
-        walloc(B->isOcean, N);
-        for (auto& g : B->group) { uint8_t* q = nullptr; walloc(q, 16 * N); g = q; }
-        walloc(B->itcz, (size_t)2 * W::ITCZ_SAMPLES);
-        walloc(B->ctl, 1);
-        WO_HIP(hipHostMalloc((void**)&B->h_ctl, sizeof(OceanCtl)));
-    } catch (...) { ocean_free(p); throw; }                    // never leave a half-allocated block behind: the next call allocates again
+    std::unique_ptr<wo_ocean_block> block(new wo_ocean_block());        // the planet gets the block once it is complete
+    wo_ocean_block* B = block.get(); DeviceArena& a = B->mem;
+    const size_t N = (size_t)p->N;
+    for (auto& o : B->out) o = a.dev<float>(N);
+    B->isOcean = a.dev<uint8_t>(N);
+    for (auto& g : B->group) g = a.dev<uint8_t>(16 * N);
+    B->itcz = a.dev<float>((size_t)2 * W::ITCZ_SAMPLES);
+    B->ctl = a.dev<OceanCtl>(1);
+    B->h_ctl = a.pinned<OceanCtl>(1);
+    p->ocean = block.release();
 }
 
 // `passes` passes of the masked smooth from a into b and back; returns the buffer that holds the result
@@ -363,10 +356,6 @@ static void ocean_run(wo_planet* p) {
 
 using namespace wo;
 
-#define WO_OCEAN_CATCH(fn)                                                              \
-    catch (const HipError& e) { set_error(std::string(fn) + ": " + e.msg); return 2; }   \
-    catch (const std::exception& e) { set_error(std::string(fn) + ": " + e.what()); return 3; }
-
 // the reference's result keys in the order it sets them (js/ocean.js:374-377, summer then winter)
 static const char* const kOceanFields[8] = {"r_ocean_current_east_summer", "r_ocean_current_north_summer", "r_ocean_speed_summer", "r_ocean_warmth_summer",
                                             "r_ocean_current_east_winter", "r_ocean_current_north_winter", "r_ocean_speed_winter", "r_ocean_warmth_winter"};
@@ -384,12 +373,12 @@ int wo_compute_ocean_currents(wo_planet* p, int32_t numRegions, wo_ocean_info* i
         set_error("wo_compute_ocean_currents: no wind result on this planet (call wo_compute_wind first, or wo_wind_upload r_lat r_lon r_isLand r_eastX r_eastY r_eastZ itczLons itczLatsSummer itczLatsWinter)");
         return 1;
     }
-    try {
+    WO_TRY
         ocean_alloc(p);
         ocean_run(p);
         if (info) *info = p->ocean->info;
         return 0;
-    } WO_OCEAN_CATCH("wo_compute_ocean_currents")
+    WO_CATCH("wo_compute_ocean_currents")
 }
 
 int wo_ocean_download(wo_planet* p, const char* field, void* out, int64_t outBytes) {
@@ -400,13 +389,13 @@ int wo_ocean_download(wo_planet* p, const char* field, void* out, int64_t outByt
     int f = -1;
     for (int i = 0; i < 8; ++i) if (std::strcmp(field, kOceanFields[i]) == 0) f = i;
     if (f < 0) { set_error(std::string("wo_ocean_download: unknown field '") + field + "'"); return 1; }
-    try {
+    WO_TRY
         const size_t bytes = (size_t)p->N * 4;
         if (outBytes < (int64_t)bytes) { set_error(std::string("wo_ocean_download: ") + field + " needs " + std::to_string(bytes) + " bytes, out has " + std::to_string(outBytes)); return 1; }
         WO_HIP(hipMemcpyAsync(out, B->out[f], bytes, hipMemcpyDeviceToHost, p->ctx->stream));
         WO_HIP(hipStreamSynchronize(p->ctx->stream));
         return 0;
-    } WO_OCEAN_CATCH("wo_ocean_download")
+    WO_CATCH("wo_ocean_download")
 }
 
 }  // extern "C"

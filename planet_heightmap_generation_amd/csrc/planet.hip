@@ -44,30 +44,36 @@ void profile_resolve(wo_planet* p) {
     p->pending.clear();
 }
 
-template <class T> static T* dalloc(size_t n) { void* q = nullptr; WO_HIP(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T))); return (T*)q; }
-template <class T> static void dfree(T*& q) { if (q) { (void)hipFree(q); q = nullptr; } }
-
 constexpr int WO_PATCH_TOTAL_SLOTS = 4096;         // pending-total slots of the patch solve (one per launch, reused modulo)
 
 
+// Failure-safe by construction: the scratch is built in an arena of its own, which the planet's arena takes over once every buffer is
+// there; a failure on the way frees what was built, `scratch` stays false (the members are then not looked at) and the next call starts afresh.
 static void ensure_scratch(wo_planet* p) {
     if (p->scratch) return;
     const size_t N = (size_t)p->N;
-    p->d_landIdx = dalloc<int32_t>(N); p->d_land[0] = dalloc<int32_t>(N); p->d_land[1] = dalloc<int32_t>(N);
-    p->d_keys[0] = dalloc<uint32_t>(N); p->d_keys[1] = dalloc<uint32_t>(N);
-    p->d_rank = dalloc<int32_t>(N);
-    p->d_cellDist = dalloc<float>(N); p->d_flow = dalloc<float>(N); p->d_task = dalloc<SolveTask>(N); p->d_out = dalloc<SolveOut>(N); WO_HIP(hipMemset(p->d_out, 0, N * sizeof(SolveOut)));   /* tags of the unchecked basin passes count up from here: no stale tag may look like a coming one */ p->d_flowCnt = dalloc<int32_t>(N); WO_HIP(hipMemset(p->d_flowCnt, 0, (size_t)N * 4)); p->d_tr = dalloc<TargetRank>(N); p->d_ev = dalloc<EventList>(N); p->d_me = dalloc<float>(N); p->d_carveSlot = dalloc<int32_t>(N);
-    p->d_accCnt = dalloc<unsigned long long>(N); p->d_jump = dalloc<int32_t>(N); p->d_nj = dalloc<int32_t>(N);
-    p->d_doneAt = dalloc<int32_t>(N);
-    p->d_totalExcess = dalloc<double>(N);
-    p->d_glac = dalloc<float>(N); p->d_iceFlow = dalloc<float>(N); p->d_iceTarget = dalloc<int32_t>(N); p->d_arank = dalloc<int32_t>(N);
-    p->d_iceUp = dalloc<uint8_t>(N);
-    p->d_listA = dalloc<int32_t>(N); p->d_listB = dalloc<int32_t>(N); p->d_counters = dalloc<int32_t>(8);
-    p->d_patchOrder = dalloc<int32_t>(N); p->d_slotOf = dalloc<int32_t>(N); p->d_patchPending = dalloc<int32_t>(N / WO_PATCH + 2); p->d_patchTotals = dalloc<int32_t>(WO_PATCH_TOTAL_SLOTS); p->d_patchBlk = dalloc<int32_t>(N);
-    WO_HIP(hipHostMalloc((void**)&p->h_patchTotals, (size_t)WO_PATCH_TOTAL_SLOTS * sizeof(int32_t)));          // read-back buffer of run_solve_patches
+    DeviceArena a;
+    p->d_landIdx = a.dev<int32_t>(N); p->d_land[0] = a.dev<int32_t>(N); p->d_land[1] = a.dev<int32_t>(N);
+    p->d_keys[0] = a.dev<uint32_t>(N); p->d_keys[1] = a.dev<uint32_t>(N);
+    p->d_rank = a.dev<int32_t>(N);
+    p->d_cellDist = a.dev<float>(N); p->d_flow = a.dev<float>(N); p->d_task = a.dev<SolveTask>(N);
+    // tags of the unchecked basin passes count up from here: no stale tag may look like a coming one
+    p->d_out = a.dev<SolveOut>(N); WO_HIP(hipMemset(p->d_out, 0, N * sizeof(SolveOut)));
+    p->d_flowCnt = a.dev<int32_t>(N); WO_HIP(hipMemset(p->d_flowCnt, 0, (size_t)N * 4));
+    p->d_tr = a.dev<TargetRank>(N); p->d_ev = a.dev<EventList>(N); p->d_me = a.dev<float>(N); p->d_carveSlot = a.dev<int32_t>(N);
+    p->d_accCnt = a.dev<unsigned long long>(N); p->d_jump = a.dev<int32_t>(N); p->d_nj = a.dev<int32_t>(N);
+    p->d_doneAt = a.dev<int32_t>(N);
+    p->d_totalExcess = a.dev<double>(N);
+    p->d_glac = a.dev<float>(N); p->d_iceFlow = a.dev<float>(N); p->d_iceTarget = a.dev<int32_t>(N); p->d_arank = a.dev<int32_t>(N);
+    p->d_iceUp = a.dev<uint8_t>(N);
+    p->d_listA = a.dev<int32_t>(N); p->d_listB = a.dev<int32_t>(N); p->d_counters = a.dev<int32_t>(8);
+    p->d_patchOrder = a.dev<int32_t>(N); p->d_slotOf = a.dev<int32_t>(N); p->d_patchPending = a.dev<int32_t>(N / WO_PATCH + 2);
+    p->d_patchTotals = a.dev<int32_t>(WO_PATCH_TOTAL_SLOTS); p->d_patchBlk = a.dev<int32_t>(N);
+    p->h_patchTotals = a.pinned<int32_t>(WO_PATCH_TOTAL_SLOTS);          // read-back buffer of run_solve_patches
     p->sortTempBytes = sort_temp_bytes(p->N);
-    WO_HIP(hipMalloc(&p->d_sortTemp, std::max<size_t>(p->sortTempBytes, 16)));
+    p->d_sortTemp = a.dev<uint8_t>(std::max<size_t>(p->sortTempBytes, 16));
     WO_HIP(hipMemsetAsync(p->d_glac, 0, N * sizeof(float), p->ctx->stream));
+    p->mem.adopt(a);
     p->scratch = true;
 }
 
@@ -114,7 +120,8 @@ static void refresh_host_ocean(wo_planet* p) {
         p->flood.staticValid = false; ++p->oceanVersion;
     }
     p->h_ocean_valid = true;
-    if (!p->d_oceanKnown) { WO_HIP(hipMalloc((void**)&p->d_oceanKnown, (size_t)p->N)); WO_HIP(hipMalloc((void**)&p->d_maskDiff, sizeof(int32_t))); }
+    if (!p->d_maskDiff) p->d_maskDiff = p->mem.dev<int32_t>(1);
+    if (!p->d_oceanKnown) p->d_oceanKnown = p->mem.dev<uint8_t>(p->N);          // (the last of the two: the comparison above looks at this one)
     WO_HIP(hipMemcpyAsync(p->d_oceanKnown, p->d_ocean, (size_t)p->N, hipMemcpyDeviceToDevice, s));
     p->oceanKnownValid = true;
 }
@@ -125,7 +132,8 @@ static void refresh_host_ocean(wo_planet* p) {
 static int32_t read_count(wo_planet* p, const int32_t* d_ptr) {
     hipStream_t s = p->ctx->stream;
     if (!p->h_word) {
-        if (hipHostMalloc((void**)&p->h_word, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&p->d_word, p->h_word, 0) != hipSuccess) { p->h_word = nullptr; p->d_word = nullptr; (void)hipGetLastError(); }
+        p->h_word = p->mem.try_pinned<unsigned long long>(8, hipHostMallocMapped);
+        if (!p->h_word || hipHostGetDevicePointer((void**)&p->d_word, p->h_word, 0) != hipSuccess) { p->mem.release(p->h_word); p->d_word = nullptr; (void)hipGetLastError(); }
         else *p->h_word = 0;
     }
     if (p->h_word) {
@@ -255,41 +263,30 @@ struct StageClock {
 // ---------------------------------------------------------------------------------------------------
 struct FloodRun { double deviceMs = 0; int64_t rounds = 0, epochs = 0, evals = 0, ties = 0; bool usedDevice = false, fellBack = false; FloodHostStats host; };
 
-static void flood_gpu_free(wo_flood_gpu& G) {
-    dfree(G.off); dfree(G.adj); dfree(G.cell); dfree(G.seedIdx); dfree(G.seeds); dfree(G.nz); dfree(G.e);
-    dfree(G.A); dfree(G.P); dfree(G.F); dfree(G.Astk); dfree(G.Pstk); dfree(G.Fstk); dfree(G.fdEpoch); dfree(G.inDirty); dfree(G.isPending);
-    for (auto& l : G.lists) dfree(l);
-    if (G.ctrl) { (void)hipFree(G.ctrl); G.ctrl = nullptr; }
-    if (G.h_ctrl) { (void)hipHostFree(G.h_ctrl); G.h_ctrl = nullptr; }
-    dfree(G.jump); dfree(G.outPar); dfree(G.outRoot); dfree(G.outSurf);
-    if (G.h_par) { (void)hipHostFree(G.h_par); G.h_par = nullptr; }
-    if (G.h_root) { (void)hipHostFree(G.h_root); G.h_root = nullptr; }
-    if (G.h_surf) { (void)hipHostFree(G.h_surf); G.h_surf = nullptr; }
-    G.version = -1; G.cap = 0; G.L = 0;
-}
-
 static void flood_gpu_upload_static(wo_planet* p) {
     wo_flood_gpu& G = p->fgpu;
     const FloodScratch& S = p->flood;
     hipStream_t s = p->ctx->stream;
     const int32_t L = S.L;
     if (L > G.cap) {
-        flood_gpu_free(G);
-        G.cap = L + L / 16 + 1024;
-        const size_t C = (size_t)G.cap;
-        G.off = dalloc<int32_t>(C + 1); G.cell = dalloc<int32_t>(C); G.seedIdx = dalloc<int32_t>(C); G.seeds = dalloc<int32_t>(C); G.nz = dalloc<double>(C);
-        G.e = dalloc<float>(C);
-        G.A = dalloc<FlHead>(C); G.P = dalloc<FlHead>(C); G.F = dalloc<FlHead>(C);
-        G.Astk = dalloc<unsigned long long>(C * FL_LD); G.Pstk = dalloc<unsigned long long>(C * FL_LD); G.Fstk = dalloc<unsigned long long>(C * FL_LD);
-        G.fdEpoch = dalloc<int32_t>(C); G.inDirty = dalloc<int32_t>(C); G.isPending = dalloc<uint8_t>(C);
-        for (auto& l : G.lists) l = dalloc<int32_t>(C);
-        WO_HIP(hipMalloc(&G.ctrl, sizeof(FlCtrl)));
-        WO_HIP(hipHostMalloc(&G.h_ctrl, sizeof(FlCtrl)));
-        G.jump = dalloc<int32_t>(C); G.outPar = dalloc<int32_t>(C); G.outRoot = dalloc<int32_t>(C); G.outSurf = dalloc<float>(C);
-        WO_HIP(hipHostMalloc((void**)&G.h_par, C * 4)); WO_HIP(hipHostMalloc((void**)&G.h_root, C * 4)); WO_HIP(hipHostMalloc((void**)&G.h_surf, C * 4));
+        // the old state goes first; the capacity is set once every buffer is there, so a failure on the way leaves a state that the next call drops again
+        G = wo_flood_gpu{};
+        const size_t C = (size_t)L + L / 16 + 1024;
+        DeviceArena& a = G.mem;
+        G.off = a.dev<int32_t>(C + 1); G.cell = a.dev<int32_t>(C); G.seedIdx = a.dev<int32_t>(C); G.seeds = a.dev<int32_t>(C); G.nz = a.dev<double>(C);
+        G.e = a.dev<float>(C);
+        G.A = a.dev<FlHead>(C); G.P = a.dev<FlHead>(C); G.F = a.dev<FlHead>(C);
+        G.Astk = a.dev<unsigned long long>(C * FL_LD); G.Pstk = a.dev<unsigned long long>(C * FL_LD); G.Fstk = a.dev<unsigned long long>(C * FL_LD);
+        G.fdEpoch = a.dev<int32_t>(C); G.inDirty = a.dev<int32_t>(C); G.isPending = a.dev<uint8_t>(C);
+        for (auto& l : G.lists) l = a.dev<int32_t>(C);
+        G.ctrl = a.dev<FlCtrl>(1);
+        G.h_ctrl = a.pinned<FlCtrl>(1);
+        G.jump = a.dev<int32_t>(C); G.outPar = a.dev<int32_t>(C); G.outRoot = a.dev<int32_t>(C); G.outSurf = a.dev<float>(C);
+        G.h_par = a.pinned<int32_t>(C); G.h_root = a.pinned<int32_t>(C); G.h_surf = a.pinned<float>(C);
+        G.cap = (int32_t)C;
     }
-    dfree(G.adj);
-    G.adj = dalloc<int32_t>(S.adjL.size());
+    G.mem.release(G.adj);
+    G.adj = G.mem.dev<int32_t>(S.adjL.size());
     std::vector<double> nz((size_t)L);
     flood_cell_noise(S, nz.data());
     std::vector<int32_t> seedIdx((size_t)L, -1);
@@ -521,11 +518,15 @@ static void mirror_build(wo_planet* p, const uint8_t* mask = nullptr) {
         inclusive_scan_parallel(mo + 1, (int64_t)N);
     }
     lap("row offsets");
-    if (!M.perm) {
-        M.perm = dalloc<int32_t>(N); M.inv = dalloc<int32_t>(N); M.off = dalloc<int32_t>((size_t)N + 1); M.adj = dalloc<int32_t>(E + WO_ROW);
-        M.dist = dalloc<float>(E + WO_ROW);
-        WO_HIP(hipMemsetAsync(M.adj + E, 0, WO_ROW * sizeof(int32_t), s)); WO_HIP(hipMemsetAsync(M.dist + E, 0, WO_ROW * sizeof(float), s)); M.xyz = dalloc<float>(3 * (size_t)N); M.e = dalloc<float>(N); M.e2 = dalloc<float>(N);
-        M.ocean = dalloc<uint8_t>(N); M.coast = dalloc<uint8_t>(N);
+    if (!M.coast) {
+        // built in an arena of its own and handed over whole; coast, assigned last, says that the buffers are there
+        DeviceArena a;
+        M.perm = a.dev<int32_t>(N); M.inv = a.dev<int32_t>(N); M.off = a.dev<int32_t>((size_t)N + 1); M.adj = a.dev<int32_t>(E + WO_ROW);
+        M.dist = a.dev<float>(E + WO_ROW);
+        WO_HIP(hipMemsetAsync(M.adj + E, 0, WO_ROW * sizeof(int32_t), s)); WO_HIP(hipMemsetAsync(M.dist + E, 0, WO_ROW * sizeof(float), s));
+        M.xyz = a.dev<float>(3 * (size_t)N); M.e = a.dev<float>(N); M.e2 = a.dev<float>(N);
+        M.ocean = a.dev<uint8_t>(N); uint8_t* coast = a.dev<uint8_t>(N);
+        M.mem.adopt(a); M.coast = coast;
     }
     // the mirror's rows are rebuilt from the planet's own arrays: a scope must not be active (its pointers would be the mirror's)
     const int32_t* o_off = M.active ? M.o_off : p->d_off; const int32_t* o_adj = M.active ? M.o_adj : p->d_adj;
@@ -538,11 +539,6 @@ static void mirror_build(wo_planet* p, const uint8_t* mask = nullptr) {
     lap("upload + rows");
     M.built = true;
     ++M.version;
-}
-static void mirror_free(wo_planet* p) {
-    auto& M = p->mirror;
-    dfree(M.perm); dfree(M.inv); dfree(M.off); dfree(M.adj); dfree(M.dist); dfree(M.xyz); dfree(M.e); dfree(M.e2); dfree(M.ocean); dfree(M.coast); dfree(M.hot);
-    M.built = false;
 }
 struct MirrorScope {
     wo_planet* p; bool on = false; float *cur = nullptr, *cur2 = nullptr;
@@ -694,7 +690,7 @@ static bool erode_setup(ErodeCall& c) {
         WO_HIP(hipMemcpyAsync(p->d_land[0], p->d_landIdx, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     }
     if (!listsKept) {
-        if (!p->d_landInit) p->d_landInit = dalloc<int32_t>((size_t)N);
+        if (!p->d_landInit) p->d_landInit = p->mem.dev<int32_t>((size_t)N);
         WO_HIP(hipMemcpyAsync(p->d_landInit, p->d_land[0], (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
         p->landListsOcean = p->oceanVersion; p->landListsMirror = c.mir.on; p->landListsL = L;
     }
@@ -771,11 +767,15 @@ static void glacial_step_relaxed(ErodeCall& c) {
 // the carve's per-task buffers, for at least `active` tasks
 static void ensure_carve_capacity(wo_planet* p, int32_t active) {
     if ((int64_t)active <= p->carveCap) return;
-    dfree(p->d_carveDeps); dfree(p->d_carveDepCnt); dfree(p->d_carveDepPos); dfree(p->d_carveRecs); dfree(p->d_carveSlotDone); dfree(p->d_carveExpect);
-    p->carveCap = (int64_t)active + active / 4 + 1024;
-    p->d_carveDeps = dalloc<int32_t>((size_t)p->carveCap * WO_CARVE_DEPS);
-    p->d_carveDepCnt = dalloc<int32_t>((size_t)p->carveCap); p->d_carveDepPos = dalloc<int32_t>((size_t)p->carveCap);
-    p->d_carveRecs = dalloc<CarveRec>((size_t)p->carveCap); p->d_carveSlotDone = dalloc<int32_t>((size_t)p->carveCap); p->d_carveExpect = dalloc<CarveExpect>((size_t)p->carveCap);
+    // the old buffers go first; the capacity is set once every new one is there (a failure on the way: the next call releases them and starts again)
+    DeviceArena& a = p->mem;
+    a.release(p->d_carveDeps); a.release(p->d_carveDepCnt); a.release(p->d_carveDepPos); a.release(p->d_carveRecs); a.release(p->d_carveSlotDone); a.release(p->d_carveExpect);
+    p->carveCap = 0;
+    const size_t cap = (size_t)active + active / 4 + 1024;
+    p->d_carveDeps = a.dev<int32_t>(cap * WO_CARVE_DEPS);
+    p->d_carveDepCnt = a.dev<int32_t>(cap); p->d_carveDepPos = a.dev<int32_t>(cap);
+    p->d_carveRecs = a.dev<CarveRec>(cap); p->d_carveSlotDone = a.dev<int32_t>(cap); p->d_carveExpect = a.dev<CarveExpect>(cap);
+    p->carveCap = (int64_t)cap;
 }
 // k_carve_granules' grid, every task in one launch: what is certainly resident at once, the occupancy query's blocks per CU less one
 // (the query is known to answer one too many near register-file edges).  Asked once per process.
@@ -805,7 +805,7 @@ static int64_t carve_launches(ErodeCall& c, const Fields& F, int32_t active) {
     // hook carve_blocks=<n>: at most n workgroups, so that every thread takes many tasks in turn
     const int blocksNow = p->opt.carveBlocks > 0 ? std::max(1, std::min(carve_granule_blocks(), p->opt.carveBlocks)) : carve_granule_blocks();
     const long long flowBudget = p->opt.carveBudgetMs * 100000ll;   // 100 MHz ticks
-    if (!p->d_carveG) p->d_carveG = dalloc<unsigned long long>((size_t)p->N);
+    if (!p->d_carveG) p->d_carveG = p->mem.dev<unsigned long long>((size_t)p->N);
     launch(p, FAM_CARVE_SETUP, k_carve_expect, grid, WO_BLOCK, F, (const CarveRec*)p->d_carveRecs, count, p->d_carveExpect);
     launch(p, FAM_CARVE_SETUP, k_carve_pack, blocks_for(p->N, 4096), WO_BLOCK, (const float*)F.e, p->d_carveG, p->N);
     launch(p, FAM_CARVE_ROUND, k_carve_granules, std::min(grid, blocksNow), WO_BLOCK, F, (const CarveRec*)p->d_carveRecs, (const CarveExpect*)p->d_carveExpect, p->d_carveG,
@@ -846,7 +846,13 @@ static void glacial_step_exact(ErodeCall& c) {
 static FlowTiles flow_tiles_buffers(wo_planet* p) {
     const size_t N = (size_t)p->N;
     if (!p->d_ftLr) {
-        p->d_ftLr = dalloc<int32_t>(N); p->d_ftParent = dalloc<int32_t>(N); p->d_ftExtCnt = dalloc<int32_t>(N); p->d_ftInflow = dalloc<uint32_t>(N); p->d_ftRootAcc = dalloc<unsigned long long>(N);
+        // (lr, which says that the buffers are there, last)
+        DeviceArena& a = p->mem;
+        if (!p->d_ftParent) p->d_ftParent = a.dev<int32_t>(N);
+        if (!p->d_ftExtCnt) p->d_ftExtCnt = a.dev<int32_t>(N);
+        if (!p->d_ftInflow) p->d_ftInflow = a.dev<uint32_t>(N);
+        if (!p->d_ftRootAcc) p->d_ftRootAcc = a.dev<unsigned long long>(N);
+        p->d_ftLr = a.dev<int32_t>(N);
         WO_HIP(hipMemsetAsync(p->d_ftInflow, 0, N * 4, p->ctx->stream)); WO_HIP(hipMemsetAsync(p->d_ftExtCnt, 0, N * 4, p->ctx->stream));
     }
     FlowTiles FT{};
@@ -928,7 +934,8 @@ static void erode_solve_basin(ErodeCall& c, Fields F, int32_t iter) {
 // RELAXED: h' = a + b h'(receiver) composed by pointer jumping (12 doublings cover chains of 4 096 cells), then heights + deposits in one sweep
 static void erode_solve_affine(ErodeCall& c, const Fields& F) {
     wo_planet* p = c.p;
-    if (!p->d_affine[0]) { p->d_affine[0] = dalloc<Affine>((size_t)p->N); p->d_affine[1] = dalloc<Affine>((size_t)p->N); }
+    if (!p->d_affine[1]) p->d_affine[1] = p->mem.dev<Affine>((size_t)p->N);
+    if (!p->d_affine[0]) p->d_affine[0] = p->mem.dev<Affine>((size_t)p->N);
     launch(p, FAM_SOLVE_SETUP, k_affine_init, c.gridL, WO_BLOCK, F, p->d_affine[0]);
     int cur = 0;
     for (int q = 0; q < 12; ++q, cur ^= 1) launch(p, FAM_SOLVE_ROUND, k_affine_jump, c.gridL, WO_BLOCK, F, (const Affine*)p->d_affine[cur], p->d_affine[cur ^ 1]);
@@ -1059,7 +1066,7 @@ static void warp(wo_planet* p, double seed, double strength, bool useHot) {
     const float* hot = useHot ? (const float*)p->d_hot : (const float*)nullptr;
     if (mir.on && useHot) {
         auto& M = p->mirror;
-        if (!M.hot) M.hot = dalloc<float>(p->N);
+        if (!M.hot) M.hot = M.mem.dev<float>(p->N);
         launch(p, FAM_MISC, k_mirror_gather_f32, blocks_for(p->N, 4096), WO_BLOCK, (const float*)p->d_hot, (const int32_t*)M.perm, M.hot, p->N);
         hot = M.hot;
     }
@@ -1072,18 +1079,6 @@ static void warp(wo_planet* p, double seed, double strength, bool useHot) {
 }  // namespace wo
 
 namespace wo {
-// device copies of per-region host arrays, freed on scope exit (also when a HIP call throws)
-struct DevBufs {
-    std::vector<void*> bufs;
-    ~DevBufs() { for (void* b : bufs) (void)hipFree(b); }
-    template <class T> T* up(const T* host, size_t n, hipStream_t s) {
-        if (!host) return nullptr;
-        void* d = nullptr; WO_HIP(hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(T))); bufs.push_back(d);
-        WO_HIP(hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-        return (T*)d;
-    }
-    template <class T> T* alloc(size_t n) { void* d = nullptr; WO_HIP(hipMalloc(&d, std::max<size_t>(n, 1) * sizeof(T))); bufs.push_back(d); return (T*)d; }
-};
 ClimateMesh climate_mesh(const wo_planet* p) { ClimateMesh M; M.N = p->N; M.off = p->d_off; M.adj = p->d_adj; M.xyz = p->d_xyz; return M; }
 }  // namespace wo
 
@@ -1092,11 +1087,6 @@ ClimateMesh climate_mesh(const wo_planet* p) { ClimateMesh M; M.N = p->N; M.off 
 // C ABI
 // =====================================================================================================
 using namespace wo;
-
-#define WO_TRY try {
-#define WO_CATCH(fn)                                                                   \
-    } catch (const HipError& e) { set_error(std::string(fn) + ": " + e.msg); return 2; } \
-      catch (const std::exception& e) { set_error(std::string(fn) + ": " + e.what()); return 3; }
 
 Options Options::from_env() {
     auto str = [](const char* n) { const char* v = std::getenv(n); return std::string(v ? v : ""); };
@@ -1149,8 +1139,8 @@ static void erode_composite_checked(wo_planet* p, int32_t hIters, double K, doub
     // nothing is ever run again.
     if (hIters <= 0 || p->floodX.on) { erode_composite(p, hIters, K, m, dt, tIters, talus, kThermal, gIters, gStrength, true); return; }
     hipStream_t s = p->ctx->stream;
-    if (!p->d_redoE) p->d_redoE = dalloc<float>((size_t)p->N);
-    if (!p->d_pendingEver) p->d_pendingEver = dalloc<int32_t>(16);
+    if (!p->d_redoE) p->d_redoE = p->mem.dev<float>((size_t)p->N);
+    if (!p->d_pendingEver) p->d_pendingEver = p->mem.dev<int32_t>(16);
     WO_HIP(hipMemcpyAsync(p->d_redoE, p->d_e, (size_t)p->N * sizeof(float), hipMemcpyDeviceToDevice, s));
     WO_HIP(hipMemsetAsync(p->d_pendingEver, 0, 16 * sizeof(int32_t), s));
     try {
@@ -1229,12 +1219,14 @@ wo_planet* wo_planet_create(wo_ctx* ctx, int32_t numRegions, const int32_t* adjO
         p->h_adj.assign(adjList, adjList + E);
         p->h_xyz.assign(r_xyz, r_xyz + 3 * (size_t)N);
         hipStream_t s = ctx->stream;
-        p->d_off = dalloc<int32_t>(N + 1); p->d_adj = dalloc<int32_t>((size_t)E + WO_ROW); p->d_dist = dalloc<float>((size_t)E + WO_ROW); p->d_xyz = dalloc<float>(3 * (size_t)N);   // + WO_ROW: load_row reads whole 16-byte pieces
+        DeviceArena& a = p->mem;
+        // + WO_ROW: load_row reads whole 16-byte pieces
+        p->d_off = a.dev<int32_t>(N + 1); p->d_adj = a.dev<int32_t>((size_t)E + WO_ROW); p->d_dist = a.dev<float>((size_t)E + WO_ROW); p->d_xyz = a.dev<float>(3 * (size_t)N);
         WO_HIP(hipMemsetAsync(p->d_adj + E, 0, WO_ROW * sizeof(int32_t), s)); WO_HIP(hipMemsetAsync(p->d_dist + E, 0, WO_ROW * sizeof(float), s));
-        p->d_e = dalloc<float>(N); p->d_e2 = dalloc<float>(N); p->d_hot = dalloc<float>(N); p->d_orig = dalloc<float>(N);
-        p->d_ocean = dalloc<uint8_t>(N); p->d_coast = dalloc<uint8_t>(N); p->d_tables = dalloc<uint8_t>(1024);
-        WO_HIP(hipHostMalloc((void**)&p->h_pinned, std::max<size_t>((size_t)N * sizeof(float), 64)));
-        WO_HIP(hipHostMalloc((void**)&p->h_count, 64));
+        p->d_e = a.dev<float>(N); p->d_e2 = a.dev<float>(N); p->d_hot = a.dev<float>(N); p->d_orig = a.dev<float>(N);
+        p->d_ocean = a.dev<uint8_t>(N); p->d_coast = a.dev<uint8_t>(N); p->d_tables = a.dev<uint8_t>(1024);
+        p->h_pinned = a.pinned<float>(std::max<size_t>(N, 16));
+        p->h_count = a.pinned<int32_t>(16);
         WO_HIP(hipMemcpyAsync(p->d_off, adjOffset, (size_t)(N + 1) * 4, hipMemcpyHostToDevice, s));
         WO_HIP(hipMemcpyAsync(p->d_adj, adjList, (size_t)E * 4, hipMemcpyHostToDevice, s));
         WO_HIP(hipMemcpyAsync(p->d_xyz, r_xyz, (size_t)N * 12, hipMemcpyHostToDevice, s));
@@ -1262,37 +1254,19 @@ void wo_planet_destroy(wo_planet* p) {
     if (!p) return;
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
-    dfree(p->d_off); dfree(p->d_adj); dfree(p->d_dist); dfree(p->d_xyz); dfree(p->d_e); dfree(p->d_e2); dfree(p->d_hot); dfree(p->d_orig);
-    flood_gpu_free(p->fgpu);
-    if (p->floodLink && p->floodLinkFree) p->floodLinkFree(p->floodLink);
-    p->floodLink = nullptr;
-    basin_free(p);
-    import_free(p);
-    ocean_free(p);
-    wind_free(p);
     if (p->side) { (void)hipStreamSynchronize(p->side); (void)hipStreamDestroy(p->side); p->side = nullptr; }
     if (p->evFork) { (void)hipEventDestroy(p->evFork); p->evFork = nullptr; }
     if (p->evJoin) { (void)hipEventDestroy(p->evJoin); p->evJoin = nullptr; }
-    mirror_free(p);
-    dfree(p->d_ocean); dfree(p->d_coast); dfree(p->d_tables); dfree(p->d_savedE); dfree(p->d_savedOcean);
-    if (p->d_oceanKnown) { (void)hipFree(p->d_oceanKnown); p->d_oceanKnown = nullptr; } if (p->d_maskDiff) { (void)hipFree(p->d_maskDiff); p->d_maskDiff = nullptr; }
-    dfree(p->d_landInit); dfree(p->d_landIdx); dfree(p->d_land[0]); dfree(p->d_land[1]); dfree(p->d_keys[0]); dfree(p->d_keys[1]); dfree(p->d_rank);
-    dfree(p->d_cellDist); dfree(p->d_flow); dfree(p->d_task); dfree(p->d_out); dfree(p->d_flowCnt); dfree(p->d_tr); dfree(p->d_ev); dfree(p->d_me); dfree(p->d_haloSend); dfree(p->d_haloRecv); dfree(p->d_haloBuf); if (p->h_haloBuf) { (void)hipHostFree(p->h_haloBuf); p->h_haloBuf = nullptr; } dfree(p->d_carveSlot); dfree(p->d_redoE); dfree(p->d_pendingEver); for (auto& r : p->d_rs) { if (r) (void)hipFree(r); r = nullptr; } dfree(p->d_carveG); dfree(p->d_carveExpect); dfree(p->d_carveRecs); dfree(p->d_carveSlotDone); dfree(p->d_carveDeps); dfree(p->d_carveDepCnt); dfree(p->d_carveDepPos); dfree(p->d_ftLr); dfree(p->d_ftParent); dfree(p->d_affine[0]); dfree(p->d_affine[1]); dfree(p->d_ftExtCnt); dfree(p->d_ftInflow); dfree(p->d_ftRootAcc); dfree(p->d_accCnt); dfree(p->d_jump); dfree(p->d_nj);
-    dfree(p->d_doneAt); dfree(p->d_totalExcess);
-    dfree(p->d_glac); dfree(p->d_iceFlow); dfree(p->d_iceTarget); dfree(p->d_arank); dfree(p->d_iceUp);
-    dfree(p->d_patchOrder); dfree(p->d_slotOf); dfree(p->d_patchPending); dfree(p->d_patchTotals); dfree(p->d_patchBlk);
-    dfree(p->d_listA); dfree(p->d_listB); dfree(p->d_counters);
-    if (p->h_patchTotals) (void)hipHostFree(p->h_patchTotals);
-    if (p->d_sortTemp) (void)hipFree(p->d_sortTemp);
-    if (p->h_pinned) (void)hipHostFree(p->h_pinned);
-    if (p->h_count) (void)hipHostFree(p->h_count);
-    if (p->h_word) { (void)hipHostFree(p->h_word); p->h_word = nullptr; }
+    if (p->floodLink && p->floodLinkFree) p->floodLinkFree(p->floodLink);
+    p->floodLink = nullptr;
+    ocean_free(p);
+    wind_free(p);
     for (auto& pe : p->pending) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
     for (auto& b : p->stageBrackets) { (void)hipEventDestroy(b.a); (void)hipEventDestroy(b.b); }
     for (auto e : p->eventPool) (void)hipEventDestroy(e);
     if (p->evStart) (void)hipEventDestroy(p->evStart);
     if (p->evStop) (void)hipEventDestroy(p->evStop);
-    delete p;
+    delete p;                           // its arenas (the planet's own, flood state, import scratch, mirror) free the memory
 }
 
 int wo_planet_upload(wo_planet* p, const float* r_elevation, const uint8_t* r_isOcean) {
@@ -1322,12 +1296,14 @@ int wo_planet_set_halo(wo_planet* p, const int32_t* sendIdx, int32_t nSend, cons
     for (int32_t i = 0; i < nRecv; ++i) if (recvIdx[i] < 0 || recvIdx[i] >= p->N) { set_error("wo_planet_set_halo: receive index out of range"); return 1; }
     WO_TRY
     hipStream_t s = p->ctx->stream;
-    dfree(p->d_haloSend); dfree(p->d_haloRecv); dfree(p->d_haloBuf);
-    if (p->h_haloBuf) { (void)hipHostFree(p->h_haloBuf); p->h_haloBuf = nullptr; }
-    p->nHaloSend = nSend; p->nHaloRecv = nRecv;
+    // the old lists go first; the counts are set once the new buffers are there
+    DeviceArena& a = p->mem;
+    a.release(p->d_haloSend); a.release(p->d_haloRecv); a.release(p->d_haloBuf); a.release(p->h_haloBuf);
+    p->nHaloSend = 0; p->nHaloRecv = 0;
     const size_t m = (size_t)std::max(nSend, nRecv);
-    p->d_haloSend = dalloc<int32_t>(nSend); p->d_haloRecv = dalloc<int32_t>(nRecv); p->d_haloBuf = dalloc<float>(m);
-    WO_HIP(hipHostMalloc((void**)&p->h_haloBuf, std::max<size_t>(m * sizeof(float), 64)));
+    p->d_haloSend = a.dev<int32_t>(nSend); p->d_haloRecv = a.dev<int32_t>(nRecv); p->d_haloBuf = a.dev<float>(m);
+    p->h_haloBuf = a.pinned<float>(std::max<size_t>(m, 16));
+    p->nHaloSend = nSend; p->nHaloRecv = nRecv;
     if (nSend) WO_HIP(hipMemcpyAsync(p->d_haloSend, sendIdx, (size_t)nSend * 4, hipMemcpyHostToDevice, s));
     if (nRecv) WO_HIP(hipMemcpyAsync(p->d_haloRecv, recvIdx, (size_t)nRecv * 4, hipMemcpyHostToDevice, s));
     WO_HIP(hipStreamSynchronize(s));
@@ -1439,7 +1415,8 @@ int wo_planet_sync(wo_planet* p) {
 int wo_planet_save_state(wo_planet* p) {
     if (!check_planet(p, "wo_planet_save_state")) return 1;
     WO_TRY
-    if (!p->d_savedE) { p->d_savedE = dalloc<float>(p->N); p->d_savedOcean = dalloc<uint8_t>(p->N); }
+    if (!p->d_savedOcean) p->d_savedOcean = p->mem.dev<uint8_t>(p->N);
+    if (!p->d_savedE) p->d_savedE = p->mem.dev<float>(p->N);
     WO_HIP(hipMemcpyAsync(p->d_savedE, p->d_e, (size_t)p->N * 4, hipMemcpyDeviceToDevice, p->ctx->stream));
     WO_HIP(hipMemcpyAsync(p->d_savedOcean, p->d_ocean, (size_t)p->N, hipMemcpyDeviceToDevice, p->ctx->stream));
     p->saved = true;
@@ -1513,13 +1490,12 @@ int wo_planet_synthetic_terrain(wo_planet* p, double seed) {
 static int with_host_field(wo_planet* p, const char* fn, float* e, const uint8_t* oc, bool needOcean, void (*body)(wo_planet*, void*), void* arg) {
     if (!check_planet(p, fn)) return 1;
     if (!e || (needOcean && !oc)) { set_error(std::string(fn) + ": null pointer"); return 1; }
-    try {
-        int rc = wo_planet_upload(p, e, oc);
-        if (rc) return rc;
-        body(p, arg);
-        return wo_planet_download(p, e);
-    } catch (const HipError& ex) { set_error(std::string(fn) + ": " + ex.msg); return 2; }
-      catch (const std::exception& ex) { set_error(std::string(fn) + ": " + ex.what()); return 3; }
+    WO_TRY
+    int rc = wo_planet_upload(p, e, oc);
+    if (rc) return rc;
+    body(p, arg);
+    return wo_planet_download(p, e);
+    WO_CATCH(fn)
 }
 
 struct JacArgs { int kind; int32_t it; double s; };
@@ -1556,18 +1532,16 @@ int wo_smooth_field(wo_planet* p, float* field, int32_t passes) {
     if (!check_planet(p, "wo_smooth_field")) return 1;
     if (!field) { set_error("wo_smooth_field: null field"); return 1; }
     if (passes <= 0) return 0;
-    float *a = nullptr, *b = nullptr;
-    try {
-        hipStream_t s = p->ctx->stream;
-        const size_t bytes = (size_t)p->N * sizeof(float);
-        a = dalloc<float>(p->N); b = dalloc<float>(p->N);
-        WO_HIP(hipMemcpyAsync(a, field, bytes, hipMemcpyHostToDevice, s));
-        WO_HIP(hipMemcpyAsync(field, smooth_field_resident(p, a, b, passes), bytes, hipMemcpyDeviceToHost, s));
-        WO_HIP(hipStreamSynchronize(s));
-        dfree(a); dfree(b);
-        return 0;
-    } catch (const HipError& e) { dfree(a); dfree(b); set_error(std::string("wo_smooth_field: ") + e.msg); return 2; }
-      catch (const std::exception& e) { dfree(a); dfree(b); set_error(std::string("wo_smooth_field: ") + e.what()); return 3; }
+    WO_TRY
+    hipStream_t s = p->ctx->stream;
+    const size_t bytes = (size_t)p->N * sizeof(float);
+    DeviceArena B;
+    float* a = B.dev<float>(p->N); float* b = B.dev<float>(p->N);
+    WO_HIP(hipMemcpyAsync(a, field, bytes, hipMemcpyHostToDevice, s));
+    WO_HIP(hipMemcpyAsync(field, smooth_field_resident(p, a, b, passes), bytes, hipMemcpyDeviceToHost, s));
+    WO_HIP(hipStreamSynchronize(s));
+    return 0;
+    WO_CATCH("wo_smooth_field")
 }
 
 // ---- climate sweeps on caller-owned fields (js/temperature.js:19-66, js/precipitation.js:18-52, :59-195) ----
@@ -1577,9 +1551,9 @@ int wo_diffuse_ocean_warmth(wo_planet* p, const float* r_oceanWarmth, const uint
     if (!r_isLand || !out) { set_error("wo_diffuse_ocean_warmth: null pointer"); return 1; }
     WO_TRY
     hipStream_t s = p->ctx->stream; const size_t N = (size_t)p->N;
-    DevBufs B;
-    const float* w = B.up(r_oceanWarmth, N, s); const uint8_t* land = B.up(r_isLand, N, s); const float* cont = B.up(r_plateContinentality, N, s);
-    float* a = B.alloc<float>(N); float* b = B.alloc<float>(N);
+    DeviceArena B;
+    const float* w = up(B, r_oceanWarmth, N, s); const uint8_t* land = up(B, r_isLand, N, s); const float* cont = up(B, r_plateContinentality, N, s);
+    float* a = B.dev<float>(N); float* b = B.dev<float>(N);
     launch(p, FAM_CLIMATE, k_warmth_seed, blocks_for(p->N, 4096), WO_BLOCK, w, land, a, p->N);
     const Fields F = p->fields(); const ClimateMesh M = climate_mesh(p);
     for (int32_t pass = 0; pass < passes; ++pass) { launch(p, FAM_CLIMATE, k_warmth_diffuse, xcd_grid(p->N), WO_BLOCK, F, M, (const float*)a, cont, b); std::swap(a, b); }
@@ -1594,9 +1568,9 @@ int wo_wind_convergence(wo_planet* p, const float* r_wind3dX, const float* r_win
     if (!r_wind3dX || !r_wind3dY || !r_wind3dZ || !out) { set_error("wo_wind_convergence: null pointer"); return 1; }
     WO_TRY
     hipStream_t s = p->ctx->stream; const size_t N = (size_t)p->N;
-    DevBufs B;
-    const float* wx = B.up(r_wind3dX, N, s); const float* wy = B.up(r_wind3dY, N, s); const float* wz = B.up(r_wind3dZ, N, s);
-    float* o = B.alloc<float>(N);
+    DeviceArena B;
+    const float* wx = up(B, r_wind3dX, N, s); const float* wy = up(B, r_wind3dY, N, s); const float* wz = up(B, r_wind3dZ, N, s);
+    float* o = B.dev<float>(N);
     launch(p, FAM_CLIMATE, k_wind_convergence, xcd_grid(p->N), WO_BLOCK, p->fields(), climate_mesh(p), wx, wy, wz, o);
     WO_HIP(hipMemcpyAsync(out, o, N * sizeof(float), hipMemcpyDeviceToHost, s));
     WO_HIP(hipStreamSynchronize(s));
@@ -1612,11 +1586,11 @@ int wo_advect_moisture(wo_planet* p, const float* r_heightKm, const uint8_t* r_i
     if (maxHops < 1) { set_error("wo_advect_moisture: maxHops must be >= 1"); return 1; }
     WO_TRY
     hipStream_t s = p->ctx->stream; const size_t N = (size_t)p->N;
-    DevBufs B;
-    const float* hk = B.up(r_heightKm, N, s); const uint8_t* land = B.up(r_isLand, N, s); const float* we = B.up(r_windE, N, s); const float* wn = B.up(r_windN, N, s);
-    const float* wx = B.up(r_wind3dX, N, s); const float* wy = B.up(r_wind3dY, N, s); const float* wz = B.up(r_wind3dZ, N, s);
-    const float* w = B.up(r_oceanWarmth, N, s); const int32_t* cd = B.up(r_coastDistLand, N, s);
-    float* a = B.alloc<float>(N); float* b = B.alloc<float>(N);
+    DeviceArena B;
+    const float* hk = up(B, r_heightKm, N, s); const uint8_t* land = up(B, r_isLand, N, s); const float* we = up(B, r_windE, N, s); const float* wn = up(B, r_windN, N, s);
+    const float* wx = up(B, r_wind3dX, N, s); const float* wy = up(B, r_wind3dY, N, s); const float* wz = up(B, r_wind3dZ, N, s);
+    const float* w = up(B, r_oceanWarmth, N, s); const int32_t* cd = up(B, r_coastDistLand, N, s);
+    float* a = B.dev<float>(N); float* b = B.dev<float>(N);
     const Fields F = p->fields(); const ClimateMesh M = climate_mesh(p);
     const double depletionBase = 1 - std::pow(0.78, 1.0 / maxHops);                  // js/precipitation.js:123
     launch(p, FAM_CLIMATE, k_moisture_seed, xcd_grid(p->N), WO_BLOCK, F, M, land, wx, wy, wz, w, cd, a);
@@ -1631,6 +1605,14 @@ int wo_advect_moisture(wo_planet* p, const float* r_heightKm, const uint8_t* r_i
 }
 
 int32_t wo_planet_num_regions(const wo_planet* p) { return p ? p->N : 0; }
+
+int wo_memory_in_use(int64_t* deviceBytes, int64_t* pinnedBytes, int64_t* allocCalls) {
+    const MemoryInUse& m = memory_in_use();
+    if (deviceBytes) *deviceBytes = m.deviceBytes.load();
+    if (pinnedBytes) *pinnedBytes = m.pinnedBytes.load();
+    if (allocCalls) *allocCalls = m.allocCalls.load();
+    return 0;
+}
 
 // projectCoarsePlates (js/coarse-plates.js:51-117) on the planet's resident r_xyz
 int wo_project_coarse_plates(wo_planet* p, int32_t coarseRegions, const int32_t* coarseAdjOffset, const int32_t* coarseAdjList,
@@ -1647,19 +1629,15 @@ int wo_project_coarse_plates(wo_planet* p, int32_t coarseRegions, const int32_t*
         for (int32_t i = 0; i < Ec; ++i)
             if (coarseAdjList[i] < 0 || coarseAdjList[i] >= coarseRegions) { set_error("wo_project_coarse_plates: coarseAdjList entry out of range"); return 1; }
     }
-    int32_t *d_off = nullptr, *d_adj = nullptr, *d_plate = nullptr, *d_grid = nullptr, *d_out = nullptr; float* d_cxyz = nullptr;
     WO_TRY
     hipStream_t s = p->ctx->stream;
     const int32_t NC = coarseRegions, E = coarseAdjOffset[NC];
     CoarsePlates C;
     C.NC = NC; C.gridZ = 64; C.gridLon = 128;
-    d_off = dalloc<int32_t>(NC + 1); d_adj = dalloc<int32_t>(E); d_plate = dalloc<int32_t>(NC); d_cxyz = dalloc<float>(3 * (size_t)NC);
-    d_grid = dalloc<int32_t>((size_t)C.gridZ * C.gridLon); d_out = dalloc<int32_t>(p->N);
-    WO_HIP(hipMemcpyAsync(d_off, coarseAdjOffset, (size_t)(NC + 1) * 4, hipMemcpyHostToDevice, s));
-    WO_HIP(hipMemcpyAsync(d_adj, coarseAdjList, (size_t)E * 4, hipMemcpyHostToDevice, s));
-    WO_HIP(hipMemcpyAsync(d_plate, coarse_r_plate, (size_t)NC * 4, hipMemcpyHostToDevice, s));
-    WO_HIP(hipMemcpyAsync(d_cxyz, coarse_xyz, (size_t)NC * 12, hipMemcpyHostToDevice, s));
-    C.off = d_off; C.adj = d_adj; C.xyz = d_cxyz; C.plate = d_plate; C.grid = nullptr;
+    DeviceArena B;
+    C.off = up(B, coarseAdjOffset, (size_t)NC + 1, s); C.adj = up(B, coarseAdjList, (size_t)E, s); C.plate = up(B, coarse_r_plate, (size_t)NC, s);
+    C.xyz = up(B, coarse_xyz, 3 * (size_t)NC, s); C.grid = nullptr;
+    int32_t* d_grid = B.dev<int32_t>((size_t)C.gridZ * C.gridLon); int32_t* d_out = B.dev<int32_t>(p->N);
     launch(p, FAM_PLATE_GRID, k_plate_grid, blocks_for((int64_t)C.gridZ * C.gridLon), WO_BLOCK, C, d_grid);
     C.grid = d_grid;
     upload_tables(p, seed + 999);                                                       // :57
@@ -1670,38 +1648,29 @@ int wo_project_coarse_plates(wo_planet* p, int32_t coarseRegions, const int32_t*
     launch(p, FAM_PLATE_PROJECT, k_plate_project, blocks_for(p->N), WO_BLOCK, C, (const uint8_t*)p->d_tables, (const float*)p->d_xyz, p->N, perturbAmp, d_out);
     WO_HIP(hipMemcpyAsync(r_plate, d_out, (size_t)p->N * 4, hipMemcpyDeviceToHost, s));
     WO_HIP(hipStreamSynchronize(s));
-    dfree(d_off); dfree(d_adj); dfree(d_plate); dfree(d_cxyz); dfree(d_grid); dfree(d_out);
     return 0;
-    } catch (const HipError& e) {
-        dfree(d_off); dfree(d_adj); dfree(d_plate); dfree(d_cxyz); dfree(d_grid); dfree(d_out);
-        set_error(std::string("wo_project_coarse_plates: ") + e.msg); return 2;
-    } catch (const std::exception& e) {
-        dfree(d_off); dfree(d_adj); dfree(d_plate); dfree(d_cxyz); dfree(d_grid); dfree(d_out);
-        set_error(std::string("wo_project_coarse_plates: ") + e.what()); return 3;
-    }
+    WO_CATCH("wo_project_coarse_plates")
 }
 
 int wo_noise_eval(wo_ctx* ctx, double seed, int32_t kind, int32_t octaves, double p0, double p1, double p2, int64_t n,
                   const double* xyz, double* out) {
     if (!ctx || !xyz || !out || n < 0 || kind < 0 || kind > 2) { set_error("wo_noise_eval: bad arguments"); return 1; }
     if (n == 0) return 0;
-    double *d_in = nullptr, *d_out = nullptr; uint8_t* d_t = nullptr;
-    try {
-        WO_HIP(hipSetDevice(ctx->device));
-        uint8_t t[1024];
-        noise_tables(seed, t, t + 512);
-        d_in = dalloc<double>(3 * (size_t)n); d_out = dalloc<double>((size_t)n); d_t = dalloc<uint8_t>(1024);
-        hipStream_t s = ctx->stream;
-        WO_HIP(hipMemcpyAsync(d_t, t, 1024, hipMemcpyHostToDevice, s));
-        WO_HIP(hipMemcpyAsync(d_in, xyz, 3 * (size_t)n * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_noise_eval, dim3(blocks_for(n, 4096)), dim3(WO_BLOCK), 0, s, (const uint8_t*)d_t, kind, octaves, p0, p1, p2, n,
-                           (const double*)d_in, d_out);
-        WO_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-        WO_HIP(hipStreamSynchronize(s));
-        dfree(d_in); dfree(d_out); dfree(d_t);
-        return 0;
-    } catch (const HipError& e) { dfree(d_in); dfree(d_out); dfree(d_t); set_error(std::string("wo_noise_eval: ") + e.msg); return 2; }
-      catch (const std::exception& e) { dfree(d_in); dfree(d_out); dfree(d_t); set_error(std::string("wo_noise_eval: ") + e.what()); return 3; }
+    WO_TRY
+    WO_HIP(hipSetDevice(ctx->device));
+    uint8_t t[1024];
+    noise_tables(seed, t, t + 512);
+    hipStream_t s = ctx->stream;
+    DeviceArena B;
+    double* d_in = B.dev<double>(3 * (size_t)n); double* d_out = B.dev<double>((size_t)n); uint8_t* d_t = B.dev<uint8_t>(1024);
+    WO_HIP(hipMemcpyAsync(d_t, t, 1024, hipMemcpyHostToDevice, s));
+    WO_HIP(hipMemcpyAsync(d_in, xyz, 3 * (size_t)n * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_noise_eval, dim3(blocks_for(n, 4096)), dim3(WO_BLOCK), 0, s, (const uint8_t*)d_t, kind, octaves, p0, p1, p2, n,
+                       (const double*)d_in, d_out);
+    WO_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    WO_HIP(hipStreamSynchronize(s));
+    return 0;
+    WO_CATCH("wo_noise_eval")
 }
 
 // ---- measurement ----
@@ -1804,37 +1773,33 @@ int wo_last_erode_stats(wo_planet* p, int32_t cap, const char** names, double* v
 // ---------------------------------------------------------------------------------------------------
 namespace wo {
 
-struct DevPlateTable {
-    PlateTable t{}; uint8_t* hasVec = nullptr; double* pole = nullptr; double* omega = nullptr; uint8_t* isOcean = nullptr; double* density = nullptr;
-    void upload(const wo_plate_table& h, hipStream_t s) {
-        const size_t n = (size_t)h.numIds;
-        hasVec = dalloc<uint8_t>(n); pole = dalloc<double>(3 * n); omega = dalloc<double>(n); isOcean = dalloc<uint8_t>(n); density = dalloc<double>(n);
-        WO_HIP(hipMemcpyAsync(hasVec, h.hasVec, n, hipMemcpyHostToDevice, s));
-        WO_HIP(hipMemcpyAsync(pole, h.pole, 3 * n * 8, hipMemcpyHostToDevice, s));
-        WO_HIP(hipMemcpyAsync(omega, h.omega, n * 8, hipMemcpyHostToDevice, s));
-        WO_HIP(hipMemcpyAsync(isOcean, h.isOcean, n, hipMemcpyHostToDevice, s));
-        WO_HIP(hipMemcpyAsync(density, h.density, n * 8, hipMemcpyHostToDevice, s));
-        t.numIds = h.numIds; t.hasVec = hasVec; t.pole = pole; t.omega = omega; t.isOcean = isOcean; t.density = density;
-    }
-    void release() { dfree(hasVec); dfree(pole); dfree(omega); dfree(isOcean); dfree(density); }
-};
+// a plate table on the device, its arrays in `a`
+static PlateTable upload_table(DeviceArena& a, const wo_plate_table& h, hipStream_t s) {
+    const size_t n = (size_t)h.numIds;
+    PlateTable t{};
+    t.numIds = h.numIds; t.hasVec = up(a, h.hasVec, n, s); t.pole = up(a, h.pole, 3 * n, s); t.omega = up(a, h.omega, n, s);
+    t.isOcean = up(a, h.isOcean, n, s); t.density = up(a, h.density, n, s);
+    return t;
+}
 
 struct DevCollision {
     CollisionOut o{};
-    void alloc(size_t N) { o.stress = dalloc<float>(N); o.subduct = dalloc<float>(N); o.btype = dalloc<int8_t>(N); o.bothOcean = dalloc<uint8_t>(N); o.hasOcean = dalloc<uint8_t>(N); o.setCode = dalloc<uint8_t>(N); }
+    void alloc(DeviceArena& a, size_t N) {
+        o.stress = a.dev<float>(N); o.subduct = a.dev<float>(N); o.btype = a.dev<int8_t>(N);
+        o.bothOcean = a.dev<uint8_t>(N); o.hasOcean = a.dev<uint8_t>(N); o.setCode = a.dev<uint8_t>(N);
+    }
     void download(CollisionHost& h, size_t N, hipStream_t s) {
         h.resize((int32_t)N);
         WO_HIP(hipMemcpyAsync(h.stress.data(), o.stress, N * 4, hipMemcpyDeviceToHost, s)); WO_HIP(hipMemcpyAsync(h.subduct.data(), o.subduct, N * 4, hipMemcpyDeviceToHost, s));
         WO_HIP(hipMemcpyAsync(h.btype.data(), o.btype, N, hipMemcpyDeviceToHost, s)); WO_HIP(hipMemcpyAsync(h.bothOcean.data(), o.bothOcean, N, hipMemcpyDeviceToHost, s));
         WO_HIP(hipMemcpyAsync(h.hasOcean.data(), o.hasOcean, N, hipMemcpyDeviceToHost, s)); WO_HIP(hipMemcpyAsync(h.setCode.data(), o.setCode, N, hipMemcpyDeviceToHost, s));
     }
-    void release() { dfree(o.stress); dfree(o.subduct); dfree(o.btype); dfree(o.bothOcean); dfree(o.hasOcean); dfree(o.setCode); }
 };
 
 static PlateTable host_table(const wo_plate_table& h) { PlateTable t; t.numIds = h.numIds; t.hasVec = h.hasVec; t.pole = h.pole; t.omega = h.omega; t.isOcean = h.isOcean; t.density = h.density; return t; }
 
-template <class T, class A> static T* upload_vec(const std::vector<T, A>& v, hipStream_t s) {
-    T* d = dalloc<T>(v.size());
+template <class T, class A> static T* upload_vec(DeviceArena& a, const std::vector<T, A>& v, hipStream_t s) {
+    T* d = a.dev<T>(v.size());
     WO_HIP(hipMemcpyAsync(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
     return d;
 }
@@ -1859,22 +1824,20 @@ static void assign_elevation(wo_planet* p, const int32_t* r_plate, const wo_plat
     const double offs[EL_TAB_COUNT] = {0, 419, 557, 77, 133, 211, 307, 501, 502};
     for (int k = 1; k < EL_TAB_COUNT; ++k) noise_tables(seed + offs[k], tabs.data() + k * 1024, tabs.data() + k * 1024 + 512);
     noise_tables(seed + 503, hs3.data(), hs3.data() + 512);
-    uint8_t* d_tabs = upload_vec(tabs, s);
-    int32_t* d_plate = dalloc<int32_t>(N);
-    WO_HIP(hipMemcpyAsync(d_plate, r_plate, (size_t)N * 4, hipMemcpyHostToDevice, s));
-    DevPlateTable dT, dTS; dT.upload(*plates, s);
-    DevCollision cS, cP; cS.alloc(N);
+    DeviceArena mem;                        // every device buffer of the call: freed when the call ends, however it ends
+    uint8_t* d_tabs = upload_vec(mem, tabs, s);
+    int32_t* d_plate = up(mem, r_plate, (size_t)N, s);
+    const PlateTable dT = upload_table(mem, *plates, s);
+    DevCollision cS, cP; cS.alloc(mem, N);
     CollisionHost hS, hP;
     launch(p, FAM_ELEV_COLLISION, k_collision, gridN, WO_BLOCK, N, (const int32_t*)p->d_off, (const int32_t*)p->d_adj, (const float*)p->d_xyz,
-           (const int32_t*)d_plate, dT.t, (const uint8_t*)d_tabs, cS.o);
+           (const int32_t*)d_plate, dT, (const uint8_t*)d_tabs, cS.o);
     cS.download(hS, N, s);
-    int32_t* d_super = nullptr;
     if (hasSuper) {
-        d_super = dalloc<int32_t>(N);
-        WO_HIP(hipMemcpyAsync(d_super, r_superPlate, (size_t)N * 4, hipMemcpyHostToDevice, s));
-        dTS.upload(*superPlates, s); cP.alloc(N);
+        int32_t* d_super = up(mem, r_superPlate, (size_t)N, s);
+        const PlateTable dTS = upload_table(mem, *superPlates, s); cP.alloc(mem, N);
         launch(p, FAM_ELEV_COLLISION, k_collision, gridN, WO_BLOCK, N, (const int32_t*)p->d_off, (const int32_t*)p->d_adj, (const float*)p->d_xyz,
-               (const int32_t*)d_super, dTS.t, (const uint8_t*)d_tabs, cP.o);
+               (const int32_t*)d_super, dTS, (const uint8_t*)d_tabs, cP.o);
         cP.download(hP, N, s);
     }
     lap(hasSuper ? "Collisions (dual)" : "Collisions");
@@ -1891,9 +1854,8 @@ static void assign_elevation(wo_planet* p, const int32_t* r_plate, const wo_plat
     // host stage as soon as their inputs exist and overlapped with the serial RNG-ordered distance fields on the host.
     ElevFields F{};
     F.xyz = p->d_xyz; F.plate = d_plate;
-    std::vector<void*> tmp;
-    auto up = [&](auto& v) { auto* d = upload_vec(v, s); tmp.push_back((void*)d); return d; };
-    auto dev = [&](auto* proto, size_t n) { using T = std::remove_pointer_t<decltype(proto)>; T* d = dalloc<T>(n); tmp.push_back((void*)d); return d; };
+    auto up = [&](auto& v) { return upload_vec(mem, v, s); };
+    auto dev = [&](auto* proto, size_t n) { return mem.dev<std::remove_pointer_t<decltype(proto)>>(n); };
     float *b_dBdry = nullptr, *b_csm = nullptr, *b_cssm = nullptr, *b_rift = nullptr, *b_ridge = nullptr, *b_frac = nullptr, *b_ba = nullptr, *b_bas = nullptr, *b_arc = nullptr, *b_arcs = nullptr;
     uint8_t* b_conv = nullptr;
     std::vector<std::vector<int32_t>> bfsSeeds;             // host seed lists stay alive until the stream has consumed them
@@ -1966,11 +1928,11 @@ static void assign_elevation(wo_planet* p, const int32_t* r_plate, const wo_plat
     F.distCoastLand = up(H.distCoastLand);
     F.elev = p->d_e;
     float* d_dl = nullptr;
-    if (debugLayers) { d_dl = dalloc<float>((size_t)DL_COUNT * N); WO_HIP(hipMemsetAsync(d_dl, 0, (size_t)DL_COUNT * N * 4, s)); }
+    if (debugLayers) { d_dl = mem.dev<float>((size_t)DL_COUNT * N); WO_HIP(hipMemsetAsync(d_dl, 0, (size_t)DL_COUNT * N * 4, s)); }
     F.dl = d_dl;
     if (domes.empty()) domes.push_back(Dome{});
-    Dome* d_domes = upload_vec(domes, s);
-    launch(p, FAM_ELEV_MAIN, k_elevation, gridN, WO_BLOCK, F, Q, dT.t, (const uint8_t*)d_tabs, (const Dome*)d_domes);
+    Dome* d_domes = upload_vec(mem, domes, s);
+    launch(p, FAM_ELEV_MAIN, k_elevation, gridN, WO_BLOCK, F, Q, dT, (const uint8_t*)d_tabs, (const Dome*)d_domes);
     if (r_elevation) WO_HIP(hipMemcpyAsync(r_elevation, p->d_e, (size_t)N * 4, hipMemcpyDeviceToHost, s));
     if (debugLayers) WO_HIP(hipMemcpyAsync(debugLayers, d_dl, (size_t)DL_COUNT * N * 4, hipMemcpyDeviceToHost, s));
     lap("Elevation loop + coastal + arcs + hotspots + compression (device)");
@@ -1979,11 +1941,6 @@ static void assign_elevation(wo_planet* p, const int32_t* r_plate, const wo_plat
     if (coastline_r) std::memcpy(coastline_r, H.coastline.data(), H.coastline.size() * 4);
     if (ocean_r) std::memcpy(ocean_r, H.ocean.data(), H.ocean.size() * 4);
     if (setCounts) { setCounts[0] = (int32_t)H.mountain.size(); setCounts[1] = (int32_t)H.coastline.size(); setCounts[2] = (int32_t)H.ocean.size(); }
-    for (void* d : tmp) (void)hipFree(d);
-    (void)hipFree(d_tabs); (void)hipFree(d_plate); (void)hipFree(d_domes);
-    if (d_super) (void)hipFree(d_super);
-    if (d_dl) (void)hipFree(d_dl);
-    dT.release(); dTS.release(); cS.release(); cP.release();
     release_stage_brackets(p);
     p->stageTiming = timing;
 }

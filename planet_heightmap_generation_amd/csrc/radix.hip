@@ -225,8 +225,9 @@ int radix_sort_pairs(wo_planet* p, int family, uint32_t* const keys[2], int32_t*
 uint32_t* radix_scratch(wo_planet* p, int which) {
     if (!p->d_rs[which]) {
         const size_t words = radix_scratch_words(p->N);
-        WO_HIP(hipMalloc((void**)&p->d_rs[which], words * 4));
-        WO_HIP(hipMemsetAsync(p->d_rs[which], 0, words * 4, cur_stream(p)));
+        uint32_t* rs = p->mem.dev<uint32_t>(words);
+        WO_HIP(hipMemsetAsync(rs, 0, words * 4, cur_stream(p)));
+        p->d_rs[which] = rs;
         p->rsFlip[which] = 0;
     }
     return p->d_rs[which];

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -200,54 +201,34 @@ __global__ __launch_bounds__(WO_BLOCK) void k_wind_finish(float* __restrict__ sp
     WIND_CELLS(r, N) { speed[r] = W::normalise_speed_cell(speed[r], m); pressureDev[r] = W::pressure_dev_cell(pressure[r]); }
 }
 
-void wind_free(wo_planet* p);
-static void wind_alloc_buffers(wo_planet* p, wo_wind_block* B);
 void wind_alloc(wo_planet* p) {
     if (p->wind) return;
-    auto* B = new wo_wind_block();
-    p->wind = B;
-    try { wind_alloc_buffers(p, B); }
-    catch (...) { wind_free(p); throw; }                     // never leave a half-allocated block behind: the next call allocates again
-}
-static void wind_alloc_buffers(wo_planet* p, wo_wind_block* B) {
+    std::unique_ptr<wo_wind_block> block(new wo_wind_block());          // the planet gets the block once it is complete
+    wo_wind_block* B = block.get(); DeviceArena& a = B->mem;
     const size_t N = (size_t)p->N;
-    for (auto& s : B->season) for (auto& a : s) walloc(a, N);
-    walloc(B->lat, N); walloc(B->lon, N); walloc(B->sinLat, N); walloc(B->cosLat, N); walloc(B->isLand, N);
-    walloc(B->cont, N); walloc(B->plateCont, N); walloc(B->coastDist, N);
-    for (auto& f : B->frame) walloc(f, N);
-    walloc(B->e, N); walloc(B->tmpA, N); walloc(B->tmpB, N); walloc(B->gradE, N); walloc(B->gradN, N);
-    walloc(B->label, N); walloc(B->compSize, N); walloc(B->plateDist, N); walloc(B->plate, N); walloc(B->plateOcean, N);
-    for (int i = 0; i < 2; ++i) { walloc(B->keys[i], N); walloc(B->vals[i], N); walloc(B->frontier[i], N); }
+    for (auto& s : B->season) for (auto& f : s) f = a.dev<float>(N);
+    B->lat = a.dev<float>(N); B->lon = a.dev<float>(N); B->sinLat = a.dev<float>(N); B->cosLat = a.dev<float>(N); B->isLand = a.dev<uint8_t>(N);
+    B->cont = a.dev<float>(N); B->plateCont = a.dev<float>(N); B->coastDist = a.dev<int32_t>(N);
+    for (auto& f : B->frame) f = a.dev<float>(N);
+    B->e = a.dev<float>(N); B->tmpA = a.dev<float>(N); B->tmpB = a.dev<float>(N); B->gradE = a.dev<float>(N); B->gradN = a.dev<float>(N);
+    B->label = a.dev<int32_t>(N); B->compSize = a.dev<int32_t>(N); B->plateDist = a.dev<int32_t>(N); B->plate = a.dev<int32_t>(N); B->plateOcean = a.dev<uint8_t>(N);
+    for (int i = 0; i < 2; ++i) { B->keys[i] = a.dev<uint32_t>(N); B->vals[i] = a.dev<int32_t>(N); B->frontier[i] = a.dev<int32_t>(N); }
     const size_t words = radix_scratch_words(p->N);
-    walloc(B->sortScratch, words);
+    B->sortScratch = a.dev<uint32_t>(words);
     WO_HIP(hipMemsetAsync(B->sortScratch, 0, words * 4, p->ctx->stream));
-    walloc(B->binOffset, (size_t)W::NUM_BINS + 1);
-    walloc(B->counts, 3); walloc(B->mainKey, 1);
-    walloc(B->specs, (size_t)W::NUM_SAMPLES); walloc(B->acc, (size_t)W::NUM_SAMPLES); walloc(B->splines, 2);
-    walloc(B->selHist, (size_t)W::SEL_BINS); walloc(B->selState, 1); walloc(B->maxSpeed, 1);
-    WO_HIP(hipHostMalloc((void**)&B->h_acc, sizeof(W::SampleAcc) * W::NUM_SAMPLES));
-    WO_HIP(hipHostMalloc((void**)&B->h_count, 64));
+    B->binOffset = a.dev<int32_t>((size_t)W::NUM_BINS + 1);
+    B->counts = a.dev<int32_t>(3); B->mainKey = a.dev<unsigned long long>(1);
+    B->specs = a.dev<W::SampleSpec>(W::NUM_SAMPLES); B->acc = a.dev<W::SampleAcc>(W::NUM_SAMPLES); B->splines = a.dev<W::Spline>(2);
+    B->selHist = a.dev<uint32_t>(W::SEL_BINS); B->selState = a.dev<W::SelState>(1); B->maxSpeed = a.dev<float>(1);
+    B->h_acc = a.pinned<W::SampleAcc>(W::NUM_SAMPLES);
+    B->h_count = a.pinned<int32_t>(16);
     std::vector<W::SampleSpec> specs(W::NUM_SAMPLES);
     W::make_sample_specs(specs.data());
     WO_HIP(hipMemcpy(B->specs, specs.data(), sizeof(W::SampleSpec) * W::NUM_SAMPLES, hipMemcpyHostToDevice));
+    p->wind = block.release();
 }
 
-void wind_free(wo_planet* p) {
-    auto* B = p->wind;
-    if (!B) return;
-    for (auto& s : B->season) for (auto& a : s) wfree(a);
-    wfree(B->lat); wfree(B->lon); wfree(B->sinLat); wfree(B->cosLat); wfree(B->isLand); wfree(B->cont); wfree(B->plateCont); wfree(B->coastDist);
-    for (auto& f : B->frame) wfree(f);
-    wfree(B->e); wfree(B->tmpA); wfree(B->tmpB); wfree(B->gradE); wfree(B->gradN);
-    wfree(B->label); wfree(B->compSize); wfree(B->plateDist); wfree(B->plate); wfree(B->oceanIds); wfree(B->plateOcean);
-    for (int i = 0; i < 2; ++i) { wfree(B->keys[i]); wfree(B->vals[i]); wfree(B->frontier[i]); }
-    wfree(B->sortScratch); wfree(B->binOffset); wfree(B->counts); wfree(B->mainKey); wfree(B->specs); wfree(B->acc); wfree(B->splines);
-    wfree(B->selHist); wfree(B->selState); wfree(B->maxSpeed);
-    if (B->h_acc) (void)hipHostFree(B->h_acc);
-    if (B->h_count) (void)hipHostFree(B->h_count);
-    delete B;
-    p->wind = nullptr;
-}
+void wind_free(wo_planet* p) { delete p->wind; p->wind = nullptr; }
 
 // one distance field; returns the number of levels after the seeds
 static int32_t wind_bfs(wo_planet* p, int32_t mode, const uint8_t* mask, uint8_t want, int32_t* dist) {
@@ -337,10 +318,6 @@ static void wind_run(wo_planet* p, double seed) {
 
 using namespace wo;
 
-#define WO_WIND_CATCH(fn)                                                               \
-    catch (const HipError& e) { set_error(std::string(fn) + ": " + e.msg); return 2; }   \
-    catch (const std::exception& e) { set_error(std::string(fn) + ": " + e.what()); return 3; }
-
 // the downloadable fields: the reference's result keys in the order it sets them (js/wind.js:649-683; wind_block.h: WindField)
 static const char* const kWindFields[WF_COUNT] = {
     "r_pressure_summer", "r_wind_east_summer", "r_wind_north_summer", "r_wind_speed_summer",
@@ -361,7 +338,7 @@ int wo_compute_wind(wo_planet* p, int32_t numRegions, const float* r_elevation, 
     if (!r_plate) { set_error("wo_compute_wind: null r_plate"); return 1; }
     if (nOceanPlates < 0 || (nOceanPlates > 0 && !oceanPlates)) { set_error("wo_compute_wind: ocean plate list of negative length, or null with a positive length"); return 1; }
     if (!(axialTilt == axialTilt)) { set_error("wo_compute_wind: axialTilt is NaN"); return 1; }   // the reference converts it and never reads it again (js/wind.js:397)
-    try {
+    WO_TRY
         wind_alloc(p);
         auto* B = p->wind;
         B->valid = false; B->have = 0;
@@ -370,7 +347,7 @@ int wo_compute_wind(wo_planet* p, int32_t numRegions, const float* r_elevation, 
         std::vector<int32_t> ids(oceanPlates, oceanPlates + nOceanPlates);
         std::sort(ids.begin(), ids.end());
         ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-        if ((int64_t)ids.size() > B->oceanIdCap || !B->oceanIds) { wfree(B->oceanIds); B->oceanIdCap = 0; walloc(B->oceanIds, ids.size()); B->oceanIdCap = (int64_t)ids.size(); }
+        if ((int64_t)ids.size() > B->oceanIdCap || !B->oceanIds) { B->mem.release(B->oceanIds); B->oceanIdCap = 0; B->oceanIds = B->mem.dev<int32_t>(ids.size()); B->oceanIdCap = (int64_t)ids.size(); }
         B->nOceanIds = (int32_t)ids.size();
         if (!ids.empty()) WO_HIP(hipMemcpyAsync(B->oceanIds, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s));
         WO_HIP(hipMemcpyAsync(B->plate, r_plate, N * 4, hipMemcpyHostToDevice, s));
@@ -381,7 +358,7 @@ int wo_compute_wind(wo_planet* p, int32_t numRegions, const float* r_elevation, 
         wind_run(p, seed);
         if (bfsLevels2) { bfsLevels2[0] = B->bfsLevels[0]; bfsLevels2[1] = B->bfsLevels[1]; }
         return 0;
-    } WO_WIND_CATCH("wo_compute_wind")
+    WO_CATCH("wo_compute_wind")
 }
 
 // where field f lives and how large it is (the ITCZ arrays are host arrays of the block)
@@ -406,7 +383,7 @@ int wo_wind_download(wo_planet* p, const char* field, void* out, int64_t outByte
     const int f = wind_field_index(field);
     if (f < 0) { set_error(std::string("wo_wind_download: unknown field '") + field + "'"); return 1; }
     if (!B->valid && !((B->have >> f) & 1u)) { set_error(std::string("wo_wind_download: no wind result on this planet: ") + field + " was never set (call wo_compute_wind first)"); return 1; }
-    try {
+    WO_TRY
         size_t bytes = 0;
         const void* src = wind_field_ptr(B, f, (size_t)p->N, &bytes);
         if (outBytes < (int64_t)bytes) { set_error(std::string("wo_wind_download: ") + field + " needs " + std::to_string(bytes) + " bytes, out has " + std::to_string(outBytes)); return 1; }
@@ -414,7 +391,7 @@ int wo_wind_download(wo_planet* p, const char* field, void* out, int64_t outByte
         WO_HIP(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, p->ctx->stream));
         WO_HIP(hipStreamSynchronize(p->ctx->stream));
         return 0;
-    } WO_WIND_CATCH("wo_wind_download")
+    WO_CATCH("wo_wind_download")
 }
 
 int wo_wind_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) {
@@ -422,7 +399,7 @@ int wo_wind_upload(wo_planet* p, const char* field, const void* data, int64_t by
     if (!field || !data) { set_error("wo_wind_upload: null pointer"); return 1; }
     const int f = wind_field_index(field);
     if (f < 0) { set_error(std::string("wo_wind_upload: unknown field '") + field + "'"); return 1; }
-    try {
+    WO_TRY
         wind_alloc(p);
         auto* B = p->wind;
         size_t want = 0;
@@ -435,18 +412,18 @@ int wo_wind_upload(wo_planet* p, const char* field, const void* data, int64_t by
         }
         B->have |= 1u << f;
         return 0;
-    } WO_WIND_CATCH("wo_wind_upload")
+    WO_CATCH("wo_wind_upload")
 }
 
 int wo_compute_gradients(wo_planet* p, int32_t numRegions, const float* r_pressure, const float* east3, const float* north3, float* r_gradE, float* r_gradN) {
     if (!check_planet(p, "wo_compute_gradients")) return 1;
     if (numRegions != p->N) { set_error("wo_compute_gradients: numRegions is " + std::to_string(numRegions) + ", the planet has " + std::to_string(p->N)); return 1; }
     if (!r_pressure || !east3 || !north3 || !r_gradE || !r_gradN) { set_error("wo_compute_gradients: null pointer"); return 1; }
-    float* d = nullptr;
-    try {
+    WO_TRY
         const size_t N = (size_t)p->N;
         hipStream_t s = p->ctx->stream;
-        walloc(d, 9 * N);                                     // pressure, east x/y/z, north x/y/z, gradE, gradN
+        DeviceArena B;
+        float* d = B.dev<float>(9 * N);                       // pressure, east x/y/z, north x/y/z, gradE, gradN
         WO_HIP(hipMemcpyAsync(d, r_pressure, N * 4, hipMemcpyHostToDevice, s));
         WO_HIP(hipMemcpyAsync(d + N, east3, 3 * N * 4, hipMemcpyHostToDevice, s));
         WO_HIP(hipMemcpyAsync(d + 4 * N, north3, 3 * N * 4, hipMemcpyHostToDevice, s));
@@ -456,10 +433,8 @@ int wo_compute_gradients(wo_planet* p, int32_t numRegions, const float* r_pressu
         WO_HIP(hipMemcpyAsync(r_gradE, d + 7 * N, N * 4, hipMemcpyDeviceToHost, s));
         WO_HIP(hipMemcpyAsync(r_gradN, d + 8 * N, N * 4, hipMemcpyDeviceToHost, s));
         WO_HIP(hipStreamSynchronize(s));
-        wfree(d);
         return 0;
-    } catch (const HipError& e) { wfree(d); set_error(std::string("wo_compute_gradients: ") + e.msg); return 2; }
-      catch (const std::exception& e) { wfree(d); set_error(std::string("wo_compute_gradients: ") + e.what()); return 3; }
+    WO_CATCH("wo_compute_gradients")
 }
 
 }  // extern "C"

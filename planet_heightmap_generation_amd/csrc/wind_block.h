@@ -10,6 +10,7 @@
 #include "wind_ops.h"
 
 struct wo_wind_block {
+    wo::DeviceArena mem;                                      // owns every device and pinned buffer of the block
     bool valid = false;                                       // a whole result of wo_compute_wind
     uint32_t have = 0;                                        // bit f: field f (WindField) was set, by wo_compute_wind or by wo_wind_upload
     // results (device): the eight season arrays, then the per-cell geography
@@ -43,9 +44,6 @@ constexpr uint32_t WF_ALL = (1u << WF_COUNT) - 1u;
 
 // wind.hip: allocates the planet's wind block if there is none
 void wind_alloc(wo_planet* p);
-
-template <class T> inline void walloc(T*& q, size_t n) { WO_HIP(hipMalloc((void**)&q, std::max<size_t>(n, 1) * sizeof(T))); }
-template <class T> inline void wfree(T*& q) { if (q) { (void)hipFree(q); q = nullptr; } }
 
 // append the flagged lanes' values with one atomic per wave; every lane of the wave calls it together
 __device__ inline void wind_append(bool flag, int32_t value, int32_t* list, int32_t* counter) {

@@ -48,6 +48,20 @@ def test_product_does_not_reference_the_oracle():
         assert "pyoracle" not in txt and "liboracle" not in txt and "wo_or_" not in txt, f
 
 
+def test_device_memory_has_one_owner():
+    """Only csrc/device_mem.h (DeviceArena) calls the HIP allocator; the hand-written allocate / free helpers are gone."""
+    csrc = REPO / "planet_heightmap_generation_amd" / "csrc"
+    call = re.compile(r"hip(Host)?(Malloc|Free)\s*\(")
+    gone = re.compile(r"\b(dalloc|dfree|walloc|wfree|DevBufs)\b")
+    files = sorted(list(csrc.glob("*.hip")) + list(csrc.glob("*.h")) + list(csrc.glob("*.cc")))
+    assert (csrc / "device_mem.h") in files and call.search((csrc / "device_mem.h").read_text())
+    for f in files:
+        txt = f.read_text(errors="ignore")
+        if f.name != "device_mem.h":
+            assert not call.search(txt), f"{f.name} calls the HIP allocator itself: {call.search(txt).group(0)}"
+        assert not gone.search(txt), f"{f.name} still has {gone.search(txt).group(0)}"
+
+
 def test_host_entry_points_reject_bad_arguments():
     """Status 1 + a message instead of a crash: null pointers, sizes that cannot be right, malformed meshes."""
     import numpy as np
