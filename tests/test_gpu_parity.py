@@ -1,19 +1,20 @@
 """HIP path (through the C ABI) against the reference's golden vectors and against the CPU oracle.
 
 Bars: integer / index work and every pass whose arithmetic is +,-,*,/,sqrt in double is BIT-EXACT.  The
-glacial passes call pow()/asin() on the device (ocml) where the reference calls V8's; a last-ulp double
-difference can flip one float32 rounding, so those cases assert RMS < 1e-5 (north_star's bound) and report
-how many cells are not bit-identical (expected: 0 on these fixtures).
+glacial passes call pow()/asin() on the device (ocml) where the reference calls V8's, and so does the solve with
+m != 0.5; a last-ulp double difference can flip one float32 rounding, so those cases are held per cell
+(erode_common.check_cells): every cell within ERODE_ULP_BOUND * max(1, |ref|), at most max(8, N / 10^4) cells
+different at all, and RMS < 1e-5 (north_star's bound) on top.  tests/test_erode_libm.py derives the bound; the
+figures are printed before they are asserted (expected: 0 cells differ on these fixtures).
 """
 import numpy as np
 import pytest
 
 from conftest import POST_TAGS, golden_cases, load_golden
+from erode_common import check_cells
 from hooks import del_hook, set_hook
 
 pytestmark = pytest.mark.gpu
-
-RMS_TOL = 1e-5      # BASELINE.json: "elevation RMS error vs reference < 1e-5"
 
 
 @pytest.fixture(scope="module")
@@ -81,7 +82,7 @@ def test_golden_cases(TP, tag):
         report.append((name, nbad, rms(got, ref)))
         uses_libm = case["fn"] == "erodeComposite" and (case["args"]["gIters"] > 0 or case["args"]["m"] != 0.5)
         if uses_libm:
-            assert rms(got, ref) < RMS_TOL, (tag, name, nbad, rms(got, ref))
+            check_cells(f"{tag} {name}", got, ref, ref.size)
         else:
             assert nbad == 0, (tag, name, nbad, float(np.abs(got - ref).max()))
     print("\n".join(f"{tag} {n:24s} non-identical cells {b:5d}  rms {r:.2e}" for n, b, r in report))
@@ -103,7 +104,7 @@ def test_against_oracle_large(TP, oracle, N, seed, h, t, g):
     pl.erode_composite(got, oc, h, 3e-4, 0.5, 1.0, t, 1.16, 0.015, g, 0.5)
     nbad = int((got != ref).sum())
     print(f"N={N}: non-identical cells {nbad}, rms {rms(got, ref):.2e}, stats {pl.last_erode_stats()}")
-    assert rms(got, ref) < RMS_TOL
+    check_cells(f"N={N} ({h}, {t}, {g})", got, ref, ref.size)
     # hydraulic + thermal only: no libm on the path -> bit-exact
     ref2 = oracle.erode_composite(om, e0, xyz, oc, h, 3e-4, 0.5, 1.0, t, 1.16, 0.015, 0, 0.0, nd)
     got2 = e0.copy()
@@ -143,9 +144,9 @@ def test_pipeline_matches_oracle_composition(TP, oracle):
     r = oracle.sharpen_ridges(om, r, roc, 3, 0.5 * 0.08)
     r = oracle.soil_creep(om, r, roc, 3, 0.1125)
     assert np.array_equal(oc, roc)
-    assert rms(e, r) < RMS_TOL
+    check_cells("pipeline, UI defaults", e, r, r.size)
     assert np.array_equal(delta, (e.astype(np.float64) - pre.astype(np.float64)).astype(np.float32))      # dl_erosionDelta = final - preErosion of the SAME run
-    assert rms(delta, (r.astype(np.float64) - pre.astype(np.float64)).astype(np.float32)) < RMS_TOL
+    check_cells("pipeline, UI defaults, delta", delta, (r.astype(np.float64) - pre.astype(np.float64)).astype(np.float32), r.size)
     pl.close()
 
 
@@ -162,7 +163,10 @@ def test_edge_cases(TP, oracle):
             a = e0.copy()
             pl.erode_composite(a, oc, h, 3e-4, 0.5, 1.0, t, 1.16, 0.015, g_, 0.7)
             b = oracle.erode_composite(om, e0, xyz, oc, h, 3e-4, 0.5, 1.0, t, 1.16, 0.015, g_, 0.7, nd)
-            assert rms(a, b) < RMS_TOL and (g_ > 0 or np.array_equal(a, b)), (oc.sum(), h, t, g_)
+            if g_ > 0:
+                check_cells(f"30 cells, {int(oc.sum())} ocean, ({h}, {t}, {g_})", a, b, V)
+            else:
+                assert np.array_equal(a, b), (oc.sum(), h, t, g_)
     # flats and exact ties: quantised heights exercise the stable-sort / least-ascent / late-edge rules
     eq = (np.round(e0 * 4) / 4).astype(np.float32)
     oc = (eq <= 0).astype(np.uint8)
@@ -266,7 +270,7 @@ def test_headline_size_properties(TP):
 def test_headline_size_against_oracle(TP, oracle):
     """BASELINE config 3 size (10 M cells) head to head with the CPU oracle on a bounded number of iterations (the
     oracle needs ~7 s per composite iteration here): warp + erodeComposite(3, 3, 1) + creep, bit for bit where no
-    libm call is involved, RMS < 1e-5 (north_star's bound) for the glacial pass."""
+    libm call is involved, the per-cell bar of erode_common.check_cells for the glacial pass."""
     from planet_heightmap_generation_amd import sphere_mesh as S
     mesh, xyz, nd = S.build_sphere(10_000_000, 0.75, 1)
     om = oracle.Mesh(mesh.adjOffset, mesh.adjList)
@@ -288,7 +292,7 @@ def test_headline_size_against_oracle(TP, oracle):
     pl.erode_composite(got3, oc, 2, 3e-4, 0.5, 1.0, 2, 1.16, 0.015, 1, 0.5)
     nbad = int((got3 != ref3).sum())
     print(f"10M cells, glacial pass: non-identical cells {nbad}, rms {rms(got3, ref3):.2e}")
-    assert rms(got3, ref3) < RMS_TOL
+    check_cells("10M cells, glacial pass", got3, ref3, ref3.size)
     ref4 = oracle.soil_creep(om, ref2, oc, 3, 0.1125)
     pl.apply_soil_creep(got2, oc, 3, 0.1125)
     assert np.array_equal(got2, ref4)
@@ -900,7 +904,8 @@ def test_relaxed_mode_runs_and_is_not_the_parity_path(TP, oracle, monkeypatch):
     args = (12, 3e-4, 0.5, 1.0, 12, 1.16, 0.015, 3, 0.5)
     ref = oracle.erode_composite(om, e0, xyz, oc, *args, nd)
     exact = e0.copy(); pl.erode_composite(exact, oc, *args)
-    assert pl.last_erode_stats()["relaxed_full"] == 0.0 and rms(exact, ref) < RMS_TOL
+    assert pl.last_erode_stats()["relaxed_full"] == 0.0
+    check_cells("exact path beside the relaxed mode", exact, ref, ref.size)
     monkeypatch.setenv("WO_RELAXED", "full")
     relaxed = e0.copy(); pl.erode_composite(relaxed, oc, *args)
     st = pl.last_erode_stats()
@@ -946,7 +951,7 @@ def test_sorts_at_tile_and_group_boundaries(TP, oracle, cells, counts):
     the radix sort (4 096: csrc/radix.hip), exactly one group of 32 radix tiles (131 072), and one pair more than each; the
     field is quantised to 1/64, so runs of equal keys cross the tile seams.  All counts of a mesh run on one planet, up, down and
     up again, which also crosses the rule that a sort starts on the group totals its predecessor cleared.  Bit for bit the C
-    oracle without the glacial passes; with them (L = 4 097) on the RMS bar of this file.  At 200 k cells the 131 072 highest
+    oracle without the glacial passes; with them (L = 4 097) on the per-cell bar of this file.  At 200 k cells the 131 072 highest
     cells reach below sea level (56 181 lie above it): the mask is not `elevation <= 0` there, and the flood's clamp at 0 lifts
     heights; this case found the chain form of the flood's pass 2 wrong on such land (46 014 cells off the oracle, fixed in
     flood_host.cc: tree_pass2_chains; without a GPU: test_emulated_kernels.py)."""
@@ -979,7 +984,7 @@ def test_sorts_at_tile_and_group_boundaries(TP, oracle, cells, counts):
             got = eq.copy()
             pl.erode_composite(got, oc, *glacial)
             print(f"{eq.size} cells, L = 4097, two glacial passes: rms {rms(got, ref):.3e}, cells that differ {int((got != ref).sum())}")
-            assert rms(got, ref) < RMS_TOL
+            check_cells(f"{eq.size} cells, L = 4097, two glacial passes", got, ref, eq.size)
     finally:
         pl.close()
 
