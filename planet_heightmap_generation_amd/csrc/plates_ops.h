@@ -1,5 +1,18 @@
 // Plate projection bodies (WO_HD: device kernels and the test-only CPU emulator drive the same code).
 // Reference: js/coarse-plates.js:51-117 projectCoarsePlates.
+//
+// The reference walks serially, warm-started from the previous cell's region, gives up after ceil(sqrt(NC)) steps and scans
+// all regions; here every cell starts from a (z, longitude) bucket grid and walks at most NC steps.  Both end on the nearest
+// coarse region because on the reference's closed Delaunay mesh the ascent has one local maximum (see plate_nearest_coarse).
+// What checks that, with every coarse region its own plate: tests/test_plates.py (oracle against the host build of these
+// bodies) and tests/test_gpu_plates.py (device against both), at the closing pole's fan, the grid's longitude seam, z = +-1 and
+// coarse meshes of 21 to 80 001 regions; DESIGN section 3.2 has the counts.
+//
+// Out of contract, not tested:
+//  - NaN or zero-length cell positions.  The lookup point becomes NaN; the reference then keeps the previous cell's region, the
+//    device returns its bucket's start cell (the int32 conversion of NaN in plate_grid_bucket is undefined on the host).
+//  - Coarse graphs other than the reference's closed Delaunay mesh (hubs, shuffled rows): they have several local maxima, and
+//    the reference's own answer then depends on the order of the cells.
 #pragma once
 #include <cstdint>
 #include <cmath>

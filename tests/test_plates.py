@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import plates_common as PC
 from plates_common import PLATE_CASES, plate_case
 
 
@@ -48,18 +49,43 @@ def test_host_smooth_edge_cases(oracle):
 @pytest.mark.parametrize("name", PLATE_CASES[:2])
 def test_emulated_projection_matches_reference(name):
     """The projection kernel body (csrc/plates_ops.h), driven cell by cell on the CPU."""
-    import subprocess
-    from pathlib import Path
-    d = Path(__file__).resolve().parent / "emu"
-    subprocess.run(["make", "-s", "-C", str(d)], check=True)
-    L = C.CDLL(str(d / "_build" / "libemu.so"))
     c = plate_case(name)
-    N = c["mesh"].numRegions
-    out = np.empty(N, np.int32)
-    L.emu_project_plates.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]
-    L.emu_project_plates(N, P(c["xyz"]), c["cmesh"].numRegions, P(c["cmesh"].adjOffset), P(c["cmesh"].adjList), P(c["cxyz"]),
-                         P(np.ascontiguousarray(c["coarse_r_plate"])), float(c["meta"]["seed"]), int(c["meta"]["P"]), P(out))
+    out = PC.emu_project_plates(c["xyz"], c["cmesh"], c["cxyz"], c["coarse_r_plate"], c["meta"]["seed"], c["meta"]["P"])
     assert np.array_equal(out, c["projected"]), int((out != c["projected"]).sum())
+
+
+# ---- the start cell does not matter: oracle (warm start, sqrt(NC) cap, brute-force fallback) against the emulator (bucket
+# grid start, NC cap) with identity plates, where every wrong walk shows.  Exact equality.
+@pytest.mark.parametrize("num_plates", (None, 0, 50, 200))
+@pytest.mark.parametrize("seed", PC.FRESH_SEEDS)
+def test_identity_walk_is_start_independent_seeds(seed, num_plates):
+    """Coarse meshes no golden uses; Fibonacci cells in index order, a 4 degree cap on the closing pole's fan (+z), a -z cap, the
+    start grid's longitude seam.  perturbAmp is 2.5 coarse cells at numPlates 0, 2.0 at 50 and 1.5 at 200 and None."""
+    ref, emu = PC.walk_answers(20000, seed, num_plates)
+    _, where = PC.query_points(seed)
+    assert ref.size == sum(n for _, n in PC.QUERY_SIZES) and max(n for _, n in PC.QUERY_SIZES) <= 50000
+    assert not PC.mismatch(emu, ref, where), PC.mismatch(emu, ref, where)
+
+
+@pytest.mark.parametrize("n, seed, num_plates", ((20, 2, None), (200, 2, 12), (2000, 4, None), (80000, 6, 12)))
+def test_identity_walk_is_start_independent_sizes(n, seed, num_plates):
+    """20 requested cells: 8192 start buckets over 21 regions; 80000: the reference gives up its walk after 283 steps."""
+    ref, emu = PC.walk_answers(n, seed, num_plates)
+    _, where = PC.query_points(seed)
+    assert not PC.mismatch(emu, ref, where), PC.mismatch(emu, ref, where)
+    assert np.unique(ref).size > (n + 1) * (0.9 if n <= 2000 else 0.05), "the query sets reach too few coarse regions to say anything"
+
+
+@pytest.mark.parametrize("num_plates", (None, 0, 50, 200))
+@pytest.mark.parametrize("seed", PC.FRESH_SEEDS)
+def test_pole_cap_reaches_the_pole_vertex(seed, num_plates):
+    """The +z cap is there for the fan of the closing pole vertex, region NC - 1: some of its cells must end on it, in the
+    reference's answer and in the emulator's, or the cap tests nothing."""
+    ref, emu = PC.walk_answers(20000, seed, num_plates)
+    cap = PC.query_points(seed)[1]["cap+z"]
+    NC = PC.coarse_mesh(20000, seed)[0].numRegions
+    print(f"seed {seed}, numPlates {num_plates}: cells of the +z cap on the pole vertex {int((ref[cap] == NC - 1).sum())}, on its fan's regions in all {np.unique(ref[cap]).size}")
+    assert (ref[cap] == NC - 1).any() and (emu[cap] == NC - 1).any()
 
 
 @pytest.mark.gpu
