@@ -333,6 +333,36 @@ typedef struct wo_ocean_info {
 } wo_ocean_info;
 int wo_compute_ocean_currents(wo_planet* p, int32_t numRegions, wo_ocean_info* info);
 int wo_ocean_download(wo_planet* p, const char* field, void* out, int64_t outBytes);
+/* wo_ocean_upload sets one field of the planet's ocean block from the host by its result key (the eight keys of
+ *   wo_ocean_download; `bytes` must be numRegions floats exactly); it allocates the block if there is none.  It serves a caller
+ *   that brings its own oceanResult to a later stage.  A block filled only by uploads is no ocean result: wo_ocean_download of
+ *   a field that was never set still fails. */
+int wo_ocean_upload(wo_planet* p, const char* field, const void* data, int64_t bytes);
+
+/* ------------------------------------------------ precipitation (js/precipitation.js) ---------- */
+/* computePrecipitation(mesh, r_xyz, r_elevation, windResult, oceanResult, precipitationOffset, landCoverage)
+ *                                                                    js/precipitation.js:196-684, js/heuristic-precip.js
+ *   on the planet's resident mesh (csrc/precip.hip; the per-cell bodies and their exactness contract are in csrc/precip_ops.h).
+ *   windResult is the planet's wind block (wo_compute_wind, or wo_wind_upload of at least r_lat r_lon r_isLand r_continentality
+ *   r_coastDistLand, the six frame arrays, the three ITCZ arrays and per season r_wind_east_* r_wind_north_* r_pressure_*);
+ *   oceanResult is the planet's ocean block (wo_compute_ocean_currents, or wo_ocean_upload of r_ocean_warmth_summer and
+ *   r_ocean_warmth_winter).  Without them the call fails with "no wind result" / "no ocean result".  r_elevation: numRegions
+ *   floats, NULL means the planet's resident field.  numRegions must equal the planet's.  All four outputs are the reference's
+ *   bit for bit wherever the host libm's pow gives V8's three scalars (csrc/precip_ops.h lists the hop counts where it does not).
+ *   The results stay on the device in a precipitation block the planet owns (a later call replaces them); wo_precip_download
+ *   copies one field (numRegions floats) to the host by the reference's result key:
+ *     r_precip_summer r_precip_winter r_rainshadow_summer r_rainshadow_winter
+ *   info (may be NULL) receives the scalars of the call.  No CPU fallback. */
+typedef struct wo_precip_info {
+    int32_t maxHops, elevSmoothPasses, convSmoothPasses, shadowHops, windwardHops, rsSmoothPasses, precipSmoothPasses, wcPasses, leeCoastHops;
+    int32_t listLengths[4];                            /* wind-aligned neighbours: upwind, downwind summer; upwind, downwind winter */
+    int32_t reserved;
+    double depletionBase, shadowDecay, windwardDecay;  /* 1 - pow(0.78, 1/maxHops), 1 - pow(0.15, 1/shadowHops), 1 - pow(0.25, 1/windwardHops) */
+    float p95[2];                                      /* maxPrecip: the 95th percentile of the blended field, summer / winter */
+} wo_precip_info;
+int wo_compute_precipitation(wo_planet* p, int32_t numRegions, const float* r_elevation, double precipitationOffset, double landCoverage,
+                             wo_precip_info* info);
+int wo_precip_download(wo_planet* p, const char* field, void* out, int64_t outBytes);
 
 /* ------------------------------------------------ device-resident variants -------------------- */
 /* The "reapply" pattern (js/planet-worker.js:341-440): fields stay in HBM, only scalars arrive.

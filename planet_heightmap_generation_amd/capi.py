@@ -69,6 +69,9 @@ SIGNATURES = {
     "wo_wind_upload": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
     "wo_compute_ocean_currents": (C.c_int, [_p, _c_i32, _p]),
     "wo_ocean_download": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
+    "wo_ocean_upload": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
+    "wo_compute_precipitation": (C.c_int, [_p, _c_i32, _p, _c_f64, _c_f64, _p]),
+    "wo_precip_download": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
     "wo_planet_upload": (C.c_int, [_p, _p, _p]),
     "wo_planet_download": (C.c_int, [_p, _p]),
     "wo_planet_set_halo": (C.c_int, [_p, _p, _c_i32, _p, _c_i32]),

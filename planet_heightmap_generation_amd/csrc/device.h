@@ -193,6 +193,9 @@ struct wo_planet {
     // ocean surface currents (ocean.hip): the ocean block — results and scratch of wo_compute_ocean_currents, allocated on its
     // first call; deleted by wo_planet_destroy (ocean_free)
     struct wo_ocean_block* ocean = nullptr;
+    // precipitation (precip.hip): the precipitation block — the four results of wo_compute_precipitation, allocated on its first
+    // call; deleted by wo_planet_destroy (precip_free)
+    struct wo_precip_block* precip = nullptr;
 
     // Patch-major mirror of the mesh for erodeComposite (planet.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
@@ -282,9 +285,15 @@ void basin_solve_launch(wo_planet* p, const Fields& F, int32_t launchTag, int32_
 // wind.hip, ocean.hip: drop the wind block / the ocean block (and with it its memory)
 void wind_free(wo_planet* p);
 void ocean_free(wo_planet* p);
+void precip_free(wo_planet* p);
 // planet.hip: the entry points' handle check (refreshes p->opt from the environment, selects the device)
 bool check_planet(wo_planet* p, const char* fn);
 // planet.hip: smoothField on a resident field (returns the buffer that holds the result)
 float* smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passes);
+// planet.hip: computeWindConvergence and advectMoisture on resident fields (the advection seeds a, ping-pongs a and b and returns
+// the buffer that holds the result)
+void wind_convergence_resident(wo_planet* p, const float* wx, const float* wy, const float* wz, float* out);
+float* advect_moisture_resident(wo_planet* p, const float* heightKm, const uint8_t* isLand, const float* windE, const float* windN, const float* wx, const float* wy,
+                                const float* wz, const float* warmth, const int32_t* coastDist, int32_t maxHops, double depletionBase, float* a, float* b);
 
 }  // namespace wo

@@ -12,7 +12,7 @@
 //                                         every workgroup folds the bin flags into the two circumpolar flags
 //                   k_ocean_smooth<4>     the masked smooth of all four arrays in one gather per pass
 //                   k_ocean_speed         de-interleaves the currents, the raw speeds, the count of ocean speeds > 0
-//   percentile      k_ocean_sel_hist / _pick x 3   both seasons per launch, over the cells with isOcean && speed > 0; the rank
+//   percentile      k_ocean_sel_hist / _pick x 3   (ocean_block.h, shared with precip.hip) both seasons per launch, over the cells with isOcean && speed > 0; the rank
 //                                         comes from the device's count, a whole wave scans the counters
 //   warmth          k_ocean_warmth, k_ocean_smooth<2>   classifyWarmth of both seasons as one float2 per cell
 //   finish          k_ocean_finish        normalised speeds, de-interleaved warmth
@@ -27,46 +27,11 @@
 
 #include "../../include/worogen.h"
 #include "device.h"
+#include "ocean_block.h"
 #include "ocean_ops.h"
 #include "wind_block.h"
 
-namespace O = wo::ocean;
-namespace W = wo::wind;
-
 namespace wo {
-// what the kernels of a call share; cleared at its start.  The head (up to p95) comes back to the host at its end.
-struct OceanCtl {
-    int32_t counts[3];                                        // rotating frontier lengths
-    uint32_t oceanCells[2];                                   // ocean speeds > 0 per season
-    uint32_t circ[2];                                         // circumpolarNH, circumpolarSH
-    float p95[2];
-    uint32_t bins[2 * O::CIRC_BINS];
-    W::SelState sel[2];
-    uint32_t hist[2][W::SEL_PASSES][W::SEL_BINS];             // season, pass: no pass clears another's counters
-};
-constexpr size_t OCEAN_CTL_HEAD = offsetof(OceanCtl, bins);
-}  // namespace wo
-
-// the ocean block of a planet
-struct wo_ocean_block {
-    wo::DeviceArena mem;                                      // owns every device and pinned buffer of the block
-    bool valid = false;
-    float* out[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // per season: east, north, speed, warmth
-    uint8_t* isOcean = nullptr;
-    void* group[2] = {nullptr, nullptr};                      // 16 bytes per cell each: frontiers (2 N entries), float4 currents, float2 warmths
-    float* itcz = nullptr;                                    // 2 x 360: itczLatsSummer, itczLatsWinter
-    wo::OceanCtl* ctl = nullptr;
-    wo::OceanCtl* h_ctl = nullptr;                            // pinned: the head of ctl
-    wo_ocean_info info{};
-};
-
-namespace wo {
-
-// the cell of a thread under the XCD-aware tiling of the index-order passes (kernels_impl.h: WO_XCD_CELLS); grid: xcd_grid(N)
-__device__ inline int32_t ocean_xcd_cell(int32_t tile) {
-    const int32_t xi = (int32_t)(blockIdx.x >> 3);
-    return (((xi / tile) * 8 + (int32_t)(blockIdx.x & 7u)) * tile + (xi % tile)) * (int32_t)blockDim.x + (int32_t)threadIdx.x;
-}
 
 __global__ __launch_bounds__(WO_BLOCK) void k_ocean_mask(const uint8_t* __restrict__ isLand, const float* __restrict__ lat, const float* __restrict__ lon,
                                                          uint8_t* __restrict__ isOcean, uint32_t* __restrict__ bins, int32_t N) {
@@ -194,51 +159,6 @@ __global__ __launch_bounds__(WO_BLOCK) void k_ocean_speed(const O::Group<4>* __r
     }
 }
 
-// histogram of one digit over the ocean speeds > 0 that agree with the digits already chosen; even workgroups take summer, odd ones winter
-__global__ __launch_bounds__(WO_BLOCK) void k_ocean_sel_hist(const float* __restrict__ spS, const float* __restrict__ spW, const uint8_t* __restrict__ isOcean, int32_t N,
-                                                             int32_t pass, OceanCtl* ctl) {
-    __shared__ uint32_t s[W::SEL_BINS];
-    const int season = blockIdx.x & 1;
-    const float* __restrict__ v = season ? spW : spS;
-    for (int i = threadIdx.x; i < W::SEL_BINS; i += blockDim.x) s[i] = 0;
-    __syncthreads();
-    const uint32_t prefix = ctl->sel[season].prefix;
-    for (int32_t r = (blockIdx.x >> 1) * blockDim.x + threadIdx.x; r < N; r += (gridDim.x >> 1) * blockDim.x) {
-        const float x = v[r];
-        if (!(isOcean[r] && x > 0.0f)) continue;
-        const uint32_t key = W::sel_key(x);
-        if (W::sel_matches(key, prefix, pass)) atomicAdd(&s[W::sel_digit(key, pass)], 1u);
-    }
-    __syncthreads();
-    uint32_t* hist = ctl->hist[season][pass];
-    for (int i = threadIdx.x; i < W::SEL_BINS; i += blockDim.x) if (s[i]) atomicAdd(&hist[i], s[i]);
-}
-// one wave per season chooses the digit (wind_ops.h: sel_pick, the counters scanned by the 64 lanes); pass 0 takes the rank
-// from the count, the last pass leaves the percentile
-__global__ __launch_bounds__(64) void k_ocean_sel_pick(OceanCtl* ctl, int32_t pass) {
-    const int season = blockIdx.x, lane = threadIdx.x;
-    const uint32_t* hist = ctl->hist[season][pass];
-    const uint32_t count = ctl->oceanCells[season];
-    W::SelState S = ctl->sel[season];
-    if (pass == 0) { S.prefix = 0u; S.k = O::percentile_rank(count); }
-    const int bins = pass == 2 ? 1024 : W::SEL_BINS, per = bins / 64, lo = lane * per;
-    uint32_t sum = 0;
-    for (int d = lo; d < lo + per; ++d) sum += hist[d];
-    uint32_t incl = sum;
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if (lane >= o) incl += up; }
-    const unsigned long long over = __ballot(incl > S.k);
-    const int owner = over ? __ffsll((long long)over) - 1 : 63;   // the lane whose counters hold the rank (none: the last digit, as sel_pick's loop ends)
-    if (lane == owner) {
-        uint32_t k = S.k - (incl - sum);
-        int d = lo;
-        for (; d < bins - 1; ++d) { if (k < hist[d]) break; k -= hist[d]; }
-        S.prefix |= (uint32_t)d << W::sel_shift(pass);
-        S.k = k;
-        ctl->sel[season] = S;
-        if (pass == W::SEL_PASSES - 1) ctl->p95[season] = O::p95_of(count, S.prefix);
-    }
-}
-
 __global__ __launch_bounds__(WO_BLOCK) void k_ocean_warmth(const float* __restrict__ lat, const uint8_t* __restrict__ isOcean, const int32_t* __restrict__ distW,
                                                            const int32_t* __restrict__ distE, int32_t warmthRange, O::Group<2>* __restrict__ out, int32_t N) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -266,7 +186,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_ocean_finish(float* __restrict__ s
 
 void ocean_free(wo_planet* p) { delete p->ocean; p->ocean = nullptr; }
 
-static void ocean_alloc(wo_planet* p) {
+void ocean_alloc(wo_planet* p) {
     if (p->ocean) return;
     std::unique_ptr<wo_ocean_block> block(new wo_ocean_block());        // the planet gets the block once it is complete
     wo_ocean_block* B = block.get(); DeviceArena& a = B->mem;
@@ -313,7 +233,7 @@ static void ocean_run(wo_planet* p) {
     auto* Wb = p->wind;
     const int32_t N = p->N, g = blocks_for(N);
     hipStream_t s = p->ctx->stream;
-    B->valid = false;
+    B->valid = false; B->have = 0;
     const O::Params P = O::params_for(N);
     int32_t *distW = Wb->vals[0], *distE = Wb->vals[1];
     OceanCtl* ctl = B->ctl;
@@ -336,8 +256,8 @@ static void ocean_run(wo_planet* p) {
     launch(p, FAM_CLIMATE, k_ocean_speed, g, WO_BLOCK, cur, (const uint8_t*)B->isOcean, B->out[0], B->out[1], B->out[2], B->out[4], B->out[5], B->out[6], ctl->oceanCells, N);
     // percentile of the ocean speeds, both seasons
     for (int pass = 0; pass < W::SEL_PASSES; ++pass) {
-        launch(p, FAM_CLIMATE, k_ocean_sel_hist, 2 * blocks_for(N, 1024), WO_BLOCK, (const float*)B->out[2], (const float*)B->out[6], (const uint8_t*)B->isOcean, N, pass, ctl);
-        launch(p, FAM_CLIMATE, k_ocean_sel_pick, 2, 64, ctl, pass);
+        launch(p, FAM_CLIMATE, k_ocean_sel_hist<OceanCtl>, 2 * blocks_for(N, 1024), WO_BLOCK, (const float*)B->out[2], (const float*)B->out[6], (const uint8_t*)B->isOcean, N, pass, ctl);
+        launch(p, FAM_CLIMATE, k_ocean_sel_pick<OceanCtl>, 2, 64, ctl, pass);
     }
     // warmth
     auto* w2a = (O::Group<2>*)B->group[0]; auto* w2b = (O::Group<2>*)B->group[1];
@@ -349,7 +269,7 @@ static void ocean_run(wo_planet* p) {
     const OceanCtl& H = *B->h_ctl;
     B->info = wo_ocean_info{(int32_t)H.circ[0], (int32_t)H.circ[1], P.coastThreshold, P.warmthRange, P.currentPasses, P.warmthPasses,
                             {(int32_t)H.oceanCells[0], (int32_t)H.oceanCells[1]}, {H.p95[0], H.p95[1]}};
-    B->valid = true;
+    B->valid = true; B->have = 0xffu;
 }
 
 }  // namespace wo
@@ -361,6 +281,11 @@ static const char* const kOceanFields[8] = {"r_ocean_current_east_summer", "r_oc
                                             "r_ocean_current_east_winter", "r_ocean_current_north_winter", "r_ocean_speed_winter", "r_ocean_warmth_winter"};
 // the fields of the wind block the stage reads
 static constexpr uint32_t kWindNeeded = (1u << WF_LAT) | (1u << WF_LON) | (1u << WF_ISLAND) | (7u << WF_FRAME0) | (7u << WF_ITCZ0);
+
+static int ocean_field_index(const char* name) {
+    for (int i = 0; i < 8; ++i) if (std::strcmp(name, kOceanFields[i]) == 0) return i;
+    return -1;
+}
 
 extern "C" {
 
@@ -385,10 +310,10 @@ int wo_ocean_download(wo_planet* p, const char* field, void* out, int64_t outByt
     if (!check_planet(p, "wo_ocean_download")) return 1;
     if (!field || !out) { set_error("wo_ocean_download: null pointer"); return 1; }
     auto* B = p->ocean;
-    if (!B || !B->valid) { set_error("wo_ocean_download: no ocean result on this planet (call wo_compute_ocean_currents first)"); return 1; }
-    int f = -1;
-    for (int i = 0; i < 8; ++i) if (std::strcmp(field, kOceanFields[i]) == 0) f = i;
+    if (!B || !(B->valid || B->have)) { set_error("wo_ocean_download: no ocean result on this planet (call wo_compute_ocean_currents first)"); return 1; }
+    const int f = ocean_field_index(field);
     if (f < 0) { set_error(std::string("wo_ocean_download: unknown field '") + field + "'"); return 1; }
+    if (!B->valid && !((B->have >> f) & 1u)) { set_error(std::string("wo_ocean_download: no ocean result on this planet: ") + field + " was never set (call wo_compute_ocean_currents first)"); return 1; }
     WO_TRY
         const size_t bytes = (size_t)p->N * 4;
         if (outBytes < (int64_t)bytes) { set_error(std::string("wo_ocean_download: ") + field + " needs " + std::to_string(bytes) + " bytes, out has " + std::to_string(outBytes)); return 1; }
@@ -396,6 +321,23 @@ int wo_ocean_download(wo_planet* p, const char* field, void* out, int64_t outByt
         WO_HIP(hipStreamSynchronize(p->ctx->stream));
         return 0;
     WO_CATCH("wo_ocean_download")
+}
+
+int wo_ocean_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) {
+    if (!check_planet(p, "wo_ocean_upload")) return 1;
+    if (!field || !data) { set_error("wo_ocean_upload: null pointer"); return 1; }
+    const int f = ocean_field_index(field);
+    if (f < 0) { set_error(std::string("wo_ocean_upload: unknown field '") + field + "'"); return 1; }
+    WO_TRY
+        const size_t want = (size_t)p->N * 4;
+        if (bytes != (int64_t)want) { set_error(std::string("wo_ocean_upload: ") + field + " takes " + std::to_string(want) + " bytes, data has " + std::to_string(bytes)); return 1; }
+        ocean_alloc(p);
+        auto* B = p->ocean;
+        WO_HIP(hipMemcpyAsync(B->out[f], data, want, hipMemcpyHostToDevice, p->ctx->stream));
+        WO_HIP(hipStreamSynchronize(p->ctx->stream));         // `data` is the caller's, and pageable
+        B->have |= 1u << f;
+        return 0;
+    WO_CATCH("wo_ocean_upload")
 }
 
 }  // extern "C"

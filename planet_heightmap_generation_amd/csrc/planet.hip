@@ -1118,6 +1118,22 @@ float* wo::smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passe
     return a;
 }
 
+// computeWindConvergence and advectMoisture (js/precipitation.js:19-52, :59-182) on device-resident fields (precip.hip); the
+// advection returns the buffer that holds the result
+void wo::wind_convergence_resident(wo_planet* p, const float* wx, const float* wy, const float* wz, float* out) {
+    launch(p, FAM_CLIMATE, k_wind_convergence, xcd_grid(p->N), WO_BLOCK, p->fields(), climate_mesh(p), wx, wy, wz, out);
+}
+float* wo::advect_moisture_resident(wo_planet* p, const float* heightKm, const uint8_t* isLand, const float* windE, const float* windN, const float* wx, const float* wy,
+                                    const float* wz, const float* warmth, const int32_t* coastDist, int32_t maxHops, double depletionBase, float* a, float* b) {
+    const Fields F = p->fields(); const ClimateMesh M = climate_mesh(p);
+    launch(p, FAM_CLIMATE, k_moisture_seed, xcd_grid(p->N), WO_BLOCK, F, M, isLand, wx, wy, wz, warmth, coastDist, a);
+    for (int32_t it = 0; it < maxHops; ++it) {
+        launch(p, FAM_CLIMATE, k_moisture_advect, xcd_grid(p->N), WO_BLOCK, F, M, (const float*)a, heightKm, isLand, windE, windN, wx, wy, wz, maxHops, depletionBase, b);
+        std::swap(a, b);
+    }
+    return a;
+}
+
 bool wo::check_planet(wo_planet* p, const char* fn) {
     if (!p) { set_error(std::string(fn) + ": null planet handle"); return false; }
     p->opt = Options::from_env();
@@ -1259,6 +1275,7 @@ void wo_planet_destroy(wo_planet* p) {
     if (p->evJoin) { (void)hipEventDestroy(p->evJoin); p->evJoin = nullptr; }
     if (p->floodLink && p->floodLinkFree) p->floodLinkFree(p->floodLink);
     p->floodLink = nullptr;
+    precip_free(p);
     ocean_free(p);
     wind_free(p);
     for (auto& pe : p->pending) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }

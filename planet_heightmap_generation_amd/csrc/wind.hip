@@ -230,6 +230,11 @@ void wind_alloc(wo_planet* p) {
 
 void wind_free(wo_planet* p) { delete p->wind; p->wind = nullptr; }
 
+// computeGradients on a device-resident field (precip.hip)
+void gradient_resident(wo_planet* p, const float* field, const W::Frames& T, float* gradE, float* gradN) {
+    launch(p, FAM_CLIMATE, k_wind_gradient, blocks_for(p->N), WO_BLOCK, (const int32_t*)p->d_off, (const int32_t*)p->d_adj, (const float*)p->d_xyz, field, T, gradE, gradN, p->N);
+}
+
 // one distance field; returns the number of levels after the seeds
 static int32_t wind_bfs(wo_planet* p, int32_t mode, const uint8_t* mask, uint8_t want, int32_t* dist) {
     auto* B = p->wind;

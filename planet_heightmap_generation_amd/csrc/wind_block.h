@@ -44,6 +44,8 @@ constexpr uint32_t WF_ALL = (1u << WF_COUNT) - 1u;
 
 // wind.hip: allocates the planet's wind block if there is none
 void wind_alloc(wo_planet* p);
+// wind.hip: computeGradients (js/wind.js:306-339) of a device-resident field
+void gradient_resident(wo_planet* p, const float* field, const wind::Frames& T, float* gradE, float* gradN);
 
 // append the flagged lanes' values with one atomic per wave; every lane of the wave calls it together
 __device__ inline void wind_append(bool flag, int32_t value, int32_t* list, int32_t* counter) {

@@ -526,6 +526,44 @@ napi_value OceanDownload(napi_env env, napi_callback_info info) {
     if (wo_ocean_download(p, key, d, (int64_t)(n * 4))) return throw_wo(env, "oceanDownload");
     return out;
 }
+// oceanUpload(planet, key, Float32Array): one field of the planet's ocean block by its result key (the C ABI checks key and size)
+napi_value OceanUpload(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    char key[64]; if (!key_at(a, 1, key)) return nullptr;
+    size_t n = 0; float* data = (float*)a.ta(2, napi_float32_array, &n); if (!a.ok) return nullptr;
+    if (wo_ocean_upload(p, key, data, (int64_t)(n * 4))) return throw_wo(env, "oceanUpload");
+    return nullptr;
+}
+// computePrecipitation(planet, r_elevation | null, precipitationOffset, landCoverage) -> the scalars of the call: the stage on the planet's
+// wind and ocean blocks; the results stay on the device (precipDownload)
+napi_value ComputePrecipitation(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* e = (float*)opt_regions(a, 1, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    wo_precip_info pi;
+    if (wo_compute_precipitation(p, wo_planet_num_regions(p), e, a.num(2), a.num(3), &pi)) return throw_wo(env, "computePrecipitation");
+    napi_value o, v; napi_create_object(env, &o);
+    const struct { const char* k; double x; } nums[] = {{"maxHops", (double)pi.maxHops}, {"elevSmoothPasses", (double)pi.elevSmoothPasses},
+        {"convSmoothPasses", (double)pi.convSmoothPasses}, {"shadowHops", (double)pi.shadowHops}, {"windwardHops", (double)pi.windwardHops},
+        {"rsSmoothPasses", (double)pi.rsSmoothPasses}, {"precipSmoothPasses", (double)pi.precipSmoothPasses}, {"wcPasses", (double)pi.wcPasses},
+        {"leeCoastHops", (double)pi.leeCoastHops}, {"upCountSummer", (double)pi.listLengths[0]}, {"downCountSummer", (double)pi.listLengths[1]},
+        {"upCountWinter", (double)pi.listLengths[2]}, {"downCountWinter", (double)pi.listLengths[3]}, {"depletionBase", pi.depletionBase},
+        {"shadowDecay", pi.shadowDecay}, {"windwardDecay", pi.windwardDecay}, {"p95Summer", (double)pi.p95[0]}, {"p95Winter", (double)pi.p95[1]}};
+    for (const auto& x : nums) { napi_create_double(env, x.x, &v); set_prop(env, o, x.k, v); }
+    return o;
+}
+// precipDownload(planet, key) -> Float32Array: one field of the planet's precipitation block by the reference's result key
+napi_value PrecipDownload(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    char key[64]; if (!key_at(a, 1, key)) return nullptr;
+    const size_t n = (size_t)wo_planet_num_regions(p);
+    void* d; napi_value out = make_ta(env, napi_float32_array, n, 4, &d);
+    if (!out) return nullptr;
+    if (wo_precip_download(p, key, d, (int64_t)(n * 4))) return throw_wo(env, "precipDownload");
+    return out;
+}
 // landComponents(numRegions, adjOffset, adjList, r_isOcean) -> Int32Array (label = smallest id of the landmass, -1 for ocean)
 napi_value LandComponents(napi_env env, napi_callback_info info) {
     Args a(env, info);
@@ -710,6 +748,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"landComponents", LandComponents}, {"sampleHeightmap", SampleHeightmap}, {"syntheticPlates", SyntheticPlates},
         {"classifyRegions", ClassifyRegions}, {"triangleCenters", TriangleCenters}, {"computeWind", ComputeWind}, {"computeGradients", ComputeGradients},
         {"windUpload", WindUpload}, {"computeOceanCurrents", ComputeOceanCurrents}, {"oceanDownload", OceanDownload},
+        {"oceanUpload", OceanUpload}, {"computePrecipitation", ComputePrecipitation}, {"precipDownload", PrecipDownload},
         {"commUniqueId", CommUniqueId}, {"commCreate", CommCreate}, {"planetSetHalo", PlanetSetHalo},
         {"planetExchangeAllgather", PlanetExchangeAllgather}, {"planetExchangeNeighbors", PlanetExchangeNeighbors}, {"planetSetFloodExchange", PlanetSetFloodExchange},
     };

@@ -1,0 +1,249 @@
+"""computePrecipitation on gfx950 (csrc/precip.hip) through ctypes: against the reference's goldens from the reference's own wind and
+ocean outputs uploaded to a fresh planet (which separates a precipitation fault from a wind or ocean fault), along the resident
+chain device wind -> device ocean -> device precipitation against the host emulator of the same bodies (tests/emu_precip, itself
+held to the goldens by test_precip.py) fed the device's own downloaded wind and ocean results, and against that emulator where
+there are no goldens: the 200 k hub mesh (rows of degree 24), the relabelled row-shuffled mesh and the radix-boundary planets.
+The reference is never the device code.
+
+The bar is bit equality on all four outputs.  Every comparison prints its figures before it asserts."""
+from functools import lru_cache
+
+import numpy as np
+import pytest
+
+import precip_common as PC
+import wind_common as WC
+
+pytestmark = pytest.mark.gpu
+
+
+def _planet(case):
+    from planet_heightmap_generation_amd import terrain_post as TP
+    return TP.Planet(WC.Mesh(case["off"], case["adj"]), case["xyz"])
+
+
+def _wind(pl, case, fields=PC.WIND_INPUTS):
+    from planet_heightmap_generation_amd import wind as WD
+    return WD.compute_wind(pl, case["xyz"], case["e"], set(case["ocean"].tolist()), case["plate"], case["seed"], fields=fields)
+
+
+def _ocean(pl, case, fields=PC.OCEAN_INPUTS):
+    from planet_heightmap_generation_amd import ocean as OD
+    return OD.compute_ocean_currents(pl, case["xyz"], case["e"], fields=fields)
+
+
+def _precip(pl, case, wind=None, ocean=None, offset=0.0, coverage=0.3, fields=None):
+    from planet_heightmap_generation_amd import precipitation as PD
+    got = PD.compute_precipitation(pl, case["xyz"], case["e"], wind, ocean, offset, coverage, fields=fields)
+    return got, PD.info(pl)
+
+
+def _info_diff(a, b):
+    return {k: (a[k], b[k]) for k in a if (np.float32(a[k]).tobytes() != np.float32(b[k]).tobytes() if k.startswith("p95") else a[k] != b[k])}
+
+
+def _chain(case, offset=0.0, coverage=0.3):
+    """device wind -> device ocean -> device precipitation on a fresh planet: (outputs, info, the device's wind and ocean inputs)"""
+    pl = _planet(case)
+    try:
+        wind = _wind(pl, case)
+        ocean = _ocean(pl, case)
+        got, info = _precip(pl, case, offset=offset, coverage=coverage)
+    finally:
+        pl.close()
+    return got, info, wind, ocean
+
+
+def _check_against_emulator(label, case, got, info, wind, ocean, offset=0.0, coverage=0.3):
+    assert not PC.pow_differs(case["N"])
+    ref = PC.emulate(case, wind, ocean, offset, coverage)
+    print(f"{label}: N {case['N']}, device {info}")
+    PC.assert_equal(f"{label}: device against the emulator fed the device's wind and ocean", got, ref)
+    assert not _info_diff(ref["_info"], info), _info_diff(ref["_info"], info)
+    return ref
+
+
+@pytest.mark.parametrize("name", PC.FULL_CASES)
+def test_matches_reference_from_uploaded_inputs(name):
+    """The reference's own wind and ocean outputs uploaded to a planet that ran neither stage."""
+    from planet_heightmap_generation_amd import capi, ocean as OD
+    case = PC.golden_case(name)
+    pl = _planet(case)
+    try:
+        got, info = _precip(pl, case, case["wind"], case["warm"], case["offset"], case["coverage"])
+        # a block filled by uploads is no ocean result: a field that was never set is not served, an uploaded one is
+        buf = np.zeros(case["N"], np.float32)
+        assert capi.lib().wo_ocean_download(pl.handle, b"r_ocean_speed_summer", capi.ptr(buf), buf.nbytes) != 0 and "no ocean result" in capi.last_error()
+        assert PC.same_bits(OD.download(pl, "r_ocean_warmth_winter"), np.ascontiguousarray(case["warm"]["r_ocean_warmth_winter"], np.float32))
+    finally:
+        pl.close()
+    print(f"{name}: {info}")
+    PC.assert_golden(f"{name} (uploaded wind and ocean)", got, case)
+    want = PC.reference_info(case)
+    assert {k: info[k] for k in want} == want
+    emu = PC.emulate(case, offset=case["offset"], coverage=case["coverage"])["_info"]
+    assert not _info_diff(emu, info), _info_diff(emu, info)
+
+
+@pytest.mark.parametrize("name", PC.GOLDEN_CASES)
+def test_resident_chain(name):
+    """computeWind, computeOceanCurrents and the stage on the device.  Pass / fail: bit equality with the emulator fed the device's
+    own downloaded wind and ocean results.  The cells differing from the golden are counted and printed; their count is asserted
+    to be 0 only when the device's inputs have the golden's checksums (the device's season winds carry the device's libm)."""
+    case = PC.golden_case(name)
+    got, info, wind, ocean = _chain(case, case["offset"], case["coverage"])
+    _check_against_emulator(name, case, got, info, wind, ocean, case["offset"], case["coverage"])
+    m = case["meta"]
+    exact = all(PC.crc(np.ascontiguousarray(dict(wind, **ocean)[k])) == m["crc_inputs"][k] for k in PC.WIND_INPUTS + PC.OCEAN_INPUTS)
+    bad = PC.differing(got, case["ref"], m["stride"], m["crc"] if m["stride"] > 1 else None)
+    print(f"{name}: the device's wind and ocean inputs have the golden's checksums: {exact}; cells that differ from the golden: {bad or 'none'}")
+    if exact:
+        assert not bad, bad
+
+
+@lru_cache(maxsize=None)
+def _scale_case(which):
+    import elev_inputs as EI
+    if which.startswith("boundary_"):
+        return WC.boundary_case(int(which[len("boundary_"):]))
+    ec = {"hub_N200000_deg24": lambda: EI.hub_case(200_000), "relabelled_N200000": lambda: EI.relabelled_case(200_000)}[which]()
+    # the stand-in terrain of the wind and ocean tests, twice as high: land reaches 0.9 (5.5 km), so that cells above the 0.8 km
+    # floor of the rain-shadow seed exist
+    return WC.case_from_elev(ec, WC.plate_mask_elevation(ec, seed=11) * np.float32(2))
+
+
+@pytest.mark.parametrize("which", ["hub_N200000_deg24", "relabelled_N200000"] + [f"boundary_{c}" for c in WC.BOUNDARY_CELLS])
+def test_matches_emulator(which):
+    """Where there are no goldens: the device chain against the emulator fed the device's own wind and ocean results; the case is
+    not trivial."""
+    case = _scale_case(which)
+    got, info, wind, ocean = _chain(case)
+    ref = _check_against_emulator(which, case, got, info, wind, ocean)
+    land = wind["r_isLand"] != 0
+    rs = got["r_rainshadow_summer"]
+    print(f"{which}: land {land.mean():.3f}, largest degree {int(np.diff(case['off']).max())}, list lengths {[info[k] for k in PC.LIST_FIELDS]}, "
+          f"land cells with a non-empty upwind list {ref['_up_cells']} of {int(land.sum())}, rain shadow min / max {rs.min():.3f} / {rs.max():.3f}, maxPrecip {info['p95Summer']:.4f} / {info['p95Winter']:.4f}")
+    assert min(ref["_up_cells"]) > 0.01 * int(land.sum())
+    assert rs.min() < 0 and rs.max() > 0 and info["p95Summer"] != 1 and info["p95Winter"] != 1
+    if which == "hub_N200000_deg24":
+        assert int(np.diff(case["off"]).max()) >= 24
+    assert ref["_info"]["shadowHops"] == info["shadowHops"]
+
+
+def test_second_call_equals_fresh_planet():
+    """Another terrain and other parameters on the same planet, then the first again: what a fresh planet gives."""
+    a = PC.golden_case("precip_config1_N10000_s1")
+    imp = PC.golden_case("precip_import_N10000_s1")        # the same cells (positions), rows in another order: its terrain and plates on a's mesh
+    assert np.array_equal(a["xyz"], imp["xyz"])
+    other = dict(a, name="import terrain on config 1's mesh", e=imp["e"], plate=imp["plate"], ocean=imp["ocean"])
+    pl = _planet(a)
+    try:
+        _wind(pl, a, fields=()); _ocean(pl, a, fields=())
+        first, info1 = _precip(pl, a)
+        repeat, _ = _precip(pl, a)
+        _wind(pl, other, fields=()); _ocean(pl, other, fields=())
+        second, info2 = _precip(pl, other, offset=0.6, coverage=0.7)
+        _wind(pl, a, fields=()); _ocean(pl, a, fields=())
+        again, _ = _precip(pl, a)
+    finally:
+        pl.close()
+    want, info3, wind, ocean = _chain(other, 0.6, 0.7)
+    PC.assert_equal("repeat of the first call", repeat, first)
+    PC.assert_equal("second call against a fresh planet", second, want)
+    PC.assert_equal("first terrain again", again, first)
+    assert not _info_diff(info2, info3) and _info_diff(info2, info1)
+    assert not PC.same_bits(second["r_precip_summer"], first["r_precip_summer"])
+    _check_against_emulator("second call", other, second, info2, wind, ocean, 0.6, 0.7)
+
+
+def _device_bytes():
+    from planet_heightmap_generation_amd import capi
+    d, h, n = np.zeros(1, np.int64), np.zeros(1, np.int64), np.zeros(1, np.int64)
+    assert capi.lib().wo_memory_in_use(capi.ptr(d), capi.ptr(h), capi.ptr(n)) == 0
+    return int(d[0]), int(h[0])
+
+
+def test_refusals_leave_the_planet_usable_and_memory_is_steady():
+    """No wind block, a wind block but no ocean block, a partially uploaded ocean block, a wrong numRegions, an unknown key, a short
+    buffer, NULL pointers: each fails with a message and leaves the device bytes unchanged, and the planet still gives the golden
+    afterwards.  The first call grows the device memory by the precipitation block alone; the second and third leave it as it is."""
+    from planet_heightmap_generation_amd import capi, ocean as OD, precipitation as PD
+    case = PC.golden_case("precip_config1_N10000_s1")
+    N = case["N"]
+    buf = np.zeros(N, np.float32)
+    pl = _planet(case)
+    try:
+        L = capi.lib()
+        m0 = _device_bytes()
+        assert L.wo_compute_precipitation(pl.handle, N, None, 0.0, 0.3, None) != 0 and "no wind result" in capi.last_error()
+        assert L.wo_precip_download(pl.handle, b"r_precip_summer", capi.ptr(buf), buf.nbytes) != 0 and "no precipitation result" in capi.last_error()
+        assert _device_bytes() == m0
+        for k in PC.WIND_INPUTS:
+            OD.upload_wind(pl, k, case["wind"][k])
+        m1 = _device_bytes()
+        assert L.wo_compute_precipitation(pl.handle, N, None, 0.0, 0.3, None) != 0 and "no ocean result" in capi.last_error()
+        assert _device_bytes() == m1
+        PD.upload_ocean(pl, "r_ocean_warmth_summer", case["warm"]["r_ocean_warmth_summer"])
+        m2 = _device_bytes()
+        assert L.wo_compute_precipitation(pl.handle, N, None, 0.0, 0.3, None) != 0 and "no ocean result" in capi.last_error()
+        assert L.wo_ocean_upload(pl.handle, b"nope", capi.ptr(buf), buf.nbytes) != 0 and "unknown field" in capi.last_error()
+        assert L.wo_ocean_upload(pl.handle, b"r_ocean_warmth_winter", capi.ptr(buf), buf.nbytes - 4) != 0 and "bytes" in capi.last_error()
+        assert L.wo_ocean_upload(pl.handle, b"r_ocean_warmth_winter", None, buf.nbytes) != 0 and "null pointer" in capi.last_error()
+        PD.upload_ocean(pl, "r_ocean_warmth_winter", case["warm"]["r_ocean_warmth_winter"])
+        assert L.wo_compute_precipitation(pl.handle, N - 1, None, 0.0, 0.3, None) != 0 and "numRegions" in capi.last_error()
+        assert L.wo_compute_precipitation(None, N, None, 0.0, 0.3, None) != 0 and "wo_compute_precipitation" in capi.last_error()
+        assert _device_bytes() == m2
+        got, info = _precip(pl, case)
+        m3 = _device_bytes()
+        assert L.wo_precip_download(pl.handle, b"nope", capi.ptr(buf), buf.nbytes) != 0 and "unknown field" in capi.last_error()
+        assert L.wo_precip_download(pl.handle, b"r_precip_summer", capi.ptr(buf), buf.nbytes - 4) != 0 and "bytes" in capi.last_error()
+        assert L.wo_precip_download(pl.handle, b"r_precip_summer", None, buf.nbytes) != 0 and "null pointer" in capi.last_error()
+        assert L.wo_precip_download(None, b"r_precip_summer", capi.ptr(buf), buf.nbytes) != 0 and "wo_precip_download" in capi.last_error()
+        after = {k: PD.download(pl, k) for k in PC.RESULT_KEYS}
+        second, _ = _precip(pl, case)
+        m4 = _device_bytes()
+        third, _ = _precip(pl, case, offset=0.6, coverage=0.7)
+        m5 = _device_bytes()
+    finally:
+        pl.close()
+    block = 4 * N * 4 + 2 * 360 * 4                       # the four results and the ITCZ latitudes, plus the control words (below)
+    print(f"device / pinned bytes: before the first call {m2}, after it {m3}, after the second {m4}, after the third {m5}; growth {m3[0] - m2[0]}, "
+          f"the four results and the ITCZ latitudes are {block}")
+    PC.assert_golden("after refused calls", got, case)
+    PC.assert_equal("downloads after refused downloads", after, got)
+    PC.assert_equal("second call", second, got)
+    assert not PC.same_bits(third["r_precip_summer"], got["r_precip_summer"])
+    assert m3 == m4 == m5
+    ctl = m3[0] - m2[0] - block
+    assert 0 < ctl <= 64 * 1024 and m3[1] - m2[1] == ctl, "the first call's growth is the block: four results, the ITCZ latitudes, the control words (device and pinned copy)"
+
+
+REFERENCE_MS_1M = 17966.5           # the reference's computePrecipitation under Node 12 on wind_common.synthetic_case(1 000 000)
+
+
+def test_faster_than_the_reference_at_1m():
+    """The one pass / fail condition on speed: the device stage at 1 M cells takes less wall time than the reference under Node on
+    the same planet (the second call on a planet: the first also allocates the block).  Also the 1 M scalars, and two calls give
+    the same checksums.  The emulator is not run at this size.  rsSmoothPasses is 7 here, as the reference's own formula gives
+    under V8 on this planet (round(150 / 20.015) = round(7.494)); the issue's text says 8, which no evaluation of :609 gives."""
+    import time
+    from planet_heightmap_generation_amd import precipitation as PD
+    case = WC.synthetic_case(1_000_000)
+    assert not PC.pow_differs(case["N"])
+    pl = _planet(case)
+    try:
+        _wind(pl, case, fields=()); _ocean(pl, case, fields=())
+        ms, crcs = [], []
+        for _ in range(2):
+            t0 = time.perf_counter()
+            PD.compute_precipitation(pl, None, case["e"], fields=())
+            ms.append((time.perf_counter() - t0) * 1e3)
+            crcs.append({k: PC.crc(PD.download(pl, k)) for k in PC.RESULT_KEYS})
+        info = PD.info(pl)
+    finally:
+        pl.close()
+    print(f"computePrecipitation at 1 M cells: {ms[0]:.1f} ms (first call), {ms[1]:.1f} ms; {info}; the reference under Node: {REFERENCE_MS_1M:.0f} ms")
+    assert [info[k] for k in ("shadowHops", "windwardHops", "convSmoothPasses", "elevSmoothPasses", "rsSmoothPasses", "precipSmoothPasses", "wcPasses", "maxHops")] \
+        == [125, 75, 20, 10, 7, 5, 15, 20]
+    assert crcs[0] == crcs[1]
+    assert ms[1] < REFERENCE_MS_1M
