@@ -363,6 +363,48 @@ typedef struct wo_precip_info {
 int wo_compute_precipitation(wo_planet* p, int32_t numRegions, const float* r_elevation, double precipitationOffset, double landCoverage,
                              wo_precip_info* info);
 int wo_precip_download(wo_planet* p, const char* field, void* out, int64_t outBytes);
+/* wo_precip_upload sets one field of the planet's precipitation block from the host by its result key (the four keys of
+ *   wo_precip_download; `bytes` must be numRegions floats exactly); it allocates the block if there is none.  It serves a caller
+ *   that brings its own precipResult to a later stage.  A block filled only by uploads is no precipitation result: it serves
+ *   the uploaded fields, and wo_precip_download of a field that was never set still fails. */
+int wo_precip_upload(wo_planet* p, const char* field, const void* data, int64_t bytes);
+
+/* ------------------------------------------------ temperature (js/temperature.js) -------------- */
+/* computeTemperature(mesh, r_xyz, r_elevation, windResult, oceanResult, precipResult, temperatureOffset)
+ *                                                                    js/temperature.js:69-237
+ *   on the planet's resident mesh (csrc/temp.hip; the per-cell bodies and their contract are in csrc/temp_ops.h).
+ *   windResult is the planet's wind block (wo_compute_wind, or wo_wind_upload of at least r_lat r_lon r_isLand r_continentality
+ *   r_plateContinentality and the three ITCZ arrays), oceanResult its ocean block (wo_compute_ocean_currents, or wo_ocean_upload
+ *   of r_ocean_warmth_* and r_ocean_speed_* of both seasons), precipResult its precipitation block (wo_compute_precipitation, or
+ *   wo_precip_upload of r_precip_summer and r_precip_winter).  Without them the call fails with "no wind result" / "no ocean
+ *   result" / "no precipitation result": the reference's branches for missing fields are not offered.  r_elevation: numRegions
+ *   floats, NULL means the planet's resident field.  numRegions must equal the planet's; temperatureOffset must be a number.
+ *   The per-cell code calls pow(t, 1.4) of the platform's libm, so the outputs are the reference's up to a per-cell bound
+ *   (tests/test_temperature_libm.py), not bit for bit.
+ *   The results stay on the device in a temperature block the planet owns (8 bytes per cell; a later call replaces them);
+ *   wo_temperature_download copies one field (numRegions floats) to the host by the reference's result key:
+ *     r_temperature_summer r_temperature_winter
+ *   and wo_temperature_upload sets one (a block filled only by uploads serves the uploaded fields and refuses the others).
+ *   info (may be NULL) receives the pass counts and the kernel launches of the call.  No CPU fallback. */
+typedef struct wo_temperature_info {
+    int32_t oceanWarmthPasses;                         /* max(4, round(1400 / avgEdgeKm)) */
+    int32_t smoothPasses;                              /* 1 */
+    int32_t launches;                                  /* kernel launches of the call */
+    int32_t reserved;
+} wo_temperature_info;
+int wo_compute_temperature(wo_planet* p, int32_t numRegions, const float* r_elevation, double temperatureOffset, wo_temperature_info* info);
+int wo_temperature_download(wo_planet* p, const char* field, void* out, int64_t outBytes);
+int wo_temperature_upload(wo_planet* p, const char* field, const void* data, int64_t bytes);
+
+/* ------------------------------------------------ Koppen classes (js/koppen.js) ---------------- */
+/* classifyKoppen(mesh, r_elevation, tempResult, precipResult)                                     js/koppen.js:67-288
+ *   One class id per cell (an index into the reference's KOPPEN_CLASSES: 0 Ocean, 1 Af .. 30 EF), from the elevation
+ *   (r_elevation: numRegions floats, NULL means the planet's resident field), the planet's temperature block and r_precip_* of
+ *   its precipitation block (computed or uploaded); otherwise the call fails with "no temperature result" / "no precipitation
+ *   result".  Given the same inputs every cell has the reference's class.  The ids stay on the device in a Koppen block the
+ *   planet owns (1 byte per cell); wo_koppen_download copies them (numRegions bytes) to the host. */
+int wo_classify_koppen(wo_planet* p, int32_t numRegions, const float* r_elevation);
+int wo_koppen_download(wo_planet* p, uint8_t* out, int64_t outBytes);
 
 /* ------------------------------------------------ device-resident variants -------------------- */
 /* The "reapply" pattern (js/planet-worker.js:341-440): fields stay in HBM, only scalars arrive.

@@ -72,6 +72,12 @@ SIGNATURES = {
     "wo_ocean_upload": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
     "wo_compute_precipitation": (C.c_int, [_p, _c_i32, _p, _c_f64, _c_f64, _p]),
     "wo_precip_download": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
+    "wo_precip_upload": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
+    "wo_compute_temperature": (C.c_int, [_p, _c_i32, _p, _c_f64, _p]),
+    "wo_temperature_download": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
+    "wo_temperature_upload": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
+    "wo_classify_koppen": (C.c_int, [_p, _c_i32, _p]),
+    "wo_koppen_download": (C.c_int, [_p, _p, _c_i64]),
     "wo_planet_upload": (C.c_int, [_p, _p, _p]),
     "wo_planet_download": (C.c_int, [_p, _p]),
     "wo_planet_set_halo": (C.c_int, [_p, _p, _c_i32, _p, _c_i32]),

@@ -95,6 +95,7 @@ struct Options {
     long long carveBudgetMs = 200;     // carve_budget_ms=<n>      spin budget of the one-launch carve (0: it gives up at once and the rounds finish)
     int  carveBlocks = 0;              // carve_blocks=<n>         at most this many workgroups for the one-launch carve
     bool oceanSplitSmooth = false;     // ocean_split_smooth=1     ocean currents: the masked smoothing field by field instead of one interleaved gather (the A/B of DESIGN section 8.3)
+    bool tempSplitDiffuse = false;     // temp_split_diffuse=1     temperature: diffuseOceanWarmth season by season with the single-field kernels instead of one float2 gather
     static Options from_env();
 };
 }  // namespace wo
@@ -196,6 +197,10 @@ struct wo_planet {
     // precipitation (precip.hip): the precipitation block — the four results of wo_compute_precipitation, allocated on its first
     // call; deleted by wo_planet_destroy (precip_free)
     struct wo_precip_block* precip = nullptr;
+    // temperature and Koppen classes (temp.hip): the temperature block (8 bytes per cell) and the Koppen block (1 byte per cell),
+    // allocated on the first call of their stage or upload; deleted by wo_planet_destroy (temp_free)
+    struct wo_temp_block* temp = nullptr;
+    struct wo_koppen_block* koppen = nullptr;
 
     // Patch-major mirror of the mesh for erodeComposite (planet.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
@@ -286,10 +291,14 @@ void basin_solve_launch(wo_planet* p, const Fields& F, int32_t launchTag, int32_
 void wind_free(wo_planet* p);
 void ocean_free(wo_planet* p);
 void precip_free(wo_planet* p);
+void temp_free(wo_planet* p);
 // planet.hip: the entry points' handle check (refreshes p->opt from the environment, selects the device)
 bool check_planet(wo_planet* p, const char* fn);
 // planet.hip: smoothField on a resident field (returns the buffer that holds the result)
 float* smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passes);
+// planet.hip: diffuseOceanWarmth of one season on resident fields with the single-field kernels (seeds a, ping-pongs a and b and
+// returns the buffer that holds the result)
+float* diffuse_warmth_resident(wo_planet* p, const float* warmth, const uint8_t* isLand, const float* plateCont, int32_t passes, float* a, float* b);
 // planet.hip: computeWindConvergence and advectMoisture on resident fields (the advection seeds a, ping-pongs a and b and returns
 // the buffer that holds the result)
 void wind_convergence_resident(wo_planet* p, const float* wx, const float* wy, const float* wz, float* out);

@@ -1104,6 +1104,7 @@ Options Options::from_env() {
     o.carveBudgetMs = test_hook_int("carve_budget_ms", 200);
     o.carveBlocks = (int)std::max<long long>(0, test_hook_int("carve_blocks", 0));
     o.oceanSplitSmooth = test_hook_int("ocean_split_smooth", 0) != 0;
+    o.tempSplitDiffuse = test_hook_int("temp_split_diffuse", 0) != 0;
     return o;
 }
 
@@ -1115,6 +1116,14 @@ float* wo::smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passe
         launch(p, FAM_SMOOTH_FIELD, k_smooth_field, xcd_grid(p->N), WO_BLOCK, F, (const float*)a, b);
         std::swap(a, b);
     }
+    return a;
+}
+
+// diffuseOceanWarmth (js/temperature.js:19-54) of one season on device-resident fields (temp.hip, the split form of its diffusion)
+float* wo::diffuse_warmth_resident(wo_planet* p, const float* warmth, const uint8_t* isLand, const float* plateCont, int32_t passes, float* a, float* b) {
+    const Fields F = p->fields(); const ClimateMesh M = climate_mesh(p);
+    launch(p, FAM_CLIMATE, k_warmth_seed, blocks_for(p->N, 4096), WO_BLOCK, warmth, isLand, a, p->N);
+    for (int32_t pass = 0; pass < passes; ++pass) { launch(p, FAM_CLIMATE, k_warmth_diffuse, xcd_grid(p->N), WO_BLOCK, F, M, (const float*)a, plateCont, b); std::swap(a, b); }
     return a;
 }
 
@@ -1275,6 +1284,7 @@ void wo_planet_destroy(wo_planet* p) {
     if (p->evJoin) { (void)hipEventDestroy(p->evJoin); p->evJoin = nullptr; }
     if (p->floodLink && p->floodLinkFree) p->floodLinkFree(p->floodLink);
     p->floodLink = nullptr;
+    temp_free(p);
     precip_free(p);
     ocean_free(p);
     wind_free(p);

@@ -31,34 +31,11 @@
 #include "../../include/worogen.h"
 #include "device.h"
 #include "ocean_block.h"
+#include "precip_block.h"
 #include "precip_ops.h"
 #include "wind_block.h"
 
 namespace P = wo::precip;
-
-namespace wo {
-// what the kernels of a call share; cleared at its start.  The head (up to sel) comes back to the host at its end.
-struct PrecipCtl {
-    uint32_t lists[4];                                        // members of the upwind, downwind lists of summer, then of winter
-    uint32_t cells[2];                                        // values that enter the percentile: N, N
-    float p95[2];                                             // maxPrecip
-    W::SelState sel[2];
-    uint32_t hist[2][W::SEL_PASSES][W::SEL_BINS];
-};
-constexpr size_t PRECIP_CTL_HEAD = offsetof(PrecipCtl, sel);
-__device__ inline uint32_t sel_count(const PrecipCtl* c, int season) { return c->cells[season]; }
-}  // namespace wo
-
-// the precipitation block of a planet
-struct wo_precip_block {
-    wo::DeviceArena mem;                                      // owns every device and pinned buffer of the block
-    bool valid = false;
-    float* out[4] = {nullptr, nullptr, nullptr, nullptr};     // r_precip_summer, r_precip_winter, r_rainshadow_summer, r_rainshadow_winter
-    float* itcz = nullptr;                                    // 2 x 360: itczLatsSummer, itczLatsWinter
-    wo::PrecipCtl* ctl = nullptr;
-    wo::PrecipCtl* h_ctl = nullptr;                           // pinned: the head of ctl
-    wo_precip_info info{};
-};
 
 namespace wo {
 
@@ -246,7 +223,7 @@ static void precip_run(wo_planet* p, const float* r_elevation, double precipitat
     const int32_t N = p->N, g = blocks_for(N), tile = xcd_tile(N), xg = xcd_grid(N);
     const size_t n = (size_t)N, E = (size_t)p->E;
     hipStream_t s = p->ctx->stream;
-    B->valid = false;
+    B->valid = false; B->have = 0;
     const P::Params Q = P::params_for(N);
     const int32_t* off = p->d_off; const int32_t* adj = p->d_adj; const float* xyz = p->d_xyz;
     const uint8_t* isLand = Wb->isLand;
@@ -339,7 +316,7 @@ static void precip_run(wo_planet* p, const float* r_elevation, double precipitat
     I.depletionBase = Q.depletionBase; I.shadowDecay = Q.shadowDecay; I.windwardDecay = Q.windwardDecay;
     I.p95[0] = H.p95[0]; I.p95[1] = H.p95[1];
     B->info = I;
-    B->valid = true;
+    B->valid = true; B->have = 0xfu;
 }
 
 }  // namespace wo
@@ -351,6 +328,11 @@ static const char* const kPrecipFields[4] = {"r_precip_summer", "r_precip_winter
 // the fields of the wind block the stage reads: pressure, east and north wind of both seasons, the ITCZ arrays, the geography
 static constexpr uint32_t kWindNeeded = 0x77u | (7u << WF_ITCZ0) | (1u << WF_LAT) | (1u << WF_LON) | (1u << WF_ISLAND) | (1u << WF_CONT) | (1u << WF_COASTDIST) | (63u << WF_FRAME0);
 static constexpr uint32_t kOceanNeeded = (1u << 3) | (1u << 7);      // r_ocean_warmth_summer, r_ocean_warmth_winter
+
+static int precip_field_index(const char* name) {
+    for (int i = 0; i < 4; ++i) if (std::strcmp(name, kPrecipFields[i]) == 0) return i;
+    return -1;
+}
 
 extern "C" {
 
@@ -381,10 +363,10 @@ int wo_precip_download(wo_planet* p, const char* field, void* out, int64_t outBy
     if (!check_planet(p, "wo_precip_download")) return 1;
     if (!field || !out) { set_error("wo_precip_download: null pointer"); return 1; }
     auto* B = p->precip;
-    if (!B || !B->valid) { set_error("wo_precip_download: no precipitation result on this planet (call wo_compute_precipitation first)"); return 1; }
-    int f = -1;
-    for (int i = 0; i < 4; ++i) if (std::strcmp(field, kPrecipFields[i]) == 0) f = i;
+    if (!B || !(B->valid || B->have)) { set_error("wo_precip_download: no precipitation result on this planet (call wo_compute_precipitation first)"); return 1; }
+    const int f = precip_field_index(field);
     if (f < 0) { set_error(std::string("wo_precip_download: unknown field '") + field + "'"); return 1; }
+    if (!B->valid && !((B->have >> f) & 1u)) { set_error(std::string("wo_precip_download: no precipitation result on this planet: ") + field + " was never set (call wo_compute_precipitation first)"); return 1; }
     WO_TRY
         const size_t bytes = (size_t)p->N * 4;
         if (outBytes < (int64_t)bytes) { set_error(std::string("wo_precip_download: ") + field + " needs " + std::to_string(bytes) + " bytes, out has " + std::to_string(outBytes)); return 1; }
@@ -392,6 +374,23 @@ int wo_precip_download(wo_planet* p, const char* field, void* out, int64_t outBy
         WO_HIP(hipStreamSynchronize(p->ctx->stream));
         return 0;
     WO_CATCH("wo_precip_download")
+}
+
+int wo_precip_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) {
+    if (!check_planet(p, "wo_precip_upload")) return 1;
+    if (!field || !data) { set_error("wo_precip_upload: null pointer"); return 1; }
+    const int f = precip_field_index(field);
+    if (f < 0) { set_error(std::string("wo_precip_upload: unknown field '") + field + "'"); return 1; }
+    WO_TRY
+        const size_t want = (size_t)p->N * 4;
+        if (bytes != (int64_t)want) { set_error(std::string("wo_precip_upload: ") + field + " takes " + std::to_string(want) + " bytes, data has " + std::to_string(bytes)); return 1; }
+        precip_alloc(p);
+        auto* B = p->precip;
+        WO_HIP(hipMemcpyAsync(B->out[f], data, want, hipMemcpyHostToDevice, p->ctx->stream));
+        WO_HIP(hipStreamSynchronize(p->ctx->stream));         // `data` is the caller's, and pageable
+        B->have |= 1u << f;
+        return 0;
+    WO_CATCH("wo_precip_upload")
 }
 
 }  // extern "C"

@@ -1,10 +1,13 @@
 // worker_threads counterpart of the reference's Web Worker (js/planet-worker.js) for the part of its message protocol
-// that is the device path: the retained state W (:277-292), `reapply` (:341-440) and the dispatcher (:944-954).
+// that is the device path: the retained state W (:277-292), `reapply` (:341-440), `computeClimate` (:579-677) and the
+// dispatcher (:944-954).
 //
-//   cmd 'retain'   { mesh: { numRegions, adjOffset, adjList, triangles? }, r_xyz, neighborDist?, prePostElev, seed, r_hotspot? }
-//                  What `generate` leaves in W for later reapplies, handed over by the caller (plate generation, ocean /
-//                  land assignment and the climate modules are the reference's own host code and stay where they are).
-//                  The mesh, positions and the pre-erosion field go to HBM ONCE and stay there.
+//   cmd 'retain'   { mesh: { numRegions, adjOffset, adjList, triangles? }, r_xyz, neighborDist?, prePostElev, seed, r_hotspot?,
+//                    r_plate?, plateIsOcean? }
+//                  What `generate` leaves in W for later reapplies, handed over by the caller (plate generation and ocean /
+//                  land assignment are the reference's own host code and stay where they are).  The mesh, positions and the
+//                  pre-erosion field go to HBM ONCE and stay there.  r_plate (Int32Array) and plateIsOcean (the ids of the
+//                  oceanic plates: a Set, an array or an Int32Array) are what a later `computeClimate` needs.
 //                  -> { type: 'retained', numRegions }
 //   cmd 'reapply'  { terrainWarp, smoothing, glacialErosion, hydraulicErosion, thermalErosion, ridgeSharpening, skipClimate? }
 //                  restore the pre-erosion field on the device (no upload), runPostProcessing resident, triangle
@@ -16,7 +19,16 @@
 //                  (device), runPostProcessing resident, synthetic plates and region classification (device), triangle
 //                  elevations.  The sampled field is kept as W.prePostElev on the device, so a following `reapply` works on the
 //                  imported planet.  Climate is not run (skipClimate is reported as true, as for reapply); the result is the
-//                  reference's `done` message with the climate fields null, buffers transferred as the reference does.
+//                  reference's `done` message with the climate fields null, buffers transferred as the reference does.  Copies
+//                  of r_plate and plateIsOcean stay in W with the seed, so a following `computeClimate` works as well.
+//   cmd 'computeClimate' { temperatureOffset?, precipitationOffset?, landCoverage? }   (:579-677)
+//                  computeWind, computeOceanCurrents, computePrecipitation, computeTemperature and classifyKoppen on the device,
+//                  resident, on the planet's current elevation.  Wind and ocean are skipped while the planet's blocks belong to
+//                  that elevation (the reference's cachedWind: `reapply`, `importHeightmap` and `retain` invalidate them); the
+//                  parameters persist in W as getClimateParams keeps them (:104-110).  Progress labels and the result as the
+//                  reference posts them:
+//                  -> { type: 'climateDone', <the 19 climate fields>, climateDebugLayers, _climateTiming: { wind, ocean,
+//                       precipitation, temperature, koppen, workerTotal } }
 //   cmd 'dispose'  frees the retained state -> { type: 'disposed' }
 //   progress / errors exactly as the reference posts them: { type: 'progress', pct, label }, { type: 'error', message, stack };
 //   an unknown command answers `Unknown command: <cmd>` (:952).
@@ -38,15 +50,18 @@ function releaseRetained() { if (W && W.planet) addon.planetDestroy(W.planet); W
 
 function handleRetain(data) {
     try {
-        const { mesh, r_xyz, neighborDist, prePostElev, seed, r_hotspot } = data;
+        const { mesh, r_xyz, neighborDist, prePostElev, seed, r_hotspot, r_plate, plateIsOcean } = data;
         if (!mesh || !(mesh.adjOffset instanceof Int32Array) || !(mesh.adjList instanceof Int32Array)) throw new TypeError('retain: mesh.adjOffset / mesh.adjList must be Int32Arrays');
         if (!(r_xyz instanceof Float32Array) || !(prePostElev instanceof Float32Array)) throw new TypeError('retain: r_xyz and prePostElev must be Float32Arrays');
+        if (r_plate !== undefined && r_plate !== null && (!(r_plate instanceof Int32Array) || r_plate.length !== mesh.numRegions)) throw new TypeError('retain: r_plate must be an Int32Array of numRegions entries');
         releaseRetained();                               // a second retain replaces the first: its device memory goes now, not at the next GC
         const planet = addon.planetCreate(defaultContext(), mesh.numRegions, mesh.adjOffset, mesh.adjList, r_xyz, neighborDist || null);
         addon.planetUpload(planet, prePostElev, null);
         if (r_hotspot) addon.planetUploadHotspot(planet, r_hotspot);
         addon.planetSaveState(planet);                  // W.prePostElev, device copy
-        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles || null, seed, hasHotspot: !!r_hotspot };
+        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles || null, seed, hasHotspot: !!r_hotspot,
+              r_plate: r_plate || null, plateIsOcean: (plateIsOcean !== undefined && plateIsOcean !== null) ? Int32Array.from(plateIsOcean) : null,
+              cachedWind: null, cachedOcean: null };
         parentPort.postMessage({ type: 'retained', numRegions: mesh.numRegions });
     } catch (err) {
         parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
@@ -59,6 +74,7 @@ function handleReapply(data) {
         const tTotal0 = performance.now();
         progress(0, 'Reapplying terrain…');
         let t0 = performance.now();
+        W.cachedWind = null; W.cachedOcean = null;     // the elevation changes: the wind and ocean blocks no longer belong to it
         addon.planetRestoreState(W.planet);             // r_elevation = new Float32Array(W.prePostElev), on the device
         const r_elevation = new Float32Array(W.numRegions);
         const tClone = performance.now() - t0;
@@ -117,7 +133,7 @@ function handleImportHeightmap(data) {
         t0 = performance.now();
         releaseRetained();
         const planet = addon.planetCreate(defaultContext(), mesh.numRegions, mesh.adjOffset, mesh.adjList, r_xyz, neighborDist);
-        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles, seed, hasHotspot: false };
+        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles, seed, hasHotspot: false, r_plate: null, plateIsOcean: null, cachedWind: null, cachedOcean: null };
         const prePostElev = addon.sampleHeightmap(planet, grayscale, imageWidth, imageHeight, true);
         addon.planetSaveState(planet);                  // W.prePostElev, device copy
         timing.push({ stage: 'Sample heightmap', ms: performance.now() - t0 });
@@ -134,6 +150,7 @@ function handleImportHeightmap(data) {
         const { r_plate, plateSeeds, plateIsOcean, plateVec } = platesFromDevice(addon.syntheticPlates(planet));
         timing.push({ stage: 'Synthetic plates', ms: performance.now() - t0 });
         const regions = addon.classifyRegions(planet);
+        W.r_plate = new Int32Array(r_plate); W.plateIsOcean = Int32Array.from(plateIsOcean);     // copies: r_plate's buffer leaves with the message
 
         progress(75, 'Computing triangle elevations\u2026');
         t0 = performance.now();
@@ -160,6 +177,87 @@ function handleImportHeightmap(data) {
     }
 }
 
+// js/planet-worker.js:104-110
+function getClimateParams(data) {
+    const pick = (k, dflt) => (data && data[k] !== undefined && data[k] !== null) ? data[k] : (W && W[k] !== undefined && W[k] !== null) ? W[k] : dflt;
+    const temperatureOffset = pick('temperatureOffset', 0), precipitationOffset = pick('precipitationOffset', 0), landCoverage = pick('landCoverage', 0.3);
+    if (W) { W.temperatureOffset = temperatureOffset; W.precipitationOffset = precipitationOffset; W.landCoverage = landCoverage; }
+    return { temperatureOffset, precipitationOffset, landCoverage };
+}
+
+const OCEAN_KEYS = ['summer', 'winter'].flatMap((s) => ['current_east', 'current_north', 'speed', 'warmth'].map((k) => `r_ocean_${k}_${s}`));
+const PRECIP_KEYS = ['r_precip_summer', 'r_rainshadow_summer', 'r_precip_winter', 'r_rainshadow_winter'];
+const TEMP_KEYS = ['r_temperature_summer', 'r_temperature_winter'];
+
+// js/planet-worker.js:579-677 with every stage on the device; the planet's resident elevation is r_elevation_final
+function handleComputeClimate(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for computeClimate' }); return; }
+    if (!W.r_plate || !W.plateIsOcean) {
+        const missing = [!W.r_plate ? 'r_plate' : null, !W.plateIsOcean ? 'plateIsOcean' : null].filter((k) => k).join(' and ');
+        parentPort.postMessage({ type: 'error', message: `computeClimate: the retained state has no ${missing} (pass them to retain, or run importHeightmap)` });
+        return;
+    }
+    const { temperatureOffset, precipitationOffset, landCoverage } = getClimateParams(data);
+    try {
+        const tTotal0 = performance.now();
+        const planet = W.planet;
+        const download = (keys, fn) => { const o = {}; for (const k of keys) o[k] = fn(planet, k); return o; };
+        let windResult = W.cachedWind, oceanResult = W.cachedOcean;
+        let tWind = 0, tOcean = 0, t0;
+        if (!windResult) {
+            progress(0, 'Simulating wind patterns\u2026');
+            t0 = performance.now();
+            windResult = addon.computeWind(planet, null, W.r_plate, W.plateIsOcean, W.seed, 23.5);
+            tWind = performance.now() - t0;
+
+            progress(30, 'Computing ocean currents\u2026');
+            t0 = performance.now();
+            addon.computeOceanCurrents(planet);
+            oceanResult = download(OCEAN_KEYS, addon.oceanDownload);
+            tOcean = performance.now() - t0;
+
+            W.cachedWind = windResult;
+            W.cachedOcean = oceanResult;
+        }
+
+        progress(50, 'Computing precipitation\u2026');
+        t0 = performance.now();
+        addon.computePrecipitation(planet, null, Number(precipitationOffset), Number(landCoverage));
+        const precipResult = download(PRECIP_KEYS, addon.precipDownload);
+        const tPrecip = performance.now() - t0;
+
+        progress(70, 'Computing temperature\u2026');
+        t0 = performance.now();
+        addon.computeTemperature(planet, null, Number(temperatureOffset));
+        const tempResult = download(TEMP_KEYS, addon.temperatureDownload);
+        const tTemp = performance.now() - t0;
+
+        progress(88, 'Classifying climates\u2026');
+        t0 = performance.now();
+        const koppen = addon.classifyKoppen(planet, null);
+        const tKoppen = performance.now() - t0;
+
+        const tWorkerTotal = performance.now() - tTotal0;
+        const climateDebugLayers = {
+            pressureSummer: windResult.r_pressure_summer, pressureWinter: windResult.r_pressure_winter,
+            windSpeedSummer: windResult.r_wind_speed_summer, windSpeedWinter: windResult.r_wind_speed_winter,
+            continentality: windResult.r_continentality,
+            precipSummer: precipResult.r_precip_summer, precipWinter: precipResult.r_precip_winter,
+            rainShadowSummer: precipResult.r_rainshadow_summer, rainShadowWinter: precipResult.r_rainshadow_winter,
+            tempSummer: tempResult.r_temperature_summer, tempWinter: tempResult.r_temperature_winter,
+            koppen
+        };
+        progress(95, 'Done');
+        const climate = {};
+        for (const k of CLIMATE_NULLS) climate[k] = k in windResult ? windResult[k] : k in oceanResult ? oceanResult[k] : k in precipResult ? precipResult[k] : tempResult[k];
+        // no transfer list: the wind and ocean arrays stay in W for the next command, as the reference's cachedWind does
+        parentPort.postMessage({ type: 'climateDone', ...climate, climateDebugLayers,
+                                 _climateTiming: { wind: tWind, ocean: tOcean, precipitation: tPrecip, temperature: tTemp, koppen: tKoppen, workerTotal: tWorkerTotal } });
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
 parentPort.on('message', (data) => {
     const { cmd } = data;
     switch (cmd) {
@@ -167,7 +265,8 @@ parentPort.on('message', (data) => {
         case 'reapply': handleReapply(data); break;
         case 'importHeightmap': handleImportHeightmap(data); break;
         case 'dispose': releaseRetained(); parentPort.postMessage({ type: 'disposed' }); break;
-        case 'generate': case 'editRecompute': case 'computeClimate':
+        case 'computeClimate': handleComputeClimate(data); break;
+        case 'generate': case 'editRecompute':
             parentPort.postMessage({ type: 'error', message: `Command not served by the device worker (host stages of the reference): ${cmd}` });
             break;
         default: parentPort.postMessage({ type: 'error', message: `Unknown command: ${cmd}` });

@@ -564,6 +564,62 @@ napi_value PrecipDownload(napi_env env, napi_callback_info info) {
     if (wo_precip_download(p, key, d, (int64_t)(n * 4))) return throw_wo(env, "precipDownload");
     return out;
 }
+// precipUpload(planet, key, Float32Array): one field of the planet's precipitation block by its result key (the C ABI checks key and size)
+napi_value PrecipUpload(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    char key[64]; if (!key_at(a, 1, key)) return nullptr;
+    size_t n = 0; float* data = (float*)a.ta(2, napi_float32_array, &n); if (!a.ok) return nullptr;
+    if (wo_precip_upload(p, key, data, (int64_t)(n * 4))) return throw_wo(env, "precipUpload");
+    return nullptr;
+}
+// computeTemperature(planet, r_elevation | null, temperatureOffset) -> the scalars of the call: the stage on the planet's wind, ocean and
+// precipitation blocks; the results stay on the device (temperatureDownload)
+napi_value ComputeTemperature(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* e = (float*)opt_regions(a, 1, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    wo_temperature_info ti;
+    if (wo_compute_temperature(p, wo_planet_num_regions(p), e, a.num(2), &ti)) return throw_wo(env, "computeTemperature");
+    napi_value o, v; napi_create_object(env, &o);
+    const struct { const char* k; double x; } nums[] = {{"oceanWarmthPasses", (double)ti.oceanWarmthPasses}, {"smoothPasses", (double)ti.smoothPasses},
+        {"launches", (double)ti.launches}};
+    for (const auto& x : nums) { napi_create_double(env, x.x, &v); set_prop(env, o, x.k, v); }
+    return o;
+}
+// temperatureDownload(planet, key) -> Float32Array: one field of the planet's temperature block by the reference's result key
+napi_value TemperatureDownload(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    char key[64]; if (!key_at(a, 1, key)) return nullptr;
+    const size_t n = (size_t)wo_planet_num_regions(p);
+    void* d; napi_value out = make_ta(env, napi_float32_array, n, 4, &d);
+    if (!out) return nullptr;
+    if (wo_temperature_download(p, key, d, (int64_t)(n * 4))) return throw_wo(env, "temperatureDownload");
+    return out;
+}
+// temperatureUpload(planet, key, Float32Array): one field of the planet's temperature block by its result key
+napi_value TemperatureUpload(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    char key[64]; if (!key_at(a, 1, key)) return nullptr;
+    size_t n = 0; float* data = (float*)a.ta(2, napi_float32_array, &n); if (!a.ok) return nullptr;
+    if (wo_temperature_upload(p, key, data, (int64_t)(n * 4))) return throw_wo(env, "temperatureUpload");
+    return nullptr;
+}
+// classifyKoppen(planet, r_elevation | null) -> Uint8Array of class ids: the classification on the planet's temperature and
+// precipitation blocks; the ids also stay on the device
+napi_value ClassifyKoppen(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* e = (float*)opt_regions(a, 1, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    const size_t n = (size_t)wo_planet_num_regions(p);
+    if (wo_classify_koppen(p, (int32_t)n, e)) return throw_wo(env, "classifyKoppen");
+    void* d; napi_value out = make_ta(env, napi_uint8_array, n, 1, &d);
+    if (!out) return nullptr;
+    if (wo_koppen_download(p, (uint8_t*)d, (int64_t)n)) return throw_wo(env, "classifyKoppen");
+    return out;
+}
 // landComponents(numRegions, adjOffset, adjList, r_isOcean) -> Int32Array (label = smallest id of the landmass, -1 for ocean)
 napi_value LandComponents(napi_env env, napi_callback_info info) {
     Args a(env, info);
@@ -749,6 +805,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"classifyRegions", ClassifyRegions}, {"triangleCenters", TriangleCenters}, {"computeWind", ComputeWind}, {"computeGradients", ComputeGradients},
         {"windUpload", WindUpload}, {"computeOceanCurrents", ComputeOceanCurrents}, {"oceanDownload", OceanDownload},
         {"oceanUpload", OceanUpload}, {"computePrecipitation", ComputePrecipitation}, {"precipDownload", PrecipDownload},
+        {"precipUpload", PrecipUpload}, {"computeTemperature", ComputeTemperature}, {"temperatureDownload", TemperatureDownload},
+        {"temperatureUpload", TemperatureUpload}, {"classifyKoppen", ClassifyKoppen},
         {"commUniqueId", CommUniqueId}, {"commCreate", CommCreate}, {"planetSetHalo", PlanetSetHalo},
         {"planetExchangeAllgather", PlanetExchangeAllgather}, {"planetExchangeNeighbors", PlanetExchangeNeighbors}, {"planetSetFloodExchange", PlanetSetFloodExchange},
     };
