@@ -233,12 +233,12 @@ static void ocean_run(wo_planet* p) {
     auto* Wb = p->wind;
     const int32_t N = p->N, g = blocks_for(N);
     hipStream_t s = p->ctx->stream;
-    B->valid = false; B->have = 0;
+    B->have = 0;
     const O::Params P = O::params_for(N);
     int32_t *distW = Wb->vals[0], *distE = Wb->vals[1];
     OceanCtl* ctl = B->ctl;
     WO_HIP(hipMemsetAsync(ctl, 0, sizeof(OceanCtl), s));
-    WO_HIP(hipMemcpyAsync(B->itcz, Wb->itcz[1], sizeof(float) * 2 * W::ITCZ_SAMPLES, hipMemcpyHostToDevice, s));      // itczLatsSummer and itczLatsWinter lie one after the other; the block outlives the copy
+    stage_itcz(p, B->itcz);
     launch(p, FAM_CLIMATE, k_ocean_mask, g, WO_BLOCK, (const uint8_t*)Wb->isLand, (const float*)Wb->lat, (const float*)Wb->lon, B->isOcean, ctl->bins, N);
     // the two distance fields, to depth warmthRange - 1
     int32_t* frontier[2] = {(int32_t*)B->group[0], (int32_t*)B->group[1]};      // 4 N entries of room each, 2 N needed
@@ -253,23 +253,24 @@ static void ocean_run(wo_planet* p) {
     launch(p, FAM_CLIMATE, k_ocean_band, g, WO_BLOCK, (const float*)Wb->lat, (const float*)Wb->lon, (const uint8_t*)B->isOcean, (const int32_t*)distW, (const int32_t*)distE,
            (const float*)B->itcz, ctl, P.coastThreshold, c4a, N);
     const O::Group<4>* cur = p->opt.oceanSplitSmooth ? ocean_smooth_split<4>(p, B->isOcean, c4a, P.currentPasses) : ocean_smooth<4>(p, B->isOcean, c4a, c4b, P.currentPasses);
-    launch(p, FAM_CLIMATE, k_ocean_speed, g, WO_BLOCK, cur, (const uint8_t*)B->isOcean, B->out[0], B->out[1], B->out[2], B->out[4], B->out[5], B->out[6], ctl->oceanCells, N);
+    float **S = B->out + ocean_field(0, 0), **Wn = B->out + ocean_field(1, 0);      // summer's four fields, winter's
+    launch(p, FAM_CLIMATE, k_ocean_speed, g, WO_BLOCK, cur, (const uint8_t*)B->isOcean, S[OF_EAST], S[OF_NORTH], S[OF_SPEED], Wn[OF_EAST], Wn[OF_NORTH], Wn[OF_SPEED], ctl->oceanCells, N);
     // percentile of the ocean speeds, both seasons
     for (int pass = 0; pass < W::SEL_PASSES; ++pass) {
-        launch(p, FAM_CLIMATE, k_ocean_sel_hist<OceanCtl>, 2 * blocks_for(N, 1024), WO_BLOCK, (const float*)B->out[2], (const float*)B->out[6], (const uint8_t*)B->isOcean, N, pass, ctl);
+        launch(p, FAM_CLIMATE, k_ocean_sel_hist<OceanCtl>, 2 * blocks_for(N, 1024), WO_BLOCK, (const float*)S[OF_SPEED], (const float*)Wn[OF_SPEED], (const uint8_t*)B->isOcean, N, pass, ctl);
         launch(p, FAM_CLIMATE, k_ocean_sel_pick<OceanCtl>, 2, 64, ctl, pass);
     }
     // warmth
     auto* w2a = (O::Group<2>*)B->group[0]; auto* w2b = (O::Group<2>*)B->group[1];
     launch(p, FAM_CLIMATE, k_ocean_warmth, g, WO_BLOCK, (const float*)Wb->lat, (const uint8_t*)B->isOcean, (const int32_t*)distW, (const int32_t*)distE, P.warmthRange, w2a, N);
     const O::Group<2>* warm = p->opt.oceanSplitSmooth ? ocean_smooth_split<2>(p, B->isOcean, w2a, P.warmthPasses) : ocean_smooth<2>(p, B->isOcean, w2a, w2b, P.warmthPasses);
-    launch(p, FAM_CLIMATE, k_ocean_finish, g, WO_BLOCK, B->out[2], B->out[6], warm, B->out[3], B->out[7], (const OceanCtl*)ctl, N);
+    launch(p, FAM_CLIMATE, k_ocean_finish, g, WO_BLOCK, S[OF_SPEED], Wn[OF_SPEED], warm, S[OF_WARMTH], Wn[OF_WARMTH], (const OceanCtl*)ctl, N);
     WO_HIP(hipMemcpyAsync(B->h_ctl, ctl, OCEAN_CTL_HEAD, hipMemcpyDeviceToHost, s));
     WO_HIP(hipStreamSynchronize(s));
     const OceanCtl& H = *B->h_ctl;
     B->info = wo_ocean_info{(int32_t)H.circ[0], (int32_t)H.circ[1], P.coastThreshold, P.warmthRange, P.currentPasses, P.warmthPasses,
                             {(int32_t)H.oceanCells[0], (int32_t)H.oceanCells[1]}, {H.p95[0], H.p95[1]}};
-    B->valid = true; B->have = 0xffu;
+    B->have = ocean_desc().all();
 }
 
 }  // namespace wo
@@ -277,14 +278,14 @@ static void ocean_run(wo_planet* p) {
 using namespace wo;
 
 // the reference's result keys in the order it sets them (js/ocean.js:374-377, summer then winter)
-static const char* const kOceanFields[8] = {"r_ocean_current_east_summer", "r_ocean_current_north_summer", "r_ocean_speed_summer", "r_ocean_warmth_summer",
+static const char* const kOceanFields[OF_COUNT] = {"r_ocean_current_east_summer", "r_ocean_current_north_summer", "r_ocean_speed_summer", "r_ocean_warmth_summer",
                                             "r_ocean_current_east_winter", "r_ocean_current_north_winter", "r_ocean_speed_winter", "r_ocean_warmth_winter"};
 // the fields of the wind block the stage reads
-static constexpr uint32_t kWindNeeded = (1u << WF_LAT) | (1u << WF_LON) | (1u << WF_ISLAND) | (7u << WF_FRAME0) | (7u << WF_ITCZ0);
-
-static int ocean_field_index(const char* name) {
-    for (int i = 0; i < 8; ++i) if (std::strcmp(name, kOceanFields[i]) == 0) return i;
-    return -1;
+static constexpr uint32_t kWindForOcean = bit(WF_LAT) | bit(WF_LON) | bit(WF_ISLAND) | (7u << WF_FRAME0) | WF_ITCZ_ALL;
+static StageBlock* ocean_of(const wo_planet* p) { return p->ocean; }
+const BlockDesc& wo::ocean_desc() {
+    static const BlockDesc D{"ocean", "wo_compute_ocean_currents", kOceanFields, OF_COUNT, ocean_of, ocean_alloc, out_slot<wo_ocean_block>};
+    return D;
 }
 
 extern "C" {
@@ -293,11 +294,7 @@ int wo_compute_ocean_currents(wo_planet* p, int32_t numRegions, wo_ocean_info* i
     if (!check_planet(p, "wo_compute_ocean_currents")) return 1;
     if (numRegions != p->N) { set_error("wo_compute_ocean_currents: numRegions is " + std::to_string(numRegions) + ", the planet has " + std::to_string(p->N)); return 1; }
     if (p->N >= (1 << O::FIELD_SHIFT)) { set_error("wo_compute_ocean_currents: the planet has 2^30 cells or more"); return 1; }
-    auto* Wb = p->wind;
-    if (!Wb || !(Wb->valid || (Wb->have & kWindNeeded) == kWindNeeded)) {
-        set_error("wo_compute_ocean_currents: no wind result on this planet (call wo_compute_wind first, or wo_wind_upload r_lat r_lon r_isLand r_eastX r_eastY r_eastZ itczLons itczLatsSummer itczLatsWinter)");
-        return 1;
-    }
+    if (!block_require(p, "wo_compute_ocean_currents", wind_desc(), kWindForOcean, "wo_wind_upload r_lat r_lon r_isLand r_eastX r_eastY r_eastZ itczLons itczLatsSummer itczLatsWinter")) return 1;
     WO_TRY
         ocean_alloc(p);
         ocean_run(p);
@@ -306,38 +303,7 @@ int wo_compute_ocean_currents(wo_planet* p, int32_t numRegions, wo_ocean_info* i
     WO_CATCH("wo_compute_ocean_currents")
 }
 
-int wo_ocean_download(wo_planet* p, const char* field, void* out, int64_t outBytes) {
-    if (!check_planet(p, "wo_ocean_download")) return 1;
-    if (!field || !out) { set_error("wo_ocean_download: null pointer"); return 1; }
-    auto* B = p->ocean;
-    if (!B || !(B->valid || B->have)) { set_error("wo_ocean_download: no ocean result on this planet (call wo_compute_ocean_currents first)"); return 1; }
-    const int f = ocean_field_index(field);
-    if (f < 0) { set_error(std::string("wo_ocean_download: unknown field '") + field + "'"); return 1; }
-    if (!B->valid && !((B->have >> f) & 1u)) { set_error(std::string("wo_ocean_download: no ocean result on this planet: ") + field + " was never set (call wo_compute_ocean_currents first)"); return 1; }
-    WO_TRY
-        const size_t bytes = (size_t)p->N * 4;
-        if (outBytes < (int64_t)bytes) { set_error(std::string("wo_ocean_download: ") + field + " needs " + std::to_string(bytes) + " bytes, out has " + std::to_string(outBytes)); return 1; }
-        WO_HIP(hipMemcpyAsync(out, B->out[f], bytes, hipMemcpyDeviceToHost, p->ctx->stream));
-        WO_HIP(hipStreamSynchronize(p->ctx->stream));
-        return 0;
-    WO_CATCH("wo_ocean_download")
-}
-
-int wo_ocean_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) {
-    if (!check_planet(p, "wo_ocean_upload")) return 1;
-    if (!field || !data) { set_error("wo_ocean_upload: null pointer"); return 1; }
-    const int f = ocean_field_index(field);
-    if (f < 0) { set_error(std::string("wo_ocean_upload: unknown field '") + field + "'"); return 1; }
-    WO_TRY
-        const size_t want = (size_t)p->N * 4;
-        if (bytes != (int64_t)want) { set_error(std::string("wo_ocean_upload: ") + field + " takes " + std::to_string(want) + " bytes, data has " + std::to_string(bytes)); return 1; }
-        ocean_alloc(p);
-        auto* B = p->ocean;
-        WO_HIP(hipMemcpyAsync(B->out[f], data, want, hipMemcpyHostToDevice, p->ctx->stream));
-        WO_HIP(hipStreamSynchronize(p->ctx->stream));         // `data` is the caller's, and pageable
-        B->have |= 1u << f;
-        return 0;
-    WO_CATCH("wo_ocean_upload")
-}
+int wo_ocean_download(wo_planet* p, const char* field, void* out, int64_t outBytes) { return block_download(p, "wo_ocean_download", ocean_desc(), field, out, outBytes); }
+int wo_ocean_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) { return block_upload(p, "wo_ocean_upload", ocean_desc(), field, data, bytes); }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 #include "../../include/worogen.h"
 #include "device.h"
 #include "ocean_ops.h"
+#include "stage_block.h"
 
 namespace O = wo::ocean;
 namespace W = wo::wind;
@@ -29,11 +30,8 @@ constexpr size_t OCEAN_CTL_HEAD = offsetof(OceanCtl, bins);
 }  // namespace wo
 
 // the ocean block of a planet
-struct wo_ocean_block {
-    wo::DeviceArena mem;                                      // owns every device and pinned buffer of the block
-    bool valid = false;                                       // a whole result of wo_compute_ocean_currents
-    uint32_t have = 0;                                        // bit f: out[f] was set, by wo_compute_ocean_currents or by wo_ocean_upload
-    float* out[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // per season: east, north, speed, warmth
+struct wo_ocean_block : wo::StageBlock {                      // have: bit f is out[f]
+    float* out[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // OceanField: per season east, north, speed, warmth
     uint8_t* isOcean = nullptr;
     void* group[2] = {nullptr, nullptr};                      // 16 bytes per cell each: frontiers (2 N entries), float4 currents, float2 warmths
     float* itcz = nullptr;                                    // 2 x 360: itczLatsSummer, itczLatsWinter
@@ -42,6 +40,12 @@ struct wo_ocean_block {
     wo_ocean_info info{};
 };
 namespace wo {
+
+// the fields of the block by the reference's result keys, in the order it sets them (js/ocean.js:374-377): summer's four, then winter's
+enum OceanField : int { OF_EAST = 0, OF_NORTH, OF_SPEED, OF_WARMTH, OF_STRIDE, OF_COUNT = 2 * OF_STRIDE };
+constexpr int ocean_field(int season, int f) { return OF_STRIDE * season + f; }
+constexpr uint32_t ocean_both(int f) { return bit(ocean_field(0, f)) | bit(ocean_field(1, f)); }      // field f of both seasons
+const BlockDesc& ocean_desc();                                // ocean.hip: the block's descriptor
 
 // ocean.hip: allocates the planet's ocean block if there is none
 void ocean_alloc(wo_planet* p);

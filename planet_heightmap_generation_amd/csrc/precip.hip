@@ -223,18 +223,16 @@ static void precip_run(wo_planet* p, const float* r_elevation, double precipitat
     const int32_t N = p->N, g = blocks_for(N), tile = xcd_tile(N), xg = xcd_grid(N);
     const size_t n = (size_t)N, E = (size_t)p->E;
     hipStream_t s = p->ctx->stream;
-    B->valid = false; B->have = 0;
+    B->have = 0;
     const P::Params Q = P::params_for(N);
     const int32_t* off = p->d_off; const int32_t* adj = p->d_adj; const float* xyz = p->d_xyz;
     const uint8_t* isLand = Wb->isLand;
     DeviceArena T;                                            // the temporaries of this call
     PrecipCtl* ctl = B->ctl;
     WO_HIP(hipMemsetAsync(ctl, 0, sizeof(PrecipCtl), s));
-    WO_HIP(hipMemcpyAsync(B->itcz, Wb->itcz[1], sizeof(float) * 2 * W::ITCZ_SAMPLES, hipMemcpyHostToDevice, s));      // itczLatsSummer and itczLatsWinter lie one after the other; the wind block outlives the copy
+    stage_itcz(p, B->itcz);
     // the elevation, its smoothed blend and that field's gradient, the heights
-    float* e = T.dev<float>(n);
-    if (r_elevation) WO_HIP(hipMemcpyAsync(e, r_elevation, n * 4, hipMemcpyHostToDevice, s));
-    else WO_HIP(hipMemcpyAsync(e, p->d_e, n * 4, hipMemcpyDeviceToDevice, s));
+    const float* e = stage_elevation(p, T, r_elevation);
     float *sa = T.dev<float>(n), *sb = T.dev<float>(n);      // smoothing scratch
     float *es = T.dev<float>(n), *gradE = T.dev<float>(n), *gradN = T.dev<float>(n), *heightKm = T.dev<float>(n);
     WO_HIP(hipMemcpyAsync(sa, e, n * 4, hipMemcpyDeviceToDevice, s));
@@ -253,7 +251,7 @@ static void precip_run(wo_planet* p, const float* r_elevation, double precipitat
     for (int k = 0; k < 2; ++k) {
         wind_convergence_resident(p, wind[k].x, wind[k].y, wind[k].z, conv[k]);
         smooth_swap(p, conv[k], sa, Q.convSmoothPasses);
-        float* r = advect_moisture_resident(p, heightKm, isLand, wind[k].e, wind[k].n, wind[k].x, wind[k].y, wind[k].z, Ob->out[4 * k + 3], Wb->coastDist, Q.maxHops,
+        float* r = advect_moisture_resident(p, heightKm, isLand, wind[k].e, wind[k].n, wind[k].x, wind[k].y, wind[k].z, Ob->out[ocean_field(k, OF_WARMTH)], Wb->coastDist, Q.maxHops,
                                             Q.depletionBase, moist[k], sa);
         if (r != moist[k]) std::swap(moist[k], sa);
     }
@@ -279,12 +277,13 @@ static void precip_run(wo_planet* p, const float* r_elevation, double precipitat
         launch(p, FAM_CLIMATE, k_precip_propagate<false>, xg, WO_BLOCK, tile, off, adj, (const G2*)dn, windward, dst, 1 - Q.windwardDecay, N);
         windward = dst;
     }
-    launch(p, FAM_CLIMATE, k_precip_merge, g, WO_BLOCK, (const G2*)seed, shadow, windward, B->out[2], B->out[3], N);
+    float **rain = B->out + PF_PRECIP0, **rs = B->out + PF_SHADOW0;      // both seasons of r_precip_*, of r_rainshadow_*
+    launch(p, FAM_CLIMATE, k_precip_merge, g, WO_BLOCK, (const G2*)seed, shadow, windward, rs[0], rs[1], N);
     for (int k = 0; k < 2; ++k) {
-        float* r = smooth_field_resident(p, B->out[2 + k], sa, Q.rsSmoothPasses);
-        if (r != B->out[2 + k]) WO_HIP(hipMemcpyAsync(B->out[2 + k], r, n * 4, hipMemcpyDeviceToDevice, s));
+        float* r = smooth_field_resident(p, rs[k], sa, Q.rsSmoothPasses);
+        if (r != rs[k]) WO_HIP(hipMemcpyAsync(rs[k], r, n * 4, hipMemcpyDeviceToDevice, s));
     }
-    launch(p, FAM_CLIMATE, k_precip_apply, g, WO_BLOCK, isLand, precip[0], precip[1], (const float*)B->out[2], (const float*)B->out[3], N);
+    launch(p, FAM_CLIMATE, k_precip_apply, g, WO_BLOCK, isLand, precip[0], precip[1], (const float*)rs[0], (const float*)rs[1], N);
     for (int k = 0; k < 2; ++k) smooth_swap(p, precip[k], sa, Q.precipSmoothPasses);
     // the heuristic model (the convergence and moisture buffers are free by now)
     float *wc = conv[0], *wcTmp = conv[1];
@@ -299,13 +298,12 @@ static void precip_run(wo_planet* p, const float* r_elevation, double precipitat
            (const float*)gradE, (const float*)gradN, (const float*)wc, (const int32_t*)Wb->coastDist, Q.avgEdgeKm, heur[0], heur[1], N);
     for (int k = 0; k < 2; ++k) smooth_swap(p, heur[k], sa, Q.precipSmoothPasses);
     // blend, percentile, normalise
-    launch(p, FAM_CLIMATE, k_precip_blend, g, WO_BLOCK, (const float*)precip[0], (const float*)precip[1], (const float*)heur[0], (const float*)heur[1], B->out[0], B->out[1],
-           ctl, N);
+    launch(p, FAM_CLIMATE, k_precip_blend, g, WO_BLOCK, (const float*)precip[0], (const float*)precip[1], (const float*)heur[0], (const float*)heur[1], rain[0], rain[1], ctl, N);
     for (int pass = 0; pass < W::SEL_PASSES; ++pass) {
-        launch(p, FAM_CLIMATE, k_ocean_sel_hist<PrecipCtl>, 2 * blocks_for(N, 1024), WO_BLOCK, (const float*)B->out[0], (const float*)B->out[1], (const uint8_t*)nullptr, N, pass, ctl);
+        launch(p, FAM_CLIMATE, k_ocean_sel_hist<PrecipCtl>, 2 * blocks_for(N, 1024), WO_BLOCK, (const float*)rain[0], (const float*)rain[1], (const uint8_t*)nullptr, N, pass, ctl);
         launch(p, FAM_CLIMATE, k_ocean_sel_pick<PrecipCtl>, 2, 64, ctl, pass);
     }
-    launch(p, FAM_CLIMATE, k_precip_finish, g, WO_BLOCK, B->out[0], B->out[1], isLand, (const float*)Wb->cont, (const PrecipCtl*)ctl, N);
+    launch(p, FAM_CLIMATE, k_precip_finish, g, WO_BLOCK, rain[0], rain[1], isLand, (const float*)Wb->cont, (const PrecipCtl*)ctl, N);
     WO_HIP(hipMemcpyAsync(B->h_ctl, ctl, PRECIP_CTL_HEAD, hipMemcpyDeviceToHost, s));
     WO_HIP(hipStreamSynchronize(s));                          // also before T frees the temporaries
     const PrecipCtl& H = *B->h_ctl;
@@ -316,7 +314,7 @@ static void precip_run(wo_planet* p, const float* r_elevation, double precipitat
     I.depletionBase = Q.depletionBase; I.shadowDecay = Q.shadowDecay; I.windwardDecay = Q.windwardDecay;
     I.p95[0] = H.p95[0]; I.p95[1] = H.p95[1];
     B->info = I;
-    B->valid = true; B->have = 0xfu;
+    B->have = precip_desc().all();
 }
 
 }  // namespace wo
@@ -324,14 +322,15 @@ static void precip_run(wo_planet* p, const float* r_elevation, double precipitat
 using namespace wo;
 
 // the reference's result keys (js/precipitation.js:640-641, :678)
-static const char* const kPrecipFields[4] = {"r_precip_summer", "r_precip_winter", "r_rainshadow_summer", "r_rainshadow_winter"};
+static const char* const kPrecipFields[PF_COUNT] = {"r_precip_summer", "r_precip_winter", "r_rainshadow_summer", "r_rainshadow_winter"};
 // the fields of the wind block the stage reads: pressure, east and north wind of both seasons, the ITCZ arrays, the geography
-static constexpr uint32_t kWindNeeded = 0x77u | (7u << WF_ITCZ0) | (1u << WF_LAT) | (1u << WF_LON) | (1u << WF_ISLAND) | (1u << WF_CONT) | (1u << WF_COASTDIST) | (63u << WF_FRAME0);
-static constexpr uint32_t kOceanNeeded = (1u << 3) | (1u << 7);      // r_ocean_warmth_summer, r_ocean_warmth_winter
-
-static int precip_field_index(const char* name) {
-    for (int i = 0; i < 4; ++i) if (std::strcmp(name, kPrecipFields[i]) == 0) return i;
-    return -1;
+static constexpr uint32_t kWindForPrecip = wind_both(WS_PRESSURE) | wind_both(WS_EAST) | wind_both(WS_NORTH) | WF_ITCZ_ALL | bit(WF_LAT) | bit(WF_LON) | bit(WF_ISLAND) |
+                                           bit(WF_CONT) | bit(WF_COASTDIST) | (63u << WF_FRAME0);
+static constexpr uint32_t kOceanForPrecip = ocean_both(OF_WARMTH);      // r_ocean_warmth_summer, r_ocean_warmth_winter
+static StageBlock* precip_of(const wo_planet* p) { return p->precip; }
+const BlockDesc& wo::precip_desc() {
+    static const BlockDesc D{"precipitation", "wo_compute_precipitation", kPrecipFields, PF_COUNT, precip_of, precip_alloc, out_slot<wo_precip_block>};
+    return D;
 }
 
 extern "C" {
@@ -340,17 +339,10 @@ int wo_compute_precipitation(wo_planet* p, int32_t numRegions, const float* r_el
     if (!check_planet(p, "wo_compute_precipitation")) return 1;
     if (numRegions != p->N) { set_error("wo_compute_precipitation: numRegions is " + std::to_string(numRegions) + ", the planet has " + std::to_string(p->N)); return 1; }
     if (!(precipitationOffset == precipitationOffset) || !(landCoverage == landCoverage)) { set_error("wo_compute_precipitation: precipitationOffset or landCoverage is NaN"); return 1; }
-    auto* Wb = p->wind;
-    if (!Wb || !(Wb->valid || (Wb->have & kWindNeeded) == kWindNeeded)) {
-        set_error("wo_compute_precipitation: no wind result on this planet (call wo_compute_wind first, or wo_wind_upload r_lat r_lon r_isLand r_continentality r_coastDistLand, "
-                  "the six frame arrays, the three ITCZ arrays and r_wind_east_* r_wind_north_* r_pressure_* of both seasons)");
-        return 1;
-    }
-    auto* Ob = p->ocean;
-    if (!Ob || !(Ob->valid || (Ob->have & kOceanNeeded) == kOceanNeeded)) {
-        set_error("wo_compute_precipitation: no ocean result on this planet (call wo_compute_ocean_currents first, or wo_ocean_upload r_ocean_warmth_summer r_ocean_warmth_winter)");
-        return 1;
-    }
+    if (!block_require(p, "wo_compute_precipitation", wind_desc(), kWindForPrecip,
+                       "wo_wind_upload r_lat r_lon r_isLand r_continentality r_coastDistLand, the six frame arrays, the three ITCZ arrays and r_wind_east_* r_wind_north_* "
+                       "r_pressure_* of both seasons")) return 1;
+    if (!block_require(p, "wo_compute_precipitation", ocean_desc(), kOceanForPrecip, "wo_ocean_upload r_ocean_warmth_summer r_ocean_warmth_winter")) return 1;
     WO_TRY
         precip_alloc(p);
         precip_run(p, r_elevation, precipitationOffset, landCoverage);
@@ -359,38 +351,7 @@ int wo_compute_precipitation(wo_planet* p, int32_t numRegions, const float* r_el
     WO_CATCH("wo_compute_precipitation")
 }
 
-int wo_precip_download(wo_planet* p, const char* field, void* out, int64_t outBytes) {
-    if (!check_planet(p, "wo_precip_download")) return 1;
-    if (!field || !out) { set_error("wo_precip_download: null pointer"); return 1; }
-    auto* B = p->precip;
-    if (!B || !(B->valid || B->have)) { set_error("wo_precip_download: no precipitation result on this planet (call wo_compute_precipitation first)"); return 1; }
-    const int f = precip_field_index(field);
-    if (f < 0) { set_error(std::string("wo_precip_download: unknown field '") + field + "'"); return 1; }
-    if (!B->valid && !((B->have >> f) & 1u)) { set_error(std::string("wo_precip_download: no precipitation result on this planet: ") + field + " was never set (call wo_compute_precipitation first)"); return 1; }
-    WO_TRY
-        const size_t bytes = (size_t)p->N * 4;
-        if (outBytes < (int64_t)bytes) { set_error(std::string("wo_precip_download: ") + field + " needs " + std::to_string(bytes) + " bytes, out has " + std::to_string(outBytes)); return 1; }
-        WO_HIP(hipMemcpyAsync(out, B->out[f], bytes, hipMemcpyDeviceToHost, p->ctx->stream));
-        WO_HIP(hipStreamSynchronize(p->ctx->stream));
-        return 0;
-    WO_CATCH("wo_precip_download")
-}
-
-int wo_precip_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) {
-    if (!check_planet(p, "wo_precip_upload")) return 1;
-    if (!field || !data) { set_error("wo_precip_upload: null pointer"); return 1; }
-    const int f = precip_field_index(field);
-    if (f < 0) { set_error(std::string("wo_precip_upload: unknown field '") + field + "'"); return 1; }
-    WO_TRY
-        const size_t want = (size_t)p->N * 4;
-        if (bytes != (int64_t)want) { set_error(std::string("wo_precip_upload: ") + field + " takes " + std::to_string(want) + " bytes, data has " + std::to_string(bytes)); return 1; }
-        precip_alloc(p);
-        auto* B = p->precip;
-        WO_HIP(hipMemcpyAsync(B->out[f], data, want, hipMemcpyHostToDevice, p->ctx->stream));
-        WO_HIP(hipStreamSynchronize(p->ctx->stream));         // `data` is the caller's, and pageable
-        B->have |= 1u << f;
-        return 0;
-    WO_CATCH("wo_precip_upload")
-}
+int wo_precip_download(wo_planet* p, const char* field, void* out, int64_t outBytes) { return block_download(p, "wo_precip_download", precip_desc(), field, out, outBytes); }
+int wo_precip_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) { return block_upload(p, "wo_precip_upload", precip_desc(), field, data, bytes); }
 
 }  // extern "C"

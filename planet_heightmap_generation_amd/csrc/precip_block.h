@@ -24,13 +24,17 @@ __device__ inline uint32_t sel_count(const PrecipCtl* c, int season) { return c-
 }  // namespace wo
 
 // the precipitation block of a planet
-struct wo_precip_block {
-    wo::DeviceArena mem;                                      // owns every device and pinned buffer of the block
-    bool valid = false;                                       // a whole result of wo_compute_precipitation
-    uint32_t have = 0;                                        // bit f: out[f] was set, by wo_compute_precipitation or by wo_precip_upload
-    float* out[4] = {nullptr, nullptr, nullptr, nullptr};     // r_precip_summer, r_precip_winter, r_rainshadow_summer, r_rainshadow_winter
+struct wo_precip_block : wo::StageBlock {                     // have: bit f is out[f]
+    float* out[4] = {nullptr, nullptr, nullptr, nullptr};     // PrecipField
     float* itcz = nullptr;                                    // 2 x 360: itczLatsSummer, itczLatsWinter
     wo::PrecipCtl* ctl = nullptr;
     wo::PrecipCtl* h_ctl = nullptr;                           // pinned: the head of ctl
     wo_precip_info info{};
 };
+
+namespace wo {
+// the fields of the block by the reference's result keys (js/precipitation.js:640-641, :678); + season
+enum PrecipField : int { PF_PRECIP0 = 0, PF_SHADOW0 = 2, PF_COUNT = 4 };
+constexpr uint32_t PF_PRECIP_BOTH = bit(PF_PRECIP0) | bit(PF_PRECIP0 + 1);      // r_precip_summer, r_precip_winter
+const BlockDesc& precip_desc();                               // precip.hip: the block's descriptor
+}  // namespace wo

@@ -30,12 +30,14 @@
 
 namespace Tm = wo::temp;
 
+namespace wo {
+// the fields of the temperature block by the reference's result keys (js/temperature.js:232)
+enum TempField : int { TF_SUMMER = 0, TF_WINTER, TF_COUNT };
+}  // namespace wo
+
 // the temperature block and the Koppen block of a planet
-struct wo_temp_block {
-    wo::DeviceArena mem;                                      // owns the two fields
-    bool valid = false;                                       // a whole result of wo_compute_temperature
-    uint32_t have = 0;                                        // bit f: out[f] was set, by wo_compute_temperature or by wo_temperature_upload
-    float* out[2] = {nullptr, nullptr};                       // r_temperature_summer, r_temperature_winter
+struct wo_temp_block : wo::StageBlock {                       // have: bit f is out[f]
+    float* out[wo::TF_COUNT] = {nullptr, nullptr};            // TempField
     wo_temperature_info info{};
 };
 struct wo_koppen_block {
@@ -53,7 +55,7 @@ struct TempArgs {
     const uint8_t* isLand;
     const float *precip[2], *warmth[2], *speed[2];
     const G2* coastal;
-    float* out[2];
+    float* out[TF_COUNT];
 };
 
 __global__ __launch_bounds__(WO_BLOCK) void k_temp_seed(const float* __restrict__ warmS, const float* __restrict__ warmW, const uint8_t* __restrict__ isLand,
@@ -114,16 +116,15 @@ static void temp_alloc(wo_planet* p) {
     p->temp = block.release();
 }
 
+static const char* const kTempFields[TF_COUNT] = {"r_temperature_summer", "r_temperature_winter"};
+static StageBlock* temp_of(const wo_planet* p) { return p->temp; }
+static const BlockDesc kTempBlock{"temperature", "wo_compute_temperature", kTempFields, TF_COUNT, temp_of, temp_alloc, out_slot<wo_temp_block>};
+
 static void koppen_alloc(wo_planet* p) {
     if (p->koppen) return;
     std::unique_ptr<wo_koppen_block> block(new wo_koppen_block());
     block->cls = block->mem.dev<uint8_t>((size_t)p->N);
     p->koppen = block.release();
-}
-
-// the elevation a stage reads: the caller's, uploaded into the call's arena, or the resident field
-static const float* stage_elevation(wo_planet* p, DeviceArena& T, const float* r_elevation) {
-    return r_elevation ? up(T, r_elevation, (size_t)p->N, p->ctx->stream) : p->d_e;
 }
 
 static void temp_run(wo_planet* p, const float* r_elevation, double temperatureOffset) {
@@ -134,14 +135,14 @@ static void temp_run(wo_planet* p, const float* r_elevation, double temperatureO
     const int32_t N = p->N, g = blocks_for(N), tile = xcd_tile(N), xg = xcd_grid(N);
     const size_t n = (size_t)N;
     hipStream_t s = p->ctx->stream;
-    B->valid = false; B->have = 0;
+    B->have = 0;
     const int32_t passes = Tm::warmth_passes(N);
     DeviceArena T;                                            // the temporaries of this call
     float* itcz = T.dev<float>((size_t)2 * W::ITCZ_SAMPLES);
-    WO_HIP(hipMemcpyAsync(itcz, Wb->itcz[1], sizeof(float) * 2 * W::ITCZ_SAMPLES, hipMemcpyHostToDevice, s));      // itczLatsSummer and itczLatsWinter lie one after the other; the wind block outlives the copy
+    stage_itcz(p, itcz);
     const float* e = stage_elevation(p, T, r_elevation);
-    const float* warm[2] = {Ob->out[3], Ob->out[7]};
-    const float* speed[2] = {Ob->out[2], Ob->out[6]};
+    const float* warm[2] = {Ob->out[ocean_field(0, OF_WARMTH)], Ob->out[ocean_field(1, OF_WARMTH)]};
+    const float* speed[2] = {Ob->out[ocean_field(0, OF_SPEED)], Ob->out[ocean_field(1, OF_SPEED)]};
     // diffuseOceanWarmth of both seasons
     G2* pair[2] = {T.dev<G2>(n), T.dev<G2>(n)};
     const G2* coastal;
@@ -164,30 +165,22 @@ static void temp_run(wo_planet* p, const float* r_elevation, double temperatureO
     }
     // the per-cell loop, then the smoothing pass with the normalisation
     float* raw[2] = {T.dev<float>(n), T.dev<float>(n)};
-    const TempArgs A{Wb->lat, Wb->lon, e, Wb->cont, Wb->plateCont, Wb->isLand, {Pb->out[0], Pb->out[1]}, {warm[0], warm[1]}, {speed[0], speed[1]}, coastal, {raw[0], raw[1]}};
+    const TempArgs A{Wb->lat, Wb->lon, e, Wb->cont, Wb->plateCont, Wb->isLand, {Pb->out[PF_PRECIP0], Pb->out[PF_PRECIP0 + 1]}, {warm[0], warm[1]}, {speed[0], speed[1]}, coastal, {raw[0], raw[1]}};
     launch(p, FAM_CLIMATE, k_temp_cell, g, WO_BLOCK, A, (const float*)itcz, temperatureOffset, N);
-    launch(p, FAM_CLIMATE, k_temp_smooth, xg, WO_BLOCK, p->fields(), (const float*)raw[0], (const float*)raw[1], B->out[0], B->out[1]);
+    launch(p, FAM_CLIMATE, k_temp_smooth, xg, WO_BLOCK, p->fields(), (const float*)raw[0], (const float*)raw[1], B->out[TF_SUMMER], B->out[TF_WINTER]);
     WO_HIP(hipStreamSynchronize(s));                          // before T frees the temporaries
     B->info = wo_temperature_info{passes, Tm::SMOOTH_PASSES, launches + 2, 0};
-    B->valid = true; B->have = 3u;
+    B->have = kTempBlock.all();
 }
 
 }  // namespace wo
 
 using namespace wo;
 
-// the reference's result keys (js/temperature.js:232)
-static const char* const kTempFields[2] = {"r_temperature_summer", "r_temperature_winter"};
 // the fields of the wind, ocean and precipitation blocks the stages read
-static constexpr uint32_t kWindNeeded = (7u << WF_ITCZ0) | (1u << WF_LAT) | (1u << WF_LON) | (1u << WF_ISLAND) | (1u << WF_CONT) | (1u << WF_PLATECONT);
-static constexpr uint32_t kOceanNeeded = (1u << 2) | (1u << 3) | (1u << 6) | (1u << 7);      // r_ocean_speed_* and r_ocean_warmth_* of both seasons
-static constexpr uint32_t kPrecipNeeded = 3u;                                              // r_precip_summer, r_precip_winter
-
-static int temp_field_index(const char* name) {
-    for (int i = 0; i < 2; ++i) if (std::strcmp(name, kTempFields[i]) == 0) return i;
-    return -1;
-}
-static bool precip_ready(const wo_planet* p) { return p->precip && (p->precip->valid || (p->precip->have & kPrecipNeeded) == kPrecipNeeded); }
+static constexpr uint32_t kWindForTemp = WF_ITCZ_ALL | bit(WF_LAT) | bit(WF_LON) | bit(WF_ISLAND) | bit(WF_CONT) | bit(WF_PLATECONT);
+static constexpr uint32_t kOceanForTemp = ocean_both(OF_SPEED) | ocean_both(OF_WARMTH);      // r_ocean_speed_* and r_ocean_warmth_* of both seasons
+static bool precip_ready(const wo_planet* p, const char* fn) { return block_require(p, fn, precip_desc(), PF_PRECIP_BOTH, "wo_precip_upload r_precip_summer r_precip_winter"); }
 
 extern "C" {
 
@@ -195,21 +188,9 @@ int wo_compute_temperature(wo_planet* p, int32_t numRegions, const float* r_elev
     if (!check_planet(p, "wo_compute_temperature")) return 1;
     if (numRegions != p->N) { set_error("wo_compute_temperature: numRegions is " + std::to_string(numRegions) + ", the planet has " + std::to_string(p->N)); return 1; }
     if (!(temperatureOffset == temperatureOffset)) { set_error("wo_compute_temperature: temperatureOffset is NaN"); return 1; }
-    auto* Wb = p->wind;
-    if (!Wb || !(Wb->valid || (Wb->have & kWindNeeded) == kWindNeeded)) {
-        set_error("wo_compute_temperature: no wind result on this planet (call wo_compute_wind first, or wo_wind_upload r_lat r_lon r_isLand r_continentality "
-                  "r_plateContinentality and the three ITCZ arrays)");
-        return 1;
-    }
-    auto* Ob = p->ocean;
-    if (!Ob || !(Ob->valid || (Ob->have & kOceanNeeded) == kOceanNeeded)) {
-        set_error("wo_compute_temperature: no ocean result on this planet (call wo_compute_ocean_currents first, or wo_ocean_upload r_ocean_warmth_* and r_ocean_speed_* of both seasons)");
-        return 1;
-    }
-    if (!precip_ready(p)) {
-        set_error("wo_compute_temperature: no precipitation result on this planet (call wo_compute_precipitation first, or wo_precip_upload r_precip_summer r_precip_winter)");
-        return 1;
-    }
+    if (!block_require(p, "wo_compute_temperature", wind_desc(), kWindForTemp, "wo_wind_upload r_lat r_lon r_isLand r_continentality r_plateContinentality and the three ITCZ arrays")) return 1;
+    if (!block_require(p, "wo_compute_temperature", ocean_desc(), kOceanForTemp, "wo_ocean_upload r_ocean_warmth_* and r_ocean_speed_* of both seasons")) return 1;
+    if (!precip_ready(p, "wo_compute_temperature")) return 1;
     WO_TRY
         temp_alloc(p);
         temp_run(p, r_elevation, temperatureOffset);
@@ -219,59 +200,24 @@ int wo_compute_temperature(wo_planet* p, int32_t numRegions, const float* r_elev
 }
 
 int wo_temperature_download(wo_planet* p, const char* field, void* out, int64_t outBytes) {
-    if (!check_planet(p, "wo_temperature_download")) return 1;
-    if (!field || !out) { set_error("wo_temperature_download: null pointer"); return 1; }
-    auto* B = p->temp;
-    if (!B || !(B->valid || B->have)) { set_error("wo_temperature_download: no temperature result on this planet (call wo_compute_temperature first)"); return 1; }
-    const int f = temp_field_index(field);
-    if (f < 0) { set_error(std::string("wo_temperature_download: unknown field '") + field + "'"); return 1; }
-    if (!B->valid && !((B->have >> f) & 1u)) { set_error(std::string("wo_temperature_download: no temperature result on this planet: ") + field + " was never set (call wo_compute_temperature first)"); return 1; }
-    WO_TRY
-        const size_t bytes = (size_t)p->N * 4;
-        if (outBytes < (int64_t)bytes) { set_error(std::string("wo_temperature_download: ") + field + " needs " + std::to_string(bytes) + " bytes, out has " + std::to_string(outBytes)); return 1; }
-        WO_HIP(hipMemcpyAsync(out, B->out[f], bytes, hipMemcpyDeviceToHost, p->ctx->stream));
-        WO_HIP(hipStreamSynchronize(p->ctx->stream));
-        return 0;
-    WO_CATCH("wo_temperature_download")
+    return block_download(p, "wo_temperature_download", kTempBlock, field, out, outBytes);
 }
-
-int wo_temperature_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) {
-    if (!check_planet(p, "wo_temperature_upload")) return 1;
-    if (!field || !data) { set_error("wo_temperature_upload: null pointer"); return 1; }
-    const int f = temp_field_index(field);
-    if (f < 0) { set_error(std::string("wo_temperature_upload: unknown field '") + field + "'"); return 1; }
-    WO_TRY
-        const size_t want = (size_t)p->N * 4;
-        if (bytes != (int64_t)want) { set_error(std::string("wo_temperature_upload: ") + field + " takes " + std::to_string(want) + " bytes, data has " + std::to_string(bytes)); return 1; }
-        temp_alloc(p);
-        auto* B = p->temp;
-        WO_HIP(hipMemcpyAsync(B->out[f], data, want, hipMemcpyHostToDevice, p->ctx->stream));
-        WO_HIP(hipStreamSynchronize(p->ctx->stream));         // `data` is the caller's, and pageable
-        B->valid = false; B->have |= 1u << f;
-        return 0;
-    WO_CATCH("wo_temperature_upload")
-}
+int wo_temperature_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) { return block_upload(p, "wo_temperature_upload", kTempBlock, field, data, bytes); }
 
 int wo_classify_koppen(wo_planet* p, int32_t numRegions, const float* r_elevation) {
     if (!check_planet(p, "wo_classify_koppen")) return 1;
     if (numRegions != p->N) { set_error("wo_classify_koppen: numRegions is " + std::to_string(numRegions) + ", the planet has " + std::to_string(p->N)); return 1; }
+    if (!block_require(p, "wo_classify_koppen", kTempBlock, kTempBlock.all(), "wo_temperature_upload r_temperature_summer r_temperature_winter")) return 1;
+    if (!precip_ready(p, "wo_classify_koppen")) return 1;
     auto* Tb = p->temp;
-    if (!Tb || !(Tb->valid || Tb->have == 3u)) {
-        set_error("wo_classify_koppen: no temperature result on this planet (call wo_compute_temperature first, or wo_temperature_upload r_temperature_summer r_temperature_winter)");
-        return 1;
-    }
-    if (!precip_ready(p)) {
-        set_error("wo_classify_koppen: no precipitation result on this planet (call wo_compute_precipitation first, or wo_precip_upload r_precip_summer r_precip_winter)");
-        return 1;
-    }
     WO_TRY
         koppen_alloc(p);
         auto* K = p->koppen;
         K->valid = false;
         DeviceArena T;
         const float* e = stage_elevation(p, T, r_elevation);
-        launch(p, FAM_CLIMATE, k_koppen, blocks_for(p->N), WO_BLOCK, e, (const float*)Tb->out[0], (const float*)Tb->out[1], (const float*)p->precip->out[0],
-               (const float*)p->precip->out[1], K->cls, p->N);
+        launch(p, FAM_CLIMATE, k_koppen, blocks_for(p->N), WO_BLOCK, e, (const float*)Tb->out[TF_SUMMER], (const float*)Tb->out[TF_WINTER], (const float*)p->precip->out[PF_PRECIP0],
+               (const float*)p->precip->out[PF_PRECIP0 + 1], K->cls, p->N);
         WO_HIP(hipStreamSynchronize(p->ctx->stream));         // before T frees the uploaded elevation
         K->valid = true;
         return 0;

@@ -230,6 +230,10 @@ void wind_alloc(wo_planet* p) {
 
 void wind_free(wo_planet* p) { delete p->wind; p->wind = nullptr; }
 
+void stage_itcz(wo_planet* p, float* dst) {
+    WO_HIP(hipMemcpyAsync(dst, p->wind->itcz[1], sizeof(float) * 2 * W::ITCZ_SAMPLES, hipMemcpyHostToDevice, p->ctx->stream));
+}
+
 // computeGradients on a device-resident field (precip.hip)
 void gradient_resident(wo_planet* p, const float* field, const W::Frames& T, float* gradE, float* gradN) {
     launch(p, FAM_CLIMATE, k_wind_gradient, blocks_for(p->N), WO_BLOCK, (const int32_t*)p->d_off, (const int32_t*)p->d_adj, (const float*)p->d_xyz, field, T, gradE, gradN, p->N);
@@ -261,7 +265,7 @@ static void wind_run(wo_planet* p, double seed) {
     auto* B = p->wind;
     const int32_t N = p->N, g = blocks_for(N);
     hipStream_t s = p->ctx->stream;
-    B->valid = false; B->have = 0;
+    B->have = 0;
     // step 0 and the geo index
     W::CellGeo G{B->lat, B->lon, B->sinLat, B->cosLat, B->isLand, B->frame[0], B->frame[1], B->frame[2], B->frame[3], B->frame[4], B->frame[5]};
     launch(p, FAM_CLIMATE, k_wind_precompute, g, WO_BLOCK, (const float*)p->d_xyz, (const float*)B->e, G, B->keys[0], B->vals[0], N);
@@ -316,7 +320,7 @@ static void wind_run(wo_planet* p, double seed) {
         launch(p, FAM_CLIMATE, k_wind_finish, g, WO_BLOCK, out[3], (const float*)B->maxSpeed, pressure, out[0], N);
     }
     WO_HIP(hipStreamSynchronize(s));                                        // sel0 is read by the copies above
-    B->valid = true; B->have = WF_ALL;
+    B->have = wind_desc().all();
 }
 
 }  // namespace wo
@@ -329,9 +333,23 @@ static const char* const kWindFields[WF_COUNT] = {
     "r_pressure_winter", "r_wind_east_winter", "r_wind_north_winter", "r_wind_speed_winter",
     "itczLons", "itczLatsSummer", "itczLatsWinter", "r_lat", "r_lon", "r_sinLat", "r_isLand",
     "r_continentality", "r_coastDistLand", "r_plateContinentality", "r_eastX", "r_eastY", "r_eastZ", "r_northX", "r_northY", "r_northZ"};
-static int wind_field_index(const char* name) {
-    for (int i = 0; i < WF_COUNT; ++i) if (std::strcmp(name, kWindFields[i]) == 0) return i;
-    return -1;
+// where field f lives and how large it is (the ITCZ arrays are host arrays of the block)
+static Slot wind_slot(StageBlock* b, int f, size_t N) {
+    auto* B = static_cast<wo_wind_block*>(b);
+    if (f >= WF_ITCZ0 && f < WF_LAT) return Slot{B->itcz[f - WF_ITCZ0], sizeof(float) * W::ITCZ_SAMPLES, true};
+    if (f < WF_ITCZ0) return Slot{B->season[f / WS_STRIDE][f % WS_STRIDE], N * 4, false};
+    switch (f) {
+        case WF_LAT: return Slot{B->lat, N * 4, false};             case WF_LON: return Slot{B->lon, N * 4, false};
+        case WF_SINLAT: return Slot{B->sinLat, N * 4, false};       case WF_ISLAND: return Slot{B->isLand, N, false};
+        case WF_CONT: return Slot{B->cont, N * 4, false};           case WF_COASTDIST: return Slot{B->coastDist, N * 4, false};
+        case WF_PLATECONT: return Slot{B->plateCont, N * 4, false};
+        default: return Slot{B->frame[f - WF_FRAME0], N * 4, false};
+    }
+}
+static StageBlock* wind_of(const wo_planet* p) { return p->wind; }
+const BlockDesc& wo::wind_desc() {
+    static const BlockDesc D{"wind", "wo_compute_wind", kWindFields, WF_COUNT, wind_of, wind_alloc, wind_slot};
+    return D;
 }
 
 extern "C" {
@@ -346,7 +364,7 @@ int wo_compute_wind(wo_planet* p, int32_t numRegions, const float* r_elevation, 
     WO_TRY
         wind_alloc(p);
         auto* B = p->wind;
-        B->valid = false; B->have = 0;
+        B->have = 0;
         hipStream_t s = p->ctx->stream;
         const size_t N = (size_t)p->N;
         std::vector<int32_t> ids(oceanPlates, oceanPlates + nOceanPlates);
@@ -366,59 +384,8 @@ int wo_compute_wind(wo_planet* p, int32_t numRegions, const float* r_elevation, 
     WO_CATCH("wo_compute_wind")
 }
 
-// where field f lives and how large it is (the ITCZ arrays are host arrays of the block)
-static void* wind_field_ptr(wo_wind_block* B, int f, size_t N, size_t* bytes) {
-    const bool itcz = f >= WF_ITCZ0 && f < WF_LAT;
-    *bytes = itcz ? sizeof(float) * W::ITCZ_SAMPLES : f == WF_ISLAND ? N : N * 4;
-    if (itcz) return B->itcz[f - WF_ITCZ0];
-    if (f < WF_ITCZ0) return B->season[f / 4][f % 4];
-    switch (f) {
-        case WF_LAT: return B->lat;           case WF_LON: return B->lon;             case WF_SINLAT: return B->sinLat;
-        case WF_ISLAND: return B->isLand;     case WF_CONT: return B->cont;           case WF_COASTDIST: return B->coastDist;
-        case WF_PLATECONT: return B->plateCont;
-        default: return B->frame[f - WF_FRAME0];
-    }
-}
-
-int wo_wind_download(wo_planet* p, const char* field, void* out, int64_t outBytes) {
-    if (!check_planet(p, "wo_wind_download")) return 1;
-    if (!field || !out) { set_error("wo_wind_download: null pointer"); return 1; }
-    auto* B = p->wind;
-    if (!B || !(B->valid || B->have)) { set_error("wo_wind_download: no wind result on this planet (call wo_compute_wind first)"); return 1; }
-    const int f = wind_field_index(field);
-    if (f < 0) { set_error(std::string("wo_wind_download: unknown field '") + field + "'"); return 1; }
-    if (!B->valid && !((B->have >> f) & 1u)) { set_error(std::string("wo_wind_download: no wind result on this planet: ") + field + " was never set (call wo_compute_wind first)"); return 1; }
-    WO_TRY
-        size_t bytes = 0;
-        const void* src = wind_field_ptr(B, f, (size_t)p->N, &bytes);
-        if (outBytes < (int64_t)bytes) { set_error(std::string("wo_wind_download: ") + field + " needs " + std::to_string(bytes) + " bytes, out has " + std::to_string(outBytes)); return 1; }
-        if (f >= WF_ITCZ0 && f < WF_LAT) { std::memcpy(out, src, bytes); return 0; }
-        WO_HIP(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, p->ctx->stream));
-        WO_HIP(hipStreamSynchronize(p->ctx->stream));
-        return 0;
-    WO_CATCH("wo_wind_download")
-}
-
-int wo_wind_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) {
-    if (!check_planet(p, "wo_wind_upload")) return 1;
-    if (!field || !data) { set_error("wo_wind_upload: null pointer"); return 1; }
-    const int f = wind_field_index(field);
-    if (f < 0) { set_error(std::string("wo_wind_upload: unknown field '") + field + "'"); return 1; }
-    WO_TRY
-        wind_alloc(p);
-        auto* B = p->wind;
-        size_t want = 0;
-        void* dst = wind_field_ptr(B, f, (size_t)p->N, &want);
-        if (bytes != (int64_t)want) { set_error(std::string("wo_wind_upload: ") + field + " takes " + std::to_string(want) + " bytes, data has " + std::to_string(bytes)); return 1; }
-        if (f >= WF_ITCZ0 && f < WF_LAT) std::memcpy(dst, data, want);
-        else {
-            WO_HIP(hipMemcpyAsync(dst, data, want, hipMemcpyHostToDevice, p->ctx->stream));
-            WO_HIP(hipStreamSynchronize(p->ctx->stream));     // `data` is the caller's, and pageable
-        }
-        B->have |= 1u << f;
-        return 0;
-    WO_CATCH("wo_wind_upload")
-}
+int wo_wind_download(wo_planet* p, const char* field, void* out, int64_t outBytes) { return block_download(p, "wo_wind_download", wind_desc(), field, out, outBytes); }
+int wo_wind_upload(wo_planet* p, const char* field, const void* data, int64_t bytes) { return block_upload(p, "wo_wind_upload", wind_desc(), field, data, bytes); }
 
 int wo_compute_gradients(wo_planet* p, int32_t numRegions, const float* r_pressure, const float* east3, const float* north3, float* r_gradE, float* r_gradN) {
     if (!check_planet(p, "wo_compute_gradients")) return 1;

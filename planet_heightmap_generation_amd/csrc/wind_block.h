@@ -7,12 +7,10 @@
 #include <cstdint>
 
 #include "device.h"
+#include "stage_block.h"
 #include "wind_ops.h"
 
-struct wo_wind_block {
-    wo::DeviceArena mem;                                      // owns every device and pinned buffer of the block
-    bool valid = false;                                       // a whole result of wo_compute_wind
-    uint32_t have = 0;                                        // bit f: field f (WindField) was set, by wo_compute_wind or by wo_wind_upload
+struct wo_wind_block : wo::StageBlock {                       // have: bit f is field f of WindField
     // results (device): the eight season arrays, then the per-cell geography
     float* season[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // pressure, east, north, speed
     float *lat = nullptr, *lon = nullptr, *sinLat = nullptr, *cosLat = nullptr;
@@ -40,7 +38,11 @@ namespace wo {
 
 // the fields of the block by the reference's result keys, in the order it sets them (js/wind.js:649-683)
 enum WindField : int { WF_SEASON0 = 0, WF_ITCZ0 = 8, WF_LAT = 11, WF_LON, WF_SINLAT, WF_ISLAND, WF_CONT, WF_COASTDIST, WF_PLATECONT, WF_FRAME0, WF_COUNT = WF_FRAME0 + 6 };
-constexpr uint32_t WF_ALL = (1u << WF_COUNT) - 1u;
+// a season's four fields: WF_SEASON0 + WS_STRIDE * season + one of these
+enum WindSeasonField : int { WS_PRESSURE = 0, WS_EAST, WS_NORTH, WS_SPEED, WS_STRIDE };
+constexpr uint32_t wind_both(int f) { return bit(WF_SEASON0 + f) | bit(WF_SEASON0 + WS_STRIDE + f); }      // field f of both seasons
+constexpr uint32_t WF_ITCZ_ALL = 7u << WF_ITCZ0;              // itczLons, itczLatsSummer, itczLatsWinter
+const BlockDesc& wind_desc();                                 // wind.hip: the block's descriptor
 
 // wind.hip: allocates the planet's wind block if there is none
 void wind_alloc(wo_planet* p);

@@ -3,6 +3,7 @@
 // koppen_cell) on the planet bound to `mesh` (native.js: planetFor).  Given the same inputs every cell has the reference's class.
 // There is no JavaScript fallback: without the addon or a device the call throws.
 import addon, { planetFor } from './native.js';
+import { TEMP_KEYS as TEMP_INPUTS, given, checkInputs, uploadInputs } from './climate-blocks.js';
 
 // class id -> { code, name, color [r, g, b] 0-1 } (the reference's table, js/koppen.js:19-51)
 export const KOPPEN_CLASSES = [
@@ -38,15 +39,7 @@ export const KOPPEN_CLASSES = [
     { code: 'ET', name: 'Tundra', color: [0.70, 0.70, 0.70] },
     { code: 'EF', name: 'Ice cap', color: [0.41, 0.41, 0.41] },
 ];
-const TEMP_INPUTS = ['r_temperature_summer', 'r_temperature_winter'];
 const PRECIP_INPUTS = ['r_precip_summer', 'r_precip_winter'];
-const given = (x) => x !== null && x !== undefined;
-function checkInputs(what, result, keys, numRegions) {
-    for (const k of keys) {
-        const a = result[k];
-        if (!(a instanceof Float32Array) || a.length !== numRegions) throw new RangeError(`classifyKoppen: ${what}.${k} must be a Float32Array of ${numRegions} entries`);
-    }
-}
 
 // classifyKoppen(mesh, r_elevation, tempResult, precipResult): the two results are the objects computeTemperature and
 // computePrecipitation returned (uploaded to the planet's blocks), or null / undefined for the blocks they left on the device.
@@ -54,10 +47,10 @@ export function classifyKoppen(mesh, r_elevation, tempResult, precipResult) {
     if (!(r_elevation instanceof Float32Array) || r_elevation.length !== mesh.numRegions) {
         throw new RangeError(`classifyKoppen: r_elevation must be a Float32Array of ${mesh.numRegions} entries`);
     }
-    if (given(tempResult)) checkInputs('tempResult', tempResult, TEMP_INPUTS, mesh.numRegions);
-    if (given(precipResult)) checkInputs('precipResult', precipResult, PRECIP_INPUTS, mesh.numRegions);
+    if (given(tempResult)) checkInputs('classifyKoppen', 'tempResult', tempResult, TEMP_INPUTS, mesh.numRegions);
+    if (given(precipResult)) checkInputs('classifyKoppen', 'precipResult', precipResult, PRECIP_INPUTS, mesh.numRegions);
     const planet = planetFor(mesh);
-    if (given(tempResult)) for (const k of TEMP_INPUTS) addon.temperatureUpload(planet, k, tempResult[k]);
-    if (given(precipResult)) for (const k of PRECIP_INPUTS) addon.precipUpload(planet, k, precipResult[k]);
+    if (given(tempResult)) uploadInputs(planet, addon.temperatureUpload, TEMP_INPUTS, tempResult);
+    if (given(precipResult)) uploadInputs(planet, addon.precipUpload, PRECIP_INPUTS, precipResult);
     return addon.classifyKoppen(planet, r_elevation);
 }

@@ -3,8 +3,8 @@
 // planet bound to `mesh` (native.js: planetFor); the exactness contract is in csrc/ocean_ops.h.  There is no JavaScript
 // fallback: without the addon or a device the call throws.
 import addon, { planetFor } from './native.js';
+import { OCEAN_KEYS, given, checkInputs, uploadInputs, downloadAll } from './climate-blocks.js';
 
-const RESULT_KEYS = ['summer', 'winter'].flatMap((s) => ['current_east', 'current_north', 'speed', 'warmth'].map((k) => `r_ocean_${k}_${s}`));
 // the keys of windResult the stage reads
 const WIND_INPUTS = ['r_lat', 'r_lon', 'r_isLand', 'r_eastX', 'r_eastY', 'r_eastZ', 'itczLons', 'itczLatsSummer', 'itczLatsWinter'];
 
@@ -12,18 +12,9 @@ const WIND_INPUTS = ['r_lat', 'r_lon', 'r_isLand', 'r_eastX', 'r_eastY', 'r_east
 // uploaded to the planet's wind block), or null / undefined for the wind block the planet's last computeWind left on the
 // device.  r_elevation is accepted and unused, as in the reference.
 export function computeOceanCurrents(mesh, r_xyz, r_elevation, windResult) {
-    const given = windResult !== null && windResult !== undefined;
-    if (given) {
-        for (const k of WIND_INPUTS) {
-            const a = windResult[k], n = k.startsWith('itcz') ? 360 : mesh.numRegions;
-            const ok = k === 'r_isLand' ? a instanceof Uint8Array : a instanceof Float32Array;
-            if (!ok || a.length !== n) throw new RangeError(`computeOceanCurrents: windResult.${k} must be a ${k === 'r_isLand' ? 'Uint8Array' : 'Float32Array'} of ${n} entries`);
-        }
-    }
+    if (given(windResult)) checkInputs('computeOceanCurrents', 'windResult', windResult, WIND_INPUTS, mesh.numRegions);
     const planet = planetFor(mesh, r_xyz);
-    if (given) for (const k of WIND_INPUTS) addon.windUpload(planet, k, windResult[k]);
+    if (given(windResult)) uploadInputs(planet, addon.windUpload, WIND_INPUTS, windResult);
     addon.computeOceanCurrents(planet);
-    const result = {};
-    for (const k of RESULT_KEYS) result[k] = addon.oceanDownload(planet, k);
-    return result;
+    return downloadAll(planet, addon.oceanDownload, OCEAN_KEYS);
 }

@@ -40,6 +40,7 @@ import addon, { defaultContext } from './native.js';
 import { runPostProcessingResident } from './post-processing.js';
 import { buildSphere, computeNeighborDist, generateTriangleCenters } from './sphere-mesh.js';
 import { platesFromDevice } from './heightmap-import.js';
+import { OCEAN_KEYS, PRECIP_KEYS, TEMP_KEYS, downloadAll } from './climate-blocks.js';
 
 let W = null;          // retained state (js/planet-worker.js:22)
 
@@ -185,10 +186,6 @@ function getClimateParams(data) {
     return { temperatureOffset, precipitationOffset, landCoverage };
 }
 
-const OCEAN_KEYS = ['summer', 'winter'].flatMap((s) => ['current_east', 'current_north', 'speed', 'warmth'].map((k) => `r_ocean_${k}_${s}`));
-const PRECIP_KEYS = ['r_precip_summer', 'r_rainshadow_summer', 'r_precip_winter', 'r_rainshadow_winter'];
-const TEMP_KEYS = ['r_temperature_summer', 'r_temperature_winter'];
-
 // js/planet-worker.js:579-677 with every stage on the device; the planet's resident elevation is r_elevation_final
 function handleComputeClimate(data) {
     if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for computeClimate' }); return; }
@@ -201,7 +198,6 @@ function handleComputeClimate(data) {
     try {
         const tTotal0 = performance.now();
         const planet = W.planet;
-        const download = (keys, fn) => { const o = {}; for (const k of keys) o[k] = fn(planet, k); return o; };
         let windResult = W.cachedWind, oceanResult = W.cachedOcean;
         let tWind = 0, tOcean = 0, t0;
         if (!windResult) {
@@ -213,7 +209,7 @@ function handleComputeClimate(data) {
             progress(30, 'Computing ocean currents\u2026');
             t0 = performance.now();
             addon.computeOceanCurrents(planet);
-            oceanResult = download(OCEAN_KEYS, addon.oceanDownload);
+            oceanResult = downloadAll(planet, addon.oceanDownload, OCEAN_KEYS);
             tOcean = performance.now() - t0;
 
             W.cachedWind = windResult;
@@ -223,13 +219,13 @@ function handleComputeClimate(data) {
         progress(50, 'Computing precipitation\u2026');
         t0 = performance.now();
         addon.computePrecipitation(planet, null, Number(precipitationOffset), Number(landCoverage));
-        const precipResult = download(PRECIP_KEYS, addon.precipDownload);
+        const precipResult = downloadAll(planet, addon.precipDownload, PRECIP_KEYS);
         const tPrecip = performance.now() - t0;
 
         progress(70, 'Computing temperature\u2026');
         t0 = performance.now();
         addon.computeTemperature(planet, null, Number(temperatureOffset));
-        const tempResult = download(TEMP_KEYS, addon.temperatureDownload);
+        const tempResult = downloadAll(planet, addon.temperatureDownload, TEMP_KEYS);
         const tTemp = performance.now() - t0;
 
         progress(88, 'Classifying climates\u2026');

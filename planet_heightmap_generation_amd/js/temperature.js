@@ -3,20 +3,12 @@
 // (csrc/temp.hip) on the planet bound to `mesh` (native.js: planetFor); the contract is in csrc/temp_ops.h.  The reference's
 // branches for missing inputs are not offered.  There is no JavaScript fallback: without the addon or a device the call throws.
 import addon, { planetFor } from './native.js';
+import { TEMP_KEYS, given, checkInputs, uploadInputs, downloadAll } from './climate-blocks.js';
 
-const RESULT_KEYS = ['r_temperature_summer', 'r_temperature_winter'];
 // the keys of windResult, oceanResult and precipResult the stage reads
 const WIND_INPUTS = ['r_lat', 'r_lon', 'r_isLand', 'r_continentality', 'r_plateContinentality', 'itczLons', 'itczLatsSummer', 'itczLatsWinter'];
 const OCEAN_INPUTS = ['r_ocean_warmth_summer', 'r_ocean_speed_summer', 'r_ocean_warmth_winter', 'r_ocean_speed_winter'];
 const PRECIP_INPUTS = ['r_precip_summer', 'r_precip_winter'];
-
-function checkInputs(fn, what, result, keys, numRegions) {
-    for (const k of keys) {
-        const a = result[k], n = k.startsWith('itcz') ? 360 : numRegions, T = k === 'r_isLand' ? Uint8Array : Float32Array;
-        if (!(a instanceof T) || a.length !== n) throw new RangeError(`${fn}: ${what}.${k} must be a ${T.name} of ${n} entries`);
-    }
-}
-const given = (x) => x !== null && x !== undefined;
 
 // computeTemperature(mesh, r_xyz, r_elevation, windResult, oceanResult, precipResult, temperatureOffset = 0): the three results are
 // the objects the earlier stages returned (their arrays are uploaded to the planet's blocks), or null / undefined for the blocks
@@ -30,11 +22,9 @@ export function computeTemperature(mesh, r_xyz, r_elevation, windResult, oceanRe
     if (given(precipResult)) checkInputs('computeTemperature', 'precipResult', precipResult, PRECIP_INPUTS, mesh.numRegions);
     if (Number.isNaN(Number(temperatureOffset))) throw new RangeError('computeTemperature: temperatureOffset must be a number');
     const planet = planetFor(mesh, r_xyz);
-    if (given(windResult)) for (const k of WIND_INPUTS) addon.windUpload(planet, k, windResult[k]);
-    if (given(oceanResult)) for (const k of OCEAN_INPUTS) addon.oceanUpload(planet, k, oceanResult[k]);
-    if (given(precipResult)) for (const k of PRECIP_INPUTS) addon.precipUpload(planet, k, precipResult[k]);
+    if (given(windResult)) uploadInputs(planet, addon.windUpload, WIND_INPUTS, windResult);
+    if (given(oceanResult)) uploadInputs(planet, addon.oceanUpload, OCEAN_INPUTS, oceanResult);
+    if (given(precipResult)) uploadInputs(planet, addon.precipUpload, PRECIP_INPUTS, precipResult);
     addon.computeTemperature(planet, r_elevation, Number(temperatureOffset));
-    const result = {};
-    for (const k of RESULT_KEYS) result[k] = addon.temperatureDownload(planet, k);
-    return result;
+    return downloadAll(planet, addon.temperatureDownload, TEMP_KEYS);
 }

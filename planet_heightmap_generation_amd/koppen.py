@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import capi
+from . import climate_blocks as CB
 from . import precipitation as PD
 from . import temperature as TD
 from . import terrain_post as TP
@@ -67,16 +68,10 @@ def classify_koppen(planet: TP.Planet, r_elevation, temp_result=None, precip_res
     dict is uploaded first (both keys of TEMP_INPUTS / PRECIP_INPUTS are required).  Every argument is checked before any device
     work."""
     n = planet.numRegions
-    e = None
-    if r_elevation is not None:
-        e = np.ascontiguousarray(r_elevation, dtype=np.float32).reshape(-1)
-        if e.size != n:
-            raise ValueError(f"r_elevation has {e.size} values, expected {n}")
-    temp_up = TD.checked_inputs(n, temp_result, TEMP_INPUTS, TD.RESULT_FIELDS, "temp_result")
-    precip_up = TD.checked_inputs(n, precip_result, PRECIP_INPUTS, PD.RESULT_FIELDS, "precip_result")
-    for k, a in temp_up.items():
-        TD.upload(planet, k, a)
-    for k, a in precip_up.items():
-        TD.upload_precip(planet, k, a)
+    e = CB.elevation_arg(n, r_elevation)
+    temp_up = CB.checked_inputs(n, temp_result, TEMP_INPUTS, TD.BLOCK, "temp_result")
+    precip_up = CB.checked_inputs(n, precip_result, PRECIP_INPUTS, PD.BLOCK, "precip_result")
+    CB.upload_inputs(planet, TD.BLOCK, temp_up)
+    CB.upload_inputs(planet, PD.BLOCK, precip_up)
     capi.check(capi.lib().wo_classify_koppen(planet.handle, n, capi.ptr(e)), "classifyKoppen")
     return download(planet)

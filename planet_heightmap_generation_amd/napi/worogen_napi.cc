@@ -7,6 +7,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -486,6 +487,31 @@ static bool key_at(Args& a, size_t i, char (&key)[64]) {
     napi_throw_type_error(a.env, nullptr, "expected a result key (string)");
     return false;
 }
+// <block>Download(planet, key) -> Float32Array: one field of the planet's ocean, precipitation or temperature block by the reference's result key
+static napi_value block_download(napi_env env, napi_callback_info info, int (*fn)(wo_planet*, const char*, void*, int64_t), const char* name) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    char key[64]; if (!key_at(a, 1, key)) return nullptr;
+    const size_t n = (size_t)wo_planet_num_regions(p);
+    void* d; napi_value out = make_ta(env, napi_float32_array, n, 4, &d);
+    if (!out) return nullptr;
+    if (fn(p, key, d, (int64_t)(n * 4))) return throw_wo(env, name);
+    return out;
+}
+// <block>Upload(planet, key, Float32Array): one field of such a block by its result key (the C ABI checks key and size)
+static napi_value block_upload(napi_env env, napi_callback_info info, int (*fn)(wo_planet*, const char*, const void*, int64_t), const char* name) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    char key[64]; if (!key_at(a, 1, key)) return nullptr;
+    size_t n = 0; float* data = (float*)a.ta(2, napi_float32_array, &n); if (!a.ok) return nullptr;
+    if (fn(p, key, data, (int64_t)(n * 4))) return throw_wo(env, name);
+    return nullptr;
+}
+// the scalars of a stage's call as number properties of o
+struct Num { const char* k; double x; };
+static void set_nums(napi_env env, napi_value o, std::initializer_list<Num> nums) {
+    for (const Num& e : nums) { napi_value v; napi_create_double(env, e.x, &v); set_prop(env, o, e.k, v); }
+}
 napi_value WindUpload(napi_env env, napi_callback_info info) {
     Args a(env, info); wo_planet* p = planet_at(a, 0);
     if (!planet_ok(env, p)) return nullptr;
@@ -509,32 +535,13 @@ napi_value ComputeOceanCurrents(napi_env env, napi_callback_info info) {
     napi_value o, v; napi_create_object(env, &o);
     napi_get_boolean(env, oi.circumpolarNH != 0, &v); set_prop(env, o, "circumpolarNH", v);
     napi_get_boolean(env, oi.circumpolarSH != 0, &v); set_prop(env, o, "circumpolarSH", v);
-    const struct { const char* k; double x; } nums[] = {{"coastThreshold", (double)oi.coastThreshold}, {"warmthRange", (double)oi.warmthRange},
+    set_nums(env, o, {{"coastThreshold", (double)oi.coastThreshold}, {"warmthRange", (double)oi.warmthRange},
         {"currentSmoothPasses", (double)oi.currentSmoothPasses}, {"warmthSmoothPasses", (double)oi.warmthSmoothPasses}, {"oceanCellsSummer", (double)oi.oceanCells[0]},
-        {"oceanCellsWinter", (double)oi.oceanCells[1]}, {"p95Summer", (double)oi.p95[0]}, {"p95Winter", (double)oi.p95[1]}};
-    for (const auto& e : nums) { napi_create_double(env, e.x, &v); set_prop(env, o, e.k, v); }
+        {"oceanCellsWinter", (double)oi.oceanCells[1]}, {"p95Summer", (double)oi.p95[0]}, {"p95Winter", (double)oi.p95[1]}});
     return o;
 }
-// oceanDownload(planet, key) -> Float32Array: one field of the planet's ocean block by the reference's result key
-napi_value OceanDownload(napi_env env, napi_callback_info info) {
-    Args a(env, info); wo_planet* p = planet_at(a, 0);
-    if (!planet_ok(env, p)) return nullptr;
-    char key[64]; if (!key_at(a, 1, key)) return nullptr;
-    const size_t n = (size_t)wo_planet_num_regions(p);
-    void* d; napi_value out = make_ta(env, napi_float32_array, n, 4, &d);
-    if (!out) return nullptr;
-    if (wo_ocean_download(p, key, d, (int64_t)(n * 4))) return throw_wo(env, "oceanDownload");
-    return out;
-}
-// oceanUpload(planet, key, Float32Array): one field of the planet's ocean block by its result key (the C ABI checks key and size)
-napi_value OceanUpload(napi_env env, napi_callback_info info) {
-    Args a(env, info); wo_planet* p = planet_at(a, 0);
-    if (!planet_ok(env, p)) return nullptr;
-    char key[64]; if (!key_at(a, 1, key)) return nullptr;
-    size_t n = 0; float* data = (float*)a.ta(2, napi_float32_array, &n); if (!a.ok) return nullptr;
-    if (wo_ocean_upload(p, key, data, (int64_t)(n * 4))) return throw_wo(env, "oceanUpload");
-    return nullptr;
-}
+napi_value OceanDownload(napi_env env, napi_callback_info info) { return block_download(env, info, wo_ocean_download, "oceanDownload"); }
+napi_value OceanUpload(napi_env env, napi_callback_info info) { return block_upload(env, info, wo_ocean_upload, "oceanUpload"); }
 // computePrecipitation(planet, r_elevation | null, precipitationOffset, landCoverage) -> the scalars of the call: the stage on the planet's
 // wind and ocean blocks; the results stay on the device (precipDownload)
 napi_value ComputePrecipitation(napi_env env, napi_callback_info info) {
@@ -543,36 +550,17 @@ napi_value ComputePrecipitation(napi_env env, napi_callback_info info) {
     float* e = (float*)opt_regions(a, 1, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
     wo_precip_info pi;
     if (wo_compute_precipitation(p, wo_planet_num_regions(p), e, a.num(2), a.num(3), &pi)) return throw_wo(env, "computePrecipitation");
-    napi_value o, v; napi_create_object(env, &o);
-    const struct { const char* k; double x; } nums[] = {{"maxHops", (double)pi.maxHops}, {"elevSmoothPasses", (double)pi.elevSmoothPasses},
+    napi_value o; napi_create_object(env, &o);
+    set_nums(env, o, {{"maxHops", (double)pi.maxHops}, {"elevSmoothPasses", (double)pi.elevSmoothPasses},
         {"convSmoothPasses", (double)pi.convSmoothPasses}, {"shadowHops", (double)pi.shadowHops}, {"windwardHops", (double)pi.windwardHops},
         {"rsSmoothPasses", (double)pi.rsSmoothPasses}, {"precipSmoothPasses", (double)pi.precipSmoothPasses}, {"wcPasses", (double)pi.wcPasses},
         {"leeCoastHops", (double)pi.leeCoastHops}, {"upCountSummer", (double)pi.listLengths[0]}, {"downCountSummer", (double)pi.listLengths[1]},
         {"upCountWinter", (double)pi.listLengths[2]}, {"downCountWinter", (double)pi.listLengths[3]}, {"depletionBase", pi.depletionBase},
-        {"shadowDecay", pi.shadowDecay}, {"windwardDecay", pi.windwardDecay}, {"p95Summer", (double)pi.p95[0]}, {"p95Winter", (double)pi.p95[1]}};
-    for (const auto& x : nums) { napi_create_double(env, x.x, &v); set_prop(env, o, x.k, v); }
+        {"shadowDecay", pi.shadowDecay}, {"windwardDecay", pi.windwardDecay}, {"p95Summer", (double)pi.p95[0]}, {"p95Winter", (double)pi.p95[1]}});
     return o;
 }
-// precipDownload(planet, key) -> Float32Array: one field of the planet's precipitation block by the reference's result key
-napi_value PrecipDownload(napi_env env, napi_callback_info info) {
-    Args a(env, info); wo_planet* p = planet_at(a, 0);
-    if (!planet_ok(env, p)) return nullptr;
-    char key[64]; if (!key_at(a, 1, key)) return nullptr;
-    const size_t n = (size_t)wo_planet_num_regions(p);
-    void* d; napi_value out = make_ta(env, napi_float32_array, n, 4, &d);
-    if (!out) return nullptr;
-    if (wo_precip_download(p, key, d, (int64_t)(n * 4))) return throw_wo(env, "precipDownload");
-    return out;
-}
-// precipUpload(planet, key, Float32Array): one field of the planet's precipitation block by its result key (the C ABI checks key and size)
-napi_value PrecipUpload(napi_env env, napi_callback_info info) {
-    Args a(env, info); wo_planet* p = planet_at(a, 0);
-    if (!planet_ok(env, p)) return nullptr;
-    char key[64]; if (!key_at(a, 1, key)) return nullptr;
-    size_t n = 0; float* data = (float*)a.ta(2, napi_float32_array, &n); if (!a.ok) return nullptr;
-    if (wo_precip_upload(p, key, data, (int64_t)(n * 4))) return throw_wo(env, "precipUpload");
-    return nullptr;
-}
+napi_value PrecipDownload(napi_env env, napi_callback_info info) { return block_download(env, info, wo_precip_download, "precipDownload"); }
+napi_value PrecipUpload(napi_env env, napi_callback_info info) { return block_upload(env, info, wo_precip_upload, "precipUpload"); }
 // computeTemperature(planet, r_elevation | null, temperatureOffset) -> the scalars of the call: the stage on the planet's wind, ocean and
 // precipitation blocks; the results stay on the device (temperatureDownload)
 napi_value ComputeTemperature(napi_env env, napi_callback_info info) {
@@ -581,32 +569,12 @@ napi_value ComputeTemperature(napi_env env, napi_callback_info info) {
     float* e = (float*)opt_regions(a, 1, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
     wo_temperature_info ti;
     if (wo_compute_temperature(p, wo_planet_num_regions(p), e, a.num(2), &ti)) return throw_wo(env, "computeTemperature");
-    napi_value o, v; napi_create_object(env, &o);
-    const struct { const char* k; double x; } nums[] = {{"oceanWarmthPasses", (double)ti.oceanWarmthPasses}, {"smoothPasses", (double)ti.smoothPasses},
-        {"launches", (double)ti.launches}};
-    for (const auto& x : nums) { napi_create_double(env, x.x, &v); set_prop(env, o, x.k, v); }
+    napi_value o; napi_create_object(env, &o);
+    set_nums(env, o, {{"oceanWarmthPasses", (double)ti.oceanWarmthPasses}, {"smoothPasses", (double)ti.smoothPasses}, {"launches", (double)ti.launches}});
     return o;
 }
-// temperatureDownload(planet, key) -> Float32Array: one field of the planet's temperature block by the reference's result key
-napi_value TemperatureDownload(napi_env env, napi_callback_info info) {
-    Args a(env, info); wo_planet* p = planet_at(a, 0);
-    if (!planet_ok(env, p)) return nullptr;
-    char key[64]; if (!key_at(a, 1, key)) return nullptr;
-    const size_t n = (size_t)wo_planet_num_regions(p);
-    void* d; napi_value out = make_ta(env, napi_float32_array, n, 4, &d);
-    if (!out) return nullptr;
-    if (wo_temperature_download(p, key, d, (int64_t)(n * 4))) return throw_wo(env, "temperatureDownload");
-    return out;
-}
-// temperatureUpload(planet, key, Float32Array): one field of the planet's temperature block by its result key
-napi_value TemperatureUpload(napi_env env, napi_callback_info info) {
-    Args a(env, info); wo_planet* p = planet_at(a, 0);
-    if (!planet_ok(env, p)) return nullptr;
-    char key[64]; if (!key_at(a, 1, key)) return nullptr;
-    size_t n = 0; float* data = (float*)a.ta(2, napi_float32_array, &n); if (!a.ok) return nullptr;
-    if (wo_temperature_upload(p, key, data, (int64_t)(n * 4))) return throw_wo(env, "temperatureUpload");
-    return nullptr;
-}
+napi_value TemperatureDownload(napi_env env, napi_callback_info info) { return block_download(env, info, wo_temperature_download, "temperatureDownload"); }
+napi_value TemperatureUpload(napi_env env, napi_callback_info info) { return block_upload(env, info, wo_temperature_upload, "temperatureUpload"); }
 // classifyKoppen(planet, r_elevation | null) -> Uint8Array of class ids: the classification on the planet's temperature and
 // precipitation blocks; the ids also stay on the device
 napi_value ClassifyKoppen(napi_env env, napi_callback_info info) {

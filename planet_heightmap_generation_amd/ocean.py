@@ -3,7 +3,7 @@
 ``compute_ocean_currents`` is the reference's ``computeOceanCurrents`` (js/ocean.js:204-382): the coast seeds, the west and east
 hop-distance fields, the circumpolar test, the band and deflection loop, the masked smoothing passes, classifyWarmth, the speeds
 and their percentile run in HIP kernels (csrc/ocean.hip; exactness contract in csrc/ocean_ops.h).  The stage reads the planet's
-wind block (left there by ``wind.compute_wind``, or filled from a caller's ``windResult`` by ``upload_wind``); its result stays
+wind block (left there by ``wind.compute_wind``, or filled from a caller's ``windResult`` by ``wind.upload``); its result stays
 on the device in the planet's ocean block, and the returned dict holds host copies under the reference's result keys (without
 ``_oceanTiming``).  There is no CPU fallback.
 """
@@ -12,42 +12,27 @@ from __future__ import annotations
 import numpy as np
 
 from . import capi
+from . import climate_blocks as CB
 from . import terrain_post as TP
 from . import wind as WD
 
 # the reference's result keys in the order it sets them (js/ocean.js:374-377), all Float32Array
 RESULT_FIELDS = tuple((f"r_ocean_{k}_{s}", np.float32) for s in ("summer", "winter") for k in ("current_east", "current_north", "speed", "warmth"))
+BLOCK = CB.Block("wo_ocean", RESULT_FIELDS)
 # the keys of windResult the stage reads
 WIND_INPUTS = ("r_lat", "r_lon", "r_isLand", "r_eastX", "r_eastY", "r_eastZ", "itczLons", "itczLatsSummer", "itczLatsWinter")
 INFO_FIELDS = ("circumpolarNH", "circumpolarSH", "coastThreshold", "warmthRange", "currentSmoothPasses", "warmthSmoothPasses",
                "oceanCellsSummer", "oceanCellsWinter", "p95Summer", "p95Winter")
 
 
-def _wind_field(n: int, field: str, data) -> np.ndarray:
-    ty = dict(WD.RESULT_FIELDS).get(field)
-    if ty is None:
-        raise KeyError(field)
-    a = np.ascontiguousarray(data, dtype=ty).reshape(-1)
-    want = WD.ITCZ_SAMPLES if field.startswith("itcz") else n
-    if a.size != want:
-        raise ValueError(f"{field} has {a.size} values, expected {want}")
-    return a
-
-
-def upload_wind(planet: TP.Planet, field: str, data) -> None:
-    """Set one field of the planet's wind block from the host by its result key (wind.RESULT_FIELDS)."""
-    a = _wind_field(planet.numRegions, field, data)
-    capi.check(capi.lib().wo_wind_upload(planet.handle, field.encode(), capi.ptr(a), a.nbytes), "wo_wind_upload")
-
-
 def download(planet: TP.Planet, field: str) -> np.ndarray:
     """One field of the planet's ocean block by the reference's result key."""
-    ty = dict(RESULT_FIELDS).get(field)
-    if ty is None:
-        raise KeyError(field)
-    out = np.empty(planet.numRegions, ty)
-    capi.check(capi.lib().wo_ocean_download(planet.handle, field.encode(), capi.ptr(out), out.nbytes), "wo_ocean_download")
-    return out
+    return CB.download(planet, BLOCK, field)
+
+
+def upload(planet: TP.Planet, field: str, data) -> None:
+    """Set one field of the planet's ocean block from the host by its result key."""
+    CB.upload(planet, BLOCK, field, data)
 
 
 def info(planet: TP.Planet) -> dict:
@@ -64,18 +49,10 @@ def compute_ocean_currents(planet: TP.Planet, r_xyz, r_elevation, wind_result=No
     other keys of wind.RESULT_FIELDS are uploaded too, anything else is ignored).  fields: the result keys to bring back
     (default: all)."""
     n = planet.numRegions
-    if r_xyz is not None and np.asarray(r_xyz).size != 3 * n:
-        raise ValueError(f"r_xyz has {np.asarray(r_xyz).size} values, expected 3 * {n}")
-    if r_elevation is not None and np.asarray(r_elevation).size != n:
-        raise ValueError(f"r_elevation has {np.asarray(r_elevation).size} values, expected {n}")
-    if wind_result is not None:
-        missing = [k for k in WIND_INPUTS if wind_result.get(k) is None]
-        if missing:
-            raise ValueError(f"wind_result lacks {missing}")
-        known = dict(WD.RESULT_FIELDS)
-        checked = {k: _wind_field(n, k, v) for k, v in wind_result.items() if k in known and v is not None}      # all refused before any device work
-        for k, a in checked.items():
-            upload_wind(planet, k, a)
+    CB.check_xyz(n, r_xyz)
+    CB.elevation_arg(n, r_elevation)
+    wind_up = CB.checked_inputs(n, wind_result, WIND_INPUTS, WD.BLOCK, "wind_result")      # all refused before any device work
+    CB.upload_inputs(planet, WD.BLOCK, wind_up)
     raw = np.zeros(10, np.int32)
     capi.check(capi.lib().wo_compute_ocean_currents(planet.handle, n, capi.ptr(raw)), "computeOceanCurrents")
     vals = [bool(raw[0]), bool(raw[1])] + [int(v) for v in raw[2:8]] + [float(v) for v in raw[8:10].view(np.float32)]

@@ -3,8 +3,8 @@
 ``compute_temperature`` is the reference's ``computeTemperature`` (js/temperature.js:69-237): the diffusion of ocean warmth onto
 coastal land, the per-cell loop, the smoothing pass and the normalisation run in HIP kernels (csrc/temp.hip; contract in
 csrc/temp_ops.h).  The stage reads the planet's wind block (``wind.compute_wind``, or a caller's ``windResult`` uploaded key by
-key), the warmth and speed fields of its ocean block (``ocean.compute_ocean_currents``, or ``precipitation.upload_ocean``) and
-``r_precip_*`` of its precipitation block (``precipitation.compute_precipitation``, or ``upload_precip``); its result stays on the
+key), the warmth and speed fields of its ocean block (``ocean.compute_ocean_currents``, or ``ocean.upload``) and
+``r_precip_*`` of its precipitation block (``precipitation.compute_precipitation``, or ``precipitation.upload``); its result stays on the
 device in the planet's temperature block, and the returned dict holds host copies under the reference's result keys (without
 ``_tempTiming``).  The reference's branches for missing inputs are not offered: a missing field is refused.  There is no CPU
 fallback.
@@ -14,6 +14,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import capi
+from . import climate_blocks as CB
 from . import ocean as OD
 from . import precipitation as PD
 from . import terrain_post as TP
@@ -21,6 +22,7 @@ from . import wind as WD
 
 # the reference's result keys (js/temperature.js:232), both Float32Array
 RESULT_FIELDS = (("r_temperature_summer", np.float32), ("r_temperature_winter", np.float32))
+BLOCK = CB.Block("wo_temperature", RESULT_FIELDS)
 # the keys of windResult, oceanResult and precipResult the stage reads
 WIND_INPUTS = ("r_lat", "r_lon", "r_isLand", "r_continentality", "r_plateContinentality", "itczLons", "itczLatsSummer", "itczLatsWinter")
 OCEAN_INPUTS = ("r_ocean_warmth_summer", "r_ocean_speed_summer", "r_ocean_warmth_winter", "r_ocean_speed_winter")
@@ -28,52 +30,19 @@ PRECIP_INPUTS = ("r_precip_summer", "r_precip_winter")
 INFO_FIELDS = ("oceanWarmthPasses", "smoothPasses", "launches")
 
 
-def _field(n: int, known, field: str, data) -> np.ndarray:
-    if field not in dict(known):
-        raise KeyError(field)
-    a = np.ascontiguousarray(data, dtype=np.float32).reshape(-1)
-    if a.size != n:
-        raise ValueError(f"{field} has {a.size} values, expected {n}")
-    return a
-
-
-def upload_precip(planet: TP.Planet, field: str, data) -> None:
-    """Set one field of the planet's precipitation block from the host by its result key (precipitation.RESULT_FIELDS)."""
-    a = _field(planet.numRegions, PD.RESULT_FIELDS, field, data)
-    capi.check(capi.lib().wo_precip_upload(planet.handle, field.encode(), capi.ptr(a), a.nbytes), "wo_precip_upload")
-
-
 def upload(planet: TP.Planet, field: str, data) -> None:
     """Set one field of the planet's temperature block from the host by its result key."""
-    a = _field(planet.numRegions, RESULT_FIELDS, field, data)
-    capi.check(capi.lib().wo_temperature_upload(planet.handle, field.encode(), capi.ptr(a), a.nbytes), "wo_temperature_upload")
+    CB.upload(planet, BLOCK, field, data)
 
 
 def download(planet: TP.Planet, field: str) -> np.ndarray:
     """One field of the planet's temperature block by the reference's result key."""
-    ty = dict(RESULT_FIELDS).get(field)
-    if ty is None:
-        raise KeyError(field)
-    out = np.empty(planet.numRegions, ty)
-    capi.check(capi.lib().wo_temperature_download(planet.handle, field.encode(), capi.ptr(out), out.nbytes), "wo_temperature_download")
-    return out
+    return CB.download(planet, BLOCK, field)
 
 
 def info(planet: TP.Planet) -> dict:
     """The scalars of the planet's last compute_temperature: oceanWarmthPasses, smoothPasses, the kernel launches of the call."""
     return dict(getattr(planet, "temperature_info", {}))
-
-
-def checked_inputs(n: int, result, required, known, what: str) -> dict:
-    """The fields of a caller's result dict that the block knows, checked; the required ones must be there."""
-    if result is None:
-        return {}
-    missing = [k for k in required if result.get(k) is None]
-    if missing:
-        raise ValueError(f"{what} lacks {missing}")
-    if known is WD.RESULT_FIELDS:
-        return {k: OD._wind_field(n, k, v) for k, v in result.items() if k in dict(known) and v is not None}
-    return {k: _field(n, known, k, v) for k, v in result.items() if k in dict(known) and v is not None}
 
 
 def compute_temperature(planet: TP.Planet, r_xyz, r_elevation, wind_result=None, ocean_result=None, precip_result=None, temperature_offset=0,
@@ -85,13 +54,8 @@ def compute_temperature(planet: TP.Planet, r_xyz, r_elevation, wind_result=None,
     WIND_INPUTS / OCEAN_INPUTS / PRECIP_INPUTS are required, other result keys are uploaded too, anything else is ignored).
     fields: the result keys to bring back (default: all).  Every argument is checked before any device work."""
     n = planet.numRegions
-    if r_xyz is not None and np.asarray(r_xyz).size != 3 * n:
-        raise ValueError(f"r_xyz has {np.asarray(r_xyz).size} values, expected 3 * {n}")
-    e = None
-    if r_elevation is not None:
-        e = np.ascontiguousarray(r_elevation, dtype=np.float32).reshape(-1)
-        if e.size != n:
-            raise ValueError(f"r_elevation has {e.size} values, expected {n}")
+    CB.check_xyz(n, r_xyz)
+    e = CB.elevation_arg(n, r_elevation)
     offset = float(temperature_offset)
     if offset != offset:
         raise ValueError("temperature_offset must be a number")
@@ -99,15 +63,12 @@ def compute_temperature(planet: TP.Planet, r_xyz, r_elevation, wind_result=None,
         unknown = [k for k in fields if k not in dict(RESULT_FIELDS)]
         if unknown:
             raise KeyError(unknown[0])
-    wind_up = checked_inputs(n, wind_result, WIND_INPUTS, WD.RESULT_FIELDS, "wind_result")
-    ocean_up = checked_inputs(n, ocean_result, OCEAN_INPUTS, OD.RESULT_FIELDS, "ocean_result")
-    precip_up = checked_inputs(n, precip_result, PRECIP_INPUTS, PD.RESULT_FIELDS, "precip_result")
-    for k, a in wind_up.items():
-        OD.upload_wind(planet, k, a)
-    for k, a in ocean_up.items():
-        PD.upload_ocean(planet, k, a)
-    for k, a in precip_up.items():
-        upload_precip(planet, k, a)
+    wind_up = CB.checked_inputs(n, wind_result, WIND_INPUTS, WD.BLOCK, "wind_result")
+    ocean_up = CB.checked_inputs(n, ocean_result, OCEAN_INPUTS, OD.BLOCK, "ocean_result")
+    precip_up = CB.checked_inputs(n, precip_result, PRECIP_INPUTS, PD.BLOCK, "precip_result")
+    CB.upload_inputs(planet, WD.BLOCK, wind_up)
+    CB.upload_inputs(planet, OD.BLOCK, ocean_up)
+    CB.upload_inputs(planet, PD.BLOCK, precip_up)
     raw = np.zeros(4, np.int32)
     capi.check(capi.lib().wo_compute_temperature(planet.handle, n, capi.ptr(e), offset, capi.ptr(raw)), "computeTemperature")
     planet.temperature_info = dict(zip(INFO_FIELDS, (int(v) for v in raw[:3])))

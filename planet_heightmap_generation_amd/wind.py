@@ -10,6 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import capi
+from . import climate_blocks as CB
 from . import terrain_post as TP
 
 # the reference's result keys in the order it sets them (js/wind.js:649-683), with the dtype of each typed array
@@ -21,7 +22,8 @@ RESULT_FIELDS = (
     ("r_continentality", np.float32), ("r_coastDistLand", np.int32), ("r_plateContinentality", np.float32),
     ("r_eastX", np.float32), ("r_eastY", np.float32), ("r_eastZ", np.float32), ("r_northX", np.float32), ("r_northY", np.float32), ("r_northZ", np.float32),
 )
-ITCZ_SAMPLES = 360
+BLOCK = CB.Block("wo_wind", RESULT_FIELDS)
+ITCZ_SAMPLES = CB.ITCZ_SAMPLES
 
 
 def smoothstep(edge0, edge1, x):
@@ -46,13 +48,8 @@ def _ocean_ids(plate_is_ocean) -> np.ndarray:
 
 def check_wind_args(n: int, r_xyz, r_elevation, plate_is_ocean, r_plate, seed, axial_tilt):
     """The arguments as the C ABI takes them; refused before any device work otherwise."""
-    if r_xyz is not None and np.asarray(r_xyz).size != 3 * n:
-        raise ValueError(f"r_xyz has {np.asarray(r_xyz).size} values, expected 3 * {n}")
-    e = None
-    if r_elevation is not None:
-        e = np.ascontiguousarray(r_elevation, dtype=np.float32).reshape(-1)
-        if e.size != n:
-            raise ValueError(f"r_elevation has {e.size} values, expected {n}")
+    CB.check_xyz(n, r_xyz)
+    e = CB.elevation_arg(n, r_elevation)
     if r_plate is None:
         raise ValueError("r_plate is required")
     plate = np.asarray(r_plate)
@@ -70,12 +67,12 @@ def check_wind_args(n: int, r_xyz, r_elevation, plate_is_ocean, r_plate, seed, a
 
 def download(planet: TP.Planet, field: str) -> np.ndarray:
     """One field of the planet's wind block by the reference's result key."""
-    ty = dict(RESULT_FIELDS).get(field)
-    if ty is None:
-        raise KeyError(field)
-    out = np.empty(ITCZ_SAMPLES if field.startswith("itcz") else planet.numRegions, ty)
-    capi.check(capi.lib().wo_wind_download(planet.handle, field.encode(), capi.ptr(out), out.nbytes), "wo_wind_download")
-    return out
+    return CB.download(planet, BLOCK, field)
+
+
+def upload(planet: TP.Planet, field: str, data) -> None:
+    """Set one field of the planet's wind block from the host by its result key."""
+    CB.upload(planet, BLOCK, field, data)
 
 
 def compute_wind(planet: TP.Planet, r_xyz, r_elevation, plate_is_ocean, r_plate, seed, axial_tilt=23.5, fields=None) -> dict:

@@ -151,7 +151,7 @@ def test_second_call_equals_fresh_planet():
 def test_refusals_leave_the_planet_usable():
     """No wind block, a partially uploaded block, a wrong numRegions, an unknown download key, a short out, a NULL planet: each
     fails with a message, and the planet still gives the golden afterwards."""
-    from planet_heightmap_generation_amd import capi, ocean as OD
+    from planet_heightmap_generation_amd import capi, ocean as OD, wind as WD
     case = OC.golden_case("ocean_N10000_wedge_s1")
     N = case["N"]
     buf = np.zeros(N, np.float32)
@@ -161,12 +161,12 @@ def test_refusals_leave_the_planet_usable():
         assert L.wo_compute_ocean_currents(pl.handle, N, None) != 0 and "no wind result" in capi.last_error()
         assert L.wo_ocean_download(pl.handle, b"r_ocean_speed_summer", capi.ptr(buf), buf.nbytes) != 0 and "no ocean result" in capi.last_error()
         for k in OC.WIND_INPUTS[:-1]:                       # everything but itczLatsWinter
-            OD.upload_wind(pl, k, case["wind"][k])
+            WD.upload(pl, k, case["wind"][k])
         assert L.wo_compute_ocean_currents(pl.handle, N, None) != 0 and "no wind result" in capi.last_error()
         assert L.wo_wind_upload(pl.handle, b"nope", capi.ptr(buf), buf.nbytes) != 0 and "unknown field" in capi.last_error()
         assert L.wo_wind_upload(pl.handle, b"r_lat", capi.ptr(buf), buf.nbytes - 4) != 0 and "bytes" in capi.last_error()
         assert L.wo_wind_upload(pl.handle, b"r_lat", None, buf.nbytes) != 0 and "null pointer" in capi.last_error()
-        OD.upload_wind(pl, "itczLatsWinter", case["wind"]["itczLatsWinter"])
+        WD.upload(pl, "itczLatsWinter", case["wind"]["itczLatsWinter"])
         assert L.wo_compute_ocean_currents(pl.handle, N - 1, None) != 0 and "numRegions" in capi.last_error()
         assert L.wo_compute_ocean_currents(None, N, None) != 0 and "wo_compute_ocean_currents" in capi.last_error()
         got, info = _ocean(pl, case)

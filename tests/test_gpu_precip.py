@@ -167,7 +167,7 @@ def test_refusals_leave_the_planet_usable_and_memory_is_steady():
     """No wind block, a wind block but no ocean block, a partially uploaded ocean block, a wrong numRegions, an unknown key, a short
     buffer, NULL pointers: each fails with a message and leaves the device bytes unchanged, and the planet still gives the golden
     afterwards.  The first call grows the device memory by the precipitation block alone; the second and third leave it as it is."""
-    from planet_heightmap_generation_amd import capi, ocean as OD, precipitation as PD
+    from planet_heightmap_generation_amd import capi, ocean as OD, precipitation as PD, wind as WD
     case = PC.golden_case("precip_config1_N10000_s1")
     N = case["N"]
     buf = np.zeros(N, np.float32)
@@ -179,17 +179,17 @@ def test_refusals_leave_the_planet_usable_and_memory_is_steady():
         assert L.wo_precip_download(pl.handle, b"r_precip_summer", capi.ptr(buf), buf.nbytes) != 0 and "no precipitation result" in capi.last_error()
         assert _device_bytes() == m0
         for k in PC.WIND_INPUTS:
-            OD.upload_wind(pl, k, case["wind"][k])
+            WD.upload(pl, k, case["wind"][k])
         m1 = _device_bytes()
         assert L.wo_compute_precipitation(pl.handle, N, None, 0.0, 0.3, None) != 0 and "no ocean result" in capi.last_error()
         assert _device_bytes() == m1
-        PD.upload_ocean(pl, "r_ocean_warmth_summer", case["warm"]["r_ocean_warmth_summer"])
+        OD.upload(pl, "r_ocean_warmth_summer", case["warm"]["r_ocean_warmth_summer"])
         m2 = _device_bytes()
         assert L.wo_compute_precipitation(pl.handle, N, None, 0.0, 0.3, None) != 0 and "no ocean result" in capi.last_error()
         assert L.wo_ocean_upload(pl.handle, b"nope", capi.ptr(buf), buf.nbytes) != 0 and "unknown field" in capi.last_error()
         assert L.wo_ocean_upload(pl.handle, b"r_ocean_warmth_winter", capi.ptr(buf), buf.nbytes - 4) != 0 and "bytes" in capi.last_error()
         assert L.wo_ocean_upload(pl.handle, b"r_ocean_warmth_winter", None, buf.nbytes) != 0 and "null pointer" in capi.last_error()
-        PD.upload_ocean(pl, "r_ocean_warmth_winter", case["warm"]["r_ocean_warmth_winter"])
+        OD.upload(pl, "r_ocean_warmth_winter", case["warm"]["r_ocean_warmth_winter"])
         assert L.wo_compute_precipitation(pl.handle, N - 1, None, 0.0, 0.3, None) != 0 and "numRegions" in capi.last_error()
         assert L.wo_compute_precipitation(None, N, None, 0.0, 0.3, None) != 0 and "wo_compute_precipitation" in capi.last_error()
         assert _device_bytes() == m2

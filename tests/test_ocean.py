@@ -105,7 +105,7 @@ class _NoDevicePlanet:
 
 
 def test_python_argument_checks_refuse_before_device_work():
-    from planet_heightmap_generation_amd import ocean as OD
+    from planet_heightmap_generation_amd import ocean as OD, wind as WD
     p, n = _NoDevicePlanet(), 100
     xyz, e = np.zeros(3 * n, np.float32), np.zeros(n, np.float32)
     wind = {k: np.zeros(360 if k.startswith("itcz") else n, np.uint8 if k == "r_isLand" else np.float32) for k in OD.WIND_INPUTS}
@@ -120,7 +120,7 @@ def test_python_argument_checks_refuse_before_device_work():
     with pytest.raises(KeyError):
         OD.download(p, "_oceanTiming")
     with pytest.raises(KeyError):
-        OD.upload_wind(p, "r_cosLat", e)
+        WD.upload(p, "r_cosLat", e)
     assert OD.WIND_INPUTS == OC.WIND_INPUTS
     assert [k for k, _ in OD.RESULT_FIELDS] == [k for k in OC.golden_case("ocean_config1_N10000_s1")["meta"]["keys"] if k != "_oceanTiming"]
 

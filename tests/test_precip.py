@@ -155,7 +155,7 @@ class _NoDevicePlanet:
 
 
 def test_python_argument_checks_refuse_before_device_work():
-    from planet_heightmap_generation_amd import precipitation as PD
+    from planet_heightmap_generation_amd import ocean as OD, precipitation as PD
     p, n = _NoDevicePlanet(), 100
     xyz, e = np.zeros(3 * n, np.float32), np.zeros(n, np.float32)
     ty = dict(r_isLand=np.uint8, r_coastDistLand=np.int32)
@@ -180,7 +180,7 @@ def test_python_argument_checks_refuse_before_device_work():
     with pytest.raises(KeyError):
         PD.download(p, "_precipTiming")
     with pytest.raises(KeyError):
-        PD.upload_ocean(p, "r_ocean_depth", e)
+        OD.upload(p, "r_ocean_depth", e)
     assert PD.WIND_INPUTS == tuple(PC.golden_case("precip_config1_N10000_s1")["meta"]["inputs"])[:len(PD.WIND_INPUTS)]
     assert set(PD.WIND_INPUTS) == set(PC.WIND_INPUTS) and PD.OCEAN_INPUTS == PC.OCEAN_INPUTS
     assert [k for k, _ in PD.RESULT_FIELDS] == sorted(k for k in PC.golden_case("precip_config1_N10000_s1")["meta"]["keys"] if k != "_precipTiming")
