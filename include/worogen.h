@@ -160,6 +160,32 @@ int wo_assign_elevation(wo_planet* p, const int32_t* r_plate, const wo_plate_tab
                         float* r_elevation, float* r_stress, float* debugLayers,
                         int32_t* mountain_r, int32_t* coastline_r, int32_t* ocean_r, int32_t* setCounts);
 
+/* ------------------------------------------------ buildSuperPlates (js/super-plates.js:16-273) -- */
+/* buildSuperPlates(mesh, r_plate, plateSeeds, plateVec, plateIsOcean, plateDensity) -> { r_superPlate, superPlateVec,
+ *                  superPlateIsOcean, superPlateDensity, numSuperPlates }            js/super-plates.js:16,272
+ * The per-cell passes run on the device, the plate-level part (at most WO_SUPER_MAX_PLATES plates) in native host code.
+ * plateSeeds is the Set in iteration order throughout; a position in it is a plate's "slot". */
+#define WO_SUPER_MAX_PLATES 1024
+/* The device half: plate areas (js/super-plates.js:21-25) and the plate adjacency graph (:29-39) over the planet's CSR.
+ * area[numPlateSeeds]: cells per plate, by slot.  firstSlot[numPlateSeeds * numPlateSeeds]: for the ordered pair (a, b),
+ * the smallest adjList index at which a cell of plate a sees a cell of plate b, 0xFFFFFFFF where it never does; sorted by
+ * it, a plate's neighbours are in the insertion order of the reference's plateNeighbors[a] Set.  An r_plate entry that is
+ * not in plateSeeds, a repeated seed and more than WO_SUPER_MAX_PLATES seeds are errors. */
+int wo_super_plate_tables(wo_planet* p, const int32_t* r_plate, const int32_t* plateSeeds, int32_t numPlateSeeds,
+                          int32_t* area, uint32_t* firstSlot);
+/* The host half: connected components of same-kind plates (js/super-plates.js:41-62), farthest-point seeding and the two
+ * Dijkstras (:64-172), area-weighted poles, kinds and densities (:182-270), from the two tables above.  Needs no GPU.
+ * `plates` is dense by plate id (a NaN density is an undefined plateDensity[id]).  plateToSuper[numPlateSeeds]: super plate
+ * per slot; the four super tables have room for numPlateSeeds entries (superPole 3 * numPlateSeeds) and hold *numSuper. */
+int wo_super_plates_group(int32_t numPlateSeeds, const int32_t* plateSeeds, const wo_plate_table* plates,
+                          const int32_t* area, const uint32_t* firstSlot, int32_t* plateToSuper, int32_t* numSuper,
+                          double* superPole, double* superOmega, uint8_t* superIsOcean, double* superDensity);
+/* Both halves and the gather r_superPlate[r] = plateToSuperPlate[r_plate[r]] (js/super-plates.js:177-180) on the device.
+ * r_superPlate: numRegions ints; the super tables as above.  The laps of the call are what wo_last_stage_timing reports. */
+int wo_build_super_plates(wo_planet* p, const int32_t* r_plate, const wo_plate_table* plates,
+                          const int32_t* plateSeeds, int32_t numPlateSeeds, int32_t* r_superPlate, int32_t* numSuper,
+                          double* superPole, double* superOmega, uint8_t* superIsOcean, double* superDensity);
+
 /* ------------------------------------------------ plate projection ----------- */
 /* projectCoarsePlates(mesh, r_xyz, coarseMesh, coarse_xyz, coarse_r_plate, seed, numPlates) -> r_plate
  *                                                                       js/coarse-plates.js:51-117

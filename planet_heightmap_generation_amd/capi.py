@@ -53,6 +53,9 @@ SIGNATURES = {
     "wo_sharpen_ridges": (C.c_int, [_p, _p, _p, _c_i32, _c_f64]),
     "wo_soil_creep": (C.c_int, [_p, _p, _p, _c_i32, _c_f64]),
     "wo_assign_elevation": (C.c_int, [_p, _p, _p, _p, _c_i32, _p, _p, _p, _p, _c_f64, _c_f64, _c_f64, _p, _p, _p, _p, _p, _p, _p]),
+    "wo_super_plate_tables": (C.c_int, [_p, _p, _p, _c_i32, _p, _p]),
+    "wo_super_plates_group": (C.c_int, [_c_i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "wo_build_super_plates": (C.c_int, [_p, _p, _p, _p, _c_i32, _p, _p, _p, _p, _p, _p]),
     "wo_smooth_field": (C.c_int, [_p, _p, _c_i32]),
     "wo_sample_heightmap": (C.c_int, [_p, _p, _c_i32, _c_i32, _p]),
     "wo_synthetic_plates": (C.c_int, [_p, _p, _p, _p, _p]),

@@ -294,6 +294,8 @@ void precip_free(wo_planet* p);
 void temp_free(wo_planet* p);
 // planet.hip: the entry points' handle check (refreshes p->opt from the environment, selects the device)
 bool check_planet(wo_planet* p, const char* fn);
+// planet.hip: drops the stage brackets an earlier erodeComposite left pending (a call that sets p->stageTiming itself calls it first)
+void release_stage_brackets(wo_planet* p);
 // planet.hip: smoothField on a resident field (returns the buffer that holds the result)
 float* smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passes);
 // planet.hip: diffuseOceanWarmth of one season on resident fields with the single-field kernels (seeds a, ping-pongs a and b and

@@ -213,7 +213,7 @@ static int64_t run_solve_patches(wo_planet* p, const Fields& F, double K, double
 }
 
 // The stage brackets of an earlier call, never asked for: their events back to the pool
-static void release_stage_brackets(wo_planet* p) {
+void release_stage_brackets(wo_planet* p) {
     for (auto& b : p->stageBrackets) { p->eventPool.push_back(b.a); p->eventPool.push_back(b.b); }
     p->stageBrackets.clear(); p->stageSeen.clear(); p->stagePending = false;
 }

@@ -122,6 +122,15 @@ bool flood_pass23_host(float* e, double carveStrength, FloodScratch& S, const st
 void smooth_reconnect_plates_host(int32_t N, const int32_t* off, const int32_t* adj, int32_t* r_plate, int32_t numSeeds,
                                   const int32_t* plateSeeds, int32_t numPasses);
 
+// super_plates_host.cc — js/super-plates.js
+// slotOf[max seed + 1]: plate id -> position in plateSeeds, -1 for the ids in between.  Throws std::invalid_argument on a
+// negative or repeated seed and on more than WO_SUPER_MAX_PLATES seeds.
+void super_plate_slots(int32_t numSeeds, const int32_t* plateSeeds, std::vector<int32_t>& slotOf);
+struct SuperPlateTables { int32_t* plateToSuper; double* pole; double* omega; uint8_t* isOcean; double* density; };   // per slot; the last four per super plate
+// js/super-plates.js:41-172 and :182-270 from the per-slot areas and first slots; returns numSuperPlates.  Every seed must lie inside the plate table.
+int32_t super_plates_group_host(int32_t P, const int32_t* plateSeeds, int32_t numIds, const uint8_t* hasVec, const double* pole, const double* omega,
+                                const uint8_t* isOcean, const double* density, const int32_t* area, const uint32_t* firstSlot, const SuperPlateTables& out);
+
 // error slot used by every extern "C" entry point (thread-local)
 void set_error(const std::string& msg);
 

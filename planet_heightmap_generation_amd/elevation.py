@@ -33,9 +33,10 @@ class SimplexNoise:
         capi.check(capi.lib().wo_noise_tables(self.seed, capi.ptr(self.perm), capi.ptr(self.pm12)), "wo_noise_tables")
 
 
-def _table(ids_is_ocean, vec: dict, density: dict):
-    """Dense-by-id arrays from the reference's keyed objects."""
-    ids = set(vec) | set(density) | set(ids_is_ocean)
+def _table(ids_is_ocean, vec: dict, density: dict, ids=()):
+    """Dense-by-id arrays from the reference's keyed objects.  ids: further plate ids the table must have room for (a plate with no
+    vector, no density and no ocean flag has no key)."""
+    ids = set(vec) | set(density) | set(ids_is_ocean) | {int(i) for i in ids}
     n = (max(ids) + 1) if ids else 1
     has = np.zeros(n, np.uint8); pole = np.zeros(3 * n, np.float64); omega = np.zeros(n, np.float64)
     oc = np.zeros(n, np.uint8); dens = np.full(n, np.nan, np.float64)

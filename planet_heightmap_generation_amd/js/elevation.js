@@ -3,22 +3,7 @@
 // _timing:[{stage, ms}] }.  Per-cell work runs in HIP kernels, the order-defined graph traversals in native host
 // code; this module only converts the reference's keyed objects / Sets into dense tables and back.
 import addon, { planetFor } from './native.js';
-
-const LAYERS = ['base', 'tectonic', 'noise', 'interior', 'coastal', 'ocean', 'hotspot', 'tecActivity', 'margins', 'backArc', 'foldRidge', 'orogenicPower'];
-
-function denseTable(isOceanSet, vec, density) {
-    let maxId = -1;
-    for (const k of Object.keys(vec)) maxId = Math.max(maxId, +k);
-    for (const k of Object.keys(density)) maxId = Math.max(maxId, +k);
-    for (const k of isOceanSet) maxId = Math.max(maxId, +k);
-    const n = maxId + 1;
-    const t = { numIds: n, hasVec: new Uint8Array(n), pole: new Float64Array(3 * n), omega: new Float64Array(n),
-                isOcean: new Uint8Array(n), density: new Float64Array(n).fill(NaN) };
-    for (const k of Object.keys(vec)) { const id = +k, v = vec[k]; t.hasVec[id] = 1; t.pole.set(v.pole, 3 * id); t.omega[id] = v.omega; }
-    for (const k of isOceanSet) t.isOcean[+k] = 1;
-    for (const k of Object.keys(density)) t.density[+k] = density[k];
-    return t;
-}
+import { denseTable, LAYERS } from './plate-table.js';
 
 export function assignElevation(mesh, r_xyz, plateIsOcean, r_plate, plateVec, plateSeeds, noise, noiseMag, seed, spread, plateDensity, superPlateData) {
     const p = planetFor(mesh, r_xyz);

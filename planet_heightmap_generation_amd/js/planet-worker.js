@@ -1,13 +1,15 @@
 // worker_threads counterpart of the reference's Web Worker (js/planet-worker.js) for the part of its message protocol
-// that is the device path: the retained state W (:277-292), `reapply` (:341-440), `computeClimate` (:579-677) and the
-// dispatcher (:944-954).
+// that is the device path: the retained state W (:277-292), `reapply` (:341-440), `editRecompute` (:442-577),
+// `computeClimate` (:579-677) and the dispatcher (:944-954).
 //
 //   cmd 'retain'   { mesh: { numRegions, adjOffset, adjList, triangles? }, r_xyz, neighborDist?, prePostElev, seed, r_hotspot?,
-//                    r_plate?, plateIsOcean? }
+//                    r_plate?, plateIsOcean?, plateSeeds?, plateVec?, plateDensity?, P? }
 //                  What `generate` leaves in W for later reapplies, handed over by the caller (plate generation and ocean /
 //                  land assignment are the reference's own host code and stay where they are).  The mesh, positions and the
 //                  pre-erosion field go to HBM ONCE and stay there.  r_plate (Int32Array) and plateIsOcean (the ids of the
-//                  oceanic plates: a Set, an array or an Int32Array) are what a later `computeClimate` needs.
+//                  oceanic plates: a Set, an array or an Int32Array) are what a later `computeClimate` needs.  plateSeeds (the Set's
+//                  iteration order: an array, a Set or an Int32Array), plateVec ({ id: { pole, omega } }), plateDensity ({ id: density })
+//                  and P (the plate count asked of `generate`) are what a later `editRecompute` needs on top of them.
 //                  -> { type: 'retained', numRegions }
 //   cmd 'reapply'  { terrainWarp, smoothing, glacialErosion, hydraulicErosion, thermalErosion, ridgeSharpening, skipClimate? }
 //                  restore the pre-erosion field on the device (no upload), runPostProcessing resident, triangle
@@ -29,9 +31,20 @@
 //                  reference posts them:
 //                  -> { type: 'climateDone', <the 19 climate fields>, climateDebugLayers, _climateTiming: { wind, ocean,
 //                       precipitation, temperature, koppen, workerTotal } }
+//   cmd 'editRecompute' { plateIsOcean, plateDensity, nMag, <the six sliders>, skipClimate? }   (:442-577)
+//                  what the editor sends when a plate changes kind: buildSuperPlates (when W.P >= 8), assignElevation, runPostProcessing
+//                  resident with the call's own hotspot layer, triangle elevations — every stage native, the field never leaves the
+//                  device between them.  The new pre-erosion field becomes W.prePostElev (on the device), so a following `reapply`
+//                  starts from the edited planet.  Climate is not run here (skipClimate is reported as true and the 19 climate fields
+//                  are null, as for reapply); a following `computeClimate` serves it with the edited plateIsOcean.  Needs a state
+//                  retained with r_plate, plateSeeds and plateVec: a state left by `importHeightmap` has synthetic plates without
+//                  poles and is refused.
+//                  -> { type: 'editDone', skipClimate: true, prePostElev, r_elevation, t_elevation, mountain_r, coastline_r, ocean_r,
+//                       r_stress, <the 19 climate fields: null>, debugLayers, _editTiming, _timing, _postTiming }
 //   cmd 'dispose'  frees the retained state -> { type: 'disposed' }
 //   progress / errors exactly as the reference posts them: { type: 'progress', pct, label }, { type: 'error', message, stack };
-//   an unknown command answers `Unknown command: <cmd>` (:952).
+//   an unknown command answers `Unknown command: <cmd>` (:952).  `generate` is not served: plate generation and ocean / land
+//   assignment are the reference's own host code.
 //
 // Usage (Node >= 12):  const w = new Worker(new URL('./planet-worker.js', import.meta.url)); w.postMessage({ cmd: 'retain', ... })
 import { parentPort } from 'worker_threads';
@@ -41,6 +54,8 @@ import { runPostProcessingResident } from './post-processing.js';
 import { buildSphere, computeNeighborDist, generateTriangleCenters } from './sphere-mesh.js';
 import { platesFromDevice } from './heightmap-import.js';
 import { OCEAN_KEYS, PRECIP_KEYS, TEMP_KEYS, downloadAll } from './climate-blocks.js';
+import { denseTable, LAYERS } from './plate-table.js';
+import { SimplexNoise } from './simplex-noise.js';
 
 let W = null;          // retained state (js/planet-worker.js:22)
 
@@ -51,7 +66,7 @@ function releaseRetained() { if (W && W.planet) addon.planetDestroy(W.planet); W
 
 function handleRetain(data) {
     try {
-        const { mesh, r_xyz, neighborDist, prePostElev, seed, r_hotspot, r_plate, plateIsOcean } = data;
+        const { mesh, r_xyz, neighborDist, prePostElev, seed, r_hotspot, r_plate, plateIsOcean, plateSeeds, plateVec, plateDensity, P } = data;
         if (!mesh || !(mesh.adjOffset instanceof Int32Array) || !(mesh.adjList instanceof Int32Array)) throw new TypeError('retain: mesh.adjOffset / mesh.adjList must be Int32Arrays');
         if (!(r_xyz instanceof Float32Array) || !(prePostElev instanceof Float32Array)) throw new TypeError('retain: r_xyz and prePostElev must be Float32Arrays');
         if (r_plate !== undefined && r_plate !== null && (!(r_plate instanceof Int32Array) || r_plate.length !== mesh.numRegions)) throw new TypeError('retain: r_plate must be an Int32Array of numRegions entries');
@@ -62,7 +77,8 @@ function handleRetain(data) {
         addon.planetSaveState(planet);                  // W.prePostElev, device copy
         W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles || null, seed, hasHotspot: !!r_hotspot,
               r_plate: r_plate || null, plateIsOcean: (plateIsOcean !== undefined && plateIsOcean !== null) ? Int32Array.from(plateIsOcean) : null,
-              cachedWind: null, cachedOcean: null };
+              plateSeeds: (plateSeeds !== undefined && plateSeeds !== null) ? Int32Array.from(plateSeeds) : null, plateVec: plateVec || null,
+              plateDensity: Object.assign({}, plateDensity || {}), P: P || 0, cachedWind: null, cachedOcean: null };
         parentPort.postMessage({ type: 'retained', numRegions: mesh.numRegions });
     } catch (err) {
         parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
@@ -134,7 +150,8 @@ function handleImportHeightmap(data) {
         t0 = performance.now();
         releaseRetained();
         const planet = addon.planetCreate(defaultContext(), mesh.numRegions, mesh.adjOffset, mesh.adjList, r_xyz, neighborDist);
-        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles, seed, hasHotspot: false, r_plate: null, plateIsOcean: null, cachedWind: null, cachedOcean: null };
+        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles, seed, hasHotspot: false, r_plate: null, plateIsOcean: null,
+              plateSeeds: null, plateVec: null, plateDensity: {}, P: 0, cachedWind: null, cachedOcean: null };
         const prePostElev = addon.sampleHeightmap(planet, grayscale, imageWidth, imageHeight, true);
         addon.planetSaveState(planet);                  // W.prePostElev, device copy
         timing.push({ stage: 'Sample heightmap', ms: performance.now() - t0 });
@@ -173,6 +190,76 @@ function handleImportHeightmap(data) {
             _params: { N, P: 0, jitter, nMag: 0, numContinents: 0, smoothing, terrainWarp, hydraulicErosion, thermalErosion, ridgeSharpening, glacialErosion, seed }
         };
         parentPort.postMessage(result, [r_xyz.buffer, t_xyz.buffer, r_plate.buffer, prePostElev.buffer, r_elevation.buffer, t_elevation.buffer, r_stress.buffer]);
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
+// addon.buildSuperPlates' result as the dense table addon.assignElevation takes for its super plates (ids 0 .. n - 1, all with a vector)
+function superPlateTable(res) {
+    const n = res.numSuperPlates;
+    return { numIds: n, hasVec: new Uint8Array(n).fill(1), pole: res.pole, omega: res.omega, isOcean: res.isOcean, density: res.density };
+}
+
+// js/planet-worker.js:442-577 with every stage native, on W.planet; the field stays on the device from assignElevation to the
+// end of the post-processing
+function handleEditRecompute(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for editRecompute (not served by the device worker before retain)' }); return; }
+    const missing = ['r_plate', 'plateSeeds', 'plateVec'].filter((k) => !W[k]);
+    if (missing.length) {
+        parentPort.postMessage({ type: 'error', message: `editRecompute: the retained state has no ${missing.join(' and ')} (pass them to retain; the synthetic plates of importHeightmap have no poles, and edits of an imported planet are not served)` });
+        return;
+    }
+    getClimateParams(data);                              // the parameters persist in W for the computeClimate that follows (:446)
+    try {
+        const tTotal0 = performance.now();
+        progress(0, 'Rebuilding elevation\u2026');
+        W.plateIsOcean = Int32Array.from(data.plateIsOcean);
+        W.plateDensity = Object.assign({}, data.plateDensity);
+        const { planet, numRegions: N, r_plate, plateSeeds, plateVec, seed } = W;
+        const nMag = data.nMag, spread = 5;
+        const plates = denseTable(W.plateIsOcean, plateVec, W.plateDensity, plateSeeds);
+
+        let sup = null;
+        if ((W.P || 0) >= 8) sup = addon.buildSuperPlates(planet, r_plate, plates, plateSeeds);
+
+        let t0 = performance.now();
+        if (!W.noise) W.noise = new SimplexNoise(seed);
+        const res = addon.assignElevation(planet, r_plate, plates, plateSeeds, sup ? sup.r_superPlate : null, sup ? superPlateTable(sup) : null,
+                                          W.noise.perm, W.noise.pm12, nMag, seed, spread, true);
+        const _timing = addon.lastStageTiming(planet);
+        const tElev = performance.now() - t0;
+        const debugLayers = {};
+        LAYERS.forEach((name, i) => { debugLayers[name] = res.debugLayers.subarray(i * N, (i + 1) * N); });
+        if (sup) debugLayers.superPlates = new Float32Array(sup.r_superPlate);
+        const prePostElev = res.r_elevation;
+
+        progress(50, 'Eroding terrain\u2026');
+        t0 = performance.now();
+        W.cachedWind = null; W.cachedOcean = null;     // the elevation changes: the wind and ocean blocks no longer belong to it
+        addon.planetSaveState(planet);                  // the new W.prePostElev, device copy: assignElevation left the field resident
+        addon.planetUploadHotspot(planet, debugLayers.hotspot);
+        const r_elevation = new Float32Array(N);
+        const { dl_erosionDelta, postTiming } = runPostProcessingResident(planet, N, r_elevation, data, seed, true);
+        const tPost = performance.now() - t0;
+        debugLayers.erosionDelta = dl_erosionDelta;
+
+        progress(75, 'Computing triangle elevations\u2026');
+        t0 = performance.now();
+        const t_elevation = W.triangles ? addon.triangleElevations(W.triangles, r_elevation) : new Float32Array(0);
+        const tTriElev = performance.now() - t0;
+
+        const climate = {};
+        for (const k of CLIMATE_NULLS) climate[k] = null;
+        const result = {
+            type: 'editDone', skipClimate: true, prePostElev, r_elevation, t_elevation,
+            mountain_r: Array.from(res.mountain), coastline_r: Array.from(res.coastline), ocean_r: Array.from(res.ocean), r_stress: res.r_stress,
+            ...climate, debugLayers,
+            _editTiming: { elevation: tElev, postProcessing: tPost, wind: 0, ocean: 0, precipitation: 0, temperature: 0, triangleElevations: tTriElev,
+                           retainState: 0, workerTotal: performance.now() - tTotal0 },
+            _timing, _postTiming: postTiming
+        };
+        parentPort.postMessage(result, [prePostElev.buffer, r_elevation.buffer, t_elevation.buffer, res.r_stress.buffer]);
     } catch (err) {
         parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
     }
@@ -262,7 +349,8 @@ parentPort.on('message', (data) => {
         case 'importHeightmap': handleImportHeightmap(data); break;
         case 'dispose': releaseRetained(); parentPort.postMessage({ type: 'disposed' }); break;
         case 'computeClimate': handleComputeClimate(data); break;
-        case 'generate': case 'editRecompute':
+        case 'editRecompute': handleEditRecompute(data); break;
+        case 'generate':
             parentPort.postMessage({ type: 'error', message: `Command not served by the device worker (host stages of the reference): ${cmd}` });
             break;
         default: parentPort.postMessage({ type: 'error', message: `Unknown command: ${cmd}` });

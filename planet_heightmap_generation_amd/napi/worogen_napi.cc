@@ -390,6 +390,36 @@ napi_value AssignElevation(napi_env env, napi_callback_info info) {
     return o;
 }
 
+// buildSuperPlates(planet, r_plate, plates, plateSeeds) -> { r_superPlate:Int32Array, numSuperPlates, pole:Float64Array(3 n), omega:Float64Array(n),
+//                                                            isOcean:Uint8Array(n), density:Float64Array(n) }   (plates as for assignElevation)
+napi_value BuildSuperPlates(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    size_t n, ns;
+    int32_t* r_plate = (int32_t*)a.ta(1, napi_int32_array, &n); if (!a.ok) return nullptr;
+    if (!regions_ok(env, p, n, "r_plate")) return nullptr;
+    wo_plate_table T{};
+    if (!read_table(a, a.argv[2], &T)) return nullptr;
+    int32_t* seeds = (int32_t*)a.ta(3, napi_int32_array, &ns); if (!a.ok) return nullptr;
+    void* rs; napi_value ra = make_ta(env, napi_int32_array, n, 4, &rs);
+    if (!ra) return nullptr;
+    const size_t room = ns > 0 ? ns : 1;
+    std::vector<double> pole(3 * room), omega(room), density(room); std::vector<uint8_t> isOcean(room);
+    int32_t numSuper = 0;
+    if (wo_build_super_plates(p, r_plate, &T, seeds, (int32_t)ns, (int32_t*)rs, &numSuper, pole.data(), omega.data(), isOcean.data(), density.data()))
+        return throw_wo(env, "buildSuperPlates");
+    const size_t m = (size_t)numSuper;
+    void *dp, *dw, *dn, *di;
+    napi_value pa = make_ta(env, napi_float64_array, 3 * m, 8, &dp), wa = make_ta(env, napi_float64_array, m, 8, &dw);
+    napi_value na = make_ta(env, napi_float64_array, m, 8, &dn), ia = make_ta(env, napi_uint8_array, m, 1, &di);
+    if (!pa || !wa || !na || !ia) return nullptr;
+    std::memcpy(dp, pole.data(), 3 * m * 8); std::memcpy(dw, omega.data(), m * 8); std::memcpy(dn, density.data(), m * 8); std::memcpy(di, isOcean.data(), m);
+    napi_value o, cnt; napi_create_object(env, &o); napi_create_int32(env, numSuper, &cnt);
+    set_prop(env, o, "r_superPlate", ra); set_prop(env, o, "numSuperPlates", cnt);
+    set_prop(env, o, "pole", pa); set_prop(env, o, "omega", wa); set_prop(env, o, "isOcean", ia); set_prop(env, o, "density", na);
+    return o;
+}
+
 // smoothField(planet, field Float32Array (in place), passes)
 napi_value SmoothField(napi_env env, napi_callback_info info) {
     PLANET_AND_ELEV();
@@ -766,7 +796,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"warpTerrainResident", WarpTerrainResident}, {"smoothElevationResident", SmoothElevationResident},
         {"erodeCompositeResident", ErodeCompositeResident}, {"sharpenRidgesResident", SharpenRidgesResident},
         {"applySoilCreepResident", ApplySoilCreepResident}, {"timerStart", TimerStart}, {"timerStopMs", TimerStopMs},
-        {"lastStageTiming", LastStageTiming}, {"lastErodeStats", LastErodeStats}, {"assignElevation", AssignElevation},
+        {"lastStageTiming", LastStageTiming}, {"lastErodeStats", LastErodeStats}, {"assignElevation", AssignElevation}, {"buildSuperPlates", BuildSuperPlates},
         {"projectCoarsePlates", ProjectCoarsePlates}, {"smoothField", SmoothField}, {"smoothAndReconnectPlates", SmoothAndReconnectPlates},
         {"diffuseOceanWarmth", DiffuseOceanWarmth}, {"computeWindConvergence", WindConvergence}, {"advectMoisture", AdvectMoisture},
         {"landComponents", LandComponents}, {"sampleHeightmap", SampleHeightmap}, {"syntheticPlates", SyntheticPlates},
