@@ -432,6 +432,32 @@ int wo_temperature_upload(wo_planet* p, const char* field, const void* data, int
 int wo_classify_koppen(wo_planet* p, int32_t numRegions, const float* r_elevation);
 int wo_koppen_download(wo_planet* p, uint8_t* out, int64_t outBytes);
 
+/* ------------------------------------------------ map export (js/planet-mesh.js) -------------- */
+/* exportMap / exportMapBatch(types, width)                                                 js/planet-mesh.js:1752-2180
+ *   The equirectangular map of the planet, width x width / 2 pixels, row 0 north, in the reference's six kinds (csrc/map.hip;
+ *   the bodies and the whole contract are in csrc/map_ops.h).  The reference draws its map triangles with WebGL, whose pixels
+ *   differ between GPUs; what it defines, the triangle list and the colour of every region, is reproduced bit for bit, and the
+ *   coverage rule is fixed here: a pixel belongs to the lowest side index one of whose triangles contains its centre (edges
+ *   included, both windings), its region is triangles[side], or -1 where nothing covers it.
+ *   wo_map_raster builds the region map of the planet's resident positions for the mesh's sides (numSides = 3 * numTriangles
+ *   entries of triangles and halfedges, the closing pole fan included) and keeps it on the device in a map block the planet owns
+ *   (4 bytes per pixel; a raster at another width replaces it).  width must be even and from 2 to 32768; numSides a multiple
+ *   of 3; every corner a region of the planet and every half-edge a side of the mesh: otherwise the call fails and the planet
+ *   keeps what it had.  regionMapOut (may be NULL) receives the map, width * width / 2 int32; counts (may be NULL) the numbers
+ *   of covered and uncovered pixels.
+ *   wo_map_color colours the map into RGBA8 (alpha 255), through the reference's colour function per region, its quantiser and
+ *   its gamma table.  r_elevation: numRegions floats, NULL means the planet's resident field.  WO_MAP_BIOME and WO_MAP_KOPPEN
+ *   read the planet's Koppen block and fail with "no Koppen result" without one (the reference falls back silently to the
+ *   colour map; that is not offered).  Pixels nothing covers are black in the three grey kinds and the reference's 0x1a1a2e,
+ *   taken through three r160's SRGBToLinear and the gamma table, in the others.  outBytes must be width * width / 2 * 4.
+ *   wo_map_download copies the resident map (outBytes: its size exactly); wo_map_free drops it, as wo_planet_destroy does. */
+enum { WO_MAP_COLOR = 0, WO_MAP_HEIGHTMAP = 1, WO_MAP_LANDHEIGHTMAP = 2, WO_MAP_LANDMASK = 3, WO_MAP_BIOME = 4, WO_MAP_KOPPEN = 5 };
+int wo_map_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width,
+                  int32_t* regionMapOut, int64_t counts[2]);
+int wo_map_color(wo_planet* p, int32_t type, const float* r_elevation, uint8_t* rgbaOut, int64_t outBytes);
+int wo_map_download(wo_planet* p, int32_t* out, int64_t outBytes);
+int wo_map_free(wo_planet* p);
+
 /* ------------------------------------------------ device-resident variants -------------------- */
 /* The "reapply" pattern (js/planet-worker.js:341-440): fields stay in HBM, only scalars arrive.
  * wo_planet_upload sets the resident r_elevation (and r_isOcean when not NULL); the *_resident

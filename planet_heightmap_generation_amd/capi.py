@@ -81,6 +81,10 @@ SIGNATURES = {
     "wo_temperature_upload": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
     "wo_classify_koppen": (C.c_int, [_p, _c_i32, _p]),
     "wo_koppen_download": (C.c_int, [_p, _p, _c_i64]),
+    "wo_map_raster": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _p, _p]),
+    "wo_map_color": (C.c_int, [_p, _c_i32, _p, _p, _c_i64]),
+    "wo_map_download": (C.c_int, [_p, _p, _c_i64]),
+    "wo_map_free": (C.c_int, [_p]),
     "wo_planet_upload": (C.c_int, [_p, _p, _p]),
     "wo_planet_download": (C.c_int, [_p, _p]),
     "wo_planet_set_halo": (C.c_int, [_p, _p, _c_i32, _p, _c_i32]),

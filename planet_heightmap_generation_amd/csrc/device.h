@@ -51,7 +51,8 @@ enum Family : int {
     FAM_SOLVE_SETUP, FAM_SOLVE_ROUND, FAM_SOLVE_FINAL, FAM_THERMAL_EXCESS, FAM_THERMAL_APPLY,
     FAM_GLAC_INDEX, FAM_ICE_RECV, FAM_ICE_ROUND, FAM_CARVE_SETUP, FAM_CARVE_ROUND, FAM_MORAINE, FAM_GLAC_BLEND,
     FAM_SOLVE_PATCH, FAM_ELEV_COLLISION, FAM_ELEV_MAIN, FAM_PLATE_GRID, FAM_PLATE_PROJECT, FAM_SMOOTH_FIELD,
-    FAM_FLOOD_EVAL, FAM_FLOOD_APPLY, FAM_FLOOD_MISC, FAM_CLIMATE, FAM_BASIN, FAM_BASIN_SORT, FAM_SOLVE_BASIN, FAM_FLOW_TILES, FAM_MISC, FAM_EVENT_PAIR, FAM_EVENT_PAIR_NOOP, FAM_EVENT_PAIR_NOOP2, FAM_COUNT
+    FAM_FLOOD_EVAL, FAM_FLOOD_APPLY, FAM_FLOOD_MISC, FAM_CLIMATE, FAM_BASIN, FAM_BASIN_SORT, FAM_SOLVE_BASIN, FAM_FLOW_TILES, FAM_MISC, FAM_EVENT_PAIR, FAM_EVENT_PAIR_NOOP, FAM_EVENT_PAIR_NOOP2,
+    FAM_MAP_LONLAT, FAM_MAP_FILL, FAM_MAP_SIDES, FAM_MAP_BIG_BOXES, FAM_MAP_RESOLVE, FAM_MAP_REGION_COLORS, FAM_MAP_PIXELS, FAM_COUNT
 };
 extern const char* const kFamilyNames[FAM_COUNT];
 
@@ -201,6 +202,9 @@ struct wo_planet {
     // allocated on the first call of their stage or upload; deleted by wo_planet_destroy (temp_free)
     struct wo_temp_block* temp = nullptr;
     struct wo_koppen_block* koppen = nullptr;
+    // map export (map.hip): the map block — the region map of the last wo_map_raster (4 bytes per pixel), allocated by that call;
+    // deleted by wo_map_free and wo_planet_destroy (map_free)
+    struct wo_map_block* map = nullptr;
 
     // Patch-major mirror of the mesh for erodeComposite (planet.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
@@ -292,6 +296,10 @@ void wind_free(wo_planet* p);
 void ocean_free(wo_planet* p);
 void precip_free(wo_planet* p);
 void temp_free(wo_planet* p);
+// map.hip: drops the map block
+void map_free(wo_planet* p);
+// temp.hip: the class ids of the planet's Koppen block (one byte per cell, on the device), nullptr when it has no Koppen result
+const uint8_t* koppen_classes(const wo_planet* p);
 // planet.hip: the entry points' handle check (refreshes p->opt from the environment, selects the device)
 bool check_planet(wo_planet* p, const char* fn);
 // planet.hip: drops the stage brackets an earlier erodeComposite left pending (a call that sets p->stageTiming itself calls it first)

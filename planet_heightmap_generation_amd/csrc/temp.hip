@@ -109,6 +109,8 @@ void temp_free(wo_planet* p) {
     delete p->koppen; p->koppen = nullptr;
 }
 
+const uint8_t* koppen_classes(const wo_planet* p) { return (p->koppen && p->koppen->valid) ? p->koppen->cls : nullptr; }
+
 static void temp_alloc(wo_planet* p) {
     if (p->temp) return;
     std::unique_ptr<wo_temp_block> block(new wo_temp_block());          // the planet gets the block once it is complete

@@ -1,0 +1,99 @@
+// Counterpart of the reference's exportMap / exportMapBatch (js/planet-mesh.js:1752-2180) on the device, for hosts without WebGL, a
+// page or a <canvas>: the equirectangular map of a planet as RGBA8 pixels and, from them, a PNG file.  The raster and the colouring
+// run in HIP kernels (csrc/map.hip) on the planet bound to `mesh` (native.js: planetFor); the triangle list and the region colours
+// are the reference's bit for bit and the coverage rule is the one csrc/map_ops.h fixes (WebGL's own pixels differ between GPUs).
+// `biome` and `koppen` read the Koppen block that classifyKoppen (js/koppen.js) left on the planet; without one the call throws
+// `no Koppen result`: the reference's silent fallback to the colour map is not offered.  No JavaScript fallback for the device passes.
+import zlib from 'zlib';
+import addon, { planetFor } from './native.js';
+
+// the reference's type names in the order of WO_MAP_COLOR .. WO_MAP_KOPPEN (include/worogen.h)
+export const MAP_TYPES = ['color', 'heightmap', 'landheightmap', 'landmask', 'biome', 'koppen'];
+
+export function mapTypeId(type) {
+    const id = MAP_TYPES.indexOf(type);
+    if (id < 0) throw new RangeError(`exportMap: unknown map type '${type}' (one of ${MAP_TYPES.join(', ')})`);
+    return id;
+}
+
+// exportFilename(type, seed) (:1952-1961)
+export function exportFilename(type, seed) {
+    switch (type) {
+        case 'landmask':       return `orogen-landmask-${seed}.png`;
+        case 'landheightmap':  return `orogen-land-heightmap-${seed}.png`;
+        case 'heightmap':      return `orogen-heightmap-${seed}.png`;
+        case 'biome':          return `orogen-satellite-${seed}.png`;
+        case 'koppen':         return `orogen-climate-${seed}.png`;
+        default:               return `orogen-colormap-${seed}.png`;
+    }
+}
+
+function checkMesh(mesh, width) {
+    if (!mesh || !(mesh.triangles instanceof Int32Array) || !(mesh.halfedges instanceof Int32Array)) throw new TypeError('exportMap: mesh.triangles and mesh.halfedges must be Int32Arrays');
+    if (!(Number.isInteger(width) && width >= 2 && width <= 32768 && width % 2 === 0)) throw new RangeError('exportMap: width must be an even integer from 2 to 32768');
+}
+
+// one raster, one colour pass per type, on a planet handle (what the worker holds); r_elevation null: the planet's resident field
+export function exportMapsOnPlanet(planet, triangles, halfedges, r_elevation, types, width) {
+    const ids = types.map(mapTypeId);
+    const r = addon.mapRaster(planet, triangles, halfedges, width, false);
+    const maps = ids.map((id, k) => ({ type: types[k], rgba: addon.mapColor(planet, id, r_elevation || null, width) }));
+    return { width: r.width, height: r.height, covered: r.covered, uncovered: r.uncovered, maps };
+}
+
+function checkElevation(mesh, r_elevation) {
+    if (!(r_elevation instanceof Float32Array) || r_elevation.length !== mesh.numRegions) throw new RangeError(`exportMap: r_elevation must be a Float32Array of ${mesh.numRegions} entries`);
+}
+
+// exportMapBatch(mesh, r_xyz, r_elevation, types, width) -> { width, height, maps: [{ type, rgba }] }: one raster, one colour pass per type
+export function exportMapBatch(mesh, r_xyz, r_elevation, types, width) {
+    checkMesh(mesh, width);
+    checkElevation(mesh, r_elevation);
+    const res = exportMapsOnPlanet(planetFor(mesh, r_xyz), mesh.triangles, mesh.halfedges, r_elevation, Array.from(types), width);
+    return { width: res.width, height: res.height, maps: res.maps };
+}
+
+// exportMap(mesh, r_xyz, r_elevation, type, width) -> { width, height, rgba }
+export function exportMap(mesh, r_xyz, r_elevation, type, width) {
+    const res = exportMapBatch(mesh, r_xyz, r_elevation, [type], width);
+    return { width: res.width, height: res.height, rgba: res.maps[0].rgba };
+}
+
+// ---- PNG: 8-bit RGBA, filter 0 on every row, one IDAT from zlib.deflateSync; CRC-32 from a table built at load (Node 12 has no
+// zlib.crc32) ----
+const CRC_TABLE = new Uint32Array(256);
+for (let n = 0; n < 256; n++) {
+    let c = n;
+    for (let k = 0; k < 8; k++) c = (c & 1) ? (0xEDB88320 ^ (c >>> 1)) : (c >>> 1);
+    CRC_TABLE[n] = c >>> 0;
+}
+function crc32(buf, from, to) {
+    let c = 0xFFFFFFFF;
+    for (let i = from; i < to; i++) c = CRC_TABLE[(c ^ buf[i]) & 0xFF] ^ (c >>> 8);
+    return (c ^ 0xFFFFFFFF) >>> 0;
+}
+function chunk(kind, body) {
+    const out = Buffer.alloc(12 + body.length);
+    out.writeUInt32BE(body.length, 0);
+    out.write(kind, 4, 4, 'latin1');
+    body.copy(out, 8);
+    out.writeUInt32BE(crc32(out, 4, 8 + body.length), 8 + body.length);
+    return out;
+}
+
+// encodePng(rgba, width, height) -> Uint8Array (the file's bytes)
+export function encodePng(rgba, width, height) {
+    if (!(rgba instanceof Uint8Array) && !(rgba instanceof Uint8ClampedArray)) throw new TypeError('encodePng: rgba must be a Uint8Array or Uint8ClampedArray');
+    if (!(Number.isInteger(width) && Number.isInteger(height) && width >= 1 && height >= 1) || rgba.length !== width * height * 4) throw new RangeError('encodePng: rgba length must be width*height*4');
+    const row = width * 4, raw = Buffer.alloc((row + 1) * height);
+    const src = Buffer.from(rgba.buffer, rgba.byteOffset, rgba.byteLength);
+    for (let y = 0; y < height; y++) src.copy(raw, y * (row + 1) + 1, y * row, (y + 1) * row);        // byte 0 of each row: filter 0
+    const ihdr = Buffer.alloc(13);
+    ihdr.writeUInt32BE(width, 0); ihdr.writeUInt32BE(height, 4);
+    ihdr[8] = 8; ihdr[9] = 6; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;                              // 8 bits, RGBA, deflate, adaptive filtering, no interlace
+    const png = Buffer.concat([Buffer.from([0x89, 0x50, 0x4E, 0x47, 0x0D, 0x0A, 0x1A, 0x0A]), chunk('IHDR', ihdr), chunk('IDAT', zlib.deflateSync(raw)),
+                               chunk('IEND', Buffer.alloc(0))]);
+    const out = new Uint8Array(png.length);                                                          // its own ArrayBuffer: the worker transfers it
+    out.set(png);
+    return out;
+}

@@ -1,8 +1,9 @@
 // worker_threads counterpart of the reference's Web Worker (js/planet-worker.js) for the part of its message protocol
 // that is the device path: the retained state W (:277-292), `reapply` (:341-440), `editRecompute` (:442-577),
-// `computeClimate` (:579-677) and the dispatcher (:944-954).
+// `computeClimate` (:579-677) and the dispatcher (:944-954); and `exportMap`, which the reference runs on its page with WebGL
+// (js/planet-mesh.js:1752-2180) and a Node host has no other way to get.
 //
-//   cmd 'retain'   { mesh: { numRegions, adjOffset, adjList, triangles? }, r_xyz, neighborDist?, prePostElev, seed, r_hotspot?,
+//   cmd 'retain'   { mesh: { numRegions, adjOffset, adjList, triangles?, halfedges? }, r_xyz, neighborDist?, prePostElev, seed, r_hotspot?,
 //                    r_plate?, plateIsOcean?, plateSeeds?, plateVec?, plateDensity?, P? }
 //                  What `generate` leaves in W for later reapplies, handed over by the caller (plate generation and ocean /
 //                  land assignment are the reference's own host code and stay where they are).  The mesh, positions and the
@@ -41,6 +42,15 @@
 //                  poles and is refused.
 //                  -> { type: 'editDone', skipClimate: true, prePostElev, r_elevation, t_elevation, mountain_r, coastline_r, ocean_r,
 //                       r_stress, <the 19 climate fields: null>, debugLayers, _editTiming, _timing, _postTiming }
+//   cmd 'exportMap' { type | types, width, png? }   (js/planet-mesh.js:1752-2180)
+//                  the equirectangular map, width x width / 2, of the planet's current elevation and Koppen block in one or
+//                  several of the reference's six kinds (color, heightmap, landheightmap, landmask, biome, koppen): one raster on
+//                  the device, one colour pass per type, and with `png` the PNG file of each (js/map-export.js).  Needs a state
+//                  retained with mesh.triangles and mesh.halfedges (importHeightmap keeps both); biome and koppen need a
+//                  computeClimate before them (`no Koppen result` otherwise: the reference's silent fallback to the colour map is
+//                  not offered).  Progress: `Rendering...` at 0, then 80 k / n after each type, `Encoding PNG...` at 85 with png.
+//                  -> { type: 'exportDone', width, height, maps: [{ type, filename, rgba, png? }],
+//                       _exportTiming: { raster, color, encode, workerTotal } }, the buffers transferred
 //   cmd 'dispose'  frees the retained state -> { type: 'disposed' }
 //   progress / errors exactly as the reference posts them: { type: 'progress', pct, label }, { type: 'error', message, stack };
 //   an unknown command answers `Unknown command: <cmd>` (:952).  `generate` is not served: plate generation and ocean / land
@@ -56,6 +66,7 @@ import { platesFromDevice } from './heightmap-import.js';
 import { OCEAN_KEYS, PRECIP_KEYS, TEMP_KEYS, downloadAll } from './climate-blocks.js';
 import { denseTable, LAYERS } from './plate-table.js';
 import { SimplexNoise } from './simplex-noise.js';
+import { MAP_TYPES, exportFilename, encodePng } from './map-export.js';
 
 let W = null;          // retained state (js/planet-worker.js:22)
 
@@ -75,7 +86,7 @@ function handleRetain(data) {
         addon.planetUpload(planet, prePostElev, null);
         if (r_hotspot) addon.planetUploadHotspot(planet, r_hotspot);
         addon.planetSaveState(planet);                  // W.prePostElev, device copy
-        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles || null, seed, hasHotspot: !!r_hotspot,
+        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles || null, halfedges: mesh.halfedges || null, seed, hasHotspot: !!r_hotspot,
               r_plate: r_plate || null, plateIsOcean: (plateIsOcean !== undefined && plateIsOcean !== null) ? Int32Array.from(plateIsOcean) : null,
               plateSeeds: (plateSeeds !== undefined && plateSeeds !== null) ? Int32Array.from(plateSeeds) : null, plateVec: plateVec || null,
               plateDensity: Object.assign({}, plateDensity || {}), P: P || 0, cachedWind: null, cachedOcean: null };
@@ -150,7 +161,7 @@ function handleImportHeightmap(data) {
         t0 = performance.now();
         releaseRetained();
         const planet = addon.planetCreate(defaultContext(), mesh.numRegions, mesh.adjOffset, mesh.adjList, r_xyz, neighborDist);
-        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles, seed, hasHotspot: false, r_plate: null, plateIsOcean: null,
+        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles, halfedges: mesh.halfedges, seed, hasHotspot: false, r_plate: null, plateIsOcean: null,
               plateSeeds: null, plateVec: null, plateDensity: {}, P: 0, cachedWind: null, cachedOcean: null };
         const prePostElev = addon.sampleHeightmap(planet, grayscale, imageWidth, imageHeight, true);
         addon.planetSaveState(planet);                  // W.prePostElev, device copy
@@ -341,6 +352,47 @@ function handleComputeClimate(data) {
     }
 }
 
+// js/planet-mesh.js:1965-2180 without the page: one raster, one colour pass per type, on W.planet's current elevation and Koppen block
+function handleExportMap(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for exportMap' }); return; }
+    const missing = ['triangles', 'halfedges'].filter((k) => !(W[k] instanceof Int32Array));
+    if (missing.length) {
+        parentPort.postMessage({ type: 'error', message: `exportMap: the retained state has no mesh.${missing.join(' and mesh.')} (pass them to retain, or run importHeightmap)` });
+        return;
+    }
+    try {
+        const tTotal0 = performance.now();
+        const types = data.types !== undefined && data.types !== null ? Array.from(data.types) : [data.type];
+        for (const t of types) if (MAP_TYPES.indexOf(t) < 0) throw new RangeError(`exportMap: unknown map type '${t}' (one of ${MAP_TYPES.join(', ')})`);
+        if (types.length === 0) throw new RangeError('exportMap: no map type given');
+        const width = data.width;
+        progress(0, 'Rendering...');
+        let t0 = performance.now();
+        const r = addon.mapRaster(W.planet, W.triangles, W.halfedges, width, false);
+        const tRaster = performance.now() - t0;
+        t0 = performance.now();
+        const maps = [];
+        types.forEach((type, k) => {
+            maps.push({ type, filename: exportFilename(type, W.seed), rgba: addon.mapColor(W.planet, MAP_TYPES.indexOf(type), null, width) });
+            progress(80 * (k + 1) / types.length, 'Rendering...');
+        });
+        const tColor = performance.now() - t0;
+        let tEncode = 0;
+        if (data.png) {
+            progress(85, 'Encoding PNG...');
+            t0 = performance.now();
+            for (const m of maps) m.png = encodePng(m.rgba, r.width, r.height);
+            tEncode = performance.now() - t0;
+        }
+        const transfer = [];
+        for (const m of maps) { transfer.push(m.rgba.buffer); if (m.png) transfer.push(m.png.buffer); }
+        parentPort.postMessage({ type: 'exportDone', width: r.width, height: r.height, maps,
+                                 _exportTiming: { raster: tRaster, color: tColor, encode: tEncode, workerTotal: performance.now() - tTotal0 } }, transfer);
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
 parentPort.on('message', (data) => {
     const { cmd } = data;
     switch (cmd) {
@@ -350,6 +402,7 @@ parentPort.on('message', (data) => {
         case 'dispose': releaseRetained(); parentPort.postMessage({ type: 'disposed' }); break;
         case 'computeClimate': handleComputeClimate(data); break;
         case 'editRecompute': handleEditRecompute(data); break;
+        case 'exportMap': handleExportMap(data); break;
         case 'generate':
             parentPort.postMessage({ type: 'error', message: `Command not served by the device worker (host stages of the reference): ${cmd}` });
             break;

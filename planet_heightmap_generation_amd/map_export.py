@@ -1,0 +1,85 @@
+"""Equirectangular map export (js/planet-mesh.js:1752-2180) over the C ABI, on a device-resident planet.
+
+``raster`` builds the region map of the planet's positions for a mesh's sides (csrc/map.hip: forward rasterisation with the lowest
+side index per pixel) and leaves it on the device; ``color`` turns it into RGBA8 in one of the reference's six kinds through the
+reference's colour function per region, its quantiser and its gamma table; ``export_map`` does both.  The triangle list and the
+region colours are the reference's bit for bit; the coverage rule is the one csrc/map_ops.h fixes (WebGL's own pixels differ
+between GPUs).  ``biome`` and ``koppen`` need the planet's Koppen block (``koppen.classify_koppen``).  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import capi
+from . import climate_blocks as CB
+from . import terrain_post as TP
+
+# the reference's type names in the order of WO_MAP_COLOR .. WO_MAP_KOPPEN (include/worogen.h)
+TYPES = ("color", "heightmap", "landheightmap", "landmask", "biome", "koppen")
+
+
+def type_id(type) -> int:
+    if isinstance(type, str):
+        if type not in TYPES:
+            raise ValueError(f"unknown map type '{type}' (one of {', '.join(TYPES)})")
+        return TYPES.index(type)
+    return int(type)
+
+
+def export_filename(type: str, seed) -> str:
+    """exportFilename(type, seed) (js/planet-mesh.js:1952-1961)."""
+    stem = dict(landmask="landmask", landheightmap="land-heightmap", heightmap="heightmap", biome="satellite", koppen="climate").get(type, "colormap")
+    return f"orogen-{stem}-{seed}.png"
+
+
+def raster(planet: TP.Planet, mesh, width: int, download: bool = False) -> dict:
+    """The region map of the planet at width x width / 2: {width, height, covered, uncovered, regionMap}; regionMap is the int32
+    (height, width) array (-1: nothing covers the pixel) when download is set, else None.  The map stays on the device."""
+    width = int(width)
+    tri = np.ascontiguousarray(mesh.triangles, dtype=np.int32)
+    he = np.ascontiguousarray(mesh.halfedges, dtype=np.int32)
+    if tri.shape != he.shape or tri.ndim != 1:
+        raise ValueError("mesh.triangles and mesh.halfedges must be int32 arrays of numSides entries")
+    ok = 2 <= width <= 32768 and width % 2 == 0
+    out = np.empty((width // 2, width), np.int32) if (download and ok) else None
+    counts = np.zeros(2, np.int64)
+    capi.check(capi.lib().wo_map_raster(planet.handle, tri.size, capi.ptr(tri), capi.ptr(he), width, capi.ptr(out), capi.ptr(counts)), "mapRaster")
+    planet._map_width = width                              # what color sizes its result by
+    return dict(width=width, height=width // 2, covered=int(counts[0]), uncovered=int(counts[1]), regionMap=out)
+
+
+def download(planet: TP.Planet, width: int) -> np.ndarray:
+    """The planet's resident region map (the width of its last raster): int32 (height, width)."""
+    out = np.empty((int(width) // 2, int(width)), np.int32)
+    capi.check(capi.lib().wo_map_download(planet.handle, capi.ptr(out), out.nbytes), "mapDownload")
+    return out
+
+
+def color(planet: TP.Planet, type, r_elevation=None, width: int | None = None) -> np.ndarray:
+    """The planet's region map coloured as `type`: uint8 (height, width, 4).  r_elevation None means the planet's resident field.
+    width: the width of the planet's last raster; raster remembers it on the planet, so it is only needed after a raster made elsewhere."""
+    e = CB.elevation_arg(planet.numRegions, r_elevation)
+    if width is None:
+        width = getattr(planet, "_map_width", None)
+    if width is None:
+        width = 2                                          # no raster made here: the library says what is missing
+    out = np.empty((int(width) // 2, int(width), 4), np.uint8)
+    capi.check(capi.lib().wo_map_color(planet.handle, type_id(type), capi.ptr(e), capi.ptr(out), out.nbytes), "mapColor")
+    return out
+
+
+def free(planet: TP.Planet) -> None:
+    capi.check(capi.lib().wo_map_free(planet.handle), "mapFree")
+    planet._map_width = None
+
+
+def export_map(planet: TP.Planet, mesh, types, width: int, r_elevation=None) -> dict:
+    """exportMapBatch: one raster, one colour pass per type.  types: one name or a sequence of names.
+    -> {width, height, covered, uncovered, maps: {type: uint8 (height, width, 4)}}"""
+    names = [types] if isinstance(types, str) else list(types)
+    for t in names:
+        type_id(t)
+    res = raster(planet, mesh, width)
+    res["maps"] = {t: color(planet, t, r_elevation, res["width"]) for t in names}
+    del res["regionMap"]
+    return res

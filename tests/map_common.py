@@ -1,0 +1,187 @@
+"""Shared pieces of the map-export tests: the golden fixture, the host emulator of csrc/map_ops.h (tests/emu_map) and an
+independent numpy statement of the coverage rule (float64 point-in-triangle over a list of map triangles)."""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+import subprocess
+
+import numpy as np
+
+from conftest import GOLDEN, REPO
+
+EMU_DIR = REPO / "tests" / "emu_map"
+TYPES = ("color", "heightmap", "landheightmap", "landmask", "biome", "koppen")
+GREY = ("heightmap", "landheightmap", "landmask")
+_emu = None
+
+
+@functools.lru_cache(maxsize=None)
+def golden():
+    return dict(np.load(GOLDEN / "map_N2000_s1.npz"))
+
+
+@functools.lru_cache(maxsize=None)
+def mesh_golden(name="mesh_N2000_s1"):
+    return dict(np.load(GOLDEN / f"{name}.npz"))
+
+
+def emu():
+    global _emu
+    if _emu is None:
+        subprocess.run(["make", "-s", "-C", str(EMU_DIR)], check=True)
+        _emu = C.CDLL(str(EMU_DIR / "_build" / "libemu_map.so"))
+        _emu.emu_geometry.restype = C.c_int32
+        _emu.emu_background.restype = C.c_uint32
+    return _emu
+
+
+def ptr(a):
+    if a is None:
+        return None
+    assert a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _mesh_args(xyz, tri, he):
+    xyz, tri, he = np.ascontiguousarray(xyz, np.float32).reshape(-1), np.ascontiguousarray(tri, np.int32), np.ascontiguousarray(he, np.int32)
+    return xyz, tri, he
+
+
+def emu_geometry(xyz, tri, he):
+    """-> (positions float32 [T, 3, 2], triRegions int32 [T], triSides int32 [T]) in the reference's order"""
+    xyz, tri, he = _mesh_args(xyz, tri, he)
+    pos, reg, side = np.empty(12 * tri.size, np.float32), np.empty(2 * tri.size, np.int32), np.empty(2 * tri.size, np.int32)
+    n = emu().emu_geometry(C.c_int32(xyz.size // 3), ptr(xyz), C.c_int32(tri.size), ptr(tri), ptr(he), ptr(pos), ptr(reg), ptr(side))
+    return pos[: 6 * n].reshape(n, 3, 2).copy(), reg[:n].copy(), side[:n].copy()
+
+
+def emu_raster(xyz, tri, he, W):
+    """-> (regionMap int32 [H, W], covered, uncovered)"""
+    xyz, tri, he = _mesh_args(xyz, tri, he)
+    out, counts = np.empty((W // 2, W), np.int32), np.zeros(2, np.int64)
+    emu().emu_raster(C.c_int32(xyz.size // 3), ptr(xyz), C.c_int32(tri.size), ptr(tri), ptr(he), C.c_int32(W), ptr(out), ptr(counts))
+    return out, int(counts[0]), int(counts[1])
+
+
+def emu_raw_colors(type, e, k):
+    e = np.ascontiguousarray(e, np.float32)
+    k = None if k is None else np.ascontiguousarray(k, np.uint8)
+    out = np.empty(3 * e.size, np.float32)
+    emu().emu_raw_colors(C.c_int32(TYPES.index(type)), C.c_int32(e.size), ptr(e), ptr(k), ptr(out))
+    return out
+
+
+def emu_region_colors(type, e, k, off, adj):
+    e, k = np.ascontiguousarray(e, np.float32), np.ascontiguousarray(k, np.uint8)
+    off, adj = np.ascontiguousarray(off, np.int32), np.ascontiguousarray(adj, np.int32)
+    out = np.empty(3 * e.size, np.float32)
+    emu().emu_region_colors(C.c_int32(TYPES.index(type)), C.c_int32(e.size), ptr(e), ptr(k), ptr(off), ptr(adj), ptr(out))
+    return out
+
+
+def emu_lut():
+    lut = np.empty(256, np.uint8)
+    emu().emu_lut(ptr(lut))
+    return lut
+
+
+def emu_background(type):
+    """the four bytes of an uncovered pixel"""
+    return np.array([emu().emu_background(C.c_int32(TYPES.index(type)))], np.uint32).view(np.uint8)
+
+
+def emu_rgba(type, e, k, off, adj, region_map):
+    """-> uint8 [H, W, 4]"""
+    e, k = np.ascontiguousarray(e, np.float32), np.ascontiguousarray(k, np.uint8)
+    off, adj = np.ascontiguousarray(off, np.int32), np.ascontiguousarray(adj, np.int32)
+    rm = np.ascontiguousarray(region_map, np.int32)
+    out = np.empty(rm.size, np.uint32)
+    emu().emu_rgba(C.c_int32(TYPES.index(type)), C.c_int32(e.size), ptr(e), ptr(k), ptr(off), ptr(adj), C.c_int64(rm.size), ptr(rm), ptr(out))
+    return out.view(np.uint8).reshape(rm.shape + (4,))
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if a.dtype == np.float32:
+        return bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
+    return bool(np.array_equal(a, b))
+
+
+def quantise(c):
+    """q = floor(c * 255 + 0.5) on the f32 value clamped to [0, 1]; NaN gives 0 (restated in numpy)"""
+    v = np.asarray(c, np.float32).astype(np.float64)
+    v = np.where(np.isnan(v), 0.0, np.clip(v, 0.0, 1.0))
+    return np.floor(v * 255.0 + 0.5).astype(np.int64)
+
+
+def numpy_raster(positions, tri_regions, W, near=1e-9):
+    """The coverage rule stated independently: float64 point-in-triangle over `positions` ([T, 3, 2] f32, triangles in ascending
+    side order) at the centres of a W x W/2 grid, the lowest triangle index winning.  -> (regionMap [H, W], ambiguous [H, W]):
+    ambiguous marks the pixels whose centre lies within `near` of an edge line of a triangle whose box holds them."""
+    H = W // 2
+    P = np.asarray(positions, np.float32).astype(np.float64)
+    xc = -2.0 + 4.0 * (np.arange(W, dtype=np.float64) + 0.5) / W
+    yc = 1.0 - 2.0 * (np.arange(H, dtype=np.float64) + 0.5) / H
+    region = np.full((H, W), -1, np.int64)
+    ambiguous = np.zeros((H, W), bool)
+    for t in range(P.shape[0] - 1, -1, -1):                  # descending: the lowest index is written last
+        (ax, ay), (bx, by), (cx, cy) = P[t]
+        area2 = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax)
+        if not (area2 > 0 or area2 < 0):
+            continue
+        i0, i1 = np.searchsorted(xc, min(ax, bx, cx) - 1e-6), np.searchsorted(xc, max(ax, bx, cx) + 1e-6)
+        j0, j1 = np.searchsorted(-yc, -(max(ay, by, cy) + 1e-6)), np.searchsorted(-yc, -(min(ay, by, cy) - 1e-6))
+        if i0 >= i1 or j0 >= j1:
+            continue
+        X, Y = xc[None, i0:i1], yc[j0:j1, None]
+        e0 = (bx - ax) * (Y - ay) - (by - ay) * (X - ax)
+        e1 = (cx - bx) * (Y - by) - (cy - by) * (X - bx)
+        e2 = (ax - cx) * (Y - cy) - (ay - cy) * (X - cx)
+        inside = ((e0 >= 0) & (e1 >= 0) & (e2 >= 0)) if area2 > 0 else ((e0 <= 0) & (e1 <= 0) & (e2 <= 0))
+        region[j0:j1, i0:i1][inside] = tri_regions[t]
+        for e, (ux, uy) in ((e0, (bx - ax, by - ay)), (e1, (cx - bx, cy - by)), (e2, (ax - cx, ay - cy))):
+            length = np.hypot(ux, uy)
+            if length > 0:
+                ambiguous[j0:j1, i0:i1] |= np.abs(e) / length < near
+    return region, ambiguous
+
+
+def fbm_like(xyz, seed):
+    """A smooth field of both signs on the sphere from a fixed seed (a few random plane waves), float32 per region."""
+    p = np.asarray(xyz, np.float32).reshape(-1, 3).astype(np.float64)
+    rng = np.random.default_rng(seed)
+    e = np.zeros(p.shape[0])
+    for o in range(4):
+        for _ in range(3):
+            d = rng.normal(size=3)
+            e += np.sin(p @ d * (1.5 * 2 ** o) + rng.uniform(0, 6.28)) / 2 ** o
+    return (e * 0.35).astype(np.float32)
+
+
+def hash_koppen(n):
+    r = np.arange(n, dtype=np.uint64)
+    return (((r * np.uint64(2654435761)) >> np.uint64(7)) % np.uint64(31)).astype(np.uint8)
+
+
+class Mesh:
+    """what terrain_post.Planet and map_export.raster read of a mesh"""
+    def __init__(self, numRegions, triangles, halfedges, adjOffset, adjList):
+        self.numRegions, self.triangles, self.halfedges, self.adjOffset, self.adjList = int(numRegions), triangles, halfedges, adjOffset, adjList
+
+
+def golden_mesh(name):
+    m = mesh_golden(name)
+    return Mesh(m["numRegions"], m["triangles"], m["halfedges"], m["ref_adjOffset"], m["ref_adjList"]), m["xyz"]
+
+
+def climate_chain(planet, r_plate, plate_is_ocean, seed):
+    """the five climate stages on the planet's resident elevation, nothing downloaded but the Koppen ids"""
+    from planet_heightmap_generation_amd import koppen as KD, ocean as OD, precipitation as PD, temperature as TD, wind as WD
+    WD.compute_wind(planet, None, None, set(int(i) for i in plate_is_ocean), r_plate, seed, fields=())
+    OD.compute_ocean_currents(planet, None, None, fields=())
+    PD.compute_precipitation(planet, None, None, fields=())
+    TD.compute_temperature(planet, None, None, fields=())
+    return KD.classify_koppen(planet, None)
