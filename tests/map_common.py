@@ -1,5 +1,7 @@
-"""Shared pieces of the map-export tests: the golden fixture, the host emulator of csrc/map_ops.h (tests/emu_map) and an
-independent numpy statement of the coverage rule (float64 point-in-triangle over a list of map triangles)."""
+"""Shared pieces of the map-export tests: the golden fixture, the host emulator of csrc/map_ops.h (tests/emu_map), an
+independent numpy statement of the coverage rule (float64 point-in-triangle over a list of map triangles), and the sweep planet:
+every pair of a Koppen class and an elevation of the golden's colour sweep on a 10 001-cell mesh, with the pixels the reference's
+recorded colours give for it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -185,3 +187,84 @@ def climate_chain(planet, r_plate, plate_is_ocean, seed):
     PD.compute_precipitation(planet, None, None, fields=())
     TD.compute_temperature(planet, None, None, fields=())
     return KD.classify_koppen(planet, None)
+
+
+# ---- the sweep planet ------------------------------------------------------------------------------------------------------------
+SWEEP_MESH, SWEEP_WIDTH = "mesh_N10000_s1", 2048     # at 1024 one region owns no pixel; at 2048 every region owns at least 3
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_planet():
+    """Region r of the 10 001-cell golden mesh takes class k = r % 31 and colour elevation sweep_e[j], j = (r // 31) % 125: each
+    of the 31 x 125 pairs is held by two or three regions.  The device takes no class ids, it classifies: the Koppen inputs of
+    region r are the first row of tests/golden/koppen_lattice.npz whose recorded class is k.  So the ids 31 and 255 of the golden's
+    sweep_k (the fallback rows of the two colour tables) cannot be produced on the device; they stay with the emulator
+    (tests/test_map_export.py: test_color_sweep_is_the_references).
+    -> dict(mesh, xyz, k, j, e_sweep, e_koppen, temp, precip): e_koppen, temp and precip are classify_koppen's arguments"""
+    import temperature_common as TC
+    g = golden()
+    mesh, xyz = golden_mesh(SWEEP_MESH)
+    assert g["sweep_e"].size == 125 and g["sweep_k"][:31].tolist() == list(range(31))
+    r = np.arange(mesh.numRegions)
+    k, j = (r % 31).astype(np.uint8), (r // 31) % 125
+    le, lt, lp, lref = TC.lattice()
+    first = np.array([int(np.flatnonzero(lref == c)[0]) for c in range(31)])
+    assert first.max() < TC.LATTICE_FINITE
+    row = first[k]
+    return dict(mesh=mesh, xyz=xyz, k=k, j=j, e_sweep=np.ascontiguousarray(g["sweep_e"][j]), e_koppen=np.ascontiguousarray(le[row]),
+                temp={key: np.ascontiguousarray(v[row]) for key, v in lt.items()}, precip={key: np.ascontiguousarray(v[row]) for key, v in lp.items()})
+
+
+def smooth_numpy(raw, off, adj):
+    """smoothBiomeColors' second loop restated: out = raw * (1 - 0.35) + mean(raw over the region's adjacency, in list order) * 0.35
+    in float64, rounded to f32; a region without neighbours keeps its colour.  A loop over regions and over each list, so the
+    sums run in the reference's order."""
+    raw = np.asarray(raw, np.float32).reshape(-1, 3).astype(np.float64)
+    out = np.empty(raw.shape, np.float32)
+    alpha = 0.35
+    with np.errstate(invalid="ignore"):
+        for r in range(raw.shape[0]):
+            start, end = int(off[r]), int(off[r + 1])
+            if end == start:
+                out[r] = raw[r]
+                continue
+            avg = np.zeros(3)
+            for i in range(start, end):
+                avg = avg + raw[adj[i]]
+            avg = avg / float(end - start)
+            out[r] = raw[r] * (1 - alpha) + avg * alpha
+    return out
+
+
+def sweep_expected(type, region_map):
+    """The RGBA of the sweep planet's region map from the golden alone: a covered pixel of region r is
+    lut[quantise(sweep_<type>[j or k])] with alpha 255 (biome: sweep_biome[k][j] per region, then smooth_numpy), an uncovered one
+    the golden's background_linear through the same two steps, or 0, 0, 0 for the grey types.  The emulator is not involved."""
+    g, S = golden(), sweep_planet()
+    k, j = S["k"].astype(np.int64), S["j"]
+    if type == "koppen":
+        region = g["sweep_koppen"].reshape(-1, 3)[k]
+    elif type == "biome":
+        region = smooth_numpy(g["sweep_biome"].reshape(g["sweep_k"].size, g["sweep_e"].size, 3)[k, j], S["mesh"].adjOffset, S["mesh"].adjList)
+    else:
+        region = g[f"sweep_{type}"].reshape(-1, 3)[j]
+    rgb = g["lut"][quantise(region)]
+    back = np.zeros(3, np.uint8) if type in GREY else g["lut"][quantise(g["background_linear"])]
+    rm = np.asarray(region_map)
+    out = np.empty(rm.shape + (4,), np.uint8)
+    out[..., :3] = np.where((rm >= 0)[..., None], rgb[np.maximum(rm, 0)], back)
+    out[..., 3] = 255
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_raster():
+    """The emulator's region map of the sweep planet with the conditions the sweep tests rest on, asserted: every region owns a
+    pixel, so every (class, elevation) pair is in the picture.  -> (regionMap, covered, uncovered)"""
+    S = sweep_planet()
+    rm, covered, uncovered = emu_raster(S["xyz"], S["mesh"].triangles, S["mesh"].halfedges, SWEEP_WIDTH)
+    owned = np.bincount(rm[rm >= 0], minlength=S["mesh"].numRegions)
+    assert owned.size == S["mesh"].numRegions == 10001 and owned.min() >= 1, f"regions without a pixel: {np.flatnonzero(owned == 0)[:8]}"
+    assert covered + uncovered == rm.size and uncovered == int((rm < 0).sum()) > 0          # the background is in the picture too
+    rm.setflags(write=False)
+    return rm, covered, uncovered

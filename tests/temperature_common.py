@@ -168,7 +168,11 @@ def koppen_differing(got, ref, stride=1):
     return int((g != ref).sum())
 
 
+LATTICE_FINITE = 3841               # the lattice's rows before its 30 non-finite ones: 15 x 256 + 1
+
+
 def lattice():
+    """(elevation, temp, precip, the reference's recorded classes) of tests/golden/koppen_lattice.npz"""
     g = np.load(GOLDEN / "koppen_lattice.npz")
     temp = dict(r_temperature_summer=g["in_tSummer"], r_temperature_winter=g["in_tWinter"])
     precip = dict(r_precip_summer=g["in_pSummer"], r_precip_winter=g["in_pWinter"])

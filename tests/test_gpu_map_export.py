@@ -1,5 +1,7 @@
 """Map export on the device (csrc/map.hip) against the host emulator of the same bodies (tests/emu_map): the region map and its
-counts in every pixel, the RGBA of all six kinds, the map block's memory, and the error answers of the C ABI."""
+counts in every pixel, the RGBA of all six kinds, the map block's memory, and the error answers of the C ABI; on the sweep planet
+(every Koppen class with every elevation of the golden's colour sweep) also against the pixels the reference's recorded colours
+give; and the climate chain with the map export on planets in flight against the same jobs one after the other."""
 import ctypes as C
 
 import numpy as np
@@ -95,6 +97,91 @@ def test_rgba_equals_emulator(imported):
         assert np.array_equal(ME.color(pl, type, I["e"]), got), type                   # the passed elevation: the same bytes
     res = ME.export_map(pl, mesh, ["heightmap", "koppen"], 64)
     assert list(res["maps"]) == ["heightmap", "koppen"] and res["maps"]["koppen"].shape == (32, 64, 4)
+
+
+# ---- 6b. the colour sweep: every class with every boundary elevation, against the reference's recorded colours -------------------
+@pytest.fixture(scope="module")
+def sweep():
+    """The sweep planet classified and rastered on the device.  Conditions, asserted from the emulator's raster
+    (map_common.sweep_raster): every one of the 10 001 regions owns a pixel at 2048 x 1024, and the device's region map is the
+    emulator's in every pixel.  The device takes no class ids, so it classifies lattice rows; the ids 31 and 255 of the golden's
+    sweep_k stay with the emulator (tests/test_map_export.py)."""
+    from planet_heightmap_generation_amd import koppen as KD, map_export as ME
+    S = MC.sweep_planet()
+    want_rm, covered, uncovered = MC.sweep_raster()
+    pl = _planet(S["mesh"], S["xyz"])
+    try:
+        classes = KD.classify_koppen(pl, S["e_koppen"], temp_result=S["temp"], precip_result=S["precip"])
+        bad = int((classes != S["k"]).sum())
+        print(f"sweep planet: {bad} of {classes.size} regions have another class than k = r % 31")
+        assert bad == 0 and np.unique(classes).size == 31
+        res = ME.raster(pl, S["mesh"], MC.SWEEP_WIDTH, download=True)
+        bad = int((res["regionMap"] != want_rm).sum())
+        print(f"sweep planet at {MC.SWEEP_WIDTH} x {MC.SWEEP_WIDTH // 2}: {bad} pixels of the region map differ from the emulator; covered {res['covered']}, uncovered {res['uncovered']}")
+        assert bad == 0 and (res["covered"], res["uncovered"]) == (covered, uncovered)
+        yield dict(S, planet=pl, rm=want_rm)
+    finally:
+        pl.close()
+
+
+@pytest.mark.parametrize("type", MC.TYPES)
+def test_sweep_rgba_equals_emulator_and_recorded_colours(sweep, type):
+    """Bytes in every pixel: against emu_rgba, against the expectation built in numpy from the golden's recorded sweep colours,
+    its table and its background alone (for biome with the smoothing restated in numpy), and the resident elevation against the
+    passed one."""
+    from planet_heightmap_generation_amd import map_export as ME
+    pl, rm, W = sweep["planet"], sweep["rm"], MC.SWEEP_WIDTH
+    got = ME.color(pl, type, sweep["e_sweep"])
+    emu = MC.emu_rgba(type, sweep["e_sweep"], sweep["k"], sweep["mesh"].adjOffset, sweep["mesh"].adjList, rm)
+    want = MC.sweep_expected(type, rm)
+    assert got.shape == emu.shape == want.shape == (W // 2, W, 4)
+    bad_emu, bad_ref = int((got != emu).any(axis=-1).sum()), int((got != want).any(axis=-1).sum())
+    print(f"{type}: {bad_emu} pixels differ from the emulator, {bad_ref} from the reference-built expectation; {np.unique(got.reshape(-1, 4), axis=0).shape[0]} distinct colours")
+    for r in np.unique(rm[(got != want).any(axis=-1) & (rm >= 0)])[:6]:
+        y, x = np.argwhere(rm == r)[0]
+        print(f"    region {int(r)}: class {int(sweep['k'][r])}, elevation {float(sweep['e_sweep'][r])!r}: device {got[y, x].tolist()}, expected {want[y, x].tolist()}")
+    assert bad_emu == 0 and bad_ref == 0
+    pl.upload(sweep["e_sweep"])
+    assert np.array_equal(ME.color(pl, type), got)                                      # the resident elevation: the same bytes
+
+
+# ---- 6c. planets in flight ---------------------------------------------------------------------------------------------------
+def test_climate_and_map_in_flight_match_sequential():
+    """Six terrains on one mesh through the five climate stages, the raster and the six colourings, four at a time (own context,
+    stream and host thread each; a worker's planet is reused, so every block is also replaced) and one after the other: every
+    array of every job is the same, f32 as bits.  The climate blocks and the map block share no mutable state between planets."""
+    import wind_common as WC
+    from planet_heightmap_generation_amd import koppen as KD, map_export as ME, precipitation as PD, sphere_mesh as SM, temperature as TD
+    from planet_heightmap_generation_amd.ensemble import EnsembleRunner
+    mesh, xyz, _ = SM.build_sphere(20000, 0.75, 1)
+    cases = [WC.synthetic_case(20000, seed=s) for s in (1, 2, 3, 4, 5, 6)]                # the same mesh six times, six terrains
+    assert all(np.array_equal(c["xyz"], np.asarray(xyz, np.float32).reshape(-1)) and np.array_equal(c["off"], mesh.adjOffset) for c in cases)
+
+    def job(pl, case):
+        pl.upload(case["e"])
+        out = dict(koppen=MC.climate_chain(pl, case["plate"], case["ocean"], case["seed"]))
+        for k in KD.TEMP_INPUTS:
+            out[k] = TD.download(pl, k)
+        for k in KD.PRECIP_INPUTS:
+            out[k] = PD.download(pl, k)
+        assert np.array_equal(out["koppen"], KD.download(pl))
+        out["regionMap"] = ME.raster(pl, mesh, 512, download=True)["regionMap"]
+        for type in MC.TYPES:
+            out["rgba_" + type] = ME.color(pl, type)
+        return out
+
+    seq = EnsembleRunner(mesh, xyz, in_flight=1).map(job, cases)
+    par = EnsembleRunner(mesh, xyz, in_flight=4).map(job, cases)
+    for i, (a, b) in enumerate(zip(seq, par)):
+        assert list(a) == list(b) and len(a) == 12
+        for k in a:
+            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, (i, k)
+            same = np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)) if a[k].dtype == np.float32 else np.array_equal(a[k], b[k])
+            assert same, f"terrain {i}: {k} differs between one and four planets in flight"
+    for k in seq[0]:
+        if k != "regionMap":                                                            # the mesh is shared, so the region map is too
+            assert not np.array_equal(seq[0][k], seq[1][k]), k
+    assert np.array_equal(seq[0]["regionMap"], seq[1]["regionMap"]) and np.unique(seq[0]["koppen"]).size > 5
 
 
 # ---- 7. the map block's memory ----------------------------------------------------------------------------------------------

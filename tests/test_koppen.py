@@ -1,6 +1,6 @@
 """classifyKoppen on the host emulator of csrc/temp_ops.h's koppen_cell against the reference: from each golden's own temperature
 and precipitation, and on the synthetic lattice tests/golden/koppen_lattice.npz, which holds every threshold of the classifier
-with its two f32 neighbours and reaches all 31 classes.  Class equality in every cell, no tolerance.  Also the class table of the
+with its two f32 neighbours, reaches all 31 classes and ends in 30 rows with one input NaN, +inf or -inf.  Class equality in every cell, no tolerance.  Also the class table of the
 Python host against the table recorded from the reference, and the census of classes and branches."""
 import json
 
@@ -64,6 +64,26 @@ def test_lattice_holds_the_thresholds():
         for v in (np.nextafter(c, f(-1)), c, np.nextafter(c, f(2))):
             assert float(v) in p_values, (p, v)
     assert {0.0, float(np.nextafter(f(0), f(1))), float(np.nextafter(f(0), f(-1)))} <= set(e.tolist()) and np.signbit(e).any()
+
+
+def test_lattice_holds_non_finite_values_in_each_input():
+    """NaN, +inf and -inf occur in each of the five inputs, in rows whose other four inputs are finite (Math.max / Math.min on a
+    NaN and the clamps on an infinity, held to the reference's recorded class by test_lattice_every_cell_and_every_class); the
+    emulator has the recorded class on exactly those rows, which lie behind every finite row."""
+    e, temp, precip, ref = TC.lattice()
+    cols = [e, temp["r_temperature_summer"], temp["r_temperature_winter"], precip["r_precip_summer"], precip["r_precip_winter"]]
+    finite = np.all([np.isfinite(c) for c in cols], axis=0)
+    for name, c in zip(("elevation", "tSummer", "tWinter", "pSummer", "pWinter"), cols):
+        others = np.all([np.isfinite(o) for o in cols if o is not c], axis=0)
+        for what, hit in (("NaN", np.isnan(c)), ("+inf", c == np.inf), ("-inf", c == -np.inf)):
+            assert (hit & others).any(), f"no row with {what} in {name} alone"
+    rows = np.flatnonzero(~finite)
+    assert rows.size == 30 and rows[0] == e.size - 30 == TC.LATTICE_FINITE, rows
+    got = TC.emulate_koppen(e, temp, precip)
+    print(f"non-finite rows: recorded classes {ref[rows].tolist()}, the emulator differs on {int((got[rows] != ref[rows]).sum())}")
+    assert np.array_equal(got[rows], ref[rows])
+    # the land rows reach several classes; the ocean rows stay ocean but for elevation NaN and +inf (NaN <= 0 is false)
+    assert np.unique(ref[rows][:15]).size >= 8 and np.flatnonzero(ref[rows][15:] != 0).tolist() == [0, 1]
 
 
 def test_planet_census():

@@ -103,6 +103,25 @@ def test_rgba_of_the_emulator_is_the_lut_of_the_region_colors():
         assert np.array_equal(got[..., :3], want) and np.all(got[..., 3] == 255), type
 
 
+def test_sweep_expectations_are_the_emulators():
+    """What tests/test_gpu_map_export.py holds the device to on the sweep planet, checked before it travels: the pixels built in
+    numpy from the golden's recorded sweep colours (map_common.sweep_expected) are emu_rgba's, byte for byte, for all six types."""
+    S = MC.sweep_planet()
+    rm, covered, uncovered = MC.sweep_raster()
+    owned = np.bincount(rm[rm >= 0], minlength=10001)
+    print(f"sweep planet at {MC.SWEEP_WIDTH} x {MC.SWEEP_WIDTH // 2}: covered {covered}, uncovered {uncovered}, fewest pixels of a region {int(owned.min())}")
+    assert (owned.min(), uncovered) == (3, 33226)
+    pairs = np.unique(S["k"].astype(np.int64) * 125 + S["j"], return_counts=True)
+    assert pairs[0].size == 31 * 125 and set(pairs[1].tolist()) == {2, 3}
+    assert np.isnan(S["e_sweep"]).any() and np.isinf(S["e_sweep"]).any() and (S["e_sweep"] > 1).any()
+    for type in MC.TYPES:
+        want = MC.sweep_expected(type, rm)
+        got = MC.emu_rgba(type, S["e_sweep"], S["k"], S["mesh"].adjOffset, S["mesh"].adjList, rm)
+        bad = int((got != want).any(axis=-1).sum())
+        print(f"{type}: {bad} pixels of the emulator differ from the reference-built expectation; {np.unique(want.reshape(-1, 4), axis=0).shape[0]} distinct colours")
+        assert bad == 0, type
+
+
 # ---- 4. encodePng ------------------------------------------------------------------------------------------------------------
 @pytest.mark.skipif(NODE is None or not ADDON.exists(), reason="node or worogen.node not available")
 def test_encode_png_and_filenames(tmp_path):

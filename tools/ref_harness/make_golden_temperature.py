@@ -90,7 +90,10 @@ def lattice():
          summerFrac >= 0.7, <= 0.3 (where the arm decides B or not B); Pann < Pthresh; Pann < Pthresh * 0.5; PsummerLocal <
          PwinterLocal; PsMonthLocal < 50; PsMonthLocal < PwMonthLocal / 2; PwMonthLocal < PsMonthLocal / 10; Pdry >= 60;
          Pann >= 25 * (100 - Pdry)
-      C  1 200 random cells, values beyond [0, 1] included (the clamps of the conversion)"""
+      C  1 200 random cells, values beyond [0, 1] included (the clamps of the conversion)
+      D  30 cells with exactly one input NaN, +inf or -inf (Math.max / Math.min on a NaN; the clamps on an infinity): each of the
+         five inputs in turn, the other four those of an ordinary land cell of class C and of an ordinary ocean cell
+    Rows are only ever appended: run() holds a regenerated lattice to the committed one on the rows both have."""
     rows = []
     add = lambda e, ts, tw, ps, pw: rows.append((e, ts, tw, ps, pw))  # noqa: E731
     TC = [-44, -40, -30, -10, -2, 3, 8, 12, 16, 19, 21, 25, 35]
@@ -171,6 +174,10 @@ def lattice():
     rng = np.random.default_rng(31031)
     for _ in range(1200):
         add(rng.choice([0.2, 0.2, 0.2, -0.1]), rng.uniform(-0.1, 1.1), rng.uniform(-0.1, 1.1), rng.uniform(-0.05, 1.2) ** 2, rng.uniform(-0.05, 1.2) ** 2)
+    for base in ((0.2, _t(20), _t(5), 0.5, 0.5), (-0.3, _t(20), _t(5), 0.5, 0.5)):
+        for i in range(5):
+            for v in (np.nan, np.inf, -np.inf):
+                add(*[v if j == i else x for j, x in enumerate(base)])
     a = np.array(rows, np.float64).astype(np.float32)
     return {k: np.ascontiguousarray(a[:, i]) for i, k in enumerate(("elevation", "tSummer", "tWinter", "pSummer", "pWinter"))}
 
@@ -224,8 +231,18 @@ def run(ref: Path, cs, write: bool, with_lattice: bool, with_climate: bool):
             reached = np.bincount(out, minlength=len(classes))
             print(f"koppen lattice: {out.size} cells, cells per class {reached.tolist()}")
             assert len(classes) == 31 and (reached > 0).all(), "the lattice does not reach every class"
+            table = json.dumps(dict(classes=classes, exports=meta["koppenExports"]), indent=1) + "\n"
+            if (GOLD / "koppen_lattice.npz").exists():          # the committed rows stay what they are, bytes and classes; so does the table
+                old = np.load(GOLD / "koppen_lattice.npz")
+                n = old["ref_koppen"].size
+                assert n <= out.size and old["ref_koppen"].tobytes() == out[:n].tobytes(), "the classes of the committed rows changed"
+                for k, v in lat.items():
+                    assert old[f"in_{k}"].tobytes() == v[:n].tobytes(), f"the committed rows of {k} changed"
+                assert (GOLD / "koppen_classes.json").read_text() == table, "koppen_classes.json changed"
+                print(f"koppen lattice: the {n} committed rows and koppen_classes.json are unchanged byte for byte; {out.size - n} rows appended, "
+                      f"classes {out[n:].tolist()}")
             np.savez_compressed(GOLD / "koppen_lattice.npz", ref_koppen=out, **{f"in_{k}": v for k, v in lat.items()})
-            (GOLD / "koppen_classes.json").write_text(json.dumps(dict(classes=classes, exports=meta["koppenExports"]), indent=1) + "\n")
+            (GOLD / "koppen_classes.json").write_text(table)
             print("wrote tests/golden/koppen_lattice.npz, tests/golden/koppen_classes.json")
         if with_climate:
             cm = meta["climate"]
