@@ -74,6 +74,12 @@ int wo_fib_sphere_points(int32_t N, double jitter, double seed, float* r_xyz);
  * addPoleToMesh (js/sphere-mesh.js:41-90,174-186).  triangles / halfedges have 3*(2*numRegions-4)
  * entries, counter-clockwise seen from outside, same contract as Delaunator's arrays. */
 int wo_sphere_delaunay(int32_t numRegions, const float* r_xyz, int32_t* triangles, int32_t* halfedges);
+/* Renumbers the closing fan of a triangulation from wo_sphere_delaunay (the pole is region numRegions - 1) the way the
+ * reference's addPoleToMesh does on the planar part (js/sphere-mesh.js:55-88): the triangles without the pole first, in
+ * their order, then one fan triangle per hull side along the hull walk that starts at the last unpaired side.  The
+ * triangulation is the same set of triangles; only the numbering of the fan (and with it the starting neighbour of the
+ * CSR rows around the pole) changes, which the order-defined host stages (generatePlates) can see.  In place. */
+int wo_sphere_reference_closure(int32_t numRegions, int32_t* triangles, int32_t* halfedges);
 /* SphereMesh constructor's CSR (js/sphere-mesh.js:94-146).  adjTriList may be NULL. */
 int wo_mesh_csr(int32_t numRegions, int32_t numSides, const int32_t* triangles, const int32_t* halfedges,
                 int32_t* adjOffset, int32_t* adjList, int32_t* adjTriList);
@@ -199,6 +205,36 @@ int wo_project_coarse_plates(wo_planet* p, int32_t coarseRegions, const int32_t*
  * rewritten in place. */
 int wo_smooth_reconnect_plates(int32_t numRegions, const int32_t* adjOffset, const int32_t* adjList, int32_t* r_plate,
                                const int32_t* plateSeeds, int32_t numPlateSeeds, int32_t numPasses);
+
+/* ------------------------------------------------ plate generation (host stages, no GPU) ------ */
+/* Branch counters of the two calls below (optional `stats` argument: NULL or WO_PLATES_GEN_STATS int64 values, zeroed
+ * by each call, which then counts its own branches). */
+#define WO_PLATES_GEN_STATS 7
+#define WO_PGS_GOVERNOR_HALVED 0       /* generatePlates: plate turns halved by the area governor        js/plates.js:148-150 */
+#define WO_PGS_SEEDS_TRIMMED 1         /* assignOceanLand: continent seeds dropped for the land budget   js/ocean-land.js:104-112 */
+#define WO_PGS_CONTINENT_AT_TARGET 2   /* assignOceanLand: continent turns skipped at their own target   :153 */
+#define WO_PGS_SEA_ABSORBED 3          /* assignOceanLand: interior seas joined to their continent        :224-228 */
+#define WO_PGS_SEA_REFUSED 4           /* assignOceanLand: interior seas kept by the 1.1 x cap            :224 */
+#define WO_PGS_SEA_TWO_CONTINENTS 5    /* assignOceanLand: interior seas bordering two continents         :218-221 */
+#define WO_PGS_ORPHANS 6               /* generatePlates: cells assigned by the orphan sweep              js/plates.js:199-214 */
+/* generatePlates(mesh, r_xyz, numPlates, seed) -> { r_plate, plateSeeds, plateVec }          js/plates.js:6-232
+ * Farthest-point seeds, round-robin directional growth, the orphan sweep, smoothAndReconnectPlates and the Euler poles,
+ * bit for bit.  r_plate: numRegions ints.  plateSeeds / pole (3 per seed) / omega have room for min(numPlates, numRegions)
+ * entries and come back in the Set's insertion order, *numPlateSeeds of them.  numPlates < 1 is refused. */
+int wo_generate_plates(int32_t numRegions, const int32_t* adjOffset, const int32_t* adjList, const float* r_xyz, int32_t numPlates,
+                       double seed, int32_t* r_plate, int32_t* plateSeeds, int32_t* numPlateSeeds, double* pole, double* omega,
+                       int64_t* stats);
+/* assignOceanLand(mesh, r_plate, plateSeeds, r_xyz, seed, numContinents, continentSizeVariety, landCoverage) -> Set
+ *                                                                                          js/ocean-land.js:7-238
+ * plateSeeds in the Set's insertion order; plateIsOcean: one byte per seed in that order (1: the plate id is in the
+ * returned Set).  An r_plate entry that is not a seed is refused (the reference throws on it). */
+int wo_assign_ocean_land(int32_t numRegions, const int32_t* adjOffset, const int32_t* adjList, const int32_t* r_plate,
+                         const int32_t* plateSeeds, int32_t numPlateSeeds, const float* r_xyz, double seed, int32_t numContinents,
+                         double continentSizeVariety, double landCoverage, uint8_t* plateIsOcean, int64_t* stats);
+/* Test / diagnostic entry, not needed by a host: the fdlibm ports the host stages use where the reference calls V8's Math,
+ * evaluated on the caller's arguments (tests/test_plates_gen.py holds them to V8's bits): fn 0 sin, 1 cos, 2 exp, over n doubles
+ * (sin / cos: |x| up to about 2^20 * pi/2 = 1 647 099, NaN beyond; csrc/import_ops.h). */
+int wo_v8_math(int32_t fn, int64_t n, const double* x, double* out);
 
 /* diffuseOceanWarmth(mesh, r_oceanWarmth, r_isLand, r_plateContinentality, passes)   js/temperature.js:19-66
  * Seeds the ocean cells with their warmth, then `passes` Jacobi sweeps of (self + neighbours) / (1 + degree); cells

@@ -35,6 +35,7 @@ SIGNATURES = {
     "wo_memory_in_use": (C.c_int, [_p, _p, _p]),
     "wo_fib_sphere_points": (C.c_int, [_c_i32, _c_f64, _c_f64, _p]),
     "wo_sphere_delaunay": (C.c_int, [_c_i32, _p, _p, _p]),
+    "wo_sphere_reference_closure": (C.c_int, [_c_i32, _p, _p]),
     "wo_mesh_csr": (C.c_int, [_c_i32, _c_i32, _p, _p, _p, _p, _p]),
     "wo_neighbor_dist": (C.c_int, [_c_i32, _p, _p, _p, _p]),
     "wo_triangle_elevations": (C.c_int, [_c_i32, _p, _p, _p]),
@@ -62,6 +63,9 @@ SIGNATURES = {
     "wo_classify_regions": (C.c_int, [_p, _p, _p, _p, _p]),
     "wo_project_coarse_plates": (C.c_int, [_p, _c_i32, _p, _p, _p, _p, _c_f64, _c_i32, _p]),
     "wo_smooth_reconnect_plates": (C.c_int, [_c_i32, _p, _p, _p, _p, _c_i32, _c_i32]),
+    "wo_generate_plates": (C.c_int, [_c_i32, _p, _p, _p, _c_i32, _c_f64, _p, _p, _p, _p, _p, _p]),
+    "wo_assign_ocean_land": (C.c_int, [_c_i32, _p, _p, _p, _p, _c_i32, _p, _c_f64, _c_i32, _c_f64, _c_f64, _p, _p]),
+    "wo_v8_math": (C.c_int, [_c_i32, _c_i64, _p, _p]),
     "wo_land_components": (C.c_int, [_c_i32, _p, _p, _p, _p]),
     "wo_diffuse_ocean_warmth": (C.c_int, [_p, _p, _p, _p, _c_i32, _p]),
     "wo_wind_convergence": (C.c_int, [_p, _p, _p, _p, _p]),

@@ -1,7 +1,9 @@
 // extern "C" entry points that need no GPU: status, mesh producers, noise tables.
 #include <cmath>
 #include <cstring>
+#include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/worogen.h"
 #include "host_util.h"
@@ -30,6 +32,54 @@ int wo_sphere_delaunay(int32_t numRegions, const float* r_xyz, int32_t* triangle
     int rc = wo::sphere_delaunay(numRegions, r_xyz, triangles, halfedges, err);
     if (rc) wo::set_error(err);
     return rc;
+}
+
+int wo_sphere_reference_closure(int32_t numRegions, int32_t* triangles, int32_t* halfedges) {
+    if (numRegions < 4 || !triangles || !halfedges) { wo::set_error("wo_sphere_reference_closure: bad arguments"); return 1; }
+    const int32_t pole = numRegions - 1, numTri = 2 * numRegions - 4;
+    const int64_t allSides = 3 * (int64_t)numTri;
+    try {
+        // the planar part: triangles without the pole, renumbered in their order; half-edges into the fan become -1
+        std::vector<int32_t> newId(numTri, -1);
+        int32_t kept = 0;
+        for (int32_t t = 0; t < numTri; ++t) {
+            for (int k = 0; k < 3; ++k) if (triangles[3 * t + k] < 0 || triangles[3 * t + k] >= numRegions) throw std::invalid_argument("triangle vertex out of range");
+            if (triangles[3 * t] != pole && triangles[3 * t + 1] != pole && triangles[3 * t + 2] != pole) newId[t] = kept++;
+        }
+        std::vector<int32_t> nt(allSides, 0), nh(allSides, 0);
+        std::vector<int32_t> unpaired;
+        for (int32_t t = 0; t < numTri; ++t) {
+            if (newId[t] < 0) continue;
+            for (int k = 0; k < 3; ++k) {
+                const int64_t so = 3 * (int64_t)t + k, sn = 3 * (int64_t)newId[t] + k;
+                const int32_t h = halfedges[so];
+                if (h < 0 || h >= allSides) throw std::invalid_argument("half-edge out of range");
+                nt[sn] = triangles[so];
+                nh[sn] = newId[h / 3] >= 0 ? 3 * newId[h / 3] + h % 3 : -1;
+                if (nh[sn] < 0) unpaired.push_back((int32_t)sn);
+            }
+        }
+        const int32_t numSides = 3 * kept, nu = (int32_t)unpaired.size();
+        if (nu < 3 || kept + nu != numTri) throw std::invalid_argument("the pole fan does not close the hull");
+        // js/sphere-mesh.js:55-88: fan triangles numbered along the hull walk that starts at the last unpaired side
+        std::vector<int32_t> pointToSide(numRegions, -1);
+        for (int32_t s : unpaired) pointToSide[nt[s]] = s;                   // a later side replaces an earlier one
+        auto next = [](int32_t s) { return s % 3 == 2 ? s - 2 : s + 1; };
+        int32_t s = unpaired.back();
+        for (int32_t i = 0; i < nu; ++i) {
+            if (s < 0) throw std::invalid_argument("the hull is not one closed walk");
+            const int32_t ns = numSides + 3 * i;
+            nh[s] = ns; nh[ns] = s;
+            nt[ns] = nt[next(s)]; nt[ns + 1] = nt[s]; nt[ns + 2] = pole;
+            const int32_t k = numSides + (3 * i + 4) % (3 * nu);
+            nh[ns + 2] = k; nh[k] = ns + 2;
+            s = pointToSide[nt[next(s)]];
+        }
+        std::copy(nt.begin(), nt.end(), triangles);
+        std::copy(nh.begin(), nh.end(), halfedges);
+    } catch (const std::invalid_argument& e) { wo::set_error(std::string("wo_sphere_reference_closure: ") + e.what()); return 1; }
+      catch (const std::exception& e) { wo::set_error(std::string("wo_sphere_reference_closure: ") + e.what()); return 3; }
+    return 0;
 }
 
 int wo_mesh_csr(int32_t numRegions, int32_t numSides, const int32_t* triangles, const int32_t* halfedges,

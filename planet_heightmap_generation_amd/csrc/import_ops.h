@@ -7,6 +7,10 @@
 //     ~6 % of f32-derived asin arguments and ~18 % of atan2 ones), and one ulp in one sampled cell can move the priority
 //     flood downstream.  Plain f64 arithmetic and bit manipulation only; the library compiles with -ffp-contract=off, so no
 //     FMA changes a result.
+//   * fd_sin / fd_cos / fd_exp (with fd_kernel_sin / fd_kernel_cos / fd_rem_pio2) are the same for s_sin.c / s_cos.c / e_exp.c: Math.sin,
+//     Math.cos and Math.exp of the plate generation's host stage (csrc/plates_gen_host.cc: Euler pole angles in [0, 2pi), continent
+//     weights exp(x) with |x| <= 1.25).  Supported domain of sin / cos: |x| up to about 2^20 * pi/2 = 1 647 099 (the reduction's
+//     special case and medium path); beyond it they return NaN instead of a number fdlibm would not give.  exp: every double.
 //   * sample_heightmap_cell restates sampleHeightmap / sampleBilinear / grayscaleToElevation (:682-727) in the
 //     reference's operation order (left-to-right association of the four bilinear products), f64 throughout, f32 store.
 //   * classification (:811-831) on the FINAL field with JS comparison semantics (NaN is land, never coast or mountain):
@@ -149,6 +153,164 @@ WO_IMP_HD inline double fd_atan2(double y, double x) {
         case 2: return pi - (z - pi_lo);
         default: return (z - pi_lo) - pi;
     }
+}
+
+// k_sin.c: sine on [-pi/4, pi/4]; (x, y) is the reduced argument head and tail, iy == 0 says y is exactly 0
+WO_IMP_HD inline double fd_kernel_sin(double x, double y, int iy) {
+    const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
+                 S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+    const int32_t ix = hi_word(x) & 0x7fffffff;
+    if (ix < 0x3e400000) { if ((int)x == 0) return x; }    // |x| < 2^-27
+    const double z = x * x, v = z * x;
+    const double r = S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)));
+    if (iy == 0) return x + v * (S1 + z * r);
+    return x - ((z * (0.5 * y - v * r) - y) - v * S1);
+}
+
+// k_cos.c: cosine on [-pi/4, pi/4]
+WO_IMP_HD inline double fd_kernel_cos(double x, double y) {
+    const double one = 1.0;
+    const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
+                 C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+    const int32_t ix = hi_word(x) & 0x7fffffff;
+    if (ix < 0x3e400000) { if ((int)x == 0) return one; }  // |x| < 2^-27
+    const double z = x * x;
+    const double r = z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))));
+    if (ix < 0x3FD33333) return one - (0.5 * z - (z * r - x * y));          // |x| < 0.3
+    double qx;
+    if (ix > 0x3fe90000) qx = 0.28125;                      // |x| > 0.78125
+    else { const uint64_t u = (uint64_t)(uint32_t)(ix - 0x00200000) << 32; memcpy(&qx, &u, 8); }     // x / 4
+    const double hz = 0.5 * z - qx, a = one - qx;
+    return a - (hz - (z * r - x * y));
+}
+
+// e_rem_pio2.c without its last branch: y[0] + y[1] = x - n * pi/2 for |x| up to about 2^20 * pi/2 (high word <= 0x413921fb), which
+// takes the special case below 3pi/4 and the medium path with up to three rounds of Cody-Waite subtraction.  Larger
+// arguments need the 1584-bit table of k_rem_pio2.c, which is not ported: returns false and the callers give NaN.
+WO_IMP_HD inline bool fd_rem_pio2(double x, double* y, int32_t* nOut) {
+    const int32_t npio2_hw[32] = {0x3FF921FB, 0x400921FB, 0x4012D97C, 0x401921FB, 0x401F6A7A, 0x4022D97C, 0x4025FDBB, 0x402921FB,
+                                  0x402C463A, 0x402F6A7A, 0x4031475C, 0x4032D97C, 0x40346B9C, 0x4035FDBB, 0x40378FDB, 0x403921FB,
+                                  0x403AB41B, 0x403C463A, 0x403DD85A, 0x403F6A7A, 0x40407E4C, 0x4041475C, 0x4042106C, 0x4042D97C,
+                                  0x4043A28C, 0x40446B9C, 0x404534AC, 0x4045FDBB, 0x4046C6CB, 0x40478FDB, 0x404858EB, 0x404921FB};
+    const double half = 0.5, invpio2 = 6.36619772367581382433e-01, pio2_1 = 1.57079632673412561417e+00, pio2_1t = 6.07710050650619224932e-11,
+                 pio2_2 = 6.07710050630396597660e-11, pio2_2t = 2.02226624879595063154e-21, pio2_3 = 2.02226624871116645580e-21,
+                 pio2_3t = 8.47842766036889956997e-32;
+    double z, w, t, r, fn;
+    const int32_t hx = hi_word(x), ix = hx & 0x7fffffff;
+    if (ix <= 0x3fe921fb) { y[0] = x; y[1] = 0; *nOut = 0; return true; }        // |x| <= pi/4
+    if (ix < 0x4002d97c) {                                                          // |x| < 3pi/4: n = +-1
+        if (hx > 0) {
+            z = x - pio2_1;
+            if (ix != 0x3ff921fb) { y[0] = z - pio2_1t; y[1] = (z - y[0]) - pio2_1t; }
+            else { z -= pio2_2; y[0] = z - pio2_2t; y[1] = (z - y[0]) - pio2_2t; }   // near pi/2: 33 + 33 + 53 bits of pi
+            *nOut = 1;
+        } else {
+            z = x + pio2_1;
+            if (ix != 0x3ff921fb) { y[0] = z + pio2_1t; y[1] = (z - y[0]) + pio2_1t; }
+            else { z += pio2_2; y[0] = z + pio2_2t; y[1] = (z - y[0]) + pio2_2t; }
+            *nOut = -1;
+        }
+        return true;
+    }
+    if (ix > 0x413921fb) return false;
+    t = fd_fabs(x);
+    const int32_t n = (int32_t)(t * invpio2 + half);
+    fn = (double)n;
+    r = t - fn * pio2_1;
+    w = fn * pio2_1t;                                                               // first round: good to 85 bits
+    if (n < 32 && ix != npio2_hw[n - 1]) {
+        y[0] = r - w;
+    } else {
+        const int32_t j = ix >> 20;
+        y[0] = r - w;
+        int32_t i = j - (int32_t)(((uint32_t)hi_word(y[0]) >> 20) & 0x7ff);
+        if (i > 16) {                                                               // second round: good to 118 bits
+            t = r; w = fn * pio2_2; r = t - w; w = fn * pio2_2t - ((t - r) - w); y[0] = r - w;
+            i = j - (int32_t)(((uint32_t)hi_word(y[0]) >> 20) & 0x7ff);
+            if (i > 49) { t = r; w = fn * pio2_3; r = t - w; w = fn * pio2_3t - ((t - r) - w); y[0] = r - w; }   // third: 151 bits
+        }
+    }
+    y[1] = (r - y[0]) - w;
+    if (hx < 0) { y[0] = -y[0]; y[1] = -y[1]; *nOut = -n; } else *nOut = n;
+    return true;
+}
+
+// s_sin.c / s_cos.c in V8's form (Math.sin, Math.cos).  Supported domain: |x| < about 1 647 099 (2^20 * pi/2: high word <= 0x413921fb), which
+// holds every argument this library forms (Euler pole angles in [0, 2pi)); infinities and NaN give NaN as in fdlibm,
+// finite arguments beyond the domain give NaN as well (fdlibm would go on to k_rem_pio2.c).
+WO_IMP_HD inline double fd_sin(double x) {
+    const int32_t ix = hi_word(x) & 0x7fffffff;
+    if (ix <= 0x3fe921fb) return fd_kernel_sin(x, 0.0, 0);
+    if (ix >= 0x7ff00000) return x - x;
+    double y[2]; int32_t n;
+    if (!fd_rem_pio2(x, y, &n)) return (x - x) / (x - x);
+    switch (n & 3) {
+        case 0: return fd_kernel_sin(y[0], y[1], 1);
+        case 1: return fd_kernel_cos(y[0], y[1]);
+        case 2: return -fd_kernel_sin(y[0], y[1], 1);
+        default: return -fd_kernel_cos(y[0], y[1]);
+    }
+}
+WO_IMP_HD inline double fd_cos(double x) {
+    const int32_t ix = hi_word(x) & 0x7fffffff;
+    if (ix <= 0x3fe921fb) return fd_kernel_cos(x, 0.0);
+    if (ix >= 0x7ff00000) return x - x;
+    double y[2]; int32_t n;
+    if (!fd_rem_pio2(x, y, &n)) return (x - x) / (x - x);
+    switch (n & 3) {
+        case 0: return fd_kernel_cos(y[0], y[1]);
+        case 1: return -fd_kernel_sin(y[0], y[1], 1);
+        case 2: return -fd_kernel_cos(y[0], y[1]);
+        default: return fd_kernel_sin(y[0], y[1], 1);
+    }
+}
+
+// e_exp.c in V8's form (Math.exp; exp(1) returns Math.E exactly).  Supported domain: every double.
+WO_IMP_HD inline double fd_exp(double x) {
+    const double one = 1.0, halF[2] = {0.5, -0.5}, o_threshold = 7.09782712893383973096e+02, u_threshold = -7.45133219101941108420e+02,
+                 ln2HI[2] = {6.93147180369123816490e-01, -6.93147180369123816490e-01}, ln2LO[2] = {1.90821492927058770002e-10, -1.90821492927058770002e-10},
+                 invln2 = 1.44269504088896338700e+00, P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03,
+                 P3 = 6.61375632143793436117e-05, P4 = -1.65339022054652515390e-06, P5 = 4.13813679705723846039e-08, E = 2.718281828459045;
+    const double huge = 1.0e+300, twom1000 = 9.33263618503218878990e-302, two1023 = 8.988465674311579539e307;
+    double y, hi = 0.0, lo = 0.0, c, t, twopk;
+    int32_t k = 0;
+    uint32_t hx = (uint32_t)hi_word(x);
+    const int32_t xsb = (int32_t)((hx >> 31) & 1);
+    hx &= 0x7fffffff;
+    if (hx >= 0x40862E42) {                                  // |x| >= 709.78...
+        if (hx >= 0x7ff00000) {
+            if (((hx & 0xfffff) | lo_word(x)) != 0) return x + x;      // NaN
+            return xsb == 0 ? x : 0.0;                       // exp(+-inf) = {inf, 0}
+        }
+        if (x > o_threshold) return huge * huge;
+        if (x < u_threshold) return twom1000 * twom1000;
+    }
+    if (hx > 0x3fd62e42) {                                   // |x| > 0.5 ln2
+        if (hx < 0x3FF0A2B2) {                               // and |x| < 1.5 ln2
+            if (x == 1.0) return E;
+            hi = x - ln2HI[xsb]; lo = ln2LO[xsb]; k = 1 - xsb - xsb;
+        } else {
+            k = (int32_t)(invln2 * x + halF[xsb]);
+            t = k;
+            hi = x - t * ln2HI[0];
+            lo = t * ln2LO[0];
+        }
+        x = hi - lo;
+    } else if (hx < 0x3e300000) {                            // |x| < 2^-28
+        if (huge + x > one) return one + x;
+    } else {
+        k = 0;
+    }
+    t = x * x;
+    { const uint64_t u = (uint64_t)(uint32_t)(0x3ff00000 + ((k >= -1021 ? k : k + 1000) * 1048576)) << 32; memcpy(&twopk, &u, 8); }
+    c = x - t * (P1 + t * (P2 + t * (P3 + t * (P4 + t * P5))));
+    if (k == 0) return one - ((x * c) / (c - 2.0) - x);
+    y = one - ((lo - (x * c) / (2.0 - c)) - hi);
+    if (k >= -1021) {
+        if (k == 1024) return y * 2.0 * two1023;
+        return y * twopk;
+    }
+    return y * twopk * twom1000;
 }
 
 // sampleHeightmap for one cell (:710-727 with sampleBilinear :682-697 and grayscaleToElevation :704-707)

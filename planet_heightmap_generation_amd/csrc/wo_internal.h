@@ -122,6 +122,13 @@ bool flood_pass23_host(float* e, double carveStrength, FloodScratch& S, const st
 void smooth_reconnect_plates_host(int32_t N, const int32_t* off, const int32_t* adj, int32_t* r_plate, int32_t numSeeds,
                                   const int32_t* plateSeeds, int32_t numPasses);
 
+// plates_gen_host.cc — js/plates.js:6-232 and js/ocean-land.js:7-238 (stats: NULL or WO_PLATES_GEN_STATS counters, see worogen.h)
+int32_t generate_plates_host(int32_t N, const int32_t* off, const int32_t* adj, const float* xyz, int32_t numPlates, double seed,
+                             int32_t* r_plate, int32_t* seedsOut, double* poleOut, double* omegaOut, int64_t* stats);
+void assign_ocean_land_host(int32_t N, const int32_t* off, const int32_t* adj, const int32_t* r_plate, int32_t P, const int32_t* plateIds,
+                            const float* xyz, double seed, int32_t numContinents, double variety, double landCoverage,
+                            uint8_t* isOceanOut, int64_t* stats);
+
 // super_plates_host.cc — js/super-plates.js
 // slotOf[max seed + 1]: plate id -> position in plateSeeds, -1 for the ids in between.  Throws std::invalid_argument on a
 // negative or repeated seed and on more than WO_SUPER_MAX_PLATES seeds.

@@ -1,12 +1,31 @@
 // worker_threads counterpart of the reference's Web Worker (js/planet-worker.js) for the part of its message protocol
-// that is the device path: the retained state W (:277-292), `reapply` (:341-440), `editRecompute` (:442-577),
+// that is the device path: `generate` (:136-339), the retained state W (:277-292), `reapply` (:341-440), `editRecompute` (:442-577),
 // `computeClimate` (:579-677) and the dispatcher (:944-954); and `exportMap`, which the reference runs on its page with WebGL
 // (js/planet-mesh.js:1752-2180) and a Node host has no other way to get.
 //
+//   cmd 'generate' { N, P, jitter, nMag, numContinents, <the six sliders>, continentSizeVariety = 0, temperatureOffset = 0, precipitationOffset = 0,
+//                    landCoverage = 0.3, seed?, toggledIndices? }   (:136-339)
+//                  a seed becomes a planet, every stage native: mesh (the pole fan numbered as the reference's addPoleToMesh numbers it), neighbour
+//                  distances, triangle centres, generateCoarsePlates (generatePlates + assignOceanLand on the 20 000-cell mesh: native host stages,
+//                  a few milliseconds, no device part), projectCoarsePlates (device), smoothAndReconnectPlates(…, 3), the toggled plates, the three
+//                  density tables, then the chain `editRecompute` runs: buildSuperPlates when P >= 8, assignElevation, runPostProcessing with the
+//                  call's hotspot layer, triangle elevations — the field stays on the device from assignElevation on.  Without `seed`:
+//                  Math.floor(Math.random() * 16777216).  Progress 0 / 10 / 20 / 25 / 35 / 60 / 75 with the reference's labels.  Climate is not run
+//                  here, as for every other command of this worker: skipClimate is reported as true, the 19 climate fields are null and the caller
+//                  follows with `computeClimate` (the reference's own behaviour above 300 k cells).  The result is the reference's `done` message
+//                  (same keys in the same order, _pipelineTiming with the reference's stage names less the climate entries), the same seven
+//                  buffers transferred.  W keeps what reapply, editRecompute, computeClimate and exportMap need: the pre-erosion field and the
+//                  hotspot layer on the device, triangles, halfedges, r_plate, plateSeeds, plateVec, the densities, P, both ocean sets and the three
+//                  climate parameters; the wind and ocean blocks are invalid, as after `retain`.  N or P not a positive integer:
+//                  `generate needs N and P (a generate without them is not served by the device worker)`, the state is kept.  A failure
+//                  before the projection (mesh, coarse plates) keeps the previous state too; one after it leaves no state at all.
+//                  -> { type: 'done', triangles, halfedges, numRegions, r_xyz, t_xyz, r_plate, plateSeeds, plateVec, plateIsOcean, originalPlateIsOcean,
+//                       plateDensity, plateDensityLand, plateDensityOcean, prePostElev, r_elevation, t_elevation, mountain_r, coastline_r, ocean_r,
+//                       r_stress, <the 19 climate fields: null>, skipClimate: true, seed, nMag, debugLayers, _timing, _pipelineTiming, _postTiming,
+//                       _workerTotal, _params }
 //   cmd 'retain'   { mesh: { numRegions, adjOffset, adjList, triangles?, halfedges? }, r_xyz, neighborDist?, prePostElev, seed, r_hotspot?,
 //                    r_plate?, plateIsOcean?, plateSeeds?, plateVec?, plateDensity?, P? }
-//                  What `generate` leaves in W for later reapplies, handed over by the caller (plate generation and ocean /
-//                  land assignment are the reference's own host code and stay where they are).  The mesh, positions and the
+//                  What `generate` leaves in W for later reapplies, handed over by a caller that made the planet elsewhere.  The mesh, positions and the
 //                  pre-erosion field go to HBM ONCE and stay there.  r_plate (Int32Array) and plateIsOcean (the ids of the
 //                  oceanic plates: a Set, an array or an Int32Array) are what a later `computeClimate` needs.  plateSeeds (the Set's
 //                  iteration order: an array, a Set or an Int32Array), plateVec ({ id: { pole, omega } }), plateDensity ({ id: density })
@@ -53,8 +72,7 @@
 //                       _exportTiming: { raster, color, encode, workerTotal } }, the buffers transferred
 //   cmd 'dispose'  frees the retained state -> { type: 'disposed' }
 //   progress / errors exactly as the reference posts them: { type: 'progress', pct, label }, { type: 'error', message, stack };
-//   an unknown command answers `Unknown command: <cmd>` (:952).  `generate` is not served: plate generation and ocean / land
-//   assignment are the reference's own host code.
+//   an unknown command answers `Unknown command: <cmd>` (:952).
 //
 // Usage (Node >= 12):  const w = new Worker(new URL('./planet-worker.js', import.meta.url)); w.postMessage({ cmd: 'retain', ... })
 import { parentPort } from 'worker_threads';
@@ -64,7 +82,8 @@ import { runPostProcessingResident } from './post-processing.js';
 import { buildSphere, computeNeighborDist, generateTriangleCenters } from './sphere-mesh.js';
 import { platesFromDevice } from './heightmap-import.js';
 import { OCEAN_KEYS, PRECIP_KEYS, TEMP_KEYS, downloadAll } from './climate-blocks.js';
-import { denseTable, LAYERS } from './plate-table.js';
+import { denseTable, plateDensities, LAYERS } from './plate-table.js';
+import { generateCoarsePlates } from './coarse-plates.js';
 import { SimplexNoise } from './simplex-noise.js';
 import { MAP_TYPES, exportFilename, encodePng } from './map-export.js';
 
@@ -212,8 +231,50 @@ function superPlateTable(res) {
     return { numIds: n, hasVec: new Uint8Array(n).fill(1), pole: res.pole, omega: res.omega, isOcean: res.isOcean, density: res.density };
 }
 
-// js/planet-worker.js:442-577 with every stage native, on W.planet; the field stays on the device from assignElevation to the
-// end of the post-processing
+// The part `generate` (:203-273) and `editRecompute` (:459-480) have in common, every stage native on W.planet: buildSuperPlates when
+// W.P >= 8, assignElevation, runPostProcessing with the call's own hotspot layer, triangle elevations.  assignElevation leaves the field
+// resident; it is saved there as the new W.prePostElev and never leaves the device before the post-processing has run.
+// onStage(name) is called before 'elevation', 'erosion' and 'triangles' (the callers post their own progress labels).
+function elevationChain(sliders, nMag, onStage) {
+    const { planet, numRegions: N, r_plate, plateSeeds, plateVec, seed } = W;
+    const spread = 5;
+    const plates = denseTable(W.plateIsOcean, plateVec, W.plateDensity, plateSeeds);
+
+    let t0 = performance.now();
+    let sup = null;
+    if ((W.P || 0) >= 8) sup = addon.buildSuperPlates(planet, r_plate, plates, plateSeeds);
+    const tSuper = performance.now() - t0;
+
+    onStage('elevation');
+    t0 = performance.now();
+    if (!W.noise) W.noise = new SimplexNoise(seed);
+    const res = addon.assignElevation(planet, r_plate, plates, plateSeeds, sup ? sup.r_superPlate : null, sup ? superPlateTable(sup) : null,
+                                      W.noise.perm, W.noise.pm12, nMag, seed, spread, true);
+    const _timing = addon.lastStageTiming(planet);
+    const tElev = performance.now() - t0;
+    const debugLayers = {};
+    LAYERS.forEach((name, i) => { debugLayers[name] = res.debugLayers.subarray(i * N, (i + 1) * N); });
+    if (sup) debugLayers.superPlates = new Float32Array(sup.r_superPlate);
+    const prePostElev = res.r_elevation;
+
+    onStage('erosion');
+    t0 = performance.now();
+    W.cachedWind = null; W.cachedOcean = null;     // the elevation changes: the wind and ocean blocks no longer belong to it
+    addon.planetSaveState(planet);                  // the new W.prePostElev, device copy: assignElevation left the field resident
+    addon.planetUploadHotspot(planet, debugLayers.hotspot);
+    const r_elevation = new Float32Array(N);
+    const { dl_erosionDelta, postTiming } = runPostProcessingResident(planet, N, r_elevation, sliders, seed, true);
+    const tPost = performance.now() - t0;
+    debugLayers.erosionDelta = dl_erosionDelta;
+
+    onStage('triangles');
+    t0 = performance.now();
+    const t_elevation = W.triangles ? addon.triangleElevations(W.triangles, r_elevation) : new Float32Array(0);
+    const tTriElev = performance.now() - t0;
+    return { sup, res, _timing, debugLayers, prePostElev, r_elevation, t_elevation, postTiming, tSuper, tElev, tPost, tTriElev };
+}
+
+// js/planet-worker.js:442-577 with every stage native, on W.planet
 function handleEditRecompute(data) {
     if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for editRecompute (not served by the device worker before retain)' }); return; }
     const missing = ['r_plate', 'plateSeeds', 'plateVec'].filter((k) => !W[k]);
@@ -224,54 +285,124 @@ function handleEditRecompute(data) {
     getClimateParams(data);                              // the parameters persist in W for the computeClimate that follows (:446)
     try {
         const tTotal0 = performance.now();
-        progress(0, 'Rebuilding elevation\u2026');
+        progress(0, 'Rebuilding elevation…');
         W.plateIsOcean = Int32Array.from(data.plateIsOcean);
         W.plateDensity = Object.assign({}, data.plateDensity);
-        const { planet, numRegions: N, r_plate, plateSeeds, plateVec, seed } = W;
-        const nMag = data.nMag, spread = 5;
-        const plates = denseTable(W.plateIsOcean, plateVec, W.plateDensity, plateSeeds);
-
-        let sup = null;
-        if ((W.P || 0) >= 8) sup = addon.buildSuperPlates(planet, r_plate, plates, plateSeeds);
-
-        let t0 = performance.now();
-        if (!W.noise) W.noise = new SimplexNoise(seed);
-        const res = addon.assignElevation(planet, r_plate, plates, plateSeeds, sup ? sup.r_superPlate : null, sup ? superPlateTable(sup) : null,
-                                          W.noise.perm, W.noise.pm12, nMag, seed, spread, true);
-        const _timing = addon.lastStageTiming(planet);
-        const tElev = performance.now() - t0;
-        const debugLayers = {};
-        LAYERS.forEach((name, i) => { debugLayers[name] = res.debugLayers.subarray(i * N, (i + 1) * N); });
-        if (sup) debugLayers.superPlates = new Float32Array(sup.r_superPlate);
-        const prePostElev = res.r_elevation;
-
-        progress(50, 'Eroding terrain\u2026');
-        t0 = performance.now();
-        W.cachedWind = null; W.cachedOcean = null;     // the elevation changes: the wind and ocean blocks no longer belong to it
-        addon.planetSaveState(planet);                  // the new W.prePostElev, device copy: assignElevation left the field resident
-        addon.planetUploadHotspot(planet, debugLayers.hotspot);
-        const r_elevation = new Float32Array(N);
-        const { dl_erosionDelta, postTiming } = runPostProcessingResident(planet, N, r_elevation, data, seed, true);
-        const tPost = performance.now() - t0;
-        debugLayers.erosionDelta = dl_erosionDelta;
-
-        progress(75, 'Computing triangle elevations\u2026');
-        t0 = performance.now();
-        const t_elevation = W.triangles ? addon.triangleElevations(W.triangles, r_elevation) : new Float32Array(0);
-        const tTriElev = performance.now() - t0;
+        const c = elevationChain(data, data.nMag, (stage) => {
+            if (stage === 'erosion') progress(50, 'Eroding terrain…');
+            else if (stage === 'triangles') progress(75, 'Computing triangle elevations…');
+        });
 
         const climate = {};
         for (const k of CLIMATE_NULLS) climate[k] = null;
         const result = {
-            type: 'editDone', skipClimate: true, prePostElev, r_elevation, t_elevation,
-            mountain_r: Array.from(res.mountain), coastline_r: Array.from(res.coastline), ocean_r: Array.from(res.ocean), r_stress: res.r_stress,
-            ...climate, debugLayers,
-            _editTiming: { elevation: tElev, postProcessing: tPost, wind: 0, ocean: 0, precipitation: 0, temperature: 0, triangleElevations: tTriElev,
+            type: 'editDone', skipClimate: true, prePostElev: c.prePostElev, r_elevation: c.r_elevation, t_elevation: c.t_elevation,
+            mountain_r: Array.from(c.res.mountain), coastline_r: Array.from(c.res.coastline), ocean_r: Array.from(c.res.ocean), r_stress: c.res.r_stress,
+            ...climate, debugLayers: c.debugLayers,
+            _editTiming: { elevation: c.tElev, postProcessing: c.tPost, wind: 0, ocean: 0, precipitation: 0, temperature: 0, triangleElevations: c.tTriElev,
                            retainState: 0, workerTotal: performance.now() - tTotal0 },
-            _timing, _postTiming: postTiming
+            _timing: c._timing, _postTiming: c.postTiming
         };
-        parentPort.postMessage(result, [prePostElev.buffer, r_elevation.buffer, t_elevation.buffer, res.r_stress.buffer]);
+        parentPort.postMessage(result, [c.prePostElev.buffer, c.r_elevation.buffer, c.t_elevation.buffer, c.res.r_stress.buffer]);
     } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
+// js/planet-worker.js:136-339 with every stage native; the result is the reference's `done` message
+function handleGenerate(data) {
+    const { N, P, jitter, nMag, numContinents, smoothing, hydraulicErosion, thermalErosion, ridgeSharpening, glacialErosion, terrainWarp,
+            continentSizeVariety = 0, temperatureOffset = 0, precipitationOffset = 0, landCoverage = 0.3, seed: overrideSeed, toggledIndices } = data;
+    if (!(Number.isInteger(N) && N >= 1 && Number.isInteger(P) && P >= 1)) {
+        // the reference would throw inside buildSphere; the retained state, if any, is kept
+        parentPort.postMessage({ type: 'error', message: 'generate needs N and P (a generate without them is not served by the device worker)' });
+        return;
+    }
+    const timing = [];
+    let replaced = false;
+    try {
+        const tTotal0 = performance.now();
+        progress(0, 'Shaping the world…');
+        const seed = (overrideSeed !== undefined && overrideSeed !== null) ? overrideSeed : Math.floor(Math.random() * 16777216);
+
+        let t0 = performance.now();
+        const { mesh, r_xyz } = buildSphere(N, jitter, seed, true);
+        timing.push({ stage: 'Sphere mesh (Fibonacci + Delaunay + pole)', ms: performance.now() - t0 });
+        t0 = performance.now();
+        const neighborDist = computeNeighborDist(mesh, r_xyz);
+        timing.push({ stage: 'Neighbor distances', ms: performance.now() - t0 });
+        t0 = performance.now();
+        const t_xyz = generateTriangleCenters(mesh, r_xyz);
+        timing.push({ stage: 'Triangle centers', ms: performance.now() - t0 });
+
+        progress(10, 'Generating coarse plates…');
+        t0 = performance.now();
+        const { coarseMesh, coarse_xyz, coarse_r_plate, coarsePlateSeeds, coarsePlateVec, coarsePlateIsOcean } =
+            generateCoarsePlates(seed, P, numContinents, continentSizeVariety, landCoverage);
+        timing.push({ stage: `Coarse plates (${P} plates, ${numContinents} continents)`, ms: performance.now() - t0 });
+
+        progress(20, 'Projecting plates…');
+        t0 = performance.now();
+        releaseRetained();
+        replaced = true;
+        const planet = addon.planetCreate(defaultContext(), mesh.numRegions, mesh.adjOffset, mesh.adjList, r_xyz, neighborDist);
+        W = { planet, numRegions: mesh.numRegions, triangles: mesh.triangles, halfedges: mesh.halfedges, seed, hasHotspot: false, r_plate: null, plateIsOcean: null,
+              plateSeeds: null, plateVec: null, plateDensity: {}, P, cachedWind: null, cachedOcean: null, temperatureOffset, precipitationOffset, landCoverage };
+        const r_plate = addon.projectCoarsePlates(planet, coarseMesh.adjOffset, coarseMesh.adjList, coarse_xyz, coarse_r_plate, seed, P);
+        timing.push({ stage: 'Project coarse → hi-res', ms: performance.now() - t0 });
+
+        progress(25, 'Smoothing boundaries…');
+        t0 = performance.now();
+        const seedArr = Int32Array.from(coarsePlateSeeds);
+        addon.smoothAndReconnectPlates(mesh.numRegions, mesh.adjOffset, mesh.adjList, r_plate, seedArr, 3);
+        timing.push({ stage: 'Smooth projected plates', ms: performance.now() - t0 });
+
+        const plateSeeds = coarsePlateSeeds, plateVec = coarsePlateVec, plateIsOcean = coarsePlateIsOcean;
+        const originalPlateIsOcean = new Set(plateIsOcean);
+        if (toggledIndices && toggledIndices.length > 0) {
+            for (const i of toggledIndices) {
+                if (i < seedArr.length) {
+                    const r = seedArr[i];
+                    if (plateIsOcean.has(r)) plateIsOcean.delete(r); else plateIsOcean.add(r);
+                }
+            }
+        }
+        const { plateDensity, plateDensityLand, plateDensityOcean } = plateDensities(plateSeeds, plateIsOcean);
+
+        W.r_plate = new Int32Array(r_plate);             // copies: r_plate's buffer leaves with the message
+        W.plateSeeds = seedArr; W.plateVec = plateVec; W.plateIsOcean = Int32Array.from(plateIsOcean);
+        W.originalPlateIsOcean = Int32Array.from(originalPlateIsOcean);
+        W.plateDensity = Object.assign({}, plateDensity);
+        W.plateDensityLand = Object.assign({}, plateDensityLand); W.plateDensityOcean = Object.assign({}, plateDensityOcean);
+        W.nMag = nMag;
+
+        const c = elevationChain({ smoothing, glacialErosion, hydraulicErosion, thermalErosion, ridgeSharpening, terrainWarp }, nMag, (stage) => {
+            if (stage === 'elevation') progress(35, 'Raising mountains…');
+            else if (stage === 'erosion') progress(60, 'Eroding terrain…');
+            else progress(75, 'Computing triangle elevations…');
+        });
+        W.hasHotspot = true;                             // the call's hotspot layer stays on the device for the reapplies that follow
+        if (c.sup) timing.push({ stage: `Super plates (${c.sup.numSuperPlates} groups from ${P} plates)`, ms: c.tSuper });
+        timing.push({ stage: 'Elevation (collisions + stress + distance fields + assignment)', ms: c.tElev });
+        timing.push({ stage: 'Terrain post-processing (total)', ms: c.tPost });
+        timing.push({ stage: 'Triangle elevations', ms: c.tTriElev });
+        timing.push({ stage: 'Clone state for retention', ms: 0 });          // the state is on the device already
+
+        const climate = {};
+        for (const k of CLIMATE_NULLS) climate[k] = null;
+        const result = {
+            type: 'done', triangles: mesh.triangles, halfedges: mesh.halfedges, numRegions: mesh.numRegions, r_xyz, t_xyz, r_plate,
+            plateSeeds: Array.from(plateSeeds), plateVec, plateIsOcean: Array.from(plateIsOcean), originalPlateIsOcean: Array.from(originalPlateIsOcean),
+            plateDensity, plateDensityLand, plateDensityOcean, prePostElev: c.prePostElev, r_elevation: c.r_elevation, t_elevation: c.t_elevation,
+            mountain_r: Array.from(c.res.mountain), coastline_r: Array.from(c.res.coastline), ocean_r: Array.from(c.res.ocean), r_stress: c.res.r_stress,
+            ...climate, skipClimate: true, seed, nMag, debugLayers: c.debugLayers,
+            _timing: c._timing, _pipelineTiming: timing, _postTiming: c.postTiming, _workerTotal: performance.now() - tTotal0,
+            _params: { N, P, jitter, nMag, numContinents, smoothing, terrainWarp, hydraulicErosion, thermalErosion, ridgeSharpening, glacialErosion,
+                       continentSizeVariety, temperatureOffset, precipitationOffset, landCoverage, seed }
+        };
+        parentPort.postMessage(result, [r_xyz.buffer, t_xyz.buffer, r_plate.buffer, c.prePostElev.buffer, c.r_elevation.buffer, c.t_elevation.buffer, c.res.r_stress.buffer]);
+    } catch (err) {
+        if (replaced) releaseRetained();                 // the half-built state is no state: a following reapply answers `No retained state`
         parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
     }
 }
@@ -403,9 +534,7 @@ parentPort.on('message', (data) => {
         case 'computeClimate': handleComputeClimate(data); break;
         case 'editRecompute': handleEditRecompute(data); break;
         case 'exportMap': handleExportMap(data); break;
-        case 'generate':
-            parentPort.postMessage({ type: 'error', message: `Command not served by the device worker (host stages of the reference): ${cmd}` });
-            break;
+        case 'generate': handleGenerate(data); break;
         default: parentPort.postMessage({ type: 'error', message: `Unknown command: ${cmd}` });
     }
 });

@@ -17,3 +17,18 @@ export function denseTable(isOceanSet, vec, density, ids) {
     for (const k of Object.keys(density)) t.density[+k] = density[k];
     return t;
 }
+
+// The three density tables of handleGenerate (js/planet-worker.js:193-201): per plate a Park-Miller stream seeded with id + 777
+// (js/rng.js:3-6), first draw oceanic (3.0 .. 3.5), second continental (2.4 .. 2.9); plateDensity takes the one of the plate's kind.
+export function plateDensities(plateSeeds, plateIsOcean) {
+    const isOcean = plateIsOcean instanceof Set ? plateIsOcean : new Set(plateIsOcean);
+    const plateDensity = {}, plateDensityLand = {}, plateDensityOcean = {};
+    for (const r of plateSeeds) {
+        let s = (Math.abs(Math.floor((r + 777) * 9301 + 49297)) % 2147483646) + 1;
+        const draw = () => { s = (s * 16807) % 2147483647; return (s - 1) / 2147483646; };
+        plateDensityOcean[r] = 3.0 + draw() * 0.5;
+        plateDensityLand[r] = 2.4 + draw() * 0.5;
+        plateDensity[r] = isOcean.has(r) ? plateDensityOcean[r] : plateDensityLand[r];
+    }
+    return { plateDensity, plateDensityLand, plateDensityOcean };
+}

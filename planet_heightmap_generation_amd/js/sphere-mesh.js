@@ -40,10 +40,13 @@ export function generateFibonacciSphere(N, jitter, rngSeed) {
     return addon.fibSpherePoints(N, jitter, rngSeed).subarray(0, 3 * N);
 }
 
-// buildSphere(N, jitter, makeRng(seed)) in the reference; here the seed itself is passed.
-export function buildSphere(N, jitter, rngSeed) {
+// buildSphere(N, jitter, makeRng(seed)) in the reference; here the seed itself is passed.  referenceClosure: number the closing
+// pole fan the way the reference's addPoleToMesh does (js/sphere-mesh.js:55-88) — the same triangles, but the CSR rows around the
+// pole then start at the reference's neighbour, which the order-defined host stages (generatePlates, the plate smoothing) can see.
+export function buildSphere(N, jitter, rngSeed, referenceClosure = false) {
     const r_xyz = addon.fibSpherePoints(N, jitter, rngSeed);         // pole already appended at index N
     const { triangles, halfedges } = addon.sphereDelaunay(r_xyz);
+    if (referenceClosure) addon.sphereReferenceClosure(N + 1, triangles, halfedges);
     return { mesh: new SphereMesh(triangles, halfedges, N + 1), r_xyz };
 }
 

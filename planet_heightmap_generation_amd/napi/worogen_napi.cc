@@ -78,6 +78,16 @@ napi_value SphereDelaunay(napi_env env, napi_callback_info info) {             /
     return o;
 }
 
+napi_value SphereReferenceClosure(napi_env env, napi_callback_info info) {     // (numRegions, triangles, halfedges): in place
+    Args a(env, info);
+    size_t ns, nh; int32_t* tri = (int32_t*)a.ta(1, napi_int32_array, &ns); if (!a.ok) return nullptr;
+    int32_t* he = (int32_t*)a.ta(2, napi_int32_array, &nh); if (!a.ok) return nullptr;
+    const int32_t V = a.i32(0);
+    if (V < 4 || ns != nh || ns != 3 * (size_t)(2 * (int64_t)V - 4)) { napi_throw_range_error(env, nullptr, "sphereReferenceClosure: triangles and halfedges must have 3*(2*numRegions-4) entries"); return nullptr; }
+    if (wo_sphere_reference_closure(V, tri, he)) return throw_wo(env, "sphereReferenceClosure");
+    return nullptr;
+}
+
 napi_value MeshCsr(napi_env env, napi_callback_info info) {                    // (numRegions, triangles, halfedges)
     Args a(env, info);
     const int32_t V = a.i32(0);
@@ -661,6 +671,55 @@ napi_value SmoothAndReconnectPlates(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
+// generatePlates(adjOffset, adjList, r_xyz, numPlates, seed) -> { r_plate, plateSeeds Int32Array (Set order), pole Float64Array(3P), omega Float64Array(P), stats Float64Array }
+napi_value GeneratePlates(napi_env env, napi_callback_info info) {
+    Args a(env, info);
+    size_t no, na, nx;
+    int32_t* off = (int32_t*)a.ta(0, napi_int32_array, &no); if (!a.ok) return nullptr;
+    int32_t* adj = (int32_t*)a.ta(1, napi_int32_array, &na); if (!a.ok) return nullptr;
+    float* xyz = (float*)a.ta(2, napi_float32_array, &nx); if (!a.ok) return nullptr;
+    const double np_ = a.num(3);
+    if (no < 2 || nx != 3 * (no - 1) || (size_t)off[no - 1] != na) { napi_throw_range_error(env, nullptr, "generatePlates: mesh arrays and r_xyz do not match"); return nullptr; }
+    if (!(np_ >= 1 && np_ <= 2147483647.0 && np_ == (double)(int64_t)np_)) { napi_throw_range_error(env, nullptr, "generatePlates: numPlates must be a positive integer"); return nullptr; }
+    const int32_t N = (int32_t)(no - 1), numPlates = (int32_t)np_;
+    const size_t cap = (size_t)(numPlates < N ? numPlates : N);
+    void* rp; napi_value rpv = make_ta(env, napi_int32_array, (size_t)N, 4, &rp); if (!rpv) return nullptr;
+    std::vector<int32_t> seeds(cap); std::vector<double> pole(3 * cap), omega(cap);
+    int32_t P = 0; int64_t st[WO_PLATES_GEN_STATS];
+    if (wo_generate_plates(N, off, adj, xyz, numPlates, a.num(4), (int32_t*)rp, seeds.data(), &P, pole.data(), omega.data(), st)) return throw_wo(env, "generatePlates");
+    void *d1, *d2, *d3, *d4;
+    napi_value sv = make_ta(env, napi_int32_array, (size_t)P, 4, &d1), pv = make_ta(env, napi_float64_array, 3 * (size_t)P, 8, &d2),
+               ov = make_ta(env, napi_float64_array, (size_t)P, 8, &d3), tv = make_ta(env, napi_float64_array, WO_PLATES_GEN_STATS, 8, &d4);
+    if (!sv || !pv || !ov || !tv) return nullptr;
+    std::memcpy(d1, seeds.data(), (size_t)P * 4); std::memcpy(d2, pole.data(), 3 * (size_t)P * 8); std::memcpy(d3, omega.data(), (size_t)P * 8);
+    for (int i = 0; i < WO_PLATES_GEN_STATS; ++i) ((double*)d4)[i] = (double)st[i];
+    napi_value o; napi_create_object(env, &o);
+    set_prop(env, o, "r_plate", rpv); set_prop(env, o, "plateSeeds", sv); set_prop(env, o, "pole", pv); set_prop(env, o, "omega", ov); set_prop(env, o, "stats", tv);
+    return o;
+}
+// assignOceanLand(adjOffset, adjList, r_plate, plateSeeds Int32Array, r_xyz, seed, numContinents, continentSizeVariety, landCoverage)
+//   -> { isOcean Uint8Array (one flag per seed), stats Float64Array }
+napi_value AssignOceanLand(napi_env env, napi_callback_info info) {
+    Args a(env, info);
+    size_t no, na, nr, ns, nx;
+    int32_t* off = (int32_t*)a.ta(0, napi_int32_array, &no); if (!a.ok) return nullptr;
+    int32_t* adj = (int32_t*)a.ta(1, napi_int32_array, &na); if (!a.ok) return nullptr;
+    int32_t* rp = (int32_t*)a.ta(2, napi_int32_array, &nr); if (!a.ok) return nullptr;
+    int32_t* seeds = (int32_t*)a.ta(3, napi_int32_array, &ns); if (!a.ok) return nullptr;
+    float* xyz = (float*)a.ta(4, napi_float32_array, &nx); if (!a.ok) return nullptr;
+    if (no < 2 || nr != no - 1 || nx != 3 * (no - 1) || (size_t)off[no - 1] != na) { napi_throw_range_error(env, nullptr, "assignOceanLand: mesh arrays, r_plate and r_xyz do not match"); return nullptr; }
+    if (ns < 1 || ns > nr) { napi_throw_range_error(env, nullptr, "assignOceanLand: plateSeeds must hold 1 .. numRegions ids"); return nullptr; }
+    void *d1, *d2;
+    napi_value fv = make_ta(env, napi_uint8_array, ns, 1, &d1), tv = make_ta(env, napi_float64_array, WO_PLATES_GEN_STATS, 8, &d2);
+    if (!fv || !tv) return nullptr;
+    int64_t st[WO_PLATES_GEN_STATS];
+    if (wo_assign_ocean_land((int32_t)(no - 1), off, adj, rp, seeds, (int32_t)ns, xyz, a.num(5), a.i32(6), a.num(7), a.num(8), (uint8_t*)d1, st)) return throw_wo(env, "assignOceanLand");
+    for (int i = 0; i < WO_PLATES_GEN_STATS; ++i) ((double*)d2)[i] = (double)st[i];
+    napi_value o; napi_create_object(env, &o);
+    set_prop(env, o, "isOcean", fv); set_prop(env, o, "stats", tv);
+    return o;
+}
+
 // ---- heightmap import (include/worogen.h: wo_sample_heightmap / wo_synthetic_plates / wo_classify_regions / wo_triangle_centers) ----
 // The image (Uint8Array or Uint8ClampedArray of imgW*imgH pixels) is checked before the planet handle is looked at.
 napi_value SampleHeightmap(napi_env env, napi_callback_info info) {            // (planet, gray, imgW, imgH, download) -> Float32Array | undefined
@@ -830,7 +889,8 @@ napi_value PlanetSetFloodExchange(napi_env env, napi_callback_info info) {    //
 
 napi_value Init(napi_env env, napi_value exports) {
     struct { const char* name; napi_callback fn; } fns[] = {
-        {"fibSpherePoints", FibSpherePoints}, {"sphereDelaunay", SphereDelaunay}, {"meshCsr", MeshCsr}, {"neighborDist", NeighborDist},
+        {"fibSpherePoints", FibSpherePoints}, {"sphereDelaunay", SphereDelaunay}, {"meshCsr", MeshCsr}, {"sphereReferenceClosure", SphereReferenceClosure},
+        {"generatePlates", GeneratePlates}, {"assignOceanLand", AssignOceanLand}, {"neighborDist", NeighborDist},
         {"triangleElevations", TriangleElevations}, {"noiseTables", NoiseTables}, {"noiseEval", NoiseEval}, {"noisePoint", NoisePoint},
         {"deviceCount", DeviceCount}, {"ctxCreate", CtxCreate}, {"planetCreate", PlanetCreate}, {"planetDestroy", PlanetDestroy},
         {"warpTerrain", WarpTerrain}, {"smoothElevation", SmoothElevation}, {"erodeComposite", ErodeComposite},

@@ -39,7 +39,8 @@ def fibonacci_sphere(N: int, jitter: float, seed: float) -> np.ndarray:
     return xyz
 
 
-def sphere_mesh_from_points(r_xyz: np.ndarray) -> SphereMesh:
+def sphere_mesh_from_points(r_xyz: np.ndarray, reference_closure: bool = False) -> SphereMesh:
+    """reference_closure: number the closing pole fan the way the reference's addPoleToMesh does (js/sphere-mesh.js:55-88)."""
     r_xyz = np.ascontiguousarray(r_xyz, dtype=np.float32).reshape(-1)
     V = r_xyz.size // 3
     ns = 3 * (2 * V - 4)
@@ -47,6 +48,8 @@ def sphere_mesh_from_points(r_xyz: np.ndarray) -> SphereMesh:
     he = np.empty(ns, dtype=np.int32)
     L = capi.lib()
     capi.check(L.wo_sphere_delaunay(V, capi.ptr(r_xyz), capi.ptr(tri), capi.ptr(he)), "wo_sphere_delaunay")
+    if reference_closure:
+        capi.check(L.wo_sphere_reference_closure(V, capi.ptr(tri), capi.ptr(he)), "wo_sphere_reference_closure")
     return sphere_mesh_from_triangles(tri, he, V)
 
 
@@ -72,10 +75,10 @@ def compute_neighbor_dist(mesh: SphereMesh, r_xyz: np.ndarray) -> np.ndarray:
     return out
 
 
-def build_sphere(N: int, jitter: float, seed: float):
+def build_sphere(N: int, jitter: float, seed: float, reference_closure: bool = False):
     """Returns (mesh, r_xyz, neighborDist) for N requested cells (numRegions = N + 1)."""
     xyz = fibonacci_sphere(N, jitter, seed)
-    mesh = sphere_mesh_from_points(xyz)
+    mesh = sphere_mesh_from_points(xyz, reference_closure)
     return mesh, xyz, compute_neighbor_dist(mesh, xyz)
 
 
