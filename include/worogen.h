@@ -1,7 +1,8 @@
 /*
  * worogen.h — C ABI of libworogen, the MI355X-native implementation of World Orogen's per-cell
  * terrain pipeline (reference: raguilar011095/planet_heightmap_generation, js/terrain-post.js,
- * js/simplex-noise.js, js/rng.js, js/sphere-mesh.js).
+ * js/simplex-noise.js, js/rng.js, js/sphere-mesh.js; further on the climate stages and, from js/planet-mesh.js,
+ * the map export and the map view's layers and centre meridian).
  *
  * This is the drop-in boundary: plain pointers and sizes, no torch / HIP types.  The N-API shim
  * (planet_heightmap_generation_amd/napi/worogen_napi.cc) and the Python ctypes loader
@@ -493,6 +494,29 @@ int wo_map_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, cons
 int wo_map_color(wo_planet* p, int32_t type, const float* r_elevation, uint8_t* rgbaOut, int64_t outBytes);
 int wo_map_download(wo_planet* p, int32_t* out, int64_t outBytes);
 int wo_map_free(wo_planet* p);
+/* buildMapMesh: the map view's centre meridian and its climate and debug layers          js/planet-mesh.js:200-382, :83-172, :506-529
+ *   (the bodies and the contract are in csrc/map_layer_ops.h).
+ *   wo_map_raster_centered is wo_map_raster around a centre meridian: every vertex longitude goes through the reference's wrapLon
+ *   (l = lon - centerLon, one turn back into [-pi, pi]) before anything else.  centerLon must be finite and within [-pi, pi]
+ *   (the reference wraps once): otherwise status 1 and nothing is allocated.  centerLon == 0 gives wo_map_raster's map bit for bit.
+ *   wo_map_color_layer colours the map as one of the layers of the reference's debugLayer switch, one colour per region:
+ *   continentalityColor, temperatureColor, precipitationColor, rainShadowColor, oceanCurrentColor, and debugValueToColor over the
+ *   range of the values (pressure, wind speed, WO_MAP_LAYER_DEBUG), which is reduced on the device.  values == NULL reads the
+ *   layer's field(s) from the planet's resident wind, ocean, precipitation or temperature block ("no wind result on this planet
+ *   (call wo_compute_wind first ...)" and so on without it); values != NULL are numRegions floats that take the field's place:
+ *   required for WO_MAP_LAYER_DEBUG, refused for the two ocean-current layers, which read the warmth and the speed (set those with
+ *   wo_ocean_upload).  r_elevation (NULL: the resident field) is read by the ocean-current layers only (ocean is elevation <= 0).
+ *   Quantiser, gamma table and alpha are wo_map_color's; pixels nothing covers take the 0x1a1a2e background of the coloured kinds
+ *   (our decision: the map view has no exporter of its own).  Plate colours and the stress colouring are not offered. */
+enum {
+    WO_MAP_LAYER_DEBUG = 0, WO_MAP_LAYER_CONTINENTALITY = 1, WO_MAP_LAYER_TEMP_SUMMER = 2, WO_MAP_LAYER_TEMP_WINTER = 3, WO_MAP_LAYER_PRECIP_SUMMER = 4,
+    WO_MAP_LAYER_PRECIP_WINTER = 5, WO_MAP_LAYER_RAINSHADOW_SUMMER = 6, WO_MAP_LAYER_RAINSHADOW_WINTER = 7, WO_MAP_LAYER_OCEANCURRENT_SUMMER = 8,
+    WO_MAP_LAYER_OCEANCURRENT_WINTER = 9, WO_MAP_LAYER_PRESSURE_SUMMER = 10, WO_MAP_LAYER_PRESSURE_WINTER = 11, WO_MAP_LAYER_WINDSPEED_SUMMER = 12,
+    WO_MAP_LAYER_WINDSPEED_WINTER = 13, WO_MAP_LAYER_COUNT = 14
+};
+int wo_map_raster_centered(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width,
+                           double centerLon, int32_t* regionMapOut, int64_t counts[2]);
+int wo_map_color_layer(wo_planet* p, int32_t layer, const float* values, const float* r_elevation, uint8_t* rgbaOut, int64_t outBytes);
 
 /* ------------------------------------------------ device-resident variants -------------------- */
 /* The "reapply" pattern (js/planet-worker.js:341-440): fields stay in HBM, only scalars arrive.

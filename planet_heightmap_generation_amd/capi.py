@@ -87,6 +87,8 @@ SIGNATURES = {
     "wo_koppen_download": (C.c_int, [_p, _p, _c_i64]),
     "wo_map_raster": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _p, _p]),
     "wo_map_color": (C.c_int, [_p, _c_i32, _p, _p, _c_i64]),
+    "wo_map_raster_centered": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _c_f64, _p, _p]),
+    "wo_map_color_layer": (C.c_int, [_p, _c_i32, _p, _p, _p, _c_i64]),
     "wo_map_download": (C.c_int, [_p, _p, _c_i64]),
     "wo_map_free": (C.c_int, [_p]),
     "wo_planet_upload": (C.c_int, [_p, _p, _p]),

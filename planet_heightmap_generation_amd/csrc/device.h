@@ -52,7 +52,8 @@ enum Family : int {
     FAM_GLAC_INDEX, FAM_ICE_RECV, FAM_ICE_ROUND, FAM_CARVE_SETUP, FAM_CARVE_ROUND, FAM_MORAINE, FAM_GLAC_BLEND,
     FAM_SOLVE_PATCH, FAM_ELEV_COLLISION, FAM_ELEV_MAIN, FAM_PLATE_GRID, FAM_PLATE_PROJECT, FAM_SMOOTH_FIELD,
     FAM_FLOOD_EVAL, FAM_FLOOD_APPLY, FAM_FLOOD_MISC, FAM_CLIMATE, FAM_BASIN, FAM_BASIN_SORT, FAM_SOLVE_BASIN, FAM_FLOW_TILES, FAM_MISC, FAM_EVENT_PAIR, FAM_EVENT_PAIR_NOOP, FAM_EVENT_PAIR_NOOP2,
-    FAM_MAP_LONLAT, FAM_MAP_FILL, FAM_MAP_SIDES, FAM_MAP_BIG_BOXES, FAM_MAP_RESOLVE, FAM_MAP_REGION_COLORS, FAM_MAP_PIXELS, FAM_COUNT
+    FAM_MAP_LONLAT, FAM_MAP_FILL, FAM_MAP_SIDES, FAM_MAP_BIG_BOXES, FAM_MAP_RESOLVE, FAM_MAP_REGION_COLORS, FAM_MAP_PIXELS,
+    FAM_MAP_RANGE, FAM_MAP_LAYER_COLORS, FAM_COUNT
 };
 extern const char* const kFamilyNames[FAM_COUNT];
 

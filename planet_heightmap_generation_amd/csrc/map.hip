@@ -17,6 +17,11 @@
 // The lowest covering side index wins, so the map does not depend on the order in which lanes, workgroups or launches arrive.
 // Launches of wo_map_color: k_map_region_colors [1] (one packed RGBA per region; `biome`: k_map_biome_raw [1] and
 // k_map_biome_smooth [1] instead), k_map_pixels [1] (region map -> RGBA8, four pixels per thread).
+// wo_map_raster_centered is the same raster around a centre meridian (the map view's, map_layer_ops.h): the two table kernels take
+// centerLon (k_map_region_lonlat_centered, k_map_center_lonlat_centered), every other launch is wo_map_raster's.
+// Launches of wo_map_color_layer: k_map_range [1] for the layers coloured over their range (the bounds as two uint32 words in
+// device memory: a wave64 shuffle reduction, then at most one atomicMax per workgroup and bound), k_map_layer_colors [1] (one packed RGBA per
+// region; it reads the bounds from device memory, no host round trip in between), k_map_pixels [1].
 // Memory (device_mem.h): the region map lives in a block with an arena of its own on the planet (int32 per pixel; a raster at
 // another width replaces it, wo_map_free and wo_planet_destroy drop it); triangles, half-edges, both longitude / latitude tables,
 // the side map, the list and the colour tables are temporaries of the call, in an arena on its stack.
@@ -28,8 +33,14 @@
 
 #include "../../include/worogen.h"
 #include "device.h"
+#include "map_layer_ops.h"
 #include "map_ops.h"
+#include "ocean_block.h"
+#include "precip_block.h"
 #include "stage_block.h"
+#include "wind_block.h"
+
+static_assert(wo::map::LAYER_COUNT == WO_MAP_LAYER_COUNT && wo::map::LAYER_WINDSPEED_WINTER == WO_MAP_LAYER_WINDSPEED_WINTER, "the layers of map_layer_ops.h are those of worogen.h");
 
 namespace M = wo::map;
 
@@ -38,6 +49,7 @@ struct wo_map_block {
     wo::DeviceArena mem;
     int32_t* region = nullptr;                                // W x H region ids, row 0 north; -1: nothing covers the pixel
     int32_t W = 0, H = 0;
+    double centerLon = 0.0;                                   // the centre meridian of the raster (wo_map_raster: 0)
     bool valid = false;
 };
 
@@ -54,6 +66,17 @@ __global__ __launch_bounds__(WO_BLOCK) void k_map_center_lonlat(const int32_t* _
                                                                 int32_t numTriangles) {
     const int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t < numTriangles) out[t] = M::lonlat_of_center(triangles, xyz, t);
+}
+
+// the same two tables around a centre meridian
+__global__ __launch_bounds__(WO_BLOCK) void k_map_region_lonlat_centered(const float* __restrict__ xyz, M::LonLat* __restrict__ out, int32_t N, double centerLon) {
+    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < N) out[r] = M::lonlat_of_centered(xyz[3 * (int64_t)r], xyz[3 * (int64_t)r + 1], xyz[3 * (int64_t)r + 2], centerLon);
+}
+__global__ __launch_bounds__(WO_BLOCK) void k_map_center_lonlat_centered(const int32_t* __restrict__ triangles, const float* __restrict__ xyz, M::LonLat* __restrict__ out,
+                                                                         int32_t numTriangles, double centerLon) {
+    const int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < numTriangles) out[t] = M::lonlat_of_center_centered(triangles, xyz, t, centerLon);
 }
 
 __global__ __launch_bounds__(WO_BLOCK) void k_map_fill(uint32_t* __restrict__ sideMap, int64_t pixels) {
@@ -142,6 +165,56 @@ __global__ __launch_bounds__(WO_BLOCK) void k_map_biome_smooth(const float* __re
     if (r < N) rgba[r] = M::pack_rgba(M::biome_smooth(raw, off, adj, r), lut);
 }
 
+// The range of a layer's values (map_layer_ops.h: RangeBits): range[0], range[1] were cleared; every bound is a maximum over uint32
+// words.  Sixteen bytes per load where v is aligned for it, four loads in flight per thread, the last N % 4 values one by one.  A
+// workgroup whose bound does not exceed what the word already holds (a relaxed read: the word only grows) skips its atomic, so the
+// atomics on the two words do not queue behind one another.
+__global__ __launch_bounds__(WO_BLOCK) void k_map_range(const float* __restrict__ v, int32_t N, uint32_t* __restrict__ range) {
+    __shared__ uint32_t blockLo, blockHi;
+    if (threadIdx.x == 0) { blockLo = 0u; blockHi = 0u; }
+    __syncthreads();
+    M::RangeBits r{0u, 0u};
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t groups = (reinterpret_cast<uintptr_t>(v) & 15u) ? 0 : (int64_t)N / 4;
+    const float4* __restrict__ v4 = reinterpret_cast<const float4*>(v);
+    int64_t g = tid;
+    for (; g + 3 * stride < groups; g += 4 * stride) {
+        const float4 q0 = v4[g], q1 = v4[g + stride], q2 = v4[g + 2 * stride], q3 = v4[g + 3 * stride];
+        M::range_take(r, q0.x); M::range_take(r, q0.y); M::range_take(r, q0.z); M::range_take(r, q0.w);
+        M::range_take(r, q1.x); M::range_take(r, q1.y); M::range_take(r, q1.z); M::range_take(r, q1.w);
+        M::range_take(r, q2.x); M::range_take(r, q2.y); M::range_take(r, q2.z); M::range_take(r, q2.w);
+        M::range_take(r, q3.x); M::range_take(r, q3.y); M::range_take(r, q3.z); M::range_take(r, q3.w);
+    }
+    for (; g < groups; g += stride) {
+        const float4 q = v4[g];
+        M::range_take(r, q.x); M::range_take(r, q.y); M::range_take(r, q.z); M::range_take(r, q.w);
+    }
+    for (int64_t i = 4 * groups + tid; i < N; i += stride) M::range_take(r, v[i]);
+    for (int d = 32; d > 0; d >>= 1) {
+        r.lo = max(r.lo, (uint32_t)__shfl_down(r.lo, d, 64));
+        r.hi = max(r.hi, (uint32_t)__shfl_down(r.hi, d, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (r.lo) atomicMax(&blockLo, r.lo);
+        if (r.hi) atomicMax(&blockHi, r.hi);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (blockLo > __hip_atomic_load(range, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(range, blockLo);
+        if (blockHi > __hip_atomic_load(range + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(range + 1, blockHi);
+    }
+}
+
+// b and e are read by the ocean-current layers only, range by the layers coloured over their range
+__global__ __launch_bounds__(WO_BLOCK) void k_map_layer_colors(int32_t layer, const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ e,
+                                                               const uint32_t* __restrict__ range, const uint8_t* __restrict__ lut, uint32_t* __restrict__ rgba, int32_t N) {
+    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    const bool current = M::layer_is_ocean_current(layer);
+    const M::RangeBits R = M::layer_needs_range(layer) ? M::RangeBits{range[0], range[1]} : M::RangeBits{0u, 0u};
+    rgba[r] = M::pack_rgba(M::layer_color(layer, a[r], current ? b[r] : 0.0f, current ? e[r] : 0.0f, R), lut);
+}
+
 // four pixels per thread: one 16-byte load of region ids, four gathers from the colour table, one 16-byte store
 __global__ __launch_bounds__(WO_BLOCK) void k_map_pixels(const int32_t* __restrict__ region, const uint32_t* __restrict__ regionRgba, uint32_t background,
                                                          uint32_t* __restrict__ out, int64_t pixels) {
@@ -184,15 +257,17 @@ static bool map_topology_ok(int32_t N, int32_t numSides, const int32_t* triangle
 
 using namespace wo;
 
-extern "C" {
-
-int wo_map_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, int32_t* regionMapOut, int64_t counts[2]) {
-    if (!check_planet(p, "wo_map_raster")) return 1;
-    if (!triangles || !halfedges) { set_error("wo_map_raster: null pointer"); return 1; }
-    if (!map_width_ok(width)) { set_error("wo_map_raster: width is " + std::to_string(width) + ", it must be even and from 2 to 32768"); return 1; }
-    if (numSides < 3 || numSides % 3 != 0 || numSides >= (1 << 30)) { set_error("wo_map_raster: numSides is " + std::to_string(numSides) + ", it must be a multiple of 3 from 3 to 2^30 - 3"); return 1; }
+// wo_map_raster (centered == false: its own two table kernels) and wo_map_raster_centered
+static int map_raster(wo_planet* p, const char* fn, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, bool centered, double centerLon,
+                      int32_t* regionMapOut, int64_t counts[2]) {
+    const std::string F = std::string(fn) + ": ";
+    if (!check_planet(p, fn)) return 1;
+    if (!triangles || !halfedges) { set_error(F + "null pointer"); return 1; }
+    if (!map_width_ok(width)) { set_error(F + "width is " + std::to_string(width) + ", it must be even and from 2 to 32768"); return 1; }
+    if (numSides < 3 || numSides % 3 != 0 || numSides >= (1 << 30)) { set_error(F + "numSides is " + std::to_string(numSides) + ", it must be a multiple of 3 from 3 to 2^30 - 3"); return 1; }
+    if (centered && !M::center_lon_ok(centerLon)) { set_error(F + "centerLon is " + std::to_string(centerLon) + ", it must be finite and from -pi to pi"); return 1; }
     std::string err;
-    if (!map_topology_ok(p->N, numSides, triangles, halfedges, err)) { set_error("wo_map_raster: " + err); return 1; }
+    if (!map_topology_ok(p->N, numSides, triangles, halfedges, err)) { set_error(F + err); return 1; }
     WO_TRY
         const int32_t W = width, H = width / 2, N = p->N, numTriangles = numSides / 3;
         const int64_t pixels = (int64_t)W * H;
@@ -206,6 +281,7 @@ int wo_map_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, cons
         }
         auto* B = p->map;
         B->valid = false;
+        B->centerLon = centered ? centerLon : 0.0;
         DeviceArena T;                                        // the temporaries of this call
         const int32_t* d_tri = up(T, triangles, (size_t)numSides, s);
         const int32_t* d_he = up(T, halfedges, (size_t)numSides, s);
@@ -217,8 +293,13 @@ int wo_map_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, cons
         unsigned long long* h_counts = T.pinned<unsigned long long>(2);
         uint32_t* bigCount = reinterpret_cast<uint32_t*>(d_counts + 1);
         WO_HIP(hipMemsetAsync(d_counts, 0, 16, s));
-        launch(p, FAM_MAP_LONLAT, k_map_region_lonlat, blocks_for(N), WO_BLOCK, (const float*)p->d_xyz, r_ll, N);
-        launch(p, FAM_MAP_LONLAT, k_map_center_lonlat, blocks_for(numTriangles), WO_BLOCK, d_tri, (const float*)p->d_xyz, t_ll, numTriangles);
+        if (centered) {
+            launch(p, FAM_MAP_LONLAT, k_map_region_lonlat_centered, blocks_for(N), WO_BLOCK, (const float*)p->d_xyz, r_ll, N, centerLon);
+            launch(p, FAM_MAP_LONLAT, k_map_center_lonlat_centered, blocks_for(numTriangles), WO_BLOCK, d_tri, (const float*)p->d_xyz, t_ll, numTriangles, centerLon);
+        } else {
+            launch(p, FAM_MAP_LONLAT, k_map_region_lonlat, blocks_for(N), WO_BLOCK, (const float*)p->d_xyz, r_ll, N);
+            launch(p, FAM_MAP_LONLAT, k_map_center_lonlat, blocks_for(numTriangles), WO_BLOCK, d_tri, (const float*)p->d_xyz, t_ll, numTriangles);
+        }
         launch(p, FAM_MAP_FILL, k_map_fill, blocks_for(pixels, 1 << 14), WO_BLOCK, sideMap, pixels);
         launch(p, FAM_MAP_SIDES, k_map_sides, blocks_for(numSides), WO_BLOCK, d_tri, d_he, (const M::LonLat*)t_ll, (const M::LonLat*)r_ll, numSides, W, H, sideMap, bigList, bigCount);
         launch(p, FAM_MAP_BIG_BOXES, k_map_big_boxes, MAP_BIG_GRID, WO_BLOCK, d_tri, d_he, (const M::LonLat*)t_ll, (const M::LonLat*)r_ll, W, H, sideMap, (const uint32_t*)bigList,
@@ -230,7 +311,39 @@ int wo_map_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, cons
         B->valid = true;
         if (counts) { counts[0] = (int64_t)h_counts[0]; counts[1] = pixels - (int64_t)h_counts[0]; }
         return 0;
-    WO_CATCH("wo_map_raster")
+    WO_CATCH(fn)
+}
+
+// where a named layer's values live: the block, and the reference's result key of the field (two for the ocean-current layers)
+struct LayerSource { const BlockDesc* block; const char *a, *b; const char* hint; };
+static LayerSource layer_source(int32_t layer) {
+    switch (layer) {
+        case M::LAYER_CONTINENTALITY: return {&wind_desc(), "r_continentality", nullptr, "wo_wind_upload r_continentality"};
+        case M::LAYER_TEMP_SUMMER: return {&temp_desc(), "r_temperature_summer", nullptr, "wo_temperature_upload r_temperature_summer"};
+        case M::LAYER_TEMP_WINTER: return {&temp_desc(), "r_temperature_winter", nullptr, "wo_temperature_upload r_temperature_winter"};
+        case M::LAYER_PRECIP_SUMMER: return {&precip_desc(), "r_precip_summer", nullptr, "wo_precip_upload r_precip_summer"};
+        case M::LAYER_PRECIP_WINTER: return {&precip_desc(), "r_precip_winter", nullptr, "wo_precip_upload r_precip_winter"};
+        case M::LAYER_RAINSHADOW_SUMMER: return {&precip_desc(), "r_rainshadow_summer", nullptr, "wo_precip_upload r_rainshadow_summer"};
+        case M::LAYER_RAINSHADOW_WINTER: return {&precip_desc(), "r_rainshadow_winter", nullptr, "wo_precip_upload r_rainshadow_winter"};
+        case M::LAYER_OCEANCURRENT_SUMMER: return {&ocean_desc(), "r_ocean_warmth_summer", "r_ocean_speed_summer", "wo_ocean_upload r_ocean_warmth_summer r_ocean_speed_summer"};
+        case M::LAYER_OCEANCURRENT_WINTER: return {&ocean_desc(), "r_ocean_warmth_winter", "r_ocean_speed_winter", "wo_ocean_upload r_ocean_warmth_winter r_ocean_speed_winter"};
+        case M::LAYER_PRESSURE_SUMMER: return {&wind_desc(), "r_pressure_summer", nullptr, "wo_wind_upload r_pressure_summer"};
+        case M::LAYER_PRESSURE_WINTER: return {&wind_desc(), "r_pressure_winter", nullptr, "wo_wind_upload r_pressure_winter"};
+        case M::LAYER_WINDSPEED_SUMMER: return {&wind_desc(), "r_wind_speed_summer", nullptr, "wo_wind_upload r_wind_speed_summer"};
+        case M::LAYER_WINDSPEED_WINTER: return {&wind_desc(), "r_wind_speed_winter", nullptr, "wo_wind_upload r_wind_speed_winter"};
+        default: return {nullptr, nullptr, nullptr, nullptr};
+    }
+}
+
+extern "C" {
+
+int wo_map_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, int32_t* regionMapOut, int64_t counts[2]) {
+    return map_raster(p, "wo_map_raster", numSides, triangles, halfedges, width, false, 0.0, regionMapOut, counts);
+}
+
+int wo_map_raster_centered(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, double centerLon, int32_t* regionMapOut,
+                           int64_t counts[2]) {
+    return map_raster(p, "wo_map_raster_centered", numSides, triangles, halfedges, width, true, centerLon, regionMapOut, counts);
 }
 
 int wo_map_color(wo_planet* p, int32_t type, const float* r_elevation, uint8_t* rgbaOut, int64_t outBytes) {
@@ -266,6 +379,51 @@ int wo_map_color(wo_planet* p, int32_t type, const float* r_elevation, uint8_t* 
         WO_HIP(hipStreamSynchronize(s));                      // before T frees the temporaries; lut is this frame's
         return 0;
     WO_CATCH("wo_map_color")
+}
+
+int wo_map_color_layer(wo_planet* p, int32_t layer, const float* values, const float* r_elevation, uint8_t* rgbaOut, int64_t outBytes) {
+    const char* fn = "wo_map_color_layer";
+    if (!check_planet(p, fn)) return 1;
+    if (!rgbaOut) { set_error("wo_map_color_layer: null pointer"); return 1; }
+    if (layer < 0 || layer >= M::LAYER_COUNT) { set_error("wo_map_color_layer: unknown map layer " + std::to_string(layer)); return 1; }
+    auto* B = p->map;
+    if (!B || !B->valid) { set_error("wo_map_color_layer: no region map on this planet (call wo_map_raster or wo_map_raster_centered first)"); return 1; }
+    const int64_t pixels = (int64_t)B->W * B->H;
+    if (outBytes != pixels * 4) { set_error("wo_map_color_layer: a " + std::to_string(B->W) + " x " + std::to_string(B->H) + " map takes " + std::to_string(pixels * 4) + " bytes, rgbaOut has " + std::to_string(outBytes)); return 1; }
+    const bool current = M::layer_is_ocean_current(layer);
+    if (layer == M::LAYER_DEBUG && !values) { set_error("wo_map_color_layer: WO_MAP_LAYER_DEBUG takes its values from the caller, values is NULL"); return 1; }
+    if (current && values) { set_error("wo_map_color_layer: an ocean-current layer reads two fields, values must be NULL (wo_ocean_upload sets the warmth and the speed)"); return 1; }
+    const LayerSource S = layer_source(layer);
+    int fa = -1, fb = -1;
+    if (!values) {                                            // the resident field(s)
+        fa = S.block->index(S.a);
+        fb = S.b ? S.block->index(S.b) : -1;
+        if (!block_require(p, fn, *S.block, bit(fa) | (fb >= 0 ? bit(fb) : 0u), S.hint)) return 1;
+    }
+    WO_TRY
+        const int32_t N = p->N, g = blocks_for(N);
+        hipStream_t s = p->ctx->stream;
+        uint8_t lut[256];
+        M::gamma_lut(lut);
+        DeviceArena T;                                        // the temporaries of this call
+        const uint8_t* d_lut = up(T, (const uint8_t*)lut, 256, s);
+        const float* a = values ? up(T, values, (size_t)N, s) : (const float*)S.block->slot(S.block->get(p), fa, (size_t)N).ptr;
+        const float* b = fb >= 0 ? (const float*)S.block->slot(S.block->get(p), fb, (size_t)N).ptr : nullptr;
+        const float* e = current ? stage_elevation(p, T, r_elevation) : nullptr;
+        uint32_t* range = T.dev<uint32_t>(2);
+        uint32_t* regionRgba = T.dev<uint32_t>((size_t)N);
+        uint32_t* out = T.dev<uint32_t>((size_t)pixels);
+        if (M::layer_needs_range(layer)) {
+            WO_HIP(hipMemsetAsync(range, 0, 8, s));
+            launch(p, FAM_MAP_RANGE, k_map_range, blocks_for(((int64_t)N + 15) / 16, 1024), WO_BLOCK, a, N, range);      // 16 values per thread and turn
+        }
+        launch(p, FAM_MAP_LAYER_COLORS, k_map_layer_colors, g, WO_BLOCK, layer, a, b, e, (const uint32_t*)range, d_lut, regionRgba, N);
+        launch(p, FAM_MAP_PIXELS, k_map_pixels, blocks_for((pixels + 3) / 4, 1 << 14), WO_BLOCK, (const int32_t*)B->region, (const uint32_t*)regionRgba, M::background_rgba(M::TYPE_COLOR, lut),
+               out, pixels);
+        WO_HIP(hipMemcpyAsync(rgbaOut, out, (size_t)pixels * 4, hipMemcpyDeviceToHost, s));
+        WO_HIP(hipStreamSynchronize(s));                      // before T frees the temporaries; lut is this frame's
+        return 0;
+    WO_CATCH("wo_map_color_layer")
 }
 
 int wo_map_download(wo_planet* p, int32_t* out, int64_t outBytes) {

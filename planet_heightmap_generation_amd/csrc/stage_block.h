@@ -86,6 +86,8 @@ inline int block_upload(wo_planet* p, const char* fn, const BlockDesc& D, const 
     WO_CATCH(fn)
 }
 
+// temp.hip: the temperature block's descriptor (those of the other three are declared beside their blocks)
+const BlockDesc& temp_desc();
 // wind.hip: the wind block's itczLatsSummer and itczLatsWinter, which lie one after the other, into `dst` (2 x ITCZ_SAMPLES floats
 // on the device); the wind block outlives the copy
 void stage_itcz(wo_planet* p, float* dst);

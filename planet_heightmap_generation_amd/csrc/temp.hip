@@ -121,6 +121,7 @@ static void temp_alloc(wo_planet* p) {
 static const char* const kTempFields[TF_COUNT] = {"r_temperature_summer", "r_temperature_winter"};
 static StageBlock* temp_of(const wo_planet* p) { return p->temp; }
 static const BlockDesc kTempBlock{"temperature", "wo_compute_temperature", kTempFields, TF_COUNT, temp_of, temp_alloc, out_slot<wo_temp_block>};
+const BlockDesc& temp_desc() { return kTempBlock; }
 
 static void koppen_alloc(wo_planet* p) {
     if (p->koppen) return;

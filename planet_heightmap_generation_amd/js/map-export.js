@@ -4,11 +4,27 @@
 // are the reference's bit for bit and the coverage rule is the one csrc/map_ops.h fixes (WebGL's own pixels differ between GPUs).
 // `biome` and `koppen` read the Koppen block that classifyKoppen (js/koppen.js) left on the planet; without one the call throws
 // `no Koppen result`: the reference's silent fallback to the colour map is not offered.  No JavaScript fallback for the device passes.
+// Beyond the export button, the reference's map view (buildMapMesh, :200-382) draws around a centre meridian and shows the layers of
+// its debugLayer switch: `centerLon` (radians, within [-pi, pi]) and `layers` offer both.  A climate layer reads the block its stage
+// left on the planet (`no wind result` and so on without one); any other array is coloured by debugValueToColor over its own range.
 import zlib from 'zlib';
 import addon, { planetFor } from './native.js';
 
 // the reference's type names in the order of WO_MAP_COLOR .. WO_MAP_KOPPEN (include/worogen.h)
 export const MAP_TYPES = ['color', 'heightmap', 'landheightmap', 'landmask', 'biome', 'koppen'];
+
+// the reference's debugLayer names in the order of WO_MAP_LAYER_DEBUG .. WO_MAP_LAYER_WINDSPEED_WINTER; `debug` is any other array
+export const MAP_LAYERS = ['debug', 'continentality', 'tempSummer', 'tempWinter', 'precipSummer', 'precipWinter', 'rainShadowSummer', 'rainShadowWinter',
+    'oceanCurrentSummer', 'oceanCurrentWinter', 'pressureSummer', 'pressureWinter', 'windSpeedSummer', 'windSpeedWinter'];
+
+export function mapLayerId(layer) {
+    const id = MAP_LAYERS.indexOf(layer);
+    if (id < 0) throw new RangeError(`exportMap: unknown map layer '${layer}' (one of ${MAP_LAYERS.join(', ')})`);
+    return id;
+}
+
+// ours: the reference exports no layer
+export function layerFilename(name, seed) { return `orogen-layer-${name}-${seed}.png`; }
 
 export function mapTypeId(type) {
     const id = MAP_TYPES.indexOf(type);
@@ -33,11 +49,30 @@ function checkMesh(mesh, width) {
     if (!(Number.isInteger(width) && width >= 2 && width <= 32768 && width % 2 === 0)) throw new RangeError('exportMap: width must be an even integer from 2 to 32768');
 }
 
-// one raster, one colour pass per type, on a planet handle (what the worker holds); r_elevation null: the planet's resident field
-export function exportMapsOnPlanet(planet, triangles, halfedges, r_elevation, types, width) {
-    const ids = types.map(mapTypeId);
-    const r = addon.mapRaster(planet, triangles, halfedges, width, false);
+// the raster of the planet, around a centre meridian when one is given (0, null or undefined: the export's own raster, the same map)
+export function rasterOnPlanet(planet, triangles, halfedges, width, centerLon) {
+    if (centerLon === undefined || centerLon === null || centerLon === 0) return addon.mapRaster(planet, triangles, halfedges, width, false);
+    if (typeof centerLon !== 'number') throw new TypeError('exportMap: centerLon must be a number (radians)');
+    return addon.mapRasterCentered(planet, triangles, halfedges, width, centerLon, false);
+}
+
+// layers: names of MAP_LAYERS other than `debug`, or { name, values } with a Float32Array that takes the field's place (under any
+// other name: coloured as `debug`)
+function checkedLayers(layers) {
+    return Array.from(layers || []).map((l) => {
+        const name = typeof l === 'string' ? l : l && l.name, values = typeof l === 'string' ? null : (l && l.values) || null;
+        const id = (values && MAP_LAYERS.indexOf(name) < 0) ? 0 : mapLayerId(name);
+        if (id === 0 && !values) throw new RangeError("exportMap: the map layer 'debug' takes its values from the caller");
+        return { name, id, values };
+    });
+}
+
+// one raster, one colour pass per type and per layer, on a planet handle (what the worker holds); r_elevation null: the planet's resident field
+export function exportMapsOnPlanet(planet, triangles, halfedges, r_elevation, types, width, opts) {
+    const ids = types.map(mapTypeId), layers = checkedLayers(opts && opts.layers);
+    const r = rasterOnPlanet(planet, triangles, halfedges, width, opts && opts.centerLon);
     const maps = ids.map((id, k) => ({ type: types[k], rgba: addon.mapColor(planet, id, r_elevation || null, width) }));
+    for (const l of layers) maps.push({ type: l.name, rgba: addon.mapColorLayer(planet, l.id, l.values, r_elevation || null, width) });
     return { width: r.width, height: r.height, covered: r.covered, uncovered: r.uncovered, maps };
 }
 
@@ -45,18 +80,21 @@ function checkElevation(mesh, r_elevation) {
     if (!(r_elevation instanceof Float32Array) || r_elevation.length !== mesh.numRegions) throw new RangeError(`exportMap: r_elevation must be a Float32Array of ${mesh.numRegions} entries`);
 }
 
-// exportMapBatch(mesh, r_xyz, r_elevation, types, width) -> { width, height, maps: [{ type, rgba }] }: one raster, one colour pass per type
-export function exportMapBatch(mesh, r_xyz, r_elevation, types, width) {
+// exportMapBatch(mesh, r_xyz, r_elevation, types, width, { layers, centerLon }) -> { width, height, maps: [{ type, rgba }] }: one raster, one
+// colour pass per type, then one per layer
+export function exportMapBatch(mesh, r_xyz, r_elevation, types, width, opts) {
     checkMesh(mesh, width);
     checkElevation(mesh, r_elevation);
-    const res = exportMapsOnPlanet(planetFor(mesh, r_xyz), mesh.triangles, mesh.halfedges, r_elevation, Array.from(types), width);
+    const res = exportMapsOnPlanet(planetFor(mesh, r_xyz), mesh.triangles, mesh.halfedges, r_elevation, Array.from(types), width, opts);
     return { width: res.width, height: res.height, maps: res.maps };
 }
 
-// exportMap(mesh, r_xyz, r_elevation, type, width) -> { width, height, rgba }
-export function exportMap(mesh, r_xyz, r_elevation, type, width) {
-    const res = exportMapBatch(mesh, r_xyz, r_elevation, [type], width);
-    return { width: res.width, height: res.height, rgba: res.maps[0].rgba };
+// exportMap(mesh, r_xyz, r_elevation, type, width, { layers, centerLon }) -> { width, height, rgba } (with layers: and maps, as exportMapBatch)
+export function exportMap(mesh, r_xyz, r_elevation, type, width, opts) {
+    const res = exportMapBatch(mesh, r_xyz, r_elevation, [type], width, opts);
+    const out = { width: res.width, height: res.height, rgba: res.maps[0].rgba };
+    if (opts && opts.layers && Array.from(opts.layers).length) out.maps = res.maps;
+    return out;
 }
 
 // ---- PNG: 8-bit RGBA, filter 0 on every row, one IDAT from zlib.deflateSync; CRC-32 from a table built at load (Node 12 has no

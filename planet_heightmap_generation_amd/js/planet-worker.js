@@ -61,13 +61,19 @@
 //                  poles and is refused.
 //                  -> { type: 'editDone', skipClimate: true, prePostElev, r_elevation, t_elevation, mountain_r, coastline_r, ocean_r,
 //                       r_stress, <the 19 climate fields: null>, debugLayers, _editTiming, _timing, _postTiming }
-//   cmd 'exportMap' { type | types, width, png? }   (js/planet-mesh.js:1752-2180)
+//   cmd 'exportMap' { type | types, width, png?, layers?, centerLon? }   (js/planet-mesh.js:1752-2180; layers and centerLon: the map view, :200-382)
 //                  the equirectangular map, width x width / 2, of the planet's current elevation and Koppen block in one or
 //                  several of the reference's six kinds (color, heightmap, landheightmap, landmask, biome, koppen): one raster on
 //                  the device, one colour pass per type, and with `png` the PNG file of each (js/map-export.js).  Needs a state
 //                  retained with mesh.triangles and mesh.halfedges (importHeightmap keeps both); biome and koppen need a
 //                  computeClimate before them (`no Koppen result` otherwise: the reference's silent fallback to the colour map is
 //                  not offered).  Progress: `Rendering...` at 0, then 80 k / n after each type, `Encoding PNG...` at 85 with png.
+//                  `layers`: names of the map view's debugLayer switch, each one more map after the types' (filename
+//                  orogen-layer-<name>-<seed>.png, ours).  A climate layer (continentality, temp*, precip*, rainShadow*, oceanCurrent*,
+//                  pressure*, windSpeed* with Summer / Winter) reads the block computeClimate left on the planet (`no wind result`
+//                  and so on before it); any other key of the retained debugLayers (erosionDelta, hotspot, the twelve assignElevation
+//                  layers, superPlates) is coloured by debugValueToColor over its own range, which is reduced on the device.
+//                  `centerLon` (radians, within [-pi, pi]) draws the map around that meridian.  Progress then counts types + layers.
 //                  -> { type: 'exportDone', width, height, maps: [{ type, filename, rgba, png? }],
 //                       _exportTiming: { raster, color, encode, workerTotal } }, the buffers transferred
 //   cmd 'dispose'  frees the retained state -> { type: 'disposed' }
@@ -85,7 +91,7 @@ import { OCEAN_KEYS, PRECIP_KEYS, TEMP_KEYS, downloadAll } from './climate-block
 import { denseTable, plateDensities, LAYERS } from './plate-table.js';
 import { generateCoarsePlates } from './coarse-plates.js';
 import { SimplexNoise } from './simplex-noise.js';
-import { MAP_TYPES, exportFilename, encodePng } from './map-export.js';
+import { MAP_TYPES, MAP_LAYERS, exportFilename, layerFilename, encodePng, rasterOnPlanet } from './map-export.js';
 
 let W = null;          // retained state (js/planet-worker.js:22)
 
@@ -146,6 +152,7 @@ function handleReapply(data) {
                               triangleElevations: tTriElev, workerTotal: performance.now() - tTotal0 },
             _postTiming: postTiming
         };
+        if (W.debugLayers) W.debugLayers = { ...W.debugLayers, erosionDelta: new Float32Array(dl_erosionDelta) };     // a copy: the buffer leaves with the message
         parentPort.postMessage(result, [r_elevation.buffer, t_elevation.buffer, dl_erosionDelta.buffer]);
     } catch (err) {
         parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
@@ -199,6 +206,7 @@ function handleImportHeightmap(data) {
         timing.push({ stage: 'Synthetic plates', ms: performance.now() - t0 });
         const regions = addon.classifyRegions(planet);
         W.r_plate = new Int32Array(r_plate); W.plateIsOcean = Int32Array.from(plateIsOcean);     // copies: r_plate's buffer leaves with the message
+        W.debugLayers = { erosionDelta: dl_erosionDelta };                                     // stays here: the message clones it
 
         progress(75, 'Computing triangle elevations\u2026');
         t0 = performance.now();
@@ -292,6 +300,7 @@ function handleEditRecompute(data) {
             if (stage === 'erosion') progress(50, 'Eroding terrain…');
             else if (stage === 'triangles') progress(75, 'Computing triangle elevations…');
         });
+        W.debugLayers = c.debugLayers;                    // what exportMap's generic layers read; the message clones them
 
         const climate = {};
         for (const k of CLIMATE_NULLS) climate[k] = null;
@@ -381,6 +390,7 @@ function handleGenerate(data) {
             else if (stage === 'erosion') progress(60, 'Eroding terrain…');
             else progress(75, 'Computing triangle elevations…');
         });
+        W.debugLayers = c.debugLayers;                    // what exportMap's generic layers read; the message clones them
         W.hasHotspot = true;                             // the call's hotspot layer stays on the device for the reapplies that follow
         if (c.sup) timing.push({ stage: `Super plates (${c.sup.numSuperPlates} groups from ${P} plates)`, ms: c.tSuper });
         timing.push({ stage: 'Elevation (collisions + stress + distance fields + assignment)', ms: c.tElev });
@@ -496,16 +506,28 @@ function handleExportMap(data) {
         const types = data.types !== undefined && data.types !== null ? Array.from(data.types) : [data.type];
         for (const t of types) if (MAP_TYPES.indexOf(t) < 0) throw new RangeError(`exportMap: unknown map type '${t}' (one of ${MAP_TYPES.join(', ')})`);
         if (types.length === 0) throw new RangeError('exportMap: no map type given');
+        // a layer is a climate layer of the map view, read from the planet's resident block, or a key of the retained debugLayers
+        const generic = W.debugLayers || {};
+        const layers = (data.layers !== undefined && data.layers !== null ? Array.from(data.layers) : []).map((name) => {
+            const id = MAP_LAYERS.indexOf(name);
+            if (id > 0) return { name, id, values: null };
+            if (name !== 'debug' && generic[name] instanceof Float32Array) return { name, id: 0, values: generic[name] };
+            throw new RangeError(`exportMap: unknown map layer '${name}' (one of ${MAP_LAYERS.slice(1).concat(Object.keys(generic)).join(', ')})`);
+        });
         const width = data.width;
         progress(0, 'Rendering...');
         let t0 = performance.now();
-        const r = addon.mapRaster(W.planet, W.triangles, W.halfedges, width, false);
+        const r = rasterOnPlanet(W.planet, W.triangles, W.halfedges, width, data.centerLon);
         const tRaster = performance.now() - t0;
         t0 = performance.now();
-        const maps = [];
+        const maps = [], total = types.length + layers.length;
         types.forEach((type, k) => {
             maps.push({ type, filename: exportFilename(type, W.seed), rgba: addon.mapColor(W.planet, MAP_TYPES.indexOf(type), null, width) });
-            progress(80 * (k + 1) / types.length, 'Rendering...');
+            progress(80 * (k + 1) / total, 'Rendering...');
+        });
+        layers.forEach((l, k) => {
+            maps.push({ type: l.name, filename: layerFilename(l.name, W.seed), rgba: addon.mapColorLayer(W.planet, l.id, l.values, null, width) });
+            progress(80 * (types.length + k + 1) / total, 'Rendering...');
         });
         const tColor = performance.now() - t0;
         let tEncode = 0;

@@ -5,6 +5,10 @@ side index per pixel) and leaves it on the device; ``color`` turns it into RGBA8
 reference's colour function per region, its quantiser and its gamma table; ``export_map`` does both.  The triangle list and the
 region colours are the reference's bit for bit; the coverage rule is the one csrc/map_ops.h fixes (WebGL's own pixels differ
 between GPUs).  ``biome`` and ``koppen`` need the planet's Koppen block (``koppen.classify_koppen``).  There is no CPU fallback.
+
+The reference's map view (buildMapMesh, js/planet-mesh.js:200-382) shows more than its export button: ``raster(center_lon=...)`` draws
+the map around a centre meridian (its wrapLon), ``color_layer`` colours it as one of the layers of its debugLayer switch, from the
+planet's resident climate blocks or from values of the caller's, and ``export_map(layers=..., center_lon=...)`` adds those maps.
 """
 from __future__ import annotations
 
@@ -16,6 +20,10 @@ from . import terrain_post as TP
 
 # the reference's type names in the order of WO_MAP_COLOR .. WO_MAP_KOPPEN (include/worogen.h)
 TYPES = ("color", "heightmap", "landheightmap", "landmask", "biome", "koppen")
+# the reference's debugLayer names in the order of WO_MAP_LAYER_DEBUG .. WO_MAP_LAYER_WINDSPEED_WINTER; `debug` is any other array of
+# its debugLayers, coloured by debugValueToColor over its own range
+LAYERS = ("debug", "continentality", "tempSummer", "tempWinter", "precipSummer", "precipWinter", "rainShadowSummer", "rainShadowWinter", "oceanCurrentSummer",
+          "oceanCurrentWinter", "pressureSummer", "pressureWinter", "windSpeedSummer", "windSpeedWinter")
 
 
 def type_id(type) -> int:
@@ -26,15 +34,29 @@ def type_id(type) -> int:
     return int(type)
 
 
+def layer_id(layer) -> int:
+    if isinstance(layer, str):
+        if layer not in LAYERS:
+            raise ValueError(f"unknown map layer '{layer}' (one of {', '.join(LAYERS)})")
+        return LAYERS.index(layer)
+    return int(layer)
+
+
+def layer_filename(name: str, seed) -> str:
+    """The file name of a layer's map.  Ours: the reference exports no layer."""
+    return f"orogen-layer-{name}-{seed}.png"
+
+
 def export_filename(type: str, seed) -> str:
     """exportFilename(type, seed) (js/planet-mesh.js:1952-1961)."""
     stem = dict(landmask="landmask", landheightmap="land-heightmap", heightmap="heightmap", biome="satellite", koppen="climate").get(type, "colormap")
     return f"orogen-{stem}-{seed}.png"
 
 
-def raster(planet: TP.Planet, mesh, width: int, download: bool = False) -> dict:
+def raster(planet: TP.Planet, mesh, width: int, download: bool = False, center_lon: float | None = 0.0) -> dict:
     """The region map of the planet at width x width / 2: {width, height, covered, uncovered, regionMap}; regionMap is the int32
-    (height, width) array (-1: nothing covers the pixel) when download is set, else None.  The map stays on the device."""
+    (height, width) array (-1: nothing covers the pixel) when download is set, else None.  The map stays on the device.
+    center_lon: the centre meridian in radians, within [-pi, pi] (0 or None: the export's own raster, the same map)."""
     width = int(width)
     tri = np.ascontiguousarray(mesh.triangles, dtype=np.int32)
     he = np.ascontiguousarray(mesh.halfedges, dtype=np.int32)
@@ -43,7 +65,11 @@ def raster(planet: TP.Planet, mesh, width: int, download: bool = False) -> dict:
     ok = 2 <= width <= 32768 and width % 2 == 0
     out = np.empty((width // 2, width), np.int32) if (download and ok) else None
     counts = np.zeros(2, np.int64)
-    capi.check(capi.lib().wo_map_raster(planet.handle, tri.size, capi.ptr(tri), capi.ptr(he), width, capi.ptr(out), capi.ptr(counts)), "mapRaster")
+    if center_lon is None or (isinstance(center_lon, (int, float)) and center_lon == 0):
+        capi.check(capi.lib().wo_map_raster(planet.handle, tri.size, capi.ptr(tri), capi.ptr(he), width, capi.ptr(out), capi.ptr(counts)), "mapRaster")
+    else:
+        capi.check(capi.lib().wo_map_raster_centered(planet.handle, tri.size, capi.ptr(tri), capi.ptr(he), width, float(center_lon), capi.ptr(out), capi.ptr(counts)),
+                   "mapRasterCentered")
     planet._map_width = width                              # what color sizes its result by
     return dict(width=width, height=width // 2, covered=int(counts[0]), uncovered=int(counts[1]), regionMap=out)
 
@@ -68,18 +94,52 @@ def color(planet: TP.Planet, type, r_elevation=None, width: int | None = None) -
     return out
 
 
+def color_layer(planet: TP.Planet, layer, values=None, r_elevation=None, width: int | None = None) -> np.ndarray:
+    """The planet's region map coloured as `layer` (a name of LAYERS): uint8 (height, width, 4).  values None reads the layer's field
+    from the planet's resident climate block; otherwise numRegions floats take its place (required for `debug`, refused for the two
+    ocean-current layers, which read two fields: ocean.upload sets those).  r_elevation (None: the resident field) is read by the
+    ocean-current layers only.  width: as for color."""
+    lid = layer_id(layer)
+    v = None
+    if values is not None:
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        if v.shape != (planet.numRegions,):
+            raise ValueError(f"values must hold numRegions = {planet.numRegions} floats, got shape {v.shape}")
+    e = CB.elevation_arg(planet.numRegions, r_elevation)
+    if width is None:
+        width = getattr(planet, "_map_width", None)
+    if width is None:
+        width = 2                                          # no raster made here: the library says what is missing
+    out = np.empty((int(width) // 2, int(width), 4), np.uint8)
+    capi.check(capi.lib().wo_map_color_layer(planet.handle, lid, capi.ptr(v), capi.ptr(e), capi.ptr(out), out.nbytes), "mapColorLayer")
+    return out
+
+
 def free(planet: TP.Planet) -> None:
     capi.check(capi.lib().wo_map_free(planet.handle), "mapFree")
     planet._map_width = None
 
 
-def export_map(planet: TP.Planet, mesh, types, width: int, r_elevation=None) -> dict:
+def export_map(planet: TP.Planet, mesh, types, width: int, r_elevation=None, layers=(), center_lon: float = 0.0) -> dict:
     """exportMapBatch: one raster, one colour pass per type.  types: one name or a sequence of names.
-    -> {width, height, covered, uncovered, maps: {type: uint8 (height, width, 4)}}"""
+    layers: names of LAYERS other than `debug` (read from the planet's resident blocks), or a mapping name -> values (None: the
+    resident block; an array: these values, under any name that is no climate layer's coloured as `debug`); their maps follow the
+    types' in `maps`.  center_lon: the centre meridian of the raster.
+    -> {width, height, covered, uncovered, maps: {name: uint8 (height, width, 4)}}"""
     names = [types] if isinstance(types, str) else list(types)
     for t in names:
         type_id(t)
-    res = raster(planet, mesh, width)
+    wanted = dict(layers) if hasattr(layers, "keys") else {name: None for name in ([layers] if isinstance(layers, str) else layers)}
+    for name, values in wanted.items():
+        if values is None or name in LAYERS:
+            layer_id(name)
+            if name == "debug" and values is None:
+                raise ValueError("the map layer 'debug' takes its values from the caller")
+        if name in names:
+            raise ValueError(f"'{name}' is asked for as a type and as a layer")
+    res = raster(planet, mesh, width, center_lon=center_lon)
     res["maps"] = {t: color(planet, t, r_elevation, res["width"]) for t in names}
+    for name, values in wanted.items():
+        res["maps"][name] = color_layer(planet, name if name in LAYERS else "debug", values, r_elevation, res["width"])
     del res["regionMap"]
     return res

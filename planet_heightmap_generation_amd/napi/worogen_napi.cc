@@ -780,7 +780,7 @@ napi_value TriangleCenters(napi_env env, napi_callback_info info) {            /
     return out;
 }
 
-// ---- map export (include/worogen.h: wo_map_raster / wo_map_color / wo_map_free) ----
+// ---- map export (include/worogen.h: wo_map_raster / wo_map_color / wo_map_free / wo_map_raster_centered / wo_map_color_layer) ----
 // mapRaster(planet, triangles, halfedges, width, download) -> { width, height, covered, uncovered, regionMap: Int32Array | null }
 napi_value MapRaster(napi_env env, napi_callback_info info) {
     Args a(env, info);
@@ -804,6 +804,30 @@ napi_value MapRaster(napi_env env, napi_callback_info info) {
     set_prop(env, o, "regionMap", map);
     return o;
 }
+// mapRasterCentered(planet, triangles, halfedges, width, centerLon, download) -> as mapRaster, around a centre meridian (radians)
+napi_value MapRasterCentered(napi_env env, napi_callback_info info) {
+    Args a(env, info);
+    size_t nt, nh;
+    int32_t* tri = (int32_t*)a.ta(1, napi_int32_array, &nt); if (!a.ok) return nullptr;
+    int32_t* he = (int32_t*)a.ta(2, napi_int32_array, &nh); if (!a.ok) return nullptr;
+    if (nt != nh || nt == 0 || nt >= ((size_t)1 << 30)) { napi_throw_range_error(env, nullptr, "mapRasterCentered: triangles and halfedges must have the same length, numSides"); return nullptr; }
+    const double w = a.num(3);
+    if (!(w >= 2 && w <= 32768 && w == (double)(int64_t)w && ((int64_t)w & 1) == 0)) { napi_throw_range_error(env, nullptr, "mapRasterCentered: width must be an even integer from 2 to 32768"); return nullptr; }
+    wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    const int32_t W = (int32_t)w, H = W / 2;
+    const double centerLon = a.num(4);                                         // the library refuses what is not finite and within [-pi, pi]
+    bool download = false; if (a.argc > 5) napi_get_value_bool(env, a.argv[5], &download);
+    void* d = nullptr; napi_value map = nullptr;
+    if (download) { map = make_ta(env, napi_int32_array, (size_t)W * (size_t)H, 4, &d); if (!map) return nullptr; }
+    else napi_get_null(env, &map);
+    int64_t counts[2] = {0, 0};
+    if (wo_map_raster_centered(p, (int32_t)nt, tri, he, W, centerLon, (int32_t*)d, counts)) return throw_wo(env, "mapRasterCentered");
+    napi_value o; napi_create_object(env, &o);
+    set_nums(env, o, {{"width", (double)W}, {"height", (double)H}, {"covered", (double)counts[0]}, {"uncovered", (double)counts[1]}});
+    set_prop(env, o, "regionMap", map);
+    return o;
+}
 // mapColor(planet, type 0..5, r_elevation | null, width) -> Uint8ClampedArray(width * width / 2 * 4): the planet's region map coloured
 napi_value MapColor(napi_env env, napi_callback_info info) {
     Args a(env, info); wo_planet* p = planet_at(a, 0);
@@ -816,6 +840,22 @@ napi_value MapColor(napi_env env, napi_callback_info info) {
     void* d; napi_value out = make_ta(env, napi_uint8_clamped_array, bytes, 1, &d);
     if (!out) return nullptr;
     if (wo_map_color(p, (int32_t)t, e, (uint8_t*)d, (int64_t)bytes)) return throw_wo(env, "mapColor");
+    return out;
+}
+// mapColorLayer(planet, layer 0..13, values | null, r_elevation | null, width) -> Uint8ClampedArray(width * width / 2 * 4): the planet's
+// region map coloured as a layer of the map view (WO_MAP_LAYER_*); values null: the layer's field of the planet's resident block
+napi_value MapColorLayer(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* v = (float*)opt_regions(a, 2, napi_float32_array, p, "values", false); if (!a.ok) return nullptr;
+    float* e = (float*)opt_regions(a, 3, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    const double l = a.num(1), w = a.num(4);
+    if (!(l >= 0 && l < WO_MAP_LAYER_COUNT && l == (double)(int64_t)l)) { napi_throw_range_error(env, nullptr, "mapColorLayer: layer must be an integer from 0 to 13"); return nullptr; }
+    if (!(w >= 2 && w <= 32768 && w == (double)(int64_t)w && ((int64_t)w & 1) == 0)) { napi_throw_range_error(env, nullptr, "mapColorLayer: width must be an even integer from 2 to 32768"); return nullptr; }
+    const size_t bytes = (size_t)w * (size_t)(w / 2) * 4;
+    void* d; napi_value out = make_ta(env, napi_uint8_clamped_array, bytes, 1, &d);
+    if (!out) return nullptr;
+    if (wo_map_color_layer(p, (int32_t)l, v, e, (uint8_t*)d, (int64_t)bytes)) return throw_wo(env, "mapColorLayer");
     return out;
 }
 napi_value MapFree(napi_env env, napi_callback_info info) {                    // (planet)
@@ -910,7 +950,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"oceanUpload", OceanUpload}, {"computePrecipitation", ComputePrecipitation}, {"precipDownload", PrecipDownload},
         {"precipUpload", PrecipUpload}, {"computeTemperature", ComputeTemperature}, {"temperatureDownload", TemperatureDownload},
         {"temperatureUpload", TemperatureUpload}, {"classifyKoppen", ClassifyKoppen},
-        {"mapRaster", MapRaster}, {"mapColor", MapColor}, {"mapFree", MapFree},
+        {"mapRaster", MapRaster}, {"mapColor", MapColor}, {"mapFree", MapFree}, {"mapRasterCentered", MapRasterCentered}, {"mapColorLayer", MapColorLayer},
         {"commUniqueId", CommUniqueId}, {"commCreate", CommCreate}, {"planetSetHalo", PlanetSetHalo},
         {"planetExchangeAllgather", PlanetExchangeAllgather}, {"planetExchangeNeighbors", PlanetExchangeNeighbors}, {"planetSetFloodExchange", PlanetSetFloodExchange},
     };
