@@ -25,7 +25,7 @@
 //      for ~40 barrier-separated levels doing almost nothing; dropped, DESIGN.md section 5 and profiles/r03c..r03g.)
 // The schedule is only a schedule: tasks are single-assignment, so any dependency-respecting order gives the same bits,
 // and a task whose predecessor is NOT where the layout promised (a cycle longer than two cells that the jumping gave
-// up on) simply stays pending and is finished by k_solve_patch launches over the same store order (planet.hip).
+// up on) simply stays pending and is finished by k_solve_patch launches over the same store order (erode.hip: run_solve_patches).
 #include <hip/hip_runtime.h>
 
 #include <string>

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "device_mem.h"
@@ -23,6 +24,9 @@ namespace wo {
 #define WO_CATCH(fn)                                                                                   \
     } catch (const ::wo::HipError& e) { ::wo::set_error(std::string(fn) + ": " + e.msg); return 2; }   \
       catch (const std::exception& e) { ::wo::set_error(std::string(fn) + ": " + e.what()); return 3; }
+
+// A helper that several translation units of the library share but that is no part of its surface: kept out of the dynamic symbol table
+#define WO_LOCAL __attribute__((visibility("hidden")))
 
 constexpr int WO_BLOCK = 256;
 inline int blocks_for(int64_t n, int maxBlocks = 1 << 20) {
@@ -116,7 +120,7 @@ struct wo_planet {
     int32_t* h_count = nullptr;         // pinned scalar(s) for round-count read-back
     // erode_composite_checked: the field at entry, tasks any basin launch of the call left pending, calls that had to run again
     float* d_redoE = nullptr; int32_t* d_pendingEver = nullptr; int64_t redoCalls = 0;
-    // host-mapped {serial, value} word the host polls (planet.hip: read_count)
+    // host-mapped {serial, value} word the host polls (read_count)
     unsigned long long *h_word = nullptr, *d_word = nullptr; uint32_t wordSerial = 0;
     wo::FloodScratch flood;
     wo::FloodExchange floodX;           // landmass decomposition: the shares pool their heights when a flood call needs the whole planet's heap (wo_planet_set_flood_exchange)
@@ -171,7 +175,7 @@ struct wo_planet {
     uint32_t* d_basinKey = nullptr; int32_t* d_basinVals[2] = {nullptr, nullptr}; int32_t *d_basinJ = nullptr, *d_basinSlot = nullptr, *d_basinRange = nullptr;
     uint8_t* d_basinLong = nullptr; int64_t basinLaunches = 0;
     wo::Affine* d_affine[2] = {nullptr, nullptr};      // relaxed mode: the affine recurrence, ping-pong
-    int64_t solvePassSerial = 0;                       // unchecked basin passes so far (their output tag: planet.hip, passTag)
+    int64_t solvePassSerial = 0;                       // unchecked basin passes so far (their output tag: erode.hip, passTag)
     int32_t* h_patchTotals = nullptr;      // pinned: the pending totals of a burst of k_solve_patch launches (run_solve_patches)
     int32_t *d_listA = nullptr, *d_listB = nullptr, *d_counters = nullptr;   // round lists + 4 counters
     void* d_sortTemp = nullptr; size_t sortTempBytes = 0;
@@ -207,7 +211,7 @@ struct wo_planet {
     // deleted by wo_map_free and wo_planet_destroy (map_free)
     struct wo_map_block* map = nullptr;
 
-    // Patch-major mirror of the mesh for erodeComposite (planet.hip, MirrorScope): the same graph with the cells renamed in
+    // Patch-major mirror of the mesh for erodeComposite (mirror.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
     // d_e2, d_ocean, d_coast) point at the mirror and the o_* members hold the planet's own buffers.
     struct Mirror {
@@ -243,7 +247,7 @@ struct wo_planet {
 
 namespace wo {
 
-// profiling-aware launch: when p->profiling every launch is bracketed by events on the planet's stream
+// profile.hip: profiling-aware launch: when p->profiling every launch is bracketed by events on the planet's stream
 hipEvent_t profile_event(wo_planet* p);
 void profile_resolve(wo_planet* p);
 
@@ -303,14 +307,26 @@ void map_free(wo_planet* p);
 const uint8_t* koppen_classes(const wo_planet* p);
 // planet.hip: the entry points' handle check (refreshes p->opt from the environment, selects the device)
 bool check_planet(wo_planet* p, const char* fn);
-// planet.hip: drops the stage brackets an earlier erodeComposite left pending (a call that sets p->stageTiming itself calls it first)
+// planet.hip: one device integer for the host (through a host-mapped word the host polls); the host's copy of the ocean mask, brought up to date
+WO_LOCAL int32_t read_count(wo_planet* p, const int32_t* d_ptr);
+WO_LOCAL void refresh_host_ocean(wo_planet* p);
+static inline void swap_elev(wo_planet* p) { std::swap(p->d_e, p->d_e2); }
+// The device ocean mask changed (or may have): the host copy is refreshed lazily.  The flood's cached
+// open-ocean / seed data is only rebuilt when the mask really differs (a "reapply" with the same mask keeps it).
+static inline void ocean_changed(wo_planet* p) { p->h_ocean_valid = false; }
+// profile.hip: drops the stage brackets an earlier erodeComposite left pending (a call that sets p->stageTiming itself calls it first)
 void release_stage_brackets(wo_planet* p);
-// planet.hip: smoothField on a resident field (returns the buffer that holds the result)
+// terrain.hip: the coast flags of the current field and mask; a noise instance's tables into p->d_tables; a pass on host arrays
+// (upload, body, download: the JS call surface, host arrays mutated in place)
+WO_LOCAL void coast_flags(wo_planet* p);
+WO_LOCAL void upload_tables(wo_planet* p, double seed);
+WO_LOCAL int with_host_field(wo_planet* p, const char* fn, float* e, const uint8_t* oc, bool needOcean, void (*body)(wo_planet*, void*), void* arg);
+// climate_sweeps.hip: smoothField on a resident field (returns the buffer that holds the result)
 float* smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passes);
-// planet.hip: diffuseOceanWarmth of one season on resident fields with the single-field kernels (seeds a, ping-pongs a and b and
+// climate_sweeps.hip: diffuseOceanWarmth of one season on resident fields with the single-field kernels (seeds a, ping-pongs a and b and
 // returns the buffer that holds the result)
 float* diffuse_warmth_resident(wo_planet* p, const float* warmth, const uint8_t* isLand, const float* plateCont, int32_t passes, float* a, float* b);
-// planet.hip: computeWindConvergence and advectMoisture on resident fields (the advection seeds a, ping-pongs a and b and returns
+// climate_sweeps.hip: computeWindConvergence and advectMoisture on resident fields (the advection seeds a, ping-pongs a and b and returns
 // the buffer that holds the result)
 void wind_convergence_resident(wo_planet* p, const float* wx, const float* wy, const float* wz, float* out);
 float* advect_moisture_resident(wo_planet* p, const float* heightKm, const uint8_t* isLand, const float* windE, const float* windN, const float* wx, const float* wy,

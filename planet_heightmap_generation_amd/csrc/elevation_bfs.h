@@ -53,6 +53,9 @@ WO_HD inline int32_t bfs_attr_pos(unsigned long long k) { return 0x7fffffff - (i
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+
+#include "common_kernels.h"
+
 namespace wo {
 
 struct BfsLists { int32_t* cur; int32_t* next; int32_t* curCount; int32_t* nextCount; };

@@ -1,7 +1,8 @@
-// gfx950 kernels of assignElevation (bodies in elevation_ops.h).  Included by planet.hip only.
+// gfx950 kernels of assignElevation (bodies in elevation_ops.h).  Included by elevation.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "common_kernels.h"
 #include "device.h"
 #include "elevation_ops.h"
 

@@ -3,10 +3,11 @@
 // label from the previous round's labels into P[]) and k_fl_apply (the changed cells commit, their neighbours go on the
 // next round's list; its last workgroup advances the control block: list flip, epoch change, termination).  The host
 // queues rounds in batches and reads the control block back once per batch; lists are appended with one atomic per
-// wavefront (ballot + popcount).  Included by planet.hip only (after kernels_impl.h).
+// wavefront (wave_append).  Included by flood.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "common_kernels.h"
 #include "device.h"
 #include "flood_ops.h"
 
@@ -28,17 +29,6 @@ struct FlCtrl {
 };
 
 struct FlLists { int32_t* dirty[2]; int32_t* pend[2]; int32_t* changed; };
-
-__device__ inline void wave_append(bool flag, int32_t value, int32_t* list, int32_t* counter) {
-    const unsigned long long mask = __ballot(flag);
-    if (mask == 0) return;
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)mask) - 1;
-    int32_t base = 0;
-    if (lane == leader) base = atomicAdd(counter, (int32_t)__popcll(mask));
-    base = __shfl(base, leader);
-    if (flag) list[base + __popcll(mask & ((1ull << lane) - 1ull))] = value;
-}
 
 __global__ __launch_bounds__(WO_BLOCK) void k_fl_init(FloodDev D, float* eL, const float* e, FlCtrl* C) {
     if (blockIdx.x == 0 && threadIdx.x == 0) { FlCtrl z{}; z.epoch = 1; *C = z; }

@@ -1,6 +1,6 @@
 // Device formulation of pass 1 of priorityFloodCarve (reference: js/terrain-post.js:107-147): the noise-keyed
 // best-first flood as a label-correcting fixed point.  Bodies only (one call = one GPU thread); the kernels are in
-// flood_kernels.h, the round driver in planet.hip, and the test-only emulator (tests/emu) drives the same bodies on
+// flood_kernels.h, the round driver in flood.hip, and the test-only emulator (tests/emu) drives the same bodies on
 // the CPU.
 //
 // What the reference computes.  A binary heap pops the visited cell with the smallest key K = f32(surface + noise);

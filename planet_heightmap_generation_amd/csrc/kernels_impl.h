@@ -1,32 +1,17 @@
-// gfx950 kernels of the terrain-post path.  Each kernel is a grid-stride wrapper around one body of
+// gfx950 kernels of erodeComposite: land list, hydraulic, flow tiles, solve, thermal, glacial, carve, and the relaxed mode's
+// k_affine_* and k_carve_jacobi.  Each kernel is a grid-stride wrapper around one body of
 // erode_ops.h (which documents the reference lines it restates); all launches go through wo::launch so the
 // HIP-event profiler sees them.  Wave64, 256-thread workgroups, no MFMA (no dense contraction anywhere on
 // this path): the passes are CSR gathers bounded by HBM/L2 bandwidth or, for the dependency rounds, by
 // launch latency.
-// (Included by planet.hip only: kernels and their host-side launches live in one translation unit.)
+// (Included by erode.hip only: kernels and their host-side launches live in one translation unit.)
 #pragma once
 #include <hip/hip_runtime.h>
-#include <hip/hip_cooperative_groups.h>
 
+#include "common_kernels.h"
 #include "device.h"
-#include "plates_ops.h"
-#include "climate_ops.h"
 
 namespace wo {
-
-#define WO_GRID_STRIDE(i, n) for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += gridDim.x * blockDim.x)
-
-// XCD-aware cell loop for index-order passes.  Workgroup b is observed to run on XCD b % 8 (MI355X_MICROARCH.md);
-// with the natural mapping the eight L2s each fetch the same +-4.9*sqrt(N) neighbour windows (measured: ~8x the
-// algorithmic bytes in FETCH_SIZE).  Here the blocks are cut into tiles of F.xcdTile consecutive blocks and whole
-// tiles are dealt round-robin to the XCDs: an L2 then sees contiguous index ranges (tile + halo), while land and
-// ocean bands still spread evenly over the eight dies (one contiguous eighth per XCD was measured slower: the land
-// fraction varies with latitude).  Launch with xcd_grid(N, tile) blocks; placement only affects speed, never results.
-#define WO_XCD_CELLS(r, n)                                                                                           \
-    for (int32_t xi_ = (int32_t)(blockIdx.x >> 3), xt_ = F.xcdTile,                                                  \
-                 r = (int32_t)((((xi_ / xt_) * 8 + (int32_t)(blockIdx.x & 7u)) * xt_ + (xi_ % xt_)) * (int32_t)blockDim.x + (int32_t)threadIdx.x), \
-                 once_ = 1;                                                                                          \
-         once_ && r < (n); once_ = 0)
 
 // The same over the ascending land list: i = position in F.landIdx, r = the cell.  The erosion passes touch land cells
 // only (28 % of a synthetic planet); the per-ocean-cell constants they used to rewrite every iteration are set once per
@@ -38,137 +23,6 @@ namespace wo {
          once_ && i < F.L; once_ = 0)                                                                                \
         for (int32_t r = F.landIdx ? F.landIdx[i] : i, once2_ = 1; once2_; once2_ = 0)          /* landIdx == nullptr: the land cells ARE the ids 0 .. L-1 (land-first mirror): one dependent load less per thread */
 
-// Block-uniform strided loop: every thread of the workgroup runs the same number of trips (needed around
-// block_append's barriers); `valid` tells whether index i is in range.
-#define WO_BLOCK_STRIDE(i, valid, n)                                                              \
-    for (int32_t base_ = blockIdx.x * blockDim.x, i = base_ + threadIdx.x, valid = (i < (n));   \
-         base_ < (n); base_ += gridDim.x * blockDim.x, i = base_ + threadIdx.x, valid = (i < (n)))
-
-// Append `value` of every thread with `flag` to out[] with ONE global atomic per workgroup (wave ballot +
-// LDS scan of the per-wave counts) instead of one per wave on a single hot counter.
-__device__ inline void block_append(bool flag, int32_t value, int32_t* out, int32_t* outCount) {
-    __shared__ int32_t s_wave[WO_BLOCK / 64];
-    __shared__ int32_t s_base;
-    const unsigned long long mask = __ballot(flag);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int prefix = __popcll(mask & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave[wave] = __popcll(mask);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t tot = 0;
-        for (int w = 0; w < WO_BLOCK / 64; ++w) { const int32_t c = s_wave[w]; s_wave[w] = tot; tot += c; }
-        s_base = tot ? atomicAdd(outCount, tot) : 0;
-    }
-    __syncthreads();
-    if (flag) out[s_base + s_wave[wave] + prefix] = value;
-    __syncthreads();
-}
-
-// ---------------------------------------------------------------- fields / Jacobi ---------------
-__global__ __launch_bounds__(WO_BLOCK) void k_coast(Fields F, uint8_t* coast) {
-    WO_XCD_CELLS(r, F.N) coast[r] = coast_flag(F, r);
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_ocean_from_elev(const float* e, uint8_t* ocean, int32_t N) {
-    WO_GRID_STRIDE(r, N) ocean[r] = (e[r] <= 0.0f) ? 1 : 0;
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_smooth(Fields F, const float* in, float* out, double strength) {
-    WO_XCD_CELLS(r, F.N) out[r] = smooth_cell(F, in, r, strength);
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_sharpen(Fields F, const float* in, const float* orig, float* out, double strength) {
-    WO_XCD_CELLS(r, F.N) out[r] = sharpen_cell(F, in, orig, r, strength);
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_creep(Fields F, const float* in, float* out, double strength) {
-    WO_XCD_CELLS(r, F.N) out[r] = creep_cell(F, in, r, strength);
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_glacial_blend(Fields F, const float* in, float* out) {
-    WO_XCD_CELLS(r, F.N) out[r] = glacial_blend_cell(F, in, r);
-}
-
-// ---------------------------------------------------------------- noise -------------------------
-__device__ inline void load_tables(const uint8_t* tables, uint8_t* sP, uint8_t* sM) {
-    for (int i = threadIdx.x; i < 512; i += blockDim.x) { sP[i] = tables[i]; sM[i] = tables[512 + i]; }
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(WO_BLOCK) void k_noise_eval(const uint8_t* tables, int32_t kind, int32_t octaves, double p0,
-                                                          double p1, double p2, int64_t n, const double* xyz, double* out) {
-    __shared__ uint8_t sP[512], sM[512];
-    load_tables(tables, sP, sM);
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const double x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-        double v;
-        if (kind == 0) v = noise3d(sP, sM, x, y, z);
-        else if (kind == 1) v = fbm(sP, sM, x, y, z, octaves, p0);
-        else v = ridged_fbm(sP, sM, x, y, z, octaves, p0, p1, p2);
-        out[i] = v;
-    }
-}
-
-// SURVEY 8(d) synthetic terrain: e = 0.9*fbm(1.5p,5) - 0.12 + 0.25*ridged(3p,4)*max(0,fbm(1.5p,5))
-__global__ __launch_bounds__(WO_BLOCK) void k_synthetic(const uint8_t* tables, const float* xyz, float* e, uint8_t* ocean, int32_t N) {
-    __shared__ uint8_t sP[512], sM[512];
-    load_tables(tables, sP, sM);
-    WO_GRID_STRIDE(r, N) {
-        const double x = xyz[3 * r], y = xyz[3 * r + 1], z = xyz[3 * r + 2];
-        const double f = fbm(sP, sM, x * 1.5, y * 1.5, z * 1.5, 5);
-        const double rg = ridged_fbm(sP, sM, x * 3, y * 3, z * 3, 4);
-        const float v = (float)(0.9 * f - 0.12 + 0.25 * rg * (f > 0 ? f : 0));
-        e[r] = v;
-        ocean[r] = (v <= 0.0f) ? 1 : 0;
-    }
-}
-
-__global__ __launch_bounds__(WO_BLOCK) void k_warp(Fields F, const uint8_t* tables, const float* in, float* out, double maxAmp,
-                                                    double warpBias, const float* hot) {
-    __shared__ uint8_t sP[512], sM[512];
-    load_tables(tables, sP, sM);
-    WO_XCD_CELLS(r, F.N) {
-        const int32_t src = warp_source_cell(F, sP, sM, r, maxAmp);
-        out[r] = warp_blend(in[r], in[src], warpBias, hot != nullptr, hot ? hot[r] : 0.0f);
-    }
-}
-
-// ---------------------------------------------------------------- halo pack / unpack (banded Jacobi) ----
-__global__ __launch_bounds__(WO_BLOCK) void k_halo_pack(const float* e, const int32_t* idx, int32_t n, float* out) { WO_GRID_STRIDE(i, n) out[i] = e[idx[i]]; }
-__global__ __launch_bounds__(WO_BLOCK) void k_halo_unpack(float* e, const int32_t* idx, int32_t n, const float* in) { WO_GRID_STRIDE(i, n) e[idx[i]] = in[i]; }
-
-// ---------------------------------------------------------------- climate-util smoothField ------
-__global__ __launch_bounds__(WO_BLOCK) void k_smooth_field(Fields F, const float* src, float* dst) {
-    WO_XCD_CELLS(r, F.N) dst[r] = smooth_field_cell(F, src, r);
-}
-
-// ---------------------------------------------------------------- climate sweeps (js/temperature.js, js/precipitation.js) ----
-__global__ __launch_bounds__(WO_BLOCK) void k_warmth_seed(const float* warmth, const uint8_t* isLand, float* out, int32_t N) {
-    WO_GRID_STRIDE(r, N) out[r] = warmth_seed_cell(warmth, isLand, r);
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_warmth_diffuse(Fields F, ClimateMesh M, const float* src, const float* cont, float* dst) {
-    WO_XCD_CELLS(r, F.N) dst[r] = warmth_diffuse_cell(M, src, cont, r);
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_wind_convergence(Fields F, ClimateMesh M, const float* wx, const float* wy, const float* wz, float* out) {
-    WO_XCD_CELLS(r, F.N) out[r] = wind_convergence_cell(M, wx, wy, wz, r);
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_moisture_seed(Fields F, ClimateMesh M, const uint8_t* isLand, const float* wx, const float* wy, const float* wz,
-                                                             const float* warmth, const int32_t* coastDist, float* out) {
-    WO_XCD_CELLS(r, F.N) out[r] = moisture_seed_cell(M, isLand, wx, wy, wz, warmth, coastDist, r);
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_moisture_advect(Fields F, ClimateMesh M, const float* src, const float* heightKm, const uint8_t* isLand,
-                                                               const float* windE, const float* windN, const float* wx, const float* wy, const float* wz,
-                                                               int32_t maxHops, double depletionBase, float* dst) {
-    WO_XCD_CELLS(r, F.N) dst[r] = moisture_advect_cell(M, src, heightKm, isLand, windE, windN, wx, wy, wz, maxHops, depletionBase, r);
-}
-
-// ---------------------------------------------------------------- plate projection --------------
-// js/coarse-plates.js:51-117: one thread per hi-res cell (12 noise3D from LDS tables, then a greedy ascent over the
-// 20 k-cell coarse mesh, which stays in L2); the start cells come from a small (z, longitude) bucket grid.
-__global__ __launch_bounds__(WO_BLOCK) void k_plate_grid(CoarsePlates C, int32_t* grid) {
-    WO_GRID_STRIDE(b, C.gridZ * C.gridLon) grid[b] = plate_grid_cell(C, b);
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_plate_project(CoarsePlates C, const uint8_t* tables, const float* r_xyz, int32_t N, double perturbAmp,
-                                                             int32_t* r_plate) {
-    __shared__ uint8_t sP[512], sM[512];
-    load_tables(tables, sP, sM);
-    WO_GRID_STRIDE(r, N) r_plate[r] = plate_project_cell(C, sP, sM, r_xyz, r, perturbAmp);
-}
 
 // ---------------------------------------------------------------- land list ---------------------
 __global__ __launch_bounds__(WO_BLOCK) void k_init_rank(int32_t* rank, int32_t N) { WO_GRID_STRIDE(r, N) rank[r] = -1; }
@@ -773,7 +627,6 @@ __global__ __launch_bounds__(WO_BLOCK) void k_solve_final(Fields F, float* out, 
         if (masked) masked[r] = v;
     }
 }
-__global__ __launch_bounds__(WO_BLOCK) void k_fill_i32(int32_t* a, int32_t v, int32_t n) { WO_GRID_STRIDE(i, n) a[i] = v; }
 
 // ---------------------------------------------------------------- thermal -----------------------
 __global__ __launch_bounds__(WO_BLOCK) void k_masked_elev(Fields F) { WO_XCD_LAND(i, r) F.me[r] = F.e[r]; }
@@ -809,6 +662,9 @@ __global__ __launch_bounds__(WO_BLOCK) void k_thermal_apply(Fields F, float* out
 
 // ---------------------------------------------------------------- glacial -----------------------
 __global__ __launch_bounds__(WO_BLOCK) void k_glac_index(Fields F, double strength) { WO_XCD_CELLS(r, F.N) F.glac[r] = glac_index_cell(F, r, strength); }
+__global__ __launch_bounds__(WO_BLOCK) void k_glacial_blend(Fields F, const float* in, float* out) {
+    WO_XCD_CELLS(r, F.N) out[r] = glacial_blend_cell(F, in, r);
+}
 __global__ __launch_bounds__(WO_BLOCK) void k_ice_receivers(Fields F) {
     WO_XCD_CELLS(r, F.N) { ice_receiver_cell(F, r); F.blocker[r] = 0; if (F.ocean[r]) { F.iceFlow[r] = 0.0f; F.iceUp[r] = 0; } }      // blocker: k_ice_climb's arrival counts (carve_setup_cell resets it)
 }
@@ -940,7 +796,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_carve_round_static(Fields F, const
 //  * The activation list is in RANK order (select_active_by_rank), so a task's dependencies all sit at lower positions; thread g
 //    takes positions g, g + G, g + 2G, ... in turn with G = all the launch's threads.  The lowest unfinished position then always
 //    belongs to a thread that has nothing earlier left, so some task can always run provided the G threads are resident: the grid
-//    is sized by the occupancy query (minus a margin, planet.hip), never by the task count.
+//    is sized by the occupancy query (minus a margin, erode.hip: carve_granule_blocks), never by the task count.
 //  * A wave is a set of 64 independent little state machines inside ONE wave-uniform loop: a lane that finds its task ready takes
 //    the turn inside the loop body, so no lane ever sits at a reconvergence point waiting for another lane's poll (whose task may
 //    depend on it).
@@ -1163,33 +1019,6 @@ __global__ __launch_bounds__(WO_BLOCK) void k_carve_jacobi(Fields F, const float
         }
         out[c] = (float)e;
     }
-}
-
-// ---- patch-major mirror of the mesh for erodeComposite (planet.hip: Mirror).  perm: mirror id -> cell id, inv: the inverse ----
-__global__ __launch_bounds__(WO_BLOCK) void k_mirror_gather_f32(const float* src, const int32_t* perm, float* dst, int32_t n) { WO_GRID_STRIDE(i, n) dst[i] = src[perm[i]]; }
-__global__ __launch_bounds__(WO_BLOCK) void k_mirror_scatter_f32(const float* src, const int32_t* perm, float* dst, int32_t n) { WO_GRID_STRIDE(i, n) dst[perm[i]] = src[i]; }
-__global__ __launch_bounds__(WO_BLOCK) void k_mirror_gather_u8(const uint8_t* src, const int32_t* perm, uint8_t* dst, int32_t n) { WO_GRID_STRIDE(i, n) dst[i] = src[perm[i]]; }
-__global__ __launch_bounds__(WO_BLOCK) void k_mirror_map_i32(const int32_t* in, const int32_t* map, int32_t* out, int32_t n) { WO_GRID_STRIDE(i, n) out[i] = map[in[i]]; }
-__global__ __launch_bounds__(WO_BLOCK) void k_mirror_invert(const int32_t* perm, int32_t* inv, int32_t n) { WO_GRID_STRIDE(i, n) inv[perm[i]] = i; }
-// rows keep their order (the reference's adjacency order is part of its semantics); only the ids are renamed
-__global__ __launch_bounds__(WO_BLOCK) void k_mirror_rows(const int32_t* off, const int32_t* adj, const float* dist, const float* xyz, const int32_t* perm,
-                                                           const int32_t* inv, const int32_t* moff, int32_t* madj, float* mdist, float* mxyz, int32_t n) {
-    WO_GRID_STRIDE(i, n) {
-        const int32_t r = perm[i];
-        const int32_t b = off[r], deg = off[r + 1] - b, mb = moff[i];
-        for (int32_t k = 0; k < deg; ++k) { madj[mb + k] = inv[adj[b + k]]; mdist[mb + k] = dist[b + k]; }
-        mxyz[3 * i] = xyz[3 * r]; mxyz[3 * i + 1] = xyz[3 * r + 1]; mxyz[3 * i + 2] = xyz[3 * r + 2];
-    }
-}
-
-// {serial, value} of a device counter into a host-mapped word: the host polls the word instead of paying a copy, a stream
-// synchronisation and its wake-up for one integer (planet.hip: read_count)
-__global__ void k_publish_count(const int32_t* __restrict__ src, unsigned long long* hostWord, uint32_t serial) {
-    if (threadIdx.x == 0 && blockIdx.x == 0)
-        __hip_atomic_store(hostWord, ((unsigned long long)serial << 32) | (unsigned long long)(uint32_t)*src, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__global__ void k_set_counters(int32_t* c, int32_t v0, int32_t v1, int32_t v2, int32_t v3) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) { c[0] = v0; c[1] = v1; c[2] = v2; c[3] = v3; }
 }
 
 }  // namespace wo

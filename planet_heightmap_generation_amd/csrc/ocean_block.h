@@ -50,7 +50,7 @@ const BlockDesc& ocean_desc();                                // ocean.hip: the 
 // ocean.hip: allocates the planet's ocean block if there is none
 void ocean_alloc(wo_planet* p);
 
-// the cell of a thread under the XCD-aware tiling of the index-order passes (kernels_impl.h: WO_XCD_CELLS); grid: xcd_grid(N)
+// the cell of a thread under the XCD-aware tiling of the index-order passes (common_kernels.h: WO_XCD_CELLS); grid: xcd_grid(N)
 __device__ inline int32_t ocean_xcd_cell(int32_t tile) {
     const int32_t xi = (int32_t)(blockIdx.x >> 3);
     return (((xi / tile) * 8 + (int32_t)(blockIdx.x & 7u)) * tile + (xi % tile)) * (int32_t)blockDim.x + (int32_t)threadIdx.x;

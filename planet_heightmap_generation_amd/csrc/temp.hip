@@ -12,7 +12,7 @@
 //   k_temp_cell [1]                      the per-cell loop, both seasons per thread (one ITCZ lookup per season from LDS)
 //   k_temp_smooth [1]                    the smoothField pass with the normalisation at its store, both seasons
 // and one of wo_classify_koppen: k_koppen [1].  Under WO_TEST_HOOKS=temp_split_diffuse the diffusion runs season by season with the
-// single-field kernels of kernels_impl.h (k_warmth_seed, k_warmth_diffuse: 2 + 2 x oceanWarmthPasses launches, then k_temp_join);
+// single-field kernels of climate_sweeps.hip (k_warmth_seed, k_warmth_diffuse: 2 + 2 x oceanWarmthPasses launches, then k_temp_join);
 // the same bits.  Temporaries live in an arena on the call's stack; no host round trip: the stream is waited for once, at the end.
 #include <hip/hip_runtime.h>
 

@@ -1,9 +1,9 @@
 #!/bin/bash
 # An alternative build of libworogen.so for research/ab/run_ab.sh: bash research/ab/build_variant.sh <name> "<extra compiler flags>" [file.hip ...]
-# Only the listed translation units (default planet.hip) are recompiled with the flags; the rest comes from the in-tree build directory.
+# Only the listed translation units (default erode.hip: the erosion kernels of kernels_impl.h) are recompiled with the flags; the rest comes from the in-tree build directory.
 set -e
 cd "$(dirname "$0")/../../planet_heightmap_generation_amd/csrc"
-name=$1; flags=$2; shift 2; units=${@:-planet.hip}
+name=$1; flags=$2; shift 2; units=${@:-erode.hip}
 make -s >/dev/null
 mkdir -p build/ab_$name
 objs=""

@@ -16,7 +16,7 @@ build_variant() {   # name, object to rebuild, flags
 }
 build_variant rs8 radix.hip.o -DWO_RS_ITEMS=8
 build_variant rs32 radix.hip.o -DWO_RS_ITEMS=32
-build_variant tw8 planet.hip.o -DWO_THERMAL_WAVES=8
-build_variant tw4 planet.hip.o -DWO_THERMAL_WAVES=4
+build_variant tw8 erode.hip.o -DWO_THERMAL_WAVES=8
+build_variant tw4 erode.hip.o -DWO_THERMAL_WAVES=4
 build_variant br512 basin.hip.o -DWO_BASIN_RANGE_SLOTS=512
 build_variant br128 basin.hip.o -DWO_BASIN_RANGE_SLOTS=128

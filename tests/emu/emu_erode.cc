@@ -64,7 +64,7 @@ int64_t run_rounds(std::vector<int32_t> list, Task task) {
     return round;
 }
 
-// solve rounds with level prediction, mirroring run_solve_rounds() in planet.hip: round k examines the
+// solve rounds with level prediction (the round form of the solve; the library's own driver is run_solve_patches in erode.hip): round k examines the
 // leftovers plus the tasks whose level in the previous iteration was k
 static int LOOKAHEAD = 2;
 int64_t run_solve_rounds_pred(Emu& E, std::vector<int32_t>& level, double K, double m, double dt) {

@@ -16,7 +16,7 @@ import pytest
 import elev_inputs as EI
 
 pytestmark = pytest.mark.gpu
-GRID_THREADS = 512 * 256            # k_bfs_push / count / assign: grid 512 x WO_BLOCK 256 (planet.hip, run_field)
+GRID_THREADS = 512 * 256            # k_bfs_push / count / assign: grid 512 x WO_BLOCK 256 (elevation.hip, run_field)
 
 
 @pytest.fixture(scope="module")

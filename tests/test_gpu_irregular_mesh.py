@@ -1,7 +1,7 @@
 """The HIP path on valid meshes the Fibonacci-sphere builder never makes (tests/irregular_mesh.py): hub cells of degree 9 .. 24, relabelled
 cells and shuffled rows, against the CPU oracle on the same mesh.
 
-The planet's largest degree picks the thermal apply kernel (csrc/planet.hip: k_thermal_apply_reg<12> up to 12, k_thermal_apply_reg<16>
+The planet's largest degree picks the thermal apply kernel (csrc/erode.hip: k_thermal_apply_reg<12> up to 12, k_thermal_apply_reg<16>
 for 13-16, the dynamic-LDS k_thermal_apply for 17-24, whose request passes 64 KiB from degree 22 on); rows longer than WO_EAGER_ROW = 12
 take the long-row glacial carve (carve_granule_turn_long_row) and rows longer than WO_ROW = 8 the plain-loop forms.  Bars as in
 test_gpu_parity.py: bit for bit where the device calls no libm; with glacial iterations or m != 0.5 (pow / asin on the device) the

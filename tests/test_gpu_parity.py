@@ -324,7 +324,7 @@ def test_planets_in_flight_match_sequential(TP):
 
 
 def test_mirror_layout_is_invisible(TP, oracle, monkeypatch):
-    """erodeComposite runs on a patch-major renaming of the cells (csrc/planet.hip, MirrorScope; WO_LAYOUT=index switches it
+    """erodeComposite runs on a patch-major renaming of the cells (csrc/mirror.hip, MirrorScope; WO_LAYOUT=index switches it
     off).  Names enter the reference only through the initial landCells order (js/terrain-post.js:384-390) and cellNoise(r) in
     the flood (:98-105), both kept: with glacial iterations, both floods and quantised (tie-heavy) terrain the field must be
     the index-order run's bit for bit, and the oracle's without the libm passes."""
@@ -1016,7 +1016,7 @@ def test_decomposed_shares_when_some_shares_have_no_land(TP, oracle):
 @pytest.mark.gpu
 def test_flood_stage_inside_the_mirror_copies_the_land_only(TP, oracle, monkeypatch, capfd):
     """Inside the land-first mirror the flood stage copies the first L floats of the mirrored field — the land heights, in the host flood's
-    own land order — instead of the whole field in the planet's order (planet.hip: flood_stage_land).  The first flood of a call after the
+    own land order — instead of the whole field in the planet's order (flood.hip: flood_stage_land).  The first flood of a call after the
     mask changed takes the full route (it rebuilds the host tables), the second one and every flood of the calls that follow the land-only
     route (WO_FLOOD_TIMING names it on stderr); the field after 12 composite iterations must be the oracle's bit for bit, call after call."""
     from planet_heightmap_generation_amd import sphere_mesh as S
