@@ -518,6 +518,39 @@ int wo_map_raster_centered(wo_planet* p, int32_t numSides, const int32_t* triang
                            double centerLon, int32_t* regionMapOut, int64_t counts[2]);
 int wo_map_color_layer(wo_planet* p, int32_t layer, const float* values, const float* r_elevation, uint8_t* rgbaOut, int64_t outBytes);
 
+/* ------------------------------------------------ globe mesh (js/planet-mesh.js) -------------- */
+/* buildMesh, updateMeshColors, updateSuperPlateBorders (globe form)                  js/planet-mesh.js:620-836, :840-957, :533-576
+ *   The displaced Voronoi-fan mesh three.js draws, as the reference's own Float32Arrays bit for bit (csrc/globe.hip; the bodies and
+ *   the whole contract are in csrc/globe_ops.h).  Every side s of the mesh (triangles, halfedges and their checks as for
+ *   wo_map_raster) gives one triangle: the centres of its inner and outer triangle and its region, each displaced by its
+ *   elevation, the winding fixed; nine floats at 9 * s in positionsOut, and the region's colour three times at 9 * s in colorsOut.
+ *   No quantiser and no gamma table: these are the linear f32 colours.  outFloats must be numSides * 9 exactly.  positionsOut or
+ *   colorsOut may be NULL (not both): without positions the call is updateMeshColors.  bounds (may be NULL; written with positions
+ *   only) receives min x, y, z, max x, y, z of the stored positions, NaN skipped, -0 < +0, all 0 where there is nothing but NaN.
+ *   r_elevation: numRegions floats, NULL means the planet's resident field; t_xyz and t_elevation are built inside the call.
+ *   wo_globe_mesh colours by source: WO_GLOBE_SOURCE_TYPE with id one of WO_MAP_* (not WO_MAP_LANDMASK: buildMesh has no such
+ *   branch; WO_MAP_BIOME and WO_MAP_KOPPEN need the Koppen block), values must be NULL; or WO_GLOBE_SOURCE_LAYER with id one of
+ *   WO_MAP_LAYER_*, values and the resident blocks under the rules and messages of wo_map_color_layer.
+ *   wo_globe_mesh_plates colours by plate (:734-736): plateColors[r_plate[region]], or (0.3, 0.3, 0.3) for a plate that is not in the
+ *   table.  r_plate: numRegions int32; plateSeeds: numPlates region ids; plateColors: one f32 triple per seed (of a seed listed
+ *   twice the last row counts).
+ *   wo_globe_lines gives line segments, six floats each, in ascending side order: WO_GLOBE_LINES_WIREFRAME one per side with
+ *   s < halfedges[s] (base 1.001, superPlates must be NULL); WO_GLOBE_LINES_SUPER_PLATE_BORDERS those of them whose two regions
+ *   differ in superPlates (numRegions floats, compared as floats: NaN differs from everything, -0 equals +0; base 1.002).
+ *   capacity is the room of segmentsOut in segments and must be at least numSides / 2; *count receives the number written, and
+ *   nothing is written behind them.
+ *   A refused call returns 1, names the offending value and allocates nothing. */
+enum { WO_GLOBE_SOURCE_TYPE = 0, WO_GLOBE_SOURCE_LAYER = 1 };
+enum { WO_GLOBE_LINES_WIREFRAME = 0, WO_GLOBE_LINES_SUPER_PLATE_BORDERS = 1 };
+int wo_globe_mesh(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t source, int32_t id,
+                  const float* values, const float* r_elevation, float* positionsOut, float* colorsOut, int64_t outFloats,
+                  float bounds[6]);
+int wo_globe_mesh_plates(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, const int32_t* r_plate,
+                         int32_t numPlates, const int32_t* plateSeeds, const float* plateColors, const float* r_elevation,
+                         float* positionsOut, float* colorsOut, int64_t outFloats, float bounds[6]);
+int wo_globe_lines(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t kind,
+                   const float* r_elevation, const float* superPlates, float* segmentsOut, int64_t capacity, int64_t* count);
+
 /* ------------------------------------------------ device-resident variants -------------------- */
 /* The "reapply" pattern (js/planet-worker.js:341-440): fields stay in HBM, only scalars arrive.
  * wo_planet_upload sets the resident r_elevation (and r_isOcean when not NULL); the *_resident

@@ -35,6 +35,7 @@
 #include "device.h"
 #include "map_layer_ops.h"
 #include "map_ops.h"
+#include "map_shared.h"
 #include "ocean_block.h"
 #include "precip_block.h"
 #include "stage_block.h"
@@ -237,10 +238,18 @@ __global__ __launch_bounds__(WO_BLOCK) void k_map_pixels(const int32_t* __restri
 
 void map_free(wo_planet* p) { delete p->map; p->map = nullptr; }
 
+// map_shared.h: the two launches the globe mesh shares with the map
+void map_launch_range(wo_planet* p, int fam, const float* v, int32_t N, uint32_t* range) {
+    launch(p, fam, k_map_range, blocks_for(((int64_t)N + 15) / 16, 1024), WO_BLOCK, v, N, range);      // 16 values per thread and turn
+}
+void map_launch_biome_raw(wo_planet* p, int fam, const float* e, const uint8_t* koppen, float* raw, int32_t N) {
+    launch(p, fam, k_map_biome_raw, blocks_for(N), WO_BLOCK, e, koppen, raw, N);
+}
+
 static bool map_width_ok(int32_t width) { return width >= 2 && width <= 32768 && (width & 1) == 0; }
 
 // numSides % 3 == 0 was checked; every corner a region of the planet, every half-edge a side of the mesh
-static bool map_topology_ok(int32_t N, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, std::string& err) {
+bool map_topology_ok(int32_t N, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, std::string& err) {
     std::atomic<int64_t> badCorner{-1}, badEdge{-1};
     parallel_ranges(numSides, [&](int64_t b, int64_t e, int) {
         for (int64_t s = b; s < e; ++s) {
@@ -315,8 +324,7 @@ static int map_raster(wo_planet* p, const char* fn, int32_t numSides, const int3
 }
 
 // where a named layer's values live: the block, and the reference's result key of the field (two for the ocean-current layers)
-struct LayerSource { const BlockDesc* block; const char *a, *b; const char* hint; };
-static LayerSource layer_source(int32_t layer) {
+LayerSource wo::layer_source(int32_t layer) {
     switch (layer) {
         case M::LAYER_CONTINENTALITY: return {&wind_desc(), "r_continentality", nullptr, "wo_wind_upload r_continentality"};
         case M::LAYER_TEMP_SUMMER: return {&temp_desc(), "r_temperature_summer", nullptr, "wo_temperature_upload r_temperature_summer"};
@@ -368,7 +376,7 @@ int wo_map_color(wo_planet* p, int32_t type, const float* r_elevation, uint8_t* 
         uint32_t* out = T.dev<uint32_t>((size_t)pixels);
         if (type == M::TYPE_BIOME) {
             float* raw = T.dev<float>(3 * (size_t)N);
-            launch(p, FAM_MAP_REGION_COLORS, k_map_biome_raw, g, WO_BLOCK, e, koppen, raw, N);
+            map_launch_biome_raw(p, FAM_MAP_REGION_COLORS, e, koppen, raw, N);
             launch(p, FAM_MAP_REGION_COLORS, k_map_biome_smooth, g, WO_BLOCK, (const float*)raw, (const int32_t*)p->d_off, (const int32_t*)p->d_adj, d_lut, regionRgba, N);
         } else {
             launch(p, FAM_MAP_REGION_COLORS, k_map_region_colors, g, WO_BLOCK, type, e, koppen, d_lut, regionRgba, N);
@@ -415,7 +423,7 @@ int wo_map_color_layer(wo_planet* p, int32_t layer, const float* values, const f
         uint32_t* out = T.dev<uint32_t>((size_t)pixels);
         if (M::layer_needs_range(layer)) {
             WO_HIP(hipMemsetAsync(range, 0, 8, s));
-            launch(p, FAM_MAP_RANGE, k_map_range, blocks_for(((int64_t)N + 15) / 16, 1024), WO_BLOCK, a, N, range);      // 16 values per thread and turn
+            map_launch_range(p, FAM_MAP_RANGE, a, N, range);
         }
         launch(p, FAM_MAP_LAYER_COLORS, k_map_layer_colors, g, WO_BLOCK, layer, a, b, e, (const uint32_t*)range, d_lut, regionRgba, N);
         launch(p, FAM_MAP_PIXELS, k_map_pixels, blocks_for((pixels + 3) / 4, 1 << 14), WO_BLOCK, (const int32_t*)B->region, (const uint32_t*)regionRgba, M::background_rgba(M::TYPE_COLOR, lut),

@@ -1,0 +1,113 @@
+// The host half of the globe export (js/globe-export.js re-exports it): computePlateColors, the GLB encoder and the file name.  It
+// loads no native code, and planet_heightmap_generation_amd/globe_export.py states the same functions byte for byte alike.
+// the opacities of the reference's two black line materials (:792, :573)
+export const LINE_OPACITY = { wireframe: 0.12, superPlateBorders: 0.55 };
+export const GLB_MAX_BYTES = 0xFFFFFFFF;                    // the container's lengths are uint32
+
+// ours: the reference exports no globe
+export function globeFilename(view, seed) { return `orogen-globe-${view}-${seed}.glb`; }
+
+// ---- computePlateColors (:181-197) -------------------------------------------------------------------------------------------
+// makeRng(seed) (js/rng.js:3-6)
+function parkMiller(seed) {
+    let s = (Math.abs(Math.floor(seed * 9301 + 49297)) % 2147483646) + 1;
+    return () => { s = (s * 16807) % 2147483647; return (s - 1) / 2147483646; };
+}
+function hue2rgb(p, q, t) {
+    if (t < 0) t += 1;
+    if (t > 1) t -= 1;
+    if (t < 1 / 6) return p + (q - p) * 6 * t;
+    if (t < 1 / 2) return q;
+    if (t < 2 / 3) return p + (q - p) * 6 * (2 / 3 - t);
+    return p;
+}
+// three r160's Color.setHSL in the default (linear) working space, restated: h by Euclidean modulo 1, s and l clamped to [0, 1], then
+// p, q and hue2rgb; no colour-space conversion.  OUR READING: three is not part of the reference's sources.
+export function setHSL(h, s, l) {
+    h = ((h % 1) + 1) % 1;
+    s = Math.max(0, Math.min(1, s));
+    l = Math.max(0, Math.min(1, l));
+    if (s === 0) return [l, l, l];
+    const p = l <= 0.5 ? l * (1 + s) : l + s - l * s;
+    const q = 2 * l - p;
+    return [hue2rgb(q, p, h + 1 / 3), hue2rgb(q, p, h), hue2rgb(q, p, h - 1 / 3)];
+}
+// computePlateColors(plateSeeds, plateIsOcean) -> Float32Array(3 per seed, in the order of plateSeeds): the triple buildMesh stores
+export function computePlateColors(plateSeeds, plateIsOcean) {
+    const ocean = plateIsOcean instanceof Set ? plateIsOcean : new Set(plateIsOcean), seeds = Array.from(plateSeeds);
+    const out = new Float32Array(3 * seeds.length);
+    seeds.forEach((r, i) => {
+        const rng = parkMiller(r);
+        let h, s, l;
+        if (ocean.has(r)) { h = 0.55 + rng() * 0.10; s = 0.40 + rng() * 0.30; l = 0.35 + rng() * 0.20; }
+        else { h = 0.25 + rng() * 0.15; s = 0.30 + rng() * 0.30; l = 0.30 + rng() * 0.20; }
+        out.set(setHSL(h, s, l), 3 * i);
+    });
+    return out;
+}
+
+// ---- binary glTF 2.0: header, one JSON chunk padded with spaces, one BIN chunk ------------------------------------------------
+function vertexBounds(a) {                                  // min and max per axis, NaN skipped, 0 where there is nothing else
+    const lo = [Infinity, Infinity, Infinity], hi = [-Infinity, -Infinity, -Infinity], seen = [false, false, false];
+    for (let i = 0; i < a.length; i++) {
+        const v = a[i], k = i % 3;
+        if (v !== v) continue;
+        seen[k] = true;
+        if (v < lo[k]) lo[k] = v;
+        if (v > hi[k]) hi[k] = v;
+    }
+    return [0, 1, 2].map((k) => (seen[k] ? lo[k] : 0)).concat([0, 1, 2].map((k) => (seen[k] ? hi[k] : 0)));
+}
+
+// encodeGlb({ position, color, bounds }, { wireframe, superPlateBorders, name }) -> Uint8Array (the file's bytes).  One buffer, one mesh: a
+// TRIANGLES primitive with POSITION (min / max from bounds) and COLOR_0, both f32 VEC3 and linear; its material the default
+// metallic-roughness one with metallic 0 and roughness 1 (our decision: the reference's Lambert shader and its normals are not
+// offered); a LINES primitive with a black material at the reference's opacity per line set.
+export function encodeGlb(mesh, opts) {
+    const o = opts || {}, { position, color, bounds } = mesh;
+    if (!(position instanceof Float32Array) || !(color instanceof Float32Array) || !(bounds instanceof Float32Array)) throw new TypeError("encodeGlb needs position, color and bounds (buildMesh's result)");
+    if (position.length !== color.length || position.length % 9) throw new RangeError(`position has ${position.length} floats and color ${color.length}: both must hold numSides * 9`);
+    const lines = [['wireframe', o.wireframe], ['superPlateBorders', o.superPlateBorders]].filter(([, a]) => a && a.length);
+    for (const [k, a] of lines) if (a.length % 6) throw new RangeError(`${k} has ${a.length} floats, no multiple of 6`);
+    const arrays = [position, color].concat(lines.map(([, a]) => a));
+    const binary = arrays.reduce((n, a) => n + a.length * 4, 0);
+    if (binary + 65536 > GLB_MAX_BYTES) {
+        throw new RangeError(`the globe's buffers take ${binary} bytes, more than a binary glTF file can hold (its lengths are uint32: ${GLB_MAX_BYTES} bytes); chunked export is not offered`);
+    }
+    const limits = [Array.from(bounds)].concat(lines.map(([, a]) => vertexBounds(a)));
+    ['the mesh'].concat(lines.map(([k]) => k)).forEach((what, i) => {
+        if (!limits[i].every(Number.isFinite)) throw new RangeError(`the bounds of ${what} are not finite (${limits[i]}): glTF's JSON cannot hold them`);
+    });
+    const views = [], accessors = [];
+    let offset = 0;
+    arrays.forEach((a, i) => {
+        views.push({ buffer: 0, byteOffset: offset, byteLength: a.length * 4, target: 34962 });
+        const acc = { bufferView: i, componentType: 5126, count: a.length / 3, type: 'VEC3' };
+        if (i !== 1) { const b = limits[i === 0 ? 0 : i - 1]; acc.min = b.slice(0, 3); acc.max = b.slice(3); }
+        accessors.push(acc);
+        offset += a.length * 4;
+    });
+    const name = o.name || 'globe';
+    const materials = [{ name: 'globe', pbrMetallicRoughness: { metallicFactor: 0, roughnessFactor: 1 } }];
+    const primitives = [{ attributes: { POSITION: 0, COLOR_0: 1 }, mode: 4, material: 0 }];
+    lines.forEach(([k], j) => {
+        materials.push({ name: k, pbrMetallicRoughness: { baseColorFactor: [0, 0, 0, LINE_OPACITY[k]], metallicFactor: 0, roughnessFactor: 1 }, alphaMode: 'BLEND' });
+        primitives.push({ attributes: { POSITION: 2 + j }, mode: 1, material: 1 + j, extras: { name: k } });
+    });
+    const doc = { asset: { version: '2.0', generator: 'planet_heightmap_generation_amd' }, scene: 0, scenes: [{ nodes: [0] }], nodes: [{ mesh: 0, name }],
+                  meshes: [{ name, primitives }], materials, buffers: [{ byteLength: binary }], bufferViews: views, accessors };
+    let text = Buffer.from(JSON.stringify(doc), 'utf8');
+    if (text.length % 4) text = Buffer.concat([text, Buffer.alloc(4 - text.length % 4, 0x20)]);
+    const pad = (4 - binary % 4) % 4, total = 12 + 8 + text.length + 8 + binary + pad;
+    let out;
+    try { out = new Uint8Array(total); } catch (err) { throw new RangeError(`a binary glTF file of ${total} bytes does not fit into one ArrayBuffer of this Node`); }
+    const dv = new DataView(out.buffer);
+    out.set([0x67, 0x6C, 0x54, 0x46], 0); dv.setUint32(4, 2, true); dv.setUint32(8, total, true);
+    dv.setUint32(12, text.length, true); out.set([0x4A, 0x53, 0x4F, 0x4E], 16);
+    out.set(text, 20);
+    let at = 20 + text.length;
+    dv.setUint32(at, binary + pad, true); out.set([0x42, 0x49, 0x4E, 0x00], at + 4);
+    at += 8;
+    for (const a of arrays) { out.set(new Uint8Array(a.buffer, a.byteOffset, a.byteLength), at); at += a.byteLength; }
+    return out;
+}

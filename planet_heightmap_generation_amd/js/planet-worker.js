@@ -76,6 +76,17 @@
 //                  `centerLon` (radians, within [-pi, pi]) draws the map around that meridian.  Progress then counts types + layers.
 //                  -> { type: 'exportDone', width, height, maps: [{ type, filename, rgba, png? }],
 //                       _exportTiming: { raster, color, encode, workerTotal } }, the buffers transferred
+//   cmd 'exportGlobe' { view?, layer?, plates?, wireframe?, superPlateBorders?, glb? }   (js/planet-mesh.js:620-836, :533-576)
+//                  the globe mesh three.js would draw, of the planet's current elevation: one displaced triangle per side, nine floats
+//                  of positions and nine of colours each, built on the device (js/globe-export.js).  `view`: color (the default),
+//                  heightmap, landheightmap, biome or koppen; `layer`: a layer as for exportMap, a climate layer from the planet's
+//                  block or a key of the retained debugLayers; `plates`: the plate colours (computePlateColors over the retained
+//                  plateSeeds and plateIsOcean, needs r_plate).  `wireframe` adds the Voronoi wireframe, `superPlateBorders` the
+//                  borders of the retained debugLayers.superPlates (true) or of a Float32Array of the caller's.  With `glb` the answer carries the binary glTF file of all of it
+//                  instead of the arrays.  Needs what exportMap needs of the retained state and answers as it does without it.
+//                  Progress: `Building globe...` at 0, `Done` at 90.
+//                  -> { type: 'globeDone', view, filename, numSides, bounds, glb | position, color[, wireframe][, superPlateBorders],
+//                       _globeTiming: { workerTotal } }, the buffers transferred
 //   cmd 'dispose'  frees the retained state -> { type: 'disposed' }
 //   progress / errors exactly as the reference posts them: { type: 'progress', pct, label }, { type: 'error', message, stack };
 //   an unknown command answers `Unknown command: <cmd>` (:952).
@@ -92,6 +103,7 @@ import { denseTable, plateDensities, LAYERS } from './plate-table.js';
 import { generateCoarsePlates } from './coarse-plates.js';
 import { SimplexNoise } from './simplex-noise.js';
 import { MAP_TYPES, MAP_LAYERS, exportFilename, layerFilename, encodePng, rasterOnPlanet } from './map-export.js';
+import { GLOBE_PLATES, GLOBE_TYPE_VIEWS, computePlateColors, exportGlobeOnPlanet, globeFilename } from './globe-export.js';
 
 let W = null;          // retained state (js/planet-worker.js:22)
 
@@ -207,6 +219,7 @@ function handleImportHeightmap(data) {
         const regions = addon.classifyRegions(planet);
         W.r_plate = new Int32Array(r_plate); W.plateIsOcean = Int32Array.from(plateIsOcean);     // copies: r_plate's buffer leaves with the message
         W.debugLayers = { erosionDelta: dl_erosionDelta };                                     // stays here: the message clones it
+        W.syntheticSeeds = Int32Array.from(plateSeeds);  // for exportGlobe's plate view only: W.plateSeeds stays null, editRecompute refuses synthetic plates
 
         progress(75, 'Computing triangle elevations\u2026');
         t0 = performance.now();
@@ -546,6 +559,57 @@ function handleExportMap(data) {
     }
 }
 
+// js/planet-mesh.js:620-836 without the page: the globe mesh of W.planet's current elevation in one view, its line sets, and the GLB file
+function handleExportGlobe(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for exportGlobe' }); return; }
+    const missing = ['triangles', 'halfedges'].filter((k) => !(W[k] instanceof Int32Array));
+    if (missing.length) {
+        parentPort.postMessage({ type: 'error', message: `exportGlobe: the retained state has no mesh.${missing.join(' and mesh.')} (pass them to retain, or run importHeightmap)` });
+        return;
+    }
+    try {
+        const tTotal0 = performance.now();
+        const generic = W.debugLayers || {};
+        let view = 'color';
+        const opts = { wireframe: !!data.wireframe, glb: !!data.glb };
+        if (data.plates) {
+            const seeds = W.plateSeeds || W.syntheticSeeds;
+            if (!W.r_plate || !seeds || !W.plateIsOcean) throw new Error('exportGlobe: the plate view needs r_plate, plateSeeds and plateIsOcean in the retained state');
+            view = GLOBE_PLATES;
+            opts.plates = { r_plate: W.r_plate, plateSeeds: seeds, plateColors: computePlateColors(seeds, W.plateIsOcean) };
+        } else if (data.layer !== undefined && data.layer !== null) {
+            const name = data.layer;
+            if (MAP_LAYERS.indexOf(name) > 0) view = name;
+            else if (name !== 'debug' && generic[name] instanceof Float32Array) { view = 'debug'; opts.values = generic[name]; }
+            else throw new RangeError(`exportGlobe: unknown map layer '${name}' (one of ${MAP_LAYERS.slice(1).concat(Object.keys(generic)).join(', ')})`);
+        } else if (data.view !== undefined && data.view !== null) {
+            if (GLOBE_TYPE_VIEWS.indexOf(data.view) < 0) throw new RangeError(`exportGlobe: unknown globe view '${data.view}' (one of ${GLOBE_TYPE_VIEWS.join(', ')})`);
+            view = data.view;
+        }
+        if (data.superPlateBorders instanceof Float32Array) opts.superPlates = data.superPlateBorders;      // the caller's own field
+        else if (data.superPlateBorders) {
+            if (!(generic.superPlates instanceof Float32Array)) throw new Error('exportGlobe: the retained debugLayers have no superPlates (generate or editRecompute with P >= 8 leaves them)');
+            opts.superPlates = generic.superPlates;
+        }
+        progress(0, 'Building globe...');
+        const name = data.plates ? GLOBE_PLATES : (data.layer !== undefined && data.layer !== null ? data.layer : view);
+        const res = exportGlobeOnPlanet(W.planet, W.triangles, W.halfedges, null, view, W.seed, opts);
+        progress(90, 'Done');
+        const msg = { type: 'globeDone', view: name, filename: globeFilename(name, W.seed), numSides: W.triangles.length, bounds: res.bounds };
+        const transfer = [];
+        if (res.glb) { msg.glb = res.glb; transfer.push(res.glb.buffer); }
+        else {
+            msg.position = res.position; msg.color = res.color;
+            transfer.push(res.position.buffer, res.color.buffer);
+            for (const k of ['wireframe', 'superPlateBorders']) if (res[k]) { msg[k] = res[k]; transfer.push(res[k].buffer); }
+        }
+        msg._globeTiming = { workerTotal: performance.now() - tTotal0 };
+        parentPort.postMessage(msg, transfer);
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
 parentPort.on('message', (data) => {
     const { cmd } = data;
     switch (cmd) {
@@ -556,6 +620,7 @@ parentPort.on('message', (data) => {
         case 'computeClimate': handleComputeClimate(data); break;
         case 'editRecompute': handleEditRecompute(data); break;
         case 'exportMap': handleExportMap(data); break;
+        case 'exportGlobe': handleExportGlobe(data); break;
         case 'generate': handleGenerate(data); break;
         default: parentPort.postMessage({ type: 'error', message: `Unknown command: ${cmd}` });
     }

@@ -865,6 +865,89 @@ napi_value MapFree(napi_env env, napi_callback_info info) {                    /
     return nullptr;
 }
 
+// ---- globe mesh (include/worogen.h: wo_globe_mesh / wo_globe_mesh_plates / wo_globe_lines) --------------------------------
+// the sides of a mesh at arguments 1 and 2
+bool globe_sides(Args& a, const char* fn, int32_t** tri, int32_t** he, size_t* ns) {
+    size_t nh;
+    *tri = (int32_t*)a.ta(1, napi_int32_array, ns); if (!a.ok) return false;
+    *he = (int32_t*)a.ta(2, napi_int32_array, &nh); if (!a.ok) return false;
+    if (*ns != nh || *ns == 0 || *ns >= ((size_t)1 << 30)) { napi_throw_range_error(a.env, nullptr, (std::string(fn) + ": triangles and halfedges must have the same length, numSides").c_str()); return false; }
+    return true;
+}
+// the two outputs asked for by the booleans at arguments i and i + 1 (undefined: true), nine floats per side each
+bool globe_outputs(Args& a, size_t i, size_t ns, napi_value* pos, void** dp, napi_value* col, void** dc) {
+    bool wp = true, wc = true;
+    if (a.has(i)) napi_get_value_bool(a.env, a.argv[i], &wp);
+    if (a.has(i + 1)) napi_get_value_bool(a.env, a.argv[i + 1], &wc);
+    *dp = *dc = nullptr;
+    napi_get_null(a.env, pos); napi_get_null(a.env, col);
+    if (wp && !(*pos = make_ta(a.env, napi_float32_array, ns * 9, 4, dp))) { napi_throw_range_error(a.env, nullptr, ("the position array of " + std::to_string(ns * 36) + " bytes does not fit into one ArrayBuffer").c_str()); return false; }
+    if (wc && !(*col = make_ta(a.env, napi_float32_array, ns * 9, 4, dc))) { napi_throw_range_error(a.env, nullptr, ("the colour array of " + std::to_string(ns * 36) + " bytes does not fit into one ArrayBuffer").c_str()); return false; }
+    return true;
+}
+napi_value globe_result(napi_env env, napi_value pos, napi_value col, const float bounds[6], bool havePositions) {
+    napi_value o; napi_create_object(env, &o);
+    set_prop(env, o, "position", pos); set_prop(env, o, "color", col);
+    napi_value b; napi_get_null(env, &b);
+    if (havePositions) { void* d; b = make_ta(env, napi_float32_array, 6, 4, &d); std::memcpy(d, bounds, 24); }
+    set_prop(env, o, "bounds", b);
+    return o;
+}
+// globeMesh(planet, triangles, halfedges, source 0 | 1, id, values | null, r_elevation | null, positions = true, colors = true)
+//   -> { position: Float32Array(numSides * 9) | null, color: the same | null, bounds: Float32Array(6) | null }
+napi_value GlobeMesh(napi_env env, napi_callback_info info) {
+    Args a(env, info);
+    int32_t *tri, *he; size_t ns;
+    if (!globe_sides(a, "globeMesh", &tri, &he, &ns)) return nullptr;
+    wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* v = (float*)opt_regions(a, 5, napi_float32_array, p, "values", false); if (!a.ok) return nullptr;
+    float* e = (float*)opt_regions(a, 6, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    napi_value pos, col; void *dp, *dc;
+    if (!globe_outputs(a, 7, ns, &pos, &dp, &col, &dc)) return nullptr;
+    float bounds[6] = {0, 0, 0, 0, 0, 0};
+    if (wo_globe_mesh(p, (int32_t)ns, tri, he, a.i32(3), a.i32(4), v, e, (float*)dp, (float*)dc, (int64_t)ns * 9, bounds)) return throw_wo(env, "globeMesh");
+    return globe_result(env, pos, col, bounds, dp != nullptr);
+}
+// globeMeshPlates(planet, triangles, halfedges, r_plate, plateSeeds Int32Array, plateColors Float32Array(3 per seed), r_elevation | null,
+//                 positions = true, colors = true) -> as globeMesh
+napi_value GlobeMeshPlates(napi_env env, napi_callback_info info) {
+    Args a(env, info);
+    int32_t *tri, *he; size_t ns;
+    if (!globe_sides(a, "globeMeshPlates", &tri, &he, &ns)) return nullptr;
+    wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    int32_t* plate = (int32_t*)opt_regions(a, 3, napi_int32_array, p, "r_plate", false); if (!a.ok) return nullptr;
+    size_t nSeeds = 0, nColors = 0; int32_t* seeds = nullptr; float* colors = nullptr;
+    if (a.has(4)) { seeds = (int32_t*)a.ta(4, napi_int32_array, &nSeeds); if (!a.ok) return nullptr; }
+    if (a.has(5)) { colors = (float*)a.ta(5, napi_float32_array, &nColors); if (!a.ok) return nullptr; }
+    if (seeds && colors && nColors != 3 * nSeeds) { napi_throw_range_error(env, nullptr, "globeMeshPlates: plateColors must hold three floats per plate seed"); return nullptr; }
+    float* e = (float*)opt_regions(a, 6, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    napi_value pos, col; void *dp, *dc;
+    if (!globe_outputs(a, 7, ns, &pos, &dp, &col, &dc)) return nullptr;
+    float bounds[6] = {0, 0, 0, 0, 0, 0};
+    if (wo_globe_mesh_plates(p, (int32_t)ns, tri, he, plate, (int32_t)nSeeds, seeds, colors, e, (float*)dp, (float*)dc, (int64_t)ns * 9, bounds)) return throw_wo(env, "globeMeshPlates");
+    return globe_result(env, pos, col, bounds, dp != nullptr);
+}
+// globeLines(planet, triangles, halfedges, kind 0 | 1, r_elevation | null, superPlates | null) -> Float32Array(segments * 6)
+napi_value GlobeLines(napi_env env, napi_callback_info info) {
+    Args a(env, info);
+    int32_t *tri, *he; size_t ns;
+    if (!globe_sides(a, "globeLines", &tri, &he, &ns)) return nullptr;
+    wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* e = (float*)opt_regions(a, 4, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    float* sp = (float*)opt_regions(a, 5, napi_float32_array, p, "superPlates", false); if (!a.ok) return nullptr;
+    const size_t room = ns / 2;
+    std::vector<float> seg(6 * room + 6);
+    int64_t count = 0;
+    if (wo_globe_lines(p, (int32_t)ns, tri, he, a.i32(3), e, sp, seg.data(), (int64_t)room, &count)) return throw_wo(env, "globeLines");
+    void* d; napi_value out = make_ta(env, napi_float32_array, (size_t)count * 6, 4, &d);
+    if (!out) return nullptr;
+    std::memcpy(d, seg.data(), (size_t)count * 24);
+    return out;
+}
+
 // ---- multi-GPU exchange over RCCL (include/worogen.h: wo_comm_*; one worker thread per GPU holds one communicator) -------
 void FinalizeComm(napi_env, void* data, void*) { wo_comm_destroy((wo_comm*)data); }
 napi_value CommUniqueId(napi_env env, napi_callback_info) {                   // () -> Uint8Array(128): rank 0 makes it, the host posts it to every worker
@@ -951,6 +1034,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"precipUpload", PrecipUpload}, {"computeTemperature", ComputeTemperature}, {"temperatureDownload", TemperatureDownload},
         {"temperatureUpload", TemperatureUpload}, {"classifyKoppen", ClassifyKoppen},
         {"mapRaster", MapRaster}, {"mapColor", MapColor}, {"mapFree", MapFree}, {"mapRasterCentered", MapRasterCentered}, {"mapColorLayer", MapColorLayer},
+        {"globeMesh", GlobeMesh}, {"globeMeshPlates", GlobeMeshPlates}, {"globeLines", GlobeLines},
         {"commUniqueId", CommUniqueId}, {"commCreate", CommCreate}, {"planetSetHalo", PlanetSetHalo},
         {"planetExchangeAllgather", PlanetExchangeAllgather}, {"planetExchangeNeighbors", PlanetExchangeNeighbors}, {"planetSetFloodExchange", PlanetSetFloodExchange},
     };

@@ -1,0 +1,367 @@
+"""The globe mesh on the device (csrc/globe.hip: wo_globe_mesh, wo_globe_mesh_plates, wo_globe_lines) against the host emulator of the
+same bodies (tests/emu_globe) in every word, every case twice: positions, winding, colours and bounds on meshes of several
+workgroups, of less than one, and mirrored; the colours-only call; the order-preserving compaction at the first and last side of a
+workgroup; the bounds with lone infinities and nothing but NaN; every view after the device's own climate chain; and the error
+answers of the C ABI."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import globe_common as GC
+import map_common as MC
+import map_layers_common as ML
+
+pytestmark = pytest.mark.gpu
+BLOCK = 256                                                   # sides per workgroup of the mesh and line kernels (csrc/device.h: WO_BLOCK)
+
+
+def _planet(mesh, xyz):
+    from planet_heightmap_generation_amd import terrain_post as TP
+    return TP.Planet(mesh, xyz)
+
+
+def _in_use():
+    from planet_heightmap_generation_amd import capi
+    d, h, n = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    assert capi.lib().wo_memory_in_use(C.byref(d), C.byref(h), C.byref(n)) == 0
+    return d.value, h.value
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def same(a, b):
+    return MC.same_bits(np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32))
+
+
+def _shape(name):
+    if name == "257":
+        mesh, xyz = GC.small_sphere(257)
+    else:
+        mesh, xyz = MC.golden_mesh("mesh_N10000_s1")
+        if name == "10k mirrored":
+            xyz = GC.mirrored(xyz)
+    return mesh, xyz
+
+
+# ---- 1. positions, winding, colours, bounds ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", ["10k", "257", "10k mirrored"])
+def test_mesh_equals_emulator(shape):
+    from planet_heightmap_generation_amd import globe_export as GE
+    mesh, xyz = _shape(shape)
+    tri, he = mesh.triangles, mesh.halfedges
+    if shape != "257":
+        assert tri.size == 60000 - 6 and tri.size % BLOCK != 0 and tri.size > 200 * BLOCK      # several workgroups, a partial last one
+    else:
+        assert tri.size < 6 * BLOCK
+    e = GC.rough_elevation(xyz, 11)
+    want_pos, sw = GC.emu_positions(xyz, e, tri, he)
+    want_col = GC.emu_view_colors("color", e, tri, mesh.adjOffset, mesh.adjList)
+    want_bounds = GC.emu_bounds(want_pos)
+    print(f"{shape}: {tri.size} sides, {int(sw.sum())} swapped, bounds {want_bounds.tolist()}")
+    pl = _planet(mesh, xyz)
+    try:
+        first = GE.build_mesh(pl, mesh, "color", r_elevation=e)
+        pl.upload(e)                                          # the resident field: the same bits
+        again = GE.build_mesh(pl, mesh, "color")
+        colours_only = GE.mesh_colors(pl, mesh, "color")
+        positions_only = GE._mesh_call(pl, mesh, "color", None, None, None, True, False)
+    finally:
+        pl.close()
+    bad = np.flatnonzero(~((bits(first["position"]) == bits(want_pos)) | (np.isnan(first["position"]) & np.isnan(want_pos))))
+    assert bad.size == 0, (bad.size, (bad[:8] // 9).tolist())
+    assert same(first["color"], want_col) and same(first["bounds"], want_bounds)
+    for k in ("position", "color", "bounds"):
+        assert np.array_equal(bits(again[k]), bits(first[k])), k                          # the second run's bits
+    assert np.array_equal(bits(colours_only), bits(first["color"]))
+    assert positions_only["color"] is None and np.array_equal(bits(positions_only["position"]), bits(first["position"])) and same(positions_only["bounds"], want_bounds)
+
+
+def test_direct_stores_give_the_staged_bits(monkeypatch):
+    """the other form of the mesh kernel (every lane stores its own nine floats) behind its test hook"""
+    from planet_heightmap_generation_amd import globe_export as GE
+    mesh, xyz = _shape("10k")
+    e = GC.rough_elevation(xyz, 11)
+    pl = _planet(mesh, xyz)
+    try:
+        staged = GE.build_mesh(pl, mesh, "heightmap", r_elevation=e)
+        monkeypatch.setenv("WO_TEST_HOOKS", "globe_direct_stores=1")
+        direct = GE.build_mesh(pl, mesh, "heightmap", r_elevation=e)
+    finally:
+        pl.close()
+    for k in ("position", "color", "bounds"):
+        assert np.array_equal(bits(direct[k]), bits(staged[k])), k
+
+
+# ---- 2. the compaction -----------------------------------------------------------------------------------------------------------
+def test_lines_and_the_compaction():
+    from planet_heightmap_generation_amd import globe_export as GE
+    mesh, xyz = _shape("10k")
+    tri, he = mesh.triangles, mesh.halfedges
+    n = mesh.numRegions
+    e = GC.rough_elevation(xyz, 11)
+    wire, sides = GC.emu_lines(GC.WIREFRAME, xyz, e, tri, he)
+    assert sides.size == tri.size // 2
+    fields = {}
+    fields["none"] = np.zeros(n, np.float32)
+    fields["none"][::2] = -0.0                                                          # -0 == +0
+    fields["every"] = np.arange(n, dtype=np.float32)
+    eligible = {"first eligible side": sides[0], "last eligible side": sides[-1],
+                "first eligible side of the second workgroup": sides[sides >= BLOCK][0], "last eligible side of the first workgroup": sides[sides < BLOCK][-1]}
+    assert eligible["last eligible side of the first workgroup"] < BLOCK <= eligible["first eligible side of the second workgroup"] < 2 * BLOCK
+    for what, s in eligible.items():                                                      # every side but s qualifies ...
+        f = np.arange(n, dtype=np.float32)
+        f[tri[he[s]]] = f[tri[s]]
+        fields[f"all but the {what}"] = f
+    nan = GC.sector_plates(xyz)
+    nan[n // 2], nan[7] = np.nan, -0.0
+    fields["a NaN cell"] = nan
+    pl = _planet(mesh, xyz)
+    try:
+        got_wire = GE.wireframe(pl, mesh, r_elevation=e)
+        assert same(got_wire, wire) and same(GE.wireframe(pl, mesh, r_elevation=e), got_wire)
+        for what, f in fields.items():
+            want, wsides = GC.emu_lines(GC.BORDERS, xyz, e, tri, he, f)
+            got = GE.super_plate_borders(pl, mesh, f, r_elevation=e)
+            print(f"{what}: {wsides.size} segments")
+            assert got.size == want.size and same(got, want), what
+            assert same(GE.super_plate_borders(pl, mesh, f, r_elevation=e), got), what
+            if what == "none":
+                assert got.size == 0
+            if what == "every":
+                assert got.size == wire.size and not same(got, wire)                     # the wireframe's sides at base 1.002
+            if what.startswith("all but"):
+                assert wsides.size == sides.size - 1 and eligible[what[len("all but the "):]] not in wsides
+        # one region against all the others (its few sides, wherever they lie); the room behind the count stays untouched
+        from planet_heightmap_generation_amd import capi
+        room = tri.size // 2
+        for what, s in eligible.items():
+            f = np.zeros(n, np.float32)
+            f[tri[s]] = 1.0
+            want, wsides = GC.emu_lines(GC.BORDERS, xyz, e, tri, he, f)
+            out = np.full(room * 6, np.float32(-7.0), np.float32)
+            count = C.c_int64(-1)
+            capi.check(capi.lib().wo_globe_lines(pl.handle, tri.size, capi.ptr(np.ascontiguousarray(tri, np.int32)), capi.ptr(np.ascontiguousarray(he, np.int32)), 1, capi.ptr(e),
+                                                 capi.ptr(f), capi.ptr(out), room, C.byref(count)), "globeLines")
+            assert count.value == wsides.size and same(out[: want.size], want) and np.all(out[want.size:] == np.float32(-7.0)), what
+        out = np.full(room * 6, np.float32(-7.0), np.float32)
+        count = C.c_int64(-1)
+        capi.check(capi.lib().wo_globe_lines(pl.handle, tri.size, capi.ptr(np.ascontiguousarray(tri, np.int32)), capi.ptr(np.ascontiguousarray(he, np.int32)), 1, capi.ptr(e),
+                                             capi.ptr(fields["none"]), capi.ptr(out), room, C.byref(count)), "globeLines")
+        assert count.value == 0 and np.all(out == np.float32(-7.0))                        # count 0, nothing written
+    finally:
+        pl.close()
+
+
+def test_exactly_one_side():
+    """Exactly one qualifying side, at the four places where the compaction's offsets change hands.  A field on the regions of a
+    real mesh cuts closed curves, never one edge; so the corners are renamed: every side starts at region 0 but the chosen one, which
+    starts at region 1 (the entry point checks ranges, not that the corners make a mesh), and sp is 0 everywhere but 1 at region 1."""
+    from planet_heightmap_generation_amd import globe_export as GE
+    mesh, xyz = _shape("10k")
+    tri, he = np.ascontiguousarray(mesh.triangles, np.int32), np.ascontiguousarray(mesh.halfedges, np.int32)
+    n = mesh.numRegions
+    e = GC.rough_elevation(xyz, 11)
+    _, sides = GC.emu_lines(GC.WIREFRAME, xyz, e, tri, he)
+    chosen = {"first": sides[0], "last": sides[-1], "first of the second workgroup": sides[sides >= BLOCK][0], "last of the first workgroup": sides[sides < BLOCK][-1]}
+    pl = _planet(mesh, xyz)
+    try:
+        for what, s in chosen.items():
+            # corners renamed so that every side starts at region 0 but side s, which starts at region 1: then sp[0] = 0, sp[1] = 1 makes
+            # sp[triangles[t]] != sp[triangles[halfedges[t]]] true for t = s and for the side whose partner is s; only s has s < partner
+            t2 = np.zeros_like(tri)
+            t2[s] = 1
+            f = np.zeros(n, np.float32)
+            f[1] = 1.0
+            want, wsides = GC.emu_lines(GC.BORDERS, xyz, e, t2, he, f)
+            assert wsides.tolist() == [int(s)], (what, wsides)
+            m2 = MC.Mesh(n, t2, he, mesh.adjOffset, mesh.adjList)
+            got = GE.super_plate_borders(pl, m2, f, r_elevation=e)
+            assert got.size == 6 and same(got, want), what
+            assert same(GE.super_plate_borders(pl, m2, f, r_elevation=e), got), what
+    finally:
+        pl.close()
+
+
+# ---- 3. the bounds -----------------------------------------------------------------------------------------------------------------
+def test_bounds_all_nan_and_lone_infinities():
+    from planet_heightmap_generation_amd import globe_export as GE
+    mesh, xyz = _shape("10k")
+    tri, he = mesh.triangles, mesh.halfedges
+    n = mesh.numRegions
+    pl = _planet(mesh, xyz)
+    try:
+        got = GE.build_mesh(pl, mesh, "color", r_elevation=np.full(n, np.nan, np.float32))
+        assert np.isnan(got["position"]).all() and same(got["bounds"], np.zeros(6, np.float32))
+        base = MC.fbm_like(xyz, 2)
+        for cell in (0, 63, ((n - 1) // 64) * 64, n - 1):
+            for v in (np.inf, -np.inf):
+                e = base.copy()
+                e[cell] = v
+                pos, _ = GC.emu_positions(xyz, e, tri, he)
+                want = GC.emu_bounds(pos)
+                got = GE.build_mesh(pl, mesh, "color", r_elevation=e)
+                assert np.isinf(want).any() and same(got["bounds"], want) and same(got["bounds"], GC.numpy_bounds(got["position"])), (cell, v, got["bounds"], want)
+    finally:
+        pl.close()
+
+
+# ---- 4. every view after the device's own climate chain ------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def imported():
+    """importHeightmap's fixture left resident, then the climate chain on the device"""
+    import import_common as IC
+    from planet_heightmap_generation_amd import heightmap_import as HI, sphere_mesh as SM
+    g = IC.golden()
+    imp = IC.meta(g)["import"]
+    img = g["img_512x256"]
+    keep = []
+    d = HI.import_heightmap(imp["N"], imp["jitter"], img, img.shape[1], img.shape[0], imp["params"], seed=imp["seed"], planet_out=keep)
+    pl = keep[0]
+    mesh = SM.sphere_mesh_from_triangles(d["triangles"], d["halfedges"], d["numRegions"])
+    koppen = MC.climate_chain(pl, d["r_plate"], d["plateIsOcean"], d["seed"])
+    yield dict(planet=pl, mesh=mesh, xyz=d["r_xyz"], e=pl.download(), koppen=np.asarray(koppen, np.uint8), d=d)
+    pl.close()
+
+
+def _blocks():
+    from planet_heightmap_generation_amd import ocean, precipitation, temperature, wind
+    return dict(wind=wind, ocean=ocean, precip=precipitation, temperature=temperature)
+
+
+def test_views_after_the_climate_chain(imported):
+    """The five types, the thirteen layers, `debug` and `plates` word for word; the two ocean-current layers may differ where ocml's
+    pow is not glibc's, in at most max(8, N / 10^4) regions, each component by one f32 ulp (DESIGN section 3's cap)."""
+    from planet_heightmap_generation_amd import globe_export as GE
+    I = imported
+    pl, mesh, e, n = I["planet"], I["mesh"], I["e"], I["mesh"].numRegions
+    tri = np.ascontiguousarray(mesh.triangles, np.int32)
+    blocks = _blocks()
+    cap = max(8, n // 10000)
+    full = GE.build_mesh(pl, mesh, "color")
+    want_pos, _ = GC.emu_positions(I["xyz"], e, tri, mesh.halfedges)
+    assert same(full["position"], want_pos) and same(full["bounds"], GC.emu_bounds(want_pos))
+    seen = set()
+    for view in GE.TYPE_VIEWS:
+        got = GE.mesh_colors(pl, mesh, view)
+        want = GC.emu_view_colors(view, e, tri, mesh.adjOffset, mesh.adjList, koppen=I["koppen"])
+        assert same(got, want), view
+        assert same(GE.mesh_colors(pl, mesh, view), got), view
+        seen.add(got.tobytes())
+    assert same(full["color"], GC.emu_view_colors("color", e, tri, mesh.adjOffset, mesh.adjList))
+    for name in ML.NAMED:
+        block, keys = ML.SOURCE[name]
+        f = [blocks[block].download(pl, k) for k in keys]
+        a, b = f[0], (f[1] if len(f) > 1 else None)
+        got = GE.mesh_colors(pl, mesh, name)
+        want = GC.emu_view_colors(name, e, tri, mesh.adjOffset, mesh.adjList, a=a, b=b)
+        assert same(GE.mesh_colors(pl, mesh, name), got), name
+        seen.add(got.tobytes())
+        if name not in ML.OCEAN_CURRENT:
+            assert same(got, want), name
+            continue
+        d = ML.ulp_distance(got, want).reshape(-1, 9)
+        regions = np.unique(tri[(d != 0).any(axis=1)])
+        print(f"{name}: {regions.size} regions differ from the emulator (cap {cap}), largest distance {int(d.max())} ulp")
+        assert regions.size <= cap and int(d.max()) <= 1, (name, regions[:12], int(d.max()))
+    v = MC.fbm_like(I["xyz"], 9)
+    got = GE.mesh_colors(pl, mesh, "debug", values=v)
+    assert same(got, GC.emu_view_colors("debug", e, tri, mesh.adjOffset, mesh.adjList, a=v)) and same(GE.mesh_colors(pl, mesh, "debug", values=v), got)
+    seen.add(got.tobytes())
+    seeds = [int(s) for s in I["d"]["plateSeeds"]]
+    table = GE.compute_plate_colors(seeds[:-1], I["d"]["plateIsOcean"])                     # the last plate has no colour: the fallback
+    plates = dict(r_plate=I["d"]["r_plate"], plateSeeds=seeds[:-1], plateColors=table)
+    got = GE.mesh_colors(pl, mesh, "plates", plates=plates)
+    want = GC.emu_colors(tri, GC.emu_plate_colors(I["d"]["r_plate"], seeds[:-1], table))
+    assert same(got, want) and same(GE.mesh_colors(pl, mesh, "plates", plates=plates), got)
+    assert (bits(got.reshape(-1, 3)) == bits(np.float32(0.3))).all(axis=1).any()
+    seen.add(got.tobytes())
+    assert len(seen) == len(GE.TYPE_VIEWS) + len(ML.NAMED) + 2                               # twenty different colourings
+
+
+# ---- 5. the error answers ------------------------------------------------------------------------------------------------------------
+def test_refusals_allocate_nothing_and_leave_the_planet_usable():
+    from planet_heightmap_generation_amd import capi, globe_export as GE
+    L = capi.lib()
+    mesh, xyz = GC.small_sphere(257)
+    tri, he = np.ascontiguousarray(mesh.triangles, np.int32), np.ascontiguousarray(mesh.halfedges, np.int32)
+    ns, n = tri.size, mesh.numRegions
+    pl = _planet(mesh, xyz)
+    pos, col, bounds = np.empty(ns * 9, np.float32), np.empty(ns * 9, np.float32), np.zeros(6, np.float32)
+    seg, count = np.empty(ns // 2 * 6, np.float32), C.c_int64(0)
+    v = MC.fbm_like(xyz, 5)
+    plate, seeds, table = np.zeros(n, np.int32), np.array([0, 5], np.int32), np.zeros(6, np.float32)
+    layer = ML.LAYERS.index
+
+    def refused(rc, *want):
+        msg = capi.last_error()
+        print(f"    status {rc}: {msg}")
+        assert rc == 1 and all(w in msg for w in want), (rc, msg, want)
+
+    def mesh_call(source, ident, values=None, t=tri, h=he, sides=ns, p=pos, c=col, floats=ns * 9):
+        return L.wo_globe_mesh(pl.handle, sides, capi.ptr(t), capi.ptr(h), source, ident, capi.ptr(values), None, capi.ptr(p), capi.ptr(c), floats, capi.ptr(bounds))
+
+    def plates_call(rp=plate, k=2, s=seeds, tb=table, c=col):
+        return L.wo_globe_mesh_plates(pl.handle, ns, capi.ptr(tri), capi.ptr(he), capi.ptr(rp), k, capi.ptr(s), capi.ptr(tb), None, capi.ptr(pos), capi.ptr(c), ns * 9, capi.ptr(bounds))
+
+    def lines_call(kind, sp=None, room=ns // 2, t=tri, h=he):
+        return L.wo_globe_lines(pl.handle, ns, capi.ptr(t), capi.ptr(h), kind, None, capi.ptr(sp), capi.ptr(seg), room, C.byref(count))
+
+    try:
+        own = _in_use()
+        # bad topology
+        bad_he, bad_tri = he.copy(), tri.copy()
+        bad_he[7], bad_tri[9] = ns, n
+        refused(mesh_call(0, 0, h=bad_he), "wo_globe_mesh", "half-edge out of range", f"halfedges[7] = {ns}")
+        refused(mesh_call(0, 0, t=bad_tri), "wo_globe_mesh", "corner out of range", f"triangles[9] = {n}")
+        refused(mesh_call(0, 0, sides=ns - 1, floats=(ns - 1) * 9), "wo_globe_mesh", f"numSides is {ns - 1}")
+        refused(lines_call(0, h=bad_he), "wo_globe_lines", "half-edge out of range")
+        refused(L.wo_globe_mesh(None, ns, capi.ptr(tri), capi.ptr(he), 0, 0, None, None, capi.ptr(pos), capi.ptr(col), ns * 9, None), "wo_globe_mesh")
+        # source, type, layer, landmask
+        refused(mesh_call(2, 0), "wo_globe_mesh", "unknown colour source 2")
+        refused(mesh_call(-1, 0), "wo_globe_mesh", "unknown colour source -1")
+        refused(mesh_call(0, 6), "wo_globe_mesh", "unknown map type 6")
+        refused(mesh_call(0, 3), "wo_globe_mesh", "landmask", "buildMesh has no such branch")
+        for bad in (-1, len(ML.LAYERS)):
+            refused(mesh_call(1, bad), "wo_globe_mesh", f"unknown map layer {bad}")
+        # the blocks
+        for t in (4, 5):
+            refused(mesh_call(0, t), "wo_globe_mesh", "no Koppen result", "wo_classify_koppen first")
+        nouns = dict(wind=("no wind result", "wo_compute_wind first"), ocean=("no ocean result", "wo_compute_ocean_currents first"),
+                     precip=("no precipitation result", "wo_compute_precipitation first"), temperature=("no temperature result", "wo_compute_temperature first"))
+        for name in ML.NAMED:
+            refused(mesh_call(1, layer(name)), "wo_globe_mesh", *nouns[ML.SOURCE[name][0]])
+        refused(mesh_call(1, layer("debug")), "wo_globe_mesh", "WO_MAP_LAYER_DEBUG", "values is NULL")
+        for name in ML.OCEAN_CURRENT:
+            refused(mesh_call(1, layer(name), values=v), "wo_globe_mesh", "ocean-current", "values must be NULL", "wo_ocean_upload")
+        # plates without a table
+        refused(plates_call(s=None), "wo_globe_mesh_plates", "colour table", "plateSeeds is NULL")
+        refused(plates_call(tb=None), "wo_globe_mesh_plates", "colour table", "plateColors is NULL")
+        refused(plates_call(rp=None), "wo_globe_mesh_plates", "r_plate", "NULL")
+        refused(plates_call(s=np.array([0, n], np.int32)), "wo_globe_mesh_plates", f"plateSeeds[1] = {n}")
+        # sizes
+        for floats in (ns * 9 - 1, ns * 9 + 9, 0):
+            refused(mesh_call(0, 0, floats=floats), "wo_globe_mesh", f"takes {ns * 9} floats", f"outFloats is {floats}")
+        refused(mesh_call(0, 0, p=None, c=None), "wo_globe_mesh", "both NULL")
+        refused(lines_call(0, room=ns // 2 - 1), "wo_globe_lines", f"can give {ns // 2} segments", f"capacity is {ns // 2 - 1}")
+        refused(lines_call(1), "wo_globe_lines", "superPlates is NULL")
+        refused(lines_call(0, sp=v), "wo_globe_lines", "superPlates must be NULL")
+        refused(lines_call(2, sp=v), "wo_globe_lines", "unknown line kind 2")
+        assert _in_use() == own                                                         # nothing was allocated by a refused call
+        with pytest.raises(ValueError, match="landmask"):
+            GE.build_mesh(pl, mesh, "landmask")
+        with pytest.raises(ValueError, match="unknown globe view 'stress'"):
+            GE.build_mesh(pl, mesh, "stress")
+        with pytest.raises(capi.WorogenError, match="no wind result"):
+            GE.mesh_colors(pl, mesh, "continentality")
+        # after all of it the planet builds what the emulator builds, and every temporary is gone again
+        e = GC.rough_elevation(xyz, 3)
+        got = GE.build_mesh(pl, mesh, "heightmap", r_elevation=e)
+        want_pos, _ = GC.emu_positions(xyz, e, tri, he)
+        assert same(got["position"], want_pos) and same(got["color"], GC.emu_view_colors("heightmap", e, tri, mesh.adjOffset, mesh.adjList))
+        assert same(GE.wireframe(pl, mesh, r_elevation=e), GC.emu_lines(GC.WIREFRAME, xyz, e, tri, he)[0])
+        assert _in_use() == own
+    finally:
+        pl.close()
