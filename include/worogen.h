@@ -551,6 +551,30 @@ int wo_globe_mesh_plates(wo_planet* p, int32_t numSides, const int32_t* triangle
 int wo_globe_lines(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t kind,
                    const float* r_elevation, const float* superPlates, float* segmentsOut, int64_t capacity, int64_t* count);
 
+/* ------------------------------------------------ arrow overlays (js/planet-mesh.js) ---------- */
+/* buildWindArrows, buildOceanCurrentArrows                                        js/planet-mesh.js:1289-1465, :1545-1720
+ *   The arrows the reference draws over its wind and ocean-current views, as its own Float32Arrays bit for bit (csrc/overlay.hip;
+ *   the bodies and the whole contract are in csrc/overlay_ops.h).  The regions are binned into 60 x 120 cells of 3 x 3 degrees; per
+ *   cell the region closest to its centre is kept, as the reference's loop over its f32 `gridDist2` leaves it.
+ *   wo_overlay_bins gives those regions, WO_OVERLAY_BINS int32 in gridRegionsOut, -1 for an empty cell, from the planet's resident
+ *   positions.  skipLand 1 is the ocean form: regions with r_elevation > 0 take part in no cell (a NaN does); r_elevation is
+ *   numRegions floats, NULL means the resident field, and it is not read with skipLand 0.
+ *   wo_overlay_arrows gives the arrows of kind WO_OVERLAY_WIND (the season's r_wind_east_* and r_wind_north_* of the wind block;
+ *   cells whose speed sqrt(e * e + n * n) is below 0.001 are dropped) or WO_OVERLAY_OCEAN (the season's r_ocean_current_east_*,
+ *   r_ocean_current_north_*, r_ocean_speed_* and r_ocean_warmth_* of the ocean block, skipLand binning with r_elevation; cells
+ *   with a speed below 0.01 are dropped), season 0 summer or 1 winter, in ascending cell order: per arrow 18 floats (the shaft and
+ *   the two wings of its head, two vertices each) in globePos and globeCol, and the map form around the centre meridian centerLon
+ *   (NaN counts as 0) in mapPos and mapCol.  The fields are computed or uploaded (wo_wind_upload, wo_ocean_upload): without them
+ *   the call fails with "no wind result" / "no ocean result".  Any of the four outputs may be NULL; with one given,
+ *   capacityArrows, the room of each in arrows, must be at least WO_OVERLAY_BINS: the count is not known before the call has run,
+ *   and a refusal comes before anything is allocated.  *count receives the number of arrows, and nothing is written behind them.
+ *   A refused call returns 1, names the offending value and allocates nothing. */
+enum { WO_OVERLAY_WIND = 0, WO_OVERLAY_OCEAN = 1 };
+enum { WO_OVERLAY_BINS = 7200 };
+int wo_overlay_bins(wo_planet* p, int32_t skipLand, const float* r_elevation, int32_t* gridRegionsOut);
+int wo_overlay_arrows(wo_planet* p, int32_t kind, int32_t season, double centerLon, const float* r_elevation, float* globePos,
+                      float* globeCol, float* mapPos, float* mapCol, int64_t capacityArrows, int64_t* count);
+
 /* ------------------------------------------------ device-resident variants -------------------- */
 /* The "reapply" pattern (js/planet-worker.js:341-440): fields stay in HBM, only scalars arrive.
  * wo_planet_upload sets the resident r_elevation (and r_isOcean when not NULL); the *_resident

@@ -94,6 +94,8 @@ SIGNATURES = {
     "wo_globe_mesh": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _c_i32, _p, _p, _p, _p, _c_i64, _p]),
     "wo_globe_mesh_plates": (C.c_int, [_p, _c_i32, _p, _p, _p, _c_i32, _p, _p, _p, _p, _p, _c_i64, _p]),
     "wo_globe_lines": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _p, _p, _p, _c_i64, _p]),
+    "wo_overlay_bins": (C.c_int, [_p, _c_i32, _p, _p]),
+    "wo_overlay_arrows": (C.c_int, [_p, _c_i32, _c_i32, _c_f64, _p, _p, _p, _p, _p, _c_i64, _p]),
     "wo_planet_upload": (C.c_int, [_p, _p, _p]),
     "wo_planet_download": (C.c_int, [_p, _p]),
     "wo_planet_set_halo": (C.c_int, [_p, _p, _c_i32, _p, _c_i32]),

@@ -58,7 +58,8 @@ enum Family : int {
     FAM_FLOOD_EVAL, FAM_FLOOD_APPLY, FAM_FLOOD_MISC, FAM_CLIMATE, FAM_BASIN, FAM_BASIN_SORT, FAM_SOLVE_BASIN, FAM_FLOW_TILES, FAM_MISC, FAM_EVENT_PAIR, FAM_EVENT_PAIR_NOOP, FAM_EVENT_PAIR_NOOP2,
     FAM_MAP_LONLAT, FAM_MAP_FILL, FAM_MAP_SIDES, FAM_MAP_BIG_BOXES, FAM_MAP_RESOLVE, FAM_MAP_REGION_COLORS, FAM_MAP_PIXELS,
     FAM_MAP_RANGE, FAM_MAP_LAYER_COLORS,
-    FAM_GLOBE_TABLES, FAM_GLOBE_REGION_COLORS, FAM_GLOBE_RANGE, FAM_GLOBE_MESH, FAM_GLOBE_LINE_COUNT, FAM_GLOBE_LINE_SCAN, FAM_GLOBE_LINE_WRITE, FAM_COUNT
+    FAM_GLOBE_TABLES, FAM_GLOBE_REGION_COLORS, FAM_GLOBE_RANGE, FAM_GLOBE_MESH, FAM_GLOBE_LINE_COUNT, FAM_GLOBE_LINE_SCAN, FAM_GLOBE_LINE_WRITE,
+    FAM_OVERLAY_BINS, FAM_OVERLAY_ARROWS, FAM_COUNT
 };
 extern const char* const kFamilyNames[FAM_COUNT];
 
@@ -104,6 +105,7 @@ struct Options {
     bool oceanSplitSmooth = false;     // ocean_split_smooth=1     ocean currents: the masked smoothing field by field instead of one interleaved gather (the A/B of DESIGN section 8.3)
     bool tempSplitDiffuse = false;     // temp_split_diffuse=1     temperature: diffuseOceanWarmth season by season with the single-field kernels instead of one float2 gather
     bool globeDirectStores = false;    // globe_direct_stores=1    globe mesh: every lane stores its own nine floats instead of staging the workgroup's in LDS (the A/B of DESIGN section 8.11)
+    bool overlayPrecheck = false;      // overlay_precheck=1       arrow overlays: a candidate reads the bin's key first and sends its atomicMin only when its own is smaller (the A/B of DESIGN section 8.12)
     static Options from_env();
 };
 }  // namespace wo

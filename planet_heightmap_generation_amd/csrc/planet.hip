@@ -123,6 +123,7 @@ Options Options::from_env() {
     o.oceanSplitSmooth = test_hook_int("ocean_split_smooth", 0) != 0;
     o.tempSplitDiffuse = test_hook_int("temp_split_diffuse", 0) != 0;
     o.globeDirectStores = test_hook_int("globe_direct_stores", 0) != 0;
+    o.overlayPrecheck = test_hook_int("overlay_precheck", 0) != 0;
     return o;
 }
 

@@ -14,7 +14,8 @@ const char* const kFamilyNames[FAM_COUNT] = {
     "glac_index", "ice_receivers", "ice_round", "carve_setup", "carve_round", "moraine_fjord", "glacial_blend", "solve_patch", "elev_collisions", "elev_uplift_fused", "plate_grid", "plate_project", "smooth_field", "flood_eval", "flood_apply", "flood_misc", "climate_sweeps", "basin_layout", "basin_sort", "solve_basin", "flow_tiles", "misc", "event_pair_empty", "event_pair_noop_kernel", "event_pair_two_noop_kernels",
     "map_lonlat", "map_fill", "map_sides", "map_big_boxes", "map_resolve", "map_region_colors", "map_pixels",
     "map_range", "map_layer_colors",
-    "globe_tables", "globe_region_colors", "globe_range", "globe_mesh", "globe_line_count", "globe_line_scan", "globe_line_write"};
+    "globe_tables", "globe_region_colors", "globe_range", "globe_mesh", "globe_line_count", "globe_line_scan", "globe_line_write",
+    "overlay_bins", "overlay_arrows"};
 
 hipEvent_t profile_event(wo_planet* p) {
     if (!p->eventPool.empty()) { hipEvent_t e = p->eventPool.back(); p->eventPool.pop_back(); return e; }

@@ -7,6 +7,7 @@
 import addon, { planetFor } from './native.js';
 import { MAP_TYPES, MAP_LAYERS } from './map-export.js';
 import { globeFilename, encodeGlb } from './globe-glb.js';
+import { windArrowsOnPlanet, oceanCurrentArrowsOnPlanet, itczLine, globeGrid } from './overlay-export.js';
 
 export const GLOBE_PLATES = 'plates';
 export const GLOBE_TYPE_VIEWS = MAP_TYPES.filter((t) => t !== 'landmask');
@@ -52,17 +53,25 @@ export function buildWireframe(mesh, r_xyz, r_elevation) { return wireframeOnPla
 // updateSuperPlateBorders(mesh, r_xyz, r_elevation, superPlates) -> Float32Array(segments * 6): the globe form
 export function updateSuperPlateBorders(mesh, r_xyz, r_elevation, superPlates) { return superPlateBordersOnPlanet(planetFor(mesh, r_xyz), mesh.triangles, mesh.halfedges, r_elevation, superPlates); }
 
-// the globe in one view on a planet handle: { filename, position, color, bounds[, wireframe][, superPlateBorders][, glb] }
+// the globe in one view on a planet handle: { filename, position, color, bounds[, wireframe][, superPlateBorders][, windArrows][, oceanCurrentArrows][, itcz][, grid][, glb] }
 export function exportGlobeOnPlanet(planet, triangles, halfedges, r_elevation, view, seed, opts) {
     const o = opts || {};
     const res = buildMeshOnPlanet(planet, triangles, halfedges, r_elevation, view, o);
     res.filename = globeFilename(view || 'color', seed);
     if (o.wireframe) res.wireframe = wireframeOnPlanet(planet, triangles, halfedges, r_elevation);
     if (o.superPlates) res.superPlateBorders = superPlateBordersOnPlanet(planet, triangles, halfedges, r_elevation, o.superPlates);
-    if (o.glb !== false) res.glb = encodeGlb(res, { wireframe: res.wireframe, superPlateBorders: res.superPlateBorders });
+    // the overlays (js/overlay-export.js): windArrows, oceanCurrentArrows: 'summer' | 'winter'; itcz: { itczLons, itczLats } of the season; grid: degrees
+    if (o.windArrows) res.windArrows = windArrowsOnPlanet(planet, o.windArrows, 0).globe;
+    if (o.oceanCurrentArrows) res.oceanCurrentArrows = oceanCurrentArrowsOnPlanet(planet, o.oceanCurrentArrows, 0, r_elevation).globe;
+    if (o.itcz) res.itcz = itczLine(o.itcz.itczLons, o.itcz.itczLats).globe;
+    if (o.grid !== undefined && o.grid !== null) res.grid = globeGrid(o.grid);
+    if (o.glb !== false) {
+        res.glb = encodeGlb(res, { wireframe: res.wireframe, superPlateBorders: res.superPlateBorders, windArrows: res.windArrows, oceanCurrentArrows: res.oceanCurrentArrows,
+                                   itcz: res.itcz, grid: res.grid });
+    }
     return res;
 }
-// exportGlobe(mesh, r_xyz, r_elevation, view, seed, { values, plates, wireframe, superPlates, glb })
+// exportGlobe(mesh, r_xyz, r_elevation, view, seed, { values, plates, wireframe, superPlates, windArrows, oceanCurrentArrows, itcz, grid, glb })
 export function exportGlobe(mesh, r_xyz, r_elevation, view, seed, opts) {
     return exportGlobeOnPlanet(planetFor(mesh, r_xyz), mesh.triangles, mesh.halfedges, r_elevation, view, seed, opts);
 }

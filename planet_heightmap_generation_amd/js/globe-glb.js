@@ -3,6 +3,11 @@
 // the opacities of the reference's two black line materials (:792, :573)
 export const LINE_OPACITY = { wireframe: 0.12, superPlateBorders: 0.55 };
 export const GLB_MAX_BYTES = 0xFFFFFFFF;                    // the container's lengths are uint32
+// how the reference's materials draw the overlays (:1474, :1516, :474): the arrows by vertex colour at opacity 0.6, the ITCZ line
+// 0x00ff88 opaque, the grid white at 0.12
+export const ARROW_OPACITY = 0.6;
+export const ITCZ_COLOR = [0, 1, 0x88 / 255];
+export const GRID_OPACITY = 0.12;
 
 // ours: the reference exports no globe
 export function globeFilename(view, seed) { return `orogen-globe-${view}-${seed}.glb`; }
@@ -59,31 +64,60 @@ function vertexBounds(a) {                                  // min and max per a
     return [0, 1, 2].map((k) => (seen[k] ? lo[k] : 0)).concat([0, 1, 2].map((k) => (seen[k] ? hi[k] : 0)));
 }
 
-// encodeGlb({ position, color, bounds }, { wireframe, superPlateBorders, name }) -> Uint8Array (the file's bytes).  One buffer, one mesh: a
-// TRIANGLES primitive with POSITION (min / max from bounds) and COLOR_0, both f32 VEC3 and linear; its material the default
-// metallic-roughness one with metallic 0 and roughness 1 (our decision: the reference's Lambert shader and its normals are not
-// offered); a LINES primitive with a black material at the reference's opacity per line set.
+// an overlay as encodeGlb takes it: the result of overlay-export.js (its globe form is taken) or the globe form itself
+function overlayPart(v, what) {
+    if (v && !(v instanceof Float32Array) && v.globe !== undefined) v = v.globe;
+    let pos = v, col = null;
+    if (!(v instanceof Float32Array)) {
+        pos = v.position; col = v.color;
+        if (!(pos instanceof Float32Array) || !(col instanceof Float32Array)) throw new TypeError(`${what} takes { position, color } as Float32Arrays`);
+        if (pos.length !== col.length) throw new RangeError(`${what} has ${pos.length} floats of positions and ${col.length} of colours`);
+    }
+    if (pos.length % 6) throw new RangeError(`${what} has ${pos.length} floats, no multiple of 6`);
+    return [pos, col];
+}
+
+// encodeGlb({ position, color, bounds }, { wireframe, superPlateBorders, name, windArrows, oceanCurrentArrows, itcz, grid }) -> Uint8Array (the
+// file's bytes).  One buffer, one mesh: a TRIANGLES primitive with POSITION (min / max from bounds) and COLOR_0, both f32 VEC3 and
+// linear; its material the default metallic-roughness one with metallic 0 and roughness 1 (our decision: the reference's Lambert
+// shader and its normals are not offered); a LINES primitive with a black material at the reference's opacity per line set.  The
+// overlays of overlay-export.js follow as further LINES primitives under unlit materials (KHR_materials_unlit, named only when one
+// of them is there): windArrows and oceanCurrentArrows with COLOR_0 at the reference's opacity 0.6, itcz in 0x00ff88 (the hex
+// channels over 255, as glTF takes a linear factor: our decision), grid white at 0.12; each is the globe form, or a result that has
+// one.  Without them the bytes are what they were before the overlays existed.
 export function encodeGlb(mesh, opts) {
     const o = opts || {}, { position, color, bounds } = mesh;
     if (!(position instanceof Float32Array) || !(color instanceof Float32Array) || !(bounds instanceof Float32Array)) throw new TypeError("encodeGlb needs position, color and bounds (buildMesh's result)");
     if (position.length !== color.length || position.length % 9) throw new RangeError(`position has ${position.length} floats and color ${color.length}: both must hold numSides * 9`);
     const lines = [['wireframe', o.wireframe], ['superPlateBorders', o.superPlateBorders]].filter(([, a]) => a && a.length);
     for (const [k, a] of lines) if (a.length % 6) throw new RangeError(`${k} has ${a.length} floats, no multiple of 6`);
+    const white = [1, 1, 1], overlays = [];                 // [name, positions, colours or null, base colour factor]
+    for (const [k, v, factor] of [['windArrows', o.windArrows, white.concat([ARROW_OPACITY])], ['oceanCurrentArrows', o.oceanCurrentArrows, white.concat([ARROW_OPACITY])],
+                                  ['itcz', o.itcz, ITCZ_COLOR.concat([1])], ['grid', o.grid, white.concat([GRID_OPACITY])]]) {
+        if (v === undefined || v === null) continue;
+        const [pos, col] = overlayPart(v, k);
+        if ((col === null) === k.endsWith('Arrows')) throw new TypeError(`${k} takes ` + (col === null ? '{ position, color }' : 'positions alone'));
+        if (pos.length) overlays.push([k, pos, col, factor]);
+    }
     const arrays = [position, color].concat(lines.map(([, a]) => a));
+    for (const [, pos, col] of overlays) { arrays.push(pos); if (col) arrays.push(col); }
     const binary = arrays.reduce((n, a) => n + a.length * 4, 0);
     if (binary + 65536 > GLB_MAX_BYTES) {
         throw new RangeError(`the globe's buffers take ${binary} bytes, more than a binary glTF file can hold (its lengths are uint32: ${GLB_MAX_BYTES} bytes); chunked export is not offered`);
     }
-    const limits = [Array.from(bounds)].concat(lines.map(([, a]) => vertexBounds(a)));
-    ['the mesh'].concat(lines.map(([k]) => k)).forEach((what, i) => {
-        if (!limits[i].every(Number.isFinite)) throw new RangeError(`the bounds of ${what} are not finite (${limits[i]}): glTF's JSON cannot hold them`);
+    // per array its bounds (POSITION accessors) or null (COLOR_0 accessors)
+    const limits = [Array.from(bounds), null].concat(lines.map(([, a]) => vertexBounds(a)));
+    const named = ['the mesh', null].concat(lines.map(([k]) => k));
+    for (const [k, pos, col] of overlays) { limits.push(vertexBounds(pos)); named.push(k); if (col) { limits.push(null); named.push(null); } }
+    named.forEach((what, i) => {
+        if (limits[i] && !limits[i].every(Number.isFinite)) throw new RangeError(`the bounds of ${what} are not finite (${limits[i]}): glTF's JSON cannot hold them`);
     });
     const views = [], accessors = [];
     let offset = 0;
     arrays.forEach((a, i) => {
         views.push({ buffer: 0, byteOffset: offset, byteLength: a.length * 4, target: 34962 });
         const acc = { bufferView: i, componentType: 5126, count: a.length / 3, type: 'VEC3' };
-        if (i !== 1) { const b = limits[i === 0 ? 0 : i - 1]; acc.min = b.slice(0, 3); acc.max = b.slice(3); }
+        if (limits[i]) { acc.min = limits[i].slice(0, 3); acc.max = limits[i].slice(3); }
         accessors.push(acc);
         offset += a.length * 4;
     });
@@ -94,8 +128,19 @@ export function encodeGlb(mesh, opts) {
         materials.push({ name: k, pbrMetallicRoughness: { baseColorFactor: [0, 0, 0, LINE_OPACITY[k]], metallicFactor: 0, roughnessFactor: 1 }, alphaMode: 'BLEND' });
         primitives.push({ attributes: { POSITION: 2 + j }, mode: 1, material: 1 + j, extras: { name: k } });
     });
-    const doc = { asset: { version: '2.0', generator: 'planet_heightmap_generation_amd' }, scene: 0, scenes: [{ nodes: [0] }], nodes: [{ mesh: 0, name }],
-                  meshes: [{ name, primitives }], materials, buffers: [{ byteLength: binary }], bufferViews: views, accessors };
+    let at0 = 2 + lines.length;
+    for (const [k, , col, factor] of overlays) {
+        const m = { name: k, pbrMetallicRoughness: { baseColorFactor: factor, metallicFactor: 0, roughnessFactor: 1 } };
+        if (factor[3] !== 1) m.alphaMode = 'BLEND';
+        m.extensions = { KHR_materials_unlit: {} };
+        materials.push(m);
+        primitives.push({ attributes: col ? { POSITION: at0, COLOR_0: at0 + 1 } : { POSITION: at0 }, mode: 1, material: materials.length - 1, extras: { name: k } });
+        at0 += col ? 2 : 1;
+    }
+    const doc = { asset: { version: '2.0', generator: 'planet_heightmap_generation_amd' } };
+    if (overlays.length) doc.extensionsUsed = ['KHR_materials_unlit'];
+    Object.assign(doc, { scene: 0, scenes: [{ nodes: [0] }], nodes: [{ mesh: 0, name }],
+                         meshes: [{ name, primitives }], materials, buffers: [{ byteLength: binary }], bufferViews: views, accessors });
     let text = Buffer.from(JSON.stringify(doc), 'utf8');
     if (text.length % 4) text = Buffer.concat([text, Buffer.alloc(4 - text.length % 4, 0x20)]);
     const pad = (4 - binary % 4) % 4, total = 12 + 8 + text.length + 8 + binary + pad;

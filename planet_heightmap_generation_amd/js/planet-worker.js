@@ -76,7 +76,7 @@
 //                  `centerLon` (radians, within [-pi, pi]) draws the map around that meridian.  Progress then counts types + layers.
 //                  -> { type: 'exportDone', width, height, maps: [{ type, filename, rgba, png? }],
 //                       _exportTiming: { raster, color, encode, workerTotal } }, the buffers transferred
-//   cmd 'exportGlobe' { view?, layer?, plates?, wireframe?, superPlateBorders?, glb? }   (js/planet-mesh.js:620-836, :533-576)
+//   cmd 'exportGlobe' { view?, layer?, plates?, wireframe?, superPlateBorders?, glb?, windArrows?, oceanCurrentArrows?, itcz?, grid? }   (js/planet-mesh.js:620-836, :533-576)
 //                  the globe mesh three.js would draw, of the planet's current elevation: one displaced triangle per side, nine floats
 //                  of positions and nine of colours each, built on the device (js/globe-export.js).  `view`: color (the default),
 //                  heightmap, landheightmap, biome or koppen; `layer`: a layer as for exportMap, a climate layer from the planet's
@@ -84,9 +84,20 @@
 //                  plateSeeds and plateIsOcean, needs r_plate).  `wireframe` adds the Voronoi wireframe, `superPlateBorders` the
 //                  borders of the retained debugLayers.superPlates (true) or of a Float32Array of the caller's.  With `glb` the answer carries the binary glTF file of all of it
 //                  instead of the arrays.  Needs what exportMap needs of the retained state and answers as it does without it.
+//                  `windArrows`, `oceanCurrentArrows`, `itcz`: 'summer' | 'winter', `grid`: degrees add the globe form of that overlay (see
+//                  exportOverlays) as arrays (arrows: { position, color }) or as LINES primitives of the GLB.
 //                  Progress: `Building globe...` at 0, `Done` at 90.
-//                  -> { type: 'globeDone', view, filename, numSides, bounds, glb | position, color[, wireframe][, superPlateBorders],
+//                  -> { type: 'globeDone', view, filename, numSides, bounds, glb | position, color[, wireframe][, superPlateBorders][, windArrows]
+//                       [, oceanCurrentArrows][, itcz][, grid],
 //                       _globeTiming: { workerTotal } }, the buffers transferred
+//   cmd 'exportOverlays' { windArrows?, oceanCurrentArrows?, itcz?, grid?, centerLon? }   (js/planet-mesh.js:1289-1749, :385-469)
+//                  the line overlays of the reference's views in both forms, globe and map (js/overlay-export.js): `windArrows`,
+//                  `oceanCurrentArrows`: 'summer' | 'winter', the arrows of that season from the blocks computeClimate left on the planet,
+//                  built on the device (`no wind result` / `no ocean result` before it); `itcz`: 'summer' | 'winter', the green line of
+//                  the pressure views from the cached wind result; `grid`: the spacing of the latitude / longitude grid in degrees.
+//                  `centerLon` (radians) is the map view's centre meridian; the map form of the ITCZ line ignores it, as the reference does.
+//                  -> { type: 'overlaysDone', centerLon[, windArrows, oceanCurrentArrows: { globe: { position, color }, map: { position, color }, count }]
+//                       [, itcz, grid: { globe, map }], _overlayTiming: { workerTotal } }, the buffers transferred
 //   cmd 'dispose'  frees the retained state -> { type: 'disposed' }
 //   progress / errors exactly as the reference posts them: { type: 'progress', pct, label }, { type: 'error', message, stack };
 //   an unknown command answers `Unknown command: <cmd>` (:952).
@@ -104,6 +115,7 @@ import { generateCoarsePlates } from './coarse-plates.js';
 import { SimplexNoise } from './simplex-noise.js';
 import { MAP_TYPES, MAP_LAYERS, exportFilename, layerFilename, encodePng, rasterOnPlanet } from './map-export.js';
 import { GLOBE_PLATES, GLOBE_TYPE_VIEWS, computePlateColors, exportGlobeOnPlanet, globeFilename } from './globe-export.js';
+import { SEASONS, windArrowsOnPlanet, oceanCurrentArrowsOnPlanet, itczLine, grids } from './overlay-export.js';
 
 let W = null;          // retained state (js/planet-worker.js:22)
 
@@ -559,6 +571,39 @@ function handleExportMap(data) {
     }
 }
 
+// what the overlay requests of exportGlobe and exportOverlays share
+function checkedSeason(cmd, key, season) {
+    if (SEASONS.indexOf(season) < 0) throw new RangeError(`${cmd}: ${key} takes a season ('summer' or 'winter'), not '${season}'`);
+    return season;
+}
+function itczOf(cmd, season) {
+    checkedSeason(cmd, 'itcz', season);
+    const wind = W.cachedWind;
+    if (!wind || !(wind.itczLons instanceof Float32Array)) throw new Error(`${cmd}: no wind result on this planet (run computeClimate first)`);
+    return { itczLons: wind.itczLons, itczLats: season === 'winter' ? wind.itczLatsWinter : wind.itczLatsSummer };
+}
+
+// js/planet-mesh.js:1289-1749, :385-469 without the page: the arrows, the ITCZ line and the grids, each in the globe and the map form
+function handleExportOverlays(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for exportOverlays' }); return; }
+    try {
+        const tTotal0 = performance.now();
+        const centerLon = Number(data.centerLon) || 0;
+        const msg = { type: 'overlaysDone', centerLon }, transfer = [];
+        const asked = (k) => data[k] !== undefined && data[k] !== null;
+        if (asked('windArrows')) msg.windArrows = windArrowsOnPlanet(W.planet, checkedSeason('exportOverlays', 'windArrows', data.windArrows), centerLon);
+        if (asked('oceanCurrentArrows')) msg.oceanCurrentArrows = oceanCurrentArrowsOnPlanet(W.planet, checkedSeason('exportOverlays', 'oceanCurrentArrows', data.oceanCurrentArrows), centerLon, null);
+        if (asked('itcz')) { const src = itczOf('exportOverlays', data.itcz); msg.itcz = itczLine(src.itczLons, src.itczLats); }
+        if (asked('grid')) msg.grid = grids(data.grid, centerLon);
+        for (const k of ['windArrows', 'oceanCurrentArrows']) if (msg[k]) transfer.push(msg[k].globe.position.buffer, msg[k].globe.color.buffer, msg[k].map.position.buffer, msg[k].map.color.buffer);
+        for (const k of ['itcz', 'grid']) if (msg[k]) transfer.push(msg[k].globe.buffer, msg[k].map.buffer);
+        msg._overlayTiming = { workerTotal: performance.now() - tTotal0 };
+        parentPort.postMessage(msg, transfer);
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
 // js/planet-mesh.js:620-836 without the page: the globe mesh of W.planet's current elevation in one view, its line sets, and the GLB file
 function handleExportGlobe(data) {
     if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for exportGlobe' }); return; }
@@ -591,6 +636,9 @@ function handleExportGlobe(data) {
             if (!(generic.superPlates instanceof Float32Array)) throw new Error('exportGlobe: the retained debugLayers have no superPlates (generate or editRecompute with P >= 8 leaves them)');
             opts.superPlates = generic.superPlates;
         }
+        for (const k of ['windArrows', 'oceanCurrentArrows']) if (data[k] !== undefined && data[k] !== null) opts[k] = checkedSeason('exportGlobe', k, data[k]);
+        if (data.itcz !== undefined && data.itcz !== null) opts.itcz = itczOf('exportGlobe', data.itcz);
+        if (data.grid !== undefined && data.grid !== null) opts.grid = data.grid;
         progress(0, 'Building globe...');
         const name = data.plates ? GLOBE_PLATES : (data.layer !== undefined && data.layer !== null ? data.layer : view);
         const res = exportGlobeOnPlanet(W.planet, W.triangles, W.halfedges, null, view, W.seed, opts);
@@ -601,7 +649,8 @@ function handleExportGlobe(data) {
         else {
             msg.position = res.position; msg.color = res.color;
             transfer.push(res.position.buffer, res.color.buffer);
-            for (const k of ['wireframe', 'superPlateBorders']) if (res[k]) { msg[k] = res[k]; transfer.push(res[k].buffer); }
+            for (const k of ['wireframe', 'superPlateBorders', 'itcz', 'grid']) if (res[k]) { msg[k] = res[k]; transfer.push(res[k].buffer); }
+            for (const k of ['windArrows', 'oceanCurrentArrows']) if (res[k]) { msg[k] = res[k]; transfer.push(res[k].position.buffer, res[k].color.buffer); }
         }
         msg._globeTiming = { workerTotal: performance.now() - tTotal0 };
         parentPort.postMessage(msg, transfer);
@@ -621,6 +670,7 @@ parentPort.on('message', (data) => {
         case 'editRecompute': handleEditRecompute(data); break;
         case 'exportMap': handleExportMap(data); break;
         case 'exportGlobe': handleExportGlobe(data); break;
+        case 'exportOverlays': handleExportOverlays(data); break;
         case 'generate': handleGenerate(data); break;
         default: parentPort.postMessage({ type: 'error', message: `Unknown command: ${cmd}` });
     }

@@ -948,6 +948,45 @@ napi_value GlobeLines(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// ---- arrow overlays (include/worogen.h: wo_overlay_bins / wo_overlay_arrows) ----------------------------------------------
+// overlayBins(planet, skipLand, r_elevation | null) -> Int32Array(7200): per 3 x 3 degree cell the region closest to its centre, -1 for none
+napi_value OverlayBins(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    bool skip = false;
+    if (a.has(1)) napi_get_value_bool(env, a.argv[1], &skip);
+    float* e = (float*)opt_regions(a, 2, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    void* d; napi_value out = make_ta(env, napi_int32_array, WO_OVERLAY_BINS, 4, &d);
+    if (!out) return nullptr;
+    if (wo_overlay_bins(p, skip ? 1 : 0, e, (int32_t*)d)) return throw_wo(env, "overlayBins");
+    return out;
+}
+// overlayArrows(planet, kind 0 wind | 1 ocean, season 0 summer | 1 winter, centerLon, r_elevation | null)
+//   -> { globe: { position, color }, map: { position, color }, count }: Float32Array(count * 18) each
+napi_value OverlayArrows(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* e = (float*)opt_regions(a, 4, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    const size_t room = (size_t)WO_OVERLAY_BINS * 18;
+    std::vector<float> buf(4 * room);
+    int64_t count = 0;
+    if (wo_overlay_arrows(p, a.i32(1), a.i32(2), a.has(3) ? a.num(3) : 0.0, e, buf.data(), buf.data() + room, buf.data() + 2 * room, buf.data() + 3 * room, WO_OVERLAY_BINS, &count))
+        return throw_wo(env, "overlayArrows");
+    napi_value o, forms[2], c;
+    napi_create_object(env, &o);
+    static const char* const names[4] = {"position", "color", "position", "color"};
+    for (int k = 0; k < 4; ++k) {
+        if (k % 2 == 0) napi_create_object(env, &forms[k / 2]);
+        void* d; napi_value ta = make_ta(env, napi_float32_array, (size_t)count * 18, 4, &d);
+        if (!ta) return nullptr;
+        std::memcpy(d, buf.data() + k * room, (size_t)count * 72);
+        set_prop(env, forms[k / 2], names[k], ta);
+    }
+    set_prop(env, o, "globe", forms[0]); set_prop(env, o, "map", forms[1]);
+    napi_create_int32(env, (int32_t)count, &c); set_prop(env, o, "count", c);
+    return o;
+}
+
 // ---- multi-GPU exchange over RCCL (include/worogen.h: wo_comm_*; one worker thread per GPU holds one communicator) -------
 void FinalizeComm(napi_env, void* data, void*) { wo_comm_destroy((wo_comm*)data); }
 napi_value CommUniqueId(napi_env env, napi_callback_info) {                   // () -> Uint8Array(128): rank 0 makes it, the host posts it to every worker
@@ -1035,6 +1074,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"temperatureUpload", TemperatureUpload}, {"classifyKoppen", ClassifyKoppen},
         {"mapRaster", MapRaster}, {"mapColor", MapColor}, {"mapFree", MapFree}, {"mapRasterCentered", MapRasterCentered}, {"mapColorLayer", MapColorLayer},
         {"globeMesh", GlobeMesh}, {"globeMeshPlates", GlobeMeshPlates}, {"globeLines", GlobeLines},
+        {"overlayBins", OverlayBins}, {"overlayArrows", OverlayArrows},
         {"commUniqueId", CommUniqueId}, {"commCreate", CommCreate}, {"planetSetHalo", PlanetSetHalo},
         {"planetExchangeAllgather", PlanetExchangeAllgather}, {"planetExchangeNeighbors", PlanetExchangeNeighbors}, {"planetSetFloodExchange", PlanetSetFloodExchange},
     };
