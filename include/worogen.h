@@ -575,6 +575,47 @@ int wo_overlay_bins(wo_planet* p, int32_t skipLand, const float* r_elevation, in
 int wo_overlay_arrows(wo_planet* p, int32_t kind, int32_t season, double centerLon, const float* r_elevation, float* globePos,
                       float* globeCol, float* mapPos, float* mapCol, int64_t capacityArrows, int64_t* count);
 
+/* ------------------------------------------------ the editor: hit test and highlights --------- */
+/* findNearestRegion, getHitInfoGlobe, getHitInfoMap                                              js/edit-mode.js:18-28, :32-60, :63-93
+ * updatePendingHighlight, updateHoverHighlight, updateKoppenHoverHighlight                        js/planet-mesh.js:1143-1244, :960-1139
+ *   The bodies and the whole contract are in csrc/pick_ops.h; every result is the reference's bit for bit.
+ *   wo_pick_regions answers numQueries directions (three doubles each) from the planet's resident f32 positions (csrc/pick.hip): per
+ *   region dot = nx * (double)x + ny * (double)y + nz * (double)z, left to right in double, uncontracted; the region is the lowest
+ *   index among those whose dot equals the maximum of the dots above -2, compared by value (-0 equals +0, a NaN dot never wins), or
+ *   -1 when no dot is above -2 (a NaN query, a query such as (-3, 0, 0)).  dotsOut (may be NULL) receives the winning dot, or -2.
+ *   numQueries 0 succeeds and touches nothing; numQueries below 0 or above WO_PICK_MAX_QUERIES, a NULL planet, directions or
+ *   regionsOut return 1.  Two calls give identical words.
+ *   wo_pick_directions_globe and wo_pick_directions_map are the two front ends, on the host (no device is touched): the direction
+ *   that reaches findNearestRegion, three doubles per query in directionsOut, and 1 in validOut; or 0 and a NaN direction where the
+ *   reference returns null, which wo_pick_regions answers with -1.  Globe form: rays holds six doubles per query, the origin and the
+ *   NORMALISED direction of the ray in the planet's local space (three's camera and matrices are the caller's business); the sphere
+ *   has radius 1.08; no hit when the discriminant or the nearer root is negative.  Map form: points holds wx, wy per query on the
+ *   map plane (x in [-2, 2], y in [-1, 1]: lon = wx * PI / 2 + centerLon, wrapped once, lat = wy * PI / 2, invalid outside
+ *   [-PI/2, PI/2]); a centerLon of NaN counts as 0.  Math.sin and Math.cos are V8's fdlibm (|lon| below about 1.6e6).  As in the
+ *   reference a NaN input passes both tests: valid 1, a NaN direction.
+ *   wo_highlight_set sets the editor state of the planet: one class byte per region, kept on the device and counted by
+ *   wo_memory_in_use, built from r_plate (numRegions int32, uploaded for the call): with pid = r_plate[r], bit 1 pid is one of the
+ *   numPending pendingPlates and pendingIsOcean of that plate is not 0 (ocean now, to become land), bit 2 pid is pending and the
+ *   plate is land now, bit 4 pid == hoveredPlate >= 0, bit 8 koppen[r] == hoveredKoppen >= 0.  counts (may be NULL) receives the
+ *   number of regions per bit.  Pending ids and a non-negative hoveredPlate must lie in [0, numRegions); a plate listed twice is
+ *   refused; hoveredKoppen >= 0 without a Koppen block is refused with "no Koppen result" (the reference skips silently: not
+ *   offered); r_plate entries outside [0, numRegions) match nothing.  The byte is evaluated at set time: a later wo_classify_koppen
+ *   does not change it.  A second call replaces the state; wo_highlight_clear and wo_planet_destroy drop it.  A refusal returns 1,
+ *   names the value and leaves the planet's state as it was.
+ *   While the state is set, wo_globe_mesh, wo_globe_mesh_plates, wo_map_color and wo_map_color_layer tint each region's f32 colour
+ *   before the vertex write or the quantiser, in the reference's order, every step stored as f32, arithmetic in double, min as
+ *   Math.min: pending and ocean now r * 0.7, min(1, g + 0.25), b * 0.7; pending and land now r * 0.7, g * 0.7, min(1, b + 0.25);
+ *   plate hover, then Koppen hover, each channel min(1, c + 0.22).  A region whose byte is 0, and every region without a state, has
+ *   exactly the words it had.  That the raster shows the tints is our decision (the reference tints its map mesh the same way); the
+ *   pixels nothing covers are never tinted. */
+enum { WO_PICK_MAX_QUERIES = 65536 };
+int wo_pick_regions(wo_planet* p, int32_t numQueries, const double* directions, int32_t* regionsOut, double* dotsOut);
+int wo_pick_directions_globe(int32_t numQueries, const double* rays, double* directionsOut, uint8_t* validOut);
+int wo_pick_directions_map(int32_t numQueries, const double* points, double centerLon, double* directionsOut, uint8_t* validOut);
+int wo_highlight_set(wo_planet* p, const int32_t* r_plate, int32_t numPending, const int32_t* pendingPlates,
+                     const uint8_t* pendingIsOcean, int32_t hoveredPlate, int32_t hoveredKoppen, int64_t counts[4]);
+int wo_highlight_clear(wo_planet* p);
+
 /* ------------------------------------------------ device-resident variants -------------------- */
 /* The "reapply" pattern (js/planet-worker.js:341-440): fields stay in HBM, only scalars arrive.
  * wo_planet_upload sets the resident r_elevation (and r_isOcean when not NULL); the *_resident

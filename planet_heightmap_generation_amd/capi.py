@@ -96,6 +96,11 @@ SIGNATURES = {
     "wo_globe_lines": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _p, _p, _p, _c_i64, _p]),
     "wo_overlay_bins": (C.c_int, [_p, _c_i32, _p, _p]),
     "wo_overlay_arrows": (C.c_int, [_p, _c_i32, _c_i32, _c_f64, _p, _p, _p, _p, _p, _c_i64, _p]),
+    "wo_pick_regions": (C.c_int, [_p, _c_i32, _p, _p, _p]),
+    "wo_pick_directions_globe": (C.c_int, [_c_i32, _p, _p, _p]),
+    "wo_pick_directions_map": (C.c_int, [_c_i32, _p, _c_f64, _p, _p]),
+    "wo_highlight_set": (C.c_int, [_p, _p, _c_i32, _p, _p, _c_i32, _c_i32, _p]),
+    "wo_highlight_clear": (C.c_int, [_p]),
     "wo_planet_upload": (C.c_int, [_p, _p, _p]),
     "wo_planet_download": (C.c_int, [_p, _p]),
     "wo_planet_set_halo": (C.c_int, [_p, _p, _c_i32, _p, _c_i32]),

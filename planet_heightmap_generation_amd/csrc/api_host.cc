@@ -9,6 +9,7 @@
 #include "host_util.h"
 #include "wo_internal.h"
 #include "noise.h"
+#include "pick_ops.h"
 
 namespace wo {
 static thread_local std::string g_err;
@@ -164,6 +165,26 @@ int wo_land_components(int32_t numRegions, const int32_t* adjOffset, const int32
         wo::mesh_components(numRegions, adjOffset, adjList, [&](int32_t r) { return r_isOcean[r] == 0; }, [](int32_t, int32_t) { return true; }, label);
         wo::parallel_ranges(numRegions, [&](int64_t b, int64_t e, int) { for (int64_t r = b; r < e; ++r) if (r_isOcean[r]) label[r] = -1; });
     } catch (const std::exception& e) { wo::set_error(std::string("wo_land_components: ") + e.what()); return 3; }
+    return 0;
+}
+
+// ---- the editor's hit test, host front ends (pick_ops.h; js/edit-mode.js:43-59, :77-92): no device is touched ----
+static bool pick_front_args_ok(const char* fn, int32_t numQueries, const void* in, const char* inName, const double* directionsOut, const uint8_t* validOut) {
+    const std::string F = std::string(fn) + ": ";
+    if (numQueries < 0 || numQueries > wo::pick::MAX_QUERIES) { wo::set_error(F + "numQueries is " + std::to_string(numQueries) + ", it must lie in [0, " + std::to_string(wo::pick::MAX_QUERIES) + "]"); return false; }
+    if (!in || !directionsOut || !validOut) { wo::set_error(F + (!in ? inName : !directionsOut ? "directionsOut" : "validOut") + " is NULL"); return false; }
+    return true;
+}
+
+int wo_pick_directions_globe(int32_t numQueries, const double* rays, double* directionsOut, uint8_t* validOut) {
+    if (!pick_front_args_ok("wo_pick_directions_globe", numQueries, rays, "rays", directionsOut, validOut)) return 1;
+    for (int32_t i = 0; i < numQueries; ++i) validOut[i] = wo::pick::direction_globe(rays + 6 * (int64_t)i, directionsOut + 3 * (int64_t)i) ? 1 : 0;
+    return 0;
+}
+
+int wo_pick_directions_map(int32_t numQueries, const double* points, double centerLon, double* directionsOut, uint8_t* validOut) {
+    if (!pick_front_args_ok("wo_pick_directions_map", numQueries, points, "points", directionsOut, validOut)) return 1;
+    for (int32_t i = 0; i < numQueries; ++i) validOut[i] = wo::pick::direction_map(points[2 * (int64_t)i], points[2 * (int64_t)i + 1], centerLon, directionsOut + 3 * (int64_t)i) ? 1 : 0;
     return 0;
 }
 

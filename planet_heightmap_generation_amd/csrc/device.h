@@ -59,7 +59,8 @@ enum Family : int {
     FAM_MAP_LONLAT, FAM_MAP_FILL, FAM_MAP_SIDES, FAM_MAP_BIG_BOXES, FAM_MAP_RESOLVE, FAM_MAP_REGION_COLORS, FAM_MAP_PIXELS,
     FAM_MAP_RANGE, FAM_MAP_LAYER_COLORS,
     FAM_GLOBE_TABLES, FAM_GLOBE_REGION_COLORS, FAM_GLOBE_RANGE, FAM_GLOBE_MESH, FAM_GLOBE_LINE_COUNT, FAM_GLOBE_LINE_SCAN, FAM_GLOBE_LINE_WRITE,
-    FAM_OVERLAY_BINS, FAM_OVERLAY_ARROWS, FAM_COUNT
+    FAM_OVERLAY_BINS, FAM_OVERLAY_ARROWS,
+    FAM_PICK, FAM_PICK_REDUCE, FAM_HIGHLIGHT, FAM_COUNT
 };
 extern const char* const kFamilyNames[FAM_COUNT];
 
@@ -106,6 +107,7 @@ struct Options {
     bool tempSplitDiffuse = false;     // temp_split_diffuse=1     temperature: diffuseOceanWarmth season by season with the single-field kernels instead of one float2 gather
     bool globeDirectStores = false;    // globe_direct_stores=1    globe mesh: every lane stores its own nine floats instead of staging the workgroup's in LDS (the A/B of DESIGN section 8.11)
     bool overlayPrecheck = false;      // overlay_precheck=1       arrow overlays: a candidate reads the bin's key first and sends its atomicMin only when its own is smaller (the A/B of DESIGN section 8.12)
+    int  pickBlocks = 0;               // pick_blocks=<n>          the hit test: at most this many workgroups per tile of queries (0: the default cap), so that the stride loop and the partial reduction run on a small planet
     static Options from_env();
 };
 }  // namespace wo
@@ -214,6 +216,9 @@ struct wo_planet {
     // map export (map.hip): the map block — the region map of the last wo_map_raster (4 bytes per pixel), allocated by that call;
     // deleted by wo_map_free and wo_planet_destroy (map_free)
     struct wo_map_block* map = nullptr;
+    // the editor's highlight state (globe.hip): one class byte per region (pick_ops.h: CLS_*), set by wo_highlight_set; deleted by
+    // wo_highlight_clear and wo_planet_destroy (highlight_free)
+    struct wo_highlight_block* highlight = nullptr;
 
     // Patch-major mirror of the mesh for erodeComposite (mirror.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
@@ -307,6 +312,9 @@ void precip_free(wo_planet* p);
 void temp_free(wo_planet* p);
 // map.hip: drops the map block
 void map_free(wo_planet* p);
+// globe.hip: drops the highlight state; its class bytes (on the device), nullptr when no state is set
+void highlight_free(wo_planet* p);
+const uint8_t* highlight_classes(const wo_planet* p);
 // temp.hip: the class ids of the planet's Koppen block (one byte per cell, on the device), nullptr when it has no Koppen result
 const uint8_t* koppen_classes(const wo_planet* p);
 // planet.hip: the entry points' handle check (refreshes p->opt from the environment, selects the device)

@@ -18,26 +18,76 @@
 //   and popcount), k_globe_line_scan [1] (one workgroup scans the workgroup counts in place and leaves the total),
 //   k_globe_line_write [1] (every lane's place is its workgroup's offset + its wave's + the popcount of the ballot below it).
 //   The segment count is waited for before the segments are copied, so that nothing is written behind them.
-// Memory (device_mem.h): everything is a temporary of the call, in an arena on its stack.
+// The editor's highlight state (wo_highlight_set / wo_highlight_clear; the bodies in pick_ops.h): one class byte per region, kept in a
+//   block of its own.  k_highlight_kinds [1] scatters the pending plates' kinds over a cleared table of one byte per region id,
+//   k_highlight_classes [1] gives every region its byte and counts the regions per bit (ballot and popcount per wave, one LDS atomic
+//   per wave and bit, one global integer atomic per workgroup and bit).  While the state is set, k_highlight_tint [1] runs over the
+//   region colours of wo_globe_mesh / wo_globe_mesh_plates before the mesh kernel reads them; a region whose byte is 0 is not
+//   written.
+// Memory (device_mem.h): everything is a temporary of the call, in an arena on its stack, but the class bytes, which the highlight
+// block owns.
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/worogen.h"
 #include "device.h"
 #include "globe_ops.h"
 #include "map_shared.h"
+#include "pick_ops.h"
 
 namespace G = wo::globe;
 namespace M = wo::map;
+namespace P = wo::pick;
 
 static_assert(G::SOURCE_TYPE == WO_GLOBE_SOURCE_TYPE && G::SOURCE_LAYER == WO_GLOBE_SOURCE_LAYER, "the sources of globe_ops.h are those of worogen.h");
 static_assert(G::LINES_WIREFRAME == WO_GLOBE_LINES_WIREFRAME && G::LINES_SUPER_PLATE_BORDERS == WO_GLOBE_LINES_SUPER_PLATE_BORDERS, "the line kinds of globe_ops.h are those of worogen.h");
 static_assert(sizeof(G::Center) == 16, "one 16-byte load per centre");
 
+struct wo_highlight_block {
+    wo::DeviceArena mem;                 // owns cls
+    uint8_t* cls = nullptr;              // one class byte per region (pick_ops.h: CLS_*)
+};
+
 namespace wo {
 
 constexpr int GLOBE_WAVES = WO_BLOCK / 64;
+
+void highlight_free(wo_planet* p) { delete p->highlight; p->highlight = nullptr; }
+const uint8_t* highlight_classes(const wo_planet* p) { return p->highlight ? p->highlight->cls : nullptr; }
+
+// kind was cleared; the entry point checked that every plate is a region id and that none is listed twice
+__global__ __launch_bounds__(WO_BLOCK) void k_highlight_kinds(const int32_t* __restrict__ plates, const uint8_t* __restrict__ isOcean, int32_t n, uint8_t* __restrict__ kind) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) kind[plates[i]] = isOcean[i] ? P::CLS_PENDING_OCEAN : P::CLS_PENDING_LAND;
+}
+// counts (four words, cleared): the regions per bit.  The grid covers N exactly.
+__global__ __launch_bounds__(WO_BLOCK) void k_highlight_classes(const int32_t* __restrict__ r_plate, const uint8_t* __restrict__ kind, int32_t hoveredPlate,
+                                                                const uint8_t* __restrict__ koppen, int32_t hoveredKoppen, uint8_t* __restrict__ cls, int32_t N,
+                                                                unsigned long long* __restrict__ counts) {
+    __shared__ uint32_t blockCount[4];
+    if (threadIdx.x < 4) blockCount[threadIdx.x] = 0u;
+    __syncthreads();
+    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    uint8_t c = 0;
+    if (r < N) { c = P::class_of(r_plate[r], N, kind, hoveredPlate, koppen, r, hoveredKoppen); cls[r] = c; }
+    for (int b = 0; b < 4; ++b) {
+        const unsigned long long mask = __ballot((c >> b) & 1);
+        if ((threadIdx.x & 63) == 0 && mask) atomicAdd(&blockCount[b], (uint32_t)__popcll(mask));
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && blockCount[threadIdx.x]) atomicAdd(counts + threadIdx.x, (unsigned long long)blockCount[threadIdx.x]);
+}
+__global__ __launch_bounds__(WO_BLOCK) void k_highlight_tint(const uint8_t* __restrict__ cls, float* __restrict__ rgb, int32_t N) {
+    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    const uint8_t c = cls[r];
+    if (!c) return;
+    const int64_t o = 3 * (int64_t)r;
+    const M::Rgb t = P::tint(M::Rgb{rgb[o], rgb[o + 1], rgb[o + 2]}, c);
+    rgb[o] = t.r; rgb[o + 1] = t.g; rgb[o + 2] = t.b;
+}
 
 __global__ __launch_bounds__(WO_BLOCK) void k_globe_centers(const int32_t* __restrict__ triangles, const float* __restrict__ xyz, const float* __restrict__ e,
                                                             G::Center* __restrict__ out, int32_t numTriangles) {
@@ -209,6 +259,11 @@ static bool globe_outputs_ok(const char* fn, int32_t numSides, const float* posi
     return true;
 }
 
+// the editor's tints over the region colours, when a highlight state is set
+static void globe_tint(wo_planet* p, float* rgb) {
+    if (rgb && highlight_classes(p)) launch(p, FAM_HIGHLIGHT, k_highlight_tint, blocks_for(p->N), WO_BLOCK, highlight_classes(p), rgb, p->N);
+}
+
 // the tables, the mesh kernel and the copies; rgb holds the region colours (nullptr without colorsOut)
 static void globe_mesh_run(wo_planet* p, DeviceArena& T, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, const float* e, const float* rgb,
                            float* positionsOut, float* colorsOut, float bounds[6]) {
@@ -299,6 +354,7 @@ int wo_globe_mesh(wo_planet* p, int32_t numSides, const int32_t* triangles, cons
                 launch(p, FAM_GLOBE_REGION_COLORS, k_globe_layer_colors, g, WO_BLOCK, id, a, b, e, (const uint32_t*)range, rgb, N);
             }
         }
+        globe_tint(p, rgb);
         globe_mesh_run(p, T, numSides, triangles, halfedges, e, rgb, positionsOut, colorsOut, bounds);
         return 0;
     WO_CATCH("wo_globe_mesh")
@@ -337,9 +393,69 @@ int wo_globe_mesh_plates(wo_planet* p, int32_t numSides, const int32_t* triangle
             const float* d_colors = numPlates > 0 ? up(T, plateColors, 3 * (size_t)numPlates, s) : nullptr;
             launch(p, FAM_GLOBE_REGION_COLORS, k_globe_plate_colors, blocks_for(N), WO_BLOCK, d_plate, (const int32_t*)slot, d_colors, rgb, N);
         }
+        globe_tint(p, rgb);
         globe_mesh_run(p, T, numSides, triangles, halfedges, e, rgb, positionsOut, colorsOut, bounds);
         return 0;
     WO_CATCH("wo_globe_mesh_plates")
+}
+
+int wo_highlight_set(wo_planet* p, const int32_t* r_plate, int32_t numPending, const int32_t* pendingPlates, const uint8_t* pendingIsOcean, int32_t hoveredPlate,
+                     int32_t hoveredKoppen, int64_t counts[4]) {
+    const char* fn = "wo_highlight_set";
+    const std::string F = "wo_highlight_set: ";
+    if (!check_planet(p, fn)) return 1;
+    const int32_t N = p->N;
+    if (!r_plate) { set_error(F + "r_plate is NULL"); return 1; }
+    if (numPending < 0) { set_error(F + "numPending is " + std::to_string(numPending)); return 1; }
+    if (numPending > 0 && (!pendingPlates || !pendingIsOcean)) { set_error(F + (pendingPlates ? "pendingIsOcean" : "pendingPlates") + " is NULL with " + std::to_string(numPending) + " pending plates"); return 1; }
+    if (numPending > N) { set_error(F + "numPending is " + std::to_string(numPending) + ", the planet has " + std::to_string(N) + " regions and no plate is listed twice"); return 1; }
+    if (hoveredPlate >= N) { set_error(F + "hoveredPlate = " + std::to_string(hoveredPlate) + " is no region of the planet, which has " + std::to_string(N)); return 1; }
+    {
+        std::vector<uint8_t> seen(numPending > 0 ? (size_t)N : 0, 0);
+        for (int32_t i = 0; i < numPending; ++i) {
+            const int32_t id = pendingPlates[i];
+            if ((uint32_t)id >= (uint32_t)N) { set_error(F + "pendingPlates[" + std::to_string(i) + "] = " + std::to_string(id) + " is no region of the planet, which has " + std::to_string(N)); return 1; }
+            if (seen[id]) { set_error(F + "pendingPlates[" + std::to_string(i) + "] = " + std::to_string(id) + " is listed twice"); return 1; }
+            seen[id] = 1;
+        }
+    }
+    const uint8_t* koppen = nullptr;
+    if (hoveredKoppen >= 0 && !(koppen = koppen_classes(p))) { set_error(F + "hoveredKoppen = " + std::to_string(hoveredKoppen) + " but there is no Koppen result on this planet (call wo_classify_koppen first)"); return 1; }
+    WO_TRY
+        hipStream_t s = p->ctx->stream;
+        auto* B = new wo_highlight_block();
+        try {
+            DeviceArena T;                                    // the temporaries of this call
+            B->cls = B->mem.dev<uint8_t>((size_t)N);
+            uint8_t* kind = T.dev<uint8_t>((size_t)N);
+            unsigned long long* d_counts = T.dev<unsigned long long>(4);
+            unsigned long long* h_counts = T.pinned<unsigned long long>(4);
+            WO_HIP(hipMemsetAsync(kind, 0, (size_t)N, s));
+            WO_HIP(hipMemsetAsync(d_counts, 0, 32, s));
+            const int32_t* d_plate = up(T, r_plate, (size_t)N, s);
+            if (numPending > 0) {
+                const int32_t* d_pending = up(T, pendingPlates, (size_t)numPending, s);
+                const uint8_t* d_isOcean = up(T, pendingIsOcean, (size_t)numPending, s);
+                launch(p, FAM_HIGHLIGHT, k_highlight_kinds, blocks_for(numPending), WO_BLOCK, d_pending, d_isOcean, numPending, kind);
+            }
+            launch(p, FAM_HIGHLIGHT, k_highlight_classes, blocks_for(N), WO_BLOCK, d_plate, (const uint8_t*)kind, hoveredPlate, koppen, hoveredKoppen, B->cls, N, d_counts);
+            WO_HIP(hipMemcpyAsync(h_counts, d_counts, 32, hipMemcpyDeviceToHost, s));
+            WO_HIP(hipStreamSynchronize(s));                  // before T frees the temporaries
+            if (counts) for (int b = 0; b < 4; ++b) counts[b] = (int64_t)h_counts[b];
+        } catch (...) { delete B; throw; }
+        highlight_free(p);                                    // a second set replaces the first
+        p->highlight = B;
+        return 0;
+    WO_CATCH("wo_highlight_set")
+}
+
+int wo_highlight_clear(wo_planet* p) {
+    if (!check_planet(p, "wo_highlight_clear")) return 1;
+    WO_TRY
+        WO_HIP(hipStreamSynchronize(p->ctx->stream));
+        highlight_free(p);
+        return 0;
+    WO_CATCH("wo_highlight_clear")
 }
 
 int wo_globe_lines(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t kind, const float* r_elevation, const float* superPlates,

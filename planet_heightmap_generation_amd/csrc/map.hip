@@ -37,6 +37,7 @@
 #include "map_ops.h"
 #include "map_shared.h"
 #include "ocean_block.h"
+#include "pick_ops.h"
 #include "precip_block.h"
 #include "stage_block.h"
 #include "wind_block.h"
@@ -149,10 +150,14 @@ __global__ __launch_bounds__(WO_BLOCK) void k_map_resolve(const uint32_t* __rest
     if (threadIdx.x == 0 && blockCovered) atomicAdd(counts, blockCovered);
 }
 
+// the editor's tints (pick_ops.h) on a region's f32 colour, before the quantiser and the gamma table; cls: the highlight state's class
+// bytes, nullptr without a state
+__device__ inline M::Rgb map_tinted(const M::Rgb& c, const uint8_t* __restrict__ cls, int32_t r) { return cls && cls[r] ? wo::pick::tint(c, cls[r]) : c; }
+
 __global__ __launch_bounds__(WO_BLOCK) void k_map_region_colors(int32_t type, const float* __restrict__ e, const uint8_t* __restrict__ koppen, const uint8_t* __restrict__ lut,
-                                                                uint32_t* __restrict__ rgba, int32_t N) {
+                                                                const uint8_t* __restrict__ cls, uint32_t* __restrict__ rgba, int32_t N) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < N) rgba[r] = M::pack_rgba(M::region_color(type, e[r], koppen ? (int32_t)koppen[r] : 0), lut);
+    if (r < N) rgba[r] = M::pack_rgba(map_tinted(M::region_color(type, e[r], koppen ? (int32_t)koppen[r] : 0), cls, r), lut);
 }
 __global__ __launch_bounds__(WO_BLOCK) void k_map_biome_raw(const float* __restrict__ e, const uint8_t* __restrict__ koppen, float* __restrict__ raw, int32_t N) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -161,9 +166,9 @@ __global__ __launch_bounds__(WO_BLOCK) void k_map_biome_raw(const float* __restr
     raw[3 * (int64_t)r] = c.r; raw[3 * (int64_t)r + 1] = c.g; raw[3 * (int64_t)r + 2] = c.b;
 }
 __global__ __launch_bounds__(WO_BLOCK) void k_map_biome_smooth(const float* __restrict__ raw, const int32_t* __restrict__ off, const int32_t* __restrict__ adj,
-                                                               const uint8_t* __restrict__ lut, uint32_t* __restrict__ rgba, int32_t N) {
+                                                               const uint8_t* __restrict__ lut, const uint8_t* __restrict__ cls, uint32_t* __restrict__ rgba, int32_t N) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < N) rgba[r] = M::pack_rgba(M::biome_smooth(raw, off, adj, r), lut);
+    if (r < N) rgba[r] = M::pack_rgba(map_tinted(M::biome_smooth(raw, off, adj, r), cls, r), lut);
 }
 
 // The range of a layer's values (map_layer_ops.h: RangeBits): range[0], range[1] were cleared; every bound is a maximum over uint32
@@ -208,12 +213,13 @@ __global__ __launch_bounds__(WO_BLOCK) void k_map_range(const float* __restrict_
 
 // b and e are read by the ocean-current layers only, range by the layers coloured over their range
 __global__ __launch_bounds__(WO_BLOCK) void k_map_layer_colors(int32_t layer, const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ e,
-                                                               const uint32_t* __restrict__ range, const uint8_t* __restrict__ lut, uint32_t* __restrict__ rgba, int32_t N) {
+                                                               const uint32_t* __restrict__ range, const uint8_t* __restrict__ lut, const uint8_t* __restrict__ cls, uint32_t* __restrict__ rgba,
+                                                               int32_t N) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= N) return;
     const bool current = M::layer_is_ocean_current(layer);
     const M::RangeBits R = M::layer_needs_range(layer) ? M::RangeBits{range[0], range[1]} : M::RangeBits{0u, 0u};
-    rgba[r] = M::pack_rgba(M::layer_color(layer, a[r], current ? b[r] : 0.0f, current ? e[r] : 0.0f, R), lut);
+    rgba[r] = M::pack_rgba(map_tinted(M::layer_color(layer, a[r], current ? b[r] : 0.0f, current ? e[r] : 0.0f, R), cls, r), lut);
 }
 
 // four pixels per thread: one 16-byte load of region ids, four gathers from the colour table, one 16-byte store
@@ -377,9 +383,10 @@ int wo_map_color(wo_planet* p, int32_t type, const float* r_elevation, uint8_t* 
         if (type == M::TYPE_BIOME) {
             float* raw = T.dev<float>(3 * (size_t)N);
             map_launch_biome_raw(p, FAM_MAP_REGION_COLORS, e, koppen, raw, N);
-            launch(p, FAM_MAP_REGION_COLORS, k_map_biome_smooth, g, WO_BLOCK, (const float*)raw, (const int32_t*)p->d_off, (const int32_t*)p->d_adj, d_lut, regionRgba, N);
+            launch(p, FAM_MAP_REGION_COLORS, k_map_biome_smooth, g, WO_BLOCK, (const float*)raw, (const int32_t*)p->d_off, (const int32_t*)p->d_adj, d_lut, highlight_classes(p),
+                   regionRgba, N);
         } else {
-            launch(p, FAM_MAP_REGION_COLORS, k_map_region_colors, g, WO_BLOCK, type, e, koppen, d_lut, regionRgba, N);
+            launch(p, FAM_MAP_REGION_COLORS, k_map_region_colors, g, WO_BLOCK, type, e, koppen, d_lut, highlight_classes(p), regionRgba, N);
         }
         launch(p, FAM_MAP_PIXELS, k_map_pixels, blocks_for((pixels + 3) / 4, 1 << 14), WO_BLOCK, (const int32_t*)B->region, (const uint32_t*)regionRgba, M::background_rgba(type, lut), out,
                pixels);
@@ -425,7 +432,7 @@ int wo_map_color_layer(wo_planet* p, int32_t layer, const float* values, const f
             WO_HIP(hipMemsetAsync(range, 0, 8, s));
             map_launch_range(p, FAM_MAP_RANGE, a, N, range);
         }
-        launch(p, FAM_MAP_LAYER_COLORS, k_map_layer_colors, g, WO_BLOCK, layer, a, b, e, (const uint32_t*)range, d_lut, regionRgba, N);
+        launch(p, FAM_MAP_LAYER_COLORS, k_map_layer_colors, g, WO_BLOCK, layer, a, b, e, (const uint32_t*)range, d_lut, highlight_classes(p), regionRgba, N);
         launch(p, FAM_MAP_PIXELS, k_map_pixels, blocks_for((pixels + 3) / 4, 1 << 14), WO_BLOCK, (const int32_t*)B->region, (const uint32_t*)regionRgba, M::background_rgba(M::TYPE_COLOR, lut),
                out, pixels);
         WO_HIP(hipMemcpyAsync(rgbaOut, out, (size_t)pixels * 4, hipMemcpyDeviceToHost, s));

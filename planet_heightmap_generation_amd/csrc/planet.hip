@@ -124,6 +124,7 @@ Options Options::from_env() {
     o.tempSplitDiffuse = test_hook_int("temp_split_diffuse", 0) != 0;
     o.globeDirectStores = test_hook_int("globe_direct_stores", 0) != 0;
     o.overlayPrecheck = test_hook_int("overlay_precheck", 0) != 0;
+    o.pickBlocks = (int)std::max<long long>(0, std::min<long long>(test_hook_int("pick_blocks", 0), 1 << 16));
     return o;
 }
 
@@ -240,6 +241,7 @@ void wo_planet_destroy(wo_planet* p) {
     if (p->evJoin) { (void)hipEventDestroy(p->evJoin); p->evJoin = nullptr; }
     if (p->floodLink && p->floodLinkFree) p->floodLinkFree(p->floodLink);
     p->floodLink = nullptr;
+    highlight_free(p);
     map_free(p);
     temp_free(p);
     precip_free(p);

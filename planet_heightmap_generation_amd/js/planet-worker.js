@@ -98,6 +98,21 @@
 //                  `centerLon` (radians) is the map view's centre meridian; the map form of the ITCZ line ignores it, as the reference does.
 //                  -> { type: 'overlaysDone', centerLon[, windArrows, oceanCurrentArrows: { globe: { position, color }, map: { position, color }, count }]
 //                       [, itcz, grid: { globe, map }], _overlayTiming: { workerTotal } }, the buffers transferred
+//   cmd 'pick' { directions | rays | map: { points, centerLon? } }   (js/edit-mode.js:18-93)
+//                  the editor's hit test on the retained planet (js/edit-mode.js here, csrc/pick.hip): which region, and so which
+//                  plate, lies under a pointer.  `directions`: three numbers per query, findNearestRegion itself; `rays`: six per
+//                  query, origin and normalised direction of the ray in the planet's local space (getHitInfoGlobe's arithmetic: the
+//                  sphere of radius 1.08); `map`: `points` wx, wy per query on the map plane around `centerLon` (getHitInfoMap's).
+//                  Exactly one of the three; at most 65536 queries.
+//                  -> { type: 'picked', regions: Int32Array (-1: no region), plates: Int32Array (-1: no region or no retained r_plate) }
+//   cmd 'setHighlight' { pendingToggles?, hoveredPlate?, hoveredKoppen? }   (js/planet-mesh.js:953-1244)
+//                  the editor state the reference's page keeps: the plates queued for a rebuild (tinted green where the plate is ocean
+//                  now, blue where it is land, by the retained plateIsOcean), the hovered plate and the hovered Koppen class
+//                  (brightened; the class needs computeClimate's Koppen result).  Uses the retained r_plate.  exportGlobe and exportMap
+//                  then show the tints with no further option, until the state is replaced or cleared: an empty request clears it,
+//                  and so do editRecompute (the reference clears pendingToggles after a rebuild), importHeightmap, generate, retain and
+//                  dispose, which replace the planet.
+//                  -> { type: 'highlightSet', cleared, counts: { pendingOcean, pendingLand, hoveredPlate, hoveredKoppen } }
 //   cmd 'dispose'  frees the retained state -> { type: 'disposed' }
 //   progress / errors exactly as the reference posts them: { type: 'progress', pct, label }, { type: 'error', message, stack };
 //   an unknown command answers `Unknown command: <cmd>` (:952).
@@ -115,6 +130,7 @@ import { generateCoarsePlates } from './coarse-plates.js';
 import { SimplexNoise } from './simplex-noise.js';
 import { MAP_TYPES, MAP_LAYERS, exportFilename, layerFilename, encodePng, rasterOnPlanet } from './map-export.js';
 import { GLOBE_PLATES, GLOBE_TYPE_VIEWS, computePlateColors, exportGlobeOnPlanet, globeFilename } from './globe-export.js';
+import { findNearestRegions, hitDirectionsGlobe, hitDirectionsMap, setHighlight, clearHighlight, PICK_MAX_QUERIES } from './edit-mode.js';
 import { SEASONS, windArrowsOnPlanet, oceanCurrentArrowsOnPlanet, itczLine, grids } from './overlay-export.js';
 
 let W = null;          // retained state (js/planet-worker.js:22)
@@ -319,6 +335,7 @@ function handleEditRecompute(data) {
     try {
         const tTotal0 = performance.now();
         progress(0, 'Rebuilding elevation…');
+        clearHighlight(W.planet);                        // the reference clears pendingToggles after a rebuild
         W.plateIsOcean = Int32Array.from(data.plateIsOcean);
         W.plateDensity = Object.assign({}, data.plateDensity);
         const c = elevationChain(data, data.nMag, (stage) => {
@@ -659,6 +676,52 @@ function handleExportGlobe(data) {
     }
 }
 
+// js/edit-mode.js:18-93 without the page: the regions and plates under a batch of pointers
+function handlePick(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for pick' }); return; }
+    try {
+        const given = ['directions', 'rays', 'map'].filter((k) => data[k] !== undefined && data[k] !== null);
+        if (given.length !== 1) throw new TypeError('pick: exactly one of directions, rays and map: { points, centerLon } is expected');
+        let directions;
+        if (data.directions) {
+            if (data.directions.length % 3) throw new RangeError('pick: directions must hold three numbers per query');
+            directions = Float64Array.from(data.directions);
+        } else if (data.rays) directions = hitDirectionsGlobe(data.rays).directions;
+        else {
+            if (!data.map.points) throw new TypeError('pick: map takes { points, centerLon }');
+            directions = hitDirectionsMap(data.map.points, Number(data.map.centerLon) || 0).directions;
+        }
+        if (directions.length / 3 > PICK_MAX_QUERIES) throw new RangeError(`pick: ${directions.length / 3} queries in one call, at most ${PICK_MAX_QUERIES}`);
+        const regions = findNearestRegions(W.planet, directions).regions;
+        const plates = new Int32Array(regions.length).fill(-1);
+        if (W.r_plate) for (let i = 0; i < regions.length; i++) if (regions[i] >= 0) plates[i] = W.r_plate[regions[i]];
+        parentPort.postMessage({ type: 'picked', regions, plates }, [regions.buffer, plates.buffer]);
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
+// js/planet-mesh.js:953-1244 without the page: the editor state whose tints the exports show
+function handleSetHighlight(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for setHighlight' }); return; }
+    try {
+        const pending = Array.from(data.pendingToggles || []);
+        const hoveredPlate = (data.hoveredPlate === undefined || data.hoveredPlate === null) ? -1 : Number(data.hoveredPlate);
+        const hoveredKoppen = (data.hoveredKoppen === undefined || data.hoveredKoppen === null) ? -1 : Number(data.hoveredKoppen);
+        if (pending.length === 0 && !(hoveredPlate >= 0) && !(hoveredKoppen >= 0)) {
+            clearHighlight(W.planet);
+            parentPort.postMessage({ type: 'highlightSet', cleared: true, counts: { pendingOcean: 0, pendingLand: 0, hoveredPlate: 0, hoveredKoppen: 0 } });
+            return;
+        }
+        if (!W.r_plate) throw new Error('setHighlight: the retained state has no r_plate (pass it to retain, or run generate or importHeightmap)');
+        if (pending.length && !W.plateIsOcean) throw new Error('setHighlight: the retained state has no plateIsOcean, which says how a pending plate is tinted');
+        const counts = setHighlight(W.planet, W.r_plate, pending, W.plateIsOcean || [], hoveredPlate, hoveredKoppen);
+        parentPort.postMessage({ type: 'highlightSet', cleared: false, counts });
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
 parentPort.on('message', (data) => {
     const { cmd } = data;
     switch (cmd) {
@@ -672,6 +735,8 @@ parentPort.on('message', (data) => {
         case 'exportGlobe': handleExportGlobe(data); break;
         case 'exportOverlays': handleExportOverlays(data); break;
         case 'generate': handleGenerate(data); break;
+        case 'pick': handlePick(data); break;
+        case 'setHighlight': handleSetHighlight(data); break;
         default: parentPort.postMessage({ type: 'error', message: `Unknown command: ${cmd}` });
     }
 });

@@ -987,6 +987,71 @@ napi_value OverlayArrows(napi_env env, napi_callback_info info) {
     return o;
 }
 
+// ---- the editor: hit test and highlights (include/worogen.h: wo_pick_* / wo_highlight_*) ---------------------------------------------
+static napi_value pick_result(napi_env env, const char* first, napi_value a, const char* second, napi_value b) {
+    napi_value o; napi_create_object(env, &o);
+    set_prop(env, o, first, a); set_prop(env, o, second, b);
+    return o;
+}
+// pickRegions(planet, directions Float64Array(3 per query)) -> { regions: Int32Array, dots: Float64Array }
+napi_value PickRegions(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    size_t n = 0; double* dirs = (double*)a.ta(1, napi_float64_array, &n); if (!a.ok) return nullptr;
+    if (n % 3) { napi_throw_range_error(env, nullptr, "pickRegions: directions must hold three doubles per query"); return nullptr; }
+    if (n / 3 > (size_t)WO_PICK_MAX_QUERIES) { napi_throw_range_error(env, nullptr, "pickRegions: more than 65536 queries in one call"); return nullptr; }
+    void *dr, *dd;
+    napi_value regions = make_ta(env, napi_int32_array, n / 3, 4, &dr), dots = make_ta(env, napi_float64_array, n / 3, 8, &dd);
+    if (!regions || !dots) return nullptr;
+    double none[3] = {0, 0, 0}; int32_t noRegion = 0;        // an empty typed array may have no storage
+    if (wo_pick_regions(p, (int32_t)(n / 3), n ? dirs : none, n ? (int32_t*)dr : &noRegion, n ? (double*)dd : nullptr)) return throw_wo(env, "pickRegions");
+    return pick_result(env, "regions", regions, "dots", dots);
+}
+static napi_value pick_directions(napi_env env, napi_callback_info info, bool map) {
+    Args a(env, info);
+    const char* name = map ? "pickDirectionsMap" : "pickDirectionsGlobe";
+    const size_t per = map ? 2 : 6;
+    size_t n = 0; double* in = (double*)a.ta(0, napi_float64_array, &n); if (!a.ok) return nullptr;
+    if (n % per || n / per > (size_t)WO_PICK_MAX_QUERIES) { napi_throw_range_error(env, nullptr, map ? "pickDirectionsMap: points must hold two doubles per query, at most 65536 queries" : "pickDirectionsGlobe: rays must hold six doubles per query, at most 65536 queries"); return nullptr; }
+    const size_t q = n / per;
+    void *dd, *dv;
+    napi_value dirs = make_ta(env, napi_float64_array, 3 * q, 8, &dd), valid = make_ta(env, napi_uint8_array, q, 1, &dv);
+    if (!dirs || !valid) return nullptr;
+    if (q) {
+        const int rc = map ? wo_pick_directions_map((int32_t)q, in, a.has(1) ? a.num(1) : 0.0, (double*)dd, (uint8_t*)dv) : wo_pick_directions_globe((int32_t)q, in, (double*)dd, (uint8_t*)dv);
+        if (rc) return throw_wo(env, name);
+    }
+    return pick_result(env, "directions", dirs, "valid", valid);
+}
+// pickDirectionsGlobe(rays Float64Array(origin xyz, direction xyz per query)) -> { directions: Float64Array(3 per query), valid: Uint8Array }
+napi_value PickDirectionsGlobe(napi_env env, napi_callback_info info) { return pick_directions(env, info, false); }
+// pickDirectionsMap(points Float64Array(wx, wy per query), centerLon = 0) -> as pickDirectionsGlobe
+napi_value PickDirectionsMap(napi_env env, napi_callback_info info) { return pick_directions(env, info, true); }
+// highlightSet(planet, r_plate Int32Array, pendingPlates Int32Array, pendingIsOcean Uint8Array, hoveredPlate, hoveredKoppen)
+//   -> { pendingOcean, pendingLand, hoveredPlate, hoveredKoppen }: the regions per tint
+napi_value HighlightSet(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    int32_t* plate = (int32_t*)opt_regions(a, 1, napi_int32_array, p, "highlightSet: r_plate (an Int32Array of numRegions entries)", true); if (!a.ok) return nullptr;
+    size_t nPending = 0, nOcean = 0;
+    int32_t* pending = (int32_t*)a.ta(2, napi_int32_array, &nPending); if (!a.ok) return nullptr;
+    uint8_t* isOcean = (uint8_t*)a.ta(3, napi_uint8_array, &nOcean); if (!a.ok) return nullptr;
+    if (nPending != nOcean) { napi_throw_range_error(env, nullptr, "highlightSet: pendingIsOcean must hold one byte per pending plate"); return nullptr; }
+    int64_t counts[4] = {0, 0, 0, 0};
+    if (wo_highlight_set(p, plate, (int32_t)nPending, nPending ? pending : nullptr, nPending ? isOcean : nullptr, a.has(4) ? a.i32(4) : -1, a.has(5) ? a.i32(5) : -1, counts))
+        return throw_wo(env, "highlightSet");
+    napi_value o; napi_create_object(env, &o);
+    set_nums(env, o, {{"pendingOcean", (double)counts[0]}, {"pendingLand", (double)counts[1]}, {"hoveredPlate", (double)counts[2]}, {"hoveredKoppen", (double)counts[3]}});
+    return o;
+}
+// highlightClear(planet)
+napi_value HighlightClear(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    if (wo_highlight_clear(p)) return throw_wo(env, "highlightClear");
+    return nullptr;
+}
+
 // ---- multi-GPU exchange over RCCL (include/worogen.h: wo_comm_*; one worker thread per GPU holds one communicator) -------
 void FinalizeComm(napi_env, void* data, void*) { wo_comm_destroy((wo_comm*)data); }
 napi_value CommUniqueId(napi_env env, napi_callback_info) {                   // () -> Uint8Array(128): rank 0 makes it, the host posts it to every worker
@@ -1075,6 +1140,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"mapRaster", MapRaster}, {"mapColor", MapColor}, {"mapFree", MapFree}, {"mapRasterCentered", MapRasterCentered}, {"mapColorLayer", MapColorLayer},
         {"globeMesh", GlobeMesh}, {"globeMeshPlates", GlobeMeshPlates}, {"globeLines", GlobeLines},
         {"overlayBins", OverlayBins}, {"overlayArrows", OverlayArrows},
+        {"pickRegions", PickRegions}, {"pickDirectionsGlobe", PickDirectionsGlobe}, {"pickDirectionsMap", PickDirectionsMap},
+        {"highlightSet", HighlightSet}, {"highlightClear", HighlightClear},
         {"commUniqueId", CommUniqueId}, {"commCreate", CommCreate}, {"planetSetHalo", PlanetSetHalo},
         {"planetExchangeAllgather", PlanetExchangeAllgather}, {"planetExchangeNeighbors", PlanetExchangeNeighbors}, {"planetSetFloodExchange", PlanetSetFloodExchange},
     };
