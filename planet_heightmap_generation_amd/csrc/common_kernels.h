@@ -1,8 +1,10 @@
-// What the kernels of more than one translation unit share: the loop shapes of a per-cell pass and the noise tables' way into LDS.
+// What the kernels of more than one translation unit share: the loop shapes of a per-cell pass and the noise tables' way into LDS;
+// the wave and workgroup primitives (wave_append among them) are in block_ops.h.
 // (Each kernel is defined in the .hip that launches it, or in that file's *_kernels.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "block_ops.h"
 #include "device.h"
 
 namespace wo {
@@ -26,18 +28,6 @@ namespace wo {
 #define WO_BLOCK_STRIDE(i, valid, n)                                                              \
     for (int32_t base_ = blockIdx.x * blockDim.x, i = base_ + threadIdx.x, valid = (i < (n));   \
          base_ < (n); base_ += gridDim.x * blockDim.x, i = base_ + threadIdx.x, valid = (i < (n)))
-
-// Append `value` of every thread with `flag` to list[] with one atomic per wavefront (ballot + popcount)
-__device__ inline void wave_append(bool flag, int32_t value, int32_t* list, int32_t* counter) {
-    const unsigned long long mask = __ballot(flag);
-    if (mask == 0) return;
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)mask) - 1;
-    int32_t base = 0;
-    if (lane == leader) base = atomicAdd(counter, (int32_t)__popcll(mask));
-    base = __shfl(base, leader);
-    if (flag) list[base + __popcll(mask & ((1ull << lane) - 1ull))] = value;
-}
 
 // the permutation tables of a noise instance (perm[512] + pm12[512]) into the workgroup's LDS
 __device__ inline void load_tables(const uint8_t* tables, uint8_t* sP, uint8_t* sM) {

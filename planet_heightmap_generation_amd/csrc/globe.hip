@@ -5,25 +5,22 @@
 //
 // Launches of wo_globe_mesh / wo_globe_mesh_plates (no host round trip between them; the stream is waited for once, at the end):
 //   k_globe_centers [1]        t_xyz and t_elevation of every triangle as one 16-byte record: 2 N records instead of 18 N sums
-//   region colours [1-3]       one f32 triple per region: k_globe_type_colors, k_globe_layer_colors (after k_map_range over the
-//                              layers coloured over their range), k_map_biome_raw + k_globe_biome_smooth, or k_globe_plate_slots +
-//                              k_globe_plate_colors
+//   region colours [1-3]       one f32 triple per region, tinted by the highlight state if one is set: view_colors.hip
 //   k_globe_mesh [1]           one lane per side: two centre records, the region's position and elevation, the colour; nine floats
 //                              of positions and nine of colours per side.  A workgroup's 256 sides are 9216 contiguous bytes of each
 //                              output: the lanes put their nine floats into LDS (stride 9, no bank conflict) and the workgroup
-//                              stores them 16 bytes per lane and instruction.  The bounds of the stored positions are reduced here:
-//                              a wave64 shuffle, one LDS atomic per wave and word, at most one global atomic per workgroup and word
-//                              after a relaxed read.  Either output may be absent: without positions it is updateMeshColors.
-// Launches of wo_globe_lines, an order-preserving compaction: k_globe_centers [1], k_globe_line_count [1] (per workgroup, ballot
-//   and popcount), k_globe_line_scan [1] (one workgroup scans the workgroup counts in place and leaves the total),
-//   k_globe_line_write [1] (every lane's place is its workgroup's offset + its wave's + the popcount of the ballot below it).
-//   The segment count is waited for before the segments are copied, so that nothing is written behind them.
+//                              stores them 16 bytes per lane and instruction.  The bounds of the stored positions are reduced here
+//                              (block_ops.h: block_max_to_global, six words).  Either output may be absent: without positions it is
+//                              updateMeshColors.
+// Launches of wo_globe_lines, an order-preserving compaction: k_globe_centers [1], k_globe_line_count [1] (per workgroup),
+//   k_block_offsets<1> [1] (one workgroup scans the workgroup counts in place and leaves the total), k_globe_line_write [1] (every
+//   lane's place is its workgroup's offset + block_ops.h's block_place).  The segment count is waited for before the segments are
+//   copied, so that nothing is written behind them.
 // The editor's highlight state (wo_highlight_set / wo_highlight_clear; the bodies in pick_ops.h): one class byte per region, kept in a
 //   block of its own.  k_highlight_kinds [1] scatters the pending plates' kinds over a cleared table of one byte per region id,
-//   k_highlight_classes [1] gives every region its byte and counts the regions per bit (ballot and popcount per wave, one LDS atomic
-//   per wave and bit, one global integer atomic per workgroup and bit).  While the state is set, k_highlight_tint [1] runs over the
-//   region colours of wo_globe_mesh / wo_globe_mesh_plates before the mesh kernel reads them; a region whose byte is 0 is not
-//   written.
+//   k_highlight_classes [1] gives every region its byte and counts the regions per bit (block_ops.h: block_add_to_global, four
+//   words).  While the state is set, the colour kernels of view_colors.hip tint the regions whose byte is not 0, on the map and on
+//   the globe.
 // Memory (device_mem.h): everything is a temporary of the call, in an arena on its stack, but the class bytes, which the highlight
 // block owns.
 #include <hip/hip_runtime.h>
@@ -32,10 +29,11 @@
 #include <vector>
 
 #include "../../include/worogen.h"
+#include "block_ops.h"
 #include "device.h"
 #include "globe_ops.h"
-#include "map_shared.h"
 #include "pick_ops.h"
+#include "view_colors.h"
 
 namespace G = wo::globe;
 namespace M = wo::map;
@@ -51,8 +49,6 @@ struct wo_highlight_block {
 };
 
 namespace wo {
-
-constexpr int GLOBE_WAVES = WO_BLOCK / 64;
 
 void highlight_free(wo_planet* p) { delete p->highlight; p->highlight = nullptr; }
 const uint8_t* highlight_classes(const wo_planet* p) { return p->highlight ? p->highlight->cls : nullptr; }
@@ -72,60 +68,14 @@ __global__ __launch_bounds__(WO_BLOCK) void k_highlight_classes(const int32_t* _
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     uint8_t c = 0;
     if (r < N) { c = P::class_of(r_plate[r], N, kind, hoveredPlate, koppen, r, hoveredKoppen); cls[r] = c; }
-    for (int b = 0; b < 4; ++b) {
-        const unsigned long long mask = __ballot((c >> b) & 1);
-        if ((threadIdx.x & 63) == 0 && mask) atomicAdd(&blockCount[b], (uint32_t)__popcll(mask));
-    }
-    __syncthreads();
-    if (threadIdx.x < 4 && blockCount[threadIdx.x]) atomicAdd(counts + threadIdx.x, (unsigned long long)blockCount[threadIdx.x]);
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_highlight_tint(const uint8_t* __restrict__ cls, float* __restrict__ rgb, int32_t N) {
-    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= N) return;
-    const uint8_t c = cls[r];
-    if (!c) return;
-    const int64_t o = 3 * (int64_t)r;
-    const M::Rgb t = P::tint(M::Rgb{rgb[o], rgb[o + 1], rgb[o + 2]}, c);
-    rgb[o] = t.r; rgb[o + 1] = t.g; rgb[o + 2] = t.b;
+    const bool has[4] = {(c & 1) != 0, (c & 2) != 0, (c & 4) != 0, (c & 8) != 0};
+    block_add_to_global<4>(has, blockCount, counts);
 }
 
 __global__ __launch_bounds__(WO_BLOCK) void k_globe_centers(const int32_t* __restrict__ triangles, const float* __restrict__ xyz, const float* __restrict__ e,
                                                             G::Center* __restrict__ out, int32_t numTriangles) {
     const int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t < numTriangles) out[t] = G::center_of(triangles, xyz, e, t);
-}
-
-__device__ inline void globe_store_rgb(float* __restrict__ rgb, int32_t r, const M::Rgb& c) {
-    rgb[3 * (int64_t)r] = c.r; rgb[3 * (int64_t)r + 1] = c.g; rgb[3 * (int64_t)r + 2] = c.b;
-}
-
-__global__ __launch_bounds__(WO_BLOCK) void k_globe_type_colors(int32_t type, const float* __restrict__ e, const uint8_t* __restrict__ koppen, float* __restrict__ rgb, int32_t N) {
-    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < N) globe_store_rgb(rgb, r, M::region_color(type, e[r], koppen ? (int32_t)koppen[r] : 0));
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_globe_biome_smooth(const float* __restrict__ raw, const int32_t* __restrict__ off, const int32_t* __restrict__ adj,
-                                                                 float* __restrict__ rgb, int32_t N) {
-    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < N) globe_store_rgb(rgb, r, M::biome_smooth(raw, off, adj, r));
-}
-// b and e are read by the ocean-current layers only, range by the layers coloured over their range
-__global__ __launch_bounds__(WO_BLOCK) void k_globe_layer_colors(int32_t layer, const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ e,
-                                                                 const uint32_t* __restrict__ range, float* __restrict__ rgb, int32_t N) {
-    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= N) return;
-    const bool current = M::layer_is_ocean_current(layer);
-    const M::RangeBits R = M::layer_needs_range(layer) ? M::RangeBits{range[0], range[1]} : M::RangeBits{0u, 0u};
-    globe_store_rgb(rgb, r, M::layer_color(layer, a[r], current ? b[r] : 0.0f, current ? e[r] : 0.0f, R));
-}
-// slot[seed] = the last row of the table with that seed (the reference's object keeps the last assignment); slot was filled with -1
-__global__ __launch_bounds__(WO_BLOCK) void k_globe_plate_slots(const int32_t* __restrict__ seeds, int32_t numPlates, int32_t* slot) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < numPlates) atomicMax(slot + seeds[i], i);             // the entry point checked 0 <= seeds[i] < N
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_globe_plate_colors(const int32_t* __restrict__ r_plate, const int32_t* __restrict__ slot, const float* __restrict__ plateColors,
-                                                                 float* __restrict__ rgb, int32_t N) {
-    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < N) globe_store_rgb(rgb, r, G::plate_color(r_plate[r], N, slot, plateColors));
 }
 
 // the workgroup's `floats` floats of `stage` to out, 16 bytes per lane and turn; out is 16-byte aligned (a workgroup's share is 9216 bytes)
@@ -160,17 +110,12 @@ __global__ __launch_bounds__(WO_BLOCK) void k_globe_mesh(const int32_t* __restri
             if (STAGED) { for (int k = 0; k < 9; ++k) stage[threadIdx.x * 9 + k] = P[k]; }
             else { for (int k = 0; k < 9; ++k) pos[9 * s + k] = P[k]; }
         }
-        for (int w = 0; w < 6; ++w)
-            for (int d = 32; d > 0; d >>= 1) b.w[w] = max(b.w[w], (uint32_t)__shfl_down(b.w[w], d, 64));
         __syncthreads();                                      // blockB is cleared, stage is written
-        if ((threadIdx.x & 63) == 0)
-            for (int w = 0; w < 6; ++w) if (b.w[w]) atomicMax(&blockB[w], b.w[w]);
+        block_max_to_global<6>(b.w, blockB, bounds);
         if (STAGED) globe_flush(stage, pos + first * 9, mine);
-        __syncthreads();                                      // blockB is complete, stage is free again
-        if (threadIdx.x < 6 && blockB[threadIdx.x] > __hip_atomic_load(bounds + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            atomicMax(bounds + threadIdx.x, blockB[threadIdx.x]);
     }
     if (col) {
+        if (STAGED) __syncthreads();                          // stage is free again
         if (active) {
             const float cr = rgb[3 * (int64_t)br], cg = rgb[3 * (int64_t)br + 1], cb = rgb[3 * (int64_t)br + 2];
             for (int j = 0; j < 3; ++j) {
@@ -188,67 +133,25 @@ __global__ __launch_bounds__(WO_BLOCK) void k_globe_mesh(const int32_t* __restri
 // ---- lines: an order-preserving compaction ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(WO_BLOCK) void k_globe_line_count(int32_t kind, const int32_t* __restrict__ triangles, const int32_t* __restrict__ halfedges, const float* __restrict__ sp,
                                                                int32_t numSides, int32_t* __restrict__ blockCount) {
-    __shared__ int32_t waveCount[GLOBE_WAVES];
+    __shared__ int32_t waveCount[BLOCK_WAVES];
     const int64_t s = (int64_t)blockIdx.x * WO_BLOCK + threadIdx.x;
-    const bool take = s < numSides && G::side_has_segment(kind, triangles, halfedges, sp, s);
-    const unsigned long long mask = __ballot(take);
-    if ((threadIdx.x & 63) == 0) waveCount[threadIdx.x >> 6] = (int32_t)__popcll(mask);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t n = 0;
-        for (int w = 0; w < GLOBE_WAVES; ++w) n += waveCount[w];
-        blockCount[blockIdx.x] = n;
-    }
-}
-
-// One workgroup: counts[0 .. n) become their exclusive prefix sums, *total their sum.  Every thread owns a run of consecutive counts.
-__global__ __launch_bounds__(WO_BLOCK) void k_globe_line_scan(int32_t* __restrict__ counts, int32_t n, int32_t* __restrict__ total) {
-    __shared__ int32_t part[WO_BLOCK];
-    const int32_t per = (n + WO_BLOCK - 1) / WO_BLOCK;
-    const int32_t b = min(n, (int32_t)threadIdx.x * per), e = min(n, b + per);
-    int32_t sum = 0;
-    for (int32_t i = b; i < e; ++i) sum += counts[i];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t run = 0;
-        for (int t = 0; t < WO_BLOCK; ++t) { const int32_t c = part[t]; part[t] = run; run += c; }
-        *total = run;
-    }
-    __syncthreads();
-    int32_t run = part[threadIdx.x];
-    for (int32_t i = b; i < e; ++i) { const int32_t c = counts[i]; counts[i] = run; run += c; }
+    const BlockPlace at = block_place(s < numSides && G::side_has_segment(kind, triangles, halfedges, sp, s), waveCount);
+    if (threadIdx.x == 0) blockCount[blockIdx.x] = at.total;
 }
 
 // capacity segments fit into out; a segment whose place lies behind it is dropped (the entry point asks for numSides / 2, which holds them all)
 __global__ __launch_bounds__(WO_BLOCK) void k_globe_line_write(int32_t kind, const int32_t* __restrict__ triangles, const int32_t* __restrict__ halfedges, const float* __restrict__ sp,
                                                                const G::Center* __restrict__ centers, int32_t numSides, const int32_t* __restrict__ blockOffset,
                                                                float* __restrict__ out, int64_t capacity) {
-    __shared__ int32_t waveCount[GLOBE_WAVES];
+    __shared__ int32_t waveCount[BLOCK_WAVES];
     const int64_t s = (int64_t)blockIdx.x * WO_BLOCK + threadIdx.x;
     const bool take = s < numSides && G::side_has_segment(kind, triangles, halfedges, sp, s);
-    const unsigned long long mask = __ballot(take);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) waveCount[wave] = (int32_t)__popcll(mask);
-    __syncthreads();
-    if (!take) return;
-    int64_t at = blockOffset[blockIdx.x];
-    for (int w = 0; w < wave; ++w) at += waveCount[w];
-    at += __popcll(mask & ((1ull << lane) - 1ull));
-    if (at >= capacity) return;
+    const int64_t at = (int64_t)blockOffset[blockIdx.x] + block_place(take, waveCount).place;
+    if (!take || at >= capacity) return;
     float seg[6];
     G::line_segment(centers[s / 3], centers[halfedges[s] / 3], G::line_base(kind), seg);
     float2* o = reinterpret_cast<float2*>(out + 6 * at);      // 24 bytes per segment: 8-byte aligned
     o[0] = make_float2(seg[0], seg[1]); o[1] = make_float2(seg[2], seg[3]); o[2] = make_float2(seg[4], seg[5]);
-}
-
-static bool globe_sides_ok(const char* fn, wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges) {
-    const std::string F = std::string(fn) + ": ";
-    if (!triangles || !halfedges) { set_error(F + "null pointer"); return false; }
-    if (numSides < 3 || numSides % 3 != 0 || numSides >= (1 << 30)) { set_error(F + "numSides is " + std::to_string(numSides) + ", it must be a multiple of 3 from 3 to 2^30 - 3"); return false; }
-    std::string err;
-    if (!map_topology_ok(p->N, numSides, triangles, halfedges, err)) { set_error(F + err); return false; }
-    return true;
 }
 
 // what both mesh entry points check of their outputs
@@ -259,38 +162,46 @@ static bool globe_outputs_ok(const char* fn, int32_t numSides, const float* posi
     return true;
 }
 
-// the editor's tints over the region colours, when a highlight state is set
-static void globe_tint(wo_planet* p, float* rgb) {
-    if (rgb && highlight_classes(p)) launch(p, FAM_HIGHLIGHT, k_highlight_tint, blocks_for(p->N), WO_BLOCK, highlight_classes(p), rgb, p->N);
-}
-
-// the tables, the mesh kernel and the copies; rgb holds the region colours (nullptr without colorsOut)
-static void globe_mesh_run(wo_planet* p, DeviceArena& T, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, const float* e, const float* rgb,
-                           float* positionsOut, float* colorsOut, float bounds[6]) {
-    hipStream_t s = p->ctx->stream;
-    const size_t floats = (size_t)numSides * 9;
-    const int32_t* d_tri = up(T, triangles, (size_t)numSides, s);
-    const int32_t* d_he = positionsOut ? up(T, halfedges, (size_t)numSides, s) : nullptr;
-    G::Center* centers = nullptr;
-    float *pos = nullptr, *col = nullptr;
-    uint32_t* d_bounds = T.dev<uint32_t>(6);
-    uint32_t* h_bounds = T.pinned<uint32_t>(6);
-    if (positionsOut) {
-        centers = T.dev<G::Center>((size_t)numSides / 3);
-        pos = T.dev<float>(floats);
-        WO_HIP(hipMemsetAsync(d_bounds, 0, 24, s));
-        launch(p, FAM_GLOBE_TABLES, k_globe_centers, blocks_for(numSides / 3), WO_BLOCK, d_tri, (const float*)p->d_xyz, e, centers, numSides / 3);
-    }
-    if (colorsOut) col = T.dev<float>(floats);
-    auto* kernel = p->opt.globeDirectStores ? k_globe_mesh<false> : k_globe_mesh<true>;
-    launch(p, FAM_GLOBE_MESH, kernel, blocks_for(numSides, 1 << 23), WO_BLOCK, d_tri, d_he, (const G::Center*)centers, (const float*)p->d_xyz, e, rgb, numSides, pos, col, d_bounds);
-    if (positionsOut) {
-        WO_HIP(hipMemcpyAsync(h_bounds, d_bounds, 24, hipMemcpyDeviceToHost, s));
-        WO_HIP(hipMemcpyAsync(positionsOut, pos, floats * 4, hipMemcpyDeviceToHost, s));
-    }
-    if (colorsOut) WO_HIP(hipMemcpyAsync(colorsOut, col, floats * 4, hipMemcpyDeviceToHost, s));
-    WO_HIP(hipStreamSynchronize(s));                          // before T frees the temporaries
-    if (positionsOut && bounds) G::bounds_decode(h_bounds, bounds);
+// what both mesh entry points do once their outputs are checked: the request's checks around those of the sides, the region
+// colours (an f32 triple per region, with colorsOut only), the tables, the mesh kernel and the copies
+static int globe_mesh(wo_planet* p, const char* fn, const ViewRequest& q, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, float* positionsOut, float* colorsOut,
+                      float bounds[6]) {
+    ViewPlan plan;
+    if (!view_resolve(fn, p, q, plan, [&] { return sides_ok(fn, p, numSides, triangles, halfedges); })) return 1;
+    WO_TRY
+        DeviceArena T;                                            // the temporaries of this call
+        const float* e = stage_elevation(p, T, q.r_elevation);
+        float* rgb = nullptr;
+        if (colorsOut) {
+            rgb = T.dev<float>(3 * (size_t)p->N);
+            view_region_colors(p, T, plan, e, ViewSink{rgb, nullptr, nullptr}, {FAM_GLOBE_REGION_COLORS, FAM_GLOBE_RANGE});
+        }
+        hipStream_t s = p->ctx->stream;
+        const size_t floats = (size_t)numSides * 9;
+        const int32_t* d_tri = up(T, triangles, (size_t)numSides, s);
+        const int32_t* d_he = positionsOut ? up(T, halfedges, (size_t)numSides, s) : nullptr;
+        G::Center* centers = nullptr;
+        float *pos = nullptr, *col = nullptr;
+        uint32_t* d_bounds = T.dev<uint32_t>(6);
+        uint32_t* h_bounds = T.pinned<uint32_t>(6);
+        if (positionsOut) {
+            centers = T.dev<G::Center>((size_t)numSides / 3);
+            pos = T.dev<float>(floats);
+            WO_HIP(hipMemsetAsync(d_bounds, 0, 24, s));
+            launch(p, FAM_GLOBE_TABLES, k_globe_centers, blocks_for(numSides / 3), WO_BLOCK, d_tri, (const float*)p->d_xyz, e, centers, numSides / 3);
+        }
+        if (colorsOut) col = T.dev<float>(floats);
+        auto* kernel = p->opt.globeDirectStores ? k_globe_mesh<false> : k_globe_mesh<true>;
+        launch(p, FAM_GLOBE_MESH, kernel, blocks_for(numSides, 1 << 23), WO_BLOCK, d_tri, d_he, (const G::Center*)centers, (const float*)p->d_xyz, e, (const float*)rgb, numSides, pos, col, d_bounds);
+        if (positionsOut) {
+            WO_HIP(hipMemcpyAsync(h_bounds, d_bounds, 24, hipMemcpyDeviceToHost, s));
+            WO_HIP(hipMemcpyAsync(positionsOut, pos, floats * 4, hipMemcpyDeviceToHost, s));
+        }
+        if (colorsOut) WO_HIP(hipMemcpyAsync(colorsOut, col, floats * 4, hipMemcpyDeviceToHost, s));
+        WO_HIP(hipStreamSynchronize(s));                          // before T frees the temporaries
+        if (positionsOut && bounds) G::bounds_decode(h_bounds, bounds);
+        return 0;
+    WO_CATCH(fn)
 }
 
 }  // namespace wo
@@ -306,97 +217,22 @@ int wo_globe_mesh(wo_planet* p, int32_t numSides, const int32_t* triangles, cons
     if (!check_planet(p, fn)) return 1;
     if (!globe_outputs_ok(fn, numSides, positionsOut, colorsOut, outFloats)) return 1;
     if (source != G::SOURCE_TYPE && source != G::SOURCE_LAYER) { set_error(F + "unknown colour source " + std::to_string(source)); return 1; }
-    const bool layered = source == G::SOURCE_LAYER;
-    if (!layered && (id < 0 || id >= M::TYPE_COUNT)) { set_error(F + "unknown map type " + std::to_string(id)); return 1; }
-    if (!layered && id == M::TYPE_LANDMASK) { set_error(F + "map type " + std::to_string(id) + " (landmask) is no view of the globe: buildMesh has no such branch"); return 1; }
-    if (layered && (id < 0 || id >= M::LAYER_COUNT)) { set_error(F + "unknown map layer " + std::to_string(id)); return 1; }
-    if (!globe_sides_ok(fn, p, numSides, triangles, halfedges)) return 1;
-    const uint8_t* koppen = nullptr;
-    LayerSource S{nullptr, nullptr, nullptr, nullptr};
-    int fa = -1, fb = -1;
-    const bool current = layered && M::layer_is_ocean_current(id);
-    if (colorsOut && !layered) {
-        if (values) { set_error(F + "a map type reads the elevation, values must be NULL"); return 1; }
-        if (M::type_needs_koppen(id) && !(koppen = koppen_classes(p))) { set_error(F + "no Koppen result on this planet (call wo_classify_koppen first)"); return 1; }
-    }
-    if (colorsOut && layered) {
-        if (id == M::LAYER_DEBUG && !values) { set_error(F + "WO_MAP_LAYER_DEBUG takes its values from the caller, values is NULL"); return 1; }
-        if (current && values) { set_error(F + "an ocean-current layer reads two fields, values must be NULL (wo_ocean_upload sets the warmth and the speed)"); return 1; }
-        S = layer_source(id);
-        if (!values) {                                        // the resident field(s)
-            fa = S.block->index(S.a);
-            fb = S.b ? S.block->index(S.b) : -1;
-            if (!block_require(p, fn, *S.block, bit(fa) | (fb >= 0 ? bit(fb) : 0u), S.hint)) return 1;
-        }
-    }
-    WO_TRY
-        const int32_t N = p->N, g = blocks_for(N);
-        hipStream_t s = p->ctx->stream;
-        DeviceArena T;                                        // the temporaries of this call
-        const float* e = stage_elevation(p, T, r_elevation);
-        float* rgb = nullptr;
-        if (colorsOut) {
-            rgb = T.dev<float>(3 * (size_t)N);
-            if (!layered && id == M::TYPE_BIOME) {
-                float* raw = T.dev<float>(3 * (size_t)N);
-                map_launch_biome_raw(p, FAM_GLOBE_REGION_COLORS, e, koppen, raw, N);
-                launch(p, FAM_GLOBE_REGION_COLORS, k_globe_biome_smooth, g, WO_BLOCK, (const float*)raw, (const int32_t*)p->d_off, (const int32_t*)p->d_adj, rgb, N);
-            } else if (!layered) {
-                launch(p, FAM_GLOBE_REGION_COLORS, k_globe_type_colors, g, WO_BLOCK, id, e, koppen, rgb, N);
-            } else {
-                const float* a = values ? up(T, values, (size_t)N, s) : (const float*)S.block->slot(S.block->get(p), fa, (size_t)N).ptr;
-                const float* b = fb >= 0 ? (const float*)S.block->slot(S.block->get(p), fb, (size_t)N).ptr : nullptr;
-                uint32_t* range = T.dev<uint32_t>(2);
-                if (M::layer_needs_range(id)) {
-                    WO_HIP(hipMemsetAsync(range, 0, 8, s));
-                    map_launch_range(p, FAM_GLOBE_RANGE, a, N, range);
-                }
-                launch(p, FAM_GLOBE_REGION_COLORS, k_globe_layer_colors, g, WO_BLOCK, id, a, b, e, (const uint32_t*)range, rgb, N);
-            }
-        }
-        globe_tint(p, rgb);
-        globe_mesh_run(p, T, numSides, triangles, halfedges, e, rgb, positionsOut, colorsOut, bounds);
-        return 0;
-    WO_CATCH("wo_globe_mesh")
+    if (source == G::SOURCE_TYPE && id == M::TYPE_LANDMASK) { set_error(F + "map type " + std::to_string(id) + " (landmask) is no view of the globe: buildMesh has no such branch"); return 1; }
+    ViewRequest q;
+    q.source = source; q.id = id; q.colors = colorsOut != nullptr; q.values = values; q.r_elevation = r_elevation;
+    return globe_mesh(p, fn, q, numSides, triangles, halfedges, positionsOut, colorsOut, bounds);
 }
 
 int wo_globe_mesh_plates(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, const int32_t* r_plate, int32_t numPlates,
                          const int32_t* plateSeeds, const float* plateColors, const float* r_elevation, float* positionsOut, float* colorsOut, int64_t outFloats,
                          float bounds[6]) {
     const char* fn = "wo_globe_mesh_plates";
-    const std::string F = "wo_globe_mesh_plates: ";
     if (!check_planet(p, fn)) return 1;
     if (!globe_outputs_ok(fn, numSides, positionsOut, colorsOut, outFloats)) return 1;
-    if (colorsOut) {
-        if (!r_plate) { set_error(F + "the plate view reads r_plate, it is NULL"); return 1; }
-        if (numPlates < 0) { set_error(F + "numPlates is " + std::to_string(numPlates)); return 1; }
-        if (!plateSeeds || !plateColors) { set_error(F + "the plate view needs a colour table, " + (plateSeeds ? "plateColors" : "plateSeeds") + " is NULL"); return 1; }
-        for (int32_t i = 0; i < numPlates; ++i)
-            if ((uint32_t)plateSeeds[i] >= (uint32_t)p->N) { set_error(F + "plateSeeds[" + std::to_string(i) + "] = " + std::to_string(plateSeeds[i]) + " is no region of the planet, which has " + std::to_string(p->N)); return 1; }
-    }
-    if (!globe_sides_ok(fn, p, numSides, triangles, halfedges)) return 1;
-    WO_TRY
-        const int32_t N = p->N;
-        hipStream_t s = p->ctx->stream;
-        DeviceArena T;                                        // the temporaries of this call
-        const float* e = stage_elevation(p, T, r_elevation);
-        float* rgb = nullptr;
-        if (colorsOut) {
-            rgb = T.dev<float>(3 * (size_t)N);
-            int32_t* slot = T.dev<int32_t>((size_t)N);
-            WO_HIP(hipMemsetAsync(slot, 0xFF, (size_t)N * 4, s));
-            const int32_t* d_plate = up(T, r_plate, (size_t)N, s);
-            if (numPlates > 0) {
-                const int32_t* d_seeds = up(T, plateSeeds, (size_t)numPlates, s);
-                launch(p, FAM_GLOBE_REGION_COLORS, k_globe_plate_slots, blocks_for(numPlates), WO_BLOCK, d_seeds, numPlates, slot);
-            }
-            const float* d_colors = numPlates > 0 ? up(T, plateColors, 3 * (size_t)numPlates, s) : nullptr;
-            launch(p, FAM_GLOBE_REGION_COLORS, k_globe_plate_colors, blocks_for(N), WO_BLOCK, d_plate, (const int32_t*)slot, d_colors, rgb, N);
-        }
-        globe_tint(p, rgb);
-        globe_mesh_run(p, T, numSides, triangles, halfedges, e, rgb, positionsOut, colorsOut, bounds);
-        return 0;
-    WO_CATCH("wo_globe_mesh_plates")
+    ViewRequest q;
+    q.source = VIEW_PLATES; q.colors = colorsOut != nullptr; q.r_elevation = r_elevation;
+    q.r_plate = r_plate; q.numPlates = numPlates; q.plateSeeds = plateSeeds; q.plateColors = plateColors;
+    return globe_mesh(p, fn, q, numSides, triangles, halfedges, positionsOut, colorsOut, bounds);
 }
 
 int wo_highlight_set(wo_planet* p, const int32_t* r_plate, int32_t numPending, const int32_t* pendingPlates, const uint8_t* pendingIsOcean, int32_t hoveredPlate,
@@ -468,7 +304,7 @@ int wo_globe_lines(wo_planet* p, int32_t numSides, const int32_t* triangles, con
     if (kind == G::LINES_SUPER_PLATE_BORDERS && !superPlates) { set_error(F + "the super-plate borders read one value per region, superPlates is NULL"); return 1; }
     if (kind == G::LINES_WIREFRAME && superPlates) { set_error(F + "the wireframe reads no super-plate values, superPlates must be NULL"); return 1; }
     if (capacity < (int64_t)numSides / 2) { set_error(F + "a mesh of " + std::to_string(numSides) + " sides can give " + std::to_string(numSides / 2) + " segments, capacity is " + std::to_string(capacity)); return 1; }
-    if (!globe_sides_ok(fn, p, numSides, triangles, halfedges)) return 1;
+    if (!sides_ok(fn, p, numSides, triangles, halfedges)) return 1;
     WO_TRY
         const int32_t N = p->N, numTriangles = numSides / 3, groups = blocks_for(numSides, 1 << 23);
         const int64_t room = (int64_t)numSides / 2;
@@ -485,7 +321,7 @@ int wo_globe_lines(wo_planet* p, int32_t numSides, const int32_t* triangles, con
         float* out = T.dev<float>(6 * (size_t)room);
         launch(p, FAM_GLOBE_TABLES, k_globe_centers, blocks_for(numTriangles), WO_BLOCK, d_tri, (const float*)p->d_xyz, e, centers, numTriangles);
         launch(p, FAM_GLOBE_LINE_COUNT, k_globe_line_count, groups, WO_BLOCK, kind, d_tri, d_he, d_sp, numSides, offsets);
-        launch(p, FAM_GLOBE_LINE_SCAN, k_globe_line_scan, 1, WO_BLOCK, offsets, groups, d_total);
+        launch(p, FAM_GLOBE_LINE_SCAN, k_block_offsets<1>, 1, BLOCK_SCAN_THREADS, offsets, groups, d_total);
         launch(p, FAM_GLOBE_LINE_WRITE, k_globe_line_write, groups, WO_BLOCK, kind, d_tri, d_he, d_sp, (const G::Center*)centers, numSides, (const int32_t*)offsets, out, room);
         WO_HIP(hipMemcpyAsync(h_total, d_total, 4, hipMemcpyDeviceToHost, s));
         WO_HIP(hipStreamSynchronize(s));

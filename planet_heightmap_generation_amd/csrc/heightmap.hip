@@ -5,9 +5,9 @@
 // Launch sequence (no hipMalloc / hipFree / device-wide synchronisation inside it; scratch is allocated before it):
 //   sample          k_sample_heightmap                      one thread per cell: r_elevation and r_isOcean = e <= 0
 //   plates          k_cc_init, k_cc_hook, k_cc_flatten       union-find, min id per component (import_ops.h)
-//   lists           k_import_count, k_import_scan, k_import_scatter
+//   lists           k_import_count, k_block_offsets<4>, k_import_scatter
 //                   count: per-256-cell-block counts of the four lists; scan: one workgroup turns them into block offsets;
-//                   scatter: each block writes its cells in ascending r (ballot + prefix inside the block), so every list
+//                   scatter: each block writes its cells in ascending r (block_ops.h: block_place), so every list
 //                   comes out ascending, which is the insertion order of the reference's Sets.
 // The one synchronisation brings the list lengths back to the host; the copies of the lists follow it.
 #include <hip/hip_runtime.h>
@@ -17,13 +17,13 @@
 #include <string>
 
 #include "../../include/worogen.h"
+#include "block_ops.h"
 #include "device.h"
 #include "import_ops.h"
 
 namespace wo {
 
 constexpr int IMP_LISTS = 4;            // plateSeeds, mountain_r, coastline_r, ocean_r
-constexpr int IMP_SCAN_THREADS = 1024;
 
 __global__ __launch_bounds__(WO_BLOCK) void k_sample_heightmap(const float* __restrict__ xyz, const uint8_t* __restrict__ img, int32_t W, int32_t H,
                                                                float* __restrict__ e, uint8_t* __restrict__ ocean, int32_t N) {
@@ -59,9 +59,7 @@ __device__ inline bool imp_in_list(uint8_t f, int j) {
 __global__ __launch_bounds__(WO_BLOCK) void k_import_count(const float* __restrict__ e, const int32_t* __restrict__ off, const int32_t* __restrict__ adj,
                                                            const int32_t* __restrict__ label, int32_t N, uint8_t* __restrict__ flags,
                                                            int32_t* __restrict__ blockCounts) {
-    __shared__ int32_t cnt[IMP_LISTS];
-    if (threadIdx.x < IMP_LISTS) cnt[threadIdx.x] = 0;
-    __syncthreads();
+    __shared__ int32_t waveCnt[IMP_LISTS][BLOCK_WAVES];
     const int32_t r = blockIdx.x * WO_BLOCK + threadIdx.x;
     uint8_t f = 0;
     if (r < N) {
@@ -69,64 +67,22 @@ __global__ __launch_bounds__(WO_BLOCK) void k_import_count(const float* __restri
         if (label && label[r] == r) f |= (f & imp::CLS_OCEAN) ? (imp::CLS_SEED | imp::CLS_SEED_OCEAN) : imp::CLS_SEED;
         flags[r] = f;
     }
-    const int lane = threadIdx.x & (warpSize - 1);
     for (int j = 0; j < IMP_LISTS; ++j) {
-        const unsigned long long m = __ballot(imp_in_list(f, j));
-        if (lane == 0 && m) atomicAdd(&cnt[j], (int32_t)__popcll(m));
+        const int32_t n = block_place(imp_in_list(f, j), waveCnt[j]).total;
+        if (threadIdx.x == 0) blockCounts[(int64_t)blockIdx.x * IMP_LISTS + j] = n;
     }
-    __syncthreads();
-    if (threadIdx.x < IMP_LISTS) blockCounts[(int64_t)blockIdx.x * IMP_LISTS + threadIdx.x] = cnt[threadIdx.x];
-}
-
-// One workgroup: blockCounts[b][j] -> exclusive offset of block b in list j; totals[j] = length of list j.
-__global__ __launch_bounds__(IMP_SCAN_THREADS) void k_import_scan(int32_t* __restrict__ blockCounts, int32_t nBlocks, int32_t* __restrict__ totals) {
-    __shared__ int32_t part[2][IMP_LISTS][IMP_SCAN_THREADS];
-    const int t = threadIdx.x;
-    const int32_t chunk = (nBlocks + IMP_SCAN_THREADS - 1) / IMP_SCAN_THREADS;
-    const int32_t b0 = std::min<int64_t>((int64_t)t * chunk, nBlocks), b1 = std::min<int64_t>((int64_t)b0 + chunk, nBlocks);
-    int32_t s[IMP_LISTS] = {0, 0, 0, 0};
-    for (int32_t b = b0; b < b1; ++b)
-        for (int j = 0; j < IMP_LISTS; ++j) s[j] += blockCounts[(int64_t)b * IMP_LISTS + j];
-    for (int j = 0; j < IMP_LISTS; ++j) part[0][j][t] = s[j];
-    __syncthreads();
-    int cur = 0;
-    for (int d = 1; d < IMP_SCAN_THREADS; d <<= 1) {         // inclusive Hillis-Steele scan of the chunk sums
-        for (int j = 0; j < IMP_LISTS; ++j) part[cur ^ 1][j][t] = part[cur][j][t] + (t >= d ? part[cur][j][t - d] : 0);
-        cur ^= 1;
-        __syncthreads();
-    }
-    int32_t run[IMP_LISTS];
-    for (int j = 0; j < IMP_LISTS; ++j) run[j] = part[cur][j][t] - s[j];
-    for (int32_t b = b0; b < b1; ++b)
-        for (int j = 0; j < IMP_LISTS; ++j) {
-            const int32_t c = blockCounts[(int64_t)b * IMP_LISTS + j];
-            blockCounts[(int64_t)b * IMP_LISTS + j] = run[j];
-            run[j] += c;
-        }
-    if (t == IMP_SCAN_THREADS - 1)
-        for (int j = 0; j < IMP_LISTS; ++j) totals[j] = part[cur][j][t];
 }
 
 // Each block writes its cells of every list at the block's offset, in ascending r.
 __global__ __launch_bounds__(WO_BLOCK) void k_import_scatter(const uint8_t* __restrict__ flags, const int32_t* __restrict__ blockOffsets, int32_t N,
                                                              int32_t* __restrict__ lists, uint8_t* __restrict__ seedOcean) {
-    constexpr int WAVES = WO_BLOCK / 64;
-    __shared__ int32_t waveCnt[IMP_LISTS][WAVES];
+    __shared__ int32_t waveCnt[IMP_LISTS][BLOCK_WAVES];
     const int32_t r = blockIdx.x * WO_BLOCK + threadIdx.x;
     const uint8_t f = r < N ? flags[r] : 0;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    unsigned long long m[IMP_LISTS];
     for (int j = 0; j < IMP_LISTS; ++j) {
-        m[j] = __ballot(imp_in_list(f, j));
-        if (lane == 0) waveCnt[j][wave] = (int32_t)__popcll(m[j]);
-    }
-    __syncthreads();
-    for (int j = 0; j < IMP_LISTS; ++j) {
-        if (!imp_in_list(f, j)) continue;
-        int32_t pos = blockOffsets[(int64_t)blockIdx.x * IMP_LISTS + j];
-        for (int w = 0; w < wave; ++w) pos += waveCnt[j][w];
-        pos += (int32_t)__popcll(m[j] & below);
+        const bool in = imp_in_list(f, j);
+        const int32_t pos = blockOffsets[(int64_t)blockIdx.x * IMP_LISTS + j] + block_place(in, waveCnt[j]).place;
+        if (!in) continue;
         lists[(int64_t)j * N + pos] = r;
         if (j == 0) seedOcean[pos] = (f & imp::CLS_SEED_OCEAN) ? 1 : 0;
     }
@@ -155,7 +111,7 @@ static void import_lists(wo_planet* p, bool withPlates, int32_t (&len)[IMP_LISTS
     hipStream_t s = p->ctx->stream;
     launch(p, FAM_MISC, k_import_count, nB, WO_BLOCK, (const float*)p->d_e, (const int32_t*)p->d_off, (const int32_t*)p->d_adj,
            (const int32_t*)(withPlates ? I.label : nullptr), N, I.flags, I.blockCounts);
-    launch(p, FAM_MISC, k_import_scan, 1, IMP_SCAN_THREADS, I.blockCounts, nB, I.totals);
+    launch(p, FAM_MISC, k_block_offsets<IMP_LISTS>, 1, BLOCK_SCAN_THREADS, I.blockCounts, nB, I.totals);
     launch(p, FAM_MISC, k_import_scatter, nB, WO_BLOCK, (const uint8_t*)I.flags, (const int32_t*)I.blockCounts, N, I.lists, I.seedOcean);
     WO_HIP(hipMemcpyAsync(I.h_totals, I.totals, IMP_LISTS * 4, hipMemcpyDeviceToHost, s));
     WO_HIP(hipStreamSynchronize(s));

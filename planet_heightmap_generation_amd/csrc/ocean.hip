@@ -26,6 +26,7 @@
 #include <string>
 
 #include "../../include/worogen.h"
+#include "block_ops.h"
 #include "device.h"
 #include "ocean_block.h"
 #include "ocean_ops.h"
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_ocean_seed(const uint8_t* __restri
         distW[r] = seed == O::SEED_WEST ? 0 : -1;
         distE[r] = seed == O::SEED_EAST ? 0 : -1;
     }
-    wind_append(seed != O::SEED_NONE, ((seed == O::SEED_EAST ? 1 : 0) << O::FIELD_SHIFT) | r, list, counter);
+    wave_append(seed != O::SEED_NONE, ((seed == O::SEED_EAST ? 1 : 0) << O::FIELD_SHIFT) | r, list, counter);
 }
 
 // one level of both fields: a frontier entry claims the unreached ocean neighbours of its cell in its own field.  A
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_ocean_level(const int32_t* __restr
     if (blockIdx.x == 0 && threadIdx.x == 0) counts[zeroIdx] = 0;
     int32_t n = counts[curIdx];
     if (n > cap) n = cap;
-    for (int32_t base = blockIdx.x * blockDim.x; base < n; base += gridDim.x * blockDim.x) {      // block-uniform trips: the waves stay whole for wind_append
+    for (int32_t base = blockIdx.x * blockDim.x; base < n; base += gridDim.x * blockDim.x) {      // block-uniform trips: the waves stay whole for wave_append
         const int32_t i = base + threadIdx.x;
         const bool valid = i < n;
         const int32_t entry = valid ? cur[i] : 0;
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_ocean_level(const int32_t* __restr
                 nb = adj[b + k];
                 claim = isOcean[nb] && dist[nb] == -1 && atomicCAS(&dist[nb], -1, level) == -1;
             }
-            wind_append(claim, (field << O::FIELD_SHIFT) | nb, next, counts + nextIdx);
+            wave_append(claim, (field << O::FIELD_SHIFT) | nb, next, counts + nextIdx);
         }
     }
 }

@@ -11,14 +11,15 @@
 //                           an atomic and never a result: the same minimum, the same bits, but every lane then waits for a load
 //                           from L2, and the form measured three times slower (the A/B of DESIGN section 8.12).
 //   k_overlay_winners [1]   the keys as region ids (wo_overlay_bins only)
-//   k_overlay_arrows [1]    one workgroup walks the 7200 bins in ascending order, 256 at a time: ballot and popcount give every kept
-//                           bin its place, and its lane writes the four runs of 18 floats there
+//   k_overlay_arrows [1]    one workgroup walks the 7200 bins in ascending order, 256 at a time: block_ops.h's block_place gives every
+//                           kept bin its place, and its lane writes the four runs of 18 floats there
 // Memory (device_mem.h): everything is a temporary of the call, in an arena on its stack.
 #include <hip/hip_runtime.h>
 
 #include <string>
 
 #include "../../include/worogen.h"
+#include "block_ops.h"
 #include "device.h"
 #include "ocean_block.h"
 #include "overlay_ops.h"
@@ -31,8 +32,6 @@ static_assert(V::KIND_WIND == WO_OVERLAY_WIND && V::KIND_OCEAN == WO_OVERLAY_OCE
 static_assert(V::BINS == WO_OVERLAY_BINS, "the bin count of overlay_ops.h is that of worogen.h");
 
 namespace wo {
-
-constexpr int OVERLAY_WAVES = WO_BLOCK / 64;
 
 // keys: BINS words, filled with EMPTY_KEY; e is read with skipLand only
 template <bool PRECHECK>
@@ -58,8 +57,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_overlay_arrows(int32_t kind, const
                                                              const float* __restrict__ b, const float* __restrict__ speed, const float* __restrict__ warmth, double centerLon,
                                                              float* __restrict__ globePos, float* __restrict__ globeCol, float* __restrict__ mapPos, float* __restrict__ mapCol,
                                                              int32_t* __restrict__ total) {
-    __shared__ int32_t waveCount[OVERLAY_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int32_t waveCount[BLOCK_WAVES];
     int32_t base = 0;
     for (int32_t first = 0; first < V::BINS; first += WO_BLOCK) {
         const int32_t i = first + (int32_t)threadIdx.x;
@@ -71,18 +69,13 @@ __global__ __launch_bounds__(WO_BLOCK) void k_overlay_arrows(int32_t kind, const
             if (kind == V::KIND_OCEAN) { src.speed = speed[r]; src.warmth = warmth[r]; }
             keep = !V::is_slow(kind, V::speed_of(kind, src));
         }
-        const unsigned long long mask = __ballot(keep);
-        if (lane == 0) waveCount[wave] = (int32_t)__popcll(mask);
-        __syncthreads();
-        int32_t at = base, all = 0;
-        for (int w = 0; w < OVERLAY_WAVES; ++w) { if (w < wave) at += waveCount[w]; all += waveCount[w]; }
+        const BlockPlace at = block_place(keep, waveCount);
         if (keep) {
-            at += (int32_t)__popcll(mask & ((1ull << lane) - 1ull));          // at < BINS: at most one arrow per bin
             const float p[3] = {xyz[3 * (int64_t)r], xyz[3 * (int64_t)r + 1], xyz[3 * (int64_t)r + 2]};
-            const int64_t o = (int64_t)at * V::ARROW_FLOATS;
+            const int64_t o = (int64_t)(base + at.place) * V::ARROW_FLOATS;      // base + place < BINS: at most one arrow per bin
             V::arrow(kind, p, src, centerLon, globePos ? globePos + o : nullptr, globeCol ? globeCol + o : nullptr, mapPos ? mapPos + o : nullptr, mapCol ? mapCol + o : nullptr);
         }
-        base += all;
+        base += at.total;
         __syncthreads();                                      // waveCount is free again
     }
     if (threadIdx.x == 0) *total = base;

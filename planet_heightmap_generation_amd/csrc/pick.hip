@@ -21,6 +21,7 @@
 #include <string>
 
 #include "../../include/worogen.h"
+#include "block_ops.h"
 #include "device.h"
 #include "pick_ops.h"
 
@@ -28,31 +29,32 @@ namespace P = wo::pick;
 
 static_assert(P::MAX_QUERIES == WO_PICK_MAX_QUERIES, "the query limit of pick_ops.h is that of worogen.h");
 
+// block_ops.h's wave_reduce finds it in Best's namespace: the pair goes field by field
+namespace wo { namespace pick {
+__device__ inline Best lane_down(Best b, int d) { return Best{__shfl_down(b.dot, d, 64), __shfl_down(b.idx, d, 64)}; }
+} }
+
 namespace wo {
 
-constexpr int PICK_WAVES = WO_BLOCK / 64;
 constexpr int PICK_BLOCKS = 1024;                     // workgroups per tile at most: four per compute unit
 constexpr int64_t PICK_PARTIALS = 1 << 20;            // partials per batch at most (12 MB)
 
-// the workgroup's best entry under P::beats; the result is valid in thread 0.  sDot / sIdx: PICK_WAVES entries, free to be overwritten.
+// the workgroup's best entry under P::beats; the result is valid in thread 0.  sDot / sIdx: BLOCK_WAVES entries, free to be overwritten.
 __device__ inline P::Best pick_block_best(P::Best b, double* sDot, int32_t* sIdx) {
-    for (int d = 32; d > 0; d >>= 1) {
-        const P::Best o{__shfl_down(b.dot, d, 64), __shfl_down(b.idx, d, 64)};
-        b = P::better_of(b, o);
-    }
+    b = wave_reduce(b, [](P::Best x, P::Best y) { return P::better_of(x, y); });
     __syncthreads();                                          // the previous use of sDot / sIdx is over
     if ((threadIdx.x & 63) == 0) { sDot[threadIdx.x >> 6] = b.dot; sIdx[threadIdx.x >> 6] = b.idx; }
     __syncthreads();
     if (threadIdx.x == 0)
-        for (int w = 1; w < PICK_WAVES; ++w) b = P::better_of(b, P::Best{sDot[w], sIdx[w]});
+        for (int w = 1; w < BLOCK_WAVES; ++w) b = P::better_of(b, P::Best{sDot[w], sIdx[w]});
     return b;
 }
 
 // queries: 3 doubles per query, padded to whole tiles with NaN.  The grid is `blocks` workgroups per tile of the batch, tile by tile.
 __global__ __launch_bounds__(WO_BLOCK) void k_pick(const float* __restrict__ xyz, int32_t N, const double* __restrict__ queries, int32_t tile0, int32_t blocks,
                                                    double* __restrict__ partDot, int32_t* __restrict__ partIdx) {
-    __shared__ double sDot[PICK_WAVES];
-    __shared__ int32_t sIdx[PICK_WAVES];
+    __shared__ double sDot[BLOCK_WAVES];
+    __shared__ int32_t sIdx[BLOCK_WAVES];
     const int32_t tile = (int32_t)blockIdx.x / blocks, block = (int32_t)blockIdx.x % blocks;      // the tile within the batch
     const double* __restrict__ q = queries + (int64_t)(tile0 + tile) * (P::TILE * 3);
     P::Best best[P::TILE];
@@ -77,8 +79,8 @@ __global__ __launch_bounds__(WO_BLOCK) void k_pick(const float* __restrict__ xyz
 // workgroup i reduces the `parts` partials of query tile0 * TILE + i
 __global__ __launch_bounds__(WO_BLOCK) void k_pick_reduce(const double* __restrict__ partDot, const int32_t* __restrict__ partIdx, int32_t parts, int32_t tile0, int32_t numQueries,
                                                           int32_t* __restrict__ regions, double* __restrict__ dots) {
-    __shared__ double sDot[PICK_WAVES];
-    __shared__ int32_t sIdx[PICK_WAVES];
+    __shared__ double sDot[BLOCK_WAVES];
+    __shared__ int32_t sIdx[BLOCK_WAVES];
     const int64_t query = (int64_t)tile0 * P::TILE + blockIdx.x;
     if (query >= numQueries) return;                          // the whole workgroup: a query of the last tile's padding
     const int64_t base = (int64_t)blockIdx.x * parts;

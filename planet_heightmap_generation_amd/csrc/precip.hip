@@ -29,6 +29,7 @@
 #include <string>
 
 #include "../../include/worogen.h"
+#include "block_ops.h"
 #include "device.h"
 #include "ocean_block.h"
 #include "precip_block.h"
@@ -118,8 +119,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_precip_weights(const int32_t* __re
         }
     }
     for (int k = 0; k < 4; ++k) {
-        uint32_t v = c[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+        const uint32_t v = wave_sum(c[k]);
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&ctl->lists[k], v);
     }
 }

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/worogen.h"
+#include "block_ops.h"
 #include "device.h"
 #include "wind_block.h"
 #include "wind_ops.h"
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_wind_bfs_seed(int32_t mode, const 
         seed = mode == 0 ? W::coast_seed_cell(isLand, label, W::main_ocean_root(*mainKey), off, adj, r) : W::plate_seed_cell(plateOcean, off, adj, r);
         dist[r] = seed ? 0 : -1;
     }
-    wind_append(seed, r, list, counter);
+    wave_append(seed, r, list, counter);
 }
 // one level: frontier cells claim their unreached neighbours inside the region (mask[nb] == want) by CAS -1 -> level
 __global__ __launch_bounds__(WO_BLOCK) void k_wind_bfs_level(const int32_t* __restrict__ cur, int32_t n, const uint8_t* __restrict__ mask, uint8_t want,
@@ -137,13 +138,13 @@ __global__ __launch_bounds__(WO_BLOCK) void k_wind_bfs_level(const int32_t* __re
     if (i == 0) *zeroCount = 0;
     const int32_t r = i < n ? cur[i] : 0;
     const int32_t b = i < n ? off[r] : 0, deg = i < n ? off[r + 1] - b : 0;
-    for (int32_t k = 0; __any(k < deg); ++k) {                // the wave stays together for wind_append
+    for (int32_t k = 0; __any(k < deg); ++k) {                // the wave stays together for wave_append
         bool claim = false; int32_t nb = -1;
         if (k < deg) {
             nb = adj[b + k];
             claim = mask[nb] == want && dist[nb] == -1 && atomicCAS(&dist[nb], -1, level) == -1;
         }
-        wind_append(claim, nb, next, nextCount);
+        wave_append(claim, nb, next, nextCount);
     }
 }
 

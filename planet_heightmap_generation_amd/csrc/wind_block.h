@@ -1,5 +1,5 @@
 // The wind block of a planet: results and scratch of wo_compute_wind (wind.hip).  The ocean-current stage (ocean.hip) reads
-// its results and borrows its scratch, so the block, its field keys and the wave-convergent append live here.
+// its results and borrows its scratch, so the block and its field keys live here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,16 +48,5 @@ const BlockDesc& wind_desc();                                 // wind.hip: the b
 void wind_alloc(wo_planet* p);
 // wind.hip: computeGradients (js/wind.js:306-339) of a device-resident field
 void gradient_resident(wo_planet* p, const float* field, const wind::Frames& T, float* gradE, float* gradN);
-
-// append the flagged lanes' values with one atomic per wave; every lane of the wave calls it together
-__device__ inline void wind_append(bool flag, int32_t value, int32_t* list, int32_t* counter) {
-    const unsigned long long m = __ballot(flag);
-    if (m == 0) return;
-    const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
-    int32_t base = 0;
-    if (lane == leader) base = atomicAdd(counter, (int32_t)__popcll(m));
-    base = __shfl(base, leader);
-    if (flag) list[base + (int32_t)__popcll(m & ((1ull << lane) - 1ull))] = value;
-}
 
 }  // namespace wo

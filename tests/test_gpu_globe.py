@@ -155,6 +155,35 @@ def test_lines_and_the_compaction():
         pl.close()
 
 
+# regions -> workgroups of the line kernels (a sphere of R regions has 6 R - 12 sides, BLOCK sides per workgroup).  The scan of the
+# workgroup counts (csrc/block_ops.h: k_block_offsets, one workgroup of 1024 threads) sees one count; 256 and 257; 1024 and 1025, where
+# a thread's run grows from one count to two.  86, 21 846 and 21 931 regions lie between those thresholds.
+SCAN_SHAPES = {44: 1, 86: 2, 10924: 256, 10925: 257, 21846: 512, 21931: 514, 43692: 1024, 43693: 1025}
+
+
+@pytest.mark.parametrize("regions", sorted(SCAN_SHAPES))
+def test_lines_over_the_scan_of_the_workgroup_counts(regions):
+    """the wireframe (every workgroup full but the last) and the borders of five sectors (most workgroups empty, the others partly
+    full) equal the emulator's segments, on meshes from the project's own builder"""
+    from planet_heightmap_generation_amd import globe_export as GE
+    mesh, xyz = GC.small_sphere(regions)
+    tri, he = mesh.triangles, mesh.halfedges
+    assert tri.size == 6 * regions - 12 and -(-tri.size // BLOCK) == SCAN_SHAPES[regions]
+    e = GC.rough_elevation(xyz, 11)
+    sp = GC.sector_plates(xyz)
+    want_wire, sides = GC.emu_lines(GC.WIREFRAME, xyz, e, tri, he)
+    want_borders, border_sides = GC.emu_lines(GC.BORDERS, xyz, e, tri, he, sp)
+    assert sides.size == tri.size // 2 and 0 < border_sides.size < sides.size
+    pl = _planet(mesh, xyz)
+    try:
+        got_wire = GE.wireframe(pl, mesh, r_elevation=e)
+        got_borders = GE.super_plate_borders(pl, mesh, sp, r_elevation=e)
+    finally:
+        pl.close()
+    assert got_wire.size == want_wire.size and same(got_wire, want_wire)
+    assert got_borders.size == want_borders.size and same(got_borders, want_borders)
+
+
 def test_exactly_one_side():
     """Exactly one qualifying side, at the four places where the compaction's offsets change hands.  A field on the regions of a
     real mesh cuts closed curves, never one edge; so the corners are renamed: every side starts at region 0 but the chosen one, which
