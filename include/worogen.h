@@ -113,6 +113,18 @@ int wo_noise_eval(wo_ctx* ctx, double seed, int32_t kind, int32_t octaves, doubl
 /* ------------------------------------------------ context / planet handle --------------------- */
 wo_ctx* wo_ctx_create(int32_t device);              /* NULL on failure (see wo_last_error)        */
 void    wo_ctx_destroy(wo_ctx* ctx);
+/* The mesh producer on the device (csrc/mesh.hip, the bodies in csrc/mesh_ops.h): every array equals, word for word, what the host
+ * sequence gives on the same points.  wo_sphere_delaunay_device is wo_sphere_delaunay.  wo_sphere_mesh_device is the whole product
+ * in one call: wo_sphere_delaunay, wo_sphere_reference_closure when referenceClosure is non-zero, wo_mesh_csr and
+ * wo_neighbor_dist.  triangles / halfedges have 3*(2*numRegions-4) entries, adjOffset numRegions+1; adjList, adjTriList (may be
+ * NULL) and neighborDist (may be NULL) have room for 3*(2*numRegions-4) entries, of which the first adjOffset[numRegions] are
+ * written.  Status and message are the host's on the same input: 1 bad arguments (a NULL context or pointer, fewer than 4 points,
+ * a zero-length point; a NULL context never touches the device), 2 star construction failed, 3 triangle count != 2V-4,
+ * 4 unmatched half-edges; 5 stands for any failure of the CSR stage, which a triangulation that passed 3 and 4 does not reach.
+ * Nothing stays allocated after the call. */
+int wo_sphere_delaunay_device(wo_ctx* ctx, int32_t numRegions, const float* r_xyz, int32_t* triangles, int32_t* halfedges);
+int wo_sphere_mesh_device(wo_ctx* ctx, int32_t numRegions, const float* r_xyz, int32_t referenceClosure, int32_t* triangles,
+                          int32_t* halfedges, int32_t* adjOffset, int32_t* adjList, int32_t* adjTriList, float* neighborDist);
 /* Uploads the mesh once (the worker keeps mesh / r_xyz / neighborDist in W between commands,
  * js/planet-worker.js:277-292).  neighborDist may be NULL: it is then computed on the device. */
 wo_planet* wo_planet_create(wo_ctx* ctx, int32_t numRegions, const int32_t* adjOffset,

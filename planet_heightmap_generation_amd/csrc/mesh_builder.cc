@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "host_util.h"
+#include "mesh_ops.h"
 #include "wo_internal.h"
 
 namespace wo {
@@ -70,30 +71,11 @@ void fib_sphere_points(int N, double jitter, double seed, float* xyz /* 3*(N+1) 
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-struct P3 { double x, y, z; };
+using mesh::P3;
+using mesh::Orient;
+using mesh::MAX_STAR;
 
-// det[b-a, c-a, d-a] evaluated on the index-sorted tuple; sign fixed up by permutation parity so the
-// floating-point value (and therefore every decision) is identical from whichever star asks.
-struct Orient {
-    const P3* pts;
-    inline double raw(int a, int b, int c, int d) const {
-        const P3 &A = pts[a], &B = pts[b], &C = pts[c], &D = pts[d];
-        const double bx = B.x - A.x, by = B.y - A.y, bz = B.z - A.z;
-        const double cx = C.x - A.x, cy = C.y - A.y, cz = C.z - A.z;
-        const double dx = D.x - A.x, dy = D.y - A.y, dz = D.z - A.z;
-        return bx * (cy * dz - cz * dy) - by * (cx * dz - cz * dx) + bz * (cx * dy - cy * dx);
-    }
-    inline double operator()(int a, int b, int c, int d) const {
-        int v[4] = {a, b, c, d};
-        int sgn = 1;
-        // 4-element sorting network, tracking parity
-#define WO_CSWAP(i, j) if (v[i] > v[j]) { int t = v[i]; v[i] = v[j]; v[j] = t; sgn = -sgn; }
-        WO_CSWAP(0, 1) WO_CSWAP(2, 3) WO_CSWAP(0, 2) WO_CSWAP(1, 3) WO_CSWAP(1, 2)
-#undef WO_CSWAP
-        return sgn * raw(v[0], v[1], v[2], v[3]);
-    }
-};
-
+// the grid's tables; mesh_ops.h's GridView reads them
 struct Grid {
     double h;       // cell edge
     int G;          // cells per axis
@@ -103,29 +85,7 @@ struct Grid {
     std::vector<uint64_t> hkey;      // open-addressing table: key+1 (0 = empty)
     std::vector<int> hval;
     uint64_t hmask;
-
-    inline int coord(double v) const {
-        int c = (int)std::floor((v + 1.0) / h);
-        if (c < 0) c = 0;
-        if (c >= G) c = G - 1;
-        return c;
-    }
-    inline uint64_t key(int ix, int iy, int iz) const {
-        return (uint64_t)ix + (uint64_t)G * ((uint64_t)iy + (uint64_t)G * (uint64_t)iz);
-    }
-    static inline uint64_t mix(uint64_t k) {
-        k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
-        return k;
-    }
-    inline int find(uint64_t k) const {
-        uint64_t slot = mix(k) & hmask;
-        for (;;) {
-            uint64_t v = hkey[slot];
-            if (v == 0) return -1;
-            if (v == k + 1) return hval[slot];
-            slot = (slot + 1) & hmask;
-        }
-    }
+    mesh::GridView view() const { return mesh::GridView{h, G, hkey.data(), hval.data(), hmask, cellStart.data(), sortedIdx.data()}; }
 };
 
 void radix_sort_pairs(std::vector<uint64_t>& keys, std::vector<int>& vals, int bits) {
@@ -146,18 +106,18 @@ void radix_sort_pairs(std::vector<uint64_t>& keys, std::vector<int>& vals, int b
 }
 
 void build_grid(Grid& g, const P3* pts, int V) {
-    const double spacing = std::sqrt(4.0 * 3.141592653589793 / (double)V);
-    g.h = 2.0 * spacing;
-    if (g.h > 0.5) g.h = 0.5;
-    g.G = (int)std::ceil(2.0 / g.h) + 1;
+    mesh::grid_dims(V, g.h, g.G);
     std::vector<uint64_t> keys(V);
     std::vector<int> vals(V);
-    parallel_ranges(V, [&](int64_t b, int64_t e, int) {
-        for (int64_t i = b; i < e; ++i) {
-            keys[i] = g.key(g.coord(pts[i].x), g.coord(pts[i].y), g.coord(pts[i].z));
-            vals[i] = (int)i;
-        }
-    });
+    {
+        const mesh::GridView gv = g.view();      // coord and key read h and G only
+        parallel_ranges(V, [&](int64_t b, int64_t e, int) {
+            for (int64_t i = b; i < e; ++i) {
+                keys[i] = gv.key(gv.coord(pts[i].x), gv.coord(pts[i].y), gv.coord(pts[i].z));
+                vals[i] = (int)i;
+            }
+        });
+    }
     int bits = 1;
     { uint64_t mx = (uint64_t)g.G * g.G * g.G; while ((1ULL << bits) < mx) ++bits; }
     radix_sort_pairs(keys, vals, bits);
@@ -171,113 +131,85 @@ void build_grid(Grid& g, const P3* pts, int V) {
     while (cap < g.cellKey.size() * 2 + 8) cap <<= 1;
     g.hkey.assign(cap, 0); g.hval.assign(cap, -1); g.hmask = cap - 1;
     for (size_t c = 0; c < g.cellKey.size(); ++c) {
-        uint64_t slot = Grid::mix(g.cellKey[c]) & g.hmask;
+        uint64_t slot = mesh::GridView::mix(g.cellKey[c]) & g.hmask;
         while (g.hkey[slot] != 0) slot = (slot + 1) & g.hmask;
         g.hkey[slot] = g.cellKey[c] + 1; g.hval[slot] = (int)c;
     }
 }
 
-constexpr int MAX_STAR = 48;
+// the candidate list of mesh_ops.h on a vector
+struct VecCand {
+    std::vector<int>& v;
+    size_t size() const { return v.size(); }
+    int operator[](int i) const { return v[i]; }
+    void push(int q) { v.push_back(q); }
+};
 
 // Star of p (neighbours counter-clockwise seen from outside).  Returns degree, or <0 on failure.
-int star_of(int p, const P3* pts, int V, const Grid& g, const Orient& orient, int* out,
-            std::vector<int>& cand) {
+int star_of(int p, const P3* pts, int V, const mesh::GridView& g, int* out, std::vector<int>& candStore) {
     const P3 P = pts[p];
     const int cx = g.coord(P.x), cy = g.coord(P.y), cz = g.coord(P.z);
     int failcode = -1;
-    for (int level = 1; level <= 6; ++level) {
-        cand.clear();
-        const bool brute = (level == 6) || ((2 * level + 1) >= g.G);
-        if (brute) {
-            for (int i = 0; i < V; ++i) if (i != p) cand.push_back(i);
-        } else {
-            for (int dz = -level; dz <= level; ++dz) {
-                int iz = cz + dz; if (iz < 0 || iz >= g.G) continue;
-                for (int dy = -level; dy <= level; ++dy) {
-                    int iy = cy + dy; if (iy < 0 || iy >= g.G) continue;
-                    for (int dx = -level; dx <= level; ++dx) {
-                        int ix = cx + dx; if (ix < 0 || ix >= g.G) continue;
-                        int c = g.find(g.key(ix, iy, iz));
-                        if (c < 0) continue;
-                        for (int k = g.cellStart[c]; k < g.cellStart[c + 1]; ++k) {
-                            int q = g.sortedIdx[k];
-                            if (q != p) cand.push_back(q);
-                        }
-                    }
-                }
-            }
-        }
-        if (cand.size() < 3) continue;
-        // nearest candidate (lowest index on ties) is always a Delaunay neighbour
-        int q0 = -1; double best = 1e300;
-        for (int q : cand) {
-            const double dx = pts[q].x - P.x, dy = pts[q].y - P.y, dz = pts[q].z - P.z;
-            const double d2 = dx * dx + dy * dy + dz * dz;
-            if (d2 < best || (d2 == best && q < q0)) { best = d2; q0 = q; }
-        }
-        int deg = 0; bool ok = true; bool certified = true;
-        // searched block in coordinates (cells cx-level .. cx+level); the grid origin is -1
-        const double lox = (cx - level) * g.h - 1.0, hix = (cx + level + 1) * g.h - 1.0;
-        const double loy = (cy - level) * g.h - 1.0, hiy = (cy + level + 1) * g.h - 1.0;
-        const double loz = (cz - level) * g.h - 1.0, hiz = (cz + level + 1) * g.h - 1.0;
-        int q = q0;
-        for (;;) {
-            if (deg >= MAX_STAR) { ok = false; failcode = -2;
-                break; }
-            out[deg++] = q;
-            // Jarvis step: r such that every other candidate lies on the origin side of plane (p,q,r)
-            int r = -1;
-            for (int s : cand) {
-                if (s == q) continue;
-                if (r < 0) { r = s; continue; }
-                if (orient(p, q, r, s) > 0.0) r = s;
-            }
-            // circumcap of (p,q,r): centre direction n = (q-p)x(r-p) (outward).  Every point of the cap is
-            // within chord distance |c - p| of the centre c = n/|n|; the face is certified empty when that
-            // ball lies inside the searched block of grid cells.
-            {
-                const P3 &Q = pts[q], &R = pts[r];
-                const double ax = Q.x - P.x, ay = Q.y - P.y, az = Q.z - P.z;
-                const double bx = R.x - P.x, by = R.y - P.y, bz = R.z - P.z;
-                double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
-                const double nl = std::sqrt(nx * nx + ny * ny + nz * nz);
-                if (!(nl > 0.0)) { ok = false; failcode = -3; break; }
-                nx /= nl; ny /= nl; nz /= nl;
-                if (nx * P.x + ny * P.y + nz * P.z <= 0.0) { certified = false; }
-                else {
-                    const double ex = nx - P.x, ey = ny - P.y, ez = nz - P.z;
-                    const double rad = std::sqrt(ex * ex + ey * ey + ez * ez) * 1.000001 + 1e-12;
-                    if (nx - rad < lox || nx + rad > hix || ny - rad < loy || ny + rad > hiy ||
-                        nz - rad < loz || nz + rad > hiz) certified = false;
-                }
-            }
-            q = r;
-            if (q == q0) break;
-        }
-        if (!ok) continue;
-        if (brute || certified) return deg;
+    VecCand cand{candStore};
+    for (int level = 1; level <= mesh::MAX_LEVEL; ++level) {
+        candStore.clear();
+        const bool brute = mesh::level_is_brute(level, g.G);
+        mesh::gather_candidates(p, V, g, cx, cy, cz, level, brute, cand);
+        const int d = mesh::star_at_level(p, pts, g, cx, cy, cz, level, brute, cand, out, failcode);
+        if (d >= 0) return d;
     }
     return failcode;
 }
 
+// the normalised points; false: a zero-length point
+bool normalise_points(int V, const float* xyz, std::vector<P3>& pts) {
+    pts.resize(V);
+    for (int i = 0; i < V; ++i)
+        if (!mesh::normalise(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], pts[i])) return false;
+    return true;
+}
+
 }  // namespace
+
+// The stars of the listed points, as sphere_delaunay computes them (the device builder's completion, mesh.hip): degOut[i] is the
+// degree of ids[i], 0 for a failed star, and starsOut holds the stars back to back, rotated to their lowest neighbour.
+// Returns the number of failed stars, -1 for a zero-length point.
+int stars_on_host(int V, const float* xyz, int n, const int* ids, std::vector<int>& degOut, std::vector<int>& starsOut) {
+    std::vector<P3> pts;
+    if (!normalise_points(V, xyz, pts)) return -1;
+    Grid g;
+    build_grid(g, pts.data(), V);
+    const mesh::GridView gv = g.view();
+    degOut.assign(n, 0);
+    std::vector<int> flat((size_t)n * MAX_STAR);
+    std::atomic<int> failed{0};
+    parallel_ranges(n, [&](int64_t b, int64_t e, int) {
+        std::vector<int> cand; cand.reserve(256);
+        int st[MAX_STAR];
+        for (int64_t i = b; i < e; ++i) {
+            const int d = star_of(ids[i], pts.data(), V, gv, st, cand);
+            if (d < 3) { failed.fetch_add(1); continue; }
+            const int m = mesh::lowest_position(st, d);
+            degOut[i] = d;
+            for (int k = 0; k < d; ++k) flat[(size_t)i * MAX_STAR + k] = st[(m + k) % d];
+        }
+    }, 64);
+    starsOut.clear();
+    for (int i = 0; i < n; ++i) starsOut.insert(starsOut.end(), flat.begin() + (size_t)i * MAX_STAR, flat.begin() + (size_t)i * MAX_STAR + degOut[i]);
+    return failed.load();
+}
 
 // triangles/halfedges sized 3*(2V-4).  Returns 0 on success.
 int sphere_delaunay(int V, const float* xyz, int* triangles, int* halfedges, std::string& err) {
     if (V < 4) { err = "sphere_delaunay: need at least 4 points"; return 1; }
-    std::vector<P3> pts(V);
     // The float32 inputs sit up to ~3e-8 off the unit sphere, enough to push one of two nearly
     // coincident points (they occur from ~1e6 jittered points up) inside the hull of the others; a planar
     // Delaunay of the projection keeps every point, so we take the radial noise out before building the hull.
-    for (int i = 0; i < V; ++i) {
-        const double x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-        const double l = std::sqrt(x * x + y * y + z * z);
-        if (!(l > 0.0)) { err = "sphere_delaunay: zero-length point"; return 1; }
-        pts[i] = {x / l, y / l, z / l};
-    }
+    std::vector<P3> pts;
+    if (!normalise_points(V, xyz, pts)) { err = "sphere_delaunay: zero-length point"; return 1; }
     Grid g;
     build_grid(g, pts.data(), V);
-    Orient orient{pts.data()};
+    const mesh::GridView gv = g.view();
 
     // pass 1: stars (degree + neighbours, rotated to start at the lowest-index neighbour)
     std::vector<int> deg(V);
@@ -290,10 +222,9 @@ int sphere_delaunay(int V, const float* xyz, int* triangles, int* halfedges, std
         std::vector<int> cand; cand.reserve(256);
         int st[MAX_STAR];
         for (int64_t p = b; p < e; ++p) {
-            int d = star_of((int)p, pts.data(), V, g, orient, st, cand);
+            int d = star_of((int)p, pts.data(), V, gv, st, cand);
             if (d < 3) { if (failed.fetch_add(1) == 0) fprintf(stderr, "star fail p=%d code=%d xyz=%.9g %.9g %.9g\n", (int)p, d, pts[p].x, pts[p].y, pts[p].z); deg[p] = 0; continue; }
-            int m = 0;
-            for (int i = 1; i < d; ++i) if (st[i] < st[m]) m = i;
+            const int m = mesh::lowest_position(st, d);
             deg[p] = d;
             if (d <= 12) {
                 for (int i = 0; i < d; ++i) starBuf[(size_t)p * 12 + i] = st[(m + i) % d];
@@ -316,7 +247,7 @@ int sphere_delaunay(int V, const float* xyz, int* triangles, int* halfedges, std
     parallel_ranges(V, [&](int64_t b, int64_t e, int) {
         for (int64_t p = b; p < e; ++p) {
             const int* s = star((int)p); int d = deg[p], c = 0;
-            for (int i = 0; i < d; ++i) { int q = s[i], r = s[(i + 1) % d]; if (p < q && p < r) ++c; }
+            for (int i = 0; i < d; ++i) { int q = s[i], r = s[(i + 1) % d]; if (mesh::owns((int)p, q, r)) ++c; }
             ownCount[p + 1] = c;
         }
     });
@@ -328,7 +259,7 @@ int sphere_delaunay(int V, const float* xyz, int* triangles, int* halfedges, std
             const int* s = star((int)p); int d = deg[p]; int t = ownCount[p];
             for (int i = 0; i < d; ++i) {
                 int q = s[i], r = s[(i + 1) % d];
-                if (p < q && p < r) {
+                if (mesh::owns((int)p, q, r)) {
                     triangles[3 * t] = (int)p; triangles[3 * t + 1] = q; triangles[3 * t + 2] = r;
                     triOfStar[starOff[p] + i] = t; ++t;
                 }
@@ -348,9 +279,8 @@ int sphere_delaunay(int V, const float* xyz, int* triangles, int* halfedges, std
                 if (i < 0) { bad.fetch_add(1); halfedges[3 * t + k] = -1; continue; }
                 const int w = sv[(i + 1) % dv];
                 // owner of (v,u,w) and the star position of that triangle in the owner's star
-                int m = v, a = u;                       // triangle as (m, a, .) counter-clockwise
-                if (u < m && u < w) { m = u; a = w; }
-                else if (w < m && w < u) { m = w; a = v; }
+                int m, a;                               // triangle as (m, a, .) counter-clockwise
+                mesh::owner_of(v, u, w, m, a);
                 const int* sm = star(m); const int dm = deg[m];
                 int j2 = -1;
                 for (int j = 0; j < dm; ++j) if (sm[j] == a) { j2 = j; break; }
@@ -371,7 +301,7 @@ int sphere_delaunay(int V, const float* xyz, int* triangles, int* halfedges, std
 // CSR from triangles/halfedges, following the circulation rule of js/sphere-mesh.js:102-141:
 // row r starts at the lowest-numbered side leaving r and steps s <- next(halfedges[s]).
 // ---------------------------------------------------------------------------------------------
-static inline int next_side(int s) { return (s % 3 == 2) ? s - 2 : s + 1; }
+using mesh::next_side;
 
 int mesh_csr(int V, int numSides, const int* triangles, const int* halfedges,
              int* adjOffset /*V+1*/, int* adjList /*numSides*/, int* adjTri /*numSides or null*/, std::string& err) {
@@ -424,8 +354,7 @@ void neighbor_dist(int V, const int* adjOffset, const int* adjList, const float*
             const double x = xyz[3 * r], y = xyz[3 * r + 1], z = xyz[3 * r + 2];
             for (int i = adjOffset[r]; i < adjOffset[r + 1]; ++i) {
                 const int nb = adjList[i];
-                const double dx = x - (double)xyz[3 * nb], dy = y - (double)xyz[3 * nb + 1], dz = z - (double)xyz[3 * nb + 2];
-                out[i] = (float)std::sqrt(dx * dx + dy * dy + dz * dz);
+                out[i] = mesh::chord(x, y, z, xyz[3 * nb], xyz[3 * nb + 1], xyz[3 * nb + 2]);
             }
         }
     });

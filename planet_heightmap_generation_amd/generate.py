@@ -53,8 +53,9 @@ def plate_densities(plateSeeds, plateIsOcean):
 
 
 def generate_planet(ctx, N, P, jitter, nMag, numContinents, sliders: dict, seed=None, continent_size_variety=0, land_coverage=0.3,
-                    toggled_indices=()):
-    """Returns (planet, result): the resident Planet (caller closes it) and the fields of the reference's `done` message."""
+                    toggled_indices=(), device_mesh=False):
+    """Returns (planet, result): the resident Planet (caller closes it) and the fields of the reference's `done` message.
+    device_mesh: the mesh and the neighbour distances come from the device builder (the same arrays) instead of the host's."""
     N, P = int(N), int(P)
     if N < 1 or P < 1:
         raise ValueError("generate_planet: N and P must be positive integers")
@@ -68,10 +69,14 @@ def generate_planet(ctx, N, P, jitter, nMag, numContinents, sliders: dict, seed=
     t_total = time.perf_counter()
     t0 = time.perf_counter()
     xyz = SM.fibonacci_sphere(N, float(jitter), float(seed))
-    mesh = SM.sphere_mesh_from_points(xyz, reference_closure=True)
+    if device_mesh:
+        mesh, nd = SM.device_sphere_mesh(xyz, True, ctx if ctx is not None else TP.default_context())
+    else:
+        mesh = SM.sphere_mesh_from_points(xyz, reference_closure=True)
     lap("Sphere mesh (Fibonacci + Delaunay + pole)", t0)
     t0 = time.perf_counter()
-    nd = SM.compute_neighbor_dist(mesh, xyz)
+    if not device_mesh:
+        nd = SM.compute_neighbor_dist(mesh, xyz)
     lap("Neighbor distances", t0)
     t0 = time.perf_counter()
     t_xyz = triangle_centers(mesh, xyz)

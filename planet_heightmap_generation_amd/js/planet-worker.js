@@ -214,10 +214,11 @@ function handleImportHeightmap(data) {
         progress(0, 'Building sphere mesh\u2026');
         const seed = (overrideSeed !== undefined && overrideSeed !== null) ? overrideSeed : Math.floor(Math.random() * 16777216);
         let t0 = performance.now();
-        const { mesh, r_xyz } = buildSphere(N, jitter, seed);
+        const built = buildSphere(N, jitter, seed, false, data.deviceMesh ? defaultContext() : null);      // deviceMesh: the device builder, the same arrays
+        const { mesh, r_xyz } = built;
         timing.push({ stage: 'Sphere mesh', ms: performance.now() - t0 });
         t0 = performance.now();
-        const neighborDist = computeNeighborDist(mesh, r_xyz);
+        const neighborDist = built.neighborDist || computeNeighborDist(mesh, r_xyz);
         timing.push({ stage: 'Neighbor distances', ms: performance.now() - t0 });
         t0 = performance.now();
         const t_xyz = generateTriangleCenters(mesh, r_xyz);
@@ -377,10 +378,11 @@ function handleGenerate(data) {
         const seed = (overrideSeed !== undefined && overrideSeed !== null) ? overrideSeed : Math.floor(Math.random() * 16777216);
 
         let t0 = performance.now();
-        const { mesh, r_xyz } = buildSphere(N, jitter, seed, true);
+        const built = buildSphere(N, jitter, seed, true, data.deviceMesh ? defaultContext() : null);       // deviceMesh: the device builder, the same arrays
+        const { mesh, r_xyz } = built;
         timing.push({ stage: 'Sphere mesh (Fibonacci + Delaunay + pole)', ms: performance.now() - t0 });
         t0 = performance.now();
-        const neighborDist = computeNeighborDist(mesh, r_xyz);
+        const neighborDist = built.neighborDist || computeNeighborDist(mesh, r_xyz);
         timing.push({ stage: 'Neighbor distances', ms: performance.now() - t0 });
         t0 = performance.now();
         const t_xyz = generateTriangleCenters(mesh, r_xyz);

@@ -4,13 +4,14 @@
 import addon from './native.js';
 
 export class SphereMesh {
-    constructor(triangles, halfedges, numRegions) {
+    // csr: { adjOffset, adjList, adjTriList } when the caller already has them (the device builder), else they are built here
+    constructor(triangles, halfedges, numRegions, csr = null) {
         this.triangles = triangles;
         this.halfedges = halfedges;
         this.numRegions = numRegions;
         this.numSides = triangles.length;
         this.numTriangles = (triangles.length / 3) | 0;
-        const csr = addon.meshCsr(numRegions, triangles, halfedges);
+        if (!csr) csr = addon.meshCsr(numRegions, triangles, halfedges);
         this._adjOffset = csr.adjOffset;
         this._adjList = csr.adjList;
         this._adjTriList = csr.adjTriList;
@@ -43,8 +44,14 @@ export function generateFibonacciSphere(N, jitter, rngSeed) {
 // buildSphere(N, jitter, makeRng(seed)) in the reference; here the seed itself is passed.  referenceClosure: number the closing
 // pole fan the way the reference's addPoleToMesh does (js/sphere-mesh.js:55-88) — the same triangles, but the CSR rows around the
 // pole then start at the reference's neighbour, which the order-defined host stages (generatePlates, the plate smoothing) can see.
-export function buildSphere(N, jitter, rngSeed, referenceClosure = false) {
+// ctx (a context handle, native.js: defaultContext()): the device builder makes the whole product in one call, the same arrays as
+// the host route, and the result carries neighborDist as well.
+export function buildSphere(N, jitter, rngSeed, referenceClosure = false, ctx = null) {
     const r_xyz = addon.fibSpherePoints(N, jitter, rngSeed);         // pole already appended at index N
+    if (ctx) {
+        const d = addon.sphereMeshDevice(ctx, r_xyz, referenceClosure ? 1 : 0);
+        return { mesh: new SphereMesh(d.triangles, d.halfedges, N + 1, d), r_xyz, neighborDist: d.neighborDist };
+    }
     const { triangles, halfedges } = addon.sphereDelaunay(r_xyz);
     if (referenceClosure) addon.sphereReferenceClosure(N + 1, triangles, halfedges);
     return { mesh: new SphereMesh(triangles, halfedges, N + 1), r_xyz };

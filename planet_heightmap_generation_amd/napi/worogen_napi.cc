@@ -158,6 +158,34 @@ napi_value CtxCreate(napi_env env, napi_callback_info info) {
     return v;
 }
 
+napi_value SphereMeshDevice(napi_env env, napi_callback_info info) {           // (ctx, xyz, referenceClosure) -> {triangles, halfedges, adjOffset, adjList, adjTriList, neighborDist}
+    Args a(env, info);
+    wo_ctx* c = (wo_ctx*)a.ext(0);
+    size_t n; float* xyz = (float*)a.ta(1, napi_float32_array, &n); if (!a.ok) return nullptr;
+    if (!c) { napi_throw_type_error(env, nullptr, "sphereMeshDevice: expected a context handle"); return nullptr; }
+    if (n % 3 != 0 || n < 12) { napi_throw_range_error(env, nullptr, "sphereMeshDevice: xyz must hold three floats for each of at least 4 points"); return nullptr; }
+    const int32_t V = (int32_t)(n / 3);
+    const size_t ns = 3 * (size_t)(2 * V - 4);
+    void *t, *h, *o1, *o2, *o3, *o4;
+    napi_value ta = make_ta(env, napi_int32_array, ns, 4, &t), ha = make_ta(env, napi_int32_array, ns, 4, &h);
+    napi_value off = make_ta(env, napi_int32_array, (size_t)V + 1, 4, &o1);
+    // the library writes the first adjOffset[V] entries of these three; on a closed triangulation that is all of them
+    napi_value alBuf, atBuf, distBuf;
+    if (!ta || !ha || !off || napi_create_arraybuffer(env, ns * 4, &o2, &alBuf) != napi_ok || napi_create_arraybuffer(env, ns * 4, &o3, &atBuf) != napi_ok ||
+        napi_create_arraybuffer(env, ns * 4, &o4, &distBuf) != napi_ok) return nullptr;
+    if (wo_sphere_mesh_device(c, V, xyz, a.has(2) && a.num(2) != 0 ? 1 : 0, (int32_t*)t, (int32_t*)h, (int32_t*)o1, (int32_t*)o2, (int32_t*)o3, (float*)o4))
+        return throw_wo(env, "sphereMeshDevice");
+    const size_t E = (size_t)((int32_t*)o1)[V];
+    napi_value al, at, dist;
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, E, alBuf, 0, &al));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, E, atBuf, 0, &at));
+    NAPI_OK(napi_create_typedarray(env, napi_float32_array, E, distBuf, 0, &dist));
+    napi_value o; napi_create_object(env, &o);
+    set_prop(env, o, "triangles", ta); set_prop(env, o, "halfedges", ha); set_prop(env, o, "adjOffset", off); set_prop(env, o, "adjList", al);
+    set_prop(env, o, "adjTriList", at); set_prop(env, o, "neighborDist", dist);
+    return o;
+}
+
 napi_value PlanetCreate(napi_env env, napi_callback_info info) {               // (ctx, numRegions, adjOffset, adjList, xyz, neighborDist|null)
     Args a(env, info);
     wo_ctx* c = (wo_ctx*)a.ext(0);
@@ -1119,7 +1147,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"fibSpherePoints", FibSpherePoints}, {"sphereDelaunay", SphereDelaunay}, {"meshCsr", MeshCsr}, {"sphereReferenceClosure", SphereReferenceClosure},
         {"generatePlates", GeneratePlates}, {"assignOceanLand", AssignOceanLand}, {"neighborDist", NeighborDist},
         {"triangleElevations", TriangleElevations}, {"noiseTables", NoiseTables}, {"noiseEval", NoiseEval}, {"noisePoint", NoisePoint},
-        {"deviceCount", DeviceCount}, {"ctxCreate", CtxCreate}, {"planetCreate", PlanetCreate}, {"planetDestroy", PlanetDestroy},
+        {"deviceCount", DeviceCount}, {"ctxCreate", CtxCreate}, {"sphereMeshDevice", SphereMeshDevice}, {"planetCreate", PlanetCreate}, {"planetDestroy", PlanetDestroy},
         {"warpTerrain", WarpTerrain}, {"smoothElevation", SmoothElevation}, {"erodeComposite", ErodeComposite},
         {"sharpenRidges", SharpenRidges}, {"applySoilCreep", ApplySoilCreep},
         {"planetUpload", PlanetUpload}, {"planetDownload", PlanetDownload}, {"planetDownloadOcean", PlanetDownloadOcean},

@@ -39,8 +39,26 @@ def fibonacci_sphere(N: int, jitter: float, seed: float) -> np.ndarray:
     return xyz
 
 
-def sphere_mesh_from_points(r_xyz: np.ndarray, reference_closure: bool = False) -> SphereMesh:
-    """reference_closure: number the closing pole fan the way the reference's addPoleToMesh does (js/sphere-mesh.js:55-88)."""
+def device_sphere_mesh(r_xyz: np.ndarray, reference_closure: bool, ctx):
+    """The whole mesh product in one device call (wo_sphere_mesh_device): (SphereMesh, neighborDist), every array equal to the host
+    route's.  ctx: a terrain_post.Context."""
+    r_xyz = np.ascontiguousarray(r_xyz, dtype=np.float32).reshape(-1)
+    V = r_xyz.size // 3
+    ns = max(3 * (2 * V - 4), 0)
+    tri, he = np.empty(ns, dtype=np.int32), np.empty(ns, dtype=np.int32)
+    off = np.empty(V + 1, dtype=np.int32)
+    adj, adjt, nd = np.empty(ns, dtype=np.int32), np.empty(ns, dtype=np.int32), np.empty(ns, dtype=np.float32)
+    capi.check(capi.lib().wo_sphere_mesh_device(ctx.handle, V, capi.ptr(r_xyz), 1 if reference_closure else 0, capi.ptr(tri), capi.ptr(he),
+                                                capi.ptr(off), capi.ptr(adj), capi.ptr(adjt), capi.ptr(nd)), "wo_sphere_mesh_device")
+    E = int(off[-1])
+    return SphereMesh(V, tri, he, off, adj[:E].copy(), adjt[:E].copy()), nd[:E].copy()
+
+
+def sphere_mesh_from_points(r_xyz: np.ndarray, reference_closure: bool = False, ctx=None) -> SphereMesh:
+    """reference_closure: number the closing pole fan the way the reference's addPoleToMesh does (js/sphere-mesh.js:55-88).
+    ctx: a terrain_post.Context sends the work to the device builder (the same arrays); None: the host builder."""
+    if ctx is not None:
+        return device_sphere_mesh(r_xyz, reference_closure, ctx)[0]
     r_xyz = np.ascontiguousarray(r_xyz, dtype=np.float32).reshape(-1)
     V = r_xyz.size // 3
     ns = 3 * (2 * V - 4)
@@ -75,9 +93,12 @@ def compute_neighbor_dist(mesh: SphereMesh, r_xyz: np.ndarray) -> np.ndarray:
     return out
 
 
-def build_sphere(N: int, jitter: float, seed: float, reference_closure: bool = False):
-    """Returns (mesh, r_xyz, neighborDist) for N requested cells (numRegions = N + 1)."""
+def build_sphere(N: int, jitter: float, seed: float, reference_closure: bool = False, ctx=None):
+    """Returns (mesh, r_xyz, neighborDist) for N requested cells (numRegions = N + 1).  ctx: as for sphere_mesh_from_points."""
     xyz = fibonacci_sphere(N, jitter, seed)
+    if ctx is not None:
+        mesh, nd = device_sphere_mesh(xyz, reference_closure, ctx)
+        return mesh, xyz, nd
     mesh = sphere_mesh_from_points(xyz, reference_closure)
     return mesh, xyz, compute_neighbor_dist(mesh, xyz)
 

@@ -1,0 +1,125 @@
+// Stand-alone host program for a sanitizer run of the mesh builder's host side (csrc/mesh_builder.cc on the bodies of csrc/mesh_ops.h):
+// wo_sphere_delaunay, wo_sphere_reference_closure, wo_mesh_csr and wo_neighbor_dist into exactly sized buffers, and stars_on_host (the
+// completion the device builder hands its unsettled points to), on the crafted point sets of tests/mesh_device_common.py: the
+// octahedron, a lat-lon grid with pole degree 16 (the bigStar case), a dense cap over a sparse sphere (level-2 stars, 769 candidates),
+// two points one f32 ulp apart, small spheres that are all brute; and the sets the builder refuses (the cube, a duplicate point, a
+// pole of degree 128, three points).  CPU only, no GPU call, not loaded into Python.
+//
+//   cd planet_heightmap_generation_amd/csrc && g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -ffp-contract=off -fsanitize=address,undefined \
+//       -fno-sanitize-recover=undefined ../../tools/sanitize/mesh_builder_main.cc api_host.cc mesh_builder.cc noise_host.cc plates_host.cc \
+//       plates_gen_host.cc -lpthread -o /tmp/mesh_builder_asan && /tmp/mesh_builder_asan
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "../../include/worogen.h"
+#include "../../planet_heightmap_generation_amd/csrc/wo_internal.h"
+
+using Points = std::vector<float>;
+
+static Points fib(int32_t N, double jitter, double seed) {
+    Points p(3 * (size_t)(N + 1));
+    if (wo_fib_sphere_points(N, jitter, seed, p.data())) p.clear();
+    return p;
+}
+static Points octahedron() { return {1, 0, 0, 0, 1, 0, -1, 0, 0, 0, -1, 0, 0, 0, -1, 0, 0, 1}; }
+static Points latlon(int rings, int perRing) {
+    const double PI = 3.141592653589793;
+    Points p;
+    for (int i = 0; i < rings; ++i)
+        for (int j = 0; j < perRing; ++j) {
+            const double la = (i + 1) * PI / (rings + 1) - PI / 2, lo = j * 2 * PI / perRing;
+            p.push_back((float)(std::cos(la) * std::cos(lo))); p.push_back((float)(std::cos(la) * std::sin(lo))); p.push_back((float)std::sin(la));
+        }
+    for (float z : {-1.f, 1.f}) { p.push_back(0.f); p.push_back(0.f); p.push_back(z); }
+    return p;
+}
+static Points cap_and_sparse(int32_t N) {
+    const Points all = fib(N, 0.75, 5);
+    Points p;
+    for (size_t i = 0; i < all.size() / 3; ++i)
+        if (all[3 * i + 2] > 0.9f || i % 40 == 0) p.insert(p.end(), all.begin() + 3 * i, all.begin() + 3 * i + 3);
+    return p;
+}
+static Points ulp_pair() {
+    Points p = fib(2000, 0.75, 3);
+    for (int k = 0; k < 3; ++k) p[3 * 500 + k] = p[3 * 501 + k];
+    p[3 * 500] = std::nextafterf(p[3 * 501], 2.f);
+    return p;
+}
+static Points cube() {
+    const float s = (float)(1 / std::sqrt(3.0));
+    Points p;
+    for (float z : {-s, s}) for (float y : {-s, s}) for (float x : {-s, s}) { p.push_back(x); p.push_back(y); p.push_back(z); }
+    return p;
+}
+static Points duplicate() {
+    Points p = fib(500, 0.75, 2);
+    for (int k = 0; k < 3; ++k) p[3 * 77 + k] = p[3 * 300 + k];
+    return p;
+}
+
+// the whole host route on one point set; wantStatus is wo_sphere_delaunay's
+static int run_case(const char* name, const Points& xyz, int wantStatus, int wantMaxDeg) {
+    const int32_t V = (int32_t)(xyz.size() / 3);
+    const size_t ns = V >= 2 ? 3 * (size_t)(2 * V - 4) : 0;
+    for (int closure = 0; closure < 2; ++closure) {
+        std::vector<int32_t> tri(ns), he(ns);
+        const int rc = wo_sphere_delaunay(V, xyz.data(), tri.data(), he.data());
+        if (rc != wantStatus) { std::fprintf(stderr, "%s: wo_sphere_delaunay gives %d, expected %d (%s)\n", name, rc, wantStatus, wo_last_error()); return 1; }
+        if (rc != 0) continue;
+        if (closure && wo_sphere_reference_closure(V, tri.data(), he.data())) { std::fprintf(stderr, "%s: closure: %s\n", name, wo_last_error()); return 1; }
+        std::vector<int32_t> off((size_t)V + 1), adj(ns), adjt(ns);
+        if (wo_mesh_csr(V, (int32_t)ns, tri.data(), he.data(), off.data(), adj.data(), adjt.data())) { std::fprintf(stderr, "%s: wo_mesh_csr: %s\n", name, wo_last_error()); return 1; }
+        adj.resize(off[V]);                              // exact size: an index past the list is a heap overflow the sanitizer sees
+        std::vector<float> nd(adj.size());
+        if (wo_neighbor_dist(V, off.data(), adj.data(), xyz.data(), nd.data())) return 1;
+        int maxDeg = 0;
+        for (int32_t r = 0; r < V; ++r) maxDeg = std::max(maxDeg, off[r + 1] - off[r]);
+        if (off[V] != (int32_t)ns || (wantMaxDeg && maxDeg != wantMaxDeg)) { std::fprintf(stderr, "%s: E %d of %zu, max degree %d\n", name, off[V], ns, maxDeg); return 1; }
+        for (size_t s = 0; s < ns; ++s) if (he[he[s]] != (int32_t)s) { std::fprintf(stderr, "%s: half-edge %zu has no twin\n", name, s); return 1; }
+        if (closure) continue;
+        // the completion of the device builder: every star again, by id, in descending order; a star is its CSR row up to rotation
+        std::vector<int> ids(V), deg, stars;
+        for (int i = 0; i < V; ++i) ids[i] = V - 1 - i;
+        if (wo::stars_on_host(V, xyz.data(), V, ids.data(), deg, stars) != 0) { std::fprintf(stderr, "%s: stars_on_host failed\n", name); return 1; }
+        size_t at = 0;
+        for (int i = 0; i < V; ++i) {
+            const int r = ids[i], d = off[r + 1] - off[r];
+            if (deg[i] != d) { std::fprintf(stderr, "%s: star of %d has %d neighbours, its row %d\n", name, r, deg[i], d); return 1; }
+            int lowest = 0;
+            for (int k = 1; k < d; ++k) if (adj[off[r] + k] < adj[off[r] + lowest]) lowest = k;
+            // the row walks the neighbours the other way round (js/sphere-mesh.js:102-141): compare as sets through the rotation
+            long sumStar = 0, sumRow = 0;
+            for (int k = 0; k < d; ++k) { sumStar += stars[at + k]; sumRow += adj[off[r] + k]; }
+            if (stars[at] != adj[off[r] + lowest] || sumStar != sumRow) { std::fprintf(stderr, "%s: star of %d differs from its row\n", name, r); return 1; }
+            at += d;
+        }
+        if (at != stars.size()) return 1;
+        std::printf("%-14s V %6d  E %7d  max degree %2d\n", name, V, off[V], maxDeg);
+    }
+    return 0;
+}
+
+int main() {
+    int bad = 0;
+    bad += run_case("octahedron", octahedron(), 0, 4);
+    bad += run_case("latlon 7x16", latlon(7, 16), 0, 16);
+    bad += run_case("cap 3000", cap_and_sparse(3000), 0, 0);
+    bad += run_case("cap 40000", cap_and_sparse(40000), 0, 0);
+    bad += run_case("ulp pair", ulp_pair(), 0, 0);
+    for (int32_t N : {3, 4, 5, 12, 63, 256, 2000}) bad += run_case(("fib " + std::to_string(N)).c_str(), fib(N, 0.75, 5), 0, 0);
+    bad += run_case("fib 20000 j0", fib(20000, 0.0, 5), 0, 0);
+    bad += run_case("cube", cube(), 3, 0);
+    bad += run_case("duplicate", duplicate(), 2, 0);
+    bad += run_case("latlon 63x128", latlon(63, 128), 2, 0);
+    bad += run_case("three points", fib(2, 0.75, 1), 1, 0);
+    // refusals before any read
+    std::vector<int32_t> i32(64);
+    if (wo_sphere_delaunay(8, nullptr, i32.data(), i32.data()) == 0) ++bad;
+    if (wo_sphere_reference_closure(3, i32.data(), i32.data()) == 0) ++bad;
+    std::printf(bad ? "FAILED\n" : "ok\n");
+    return bad ? 1 : 0;
+}
