@@ -125,6 +125,18 @@ void    wo_ctx_destroy(wo_ctx* ctx);
 int wo_sphere_delaunay_device(wo_ctx* ctx, int32_t numRegions, const float* r_xyz, int32_t* triangles, int32_t* halfedges);
 int wo_sphere_mesh_device(wo_ctx* ctx, int32_t numRegions, const float* r_xyz, int32_t referenceClosure, int32_t* triangles,
                           int32_t* halfedges, int32_t* adjOffset, int32_t* adjList, int32_t* adjTriList, float* neighborDist);
+/* The Fibonacci sphere's points on the device (csrc/points.hip, the bodies in csrc/points_ops.h): generateFibonacciSphere(N, jitter,
+ * makeRng(seed)) plus the pole, one thread per point.  The loop's carried values are evaluated in closed form (Park-Miller jump-ahead,
+ * piecewise-linear tables of the two f64 accumulations) and the trigonometry is V8's fdlibm, so the floats are the reference's.
+ * wo_fib_sphere_points_device downloads them: r_xyz has 3*(N+1) floats, as for wo_fib_sphere_points.  wo_sphere_mesh_seed_device is the
+ * whole mesh from the seed in one call: the points are generated into the buffer the mesh stage reads (no upload) and downloaded
+ * beside the mesh arrays, whose sizes and values are wo_sphere_mesh_device's on the same points (numRegions = N + 1).  Status: 1 bad
+ * arguments (a NULL context, which never touches the device; a NULL pointer, adjTriList and neighborDist excepted; N < 1; N + 1 < 4 for
+ * the mesh form), 2 to 5 the mesh's own.  Nothing stays allocated after the call. */
+int wo_fib_sphere_points_device(wo_ctx* ctx, int32_t N, double jitter, double seed, float* r_xyz);
+int wo_sphere_mesh_seed_device(wo_ctx* ctx, int32_t N, double jitter, double seed, int32_t referenceClosure, float* r_xyz,
+                               int32_t* triangles, int32_t* halfedges, int32_t* adjOffset, int32_t* adjList, int32_t* adjTriList,
+                               float* neighborDist);
 /* Uploads the mesh once (the worker keeps mesh / r_xyz / neighborDist in W between commands,
  * js/planet-worker.js:277-292).  neighborDist may be NULL: it is then computed on the device. */
 wo_planet* wo_planet_create(wo_ctx* ctx, int32_t numRegions, const int32_t* adjOffset,

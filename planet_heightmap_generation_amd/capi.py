@@ -47,6 +47,8 @@ SIGNATURES = {
     "wo_ctx_destroy": (None, [_p]),
     "wo_sphere_delaunay_device": (C.c_int, [_p, _c_i32, _p, _p, _p]),
     "wo_sphere_mesh_device": (C.c_int, [_p, _c_i32, _p, _c_i32, _p, _p, _p, _p, _p, _p]),
+    "wo_fib_sphere_points_device": (C.c_int, [_p, _c_i32, _c_f64, _c_f64, _p]),
+    "wo_sphere_mesh_seed_device": (C.c_int, [_p, _c_i32, _c_f64, _c_f64, _c_i32, _p, _p, _p, _p, _p, _p, _p]),
     "wo_planet_create": (_p, [_p, _c_i32, _p, _p, _p, _p]),
     "wo_planet_destroy": (None, [_p]),
     "wo_planet_num_regions": (_c_i32, [_p]),

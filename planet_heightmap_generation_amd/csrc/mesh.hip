@@ -4,6 +4,7 @@
 // route's on the same points.
 //
 // Launches of wo_sphere_mesh_device, in order (V points, WO_BLOCK threads where nothing else is said):
+//   (wo_sphere_mesh_seed_device: k_fib_points of points.hip writes the points where the other two entries upload them)
 //   k_mesh_points [1]        normalised f64 points (x / l, the host's bits) and the grid key of every point
 //   k_mesh_cell_insert [1]   the occupied cells into an open-addressing table (64-bit atomicCAS of key + 1) and their point counts.
 //                            No dense G^3 table: the table has 2 min(V, G^3) + 8 slots rounded up to a power of two, so it is never
@@ -43,10 +44,14 @@
 #include "block_ops.h"
 #include "device.h"
 #include "mesh_ops.h"
+#include "points_ops.h"
 
 namespace M = wo::mesh;
 
 namespace wo {
+
+// points.hip
+WO_LOCAL bool fib_points_to_device(hipStream_t s, DeviceArena& A, int32_t N, double jitter, double seed, float* d_xyz);
 
 constexpr int L1_THREADS = 64;                    // workgroup of k_mesh_stars_l1: one wave, 32 KB of LDS
 constexpr int L1_CAP = 128;                       // candidates per point at level 1 (test hook mesh_cand_cap lowers it)
@@ -374,8 +379,11 @@ struct MeshOut {
     int32_t *triangles, *halfedges, *adjOffset, *adjList, *adjTriList; float* neighborDist;
     bool csr, closure;
 };
+// where the points come from: the caller's array (xyz, uploaded), or the seed (gen: V - 1 Fibonacci points and the pole are generated
+// into the buffer the stages read and downloaded into outXyz, which is complete before the host reads it: stars_on_host)
+struct MeshIn { const float* xyz; bool gen; double jitter, seed; float* outXyz; };
 
-void mesh_device(wo_ctx* ctx, int32_t V, const float* xyz, const MeshOut& out) {
+void mesh_device(wo_ctx* ctx, int32_t V, const MeshIn& in, const MeshOut& out) {
     WO_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const int32_t candCap = (int32_t)std::max<long long>(0, std::min<long long>(test_hook_int("mesh_cand_cap", L1_CAP), L1_CAP));
@@ -392,7 +400,13 @@ void mesh_device(wo_ctx* ctx, int32_t V, const float* xyz, const MeshOut& out) {
     };
 
     // ---- points and grid
-    float* d_xyz = up(A, xyz, (size_t)3 * V, s);
+    const float* xyz = in.gen ? in.outXyz : in.xyz;           // the host's copy
+    float* d_xyz;
+    if (in.gen) {
+        d_xyz = A.dev<float>((size_t)3 * V);
+        if (!fib_points_to_device(s, A, V - 1, in.jitter, in.seed, d_xyz)) throw StatusError{1, "fib_sphere_points: chain table overflow"};
+        WO_HIP(hipMemcpyAsync(in.outXyz, d_xyz, (size_t)3 * V * sizeof(float), hipMemcpyDeviceToHost, s));     // every later read_ctrl waits for it
+    } else d_xyz = up(A, in.xyz, (size_t)3 * V, s);
     M::P3* pts = A.dev<M::P3>((size_t)V);
     M::GridView g{};
     M::grid_dims(V, g.h, g.G);
@@ -534,9 +548,9 @@ void mesh_device(wo_ctx* ctx, int32_t V, const float* xyz, const MeshOut& out) {
     WO_HIP(hipStreamSynchronize(s));                          // before A frees the temporaries
 }
 
-int run_mesh_device(const char* fn, wo_ctx* ctx, int32_t V, const float* xyz, const MeshOut& out) {
+int run_mesh_device(const char* fn, wo_ctx* ctx, int32_t V, const MeshIn& in, const MeshOut& out) {
     WO_TRY
-        try { mesh_device(ctx, V, xyz, out); }
+        try { mesh_device(ctx, V, in, out); }
         catch (const StatusError& e) {
             (void)hipStreamSynchronize(ctx->stream);          // nothing of this call is in flight when its arenas go
             set_error(e.msg); return e.code;
@@ -556,7 +570,7 @@ int wo_sphere_delaunay_device(wo_ctx* ctx, int32_t numRegions, const float* r_xy
     if (!ctx) { set_error("wo_sphere_delaunay_device: null context"); return 1; }
     if (!r_xyz || !triangles || !halfedges) { set_error("wo_sphere_delaunay_device: null pointer"); return 1; }
     if (numRegions < 4) { set_error("sphere_delaunay: need at least 4 points"); return 1; }
-    return run_mesh_device("wo_sphere_delaunay_device", ctx, numRegions, r_xyz, MeshOut{triangles, halfedges, nullptr, nullptr, nullptr, nullptr, false, false});
+    return run_mesh_device("wo_sphere_delaunay_device", ctx, numRegions, MeshIn{r_xyz, false, 0.0, 0.0, nullptr}, MeshOut{triangles, halfedges, nullptr, nullptr, nullptr, nullptr, false, false});
 }
 
 int wo_sphere_mesh_device(wo_ctx* ctx, int32_t numRegions, const float* r_xyz, int32_t referenceClosure, int32_t* triangles, int32_t* halfedges,
@@ -564,7 +578,16 @@ int wo_sphere_mesh_device(wo_ctx* ctx, int32_t numRegions, const float* r_xyz, i
     if (!ctx) { set_error("wo_sphere_mesh_device: null context"); return 1; }
     if (!r_xyz || !triangles || !halfedges || !adjOffset || !adjList) { set_error("wo_sphere_mesh_device: null pointer"); return 1; }
     if (numRegions < 4) { set_error("sphere_delaunay: need at least 4 points"); return 1; }
-    return run_mesh_device("wo_sphere_mesh_device", ctx, numRegions, r_xyz,
+    return run_mesh_device("wo_sphere_mesh_device", ctx, numRegions, MeshIn{r_xyz, false, 0.0, 0.0, nullptr},
+                           MeshOut{triangles, halfedges, adjOffset, adjList, adjTriList, neighborDist, true, referenceClosure != 0});
+}
+
+int wo_sphere_mesh_seed_device(wo_ctx* ctx, int32_t N, double jitter, double seed, int32_t referenceClosure, float* r_xyz, int32_t* triangles,
+                               int32_t* halfedges, int32_t* adjOffset, int32_t* adjList, int32_t* adjTriList, float* neighborDist) {
+    if (!ctx) { set_error("wo_sphere_mesh_seed_device: null context"); return 1; }
+    if (!r_xyz || !triangles || !halfedges || !adjOffset || !adjList) { set_error("wo_sphere_mesh_seed_device: null pointer"); return 1; }
+    if (N < 3 || N > points::FIB_MAX_N) { set_error("wo_sphere_mesh_seed_device: need at least 4 points (N + 1), N in range"); return 1; }
+    return run_mesh_device("wo_sphere_mesh_seed_device", ctx, N + 1, MeshIn{nullptr, true, jitter, seed, r_xyz},
                            MeshOut{triangles, halfedges, adjOffset, adjList, adjTriList, neighborDist, true, referenceClosure != 0});
 }
 

@@ -53,9 +53,10 @@ def plate_densities(plateSeeds, plateIsOcean):
 
 
 def generate_planet(ctx, N, P, jitter, nMag, numContinents, sliders: dict, seed=None, continent_size_variety=0, land_coverage=0.3,
-                    toggled_indices=(), device_mesh=False):
+                    toggled_indices=(), device_mesh=False, device_points=False):
     """Returns (planet, result): the resident Planet (caller closes it) and the fields of the reference's `done` message.
-    device_mesh: the mesh and the neighbour distances come from the device builder (the same arrays) instead of the host's."""
+    device_mesh: the mesh and the neighbour distances come from the device builder (the same arrays) instead of the host's.
+    device_points: the points come from the device as well, in the same call (the same floats); implies device_mesh."""
     N, P = int(N), int(P)
     if N < 1 or P < 1:
         raise ValueError("generate_planet: N and P must be positive integers")
@@ -68,11 +69,15 @@ def generate_planet(ctx, N, P, jitter, nMag, numContinents, sliders: dict, seed=
 
     t_total = time.perf_counter()
     t0 = time.perf_counter()
-    xyz = SM.fibonacci_sphere(N, float(jitter), float(seed))
-    if device_mesh:
-        mesh, nd = SM.device_sphere_mesh(xyz, True, ctx if ctx is not None else TP.default_context())
+    device_mesh = bool(device_mesh or device_points)
+    if device_points:
+        mesh, xyz, nd = SM.device_sphere_from_seed(N, float(jitter), float(seed), True, ctx if ctx is not None else TP.default_context())
     else:
-        mesh = SM.sphere_mesh_from_points(xyz, reference_closure=True)
+        xyz = SM.fibonacci_sphere(N, float(jitter), float(seed))
+        if device_mesh:
+            mesh, nd = SM.device_sphere_mesh(xyz, True, ctx if ctx is not None else TP.default_context())
+        else:
+            mesh = SM.sphere_mesh_from_points(xyz, reference_closure=True)
     lap("Sphere mesh (Fibonacci + Delaunay + pole)", t0)
     t0 = time.perf_counter()
     if not device_mesh:

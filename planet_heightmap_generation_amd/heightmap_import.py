@@ -75,11 +75,13 @@ def triangle_centers(mesh, r_xyz) -> np.ndarray:
 _SLIDERS = ("smoothing", "hydraulicErosion", "thermalErosion", "ridgeSharpening", "glacialErosion", "terrainWarp")
 
 
-def import_heightmap(N, jitter, gray, W, H, params: dict, seed=None, planet_out: list | None = None, device_mesh=False) -> dict:
+def import_heightmap(N, jitter, gray, W, H, params: dict, seed=None, planet_out: list | None = None, device_mesh=False,
+                     device_points=False) -> dict:
     """handleImportHeightmap (js/planet-worker.js:771-940) without the message layer and without climate: the fields of the
     reference's `done` message.  The planet stays resident (W.prePostElev is its saved state) and is appended to planet_out
     when a list is given, so that a following reapply works on it; otherwise it is closed.  device_mesh: the mesh and the
-    neighbour distances come from the device builder (the same arrays) instead of the host's."""
+    neighbour distances come from the device builder (the same arrays) instead of the host's.  device_points: the points come from
+    the device as well, in the same call (the same floats); implies device_mesh."""
     g = check_image(gray, W, H)
     seed = random.randrange(16777216) if seed is None else seed
     timing = []
@@ -89,11 +91,15 @@ def import_heightmap(N, jitter, gray, W, H, params: dict, seed=None, planet_out:
 
     t_total = time.perf_counter()
     t0 = time.perf_counter()
-    xyz = SM.fibonacci_sphere(int(N), float(jitter), float(seed))
-    if device_mesh:
-        mesh, nd = SM.device_sphere_mesh(xyz, False, TP.default_context())
+    device_mesh = bool(device_mesh or device_points)
+    if device_points:
+        mesh, xyz, nd = SM.device_sphere_from_seed(int(N), float(jitter), float(seed), False, TP.default_context())
     else:
-        mesh = SM.sphere_mesh_from_points(xyz)
+        xyz = SM.fibonacci_sphere(int(N), float(jitter), float(seed))
+        if device_mesh:
+            mesh, nd = SM.device_sphere_mesh(xyz, False, TP.default_context())
+        else:
+            mesh = SM.sphere_mesh_from_points(xyz)
     lap("Sphere mesh", t0)
     t0 = time.perf_counter()
     if not device_mesh:

@@ -214,7 +214,7 @@ function handleImportHeightmap(data) {
         progress(0, 'Building sphere mesh\u2026');
         const seed = (overrideSeed !== undefined && overrideSeed !== null) ? overrideSeed : Math.floor(Math.random() * 16777216);
         let t0 = performance.now();
-        const built = buildSphere(N, jitter, seed, false, data.deviceMesh ? defaultContext() : null);      // deviceMesh: the device builder, the same arrays
+        const built = buildSphere(N, jitter, seed, false, (data.deviceMesh || data.devicePoints) ? defaultContext() : null, !!data.devicePoints);      // deviceMesh: the device builder, the same arrays; devicePoints: the points from the device too
         const { mesh, r_xyz } = built;
         timing.push({ stage: 'Sphere mesh', ms: performance.now() - t0 });
         t0 = performance.now();
@@ -378,7 +378,7 @@ function handleGenerate(data) {
         const seed = (overrideSeed !== undefined && overrideSeed !== null) ? overrideSeed : Math.floor(Math.random() * 16777216);
 
         let t0 = performance.now();
-        const built = buildSphere(N, jitter, seed, true, data.deviceMesh ? defaultContext() : null);       // deviceMesh: the device builder, the same arrays
+        const built = buildSphere(N, jitter, seed, true, (data.deviceMesh || data.devicePoints) ? defaultContext() : null, !!data.devicePoints);       // deviceMesh: the device builder, the same arrays; devicePoints: the points from the device too
         const { mesh, r_xyz } = built;
         timing.push({ stage: 'Sphere mesh (Fibonacci + Delaunay + pole)', ms: performance.now() - t0 });
         t0 = performance.now();

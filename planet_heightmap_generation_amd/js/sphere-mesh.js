@@ -37,16 +37,23 @@ export class SphereMesh {
     }
 }
 
-export function generateFibonacciSphere(N, jitter, rngSeed) {
-    return addon.fibSpherePoints(N, jitter, rngSeed).subarray(0, 3 * N);
+// ctx (a context handle): the points are made on the device, one thread per point (the same floats)
+export function generateFibonacciSphere(N, jitter, rngSeed, ctx = null) {
+    return (ctx ? addon.fibSpherePointsDevice(ctx, N, jitter, rngSeed) : addon.fibSpherePoints(N, jitter, rngSeed)).subarray(0, 3 * N);
 }
 
 // buildSphere(N, jitter, makeRng(seed)) in the reference; here the seed itself is passed.  referenceClosure: number the closing
 // pole fan the way the reference's addPoleToMesh does (js/sphere-mesh.js:55-88) — the same triangles, but the CSR rows around the
 // pole then start at the reference's neighbour, which the order-defined host stages (generatePlates, the plate smoothing) can see.
 // ctx (a context handle, native.js: defaultContext()): the device builder makes the whole product in one call, the same arrays as
-// the host route, and the result carries neighborDist as well.
-export function buildSphere(N, jitter, rngSeed, referenceClosure = false, ctx = null) {
+// the host route, and the result carries neighborDist as well.  devicePoints (needs ctx): the points are generated on the device too,
+// into the buffer the mesh stage reads, in the same call.
+export function buildSphere(N, jitter, rngSeed, referenceClosure = false, ctx = null, devicePoints = false) {
+    if (devicePoints) {
+        if (!ctx) throw new TypeError('buildSphere: devicePoints needs a context');
+        const d = addon.sphereMeshSeedDevice(ctx, N, jitter, rngSeed, referenceClosure ? 1 : 0);
+        return { mesh: new SphereMesh(d.triangles, d.halfedges, N + 1, d), r_xyz: d.r_xyz, neighborDist: d.neighborDist };
+    }
     const r_xyz = addon.fibSpherePoints(N, jitter, rngSeed);         // pole already appended at index N
     if (ctx) {
         const d = addon.sphereMeshDevice(ctx, r_xyz, referenceClosure ? 1 : 0);

@@ -186,6 +186,47 @@ napi_value SphereMeshDevice(napi_env env, napi_callback_info info) {           /
     return o;
 }
 
+napi_value FibSpherePointsDevice(napi_env env, napi_callback_info info) {       // (ctx, N, jitter, seed) -> Float32Array(3*(N+1))
+    Args a(env, info);
+    wo_ctx* c = (wo_ctx*)a.ext(0);
+    const int32_t N = a.i32(1);
+    if (!c) { napi_throw_type_error(env, nullptr, "fibSpherePointsDevice: expected a context handle"); return nullptr; }
+    if (N < 1) { napi_throw_range_error(env, nullptr, "fibSpherePointsDevice: N must be at least 1"); return nullptr; }
+    void* d; napi_value out = make_ta(env, napi_float32_array, 3 * ((size_t)N + 1), 4, &d);
+    if (!out) return nullptr;
+    if (wo_fib_sphere_points_device(c, N, a.num(2), a.num(3), (float*)d)) return throw_wo(env, "fibSpherePointsDevice");
+    return out;
+}
+
+napi_value SphereMeshSeedDevice(napi_env env, napi_callback_info info) {       // (ctx, N, jitter, seed, referenceClosure) -> {r_xyz, triangles, halfedges, adjOffset, adjList, adjTriList, neighborDist}
+    Args a(env, info);
+    wo_ctx* c = (wo_ctx*)a.ext(0);
+    const int32_t N = a.i32(1);
+    if (!c) { napi_throw_type_error(env, nullptr, "sphereMeshSeedDevice: expected a context handle"); return nullptr; }
+    if (N < 3) { napi_throw_range_error(env, nullptr, "sphereMeshSeedDevice: N + 1 must be at least 4 points"); return nullptr; }
+    const int32_t V = N + 1;
+    const size_t ns = 3 * (size_t)(2 * V - 4);
+    void *x, *t, *h, *o1, *o2, *o3, *o4;
+    napi_value xa = make_ta(env, napi_float32_array, 3 * (size_t)V, 4, &x);
+    napi_value ta = make_ta(env, napi_int32_array, ns, 4, &t), ha = make_ta(env, napi_int32_array, ns, 4, &h);
+    napi_value off = make_ta(env, napi_int32_array, (size_t)V + 1, 4, &o1);
+    napi_value alBuf, atBuf, distBuf;
+    if (!xa || !ta || !ha || !off || napi_create_arraybuffer(env, ns * 4, &o2, &alBuf) != napi_ok || napi_create_arraybuffer(env, ns * 4, &o3, &atBuf) != napi_ok ||
+        napi_create_arraybuffer(env, ns * 4, &o4, &distBuf) != napi_ok) return nullptr;
+    if (wo_sphere_mesh_seed_device(c, N, a.num(2), a.num(3), a.has(4) && a.num(4) != 0 ? 1 : 0, (float*)x, (int32_t*)t, (int32_t*)h, (int32_t*)o1, (int32_t*)o2,
+                                   (int32_t*)o3, (float*)o4))
+        return throw_wo(env, "sphereMeshSeedDevice");
+    const size_t E = (size_t)((int32_t*)o1)[V];
+    napi_value al, at, dist;
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, E, alBuf, 0, &al));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, E, atBuf, 0, &at));
+    NAPI_OK(napi_create_typedarray(env, napi_float32_array, E, distBuf, 0, &dist));
+    napi_value o; napi_create_object(env, &o);
+    set_prop(env, o, "r_xyz", xa); set_prop(env, o, "triangles", ta); set_prop(env, o, "halfedges", ha); set_prop(env, o, "adjOffset", off);
+    set_prop(env, o, "adjList", al); set_prop(env, o, "adjTriList", at); set_prop(env, o, "neighborDist", dist);
+    return o;
+}
+
 napi_value PlanetCreate(napi_env env, napi_callback_info info) {               // (ctx, numRegions, adjOffset, adjList, xyz, neighborDist|null)
     Args a(env, info);
     wo_ctx* c = (wo_ctx*)a.ext(0);
@@ -1147,7 +1188,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"fibSpherePoints", FibSpherePoints}, {"sphereDelaunay", SphereDelaunay}, {"meshCsr", MeshCsr}, {"sphereReferenceClosure", SphereReferenceClosure},
         {"generatePlates", GeneratePlates}, {"assignOceanLand", AssignOceanLand}, {"neighborDist", NeighborDist},
         {"triangleElevations", TriangleElevations}, {"noiseTables", NoiseTables}, {"noiseEval", NoiseEval}, {"noisePoint", NoisePoint},
-        {"deviceCount", DeviceCount}, {"ctxCreate", CtxCreate}, {"sphereMeshDevice", SphereMeshDevice}, {"planetCreate", PlanetCreate}, {"planetDestroy", PlanetDestroy},
+        {"deviceCount", DeviceCount}, {"ctxCreate", CtxCreate}, {"sphereMeshDevice", SphereMeshDevice}, {"fibSpherePointsDevice", FibSpherePointsDevice},
+        {"sphereMeshSeedDevice", SphereMeshSeedDevice}, {"planetCreate", PlanetCreate}, {"planetDestroy", PlanetDestroy},
         {"warpTerrain", WarpTerrain}, {"smoothElevation", SmoothElevation}, {"erodeComposite", ErodeComposite},
         {"sharpenRidges", SharpenRidges}, {"applySoilCreep", ApplySoilCreep},
         {"planetUpload", PlanetUpload}, {"planetDownload", PlanetDownload}, {"planetDownloadOcean", PlanetDownloadOcean},

@@ -32,11 +32,31 @@ class SphereMesh:
         return self.numSides // 3
 
 
-def fibonacci_sphere(N: int, jitter: float, seed: float) -> np.ndarray:
-    """generateFibonacciSphere + appended pole: float32 [3*(N+1)] (js/sphere-mesh.js:9-37,179-181)."""
-    xyz = np.empty(3 * (N + 1), dtype=np.float32)
+def fibonacci_sphere(N: int, jitter: float, seed: float, ctx=None) -> np.ndarray:
+    """generateFibonacciSphere + appended pole: float32 [3*(N+1)] (js/sphere-mesh.js:9-37,179-181).  ctx: a terrain_post.Context
+    makes the points on the device (wo_fib_sphere_points_device), one thread per point; None: the host loop."""
+    xyz = np.empty(3 * (max(int(N), 0) + 1), dtype=np.float32)
+    if ctx is not None:
+        capi.check(capi.lib().wo_fib_sphere_points_device(ctx.handle, N, float(jitter), float(seed), capi.ptr(xyz)), "wo_fib_sphere_points_device")
+        return xyz
     capi.check(capi.lib().wo_fib_sphere_points(N, float(jitter), float(seed), capi.ptr(xyz)), "wo_fib_sphere_points")
     return xyz
+
+
+def device_sphere_from_seed(N: int, jitter: float, seed: float, reference_closure: bool, ctx):
+    """Points and mesh in one device call (wo_sphere_mesh_seed_device): (SphereMesh, r_xyz, neighborDist).  The points are generated
+    where the mesh stage reads them; the arrays are device_sphere_mesh's on those points."""
+    V = int(N) + 1
+    ns = max(3 * (2 * V - 4), 0)
+    xyz = np.empty(3 * V, dtype=np.float32)
+    tri, he = np.empty(ns, dtype=np.int32), np.empty(ns, dtype=np.int32)
+    off = np.empty(V + 1, dtype=np.int32)
+    adj, adjt, nd = np.empty(ns, dtype=np.int32), np.empty(ns, dtype=np.int32), np.empty(ns, dtype=np.float32)
+    capi.check(capi.lib().wo_sphere_mesh_seed_device(ctx.handle, int(N), float(jitter), float(seed), 1 if reference_closure else 0, capi.ptr(xyz),
+                                                     capi.ptr(tri), capi.ptr(he), capi.ptr(off), capi.ptr(adj), capi.ptr(adjt), capi.ptr(nd)),
+               "wo_sphere_mesh_seed_device")
+    E = int(off[-1])
+    return SphereMesh(V, tri, he, off, adj[:E].copy(), adjt[:E].copy()), xyz, nd[:E].copy()
 
 
 def device_sphere_mesh(r_xyz: np.ndarray, reference_closure: bool, ctx):
@@ -93,8 +113,13 @@ def compute_neighbor_dist(mesh: SphereMesh, r_xyz: np.ndarray) -> np.ndarray:
     return out
 
 
-def build_sphere(N: int, jitter: float, seed: float, reference_closure: bool = False, ctx=None):
-    """Returns (mesh, r_xyz, neighborDist) for N requested cells (numRegions = N + 1).  ctx: as for sphere_mesh_from_points."""
+def build_sphere(N: int, jitter: float, seed: float, reference_closure: bool = False, ctx=None, device_points: bool = False):
+    """Returns (mesh, r_xyz, neighborDist) for N requested cells (numRegions = N + 1).  ctx: as for sphere_mesh_from_points.
+    device_points (needs ctx): the points are generated on the device too, in the same call (device_sphere_from_seed)."""
+    if device_points:
+        if ctx is None:
+            raise ValueError("build_sphere: device_points needs a context")
+        return device_sphere_from_seed(N, jitter, seed, reference_closure, ctx)
     xyz = fibonacci_sphere(N, jitter, seed)
     if ctx is not None:
         mesh, nd = device_sphere_mesh(xyz, reference_closure, ctx)

@@ -1,15 +1,17 @@
 // Per-stage _pipelineTiming of the worker's `generate` (DESIGN 8.9): one warm-up at the size, then <repeats> runs; prints the median,
 // smallest and largest of every stage and of _workerTotal as JSON.  Needs a HIP device.
-//   node tools/generate_timing.mjs <N> [repeats = 3] [P = 80] [deviceMesh]      deviceMesh: the mesh from the device builder (DESIGN 8.15)
+//   node tools/generate_timing.mjs <N> [repeats = 3] [P = 80] [deviceMesh | devicePoints]      deviceMesh: the mesh from the device builder (DESIGN 8.15);
+//                                                                             devicePoints: the points from the device as well (DESIGN 8.16)
 import path from 'path';
 import { fileURLToPath } from 'url';
 import { Worker } from 'worker_threads';
 
 const here = path.dirname(fileURLToPath(import.meta.url));
-const N = Number(process.argv[2]), repeats = Number(process.argv[3] || 3), P = Number(process.argv[4] || 80), deviceMesh = process.argv[5] === 'deviceMesh';
+const N = Number(process.argv[2]), repeats = Number(process.argv[3] || 3), P = Number(process.argv[4] || 80), deviceMesh = process.argv[5] === 'deviceMesh',
+      devicePoints = process.argv[5] === 'devicePoints';
 if (!(Number.isInteger(N) && N >= 1 && Number.isInteger(repeats) && repeats >= 1)) { console.error('usage: node generate_timing.mjs <N> [repeats] [P]'); process.exit(2); }
 const message = { cmd: 'generate', N, P, jitter: 0.75, nMag: 0.4, numContinents: 4, seed: 1, terrainWarp: 0.75, smoothing: 0.10, glacialErosion: 0.50,
-                  hydraulicErosion: 0.50, thermalErosion: 0.10, ridgeSharpening: 0.50, deviceMesh };       // the generator page's defaults
+                  hydraulicErosion: 0.50, thermalErosion: 0.10, ridgeSharpening: 0.50, deviceMesh, devicePoints };       // the generator page's defaults
 const w = new Worker(path.join(here, '..', 'planet_heightmap_generation_amd', 'js', 'planet-worker.js'));
 let waiting = null;
 w.on('message', (m) => { if (m.type !== 'progress' && waiting) { const f = waiting; waiting = null; f(m); } });
@@ -24,7 +26,7 @@ async function main() {
         if (d.type !== 'done') { console.error('generate answered', d.type, d.message); process.exit(1); }
         if (i > 0) runs.push(d);
     }
-    const out = { N, P, repeats, deviceMesh, stages: {}, workerTotal: stat(runs.map((d) => d._workerTotal)) };
+    const out = { N, P, repeats, deviceMesh, devicePoints, stages: {}, workerTotal: stat(runs.map((d) => d._workerTotal)) };
     runs[0]._pipelineTiming.forEach((s, k) => { out.stages[s.stage] = stat(runs.map((d) => d._pipelineTiming[k].ms)); });
     await ask({ cmd: 'dispose' });
     await w.terminate();
