@@ -73,7 +73,11 @@ int         wo_memory_in_use(int64_t* deviceBytes, int64_t* pinnedBytes, int64_t
 int wo_fib_sphere_points(int32_t N, double jitter, double seed, float* r_xyz);
 /* Spherical Delaunay of numRegions unit vectors == the reference's stereographic Delaunator run +
  * addPoleToMesh (js/sphere-mesh.js:41-90,174-186).  triangles / halfedges have 3*(2*numRegions-4)
- * entries, counter-clockwise seen from outside, same contract as Delaunator's arrays. */
+ * entries, counter-clockwise seen from outside, same contract as Delaunator's arrays.  Status: 1 bad arguments (a NULL
+ * pointer, fewer than 4 points, a zero-length point), 2 star construction failed: a star of more than 48 neighbours or a duplicate
+ * point, or, with a message of its own, a point set whose hull does not hold the sphere's centre strictly inside (points inside a
+ * hemisphere have no triangulation of the sphere, and are refused instead of answered with their hull), 3 triangle count != 2V-4,
+ * 4 unmatched half-edges.  Nothing is written to the outputs on status 1 and 2. */
 int wo_sphere_delaunay(int32_t numRegions, const float* r_xyz, int32_t* triangles, int32_t* halfedges);
 /* Renumbers the closing fan of a triangulation from wo_sphere_delaunay (the pole is region numRegions - 1) the way the
  * reference's addPoleToMesh does on the planar part (js/sphere-mesh.js:55-88): the triangles without the pole first, in
@@ -119,7 +123,8 @@ void    wo_ctx_destroy(wo_ctx* ctx);
  * wo_neighbor_dist.  triangles / halfedges have 3*(2*numRegions-4) entries, adjOffset numRegions+1; adjList, adjTriList (may be
  * NULL) and neighborDist (may be NULL) have room for 3*(2*numRegions-4) entries, of which the first adjOffset[numRegions] are
  * written.  Status and message are the host's on the same input: 1 bad arguments (a NULL context or pointer, fewer than 4 points,
- * a zero-length point; a NULL context never touches the device), 2 star construction failed, 3 triangle count != 2V-4,
+ * a zero-length point; a NULL context never touches the device), 2 star construction failed (the refusal of a point set whose
+ * hull does not hold the centre strictly inside included, see wo_sphere_delaunay), 3 triangle count != 2V-4,
  * 4 unmatched half-edges; 5 stands for any failure of the CSR stage, which a triangulation that passed 3 and 4 does not reach.
  * Nothing stays allocated after the call. */
 int wo_sphere_delaunay_device(wo_ctx* ctx, int32_t numRegions, const float* r_xyz, int32_t* triangles, int32_t* halfedges);

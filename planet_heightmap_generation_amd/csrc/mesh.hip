@@ -61,7 +61,7 @@ constexpr int SCAN_ITEMS = 8;                     // consecutive elements per th
 constexpr int SCAN_TILE = WO_BLOCK * SCAN_ITEMS;
 
 // the call's words on the device
-enum Ctrl : int { C_ZERO_LEN = 0, C_RETRY, C_HOST, C_FAILED, C_BIG, C_BAD_HE, C_TOTAL_DEG, C_TOTAL_T, C_CSR_BAD, C_TOTAL_ADJ, C_TOTAL_CELLS, C_COUNT = 16 };
+enum Ctrl : int { C_ZERO_LEN = 0, C_RETRY, C_HOST, C_FAILED, C_BIG, C_BAD_HE, C_TOTAL_DEG, C_TOTAL_T, C_CSR_BAD, C_TOTAL_ADJ, C_TOTAL_CELLS, C_OUTSIDE, C_COUNT = 16 };
 
 // where the stars live: STAR_INLINE entries per point, and a pool of MAX_STAR entries per big star
 struct StarStore {
@@ -232,7 +232,10 @@ __global__ __launch_bounds__(WO_BLOCK) void k_mesh_stars_retry(const int32_t* __
             const int d = M::star_at_level(p, pts, g, cx, cy, cz, level, brute, cand, st, failcode);
             if (d >= 0) { toHost = !take_star(S, p, st, d); settled = true; break; }
         }
-        if (!settled && !toHost) atomicAdd(&S.ctrl[C_FAILED], 1);
+        if (!settled && !toHost) {
+            atomicAdd(&S.ctrl[C_FAILED], 1);
+            if (failcode == M::FAIL_CENTRE_OUTSIDE) atomicAdd(&S.ctrl[C_OUTSIDE], 1);       // only the brute level sets it, and it is the last
+        }
     }
     wave_append(toHost, p, hostList, S.ctrl + C_HOST);
 }
@@ -448,7 +451,7 @@ void mesh_device(wo_ctx* ctx, int32_t V, const MeshIn& in, const MeshOut& out) {
     gridTmp.clear();
     if (h_ctrl[C_ZERO_LEN]) throw StatusError{1, "sphere_delaunay: zero-length point"};
     const int32_t nRetry = h_ctrl[C_RETRY];
-    int64_t failed = 0;
+    int64_t failed = 0, outside = 0;
     if (nRetry > 0) {
         DeviceArena R;
         const int32_t batch = std::min(nRetry, RETRY_BATCH);
@@ -466,9 +469,10 @@ void mesh_device(wo_ctx* ctx, int32_t V, const MeshIn& in, const MeshOut& out) {
             WO_HIP(hipMemcpyAsync(ids.data(), hostList, (size_t)nHost * sizeof(int32_t), hipMemcpyDeviceToHost, s));
             WO_HIP(hipStreamSynchronize(s));
             std::sort(ids.begin(), ids.end());
-            const int hostFailed = stars_on_host(V, xyz, nHost, ids.data(), hdeg, hstars);
+            int hostOutside = 0;
+            const int hostFailed = stars_on_host(V, xyz, nHost, ids.data(), hdeg, hstars, &hostOutside);
             if (hostFailed < 0) throw StatusError{1, "sphere_delaunay: zero-length point"};
-            failed += hostFailed;
+            failed += hostFailed; outside += hostOutside;
             std::vector<int32_t> hoff((size_t)nHost + 1, 0);
             int32_t nBig = 0;
             for (int32_t i = 0; i < nHost; ++i) { hoff[i + 1] = hoff[i] + hdeg[i]; if (hdeg[i] > M::STAR_INLINE) ++nBig; }
@@ -490,8 +494,8 @@ void mesh_device(wo_ctx* ctx, int32_t V, const MeshIn& in, const MeshOut& out) {
             WO_HIP(hipStreamSynchronize(s));                  // before the host vectors and R go
         }
     }
-    failed += h_ctrl[C_FAILED];
-    if (failed != 0) throw StatusError{2, "sphere_delaunay: star construction failed for " + std::to_string(failed) + " points"};
+    failed += h_ctrl[C_FAILED]; outside += h_ctrl[C_OUTSIDE];
+    if (failed != 0) throw StatusError{2, star_failure_message(failed, outside)};
 
     // ---- triangles and half-edges
     int32_t* starOff = A.dev<int32_t>((size_t)V + 1);

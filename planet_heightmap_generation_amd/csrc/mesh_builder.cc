@@ -174,7 +174,8 @@ bool normalise_points(int V, const float* xyz, std::vector<P3>& pts) {
 // The stars of the listed points, as sphere_delaunay computes them (the device builder's completion, mesh.hip): degOut[i] is the
 // degree of ids[i], 0 for a failed star, and starsOut holds the stars back to back, rotated to their lowest neighbour.
 // Returns the number of failed stars, -1 for a zero-length point.
-int stars_on_host(int V, const float* xyz, int n, const int* ids, std::vector<int>& degOut, std::vector<int>& starsOut) {
+int stars_on_host(int V, const float* xyz, int n, const int* ids, std::vector<int>& degOut, std::vector<int>& starsOut, int* centreOutside) {
+    if (centreOutside) *centreOutside = 0;
     std::vector<P3> pts;
     if (!normalise_points(V, xyz, pts)) return -1;
     Grid g;
@@ -182,13 +183,13 @@ int stars_on_host(int V, const float* xyz, int n, const int* ids, std::vector<in
     const mesh::GridView gv = g.view();
     degOut.assign(n, 0);
     std::vector<int> flat((size_t)n * MAX_STAR);
-    std::atomic<int> failed{0};
+    std::atomic<int> failed{0}, outside{0};
     parallel_ranges(n, [&](int64_t b, int64_t e, int) {
         std::vector<int> cand; cand.reserve(256);
         int st[MAX_STAR];
         for (int64_t i = b; i < e; ++i) {
             const int d = star_of(ids[i], pts.data(), V, gv, st, cand);
-            if (d < 3) { failed.fetch_add(1); continue; }
+            if (d < 3) { failed.fetch_add(1); if (d == mesh::FAIL_CENTRE_OUTSIDE) outside.fetch_add(1); continue; }
             const int m = mesh::lowest_position(st, d);
             degOut[i] = d;
             for (int k = 0; k < d; ++k) flat[(size_t)i * MAX_STAR + k] = st[(m + k) % d];
@@ -196,7 +197,15 @@ int stars_on_host(int V, const float* xyz, int n, const int* ids, std::vector<in
     }, 64);
     starsOut.clear();
     for (int i = 0; i < n; ++i) starsOut.insert(starsOut.end(), flat.begin() + (size_t)i * MAX_STAR, flat.begin() + (size_t)i * MAX_STAR + degOut[i]);
+    if (centreOutside) *centreOutside = outside.load();
     return failed.load();
+}
+
+std::string star_failure_message(long long failed, long long centreOutside) {
+    if (centreOutside > 0)
+        return "sphere_delaunay: the hull of the points does not hold the sphere's centre strictly inside (" + std::to_string(centreOutside) +
+               " points have a face that sees it): the points lie in a hemisphere and have no triangulation of the sphere";
+    return "sphere_delaunay: star construction failed for " + std::to_string(failed) + " points";
 }
 
 // triangles/halfedges sized 3*(2V-4).  Returns 0 on success.
@@ -216,13 +225,14 @@ int sphere_delaunay(int V, const float* xyz, int* triangles, int* halfedges, std
     std::vector<int> starBuf((size_t)V * 12);         // common case storage
     std::vector<std::vector<int>> bigStar;            // rare degree > 12
     std::vector<int> bigIndex(V, -1);
-    std::atomic<int> failed{0};
+    std::atomic<int> failed{0}, outside{0};
     std::vector<std::vector<std::pair<int, std::vector<int>>>> bigLocal(host_threads() + 1);
     parallel_ranges(V, [&](int64_t b, int64_t e, int tid) {
         std::vector<int> cand; cand.reserve(256);
         int st[MAX_STAR];
         for (int64_t p = b; p < e; ++p) {
             int d = star_of((int)p, pts.data(), V, gv, st, cand);
+            if (d == mesh::FAIL_CENTRE_OUTSIDE) outside.fetch_add(1);
             if (d < 3) { if (failed.fetch_add(1) == 0) fprintf(stderr, "star fail p=%d code=%d xyz=%.9g %.9g %.9g\n", (int)p, d, pts[p].x, pts[p].y, pts[p].z); deg[p] = 0; continue; }
             const int m = mesh::lowest_position(st, d);
             deg[p] = d;
@@ -235,7 +245,7 @@ int sphere_delaunay(int V, const float* xyz, int* triangles, int* halfedges, std
             }
         }
     }, 1024);
-    if (failed.load() != 0) { err = "sphere_delaunay: star construction failed for " + std::to_string(failed.load()) + " points"; return 2; }
+    if (failed.load() != 0) { err = star_failure_message(failed.load(), outside.load()); return 2; }
     for (auto& l : bigLocal) for (auto& pr : l) { bigIndex[pr.first] = (int)bigStar.size(); bigStar.push_back(std::move(pr.second)); }
     auto star = [&](int p) -> const int* { return bigIndex[p] >= 0 ? bigStar[bigIndex[p]].data() : &starBuf[(size_t)p * 12]; };
 

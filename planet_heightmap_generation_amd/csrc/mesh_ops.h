@@ -11,6 +11,9 @@
 //     where orientations are exactly zero.
 //   * star_at_level: nearest candidate (lowest index among equals) first, then Jarvis steps with a strict `> 0`, sequential in
 //     candidate order; the star is accepted when every face's circumcap lies inside the searched block (or the level is brute).
+//     A face whose outward normal n has n.P <= 0 sees the centre on its outer side: no block certifies it, and the brute level,
+//     which has seen every point, refuses the star with FAIL_CENTRE_OUTSIDE: the points lie in a closed hemisphere, their hull is
+//     no triangulation of the sphere.
 //   * The candidate list is a template parameter with size(), operator[] and push(): a std::vector on the host, a strided slice of
 //     LDS or of global scratch on the device.
 #pragma once
@@ -30,6 +33,7 @@ namespace mesh {
 constexpr int MAX_STAR = 48;          // a star of more neighbours is a failure
 constexpr int MAX_LEVEL = 6;          // levels 1..5 search a (2 level + 1)^3 block of cells, level 6 is brute
 constexpr int STAR_INLINE = 12;       // neighbours kept in the common per-point storage
+constexpr int FAIL_CENTRE_OUTSIDE = -4;   // failcode of a brute star with a face that does not have the centre strictly behind it
 
 struct P3 { double x, y, z; };
 
@@ -177,8 +181,10 @@ WO_MESH_HD inline int star_at_level(int p, const P3* pts, const GridView& g, int
             const double nl = sqrt(nx * nx + ny * ny + nz * nz);
             if (!(nl > 0.0)) { ok = false; failcode = -3; break; }
             nx /= nl; ny /= nl; nz /= nl;
-            if (nx * P.x + ny * P.y + nz * P.z <= 0.0) { certified = false; }
-            else {
+            if (nx * P.x + ny * P.y + nz * P.z <= 0.0) {
+                if (brute) { ok = false; failcode = FAIL_CENTRE_OUTSIDE; break; }
+                certified = false;
+            } else {
                 const double ex = nx - P.x, ey = ny - P.y, ez = nz - P.z;
                 const double rad = sqrt(ex * ex + ey * ey + ez * ez) * 1.000001 + 1e-12;
                 if (nx - rad < lox || nx + rad > hix || ny - rad < loy || ny + rad > hiy ||

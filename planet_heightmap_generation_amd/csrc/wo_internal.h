@@ -14,8 +14,11 @@ int sphere_delaunay(int V, const float* xyz, int* triangles, int* halfedges, std
 int mesh_csr(int V, int numSides, const int* triangles, const int* halfedges,
              int* adjOffset, int* adjList, int* adjTri, std::string& err);
 void neighbor_dist(int V, const int* adjOffset, const int* adjList, const float* xyz, float* out);
-// the stars of the listed points as sphere_delaunay computes them (the completion of the device builder, mesh.hip)
-int stars_on_host(int V, const float* xyz, int n, const int* ids, std::vector<int>& degOut, std::vector<int>& starsOut);
+// the stars of the listed points as sphere_delaunay computes them (the completion of the device builder, mesh.hip); centreOutside, when
+// given, receives how many of the failed stars have a face that does not hold the centre strictly behind it
+int stars_on_host(int V, const float* xyz, int n, const int* ids, std::vector<int>& degOut, std::vector<int>& starsOut, int* centreOutside = nullptr);
+// the message of status 2, for both builders: `failed` stars in all, `centreOutside` of them refused for the centre
+std::string star_failure_message(long long failed, long long centreOutside);
 
 // flood_host.cc
 #if defined(__HIPCC__)

@@ -76,7 +76,9 @@ def device_sphere_mesh(r_xyz: np.ndarray, reference_closure: bool, ctx):
 
 def sphere_mesh_from_points(r_xyz: np.ndarray, reference_closure: bool = False, ctx=None) -> SphereMesh:
     """reference_closure: number the closing pole fan the way the reference's addPoleToMesh does (js/sphere-mesh.js:55-88).
-    ctx: a terrain_post.Context sends the work to the device builder (the same arrays); None: the host builder."""
+    ctx: a terrain_post.Context sends the work to the device builder (the same arrays); None: the host builder.
+    Raises capi.WorogenError (status 2) for points whose hull does not hold the sphere's centre strictly inside, e.g. points inside
+    a hemisphere: they have no triangulation of the sphere."""
     if ctx is not None:
         return device_sphere_mesh(r_xyz, reference_closure, ctx)[0]
     r_xyz = np.ascontiguousarray(r_xyz, dtype=np.float32).reshape(-1)

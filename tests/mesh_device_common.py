@@ -58,6 +58,121 @@ def duplicate():
     return np.ascontiguousarray(p).reshape(-1)
 
 
+def _unit32(p):
+    p = np.asarray(p, np.float64)
+    return np.ascontiguousarray(p / np.linalg.norm(p, axis=1)[:, None], np.float32).reshape(-1)
+
+
+def clusters(k, m, seed=11):
+    """k tight clusters of m points: the centres are fibonacci_sphere(k - 1, 0.75, 2), the points centre + N(0, 1e-3), normalised.  The
+    cell edge follows the point count, so every cluster sits in a few cells: hundreds to thousands of level-1 candidates per point."""
+    c = fib(k - 1, 0.75, 2).reshape(-1, 3).astype(np.float64)
+    rng = np.random.default_rng(seed)
+    return _unit32((c[:, None, :] + rng.normal(0.0, 1e-3, (k, m, 3))).reshape(-1, 3))
+
+
+def fib_plus_cluster(N, at, m, seed=12):
+    """fibonacci_sphere(N, 0.75, 5) and m more points at its point `at` + N(0, 1e-3): the cluster's cells hold more than a retry
+    buffer does, while the cell edge is that of a sparse sphere"""
+    p = fib(N, 0.75, 5)
+    rng = np.random.default_rng(seed)
+    return np.concatenate([p, _unit32(p.reshape(-1, 3)[at].astype(np.float64) + rng.normal(0.0, 1e-3, (m, 3)))])
+
+
+def hubs(n, k, radius=0.07, seed=13):
+    """n hub points (fibonacci_sphere(n - 1, 0.75, 1)), each inside a ring of k points of radius `radius` spacings (angles jittered by
+    +-0.2 of a step, radii by +-3 %): every hub is a star of k neighbours.  Hubs first, then the rings hub by hub."""
+    c = fib(n - 1, 0.75, 1).reshape(-1, 3).astype(np.float64)
+    c /= np.linalg.norm(c, axis=1)[:, None]
+    rng = np.random.default_rng(seed)
+    ref = np.where(np.abs(c[:, 2:3]) < 0.9, [[0.0, 0.0, 1.0]], [[1.0, 0.0, 0.0]])
+    u = np.cross(c, ref)
+    u /= np.linalg.norm(u, axis=1)[:, None]
+    v = np.cross(c, u)
+    ang = (np.arange(k)[None, :] + rng.uniform(-0.2, 0.2, (n, k))) * (2 * np.pi / k)
+    rad = radius * np.sqrt(4 * np.pi / n) * (1 + rng.uniform(-0.03, 0.03, (n, k)))
+    ring = c[:, None, :] + rad[..., None] * (np.cos(ang)[..., None] * u[:, None, :] + np.sin(ang)[..., None] * v[:, None, :])
+    return np.concatenate([_unit32(c), _unit32(ring.reshape(-1, 3))])
+
+
+def hemi_and_three(N):
+    """the points of z > 0.5 of fibonacci_sphere(N, 0.75, 5) and three far points that close the hull round the centre: the faces at
+    the three are as wide as a hemisphere, no block of cells certifies them, and the rim's stars reach the brute level"""
+    p = fib(N, 0.75, 5).reshape(-1, 3)
+    far = np.array([[0, 0, -1], [0.6, 0, -0.8], [-0.6, 0.1, -0.79]], np.float32)
+    return np.ascontiguousarray(np.concatenate([p[p[:, 2] > 0.5], far])).reshape(-1)
+
+
+def polering(k, seed=14):
+    """fibonacci_sphere(3000, 0.75, 5) without its points of z >= 0.97, k points on the parallel of colatitude 8 degrees (radii
+    jittered by +-3e-4 of the radius, angles by +-0.2 of a step: a wider radial jitter hides ring points from the pole), the pole
+    last: the pole's star has k neighbours"""
+    p = fib(3000, 0.75, 5).reshape(-1, 3)
+    p = p[p[:, 2] < 0.97]
+    rng = np.random.default_rng(seed)
+    ang = (np.arange(k) + rng.uniform(-0.2, 0.2, k)) * (2 * np.pi / k)
+    col = np.deg2rad(8.0) * (1 + rng.uniform(-3e-4, 3e-4, k))
+    ring = np.stack([np.sin(col) * np.cos(ang), np.sin(col) * np.sin(ang), np.cos(col)], 1)
+    return np.concatenate([np.ascontiguousarray(p).reshape(-1), _unit32(ring), np.array([0, 0, 1], np.float32)])
+
+
+def hemisphere(N, zmin):
+    """only the points of z > zmin of fibonacci_sphere(N, 0.75, 5): inside an open hemisphere, refused"""
+    p = fib(N, 0.75, 5).reshape(-1, 3)
+    return np.ascontiguousarray(p[p[:, 2] > zmin]).reshape(-1)
+
+
+# the sets of tests/test_mesh_delaunay.py and tests/test_gpu_mesh_builder.py that the builders accept, and the branch of the device
+# builder each one reaches (asserted from numpy or from the host route in test_mesh_delaunay.py)
+NEW_ACCEPTED = ("clusters:12x1500", "fib2000+cluster4500", "hubs:2000x13", "hemi:40000+3", "polering:48")
+HEMISPHERES = {"hemisphere:2000": (2000, 0.5), "hemisphere:20000": (20000, 0.2)}
+
+
+@lru_cache(maxsize=None)
+def point_set(name):
+    """the point set of a name, as every test of the mesh builders spells it"""
+    kind, _, rest = name.partition(":")
+    if kind == "fib":
+        N, j = rest.split(",")
+        return fib(int(N), float(j), 5)
+    if kind == "cap":
+        return cap_and_sparse(int(rest))
+    if kind == "latlon":
+        r, n = rest.split("x")
+        return latlon(int(r), int(n))
+    if kind == "clusters":
+        k, m = rest.split("x")
+        return clusters(int(k), int(m))
+    if kind == "hubs":
+        n, k = rest.split("x")
+        return hubs(int(n), int(k))
+    if kind == "polering":
+        return polering(int(rest))
+    if kind == "hemisphere":
+        return hemisphere(*HEMISPHERES[name])
+    if name == "fib2000+cluster4500":
+        return fib_plus_cluster(2000, 777, 4500)
+    if name == "hemi:40000+3":
+        return hemi_and_three(40000)
+    return dict(octahedron=octahedron, ulp=ulp_pair, cube=cube, duplicate=duplicate)[kind]()
+
+
+def level1_candidates(xyz):
+    """How many candidates level 1 offers every point: the grid contract of csrc/mesh_ops.h restated in numpy (cell edge
+    h = min(0.5, 2 sqrt(4 pi / V)), G = ceil(2 / h) + 1 cells per axis from -1, coord = clip(floor((v + 1) / h), 0, G - 1)), the
+    points of the 27 cells round a point's own, less the point itself."""
+    from delaunay_check import unit_points
+    P = unit_points(xyz)
+    V = P.shape[0]
+    h = min(0.5, 2.0 * np.sqrt(4.0 * np.pi / V))
+    G = int(np.ceil(2.0 / h)) + 1
+    c = np.clip(np.floor((P + 1.0) / h).astype(np.int64), 0, G - 1)
+    cnt = np.zeros((G + 2, G + 2, G + 2), np.int64)
+    np.add.at(cnt, (c[:, 0] + 1, c[:, 1] + 1, c[:, 2] + 1), 1)
+    block = sum(cnt[1 + dx:G + 1 + dx, 1 + dy:G + 1 + dy, 1 + dz:G + 1 + dz] for dx in (-1, 0, 1) for dy in (-1, 0, 1) for dz in (-1, 0, 1))
+    return block[c[:, 0], c[:, 1], c[:, 2]] - 1, G
+
+
 NAMES = ("triangles", "halfedges", "adjOffset", "adjList", "adjTriList", "neighborDist")
 
 

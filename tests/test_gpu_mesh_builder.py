@@ -6,12 +6,18 @@ sentinels), and wo_memory_in_use is back to its starting value after every case.
 The point sets: Fibonacci spheres from V = 4 (all brute) over N = 63 (brute and level 1 mixed: level 2 spans the whole grid) and
 N = 256 (a workgroup and one lane) to 1 M cells (level-2 stars, degree 12); the committed goldens; crafted sets the host builder
 succeeds on (the octahedron, a lat-lon grid with pole degree 16 and rows of near-cocircular quadruples, a dense cap over a sparse
-sphere with up to 769 candidates, two points one f32 ulp apart); and the sets it refuses, with its status."""
+sphere with up to 769 candidates, two points one f32 ulp apart); the sets of mesh_device_common.NEW_ACCEPTED, which reach the
+hand-over's branches with no hook (a second, partly filled retry batch; more candidates than the retry buffer holds; the pool of
+big stars running full in level 1 and grown by the host; brute force on more points than the device takes; a star of exactly
+MAX_STAR neighbours), each under the condition tests/test_mesh_delaunay.py asserts; and the sets the host refuses, with its status
+and message.  test_properties_without_the_host_route holds the device's own arrays to the Delaunay property by
+tests/delaunay_check.py, with the host route out of the picture."""
 from functools import lru_cache
 
 import numpy as np
 import pytest
 
+import delaunay_check as DC
 import hooks
 import mesh_device_common as MD
 from conftest import load_golden
@@ -19,18 +25,7 @@ from conftest import load_golden
 pytestmark = pytest.mark.gpu
 
 
-@lru_cache(maxsize=None)
-def points(name):
-    kind, _, rest = name.partition(":")
-    if kind == "fib":
-        N, j = rest.split(",")
-        return MD.fib(int(N), float(j), 5)
-    if kind == "cap":
-        return MD.cap_and_sparse(int(rest))
-    if kind == "latlon":
-        r, n = rest.split("x")
-        return MD.latlon(int(r), int(n))
-    return dict(octahedron=MD.octahedron, ulp=MD.ulp_pair, cube=MD.cube, duplicate=MD.duplicate)[kind]()
+points = MD.point_set
 
 
 @lru_cache(maxsize=None)
@@ -91,12 +86,23 @@ def test_goldens(name):
 
 
 @pytest.mark.parametrize("closure", [False, True], ids=["plain", "closure"])
-@pytest.mark.parametrize("name,V,maxdeg", [("octahedron", 6, 4), ("latlon:7x16", 114, 16), ("cap:3000", 219, None), ("cap:40000", 2943, None), ("ulp", 2001, None)])
+@pytest.mark.parametrize("name,V,maxdeg", [("octahedron", 6, 4), ("latlon:7x16", 114, 16), ("cap:3000", 219, None), ("cap:40000", 2943, None), ("ulp", 2001, None),
+                                           ("polering:48", 3002, 48)])
 def test_crafted_point_sets(name, V, maxdeg, closure):
     assert points(name).size == 3 * V
     h = check_case(name, closure)
     if maxdeg is not None:
-        assert np.diff(h["adjOffset"]).max() == maxdeg    # 16: beyond the common storage of a star
+        assert np.diff(h["adjOffset"]).max() == maxdeg    # 16: beyond the common storage of a star; 48: MAX_STAR, the last accepted
+    check_case(name, False, csr=False)
+
+
+@pytest.mark.parametrize("closure", [False, True], ids=["plain", "closure"])
+@pytest.mark.parametrize("name,V", [("clusters:12x1500", 18000), ("fib2000+cluster4500", 6501), ("hubs:2000x13", 28000), ("hemi:40000+3", 10008)])
+def test_hand_over_branches_without_a_hook(name, V, closure):
+    """two retry batches, the second partly filled; candidates past RETRY_CAP; the pool of big stars full in k_mesh_stars_l1 and grown by
+    the host; brute force on more than RETRY_CAP + 1 points: what makes each set reach its branch is asserted in test_mesh_delaunay.py"""
+    assert name in MD.NEW_ACCEPTED and points(name).size == 3 * V
+    check_case(name, closure)
     check_case(name, False, csr=False)
 
 
@@ -106,13 +112,18 @@ def test_optional_outputs_may_be_null():
     assert rc == 0 and all(np.array_equal(d[k], h[k]) for k in d) and set(d) == {"triangles", "halfedges", "adjOffset", "adjList"}
 
 
-@pytest.mark.parametrize("name,status", [("cube", 3), ("duplicate", 2), ("latlon:63x128", 2), ("fib:2,0.75", 1)])
+@pytest.mark.parametrize("name,status", [("cube", 3), ("duplicate", 2), ("latlon:63x128", 2), ("fib:2,0.75", 1), ("polering:49", 2), ("hemisphere:2000", 2),
+                                         ("hemisphere:20000", 2)])
 def test_failures_have_the_hosts_status(name, status):
     from planet_heightmap_generation_amd import capi
     check_case(name, False, want_status=status)
     host_message = (MD.host_route(points(name))[0], capi.last_error())[1]
     MD.device_route(points(name))
     assert capi.last_error() == host_message
+    if name.startswith("hemisphere"):                     # the refusal says what is wrong (499 points: brute on the device; 7 993: on the host)
+        assert "does not hold the sphere's centre strictly inside" in host_message and "hemisphere" in host_message
+    if name == "polering:49":
+        assert host_message == "sphere_delaunay: star construction failed for 1 points"
     check_case(name, False, csr=False, want_status=status)
     check_case("fib:2000,0.75", True)                     # the context still serves the next call
 
@@ -145,21 +156,40 @@ def test_hooks_give_the_plain_result(name, hook, monkeypatch):
     assert MD.same(plain, h)
 
 
+@pytest.mark.parametrize("hook", [dict(mesh_cand_cap=8), dict(mesh_device_levels=0)], ids=["cand_cap=8", "device_levels=0"])
+@pytest.mark.parametrize("name", ["hubs:2000x13", "fib2000+cluster4500"])
+def test_hooks_give_the_plain_result_on_the_hand_over_sets(name, hook, monkeypatch):
+    """the pool of big stars grows when every big star is the host's (hubs: 1 964 of them for a pool of 1 814), and when the retry kernel
+    meets the full pool instead of level 1"""
+    _, plain = MD.device_route(points(name), True)
+    for k, v in hook.items():
+        hooks.set_hook(monkeypatch, k, v)
+    h = check_case(name, True)
+    assert MD.same(plain, h)
+
+
+def test_three_retry_batches_give_the_plain_result(monkeypatch):
+    """mesh_cand_cap=8 on 40 001 points: all of them retry, in batches of 16 384, 16 384 and 7 233"""
+    name = "fib:40000,0.75"
+    assert 2 * 16384 < points(name).size // 3 < 3 * 16384
+    _, plain = MD.device_route(points(name), True)
+    hooks.set_hook(monkeypatch, "mesh_cand_cap", 8)
+    h = check_case(name, True)
+    assert MD.same(plain, h)
+
+
 def test_properties_without_the_host_route():
-    xyz = points("fib:20000,0.75")
-    rc, d = MD.device_route(xyz, False)
-    assert rc == 0
-    V = xyz.size // 3
-    tri, he = d["triangles"], d["halfedges"]
-    assert tri.size == 3 * (2 * V - 4)
-    assert np.array_equal(he[he], np.arange(he.size))
-    P = xyz.reshape(-1, 3).astype(np.float64)
-    P /= np.linalg.norm(P, axis=1)[:, None]
-    T = tri.reshape(-1, 3)
-    vol = np.einsum("ij,ij->i", np.cross(P[T[:, 1]] - P[T[:, 0]], P[T[:, 2]] - P[T[:, 0]]), P[T[:, 0]])
-    assert (vol > 0).all()                                   # counter-clockwise seen from outside
-    deg = np.diff(d["adjOffset"])
-    assert deg.min() >= 3 and abs(deg.mean() - 6) < 1e-3
+    """the device's own arrays are a Delaunay triangulation by tests/delaunay_check.py: closed, outward, covering the sphere once, locally
+    convex at every side.  The host route, which compiles the same bodies, is not asked."""
+    for name in ("fib:20000,0.75", "cap:40000", "hemi:40000+3"):
+        xyz = points(name)
+        V = xyz.size // 3
+        rc, d = MD.device_route(xyz, False)
+        assert rc == 0
+        fig = DC.assert_delaunay(name, xyz, d["triangles"], d["halfedges"])
+        assert fig["V"] == V and fig["min_volume"] > 0       # counter-clockwise seen from outside
+        deg = np.diff(d["adjOffset"])
+        assert deg.min() >= 3 and deg.sum() == 6 * V - 12    # the mean degree is 6 - 12 / V
 
 
 def _same_done(a, b, skip=("_timing", "_pipelineTiming", "_postTiming", "_workerTotal", "mesh")):

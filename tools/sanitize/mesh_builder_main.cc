@@ -2,8 +2,11 @@
 // wo_sphere_delaunay, wo_sphere_reference_closure, wo_mesh_csr and wo_neighbor_dist into exactly sized buffers, and stars_on_host (the
 // completion the device builder hands its unsettled points to), on the crafted point sets of tests/mesh_device_common.py: the
 // octahedron, a lat-lon grid with pole degree 16 (the bigStar case), a dense cap over a sparse sphere (level-2 stars, 769 candidates),
-// two points one f32 ulp apart, small spheres that are all brute; and the sets the builder refuses (the cube, a duplicate point, a
-// pole of degree 128, three points).  CPU only, no GPU call, not loaded into Python.
+// two points one f32 ulp apart, small spheres that are all brute; the sets that drive the completion hardest (tight clusters with
+// thousands of candidates per point, a sphere with one such cluster, hubs of degree 13 in their thousands, most of a hemisphere closed
+// by three far points, a pole of exactly MAX_STAR neighbours; the same constructions as in the tests, with this file's own random
+// numbers); and the sets the builder refuses (the cube, a duplicate point, a pole of degree 128, a pole of degree 49, three points,
+// and point sets inside a hemisphere, refused for the centre).  CPU only, no GPU call, not loaded into Python.
 //
 //   cd planet_heightmap_generation_amd/csrc && g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -ffp-contract=off -fsanitize=address,undefined \
 //       -fno-sanitize-recover=undefined ../../tools/sanitize/mesh_builder_main.cc api_host.cc mesh_builder.cc noise_host.cc plates_host.cc \
@@ -11,6 +14,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <random>
 #include <string>
 #include <vector>
 
@@ -61,6 +65,98 @@ static Points duplicate() {
     return p;
 }
 
+static void push_unit(Points& p, double x, double y, double z) {
+    const double l = std::sqrt(x * x + y * y + z * z);
+    p.push_back((float)(x / l)); p.push_back((float)(y / l)); p.push_back((float)(z / l));
+}
+// m points at c + N(0, 1e-3), normalised
+static void add_cluster(Points& p, const float* c, int m, std::mt19937_64& rng) {
+    std::normal_distribution<double> n(0.0, 1e-3);
+    for (int i = 0; i < m; ++i) { const double x = c[0] + n(rng), y = c[1] + n(rng), z = c[2] + n(rng); push_unit(p, x, y, z); }
+}
+static Points clusters(int k, int m) {
+    const Points c = fib(k - 1, 0.75, 2);
+    std::mt19937_64 rng(11);
+    Points p;
+    for (int i = 0; i < k; ++i) add_cluster(p, &c[3 * i], m, rng);
+    return p;
+}
+static Points fib_plus_cluster(int32_t N, int at, int m) {
+    Points p = fib(N, 0.75, 5);
+    const float c[3] = {p[3 * at], p[3 * at + 1], p[3 * at + 2]};
+    std::mt19937_64 rng(12);
+    add_cluster(p, c, m, rng);
+    return p;
+}
+// a ring of k points round the direction c at angular radius rad (jittered by +-radJitter of it), the angles jittered by +-0.2 of a step
+static void add_ring(Points& p, const double* c, int k, double rad, double radJitter, std::mt19937_64& rng) {
+    std::uniform_real_distribution<double> u(-1.0, 1.0);
+    const double PI = 3.141592653589793;
+    const double ref[3] = {std::fabs(c[2]) < 0.9 ? 0.0 : 1.0, 0.0, std::fabs(c[2]) < 0.9 ? 1.0 : 0.0};
+    double a[3] = {c[1] * ref[2] - c[2] * ref[1], c[2] * ref[0] - c[0] * ref[2], c[0] * ref[1] - c[1] * ref[0]};
+    const double al = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    for (double& v : a) v /= al;
+    const double b[3] = {c[1] * a[2] - c[2] * a[1], c[2] * a[0] - c[0] * a[2], c[0] * a[1] - c[1] * a[0]};
+    for (int j = 0; j < k; ++j) {
+        const double ang = (j + 0.2 * u(rng)) * 2 * PI / k, r = rad * (1 + radJitter * u(rng));
+        const double ct = std::cos(r), st = std::sin(r);
+        push_unit(p, ct * c[0] + st * (std::cos(ang) * a[0] + std::sin(ang) * b[0]), ct * c[1] + st * (std::cos(ang) * a[1] + std::sin(ang) * b[1]),
+                  ct * c[2] + st * (std::cos(ang) * a[2] + std::sin(ang) * b[2]));
+    }
+}
+static Points hubs(int n, int k) {
+    Points p = fib(n - 1, 0.75, 1);
+    std::mt19937_64 rng(13);
+    for (int i = 0; i < n; ++i) {
+        const double c[3] = {p[3 * i], p[3 * i + 1], p[3 * i + 2]};
+        add_ring(p, c, k, 0.07 * std::sqrt(4 * 3.141592653589793 / n), 0.03, rng);
+    }
+    return p;
+}
+static Points hemisphere(int32_t N, float zmin) {
+    const Points all = fib(N, 0.75, 5);
+    Points p;
+    for (size_t i = 0; i < all.size() / 3; ++i)
+        if (all[3 * i + 2] > zmin) p.insert(p.end(), all.begin() + 3 * i, all.begin() + 3 * i + 3);
+    return p;
+}
+static Points hemi_and_three(int32_t N) {
+    Points p = hemisphere(N, 0.5f);
+    for (float v : {0.f, 0.f, -1.f, 0.6f, 0.f, -0.8f, -0.6f, 0.1f, -0.79f}) p.push_back(v);
+    return p;
+}
+static Points polering(int k) {
+    const Points all = fib(3000, 0.75, 5);
+    Points p;
+    for (size_t i = 0; i < all.size() / 3; ++i)
+        if (all[3 * i + 2] < 0.97f) p.insert(p.end(), all.begin() + 3 * i, all.begin() + 3 * i + 3);
+    std::mt19937_64 rng(14);
+    const double pole[3] = {0, 0, 1};
+    add_ring(p, pole, k, 8.0 * 3.141592653589793 / 180.0, 3e-4, rng);
+    for (float v : {0.f, 0.f, 1.f}) p.push_back(v);
+    return p;
+}
+
+// a refused set through the completion as well: every star by id; the failed ones are counted, and those refused for the centre
+static int refused_case(const char* name, const Points& xyz, bool forTheCentre) {
+    const int32_t V = (int32_t)(xyz.size() / 3);
+    std::vector<int> ids(V), deg, stars;
+    for (int i = 0; i < V; ++i) ids[i] = i;
+    int outside = -1;
+    const int failed = wo::stars_on_host(V, xyz.data(), V, ids.data(), deg, stars, &outside);
+    size_t total = 0;
+    int zero = 0;
+    for (int i = 0; i < V; ++i) { total += deg[i]; zero += deg[i] == 0; }
+    const std::string msg = wo::star_failure_message(failed, outside);
+    const bool says = msg.find("hemisphere") != std::string::npos;
+    if (failed <= 0 || zero != failed || total != stars.size() || (outside > 0) != forTheCentre || (forTheCentre && outside != failed) || says != forTheCentre) {
+        std::fprintf(stderr, "%s: stars_on_host: %d failed, %d for the centre, %d of degree 0 (%s)\n", name, failed, outside, zero, msg.c_str());
+        return 1;
+    }
+    std::printf("%-14s V %6d  refused: %d stars failed, %d for the centre\n", name, V, failed, outside);
+    return 0;
+}
+
 // the whole host route on one point set; wantStatus is wo_sphere_delaunay's
 static int run_case(const char* name, const Points& xyz, int wantStatus, int wantMaxDeg) {
     const int32_t V = (int32_t)(xyz.size() / 3);
@@ -69,7 +165,10 @@ static int run_case(const char* name, const Points& xyz, int wantStatus, int wan
         std::vector<int32_t> tri(ns), he(ns);
         const int rc = wo_sphere_delaunay(V, xyz.data(), tri.data(), he.data());
         if (rc != wantStatus) { std::fprintf(stderr, "%s: wo_sphere_delaunay gives %d, expected %d (%s)\n", name, rc, wantStatus, wo_last_error()); return 1; }
-        if (rc != 0) continue;
+        if (rc != 0) {
+            if (rc == 2 && !closure && refused_case(name, xyz, std::string(wo_last_error()).find("hemisphere") != std::string::npos)) return 1;
+            continue;
+        }
         if (closure && wo_sphere_reference_closure(V, tri.data(), he.data())) { std::fprintf(stderr, "%s: closure: %s\n", name, wo_last_error()); return 1; }
         std::vector<int32_t> off((size_t)V + 1), adj(ns), adjt(ns);
         if (wo_mesh_csr(V, (int32_t)ns, tri.data(), he.data(), off.data(), adj.data(), adjt.data())) { std::fprintf(stderr, "%s: wo_mesh_csr: %s\n", name, wo_last_error()); return 1; }
@@ -112,9 +211,21 @@ int main() {
     bad += run_case("ulp pair", ulp_pair(), 0, 0);
     for (int32_t N : {3, 4, 5, 12, 63, 256, 2000}) bad += run_case(("fib " + std::to_string(N)).c_str(), fib(N, 0.75, 5), 0, 0);
     bad += run_case("fib 20000 j0", fib(20000, 0.0, 5), 0, 0);
+    bad += run_case("clusters 12x1500", clusters(12, 1500), 0, 0);
+    bad += run_case("fib+cluster", fib_plus_cluster(2000, 777, 4500), 0, 0);
+    bad += run_case("hubs 2000x13", hubs(2000, 13), 0, 0);
+    bad += run_case("hemi 40000+3", hemi_and_three(40000), 0, 0);
+    bad += run_case("polering 48", polering(48), 0, 48);
     bad += run_case("cube", cube(), 3, 0);
     bad += run_case("duplicate", duplicate(), 2, 0);
     bad += run_case("latlon 63x128", latlon(63, 128), 2, 0);
+    bad += run_case("polering 49", polering(49), 2, 0);
+    for (const auto& hm : {std::make_pair(2000, 0.5f), std::make_pair(20000, 0.2f)}) {
+        const Points p = hemisphere(hm.first, hm.second);
+        const std::string name = "hemisphere " + std::to_string(hm.first);
+        bad += run_case(name.c_str(), p, 2, 0);
+        if (std::string(wo_last_error()).find("hemisphere") == std::string::npos) { std::fprintf(stderr, "%s: refused, but not for the centre\n", name.c_str()); ++bad; }
+    }
     bad += run_case("three points", fib(2, 0.75, 1), 1, 0);
     // refusals before any read
     std::vector<int32_t> i32(64);
