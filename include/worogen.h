@@ -546,6 +546,32 @@ enum {
 int wo_map_raster_centered(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width,
                            double centerLon, int32_t* regionMapOut, int64_t counts[2]);
 int wo_map_color_layer(wo_planet* p, int32_t layer, const float* values, const float* r_elevation, uint8_t* rgbaOut, int64_t outBytes);
+/* The cube map of the planet: six square faces by gnomonic projection (ours: the reference exports none; csrc/cube.hip, the bodies
+ *   and the whole contract are in csrc/cube_ops.h).  Great-circle arcs project to straight lines, so the faces are exactly the globe
+ *   mesh of wo_globe_mesh seen from its centre; there is no seam, no wrap and no pole, and on a closed mesh every pixel is covered.
+ *   Faces in the OpenGL order +X, -X, +Y, -Y, +Z, -Z (px nx py ny pz nz).  For a point (x, y, z) and a face with major-axis
+ *   component ma (positive in front of the face) the face coordinates are a = sc / ma, b = tc / ma, in double on the f32 inputs,
+ *   stored as f32:
+ *       face   ma   sc   tc          face   ma   sc   tc          face   ma   sc   tc
+ *       +X     +x   -z   -y          +Y     +y   +x   +z          +Z     +z   +x   -y
+ *       -X     -x   +z   -y          -Y     -y   +x   -z          -Z     -z   -x   -y
+ *   North is +Y and longitude 0 is +Z, so pz is centred on the map's centre and row 0 of the four side faces is north.  The centre
+ *   of pixel (i, j) of a face is a = -1 + 2 (i + 0.5) / faceSize, b = -1 + 2 (j + 0.5) / faceSize.  Vertices, coverage rule (the lowest
+ *   side index whose triangle contains the centre, edges included, both windings) and region are wo_map_raster's.
+ *   A side is drawn on a face only if all three of its vertices have ma > 0 there; it is neither clipped nor split.  A face's
+ *   corner lies 54.74 degrees from its centre, so this loses pixels only on a mesh with a side that spans more than
+ *   90 - 54.74 = 35.26 degrees; the call does not check it.
+ *   wo_map_raster_cube leaves the six faces, stacked vertically in face order, in the planet's map block as ONE region map of
+ *   faceSize x 6 faceSize (face f, row j, column i at (f * faceSize + j) * faceSize + i): wo_map_color, wo_map_color_layer (outBytes:
+ *   6 * faceSize * faceSize * 4), wo_map_download, wo_map_free and the tints of wo_highlight_set serve it as they serve a map, and
+ *   the next raster of either kind replaces it.  faceSize must be from 1 to 16384 (odd sizes are allowed); the other checks and
+ *   their messages are wo_map_raster's: otherwise status 1 and the planet keeps what it had.  regionMapOut (may be NULL): 6 *
+ *   faceSize * faceSize int32; counts (may be NULL): covered and uncovered pixels.
+ *   wo_map_dims gives the width and height of the planet's resident region map (faceSize, 6 faceSize after wo_map_raster_cube), or
+ *   0, 0 when it has none.  It does not touch the device. */
+int wo_map_raster_cube(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t faceSize,
+                       int32_t* regionMapOut, int64_t counts[2]);
+int wo_map_dims(wo_planet* p, int32_t dims[2]);
 
 /* ------------------------------------------------ globe mesh (js/planet-mesh.js) -------------- */
 /* buildMesh, updateMeshColors, updateSuperPlateBorders (globe form)                  js/planet-mesh.js:620-836, :840-957, :533-576

@@ -20,9 +20,10 @@
 // k_map_pixels [1] (region map -> RGBA8, four pixels per thread).
 // wo_map_raster_centered is the same raster around a centre meridian (the map view's, map_layer_ops.h): the two table kernels take
 // centerLon (k_map_region_lonlat_centered, k_map_center_lonlat_centered), every other launch is wo_map_raster's.
-// Memory (device_mem.h): the region map lives in a block with an arena of its own on the planet (int32 per pixel; a raster at
-// another width replaces it, wo_map_free and wo_planet_destroy drop it); triangles, half-edges, both longitude / latitude tables,
-// the side map, the list and the colour tables are temporaries of the call, in an arena on its stack.
+// Memory (device_mem.h): the region map lives in a block with an arena of its own on the planet (map_block.h; int32 per pixel; a
+// raster at another width or height, wo_map_raster_cube's included, replaces it, wo_map_free and wo_planet_destroy drop it);
+// triangles, half-edges, both longitude / latitude tables, the side map, the list and the colour tables are temporaries of the call,
+// in an arena on its stack.
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -31,6 +32,7 @@
 #include "../../include/worogen.h"
 #include "block_ops.h"
 #include "device.h"
+#include "map_block.h"
 #include "map_layer_ops.h"
 #include "map_ops.h"
 #include "stage_block.h"
@@ -39,15 +41,6 @@
 static_assert(wo::map::LAYER_COUNT == WO_MAP_LAYER_COUNT && wo::map::LAYER_WINDSPEED_WINTER == WO_MAP_LAYER_WINDSPEED_WINTER, "the layers of map_layer_ops.h are those of worogen.h");
 
 namespace M = wo::map;
-
-// the map block of a planet
-struct wo_map_block {
-    wo::DeviceArena mem;
-    int32_t* region = nullptr;                                // W x H region ids, row 0 north; -1: nothing covers the pixel
-    int32_t W = 0, H = 0;
-    double centerLon = 0.0;                                   // the centre meridian of the raster (wo_map_raster: 0)
-    bool valid = false;
-};
 
 namespace wo {
 
@@ -163,6 +156,18 @@ __global__ __launch_bounds__(WO_BLOCK) void k_map_pixels(const int32_t* __restri
 
 void map_free(wo_planet* p) { delete p->map; p->map = nullptr; }
 
+wo_map_block* map_block_for(wo_planet* p, int32_t W, int32_t H) {
+    if (!p->map || p->map->W != W || p->map->H != H) {        // a cube block of face size 64 is no 64 x 32 map
+        map_free(p);
+        std::unique_ptr<wo_map_block> block(new wo_map_block());
+        block->region = block->mem.dev<int32_t>((size_t)W * (size_t)H);
+        block->W = W; block->H = H;
+        p->map = block.release();
+    }
+    p->map->valid = false;
+    return p->map;
+}
+
 static bool map_width_ok(int32_t width) { return width >= 2 && width <= 32768 && (width & 1) == 0; }
 
 }  // namespace wo
@@ -181,15 +186,7 @@ static int map_raster(wo_planet* p, const char* fn, int32_t numSides, const int3
         const int32_t W = width, H = width / 2, N = p->N, numTriangles = numSides / 3;
         const int64_t pixels = (int64_t)W * H;
         hipStream_t s = p->ctx->stream;
-        if (!p->map || p->map->W != W) {                     // the old map goes first; the planet gets the new block once it is complete
-            map_free(p);
-            std::unique_ptr<wo_map_block> block(new wo_map_block());
-            block->region = block->mem.dev<int32_t>((size_t)pixels);
-            block->W = W; block->H = H;
-            p->map = block.release();
-        }
-        auto* B = p->map;
-        B->valid = false;
+        auto* B = map_block_for(p, W, H);
         B->centerLon = centered ? centerLon : 0.0;
         DeviceArena T;                                        // the temporaries of this call
         const int32_t* d_tri = up(T, triangles, (size_t)numSides, s);
@@ -295,6 +292,15 @@ int wo_map_download(wo_planet* p, int32_t* out, int64_t outBytes) {
         WO_HIP(hipStreamSynchronize(p->ctx->stream));
         return 0;
     WO_CATCH("wo_map_download")
+}
+
+int wo_map_dims(wo_planet* p, int32_t dims[2]) {
+    if (!check_planet(p, "wo_map_dims")) return 1;
+    if (!dims) { set_error("wo_map_dims: null pointer"); return 1; }
+    auto* B = p->map;
+    dims[0] = (B && B->valid) ? B->W : 0;
+    dims[1] = (B && B->valid) ? B->H : 0;
+    return 0;
 }
 
 int wo_map_free(wo_planet* p) {

@@ -7,6 +7,9 @@
 // Beyond the export button, the reference's map view (buildMapMesh, :200-382) draws around a centre meridian and shows the layers of
 // its debugLayer switch: `centerLon` (radians, within [-pi, pi]) and `layers` offer both.  A climate layer reads the block its stage
 // left on the planet (`no wind result` and so on without one); any other array is coloured by debugValueToColor over its own range.
+// exportCubeMap / exportCubeMapBatch give the cube map instead (ours; csrc/cube.hip, the contract is in csrc/cube_ops.h): six square faces
+// by gnomonic projection, exactly the globe mesh seen from its centre, in the OpenGL order of CUBE_FACES.  The six faces lie stacked in
+// one faceSize x 6 faceSize image on the device; each face handed out is a view of that one buffer.
 import zlib from 'zlib';
 import addon, { planetFor } from './native.js';
 
@@ -44,6 +47,36 @@ export function exportFilename(type, seed) {
     }
 }
 
+// the cube map's faces in the order +X, -X, +Y, -Y, +Z, -Z (the OpenGL cube-map table; north is +Y, longitude 0 is +Z)
+export const CUBE_FACES = ['px', 'nx', 'py', 'ny', 'pz', 'nz'];
+export const CUBE_MAX_FACE_SIZE = 16384;
+
+// ours: exportFilename's stems (a name that is no type's: the layer's), then the face
+export function cubeFilename(type, face, seed) {
+    if (CUBE_FACES.indexOf(face) < 0) throw new RangeError(`exportCubeMap: unknown cube face '${face}' (one of ${CUBE_FACES.join(', ')})`);
+    const name = MAP_TYPES.indexOf(type) >= 0 ? exportFilename(type, seed) : layerFilename(type, seed);
+    return `${name.slice(0, -4)}-${face}.png`;
+}
+
+// the direction of the centre of pixel (column i, row j) of a face (csrc/cube_ops.h: cube_direction); not normalised
+export function cubeDirection(face, i, j, faceSize) {
+    const f = typeof face === 'number' ? face : CUBE_FACES.indexOf(face);
+    if (!(Number.isInteger(f) && f >= 0 && f < 6)) throw new RangeError(`exportCubeMap: unknown cube face '${face}' (one of ${CUBE_FACES.join(', ')})`);
+    const a = -1 + 2 * (i + 0.5) / faceSize, b = -1 + 2 * (j + 0.5) / faceSize;
+    return [[1, -b, -a], [-1, -b, a], [a, 1, b], [a, -1, -b], [a, -b, 1], [-a, -b, -1]][f];
+}
+
+// the six faces of a stacked faceSize x 6 faceSize image: views of its buffer, nothing is copied
+export function cubeFaces(rgba, faceSize) {
+    const n = faceSize * faceSize * 4;
+    if (rgba.length !== 6 * n) throw new RangeError('exportCubeMap: the image does not hold six faces of faceSize x faceSize');
+    return CUBE_FACES.map((face, f) => ({ face, rgba: rgba.subarray(f * n, (f + 1) * n) }));
+}
+
+function checkFaceSize(faceSize) {
+    if (!(Number.isInteger(faceSize) && faceSize >= 1 && faceSize <= CUBE_MAX_FACE_SIZE)) throw new RangeError('exportCubeMap: faceSize must be an integer from 1 to 16384');
+}
+
 function checkMesh(mesh, width) {
     if (!mesh || !(mesh.triangles instanceof Int32Array) || !(mesh.halfedges instanceof Int32Array)) throw new TypeError('exportMap: mesh.triangles and mesh.halfedges must be Int32Arrays');
     if (!(Number.isInteger(width) && width >= 2 && width <= 32768 && width % 2 === 0)) throw new RangeError('exportMap: width must be an even integer from 2 to 32768');
@@ -76,6 +109,17 @@ export function exportMapsOnPlanet(planet, triangles, halfedges, r_elevation, ty
     return { width: r.width, height: r.height, covered: r.covered, uncovered: r.uncovered, maps };
 }
 
+// the cube map's counterpart: one raster of the six faces, one colour pass per type and per layer; rgba is the stacked image, faces its views
+export function exportCubeMapsOnPlanet(planet, triangles, halfedges, r_elevation, types, faceSize, opts) {
+    checkFaceSize(faceSize);
+    const ids = types.map(mapTypeId), layers = checkedLayers(opts && opts.layers);
+    const r = addon.mapRasterCube(planet, triangles, halfedges, faceSize, false);
+    const maps = ids.map((id, k) => ({ type: types[k], rgba: addon.mapColor(planet, id, r_elevation || null) }));
+    for (const l of layers) maps.push({ type: l.name, rgba: addon.mapColorLayer(planet, l.id, l.values, r_elevation || null) });
+    for (const m of maps) m.faces = cubeFaces(m.rgba, faceSize);
+    return { faceSize: r.faceSize, covered: r.covered, uncovered: r.uncovered, maps };
+}
+
 function checkElevation(mesh, r_elevation) {
     if (!(r_elevation instanceof Float32Array) || r_elevation.length !== mesh.numRegions) throw new RangeError(`exportMap: r_elevation must be a Float32Array of ${mesh.numRegions} entries`);
 }
@@ -93,6 +137,23 @@ export function exportMapBatch(mesh, r_xyz, r_elevation, types, width, opts) {
 export function exportMap(mesh, r_xyz, r_elevation, type, width, opts) {
     const res = exportMapBatch(mesh, r_xyz, r_elevation, [type], width, opts);
     const out = { width: res.width, height: res.height, rgba: res.maps[0].rgba };
+    if (opts && opts.layers && Array.from(opts.layers).length) out.maps = res.maps;
+    return out;
+}
+
+// exportCubeMapBatch(mesh, r_xyz, r_elevation, types, faceSize, { layers }) -> { faceSize, maps: [{ type, rgba, faces: [{ face, rgba }] }] }
+export function exportCubeMapBatch(mesh, r_xyz, r_elevation, types, faceSize, opts) {
+    if (!mesh || !(mesh.triangles instanceof Int32Array) || !(mesh.halfedges instanceof Int32Array)) throw new TypeError('exportCubeMap: mesh.triangles and mesh.halfedges must be Int32Arrays');
+    checkFaceSize(faceSize);
+    checkElevation(mesh, r_elevation);
+    const res = exportCubeMapsOnPlanet(planetFor(mesh, r_xyz), mesh.triangles, mesh.halfedges, r_elevation, Array.from(types), faceSize, opts);
+    return { faceSize: res.faceSize, maps: res.maps };
+}
+
+// exportCubeMap(mesh, r_xyz, r_elevation, type, faceSize, { layers }) -> { faceSize, rgba, faces } (with layers: and maps, as exportCubeMapBatch)
+export function exportCubeMap(mesh, r_xyz, r_elevation, type, faceSize, opts) {
+    const res = exportCubeMapBatch(mesh, r_xyz, r_elevation, [type], faceSize, opts);
+    const out = { faceSize: res.faceSize, rgba: res.maps[0].rgba, faces: res.maps[0].faces };
     if (opts && opts.layers && Array.from(opts.layers).length) out.maps = res.maps;
     return out;
 }

@@ -76,6 +76,18 @@
 //                  `centerLon` (radians, within [-pi, pi]) draws the map around that meridian.  Progress then counts types + layers.
 //                  -> { type: 'exportDone', width, height, maps: [{ type, filename, rgba, png? }],
 //                       _exportTiming: { raster, color, encode, workerTotal } }, the buffers transferred
+//   cmd 'exportCubeMap' { type | types, faceSize, png?, layers?, layout? }   (ours: the reference exports no cube map)
+//                  the cube map of the planet's current elevation and Koppen block: six square faces of faceSize x faceSize by
+//                  gnomonic projection, exactly the globe mesh seen from its centre, in the OpenGL order px nx py ny pz nz (north
+//                  is +Y, longitude 0 is +Z: pz is centred on the map's centre, row 0 of the four side faces is north; the face
+//                  table is in include/worogen.h).  One raster on the device (csrc/cube.hip), one colour pass per type and layer;
+//                  types, layers, their needs and their checks are exportMap's, the messages name exportCubeMap.  faceSize: an
+//                  integer from 1 to 16384.  `layout`: 'faces' (the default) gives six images per map, views of one buffer,
+//                  filenames orogen-<stem>-<seed>-<face>.png; 'column' gives the one faceSize x 6 faceSize image with the faces
+//                  stacked in that order, as a single entry { face: 'column', filename: orogen-<stem>-<seed>-column.png }.  A side
+//                  that spans more than 35.26 degrees may be missing from a face (no generated mesh has one).  Progress as exportMap.
+//                  -> { type: 'exportCubeDone', faceSize, maps: [{ type, faces: [{ face, filename, rgba, png? }] }],
+//                       _exportTiming: { raster, color, encode, workerTotal } }, the buffers transferred
 //   cmd 'exportGlobe' { view?, layer?, plates?, wireframe?, superPlateBorders?, glb?, windArrows?, oceanCurrentArrows?, itcz?, grid? }   (js/planet-mesh.js:620-836, :533-576)
 //                  the globe mesh three.js would draw, of the planet's current elevation: one displaced triangle per side, nine floats
 //                  of positions and nine of colours each, built on the device (js/globe-export.js).  `view`: color (the default),
@@ -128,7 +140,7 @@ import { OCEAN_KEYS, PRECIP_KEYS, TEMP_KEYS, downloadAll } from './climate-block
 import { denseTable, plateDensities, LAYERS } from './plate-table.js';
 import { generateCoarsePlates } from './coarse-plates.js';
 import { SimplexNoise } from './simplex-noise.js';
-import { MAP_TYPES, MAP_LAYERS, exportFilename, layerFilename, encodePng, rasterOnPlanet } from './map-export.js';
+import { MAP_TYPES, MAP_LAYERS, CUBE_MAX_FACE_SIZE, exportFilename, layerFilename, cubeFilename, cubeFaces, encodePng, rasterOnPlanet } from './map-export.js';
 import { GLOBE_PLATES, GLOBE_TYPE_VIEWS, computePlateColors, exportGlobeOnPlanet, globeFilename } from './globe-export.js';
 import { findNearestRegions, hitDirectionsGlobe, hitDirectionsMap, setHighlight, clearHighlight, PICK_MAX_QUERIES } from './edit-mode.js';
 import { SEASONS, windArrowsOnPlanet, oceanCurrentArrowsOnPlanet, itczLine, grids } from './overlay-export.js';
@@ -537,6 +549,22 @@ function handleComputeClimate(data) {
     }
 }
 
+// the types and layers an exportMap or exportCubeMap request asks for, checked
+function requestedMaps(cmd, data) {
+    const types = data.types !== undefined && data.types !== null ? Array.from(data.types) : [data.type];
+    for (const t of types) if (MAP_TYPES.indexOf(t) < 0) throw new RangeError(`${cmd}: unknown map type '${t}' (one of ${MAP_TYPES.join(', ')})`);
+    if (types.length === 0) throw new RangeError(`${cmd}: no map type given`);
+    // a layer is a climate layer of the map view, read from the planet's resident block, or a key of the retained debugLayers
+    const generic = W.debugLayers || {};
+    const layers = (data.layers !== undefined && data.layers !== null ? Array.from(data.layers) : []).map((name) => {
+        const id = MAP_LAYERS.indexOf(name);
+        if (id > 0) return { name, id, values: null };
+        if (name !== 'debug' && generic[name] instanceof Float32Array) return { name, id: 0, values: generic[name] };
+        throw new RangeError(`${cmd}: unknown map layer '${name}' (one of ${MAP_LAYERS.slice(1).concat(Object.keys(generic)).join(', ')})`);
+    });
+    return { types, layers };
+}
+
 // js/planet-mesh.js:1965-2180 without the page: one raster, one colour pass per type, on W.planet's current elevation and Koppen block
 function handleExportMap(data) {
     if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for exportMap' }); return; }
@@ -547,17 +575,7 @@ function handleExportMap(data) {
     }
     try {
         const tTotal0 = performance.now();
-        const types = data.types !== undefined && data.types !== null ? Array.from(data.types) : [data.type];
-        for (const t of types) if (MAP_TYPES.indexOf(t) < 0) throw new RangeError(`exportMap: unknown map type '${t}' (one of ${MAP_TYPES.join(', ')})`);
-        if (types.length === 0) throw new RangeError('exportMap: no map type given');
-        // a layer is a climate layer of the map view, read from the planet's resident block, or a key of the retained debugLayers
-        const generic = W.debugLayers || {};
-        const layers = (data.layers !== undefined && data.layers !== null ? Array.from(data.layers) : []).map((name) => {
-            const id = MAP_LAYERS.indexOf(name);
-            if (id > 0) return { name, id, values: null };
-            if (name !== 'debug' && generic[name] instanceof Float32Array) return { name, id: 0, values: generic[name] };
-            throw new RangeError(`exportMap: unknown map layer '${name}' (one of ${MAP_LAYERS.slice(1).concat(Object.keys(generic)).join(', ')})`);
-        });
+        const { types, layers } = requestedMaps('exportMap', data);
         const width = data.width;
         progress(0, 'Rendering...');
         let t0 = performance.now();
@@ -584,6 +602,57 @@ function handleExportMap(data) {
         const transfer = [];
         for (const m of maps) { transfer.push(m.rgba.buffer); if (m.png) transfer.push(m.png.buffer); }
         parentPort.postMessage({ type: 'exportDone', width: r.width, height: r.height, maps,
+                                 _exportTiming: { raster: tRaster, color: tColor, encode: tEncode, workerTotal: performance.now() - tTotal0 } }, transfer);
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
+// ours: the cube map of W.planet's current elevation and Koppen block: one raster of the six faces, one colour pass per type and layer
+function handleExportCubeMap(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for exportCubeMap' }); return; }
+    const missing = ['triangles', 'halfedges'].filter((k) => !(W[k] instanceof Int32Array));
+    if (missing.length) {
+        parentPort.postMessage({ type: 'error', message: `exportCubeMap: the retained state has no mesh.${missing.join(' and mesh.')} (pass them to retain, or run importHeightmap)` });
+        return;
+    }
+    try {
+        const tTotal0 = performance.now();
+        const { types, layers } = requestedMaps('exportCubeMap', data);
+        const S = data.faceSize, layout = data.layout === undefined || data.layout === null ? 'faces' : data.layout;
+        if (!(Number.isInteger(S) && S >= 1 && S <= CUBE_MAX_FACE_SIZE)) throw new RangeError('exportCubeMap: faceSize must be an integer from 1 to 16384');
+        if (layout !== 'faces' && layout !== 'column') throw new RangeError(`exportCubeMap: unknown layout '${layout}' (one of faces, column)`);
+        progress(0, 'Rendering...');
+        let t0 = performance.now();
+        addon.mapRasterCube(W.planet, W.triangles, W.halfedges, S, false);
+        const tRaster = performance.now() - t0;
+        t0 = performance.now();
+        const images = [], total = types.length + layers.length;             // one S x 6S image per map; the faces are views of it
+        types.forEach((type, k) => {
+            images.push({ type, rgba: addon.mapColor(W.planet, MAP_TYPES.indexOf(type), null) });
+            progress(80 * (k + 1) / total, 'Rendering...');
+        });
+        layers.forEach((l, k) => {
+            images.push({ type: l.name, rgba: addon.mapColorLayer(W.planet, l.id, l.values, null) });
+            progress(80 * (types.length + k + 1) / total, 'Rendering...');
+        });
+        const tColor = performance.now() - t0;
+        const stem = (type) => cubeFilename(type, 'px', W.seed).slice(0, -'-px.png'.length);
+        const maps = images.map((m) => ({
+            type: m.type,
+            faces: layout === 'column' ? [{ face: 'column', filename: `${stem(m.type)}-column.png`, rgba: m.rgba }]
+                : cubeFaces(m.rgba, S).map((f) => ({ face: f.face, filename: cubeFilename(m.type, f.face, W.seed), rgba: f.rgba }))
+        }));
+        let tEncode = 0;
+        if (data.png) {
+            progress(85, 'Encoding PNG...');
+            t0 = performance.now();
+            for (const m of maps) for (const f of m.faces) f.png = encodePng(f.rgba, S, layout === 'column' ? 6 * S : S);
+            tEncode = performance.now() - t0;
+        }
+        const transfer = images.map((m) => m.rgba.buffer);                     // each image's one buffer; the six views travel with it
+        for (const m of maps) for (const f of m.faces) if (f.png) transfer.push(f.png.buffer);
+        parentPort.postMessage({ type: 'exportCubeDone', faceSize: S, maps,
                                  _exportTiming: { raster: tRaster, color: tColor, encode: tEncode, workerTotal: performance.now() - tTotal0 } }, transfer);
     } catch (err) {
         parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
@@ -734,6 +803,7 @@ parentPort.on('message', (data) => {
         case 'computeClimate': handleComputeClimate(data); break;
         case 'editRecompute': handleEditRecompute(data); break;
         case 'exportMap': handleExportMap(data); break;
+        case 'exportCubeMap': handleExportCubeMap(data); break;
         case 'exportGlobe': handleExportGlobe(data); break;
         case 'exportOverlays': handleExportOverlays(data); break;
         case 'generate': handleGenerate(data); break;

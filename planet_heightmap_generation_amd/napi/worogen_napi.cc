@@ -849,7 +849,8 @@ napi_value TriangleCenters(napi_env env, napi_callback_info info) {            /
     return out;
 }
 
-// ---- map export (include/worogen.h: wo_map_raster / wo_map_color / wo_map_free / wo_map_raster_centered / wo_map_color_layer) ----
+// ---- map export (include/worogen.h: wo_map_raster / wo_map_color / wo_map_free / wo_map_raster_centered / wo_map_color_layer /
+// wo_map_raster_cube / wo_map_dims) ----
 // mapRaster(planet, triangles, halfedges, width, download) -> { width, height, covered, uncovered, regionMap: Int32Array | null }
 napi_value MapRaster(napi_env env, napi_callback_info info) {
     Args a(env, info);
@@ -897,35 +898,84 @@ napi_value MapRasterCentered(napi_env env, napi_callback_info info) {
     set_prop(env, o, "regionMap", map);
     return o;
 }
-// mapColor(planet, type 0..5, r_elevation | null, width) -> Uint8ClampedArray(width * width / 2 * 4): the planet's region map coloured
+// The size of the RGBA of the planet's region map: of a width x width / 2 map when argument i gives a width, else of the resident map
+// (wo_map_dims: the six stacked faces after mapRasterCube; the library says what is missing when there is none)
+bool map_bytes(Args& a, size_t i, wo_planet* p, const char* fn, size_t* bytes) {
+    if (a.has(i)) {
+        const double w = a.num(i);
+        if (!(w >= 2 && w <= 32768 && w == (double)(int64_t)w && ((int64_t)w & 1) == 0)) { napi_throw_range_error(a.env, nullptr, (std::string(fn) + ": width must be an even integer from 2 to 32768").c_str()); return false; }
+        *bytes = (size_t)w * (size_t)(w / 2) * 4;
+        return true;
+    }
+    int32_t dims[2] = {0, 0};
+    if (wo_map_dims(p, dims)) { throw_wo(a.env, fn); return false; }
+    *bytes = (size_t)dims[0] * (size_t)dims[1] * 4;
+    return true;
+}
+// mapColor(planet, type 0..5, r_elevation | null, width?) -> Uint8ClampedArray(width * width / 2 * 4): the planet's region map coloured;
+// without a width the result has the size of the resident map
 napi_value MapColor(napi_env env, napi_callback_info info) {
     Args a(env, info); wo_planet* p = planet_at(a, 0);
     if (!planet_ok(env, p)) return nullptr;
     float* e = (float*)opt_regions(a, 2, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
-    const double t = a.num(1), w = a.num(3);
+    const double t = a.num(1);
     if (!(t >= 0 && t <= 5 && t == (double)(int64_t)t)) { napi_throw_range_error(env, nullptr, "mapColor: type must be an integer from 0 to 5"); return nullptr; }
-    if (!(w >= 2 && w <= 32768 && w == (double)(int64_t)w && ((int64_t)w & 1) == 0)) { napi_throw_range_error(env, nullptr, "mapColor: width must be an even integer from 2 to 32768"); return nullptr; }
-    const size_t bytes = (size_t)w * (size_t)(w / 2) * 4;
+    size_t bytes;
+    if (!map_bytes(a, 3, p, "mapColor", &bytes)) return nullptr;
     void* d; napi_value out = make_ta(env, napi_uint8_clamped_array, bytes, 1, &d);
     if (!out) return nullptr;
     if (wo_map_color(p, (int32_t)t, e, (uint8_t*)d, (int64_t)bytes)) return throw_wo(env, "mapColor");
     return out;
 }
-// mapColorLayer(planet, layer 0..13, values | null, r_elevation | null, width) -> Uint8ClampedArray(width * width / 2 * 4): the planet's
+// mapColorLayer(planet, layer 0..13, values | null, r_elevation | null, width?) -> Uint8ClampedArray(width * width / 2 * 4): the planet's
 // region map coloured as a layer of the map view (WO_MAP_LAYER_*); values null: the layer's field of the planet's resident block
 napi_value MapColorLayer(napi_env env, napi_callback_info info) {
     Args a(env, info); wo_planet* p = planet_at(a, 0);
     if (!planet_ok(env, p)) return nullptr;
     float* v = (float*)opt_regions(a, 2, napi_float32_array, p, "values", false); if (!a.ok) return nullptr;
     float* e = (float*)opt_regions(a, 3, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
-    const double l = a.num(1), w = a.num(4);
+    const double l = a.num(1);
     if (!(l >= 0 && l < WO_MAP_LAYER_COUNT && l == (double)(int64_t)l)) { napi_throw_range_error(env, nullptr, "mapColorLayer: layer must be an integer from 0 to 13"); return nullptr; }
-    if (!(w >= 2 && w <= 32768 && w == (double)(int64_t)w && ((int64_t)w & 1) == 0)) { napi_throw_range_error(env, nullptr, "mapColorLayer: width must be an even integer from 2 to 32768"); return nullptr; }
-    const size_t bytes = (size_t)w * (size_t)(w / 2) * 4;
+    size_t bytes;
+    if (!map_bytes(a, 4, p, "mapColorLayer", &bytes)) return nullptr;
     void* d; napi_value out = make_ta(env, napi_uint8_clamped_array, bytes, 1, &d);
     if (!out) return nullptr;
     if (wo_map_color_layer(p, (int32_t)l, v, e, (uint8_t*)d, (int64_t)bytes)) return throw_wo(env, "mapColorLayer");
     return out;
+}
+// mapRasterCube(planet, triangles, halfedges, faceSize, download) -> { faceSize, width, height, covered, uncovered, regionMap: Int32Array | null }:
+// the six faces stacked, width = faceSize, height = 6 faceSize (include/worogen.h: wo_map_raster_cube)
+napi_value MapRasterCube(napi_env env, napi_callback_info info) {
+    Args a(env, info);
+    size_t nt, nh;
+    int32_t* tri = (int32_t*)a.ta(1, napi_int32_array, &nt); if (!a.ok) return nullptr;
+    int32_t* he = (int32_t*)a.ta(2, napi_int32_array, &nh); if (!a.ok) return nullptr;
+    if (nt != nh || nt == 0 || nt >= ((size_t)1 << 30)) { napi_throw_range_error(env, nullptr, "mapRasterCube: triangles and halfedges must have the same length, numSides"); return nullptr; }
+    const double w = a.num(3);
+    if (!(w >= 1 && w <= 16384 && w == (double)(int64_t)w)) { napi_throw_range_error(env, nullptr, "mapRasterCube: faceSize must be an integer from 1 to 16384"); return nullptr; }
+    wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    const int32_t S = (int32_t)w;
+    bool download = false; if (a.argc > 4) napi_get_value_bool(env, a.argv[4], &download);
+    void* d = nullptr; napi_value map = nullptr;
+    if (download) { map = make_ta(env, napi_int32_array, 6 * (size_t)S * (size_t)S, 4, &d); if (!map) return nullptr; }
+    else napi_get_null(env, &map);
+    int64_t counts[2] = {0, 0};
+    if (wo_map_raster_cube(p, (int32_t)nt, tri, he, S, (int32_t*)d, counts)) return throw_wo(env, "mapRasterCube");
+    napi_value o; napi_create_object(env, &o);
+    set_nums(env, o, {{"faceSize", (double)S}, {"width", (double)S}, {"height", 6.0 * (double)S}, {"covered", (double)counts[0]}, {"uncovered", (double)counts[1]}});
+    set_prop(env, o, "regionMap", map);
+    return o;
+}
+// mapDims(planet) -> { width, height } of the planet's resident region map, 0 and 0 without one
+napi_value MapDims(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    int32_t dims[2] = {0, 0};
+    if (wo_map_dims(p, dims)) return throw_wo(env, "mapDims");
+    napi_value o; napi_create_object(env, &o);
+    set_nums(env, o, {{"width", (double)dims[0]}, {"height", (double)dims[1]}});
+    return o;
 }
 napi_value MapFree(napi_env env, napi_callback_info info) {                    // (planet)
     Args a(env, info); wo_planet* p = planet_at(a, 0);
@@ -1208,6 +1258,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"precipUpload", PrecipUpload}, {"computeTemperature", ComputeTemperature}, {"temperatureDownload", TemperatureDownload},
         {"temperatureUpload", TemperatureUpload}, {"classifyKoppen", ClassifyKoppen},
         {"mapRaster", MapRaster}, {"mapColor", MapColor}, {"mapFree", MapFree}, {"mapRasterCentered", MapRasterCentered}, {"mapColorLayer", MapColorLayer},
+        {"mapRasterCube", MapRasterCube}, {"mapDims", MapDims},
         {"globeMesh", GlobeMesh}, {"globeMeshPlates", GlobeMeshPlates}, {"globeLines", GlobeLines},
         {"overlayBins", OverlayBins}, {"overlayArrows", OverlayArrows},
         {"pickRegions", PickRegions}, {"pickDirectionsGlobe", PickDirectionsGlobe}, {"pickDirectionsMap", PickDirectionsMap},
