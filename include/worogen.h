@@ -572,6 +572,40 @@ int wo_map_color_layer(wo_planet* p, int32_t layer, const float* values, const f
 int wo_map_raster_cube(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t faceSize,
                        int32_t* regionMapOut, int64_t counts[2]);
 int wo_map_dims(wo_planet* p, int32_t dims[2]);
+/* Relief: a smooth height per pixel, its 16-bit encoding and the normals of the displaced surface, on the equirectangular map or the
+ *   cube map (ours: the reference exports neither; csrc/relief.hip, the bodies and the whole contract are in csrc/relief_ops.h).
+ *   The surface is the globe mesh of wo_globe_mesh: one flat triangle per side between the centres of its two triangles (elevation:
+ *   the mean of the triangle's three regions, stored f32) and its region.  The height of a pixel is the elevation of the side that
+ *   covers it, interpolated at the pixel centre from the edge functions of the raster: affine in the map plane on the map,
+ *   perspective-correct on a cube face (the elevation where the ray through the pixel centre meets the flat 3-D triangle).  Pixels
+ *   nothing covers hold the quiet NaN 0x7FC00000; a NaN elevation propagates.
+ *   wo_relief_raster is wo_map_raster_centered, and wo_relief_raster_cube is wo_map_raster_cube, with one more pass: region map,
+ *   counts, checks and messages (under the relief call's name) are theirs, and the region map serves wo_map_color, wo_map_color_layer,
+ *   wo_map_download, wo_map_dims and the tints as before.  The pass leaves a height map of the same shape (f32 per pixel) in the map
+ *   block.  r_elevation: numRegions floats, NULL means the planet's resident field.  heightOut (may be NULL) receives the height map.
+ *   Any later raster of either kind through any entry point ends the relief; wo_map_free and wo_planet_destroy drop it.  Without a
+ *   relief the three calls below answer status 1, "no relief raster".
+ *   wo_relief_download copies the height map (outBytes: width * height * 4).
+ *   wo_relief_height16 encodes it in native-endian uint16 (outBytes: width * height * 2): q = floor(shade * 65535 + 0.5) of the
+ *   reference's heightmap shade (WO_RELIEF_HEIGHT: (km + 5) / 11 clamped to [0, 1]) or land-heightmap shade (WO_RELIEF_LAND_HEIGHT:
+ *   km / 6, 0 at and below sea level); NaN gives 0.  Linear: no gamma table.
+ *   wo_relief_normals gives RGBA8 normals (outBytes: width * height * 4; alpha 255; byte = floor((c * 0.5 + 0.5) * 255 + 0.5)) of the
+ *   surface at radius 1 + strength * (h > 0 ? 0.04 h : 0.012 h) (strength 1: the globe's displacement), by central differences
+ *   between the points of the four neighbouring pixels (map: columns wrap, rows stop at the poles; cube: across the edges of the
+ *   faces), less the lean that the same stencil has on a perfect sphere, so that a constant field gives exactly (128, 128, 255).
+ *   WO_RELIEF_NORMAL_TANGENT: components along (image right, image up, outward): on the map (east, north, outward).
+ *   WO_RELIEF_NORMAL_OBJECT: x, y, z of the planet's frame.  WO_RELIEF_FLAT_OCEAN in flags: elevations <= 0 count as 0.  strength
+ *   must be finite and >= 0.  A NaN neighbour takes the pixel's own height; a NaN pixel gets the flat normal. */
+enum { WO_RELIEF_HEIGHT = 0, WO_RELIEF_LAND_HEIGHT = 1 };
+enum { WO_RELIEF_NORMAL_TANGENT = 0, WO_RELIEF_NORMAL_OBJECT = 1 };
+enum { WO_RELIEF_FLAT_OCEAN = 1 };
+int wo_relief_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, double centerLon,
+                     const float* r_elevation, float* heightOut, int64_t counts[2]);
+int wo_relief_raster_cube(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t faceSize,
+                          const float* r_elevation, float* heightOut, int64_t counts[2]);
+int wo_relief_download(wo_planet* p, float* out, int64_t outBytes);
+int wo_relief_height16(wo_planet* p, int32_t kind, uint16_t* out, int64_t outBytes);
+int wo_relief_normals(wo_planet* p, int32_t space, double strength, int32_t flags, uint8_t* rgbaOut, int64_t outBytes);
 
 /* ------------------------------------------------ globe mesh (js/planet-mesh.js) -------------- */
 /* buildMesh, updateMeshColors, updateSuperPlateBorders (globe form)                  js/planet-mesh.js:620-836, :840-957, :533-576

@@ -97,6 +97,11 @@ SIGNATURES = {
     "wo_map_free": (C.c_int, [_p]),
     "wo_map_raster_cube": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _p, _p]),
     "wo_map_dims": (C.c_int, [_p, _p]),
+    "wo_relief_raster": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _c_f64, _p, _p, _p]),
+    "wo_relief_raster_cube": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _p, _p, _p]),
+    "wo_relief_download": (C.c_int, [_p, _p, _c_i64]),
+    "wo_relief_height16": (C.c_int, [_p, _c_i32, _p, _c_i64]),
+    "wo_relief_normals": (C.c_int, [_p, _c_i32, _c_f64, _c_i32, _p, _c_i64]),
     "wo_globe_mesh": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _c_i32, _p, _p, _p, _p, _c_i64, _p]),
     "wo_globe_mesh_plates": (C.c_int, [_p, _c_i32, _p, _p, _p, _c_i32, _p, _p, _p, _p, _p, _c_i64, _p]),
     "wo_globe_lines": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _p, _p, _p, _c_i64, _p]),

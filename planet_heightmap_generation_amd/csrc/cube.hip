@@ -14,6 +14,8 @@
 //                             over the list, whose length never comes back to the host
 //   k_map_resolve [1]         side -> region (triangles[s], or -1) into the planet's region map, and the covered count   (map.hip)
 // The lowest covering side index wins, so the map does not depend on the order in which lanes, workgroups or launches arrive.
+// wo_relief_raster_cube (relief.hip) is the same call with a request: after k_map_resolve, while the side map and the centres still
+// live, relief_heights_cube adds its height pass.
 // Memory (device_mem.h): triangles, half-edges, the centres, the side map and the list are temporaries of the call, in an arena on
 // its stack.
 #include <hip/hip_runtime.h>
@@ -98,10 +100,9 @@ __global__ __launch_bounds__(WO_BLOCK) void k_cube_big_boxes(const int32_t* __re
 
 using namespace wo;
 
-extern "C" {
-
-int wo_map_raster_cube(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t faceSize, int32_t* regionMapOut, int64_t counts[2]) {
-    const char* fn = "wo_map_raster_cube";
+// wo_map_raster_cube and, with a request, wo_relief_raster_cube
+int wo::cube_raster(wo_planet* p, const char* fn, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t faceSize, int32_t* regionMapOut, int64_t counts[2],
+                    const ReliefRequest* relief) {
     const std::string F = std::string(fn) + ": ";
     if (!check_planet(p, fn)) return 1;
     if (!Q::face_size_ok(faceSize)) { set_error(F + "faceSize is " + std::to_string(faceSize) + ", it must be from 1 to 16384"); return 1; }
@@ -128,13 +129,22 @@ int wo_map_raster_cube(wo_planet* p, int32_t numSides, const int32_t* triangles,
         launch(p, FAM_CUBE_BIG_BOXES, k_cube_big_boxes, CUBE_BIG_GRID, WO_BLOCK, d_tri, d_he, (const float*)t_xyz, (const float*)p->d_xyz, S, sideMap, (const uint32_t*)bigList,
                (const uint32_t*)bigCount);
         launch(p, FAM_CUBE_RESOLVE, k_map_resolve, blocks_for(pixels, 1 << 14), WO_BLOCK, (const uint32_t*)sideMap, d_tri, B->region, pixels, d_counts);
+        if (relief) relief_heights_cube(p, T, B, *relief, d_tri, d_he, numTriangles, t_xyz, sideMap);
         WO_HIP(hipMemcpyAsync(h_counts, d_counts, 16, hipMemcpyDeviceToHost, s));
         if (regionMapOut) WO_HIP(hipMemcpyAsync(regionMapOut, B->region, (size_t)pixels * 4, hipMemcpyDeviceToHost, s));
         WO_HIP(hipStreamSynchronize(s));                      // before T frees the temporaries
         B->valid = true;
+        B->heightValid = relief != nullptr;
+        B->heightCube = true;
         if (counts) { counts[0] = (int64_t)h_counts[0]; counts[1] = pixels - (int64_t)h_counts[0]; }
         return 0;
     WO_CATCH(fn)
+}
+
+extern "C" {
+
+int wo_map_raster_cube(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t faceSize, int32_t* regionMapOut, int64_t counts[2]) {
+    return cube_raster(p, "wo_map_raster_cube", numSides, triangles, halfedges, faceSize, regionMapOut, counts, nullptr);
 }
 
 }  // extern "C"

@@ -61,7 +61,8 @@ enum Family : int {
     FAM_GLOBE_TABLES, FAM_GLOBE_REGION_COLORS, FAM_GLOBE_RANGE, FAM_GLOBE_MESH, FAM_GLOBE_LINE_COUNT, FAM_GLOBE_LINE_SCAN, FAM_GLOBE_LINE_WRITE,
     FAM_OVERLAY_BINS, FAM_OVERLAY_ARROWS,
     FAM_PICK, FAM_PICK_REDUCE, FAM_HIGHLIGHT,
-    FAM_CUBE_CENTERS, FAM_CUBE_FILL, FAM_CUBE_SIDES, FAM_CUBE_BIG_BOXES, FAM_CUBE_RESOLVE, FAM_COUNT
+    FAM_CUBE_CENTERS, FAM_CUBE_FILL, FAM_CUBE_SIDES, FAM_CUBE_BIG_BOXES, FAM_CUBE_RESOLVE,
+    FAM_RELIEF_TRI_ELEVATION, FAM_RELIEF_HEIGHTS, FAM_RELIEF_HEIGHT16, FAM_RELIEF_TABLES, FAM_RELIEF_NORMALS, FAM_COUNT
 };
 extern const char* const kFamilyNames[FAM_COUNT];
 
@@ -215,7 +216,8 @@ struct wo_planet {
     struct wo_temp_block* temp = nullptr;
     struct wo_koppen_block* koppen = nullptr;
     // map export (map.hip, cube.hip; map_block.h): the map block — the region map of the last wo_map_raster or wo_map_raster_cube
-    // (4 bytes per pixel), allocated by that call; deleted by wo_map_free and wo_planet_destroy (map_free)
+    // (4 bytes per pixel) and, after wo_relief_raster or wo_relief_raster_cube, the height map of the same shape (4 bytes per
+    // pixel), allocated by that call; deleted by wo_map_free and wo_planet_destroy (map_free)
     struct wo_map_block* map = nullptr;
     // the editor's highlight state (globe.hip): one class byte per region (pick_ops.h: CLS_*), set by wo_highlight_set; deleted by
     // wo_highlight_clear and wo_planet_destroy (highlight_free)

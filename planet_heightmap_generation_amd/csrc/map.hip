@@ -20,6 +20,8 @@
 // k_map_pixels [1] (region map -> RGBA8, four pixels per thread).
 // wo_map_raster_centered is the same raster around a centre meridian (the map view's, map_layer_ops.h): the two table kernels take
 // centerLon (k_map_region_lonlat_centered, k_map_center_lonlat_centered), every other launch is wo_map_raster's.
+// wo_relief_raster (relief.hip) is wo_map_raster_centered with a request: after k_map_resolve, while the side map and the two tables
+// still live, relief_heights_map adds its height pass; the launches above are the same and so are the region map and the counts.
 // Memory (device_mem.h): the region map lives in a block with an arena of its own on the planet (map_block.h; int32 per pixel; a
 // raster at another width or height, wo_map_raster_cube's included, replaces it, wo_map_free and wo_planet_destroy drop it);
 // triangles, half-edges, both longitude / latitude tables, the side map, the list and the colour tables are temporaries of the call,
@@ -164,7 +166,7 @@ wo_map_block* map_block_for(wo_planet* p, int32_t W, int32_t H) {
         block->W = W; block->H = H;
         p->map = block.release();
     }
-    p->map->valid = false;
+    p->map->valid = p->map->heightValid = false;             // any raster, through any entry point, ends the relief of the last
     return p->map;
 }
 
@@ -174,9 +176,9 @@ static bool map_width_ok(int32_t width) { return width >= 2 && width <= 32768 &&
 
 using namespace wo;
 
-// wo_map_raster (centered == false: its own two table kernels) and wo_map_raster_centered
-static int map_raster(wo_planet* p, const char* fn, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, bool centered, double centerLon,
-                      int32_t* regionMapOut, int64_t counts[2]) {
+// wo_map_raster (centered == false: its own two table kernels), wo_map_raster_centered and, with a request, wo_relief_raster
+int wo::map_raster(wo_planet* p, const char* fn, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, bool centered, double centerLon,
+                   int32_t* regionMapOut, int64_t counts[2], const ReliefRequest* relief) {
     const std::string F = std::string(fn) + ": ";
     if (!check_planet(p, fn)) return 1;
     if (!map_width_ok(width)) { set_error(F + "width is " + std::to_string(width) + ", it must be even and from 2 to 32768"); return 1; }
@@ -211,10 +213,13 @@ static int map_raster(wo_planet* p, const char* fn, int32_t numSides, const int3
         launch(p, FAM_MAP_BIG_BOXES, k_map_big_boxes, MAP_BIG_GRID, WO_BLOCK, d_tri, d_he, (const M::LonLat*)t_ll, (const M::LonLat*)r_ll, W, H, sideMap, (const uint32_t*)bigList,
                (const uint32_t*)bigCount);
         launch(p, FAM_MAP_RESOLVE, k_map_resolve, blocks_for(pixels, 1 << 14), WO_BLOCK, (const uint32_t*)sideMap, d_tri, B->region, pixels, d_counts);
+        if (relief) relief_heights_map(p, T, B, *relief, d_tri, d_he, numTriangles, t_ll, r_ll, sideMap);
         WO_HIP(hipMemcpyAsync(h_counts, d_counts, 16, hipMemcpyDeviceToHost, s));
         if (regionMapOut) WO_HIP(hipMemcpyAsync(regionMapOut, B->region, (size_t)pixels * 4, hipMemcpyDeviceToHost, s));
         WO_HIP(hipStreamSynchronize(s));                      // before T frees the temporaries
         B->valid = true;
+        B->heightValid = relief != nullptr;
+        B->heightCube = false;
         if (counts) { counts[0] = (int64_t)h_counts[0]; counts[1] = pixels - (int64_t)h_counts[0]; }
         return 0;
     WO_CATCH(fn)
@@ -260,12 +265,12 @@ static int map_paint(wo_planet* p, const char* fn, const char* rasters, const Vi
 extern "C" {
 
 int wo_map_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, int32_t* regionMapOut, int64_t counts[2]) {
-    return map_raster(p, "wo_map_raster", numSides, triangles, halfedges, width, false, 0.0, regionMapOut, counts);
+    return map_raster(p, "wo_map_raster", numSides, triangles, halfedges, width, false, 0.0, regionMapOut, counts, nullptr);
 }
 
 int wo_map_raster_centered(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, double centerLon, int32_t* regionMapOut,
                            int64_t counts[2]) {
-    return map_raster(p, "wo_map_raster_centered", numSides, triangles, halfedges, width, true, centerLon, regionMapOut, counts);
+    return map_raster(p, "wo_map_raster_centered", numSides, triangles, halfedges, width, true, centerLon, regionMapOut, counts, nullptr);
 }
 
 int wo_map_color(wo_planet* p, int32_t type, const float* r_elevation, uint8_t* rgbaOut, int64_t outBytes) {

@@ -17,7 +17,8 @@ const char* const kFamilyNames[FAM_COUNT] = {
     "globe_tables", "globe_region_colors", "globe_range", "globe_mesh", "globe_line_count", "globe_line_scan", "globe_line_write",
     "overlay_bins", "overlay_arrows",
     "pick", "pick_reduce", "highlight",
-    "cube_centers", "cube_fill", "cube_sides", "cube_big_boxes", "cube_resolve"};
+    "cube_centers", "cube_fill", "cube_sides", "cube_big_boxes", "cube_resolve",
+    "relief_tri_elevation", "relief_heights", "relief_height16", "relief_tables", "relief_normals"};
 
 hipEvent_t profile_event(wo_planet* p) {
     if (!p->eventPool.empty()) { hipEvent_t e = p->eventPool.back(); p->eventPool.pop_back(); return e; }

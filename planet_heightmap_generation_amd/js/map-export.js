@@ -180,6 +180,10 @@ function chunk(kind, body) {
     return out;
 }
 
+// the chunk writer and the signature, for the 16-bit encoder of js/relief-export.js
+export { chunk as pngChunk };
+export const PNG_SIGNATURE = [0x89, 0x50, 0x4E, 0x47, 0x0D, 0x0A, 0x1A, 0x0A];
+
 // encodePng(rgba, width, height) -> Uint8Array (the file's bytes)
 export function encodePng(rgba, width, height) {
     if (!(rgba instanceof Uint8Array) && !(rgba instanceof Uint8ClampedArray)) throw new TypeError('encodePng: rgba must be a Uint8Array or Uint8ClampedArray');

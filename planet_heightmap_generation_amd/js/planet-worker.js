@@ -88,6 +88,19 @@
 //                  that spans more than 35.26 degrees may be missing from a face (no generated mesh has one).  Progress as exportMap.
 //                  -> { type: 'exportCubeDone', faceSize, maps: [{ type, faces: [{ face, filename, rgba, png? }] }],
 //                       _exportTiming: { raster, color, encode, workerTotal } }, the buffers transferred
+//   cmd 'exportRelief' { projection?, width | faceSize, centerLon?, kinds, strength?, flatOcean?, layout?, png? }   (ours: the reference exports no relief)
+//                  the relief of the planet's current elevation (js/relief-export.js; csrc/relief.hip): the globe mesh's own flat
+//                  triangles sampled at every pixel centre, so heights vary inside a region.  `projection`: 'map' (the default;
+//                  width x width / 2 around `centerLon`) or 'cube' (six faces of faceSize, `layout` as for exportCubeMap).  `kinds`:
+//                  some of height16, landHeight16 (16-bit grey, linear in the reference's heightmap / land-heightmap shade, no gamma:
+//                  Uint16Array), normal, normalObject (RGBA8 normals in tangent / object space of the surface displaced as the globe
+//                  is, times `strength`, default 1; `flatOcean`: elevations <= 0 count as 0: Uint8ClampedArray).  With `png` every
+//                  image comes with its file: 16-bit greyscale PNGs for the first two.  Filenames orogen-<kind>-<seed>.png and
+//                  orogen-cube-<kind>-<face>-<seed>.png.  Needs what exportMap needs of the retained state.  The relief raster leaves
+//                  the same region map as exportMap's, so the planet stays paintable.
+//                  -> { type: 'exportReliefDone', projection, width, height | faceSize, covered, uncovered,
+//                       maps: [{ kind, filename, data, png? }] | [{ kind, faces: [{ face, filename, kind, data, png? }] }],
+//                       _exportTiming: { render, encode, workerTotal } }, the buffers transferred
 //   cmd 'exportGlobe' { view?, layer?, plates?, wireframe?, superPlateBorders?, glb?, windArrows?, oceanCurrentArrows?, itcz?, grid? }   (js/planet-mesh.js:620-836, :533-576)
 //                  the globe mesh three.js would draw, of the planet's current elevation: one displaced triangle per side, nine floats
 //                  of positions and nine of colours each, built on the device (js/globe-export.js).  `view`: color (the default),
@@ -141,6 +154,7 @@ import { denseTable, plateDensities, LAYERS } from './plate-table.js';
 import { generateCoarsePlates } from './coarse-plates.js';
 import { SimplexNoise } from './simplex-noise.js';
 import { MAP_TYPES, MAP_LAYERS, CUBE_MAX_FACE_SIZE, exportFilename, layerFilename, cubeFilename, cubeFaces, encodePng, rasterOnPlanet } from './map-export.js';
+import { RELIEF_KINDS, reliefIs16, reliefFilename, reliefFaces, exportReliefOnPlanet, exportCubeReliefOnPlanet, encodePng16 } from './relief-export.js';
 import { GLOBE_PLATES, GLOBE_TYPE_VIEWS, computePlateColors, exportGlobeOnPlanet, globeFilename } from './globe-export.js';
 import { findNearestRegions, hitDirectionsGlobe, hitDirectionsMap, setHighlight, clearHighlight, PICK_MAX_QUERIES } from './edit-mode.js';
 import { SEASONS, windArrowsOnPlanet, oceanCurrentArrowsOnPlanet, itczLine, grids } from './overlay-export.js';
@@ -608,6 +622,68 @@ function handleExportMap(data) {
     }
 }
 
+// ours: the relief of W.planet's current elevation on the map or on the cube: one relief raster, one pass per kind
+function handleExportRelief(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for exportRelief' }); return; }
+    const missing = ['triangles', 'halfedges'].filter((k) => !(W[k] instanceof Int32Array));
+    if (missing.length) {
+        parentPort.postMessage({ type: 'error', message: `exportRelief: the retained state has no mesh.${missing.join(' and mesh.')} (pass them to retain, or run importHeightmap)` });
+        return;
+    }
+    try {
+        const tTotal0 = performance.now();
+        const kinds = data.kinds !== undefined && data.kinds !== null ? Array.from(data.kinds) : [];
+        if (kinds.length === 0) throw new RangeError(`exportRelief: no relief kind given (some of ${RELIEF_KINDS.join(', ')})`);
+        const projection = data.projection === undefined || data.projection === null ? 'map' : data.projection;
+        if (projection !== 'map' && projection !== 'cube') throw new RangeError(`exportRelief: unknown projection '${projection}' (one of map, cube)`);
+        const layout = data.layout === undefined || data.layout === null ? 'faces' : data.layout;
+        if (layout !== 'faces' && layout !== 'column') throw new RangeError(`exportRelief: unknown layout '${layout}' (one of faces, column)`);
+        const opts = { centerLon: data.centerLon, strength: data.strength, flatOcean: !!data.flatOcean };
+        const encode = (m, w, h) => (reliefIs16(m.kind) ? encodePng16(m.data, w, h) : encodePng(m.data, w, h));
+        progress(0, 'Rendering...');
+        let t0 = performance.now(), tEncode = 0;
+        if (projection === 'map') {
+            const width = data.width;
+            if (!(Number.isInteger(width) && width >= 2 && width <= 32768 && width % 2 === 0)) throw new RangeError('exportRelief: width must be an even integer from 2 to 32768');
+            const r = exportReliefOnPlanet(W.planet, W.triangles, W.halfedges, null, kinds, width, opts);
+            const tRender = performance.now() - t0;
+            const maps = r.maps.map((m) => ({ kind: m.kind, filename: reliefFilename(m.kind, W.seed), data: m.data }));
+            if (data.png) {
+                progress(85, 'Encoding PNG...');
+                t0 = performance.now();
+                for (const m of maps) m.png = encode(m, r.width, r.height);
+                tEncode = performance.now() - t0;
+            }
+            const transfer = [];
+            for (const m of maps) { transfer.push(m.data.buffer); if (m.png) transfer.push(m.png.buffer); }
+            parentPort.postMessage({ type: 'exportReliefDone', projection, width: r.width, height: r.height, covered: r.covered, uncovered: r.uncovered, maps,
+                                     _exportTiming: { render: tRender, encode: tEncode, workerTotal: performance.now() - tTotal0 } }, transfer);
+            return;
+        }
+        const S = data.faceSize;
+        if (!(Number.isInteger(S) && S >= 1 && S <= CUBE_MAX_FACE_SIZE)) throw new RangeError('exportRelief: faceSize must be an integer from 1 to 16384');
+        const r = exportCubeReliefOnPlanet(W.planet, W.triangles, W.halfedges, null, kinds, S, opts);
+        const tRender = performance.now() - t0;
+        const maps = r.maps.map((m) => ({                                      // one S x 6S image per kind; the faces are views of it
+            kind: m.kind,
+            faces: layout === 'column' ? [{ face: 'column', filename: reliefFilename(m.kind, W.seed, 'column'), kind: m.kind, data: m.data }]
+                : reliefFaces(m.data, S, reliefIs16(m.kind) ? 1 : 4).map((f) => ({ face: f.face, filename: reliefFilename(m.kind, W.seed, f.face), kind: m.kind, data: f.data }))
+        }));
+        if (data.png) {
+            progress(85, 'Encoding PNG...');
+            t0 = performance.now();
+            for (const m of maps) for (const f of m.faces) f.png = encode(f, S, layout === 'column' ? 6 * S : S);
+            tEncode = performance.now() - t0;
+        }
+        const transfer = r.maps.map((m) => m.data.buffer);                     // each image's one buffer; the six views travel with it
+        for (const m of maps) for (const f of m.faces) if (f.png) transfer.push(f.png.buffer);
+        parentPort.postMessage({ type: 'exportReliefDone', projection, faceSize: S, covered: r.covered, uncovered: r.uncovered, maps,
+                                 _exportTiming: { render: tRender, encode: tEncode, workerTotal: performance.now() - tTotal0 } }, transfer);
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
 // ours: the cube map of W.planet's current elevation and Koppen block: one raster of the six faces, one colour pass per type and layer
 function handleExportCubeMap(data) {
     if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for exportCubeMap' }); return; }
@@ -804,6 +880,7 @@ parentPort.on('message', (data) => {
         case 'editRecompute': handleEditRecompute(data); break;
         case 'exportMap': handleExportMap(data); break;
         case 'exportCubeMap': handleExportCubeMap(data); break;
+        case 'exportRelief': handleExportRelief(data); break;
         case 'exportGlobe': handleExportGlobe(data); break;
         case 'exportOverlays': handleExportOverlays(data); break;
         case 'generate': handleGenerate(data); break;

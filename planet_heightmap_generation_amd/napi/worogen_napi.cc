@@ -977,6 +977,103 @@ napi_value MapDims(napi_env env, napi_callback_info info) {
     set_nums(env, o, {{"width", (double)dims[0]}, {"height", (double)dims[1]}});
     return o;
 }
+// reliefRaster(planet, triangles, halfedges, width, centerLon, r_elevation | null, download) -> { width, height, covered, uncovered,
+// heights: Float32Array | null }: mapRasterCentered, and the height map beside its region map (include/worogen.h: wo_relief_raster)
+napi_value ReliefRaster(napi_env env, napi_callback_info info) {
+    Args a(env, info);
+    size_t nt, nh;
+    int32_t* tri = (int32_t*)a.ta(1, napi_int32_array, &nt); if (!a.ok) return nullptr;
+    int32_t* he = (int32_t*)a.ta(2, napi_int32_array, &nh); if (!a.ok) return nullptr;
+    if (nt != nh || nt == 0 || nt >= ((size_t)1 << 30)) { napi_throw_range_error(env, nullptr, "reliefRaster: triangles and halfedges must have the same length, numSides"); return nullptr; }
+    const double w = a.num(3);
+    if (!(w >= 2 && w <= 32768 && w == (double)(int64_t)w && ((int64_t)w & 1) == 0)) { napi_throw_range_error(env, nullptr, "reliefRaster: width must be an even integer from 2 to 32768"); return nullptr; }
+    wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    const int32_t W = (int32_t)w, H = W / 2;
+    const double centerLon = a.num(4);                                         // the library refuses what is not finite and within [-pi, pi]
+    float* e = (float*)opt_regions(a, 5, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    bool download = false; if (a.argc > 6) napi_get_value_bool(env, a.argv[6], &download);
+    void* d = nullptr; napi_value map = nullptr;
+    if (download) { map = make_ta(env, napi_float32_array, (size_t)W * (size_t)H, 4, &d); if (!map) return nullptr; }
+    else napi_get_null(env, &map);
+    int64_t counts[2] = {0, 0};
+    if (wo_relief_raster(p, (int32_t)nt, tri, he, W, centerLon, e, (float*)d, counts)) return throw_wo(env, "reliefRaster");
+    napi_value o; napi_create_object(env, &o);
+    set_nums(env, o, {{"width", (double)W}, {"height", (double)H}, {"covered", (double)counts[0]}, {"uncovered", (double)counts[1]}});
+    set_prop(env, o, "heights", map);
+    return o;
+}
+// reliefRasterCube(planet, triangles, halfedges, faceSize, r_elevation | null, download) -> { faceSize, width, height, covered, uncovered,
+// heights: Float32Array | null }: mapRasterCube, and the height map of the six stacked faces (wo_relief_raster_cube)
+napi_value ReliefRasterCube(napi_env env, napi_callback_info info) {
+    Args a(env, info);
+    size_t nt, nh;
+    int32_t* tri = (int32_t*)a.ta(1, napi_int32_array, &nt); if (!a.ok) return nullptr;
+    int32_t* he = (int32_t*)a.ta(2, napi_int32_array, &nh); if (!a.ok) return nullptr;
+    if (nt != nh || nt == 0 || nt >= ((size_t)1 << 30)) { napi_throw_range_error(env, nullptr, "reliefRasterCube: triangles and halfedges must have the same length, numSides"); return nullptr; }
+    const double w = a.num(3);
+    if (!(w >= 1 && w <= 16384 && w == (double)(int64_t)w)) { napi_throw_range_error(env, nullptr, "reliefRasterCube: faceSize must be an integer from 1 to 16384"); return nullptr; }
+    wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    const int32_t S = (int32_t)w;
+    float* e = (float*)opt_regions(a, 4, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    bool download = false; if (a.argc > 5) napi_get_value_bool(env, a.argv[5], &download);
+    void* d = nullptr; napi_value map = nullptr;
+    if (download) { map = make_ta(env, napi_float32_array, 6 * (size_t)S * (size_t)S, 4, &d); if (!map) return nullptr; }
+    else napi_get_null(env, &map);
+    int64_t counts[2] = {0, 0};
+    if (wo_relief_raster_cube(p, (int32_t)nt, tri, he, S, e, (float*)d, counts)) return throw_wo(env, "reliefRasterCube");
+    napi_value o; napi_create_object(env, &o);
+    set_nums(env, o, {{"faceSize", (double)S}, {"width", (double)S}, {"height", 6.0 * (double)S}, {"covered", (double)counts[0]}, {"uncovered", (double)counts[1]}});
+    set_prop(env, o, "heights", map);
+    return o;
+}
+// the pixels of the planet's resident map (wo_map_dims; 0 without one: the library then says what is missing)
+bool relief_pixels(napi_env env, wo_planet* p, const char* fn, size_t* pixels) {
+    int32_t dims[2] = {0, 0};
+    if (wo_map_dims(p, dims)) { throw_wo(env, fn); return false; }
+    *pixels = (size_t)dims[0] * (size_t)dims[1];
+    return true;
+}
+// reliefHeights(planet) -> Float32Array: the resident height map (NaN: nothing covers the pixel)
+napi_value ReliefHeights(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    size_t n;
+    if (!relief_pixels(env, p, "reliefHeights", &n)) return nullptr;
+    void* d; napi_value out = make_ta(env, napi_float32_array, n, 4, &d);
+    if (!out) return nullptr;
+    if (wo_relief_download(p, (float*)d, (int64_t)n * 4)) return throw_wo(env, "reliefHeights");
+    return out;
+}
+// reliefHeight16(planet, kind 0..1) -> Uint16Array: the height map in 16 bits, linear (WO_RELIEF_HEIGHT, WO_RELIEF_LAND_HEIGHT)
+napi_value ReliefHeight16(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    const double k = a.num(1);
+    if (!(k >= 0 && k <= 1 && k == (double)(int64_t)k)) { napi_throw_range_error(env, nullptr, "reliefHeight16: kind must be 0 or 1"); return nullptr; }
+    size_t n;
+    if (!relief_pixels(env, p, "reliefHeight16", &n)) return nullptr;
+    void* d; napi_value out = make_ta(env, napi_uint16_array, n, 2, &d);
+    if (!out) return nullptr;
+    if (wo_relief_height16(p, (int32_t)k, (uint16_t*)d, (int64_t)n * 2)) return throw_wo(env, "reliefHeight16");
+    return out;
+}
+// reliefNormals(planet, space 0..1, strength, flags) -> Uint8ClampedArray: RGBA8 normals of the displaced surface (WO_RELIEF_NORMAL_*,
+// WO_RELIEF_FLAT_OCEAN); the library refuses a strength that is not finite and >= 0
+napi_value ReliefNormals(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    const double s = a.num(1), strength = a.num(2), flags = a.num(3);
+    if (!(s >= 0 && s <= 1 && s == (double)(int64_t)s)) { napi_throw_range_error(env, nullptr, "reliefNormals: space must be 0 or 1"); return nullptr; }
+    if (!(flags >= 0 && flags <= 1 && flags == (double)(int64_t)flags)) { napi_throw_range_error(env, nullptr, "reliefNormals: flags must be 0 or 1"); return nullptr; }
+    size_t n;
+    if (!relief_pixels(env, p, "reliefNormals", &n)) return nullptr;
+    void* d; napi_value out = make_ta(env, napi_uint8_clamped_array, n * 4, 1, &d);
+    if (!out) return nullptr;
+    if (wo_relief_normals(p, (int32_t)s, strength, (int32_t)flags, (uint8_t*)d, (int64_t)n * 4)) return throw_wo(env, "reliefNormals");
+    return out;
+}
 napi_value MapFree(napi_env env, napi_callback_info info) {                    // (planet)
     Args a(env, info); wo_planet* p = planet_at(a, 0);
     if (!planet_ok(env, p)) return nullptr;
@@ -1259,6 +1356,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"temperatureUpload", TemperatureUpload}, {"classifyKoppen", ClassifyKoppen},
         {"mapRaster", MapRaster}, {"mapColor", MapColor}, {"mapFree", MapFree}, {"mapRasterCentered", MapRasterCentered}, {"mapColorLayer", MapColorLayer},
         {"mapRasterCube", MapRasterCube}, {"mapDims", MapDims},
+        {"reliefRaster", ReliefRaster}, {"reliefRasterCube", ReliefRasterCube}, {"reliefHeights", ReliefHeights}, {"reliefHeight16", ReliefHeight16},
+        {"reliefNormals", ReliefNormals},
         {"globeMesh", GlobeMesh}, {"globeMeshPlates", GlobeMeshPlates}, {"globeLines", GlobeLines},
         {"overlayBins", OverlayBins}, {"overlayArrows", OverlayArrows},
         {"pickRegions", PickRegions}, {"pickDirectionsGlobe", PickDirectionsGlobe}, {"pickDirectionsMap", PickDirectionsMap},
