@@ -607,6 +607,46 @@ int wo_relief_download(wo_planet* p, float* out, int64_t outBytes);
 int wo_relief_height16(wo_planet* p, int32_t kind, uint16_t* out, int64_t outBytes);
 int wo_relief_normals(wo_planet* p, int32_t space, double strength, int32_t flags, uint8_t* rgbaOut, int64_t outBytes);
 
+/* ------------------------------------------------ rivers and lakes ---------------------------- */
+/* Rivers and lakes of the final terrain (ours: the reference keeps no drainage beyond the scratch of erodeComposite; csrc/rivers.hip,
+ *   the bodies and the whole contract are in csrc/rivers_ops.h).  A cell is land iff e > 0.  Every land cell drains to its neighbour
+ *   with the lowest key (e, index), if that key is below its own; the others are pits.  Depressions are resolved so that rivers
+ *   reach the sea: the basins spill over their lowest pass towards the drained cells in the order of Prim's algorithm (the minimum
+ *   spanning tree of the basin graph, built by Boruvka rounds on the device), a spilled basin's pit drains to the cell beyond the
+ *   pass, and the cells of the basin below its water level carry that level as their lake level.  Basins on a landmass with no
+ *   drained cell stay endorheic.  The discharge is the runoff accumulated down the final receivers in 2^-16 fixed point, uint64:
+ *   exact, so every field is defined bit for bit.
+ *   wo_compute_rivers leaves five fields resident in a rivers block the planet owns (24 bytes per cell; a second call replaces
+ *   them; wo_planet_destroy drops the block): r_river_receiver (int32: the final receiver, -1 at roots and off land),
+ *   r_river_basin (int32: the cell id of the basin's pit, -1 drained, -2 not land), r_lake_level (f32, the quiet NaN 0x7FC00000
+ *   where there is no lake), r_river_discharge (uint64, units of 2^-16; ocean cells hold what reaches them) and r_river_flow
+ *   (f32: discharge * 2^-16).  r_elevation: numRegions floats, NULL means the resident field.  runoffSource:
+ *   WO_RIVERS_RUNOFF_PRECIP (r_precip_summer + r_precip_winter) * 0.5f of the precipitation block, computed or uploaded ("no
+ *   precipitation result" without it), WO_RIVERS_RUNOFF_UNIFORM 1 per land cell, WO_RIVERS_RUNOFF_VALUES numRegions floats in
+ *   runoffValues (NULL for the other two).  The runoff is clamped to [0, 16]; NaN counts 0.  info (may be NULL) receives the counts.
+ *   wo_rivers_download copies one field by its key (outBytes at least its size).  Without a rivers block it, wo_river_lines and
+ *   wo_map_color_rivers answer status 1, "no rivers result".
+ *   wo_river_lines gives one segment of six floats per river cell, in ascending cell order: a land cell with discharge >=
+ *   ceil(minFlow * 65536), a receiver among its neighbours and no lake level of its own (lakes, and the jump from a spilled pit
+ *   across its pass, are not drawn).  It runs from the cell to its receiver, both ends displaced as wo_globe_lines displaces, at
+ *   base 1.003, by r_elevation (NULL: the resident field).  flowsOut (may be NULL) receives r_river_flow of the segment's cell.
+ *   capacity, the room of both outputs in segments, must be at least numRegions; *count receives the number written.
+ *   wo_map_color_rivers is wo_map_color(p, type, ...) in every byte, except that the pixels of the resident region map (map or
+ *   cube) whose region is a river cell under minFlow or has a lake level are RGBA (41, 98, 168, 255).  r_river_flow itself goes
+ *   through wo_map_color_layer's WO_MAP_LAYER_DEBUG unchanged.  minFlow must be finite.
+ *   A refused call returns 1, names the call and the offending value, and allocates nothing. */
+enum { WO_RIVERS_RUNOFF_PRECIP = 0, WO_RIVERS_RUNOFF_UNIFORM = 1, WO_RIVERS_RUNOFF_VALUES = 2 };
+typedef struct wo_rivers_info {
+    int32_t landCells, pits, spilledBasins, endorheicBasins, lakeCells;
+    int32_t rounds, launches;                /* contraction rounds that merged components; kernel launches of the call */
+} wo_rivers_info;
+int wo_compute_rivers(wo_planet* p, int32_t numRegions, const float* r_elevation, int32_t runoffSource, const float* runoffValues,
+                      wo_rivers_info* info);
+int wo_rivers_download(wo_planet* p, const char* field, void* out, int64_t outBytes);
+int wo_river_lines(wo_planet* p, double minFlow, const float* r_elevation, float* segmentsOut, float* flowsOut, int64_t capacity,
+                   int64_t* count);
+int wo_map_color_rivers(wo_planet* p, int32_t type, const float* r_elevation, double minFlow, uint8_t* rgbaOut, int64_t outBytes);
+
 /* ------------------------------------------------ globe mesh (js/planet-mesh.js) -------------- */
 /* buildMesh, updateMeshColors, updateSuperPlateBorders (globe form)                  js/planet-mesh.js:620-836, :840-957, :533-576
  *   The displaced Voronoi-fan mesh three.js draws, as the reference's own Float32Arrays bit for bit (csrc/globe.hip; the bodies and

@@ -62,7 +62,8 @@ enum Family : int {
     FAM_OVERLAY_BINS, FAM_OVERLAY_ARROWS,
     FAM_PICK, FAM_PICK_REDUCE, FAM_HIGHLIGHT,
     FAM_CUBE_CENTERS, FAM_CUBE_FILL, FAM_CUBE_SIDES, FAM_CUBE_BIG_BOXES, FAM_CUBE_RESOLVE,
-    FAM_RELIEF_TRI_ELEVATION, FAM_RELIEF_HEIGHTS, FAM_RELIEF_HEIGHT16, FAM_RELIEF_TABLES, FAM_RELIEF_NORMALS, FAM_COUNT
+    FAM_RELIEF_TRI_ELEVATION, FAM_RELIEF_HEIGHTS, FAM_RELIEF_HEIGHT16, FAM_RELIEF_TABLES, FAM_RELIEF_NORMALS,
+    FAM_RIVERS, FAM_RIVERS_CLIMB, FAM_RIVERS_LINES, FAM_COUNT
 };
 extern const char* const kFamilyNames[FAM_COUNT];
 
@@ -222,6 +223,9 @@ struct wo_planet {
     // the editor's highlight state (globe.hip): one class byte per region (pick_ops.h: CLS_*), set by wo_highlight_set; deleted by
     // wo_highlight_clear and wo_planet_destroy (highlight_free)
     struct wo_highlight_block* highlight = nullptr;
+    // rivers and lakes (rivers.hip; rivers_block.h): the rivers block — the five results of wo_compute_rivers (24 bytes per cell),
+    // allocated on its first call; deleted by wo_planet_destroy (rivers_free)
+    struct wo_rivers_block* rivers = nullptr;
 
     // Patch-major mirror of the mesh for erodeComposite (mirror.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
@@ -313,6 +317,7 @@ void wind_free(wo_planet* p);
 void ocean_free(wo_planet* p);
 void precip_free(wo_planet* p);
 void temp_free(wo_planet* p);
+void rivers_free(wo_planet* p);
 // map.hip: drops the map block
 void map_free(wo_planet* p);
 // globe.hip: drops the highlight state; its class bytes (on the device), nullptr when no state is set

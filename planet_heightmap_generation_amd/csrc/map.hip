@@ -37,6 +37,7 @@
 #include "map_block.h"
 #include "map_layer_ops.h"
 #include "map_ops.h"
+#include "rivers_block.h"
 #include "stage_block.h"
 #include "view_colors.h"
 
@@ -227,8 +228,10 @@ int wo::map_raster(wo_planet* p, const char* fn, int32_t numSides, const int32_t
 
 // wo_map_color and wo_map_color_layer: the request's checks around those of the region map (`rasters`: the calls that give one, as the
 // message names them), one packed colour per region, then the pixels; backgroundType: the map type whose background the uncovered
-// pixels take
-static int map_paint(wo_planet* p, const char* fn, const char* rasters, const ViewRequest& q, ViewFamilies families, int32_t backgroundType, uint8_t* rgbaOut, int64_t outBytes) {
+// pixels take; riverMinQ (wo_map_color_rivers: a map type and a rivers block, which the caller checked): the river cells under that
+// threshold and the lakes take the river tint (rivers.hip) before the pixels are written
+static int map_paint(wo_planet* p, const char* fn, const char* rasters, const ViewRequest& q, ViewFamilies families, int32_t backgroundType, uint8_t* rgbaOut, int64_t outBytes,
+                     const uint64_t* riverMinQ = nullptr) {
     const std::string F = std::string(fn) + ": ";
     if (!check_planet(p, fn)) return 1;
     if (!rgbaOut) { set_error(F + "null pointer"); return 1; }
@@ -254,6 +257,7 @@ static int map_paint(wo_planet* p, const char* fn, const char* rasters, const Vi
         uint32_t* regionRgba = T.dev<uint32_t>((size_t)N);
         uint32_t* out = T.dev<uint32_t>((size_t)pixels);
         view_region_colors(p, T, plan, e, ViewSink{nullptr, regionRgba, d_lut}, families);
+        if (riverMinQ) rivers_tint_regions(p, e, *riverMinQ, regionRgba);
         launch(p, FAM_MAP_PIXELS, k_map_pixels, blocks_for((pixels + 3) / 4, 1 << 14), WO_BLOCK, (const int32_t*)B->region, (const uint32_t*)regionRgba, M::background_rgba(backgroundType, lut), out,
                pixels);
         WO_HIP(hipMemcpyAsync(rgbaOut, out, (size_t)pixels * 4, hipMemcpyDeviceToHost, s));
@@ -277,6 +281,17 @@ int wo_map_color(wo_planet* p, int32_t type, const float* r_elevation, uint8_t* 
     ViewRequest q;
     q.source = VIEW_TYPE; q.id = type; q.r_elevation = r_elevation;
     return map_paint(p, "wo_map_color", "wo_map_raster", q, {FAM_MAP_REGION_COLORS, FAM_MAP_RANGE}, type, rgbaOut, outBytes);
+}
+
+int wo_map_color_rivers(wo_planet* p, int32_t type, const float* r_elevation, double minFlow, uint8_t* rgbaOut, int64_t outBytes) {
+    const char* fn = "wo_map_color_rivers";
+    if (!check_planet(p, fn)) return 1;
+    if (!(minFlow - minFlow == 0.0)) { set_error(std::string(fn) + ": minFlow is " + std::to_string(minFlow) + ", it must be finite"); return 1; }
+    if (!block_require(p, fn, rivers_desc(), rivers_desc().all(), nullptr)) return 1;
+    ViewRequest q;
+    q.source = VIEW_TYPE; q.id = type; q.r_elevation = r_elevation;
+    const uint64_t minQ = rivers::min_q(minFlow);
+    return map_paint(p, fn, "wo_map_raster", q, {FAM_MAP_REGION_COLORS, FAM_MAP_RANGE}, type, rgbaOut, outBytes, &minQ);
 }
 
 int wo_map_color_layer(wo_planet* p, int32_t layer, const float* values, const float* r_elevation, uint8_t* rgbaOut, int64_t outBytes) {

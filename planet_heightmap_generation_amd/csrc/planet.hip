@@ -244,6 +244,7 @@ void wo_planet_destroy(wo_planet* p) {
     highlight_free(p);
     map_free(p);
     temp_free(p);
+    rivers_free(p);
     precip_free(p);
     ocean_free(p);
     wind_free(p);

@@ -18,7 +18,8 @@ const char* const kFamilyNames[FAM_COUNT] = {
     "overlay_bins", "overlay_arrows",
     "pick", "pick_reduce", "highlight",
     "cube_centers", "cube_fill", "cube_sides", "cube_big_boxes", "cube_resolve",
-    "relief_tri_elevation", "relief_heights", "relief_height16", "relief_tables", "relief_normals"};
+    "relief_tri_elevation", "relief_heights", "relief_height16", "relief_tables", "relief_normals",
+    "rivers", "rivers_climb", "rivers_lines"};
 
 hipEvent_t profile_event(wo_planet* p) {
     if (!p->eventPool.empty()) { hipEvent_t e = p->eventPool.back(); p->eventPool.pop_back(); return e; }

@@ -7,6 +7,7 @@ export const GLB_MAX_BYTES = 0xFFFFFFFF;                    // the container's l
 // 0x00ff88 opaque, the grid white at 0.12
 export const ARROW_OPACITY = 0.6;
 export const ITCZ_COLOR = [0, 1, 0x88 / 255];
+export const RIVER_COLOR = [41 / 255, 98 / 255, 168 / 255];      // the map tint of the rivers (csrc/rivers_ops.h)
 export const GRID_OPACITY = 0.12;
 
 // ours: the reference exports no globe
@@ -77,14 +78,15 @@ function overlayPart(v, what) {
     return [pos, col];
 }
 
-// encodeGlb({ position, color, bounds }, { wireframe, superPlateBorders, name, windArrows, oceanCurrentArrows, itcz, grid }) -> Uint8Array (the
+// encodeGlb({ position, color, bounds }, { wireframe, superPlateBorders, name, windArrows, oceanCurrentArrows, itcz, grid, rivers }) -> Uint8Array (the
 // file's bytes).  One buffer, one mesh: a TRIANGLES primitive with POSITION (min / max from bounds) and COLOR_0, both f32 VEC3 and
 // linear; its material the default metallic-roughness one with metallic 0 and roughness 1 (our decision: the reference's Lambert
 // shader and its normals are not offered); a LINES primitive with a black material at the reference's opacity per line set.  The
 // overlays of overlay-export.js follow as further LINES primitives under unlit materials (KHR_materials_unlit, named only when one
 // of them is there): windArrows and oceanCurrentArrows with COLOR_0 at the reference's opacity 0.6, itcz in 0x00ff88 (the hex
-// channels over 255, as glTF takes a linear factor: our decision), grid white at 0.12; each is the globe form, or a result that has
-// one.  Without them the bytes are what they were before the overlays existed.
+// channels over 255, as glTF takes a linear factor: our decision), grid white at 0.12, rivers (the segments of js/rivers.js) in the
+// map tint's (41, 98, 168) over 255; each is the globe form, or a result that has one.  Without them the bytes are what they were
+// before the overlays existed.
 export function encodeGlb(mesh, opts) {
     const o = opts || {}, { position, color, bounds } = mesh;
     if (!(position instanceof Float32Array) || !(color instanceof Float32Array) || !(bounds instanceof Float32Array)) throw new TypeError("encodeGlb needs position, color and bounds (buildMesh's result)");
@@ -93,7 +95,7 @@ export function encodeGlb(mesh, opts) {
     for (const [k, a] of lines) if (a.length % 6) throw new RangeError(`${k} has ${a.length} floats, no multiple of 6`);
     const white = [1, 1, 1], overlays = [];                 // [name, positions, colours or null, base colour factor]
     for (const [k, v, factor] of [['windArrows', o.windArrows, white.concat([ARROW_OPACITY])], ['oceanCurrentArrows', o.oceanCurrentArrows, white.concat([ARROW_OPACITY])],
-                                  ['itcz', o.itcz, ITCZ_COLOR.concat([1])], ['grid', o.grid, white.concat([GRID_OPACITY])]]) {
+                                  ['itcz', o.itcz, ITCZ_COLOR.concat([1])], ['grid', o.grid, white.concat([GRID_OPACITY])], ['rivers', o.rivers, RIVER_COLOR.concat([1])]]) {
         if (v === undefined || v === null) continue;
         const [pos, col] = overlayPart(v, k);
         if ((col === null) === k.endsWith('Arrows')) throw new TypeError(`${k} takes ` + (col === null ? '{ position, color }' : 'positions alone'));

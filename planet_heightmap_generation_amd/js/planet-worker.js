@@ -101,7 +101,7 @@
 //                  -> { type: 'exportReliefDone', projection, width, height | faceSize, covered, uncovered,
 //                       maps: [{ kind, filename, data, png? }] | [{ kind, faces: [{ face, filename, kind, data, png? }] }],
 //                       _exportTiming: { render, encode, workerTotal } }, the buffers transferred
-//   cmd 'exportGlobe' { view?, layer?, plates?, wireframe?, superPlateBorders?, glb?, windArrows?, oceanCurrentArrows?, itcz?, grid? }   (js/planet-mesh.js:620-836, :533-576)
+//   cmd 'exportGlobe' { view?, layer?, plates?, wireframe?, superPlateBorders?, glb?, windArrows?, oceanCurrentArrows?, itcz?, grid?, rivers? }   (js/planet-mesh.js:620-836, :533-576)
 //                  the globe mesh three.js would draw, of the planet's current elevation: one displaced triangle per side, nine floats
 //                  of positions and nine of colours each, built on the device (js/globe-export.js).  `view`: color (the default),
 //                  heightmap, landheightmap, biome or koppen; `layer`: a layer as for exportMap, a climate layer from the planet's
@@ -115,6 +115,19 @@
 //                  -> { type: 'globeDone', view, filename, numSides, bounds, glb | position, color[, wireframe][, superPlateBorders][, windArrows]
 //                       [, oceanCurrentArrows][, itcz][, grid],
 //                       _globeTiming: { workerTotal } }, the buffers transferred
+//   cmd 'computeRivers' { runoff?, download? }   (ours: js/rivers.js, csrc/rivers.hip)
+//                  the rivers and lakes of the planet's current elevation: every land cell drains to its lowest neighbour, depressions
+//                  spill over their lowest pass so that rivers reach the sea, and the runoff is accumulated down the receivers.
+//                  `runoff`: 'precip' (the default: the mean of the two precipitation fields computeClimate left on the planet; `no
+//                  precipitation result` before it), 'uniform' (1 per land cell, needs no climate) or a Float32Array of numRegions
+//                  values.  The five fields stay on the planet for the `rivers` option of exportMap, exportCubeMap and exportGlobe,
+//                  until the next computeRivers; they describe the elevation of that moment.  With `download` they come back too.
+//                  -> { type: 'riversDone', landCells, pits, spilledBasins, endorheicBasins, lakeCells, rounds, launches
+//                       [, r_river_receiver, r_river_basin: Int32Array, r_lake_level, r_river_flow: Float32Array, r_river_discharge: BigUint64Array],
+//                       _riversTiming: { workerTotal } }, the buffers transferred
+//                  exportMap and exportCubeMap take `rivers: { minFlow }`: the types' maps (not the layers') get the river cells whose flow
+//                  reaches minFlow and the lakes painted (41, 98, 168); exportGlobe takes the same and adds the river segments as `rivers`
+//                  (Float32Array, six floats each) or as one more LINES primitive of the GLB.  `no rivers result` before computeRivers.
 //   cmd 'exportOverlays' { windArrows?, oceanCurrentArrows?, itcz?, grid?, centerLon? }   (js/planet-mesh.js:1289-1749, :385-469)
 //                  the line overlays of the reference's views in both forms, globe and map (js/overlay-export.js): `windArrows`,
 //                  `oceanCurrentArrows`: 'summer' | 'winter', the arrows of that season from the blocks computeClimate left on the planet,
@@ -157,6 +170,7 @@ import { MAP_TYPES, MAP_LAYERS, CUBE_MAX_FACE_SIZE, exportFilename, layerFilenam
 import { RELIEF_KINDS, reliefIs16, reliefFilename, reliefFaces, exportReliefOnPlanet, exportCubeReliefOnPlanet, encodePng16 } from './relief-export.js';
 import { GLOBE_PLATES, GLOBE_TYPE_VIEWS, computePlateColors, exportGlobeOnPlanet, globeFilename } from './globe-export.js';
 import { findNearestRegions, hitDirectionsGlobe, hitDirectionsMap, setHighlight, clearHighlight, PICK_MAX_QUERIES } from './edit-mode.js';
+import { computeRiversOnPlanet, checkedMinFlow, RIVER_KEYS } from './rivers.js';
 import { SEASONS, windArrowsOnPlanet, oceanCurrentArrowsOnPlanet, itczLine, grids } from './overlay-export.js';
 
 let W = null;          // retained state (js/planet-worker.js:22)
@@ -591,6 +605,7 @@ function handleExportMap(data) {
         const tTotal0 = performance.now();
         const { types, layers } = requestedMaps('exportMap', data);
         const width = data.width;
+        const rivers = data.rivers !== undefined && data.rivers !== null ? checkedMinFlow('exportMap', data.rivers) : null;
         progress(0, 'Rendering...');
         let t0 = performance.now();
         const r = rasterOnPlanet(W.planet, W.triangles, W.halfedges, width, data.centerLon);
@@ -598,7 +613,8 @@ function handleExportMap(data) {
         t0 = performance.now();
         const maps = [], total = types.length + layers.length;
         types.forEach((type, k) => {
-            maps.push({ type, filename: exportFilename(type, W.seed), rgba: addon.mapColor(W.planet, MAP_TYPES.indexOf(type), null, width) });
+            maps.push({ type, filename: exportFilename(type, W.seed), rgba: rivers === null ? addon.mapColor(W.planet, MAP_TYPES.indexOf(type), null, width)
+                                                                                                 : addon.mapColorRivers(W.planet, MAP_TYPES.indexOf(type), null, rivers, width) });
             progress(80 * (k + 1) / total, 'Rendering...');
         });
         layers.forEach((l, k) => {
@@ -698,6 +714,7 @@ function handleExportCubeMap(data) {
         const S = data.faceSize, layout = data.layout === undefined || data.layout === null ? 'faces' : data.layout;
         if (!(Number.isInteger(S) && S >= 1 && S <= CUBE_MAX_FACE_SIZE)) throw new RangeError('exportCubeMap: faceSize must be an integer from 1 to 16384');
         if (layout !== 'faces' && layout !== 'column') throw new RangeError(`exportCubeMap: unknown layout '${layout}' (one of faces, column)`);
+        const rivers = data.rivers !== undefined && data.rivers !== null ? checkedMinFlow('exportCubeMap', data.rivers) : null;
         progress(0, 'Rendering...');
         let t0 = performance.now();
         addon.mapRasterCube(W.planet, W.triangles, W.halfedges, S, false);
@@ -705,7 +722,7 @@ function handleExportCubeMap(data) {
         t0 = performance.now();
         const images = [], total = types.length + layers.length;             // one S x 6S image per map; the faces are views of it
         types.forEach((type, k) => {
-            images.push({ type, rgba: addon.mapColor(W.planet, MAP_TYPES.indexOf(type), null) });
+            images.push({ type, rgba: rivers === null ? addon.mapColor(W.planet, MAP_TYPES.indexOf(type), null) : addon.mapColorRivers(W.planet, MAP_TYPES.indexOf(type), null, rivers) });
             progress(80 * (k + 1) / total, 'Rendering...');
         });
         layers.forEach((l, k) => {
@@ -803,6 +820,7 @@ function handleExportGlobe(data) {
         for (const k of ['windArrows', 'oceanCurrentArrows']) if (data[k] !== undefined && data[k] !== null) opts[k] = checkedSeason('exportGlobe', k, data[k]);
         if (data.itcz !== undefined && data.itcz !== null) opts.itcz = itczOf('exportGlobe', data.itcz);
         if (data.grid !== undefined && data.grid !== null) opts.grid = data.grid;
+        if (data.rivers !== undefined && data.rivers !== null) opts.rivers = { minFlow: checkedMinFlow('exportGlobe', data.rivers) };
         progress(0, 'Building globe...');
         const name = data.plates ? GLOBE_PLATES : (data.layer !== undefined && data.layer !== null ? data.layer : view);
         const res = exportGlobeOnPlanet(W.planet, W.triangles, W.halfedges, null, view, W.seed, opts);
@@ -813,11 +831,27 @@ function handleExportGlobe(data) {
         else {
             msg.position = res.position; msg.color = res.color;
             transfer.push(res.position.buffer, res.color.buffer);
-            for (const k of ['wireframe', 'superPlateBorders', 'itcz', 'grid']) if (res[k]) { msg[k] = res[k]; transfer.push(res[k].buffer); }
+            for (const k of ['wireframe', 'superPlateBorders', 'itcz', 'grid', 'rivers']) if (res[k]) { msg[k] = res[k]; transfer.push(res[k].buffer); }
             for (const k of ['windArrows', 'oceanCurrentArrows']) if (res[k]) { msg[k] = res[k]; transfer.push(res[k].position.buffer, res[k].color.buffer); }
         }
         msg._globeTiming = { workerTotal: performance.now() - tTotal0 };
         parentPort.postMessage(msg, transfer);
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
+// ours: the rivers and lakes of W.planet's current elevation, resident for the exports
+function handleComputeRivers(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for computeRivers' }); return; }
+    try {
+        const tTotal0 = performance.now();
+        progress(0, 'Tracing rivers...');
+        const res = computeRiversOnPlanet(W.planet, null, data.runoff, !!data.download);
+        progress(90, 'Done');
+        const transfer = [];
+        for (const k of RIVER_KEYS) if (res[k]) transfer.push(res[k].buffer);
+        parentPort.postMessage({ type: 'riversDone', ...res, _riversTiming: { workerTotal: performance.now() - tTotal0 } }, transfer);
     } catch (err) {
         parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
     }
@@ -882,6 +916,7 @@ parentPort.on('message', (data) => {
         case 'exportCubeMap': handleExportCubeMap(data); break;
         case 'exportRelief': handleExportRelief(data); break;
         case 'exportGlobe': handleExportGlobe(data); break;
+        case 'computeRivers': handleComputeRivers(data); break;
         case 'exportOverlays': handleExportOverlays(data); break;
         case 'generate': handleGenerate(data); break;
         case 'pick': handlePick(data); break;

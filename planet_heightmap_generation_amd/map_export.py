@@ -153,13 +153,17 @@ def download(planet: TP.Planet, width: int | None = None) -> np.ndarray:
     return out
 
 
-def color(planet: TP.Planet, type, r_elevation=None, width: int | None = None) -> np.ndarray:
+def color(planet: TP.Planet, type, r_elevation=None, width: int | None = None, rivers: float | None = None) -> np.ndarray:
     """The planet's region map coloured as `type`: uint8 (height, width, 4), after raster_cube (6, S, S, 4).  r_elevation None means
     the planet's resident field.  width: the width of the planet's last raster; raster and raster_cube remember the shape on the
-    planet, so it is only needed after a raster made elsewhere."""
+    planet, so it is only needed after a raster made elsewhere.  rivers: a minimum flow; the river cells that reach it and the lakes
+    of the planet's rivers block (rivers.compute_rivers) are painted over the type's colours (None: off)."""
     e = CB.elevation_arg(planet.numRegions, r_elevation)
     out = np.empty(_map_shape(planet, width) + (4,), np.uint8)
-    capi.check(capi.lib().wo_map_color(planet.handle, type_id(type), capi.ptr(e), capi.ptr(out), out.nbytes), "mapColor")
+    if rivers is None:
+        capi.check(capi.lib().wo_map_color(planet.handle, type_id(type), capi.ptr(e), capi.ptr(out), out.nbytes), "mapColor")
+    else:
+        capi.check(capi.lib().wo_map_color_rivers(planet.handle, type_id(type), capi.ptr(e), float(rivers), capi.ptr(out), out.nbytes), "mapColorRivers")
     return out
 
 
@@ -201,29 +205,30 @@ def _wanted_layers(names, layers) -> dict:
     return wanted
 
 
-def export_cube(planet: TP.Planet, mesh, types, face_size: int, r_elevation=None, layers=()) -> dict:
-    """export_map for the cube map: one raster of the six faces, one colour pass per type, then one per layer (types and layers as
-    for export_map).  -> {faceSize, covered, uncovered, maps: {name: uint8 (6, S, S, 4)}}; maps[name][f] is face FACES[f]."""
+def export_cube(planet: TP.Planet, mesh, types, face_size: int, r_elevation=None, layers=(), rivers: float | None = None) -> dict:
+    """export_map for the cube map: one raster of the six faces, one colour pass per type, then one per layer (types, layers and
+    rivers as for export_map).  -> {faceSize, covered, uncovered, maps: {name: uint8 (6, S, S, 4)}}; maps[name][f] is face FACES[f]."""
     names = [types] if isinstance(types, str) else list(types)
     wanted = _wanted_layers(names, layers)
     res = raster_cube(planet, mesh, face_size)
-    res["maps"] = {t: color(planet, t, r_elevation) for t in names}
+    res["maps"] = {t: color(planet, t, r_elevation, rivers=rivers) for t in names}
     for name, values in wanted.items():
         res["maps"][name] = color_layer(planet, name if name in LAYERS else "debug", values, r_elevation)
     del res["regionMap"]
     return res
 
 
-def export_map(planet: TP.Planet, mesh, types, width: int, r_elevation=None, layers=(), center_lon: float = 0.0) -> dict:
+def export_map(planet: TP.Planet, mesh, types, width: int, r_elevation=None, layers=(), center_lon: float = 0.0, rivers: float | None = None) -> dict:
     """exportMapBatch: one raster, one colour pass per type.  types: one name or a sequence of names.
     layers: names of LAYERS other than `debug` (read from the planet's resident blocks), or a mapping name -> values (None: the
     resident block; an array: these values, under any name that is no climate layer's coloured as `debug`); their maps follow the
-    types' in `maps`.  center_lon: the centre meridian of the raster.
+    types' in `maps`.  center_lon: the centre meridian of the raster.  rivers: a minimum flow; the types' maps get the rivers and
+    lakes of the planet's rivers block painted over them (None: off; the layers stay as they are).
     -> {width, height, covered, uncovered, maps: {name: uint8 (height, width, 4)}}"""
     names = [types] if isinstance(types, str) else list(types)
     wanted = _wanted_layers(names, layers)
     res = raster(planet, mesh, width, center_lon=center_lon)
-    res["maps"] = {t: color(planet, t, r_elevation, res["width"]) for t in names}
+    res["maps"] = {t: color(planet, t, r_elevation, res["width"], rivers) for t in names}
     for name, values in wanted.items():
         res["maps"][name] = color_layer(planet, name if name in LAYERS else "debug", values, r_elevation, res["width"])
     del res["regionMap"]

@@ -1074,6 +1074,71 @@ napi_value ReliefNormals(napi_env env, napi_callback_info info) {
     if (wo_relief_normals(p, (int32_t)s, strength, (int32_t)flags, (uint8_t*)d, (int64_t)n * 4)) return throw_wo(env, "reliefNormals");
     return out;
 }
+
+// ---- rivers and lakes (include/worogen.h: wo_compute_rivers and what reads its block) ------------------------------------------
+// computeRivers(planet, r_elevation | null, source 0 precip | 1 uniform | 2 values, values | null) -> { landCells, pits, spilledBasins,
+// endorheicBasins, lakeCells, rounds, launches }; the five fields stay on the planet
+napi_value ComputeRivers(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* e = (float*)opt_regions(a, 1, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    const double s = a.num(2);
+    if (!(s >= 0 && s <= 2 && s == (double)(int64_t)s)) { napi_throw_range_error(env, nullptr, "computeRivers: source must be 0, 1 or 2"); return nullptr; }
+    float* v = (float*)opt_regions(a, 3, napi_float32_array, p, "runoff values", false); if (!a.ok) return nullptr;
+    wo_rivers_info I{};
+    if (wo_compute_rivers(p, wo_planet_num_regions(p), e, (int32_t)s, v, &I)) return throw_wo(env, "computeRivers");
+    napi_value o; napi_create_object(env, &o);
+    set_nums(env, o, {{"landCells", (double)I.landCells}, {"pits", (double)I.pits}, {"spilledBasins", (double)I.spilledBasins}, {"endorheicBasins", (double)I.endorheicBasins},
+                      {"lakeCells", (double)I.lakeCells}, {"rounds", (double)I.rounds}, {"launches", (double)I.launches}});
+    return o;
+}
+// riversDownload(planet, key) -> Int32Array (r_river_receiver, r_river_basin), Float32Array (r_lake_level, r_river_flow) or
+// BigUint64Array (r_river_discharge)
+napi_value RiversDownload(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    char key[64]; if (!key_at(a, 1, key)) return nullptr;
+    const size_t n = (size_t)wo_planet_num_regions(p);
+    const bool i32 = !std::strcmp(key, "r_river_receiver") || !std::strcmp(key, "r_river_basin"), u64 = !std::strcmp(key, "r_river_discharge");
+    const size_t elem = u64 ? 8 : 4;
+    void* d; napi_value out = make_ta(env, u64 ? napi_biguint64_array : i32 ? napi_int32_array : napi_float32_array, n, elem, &d);
+    if (!out) return nullptr;
+    if (wo_rivers_download(p, key, d, (int64_t)(n * elem))) return throw_wo(env, "riversDownload");
+    return out;
+}
+// riverLines(planet, minFlow, r_elevation | null) -> { segments: Float32Array(count * 6), flows: Float32Array(count), count }
+napi_value RiverLines(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* e = (float*)opt_regions(a, 2, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    const size_t n = (size_t)wo_planet_num_regions(p);
+    std::vector<float> seg(6 * n + 6), flows(n + 1);
+    int64_t count = 0;
+    if (wo_river_lines(p, a.num(1), e, seg.data(), flows.data(), (int64_t)n, &count)) return throw_wo(env, "riverLines");
+    void *ds, *df;
+    napi_value s = make_ta(env, napi_float32_array, (size_t)count * 6, 4, &ds); if (!s) return nullptr;
+    napi_value f = make_ta(env, napi_float32_array, (size_t)count, 4, &df); if (!f) return nullptr;
+    std::memcpy(ds, seg.data(), (size_t)count * 24);
+    std::memcpy(df, flows.data(), (size_t)count * 4);
+    napi_value o; napi_create_object(env, &o);
+    set_prop(env, o, "segments", s); set_prop(env, o, "flows", f);
+    set_nums(env, o, {{"count", (double)count}});
+    return o;
+}
+// mapColorRivers(planet, type 0..5, r_elevation | null, minFlow, width?) -> as mapColor, the rivers under minFlow and the lakes painted
+napi_value MapColorRivers(napi_env env, napi_callback_info info) {
+    Args a(env, info); wo_planet* p = planet_at(a, 0);
+    if (!planet_ok(env, p)) return nullptr;
+    float* e = (float*)opt_regions(a, 2, napi_float32_array, p, "r_elevation", false); if (!a.ok) return nullptr;
+    const double t = a.num(1);
+    if (!(t >= 0 && t <= 5 && t == (double)(int64_t)t)) { napi_throw_range_error(env, nullptr, "mapColorRivers: type must be an integer from 0 to 5"); return nullptr; }
+    size_t bytes;
+    if (!map_bytes(a, 4, p, "mapColorRivers", &bytes)) return nullptr;
+    void* d; napi_value out = make_ta(env, napi_uint8_clamped_array, bytes, 1, &d);
+    if (!out) return nullptr;
+    if (wo_map_color_rivers(p, (int32_t)t, e, a.num(3), (uint8_t*)d, (int64_t)bytes)) return throw_wo(env, "mapColorRivers");
+    return out;
+}
 napi_value MapFree(napi_env env, napi_callback_info info) {                    // (planet)
     Args a(env, info); wo_planet* p = planet_at(a, 0);
     if (!planet_ok(env, p)) return nullptr;
@@ -1358,6 +1423,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"mapRasterCube", MapRasterCube}, {"mapDims", MapDims},
         {"reliefRaster", ReliefRaster}, {"reliefRasterCube", ReliefRasterCube}, {"reliefHeights", ReliefHeights}, {"reliefHeight16", ReliefHeight16},
         {"reliefNormals", ReliefNormals},
+        {"computeRivers", ComputeRivers}, {"riversDownload", RiversDownload}, {"riverLines", RiverLines}, {"mapColorRivers", MapColorRivers},
         {"globeMesh", GlobeMesh}, {"globeMeshPlates", GlobeMeshPlates}, {"globeLines", GlobeLines},
         {"overlayBins", OverlayBins}, {"overlayArrows", OverlayArrows},
         {"pickRegions", PickRegions}, {"pickDirectionsGlobe", PickDirectionsGlobe}, {"pickDirectionsMap", PickDirectionsMap},
