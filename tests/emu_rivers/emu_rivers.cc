@@ -102,6 +102,28 @@ void emu_rivers_compute(int32_t N, const int32_t* off, const int32_t* adj, const
     info[0] = land; info[1] = P; info[2] = spilled; info[3] = P - spilled; info[4] = lakes; info[5] = rounds; info[6] = drowned;
 }
 
+// One contraction round's two bodies on the caller's arrays, for the tests that hold the rule of a mutual choice directly (the five
+// fields cannot: whichever of the two components stays the root, the chosen passes are the same tree).
+// best[c] for c = 0 .. numPits: the lowest cell_offer over the cells of component c, NO_PASS for the drained class
+void emu_rivers_offers(int32_t N, const int32_t* off, const int32_t* adj, const float* e, const int32_t* cellPit, const int32_t* comp, int32_t numPits, uint64_t* best) {
+    for (int32_t c = 0; c <= numPits; ++c) best[c] = NO_PASS;
+    for (int32_t u = 0; u < N; ++u) {
+        if (cellPit[u] < 0) continue;
+        const int32_t cu = comp[cellPit[u]];
+        if (cu == numPits) continue;
+        const uint64_t key = cell_offer(off, adj, e, cellPit, comp, u, cu);
+        if (key < best[cu]) best[cu] = key;
+    }
+}
+// -> hook_of for root c; edge: u, v, pu, pv of the pass it recorded, all -1 when it stays a root
+int32_t emu_rivers_hook(int32_t N, const int32_t* off, const int32_t* adj, const float* e, const int32_t* cellPit, const int32_t* comp, const uint64_t* best, int32_t c,
+                        int32_t* edge) {
+    PassEdge g{-1, -1, -1, -1, 0.0f, 0.0f};
+    const int32_t to = hook_of(off, adj, e, cellPit, comp, best, N, c, &g);
+    edge[0] = g.u; edge[1] = g.v; edge[2] = g.pu; edge[3] = g.pv;
+    return to;
+}
+
 // -> the number of segments; segments: 6 floats each, flows: one each, both with room for N
 int32_t emu_rivers_lines(int32_t N, const float* xyz, const float* e, const int32_t* receiver, const int32_t* basin, const float* lake, const uint64_t* D, const float* flow,
                          double minFlow, float* segments, float* flows) {

@@ -1,6 +1,7 @@
 """Shared pieces of the rivers tests: an independent serial statement of the contract of csrc/rivers_ops.h in Python (receivers by a row
 loop, basins by following chains, spills by a literal Prim with heapq over the pass keys, W in pop order, discharge with Python
-ints), the host emulator of the same header (tests/emu_rivers), the meshes and the field builders."""
+ints), the host emulator of the same header (tests/emu_rivers), the meshes and the field builders.  The oracle takes any CSR graph
+(oracle_structure_graph, oracle_graph); oracle_structure and oracle are its kept forms on the meshes and fields named here."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,6 +20,7 @@ from conftest import REPO
 EMU_DIR = REPO / "tests" / "emu_rivers"
 FIELDS = ("r_river_receiver", "r_river_basin", "r_lake_level", "r_river_discharge", "r_river_flow")
 QUIET_NAN = 0x7FC00000
+NO_PASS = 0xFFFFFFFFFFFFFFFF
 TINT = (41, 98, 168, 255)
 MESHES = ("N256", "N2000", "N10000")
 FIELD_KINDS = ("noise", "bowl", "plateau", "allLand", "allOcean", "cone")
@@ -98,14 +100,12 @@ def quantise(runoff):
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def oracle_structure(which, kind):
-    """Steps 1 to 6 on a mesh and a field -> dict(e, land, recv2 (step 2), receiver (final), basin, lake, pits, spilled, endorheic, drowned)"""
-    _, xyz, off, adj = mesh(which)
-    e32 = field(kind, xyz)
+def oracle_structure_graph(off, adj, e):
+    """Steps 1 to 6 on any CSR graph and field -> dict(e, land, recv2 (step 2), receiver (final), basin, lake, pits, spilled, endorheic, drowned)"""
+    e32 = np.ascontiguousarray(e, np.float32)
     e = e32.tolist()
     n = len(e)
-    offl, adjl = off.tolist(), adj.tolist()
+    offl, adjl = np.asarray(off).tolist(), np.asarray(adj).tolist()
     land = [x > 0 for x in e]
     recv = [-1] * n
     for r in range(n):
@@ -188,9 +188,25 @@ def oracle_structure(which, kind):
                 spilled=len(spill_to), endorheic=len(pits) - len(spill_to), drowned=drowned)
 
 
+@functools.lru_cache(maxsize=None)
+def oracle_structure(which, kind):
+    """oracle_structure_graph on a mesh and a field of this file by their names, kept"""
+    _, xyz, off, adj = mesh(which)
+    return oracle_structure_graph(off, adj, field(kind, xyz))
+
+
 def oracle(which, kind, runoff):
     """The five fields under their keys (+ the structure's entries) for per-cell runoff values"""
-    S = oracle_structure(which, kind)
+    return oracle_discharge(oracle_structure(which, kind), runoff)
+
+
+def oracle_graph(off, adj, e, runoff):
+    """oracle on any CSR graph: (off, adj, e, runoff) arrays"""
+    return oracle_discharge(oracle_structure_graph(off, adj, e), runoff)
+
+
+def oracle_discharge(S, runoff):
+    """Step 7 on a structure"""
     n = S["e"].size
     q = quantise(runoff)
     D = [q[r] if S["land"][r] else 0 for r in range(n)]
@@ -271,6 +287,27 @@ def emu_compute(off, adj, e, source, a=None, b=None):
     emu().emu_rivers_compute(C.c_int32(n), MC.ptr(off), MC.ptr(adj), MC.ptr(e), C.c_int32(source), MC.ptr(a), MC.ptr(b), *(MC.ptr(out[k]) for k in FIELDS), MC.ptr(info))
     out["info"] = dict(zip(("landCells", "pits", "spilled", "endorheic", "lakeCells", "rounds", "drowned"), info.tolist()))
     return out
+
+
+def emu_first_round(off, adj, e, basin):
+    """The first contraction round's bodies (cell_offer, hook_of) on the basins of a structure, every pit a component of its own, the
+    pit list in ascending cell order as the emulator builds it -> (pits, best uint64 [P + 1], to int32 [P], edges int32 [P, 4]: the
+    pass root c recorded as u, v, pu, pv, -1 where it stayed a root)"""
+    off, adj, e = np.ascontiguousarray(off, np.int32), np.ascontiguousarray(adj, np.int32), np.ascontiguousarray(e, np.float32)
+    n = e.size
+    pits = np.nonzero(basin == np.arange(n))[0].astype(np.int32)
+    P = pits.size
+    index = np.full(n, -1, np.int32)
+    index[pits] = np.arange(P, dtype=np.int32)
+    cellPit = np.where(basin >= 0, index[np.maximum(basin, 0)], np.where(basin == -1, P, -1)).astype(np.int32)
+    comp = np.arange(P + 1, dtype=np.int32)
+    best = np.empty(P + 1, np.uint64)
+    emu().emu_rivers_offers(C.c_int32(n), MC.ptr(off), MC.ptr(adj), MC.ptr(e), MC.ptr(cellPit), MC.ptr(comp), C.c_int32(P), MC.ptr(best))
+    to, edges = np.empty(P, np.int32), np.empty((P, 4), np.int32)
+    emu().emu_rivers_hook.restype = C.c_int32
+    for c in range(P):
+        to[c] = emu().emu_rivers_hook(C.c_int32(n), MC.ptr(off), MC.ptr(adj), MC.ptr(e), MC.ptr(cellPit), MC.ptr(comp), MC.ptr(best), C.c_int32(c), MC.ptr(edges[c]))
+    return pits, best, to, edges
 
 
 def emu_by_source(off, adj, e, source, xyz):

@@ -2,11 +2,13 @@
 runs, under serial Boruvka rounds) against the independent serial oracle of tests/rivers_common.py (a literal Prim over the pass
 keys) in every bit of all five fields, on three meshes, six fields and the three runoff sources; and the properties of the result
 that need neither: the final receivers are a forest, the lakes are exactly the cells below their basin's level, the discharge is
-conserved, the lines are ordered and honour the threshold."""
+conserved, the lines are ordered and honour the threshold.  Then the same equality on the explicit graphs of tests/rivers_graphs.py
+(ramps, sawtooth paths, the 23-ary tree, empty rows, the hub meshes), and the properties each of those graphs is there for."""
 import numpy as np
 import pytest
 
 import rivers_common as RV
+import rivers_graphs as RG
 
 
 @pytest.mark.parametrize("kind", RV.FIELD_KINDS)
@@ -115,3 +117,128 @@ def test_properties(which, kind):
         p0 = seg[:, 0, :].astype(np.float64)
         p0 /= np.linalg.norm(p0, axis=1, keepdims=True) if cells.size else 1.0
         assert np.allclose(p0, xyz[cells].astype(np.float64), atol=1e-6)
+
+
+# ---- the explicit graphs of rivers_graphs.py -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,runoff", [c for c in RG.CASES if c[0] in RG.EMULATED])
+def test_shapes_emulator_equals_oracle(name, runoff):
+    """every shape the device is held to (tests/test_gpu_rivers_shapes.py) but the 32 769-cell ramps, on which the emulator, which
+    follows every cell's chain to its end, takes seconds: those are the oracle's alone"""
+    G = RG.shape(name)
+    got, want = RG.emulated(name, runoff), RG.reference(name, runoff)
+    RV.assert_fields_equal((name, runoff), got, want)
+    I = got["info"]
+    assert (I["pits"], I["spilled"], I["endorheic"], I["drowned"]) == (want["pits"], want["spilled"], want["endorheic"], want["drowned"]), (name, I)
+    assert I["landCells"] == int(want["land"].sum()) and I["lakeCells"] == int((~np.isnan(want["r_lake_level"])).sum())
+    kept = []
+    for min_flow in RG.thresholds(want):
+        seg, flows = RV.emu_lines(G.xyz, G.e, got, min_flow)
+        wseg, wflows = RV.oracle_lines(want, G.xyz, min_flow)
+        assert np.array_equal(RV.bits(seg), RV.bits(wseg)) and np.array_equal(RV.bits(flows), RV.bits(wflows)), (name, runoff, min_flow)
+        assert np.array_equal(RV.emu_tinted(G.e, got, min_flow), RV.oracle_tinted(want, min_flow))
+        kept.append(seg.shape[0])
+    assert kept[0] > 0 and (0 < kept[1] < kept[0] if RG.splits(want) else kept[1] == 0), (name, runoff, kept)
+
+
+@pytest.mark.parametrize("n", [4096, 4097, 4098, 8193, 32769])
+@pytest.mark.parametrize("reversed", [False, True])
+def test_ramp_is_one_chain_and_carries_into_the_high_word(n, reversed):
+    """One receiver chain over all n - 1 land cells and no pit; the ocean cell holds exactly land * q.  With runoff 16, q = 2^20: the
+    ocean cell of the 4 097-cell ramp holds 2^32 exactly, that of 8 193 cells 2^33, and the 4 096-cell ramp, with 4 095 land cells,
+    ends 2^20 short of 2^32, so the three sizes stand on both sides of the carry as they do on both sides of 2^12 hops."""
+    name = f"ramp-{n}{'-reversed' if reversed else ''}"
+    G = RG.shape(name)
+    ocean, step = (n - 1, 1) if reversed else (0, -1)
+    assert G.n == n and RG.max_degree(G) == 2 and G.e[ocean] == -1.0 and int((G.e > 0).sum()) == n - 1
+    for runoff in RG.SHAPES[name][1]:
+        O = RG.reference(name, runoff)
+        land = np.arange(n) != ocean
+        assert O["pits"] == 0 and np.array_equal(O["r_river_receiver"][land], np.arange(n)[land] + step) and O["r_river_receiver"][ocean] == -1
+        assert (O["r_river_basin"][land] == -1).all()
+        q = (16 if runoff == "max" else 1) << 16
+        D = O["r_river_discharge"]
+        assert int(D[ocean]) == (n - 1) * q == int(D.max())
+        hops = np.abs(np.arange(n) - ocean)                   # a land cell holds what falls on it and on the cells above it
+        assert np.array_equal(D[land], ((n - hops[land]) * q).astype(np.uint64))
+        if runoff == "max":
+            assert int(D[ocean]) >= 2 ** 32 if n >= 4097 else int(D[ocean]) == 2 ** 32 - 2 ** 20
+        if n == 8193 and runoff == "max":
+            assert int(D[ocean]) == 2 ** 33
+
+
+@pytest.mark.parametrize("P", [4096, 16384])
+def test_sawtooth_rounds_and_spills(P):
+    """what each order of the pass levels is for: the emulator's round count, every basin spilled, some drowned"""
+    want_rounds = dict(asc=lambda r: r == 1, desc=lambda r: r == 2, pairs=lambda r: r == 2, ruler=lambda r: r >= 10, random=lambda r: r >= 5)
+    for kind in (RG.SAW_KINDS if P == 4096 else ("asc", "ruler")):
+        name = f"saw-{kind}-{P}"
+        G, O, I = RG.shape(name), RG.reference(name, "max"), RG.emulated(name, "max")["info"]
+        print(name, I, "max D 2^%.2f" % np.log2(float(O["r_river_discharge"].max())))
+        assert G.n == 2 * P + 1
+        passes, floors = G.e[1::2], G.e[2::2]
+        assert (passes > 1).all() and (passes <= 2).all() and (floors >= 0.5).all() and (floors < 0.75).all() and np.unique(passes).size == P
+        assert O["pits"] == O["spilled"] == P and O["endorheic"] == 0 and O["drowned"] > 0, (name, O["pits"], O["spilled"], O["drowned"])
+        assert want_rounds[kind](I["rounds"]), (name, I)
+        assert int(O["r_river_discharge"].max()) == (2 * P) << 20 >= 2 ** 32      # all of it reaches the ocean cell
+    # asc is one chain of P hooks: basin k spills into basin k - 1, the first over pass 1 to the drained pass cell
+    O = RG.reference(f"saw-asc-{P}", "max")
+    pits = np.arange(2, 2 * P + 1, 2)
+    assert np.array_equal(O["r_river_receiver"][pits], pits - 1 - (O["r_river_basin"][pits - 1] == pits))
+    # pairs: basins 2 j and 2 j + 1 share the low pass 2 j + 1 and chose each other in the first round
+    if P == 4096:
+        e = RG.shape("saw-pairs-4096").e[1::2]
+        assert e[0::2].max() < e[1::2].min()
+
+
+def test_mutual_choice_keeps_the_lower_component_as_root():
+    """On the pairs sawtooth basins 2 j and 2 j + 1 (pit-list indices 2 j - 1 and 2 j) choose the pass between them in the first round.
+    rivers_ops.h: the lower id stays a root, the higher hooks to it and records the pass with u on its own side.  The five fields
+    cannot hold this rule (either root gives the same tree), so hook_of is called directly."""
+    P = 64
+    G = RG.sawtooth(P, "pairs")
+    S = RV.oracle_structure_graph(G.off, G.adj, G.e)
+    pits, best, to, edges = RV.emu_first_round(G.off, G.adj, G.e, S["basin"])
+    assert np.array_equal(pits, np.arange(2, 2 * P + 1, 2)) and best[P] == np.uint64(RV.NO_PASS) and (best[:P] != np.uint64(RV.NO_PASS)).all()
+    # basin 1 (index 0) hooks to the drained class over pass 1, from its own cell 2 or 1 to the drained cell
+    assert to[0] == P and edges[0, 2] == 0 and edges[0, 3] == P and S["basin"][edges[0, 0]] == 2 and S["basin"][edges[0, 1]] == -1
+    for lo in range(1, P - 1, 2):
+        hi = lo + 1
+        assert best[lo] == best[hi], (lo, hi)
+        assert to[lo] == lo and (edges[lo] == -1).all(), (lo, to[lo], edges[lo])
+        assert to[hi] == lo and edges[hi, 2] == hi and edges[hi, 3] == lo, (hi, to[hi], edges[hi])
+        u, v = edges[hi, 0], edges[hi, 1]
+        assert S["basin"][u] == pits[hi] and S["basin"][v] == pits[lo] and abs(int(u) - int(v)) == 1 and max(G.e[u], G.e[v]) == G.e[2 * hi + 1]
+    assert to[P - 1] == P - 2 and best[P - 1] != best[P - 2]  # the last basin has one pass only, which its neighbour did not choose
+
+
+def test_tree_rows_and_donors():
+    G = RG.shape("tree-23-3")
+    assert G.n == 12721 and RG.max_degree(G) == 24
+    O = RG.reference("tree-23-3", "max")
+    donors = np.bincount(O["r_river_receiver"][O["r_river_receiver"] >= 0], minlength=G.n)
+    assert O["pits"] == 0 and int((donors == 23).sum()) == 1 + 23 + 529 and donors[0] == 1
+    D = O["r_river_discharge"]
+    assert int(D[0]) == 12720 << 20 == int(D.max()) and int(D[0]) >= 2 ** 33
+    assert int(D[1]) == 12720 << 20 and (D[2:25] == np.uint64(553 << 20)).all()
+
+
+def test_isolated_cells_have_empty_rows():
+    G = RG.shape("isolated")
+    O = RG.reference("isolated", "max")
+    deg = np.diff(G.off)
+    assert G.n == 602 and np.array_equal(np.nonzero(deg == 0)[0], [0, 601]) and G.e[0] > 0 and G.e[601] < 0
+    assert (O["pits"], O["spilled"], O["endorheic"]) == (1, 0, 1) and O["r_river_basin"][0] == 0 and O["r_river_basin"][601] == -2
+    assert int(O["r_river_discharge"][0]) == 16 << 16 and int(O["r_river_discharge"][601]) == 0
+
+
+def test_hub_forms_are_three_orders_of_one_graph():
+    built, permuted, shuffled = (RG.shape(f"hub-{f}-e0") for f in ("built", "permuted", "shuffled"))
+    for G in (built, permuted, shuffled):
+        assert RG.max_degree(G) == 24
+    assert np.array_equal(built.off, shuffled.off) and not np.array_equal(built.adj, shuffled.adj)
+    rows = lambda G, r: sorted(G.adj[G.off[r]:G.off[r + 1]].tolist())
+    assert all(rows(built, r) == rows(shuffled, r) for r in range(0, built.n, 37))
+    assert not np.array_equal(built.off, permuted.off) and np.array_equal(np.sort(built.e), np.sort(permuted.e))
+    for form in ("built", "permuted", "shuffled"):            # relabelling and row order move ties and slots, not the count of land
+        assert RG.reference(f"hub-{form}-bowl", "uniform")["pits"] > 2000 and RG.emulated(f"hub-{form}-bowl", "uniform")["info"]["rounds"] >= 3
+        assert int(RG.reference(f"hub-{form}-bowl", "values")["r_river_discharge"].max()) >= 2 ** 32
