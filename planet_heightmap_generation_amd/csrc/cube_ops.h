@@ -1,4 +1,4 @@
-// Cube-map export: the per-vertex, per-side and per-pixel bodies shared by the device kernels (cube.hip) and the test-only CPU
+// Cube-map export: the per-vertex, per-side and per-pixel bodies shared by the device kernels (cube.hip, raster.hip) and the test-only CPU
 // emulator (tests/emu_cube), so that both compile the very same arithmetic.  The library compiles with -ffp-contract=off: no FMA
 // changes a result, and nothing here calls libm beyond floor / ceil / fmin / fmax.  Ours: the reference exports no cube map.
 //
@@ -110,6 +110,32 @@ WO_IMP_HD inline bool tri_box(const map::Tri& t, double area2, int32_t S, map::B
 
 // where pixel (i, j) of face f lies in the S x 6S map
 WO_IMP_HD inline int64_t pixel_index(int32_t f, int32_t i, int32_t j, int32_t S) { return ((int64_t)f * S + j) * (int64_t)S + i; }
+
+// The gnomonic projection as the shared raster (raster.hip) and the height pass (relief.hip) take it: the centres, the resident
+// positions, the face size and the functions above under the names of map::Projection.  A side yields at most PIECES triangles: one
+// per axis k, on the face in front of which the side's first vertex lies (ma > 0 holds on at most one face per axis).
+struct Projection {
+    static constexpr int PIECES = 3;
+    using Side = float[3][3];                                 // a side's vertices: 3 floats each
+    const float* t_xyz;
+    const float* r_xyz;
+    int32_t S;
+    WO_IMP_HD int64_t pixels() const { return (int64_t)FACE_COUNT * S * S; }
+    // fetches side s; returns how many pieces it has
+    WO_IMP_HD int vertices(const int32_t* triangles, const int32_t* halfedges, int64_t s, Side& v) const {
+        side_vertices(triangles, halfedges, t_xyz, r_xyz, s, v);
+        return PIECES;
+    }
+    // piece k of a side: its face, its triangle there, tri_area2 of it and its clipped box; false where nothing is drawn
+    WO_IMP_HD bool piece(const Side& v, int k, map::Tri& t, double& area2, map::Box& b, int32_t& f) const {
+        f = face_of_axis(k, v[0][k]);
+        if (!side_on_face(v, f, t)) return false;
+        area2 = map::tri_area2(t);
+        return tri_box(t, area2, S, b);
+    }
+    WO_IMP_HD void center(int32_t i, int32_t j, double& xc, double& yc) const { xc = pixel_c(i, S); yc = pixel_c(j, S); }
+    WO_IMP_HD int64_t index(int32_t f, int32_t i, int32_t j) const { return pixel_index(f, i, j, S); }      // in the side map
+};
 
 // the direction of the centre of pixel (i, j) of face f: the major axis is +-1, the other two come from ac and bc through the table
 WO_IMP_HD inline void cube_direction(int32_t f, int64_t i, int64_t j, int32_t S, double d[3]) {

@@ -3,36 +3,25 @@
 // per-vertex, per-side, per-pixel and per-region bodies and the contract are in map_ops.h; everything runs on the planet's
 // resident positions, elevation and Koppen block, on its stream.
 //
-// Launches of wo_map_raster (no host round trip between them; the stream is waited for once, at the end):
+// wo_map_raster is the raster of raster.hip (its launches are listed there) under map::Projection, in the map_* families, with the
+// map's two tables:
 //   k_map_region_lonlat [1]   longitude and latitude of every region, one thread each
 //   k_map_center_lonlat [1]   the same of every triangle centre: 3 N evaluations of atan2 / asin in all, not 18 N
-//   k_map_fill [1]            the side map (u32 per pixel) := no side
-//   k_map_sides [1]           forward rasterisation, one lane per side: the side's one or two triangles; a pixel box of at most
-//                             SMALL_BOX pixels is walked by the lane itself, atomicMin of the side index into the side map; a
-//                             larger one (the pole fan, the triangles at region N, the seam: thousands of pixels wide) is appended
-//                             to a list
-//   k_map_big_boxes [1]       one workgroup per listed triangle at a time, its threads stride over the box; the grid is fixed and
-//                             strides over the list, whose length never comes back to the host
-//   k_map_resolve [1]         side -> region (triangles[s], or -1) into the planet's region map, and the covered / uncovered counts
-//                             (block_ops.h: block_add_to_global)
-// The lowest covering side index wins, so the map does not depend on the order in which lanes, workgroups or launches arrive.
+// wo_map_raster_centered is the same raster around a centre meridian (the map view's, map_layer_ops.h): the two table kernels are
+// the <true> instances, which take centerLon through lonlat_of_centered; every other launch is wo_map_raster's.
+// wo_relief_raster is wo_map_raster_centered with a request: after k_map_resolve, while the side map and the two tables still live,
+// relief_heights (relief.hip) adds its height pass; the launches above are the same and so are the region map and the counts.
 // Launches of wo_map_color and wo_map_color_layer: the region colours of view_colors.hip, one packed RGBA per region [1-2], then
 // k_map_pixels [1] (region map -> RGBA8, four pixels per thread).
-// wo_map_raster_centered is the same raster around a centre meridian (the map view's, map_layer_ops.h): the two table kernels take
-// centerLon (k_map_region_lonlat_centered, k_map_center_lonlat_centered), every other launch is wo_map_raster's.
-// wo_relief_raster (relief.hip) is wo_map_raster_centered with a request: after k_map_resolve, while the side map and the two tables
-// still live, relief_heights_map adds its height pass; the launches above are the same and so are the region map and the counts.
 // Memory (device_mem.h): the region map lives in a block with an arena of its own on the planet (map_block.h; int32 per pixel; a
-// raster at another width or height, wo_map_raster_cube's included, replaces it, wo_map_free and wo_planet_destroy drop it);
-// triangles, half-edges, both longitude / latitude tables, the side map, the list and the colour tables are temporaries of the call,
-// in an arena on its stack.
+// raster at another width or height, wo_map_raster_cube's included, replaces it, wo_map_free and wo_planet_destroy drop it); the
+// colour tables are temporaries of the call, in an arena on its stack.
 #include <hip/hip_runtime.h>
 
 #include <memory>
 #include <string>
 
 #include "../../include/worogen.h"
-#include "block_ops.h"
 #include "device.h"
 #include "map_block.h"
 #include "map_layer_ops.h"
@@ -47,94 +36,23 @@ namespace M = wo::map;
 
 namespace wo {
 
-constexpr int MAP_BIG_GRID = 4096;                            // workgroups of k_map_big_boxes
-
-__global__ __launch_bounds__(WO_BLOCK) void k_map_region_lonlat(const float* __restrict__ xyz, M::LonLat* __restrict__ out, int32_t N) {
+// the two tables; Centered: around a centre meridian (centerLon is not read otherwise)
+template <bool Centered>
+__global__ __launch_bounds__(WO_BLOCK) void k_map_region_lonlat(const float* __restrict__ xyz, M::LonLat* __restrict__ out, int32_t N, double centerLon) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < N) out[r] = M::lonlat_of(xyz[3 * (int64_t)r], xyz[3 * (int64_t)r + 1], xyz[3 * (int64_t)r + 2]);
+    if (r >= N) return;
+    const float x = xyz[3 * (int64_t)r], y = xyz[3 * (int64_t)r + 1], z = xyz[3 * (int64_t)r + 2];
+    if constexpr (Centered) out[r] = M::lonlat_of_centered(x, y, z, centerLon);
+    else out[r] = M::lonlat_of(x, y, z);
 }
 
+template <bool Centered>
 __global__ __launch_bounds__(WO_BLOCK) void k_map_center_lonlat(const int32_t* __restrict__ triangles, const float* __restrict__ xyz, M::LonLat* __restrict__ out,
-                                                                int32_t numTriangles) {
+                                                                int32_t numTriangles, double centerLon) {
     const int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < numTriangles) out[t] = M::lonlat_of_center(triangles, xyz, t);
-}
-
-// the same two tables around a centre meridian
-__global__ __launch_bounds__(WO_BLOCK) void k_map_region_lonlat_centered(const float* __restrict__ xyz, M::LonLat* __restrict__ out, int32_t N, double centerLon) {
-    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < N) out[r] = M::lonlat_of_centered(xyz[3 * (int64_t)r], xyz[3 * (int64_t)r + 1], xyz[3 * (int64_t)r + 2], centerLon);
-}
-__global__ __launch_bounds__(WO_BLOCK) void k_map_center_lonlat_centered(const int32_t* __restrict__ triangles, const float* __restrict__ xyz, M::LonLat* __restrict__ out,
-                                                                         int32_t numTriangles, double centerLon) {
-    const int32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < numTriangles) out[t] = M::lonlat_of_center_centered(triangles, xyz, t, centerLon);
-}
-
-__global__ __launch_bounds__(WO_BLOCK) void k_map_fill(uint32_t* __restrict__ sideMap, int64_t pixels) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (int64_t)gridDim.x * blockDim.x) sideMap[i] = M::NO_SIDE;
-}
-
-// the pixels of box b that triangle t covers take min(side index)
-__device__ inline void map_cover_pixel(const M::Tri& t, double area2, int32_t W, int32_t H, int32_t i, int32_t j, uint32_t s, uint32_t* sideMap) {
-    if (M::tri_covers(t, area2, M::pixel_xc(i, W), M::pixel_yc(j, H))) atomicMin(sideMap + ((int64_t)j * W + i), s);
-}
-
-__global__ __launch_bounds__(WO_BLOCK) void k_map_sides(const int32_t* __restrict__ triangles, const int32_t* __restrict__ halfedges, const M::LonLat* __restrict__ t_ll,
-                                                        const M::LonLat* __restrict__ r_ll, int32_t numSides, int32_t W, int32_t H, uint32_t* sideMap,
-                                                        uint32_t* __restrict__ bigList, uint32_t* bigCount) {
-    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < numSides; s += (int64_t)gridDim.x * blockDim.x) {
-        M::LonLat v[3];
-        M::side_vertices(triangles, halfedges, t_ll, r_ll, s, v);
-        M::Tri tri[2];
-        const int n = M::side_triangles(v, tri);
-        for (int k = 0; k < n; ++k) {
-            const double area2 = M::tri_area2(tri[k]);
-            M::Box b;
-            if (!M::tri_box(tri[k], area2, W, H, b)) continue;
-            if (M::box_pixels(b) > M::SMALL_BOX) {                  // at most 2 * numSides entries: the list's size
-                bigList[atomicAdd(bigCount, 1u)] = (uint32_t)s * 2u + (uint32_t)k;
-                continue;
-            }
-            for (int32_t j = b.j0; j <= b.j1; ++j)
-                for (int32_t i = b.i0; i <= b.i1; ++i) map_cover_pixel(tri[k], area2, W, H, i, j, (uint32_t)s, sideMap);
-        }
-    }
-}
-
-__global__ __launch_bounds__(WO_BLOCK) void k_map_big_boxes(const int32_t* __restrict__ triangles, const int32_t* __restrict__ halfedges, const M::LonLat* __restrict__ t_ll,
-                                                            const M::LonLat* __restrict__ r_ll, int32_t W, int32_t H, uint32_t* sideMap,
-                                                            const uint32_t* __restrict__ bigList, const uint32_t* __restrict__ bigCount) {
-    const uint32_t count = *bigCount;
-    for (uint32_t e = blockIdx.x; e < count; e += gridDim.x) {
-        const uint32_t code = bigList[e], s = code >> 1;
-        M::LonLat v[3];
-        M::side_vertices(triangles, halfedges, t_ll, r_ll, s, v);
-        M::Tri tri[2];
-        M::side_triangles(v, tri);
-        const M::Tri& t = tri[code & 1u];
-        const double area2 = M::tri_area2(t);
-        M::Box b;
-        if (!M::tri_box(t, area2, W, H, b)) continue;
-        const int64_t bw = b.i1 - b.i0 + 1, n = M::box_pixels(b);
-        for (int64_t q = threadIdx.x; q < n; q += blockDim.x)
-            map_cover_pixel(t, area2, W, H, b.i0 + (int32_t)(q % bw), b.j0 + (int32_t)(q / bw), s, sideMap);
-    }
-}
-
-// counts[0] += covered pixels
-__global__ __launch_bounds__(WO_BLOCK) void k_map_resolve(const uint32_t* __restrict__ sideMap, const int32_t* __restrict__ triangles, int32_t* __restrict__ region,
-                                                          int64_t pixels, unsigned long long* counts) {
-    __shared__ unsigned long long blockCovered[1];
-    if (threadIdx.x == 0) blockCovered[0] = 0;
-    __syncthreads();
-    unsigned long long covered[1] = {0};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pixels; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t s = sideMap[i];
-        region[i] = s == M::NO_SIDE ? -1 : triangles[s];
-        covered[0] += s != M::NO_SIDE;
-    }
-    block_add_to_global<1>(covered, blockCovered, counts);
+    if (t >= numTriangles) return;
+    if constexpr (Centered) out[t] = M::lonlat_of_center_centered(triangles, xyz, t, centerLon);
+    else out[t] = M::lonlat_of_center(triangles, xyz, t);
 }
 
 // four pixels per thread: one 16-byte load of region ids, four gathers from the colour table, one 16-byte store
@@ -177,53 +95,29 @@ static bool map_width_ok(int32_t width) { return width >= 2 && width <= 32768 &&
 
 using namespace wo;
 
-// wo_map_raster (centered == false: its own two table kernels), wo_map_raster_centered and, with a request, wo_relief_raster
-int wo::map_raster(wo_planet* p, const char* fn, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, bool centered, double centerLon,
-                   int32_t* regionMapOut, int64_t counts[2], const ReliefRequest* relief) {
+// wo_map_raster (centered == false: the plain table kernels), wo_map_raster_centered and, with a request, wo_relief_raster: the checks
+// of the width and the centre, and the raster of raster.hip with the map's tables and families
+static int map_raster(wo_planet* p, const char* fn, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, bool centered, double centerLon,
+                      int32_t* regionMapOut, int64_t counts[2], const ReliefRequest* relief) {
     const std::string F = std::string(fn) + ": ";
     if (!check_planet(p, fn)) return 1;
     if (!map_width_ok(width)) { set_error(F + "width is " + std::to_string(width) + ", it must be even and from 2 to 32768"); return 1; }
     if (centered && !M::center_lon_ok(centerLon)) { set_error(F + "centerLon is " + std::to_string(centerLon) + ", it must be finite and from -pi to pi"); return 1; }
-    if (!sides_ok(fn, p, numSides, triangles, halfedges)) return 1;
-    WO_TRY
-        const int32_t W = width, H = width / 2, N = p->N, numTriangles = numSides / 3;
-        const int64_t pixels = (int64_t)W * H;
-        hipStream_t s = p->ctx->stream;
-        auto* B = map_block_for(p, W, H);
-        B->centerLon = centered ? centerLon : 0.0;
-        DeviceArena T;                                        // the temporaries of this call
-        const int32_t* d_tri = up(T, triangles, (size_t)numSides, s);
-        const int32_t* d_he = up(T, halfedges, (size_t)numSides, s);
-        M::LonLat* r_ll = T.dev<M::LonLat>((size_t)N);
-        M::LonLat* t_ll = T.dev<M::LonLat>((size_t)numTriangles);
-        uint32_t* sideMap = T.dev<uint32_t>((size_t)pixels);
-        uint32_t* bigList = T.dev<uint32_t>(2 * (size_t)numSides);
-        unsigned long long* d_counts = T.dev<unsigned long long>(2);      // [0] covered pixels, [1] (as u32) the length of bigList
-        unsigned long long* h_counts = T.pinned<unsigned long long>(2);
-        uint32_t* bigCount = reinterpret_cast<uint32_t*>(d_counts + 1);
-        WO_HIP(hipMemsetAsync(d_counts, 0, 16, s));
-        if (centered) {
-            launch(p, FAM_MAP_LONLAT, k_map_region_lonlat_centered, blocks_for(N), WO_BLOCK, (const float*)p->d_xyz, r_ll, N, centerLon);
-            launch(p, FAM_MAP_LONLAT, k_map_center_lonlat_centered, blocks_for(numTriangles), WO_BLOCK, d_tri, (const float*)p->d_xyz, t_ll, numTriangles, centerLon);
-        } else {
-            launch(p, FAM_MAP_LONLAT, k_map_region_lonlat, blocks_for(N), WO_BLOCK, (const float*)p->d_xyz, r_ll, N);
-            launch(p, FAM_MAP_LONLAT, k_map_center_lonlat, blocks_for(numTriangles), WO_BLOCK, d_tri, (const float*)p->d_xyz, t_ll, numTriangles);
-        }
-        launch(p, FAM_MAP_FILL, k_map_fill, blocks_for(pixels, 1 << 14), WO_BLOCK, sideMap, pixels);
-        launch(p, FAM_MAP_SIDES, k_map_sides, blocks_for(numSides), WO_BLOCK, d_tri, d_he, (const M::LonLat*)t_ll, (const M::LonLat*)r_ll, numSides, W, H, sideMap, bigList, bigCount);
-        launch(p, FAM_MAP_BIG_BOXES, k_map_big_boxes, MAP_BIG_GRID, WO_BLOCK, d_tri, d_he, (const M::LonLat*)t_ll, (const M::LonLat*)r_ll, W, H, sideMap, (const uint32_t*)bigList,
-               (const uint32_t*)bigCount);
-        launch(p, FAM_MAP_RESOLVE, k_map_resolve, blocks_for(pixels, 1 << 14), WO_BLOCK, (const uint32_t*)sideMap, d_tri, B->region, pixels, d_counts);
-        if (relief) relief_heights_map(p, T, B, *relief, d_tri, d_he, numTriangles, t_ll, r_ll, sideMap);
-        WO_HIP(hipMemcpyAsync(h_counts, d_counts, 16, hipMemcpyDeviceToHost, s));
-        if (regionMapOut) WO_HIP(hipMemcpyAsync(regionMapOut, B->region, (size_t)pixels * 4, hipMemcpyDeviceToHost, s));
-        WO_HIP(hipStreamSynchronize(s));                      // before T frees the temporaries
-        B->valid = true;
-        B->heightValid = relief != nullptr;
-        B->heightCube = false;
-        if (counts) { counts[0] = (int64_t)h_counts[0]; counts[1] = pixels - (int64_t)h_counts[0]; }
-        return 0;
-    WO_CATCH(fn)
+    const int32_t W = width, H = width / 2, N = p->N, numTriangles = numSides / 3;
+    M::LonLat *r_ll = nullptr, *t_ll = nullptr;
+    const auto tables = [&](DeviceArena& T) {
+        r_ll = T.dev<M::LonLat>((size_t)N);
+        t_ll = T.dev<M::LonLat>((size_t)numTriangles);
+        return M::Projection{t_ll, r_ll, W, H};
+    };
+    const auto launchTables = [&](const int32_t* d_tri) {
+        launch(p, FAM_MAP_LONLAT, centered ? k_map_region_lonlat<true> : k_map_region_lonlat<false>, blocks_for(N), WO_BLOCK, (const float*)p->d_xyz, r_ll, N, centerLon);
+        launch(p, FAM_MAP_LONLAT, centered ? k_map_center_lonlat<true> : k_map_center_lonlat<false>, blocks_for(numTriangles), WO_BLOCK, d_tri, (const float*)p->d_xyz, t_ll,
+               numTriangles, centerLon);
+    };
+    return raster<M::Projection>(p, fn, numSides, triangles, halfedges,
+                                 {W, H, centered ? centerLon : 0.0, false, FAM_MAP_FILL, FAM_MAP_SIDES, FAM_MAP_BIG_BOXES, FAM_MAP_RESOLVE, tables, launchTables}, regionMapOut, counts,
+                                 relief);
 }
 
 // wo_map_color and wo_map_color_layer: the request's checks around those of the region map (`rasters`: the calls that give one, as the
@@ -275,6 +169,12 @@ int wo_map_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, cons
 int wo_map_raster_centered(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, double centerLon, int32_t* regionMapOut,
                            int64_t counts[2]) {
     return map_raster(p, "wo_map_raster_centered", numSides, triangles, halfedges, width, true, centerLon, regionMapOut, counts, nullptr);
+}
+
+int wo_relief_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, double centerLon, const float* r_elevation,
+                     float* heightOut, int64_t counts[2]) {
+    const ReliefRequest q{r_elevation, heightOut};
+    return map_raster(p, "wo_relief_raster", numSides, triangles, halfedges, width, true, centerLon, nullptr, counts, &q);
 }
 
 int wo_map_color(wo_planet* p, int32_t type, const float* r_elevation, uint8_t* rgbaOut, int64_t outBytes) {

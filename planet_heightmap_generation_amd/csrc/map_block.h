@@ -1,13 +1,13 @@
-// The map block of a planet and the two raster launches that the equirectangular export (map.hip) and the cube-map export (cube.hip)
-// share: both leave a W x H region map in the same block, so that the colouring, the download and wo_map_free serve either.  The
-// relief export (relief.hip) runs the same two rasters and adds a height map of the same shape to the block.
+// The map block of a planet and the one raster (raster.hip) that the equirectangular export (map.hip) and the cube-map export
+// (cube.hip) run: both leave a W x H region map in the same block, so that the colouring, the download and wo_map_free serve either.
+// The relief export (relief.hip) is the same raster with a request, which adds a height map of the same shape to the block.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
 
 #include "device.h"
-#include "map_ops.h"
 
 struct wo_map_block {
     wo::DeviceArena mem;
@@ -27,27 +27,35 @@ namespace wo {
 // new one (the old map goes first; the planet gets the new block once it is complete)
 WO_LOCAL wo_map_block* map_block_for(wo_planet* p, int32_t W, int32_t H);
 
-// map.hip: the side map (u32 per pixel) := no side
-__global__ void k_map_fill(uint32_t* __restrict__ sideMap, int64_t pixels);
-// map.hip: side -> region (triangles[s], or -1) and counts[0] += covered pixels
-__global__ void k_map_resolve(const uint32_t* __restrict__ sideMap, const int32_t* __restrict__ triangles, int32_t* __restrict__ region, int64_t pixels, unsigned long long* counts);
-
-// A relief raster's request to the two rasters below: the elevation to interpolate (the caller's host pointer, NULL: the resident
-// field) and where the height map goes on the host (may be NULL)
+// A relief raster's request to the raster below: the elevation to interpolate (the caller's host pointer, NULL: the resident field)
+// and where the height map goes on the host (may be NULL)
 struct ReliefRequest { const float* r_elevation; float* heightOut; };
 
-// map.hip, cube.hip: the bodies of wo_map_raster / wo_map_raster_centered and of wo_map_raster_cube under the entry point's name;
-// with a request, the height pass of relief.hip runs after k_map_resolve, while the side map and the vertex tables still live
-WO_LOCAL int map_raster(wo_planet* p, const char* fn, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, bool centered, double centerLon,
-                        int32_t* regionMapOut, int64_t counts[2], const ReliefRequest* relief);
-WO_LOCAL int cube_raster(wo_planet* p, const char* fn, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t faceSize, int32_t* regionMapOut,
-                         int64_t counts[2], const ReliefRequest* relief);
+// What tells one raster from another, next to its projection P (map::Projection, cube::Projection): the block's shape and centre
+// meridian, whether a height map left in the block is a cube's, the profiling families of the four shared launches, and the
+// projection's vertex tables: `tables` allocates them in the call's arena and returns the projection, `launchTables` launches their
+// kernels (in a family of its own) from the uploaded triangles.  Two steps, because every allocation of a raster comes before its
+// first launch: the stream does not wait for the allocator between two launches.
+template <class P> struct RasterKind {
+    int32_t W, H;
+    double centerLon;
+    bool heightCube;
+    int famFill, famSides, famBigBoxes, famResolve;
+    std::function<P(DeviceArena& T)> tables;
+    std::function<void(const int32_t* d_tri)> launchTables;
+};
+
+// raster.hip: the body of every raster entry point, under the entry point's name, after the checks of its own arguments: the checks
+// of the sides, the uploads, the tables, fill, sides, big boxes and resolve into the block, the counts.  With a request, the height
+// pass runs after the resolve, while the side map and the tables still live.  Instantiated for the two projections.
+template <class P>
+WO_LOCAL int raster(wo_planet* p, const char* fn, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, const RasterKind<P>& kind, int32_t* regionMapOut,
+                    int64_t counts[2], const ReliefRequest* relief);
 
 // relief.hip: the height pass into B->height on the planet's stream (T: the raster's arena, for the triangle elevations and the
-// caller's field); the raster marks the height map valid once the stream has been waited for
-WO_LOCAL void relief_heights_map(wo_planet* p, DeviceArena& T, wo_map_block* B, const ReliefRequest& q, const int32_t* d_tri, const int32_t* d_he, int32_t numTriangles,
-                                 const map::LonLat* t_ll, const map::LonLat* r_ll, const uint32_t* sideMap);
-WO_LOCAL void relief_heights_cube(wo_planet* p, DeviceArena& T, wo_map_block* B, const ReliefRequest& q, const int32_t* d_tri, const int32_t* d_he, int32_t numTriangles,
-                                  const float* t_xyz, const uint32_t* sideMap);
+// caller's field); the raster marks the height map valid once the stream has been waited for.  Instantiated for the two projections.
+template <class P>
+WO_LOCAL void relief_heights(wo_planet* p, DeviceArena& T, wo_map_block* B, const ReliefRequest& q, const P& proj, const int32_t* d_tri, const int32_t* d_he, int32_t numTriangles,
+                             const uint32_t* sideMap);
 
 }  // namespace wo

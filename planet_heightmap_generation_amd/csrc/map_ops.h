@@ -1,5 +1,5 @@
 // Equirectangular map export (the reference's exportMap / exportMapBatch, js/planet-mesh.js:1752-2180): the per-vertex, per-side,
-// per-pixel and per-region bodies shared by the device kernels (map.hip) and the test-only CPU emulator (tests/emu_map), so that
+// per-pixel and per-region bodies shared by the device kernels (map.hip, raster.hip) and the test-only CPU emulator (tests/emu_map), so that
 // both compile the very same arithmetic.  The library compiles with -ffp-contract=off: no FMA changes a result.
 //
 // The reference draws its map triangles with WebGL, whose rasteriser (sub-pixel snapping, fill rule, float-to-UNORM rounding)
@@ -140,6 +140,33 @@ WO_IMP_HD inline void side_vertices(const int32_t* triangles, const int32_t* hal
     v[1] = t_ll[halfedges[s] / 3];
     v[2] = r_ll[triangles[s]];
 }
+
+// The equirectangular projection as the shared raster (raster.hip) and the height pass (relief.hip) take it: the two tables, the size
+// and the functions above under the names that cube::Projection (cube_ops.h) gives its own.  A side yields at most PIECES triangles:
+// its triangle and, where it wraps, the seam copy.
+struct Projection {
+    static constexpr int PIECES = 2;
+    using Side = Tri[PIECES];                                 // a side's vertices, as side_triangles leaves them
+    const LonLat* t_ll;
+    const LonLat* r_ll;
+    int32_t W, H;
+    WO_IMP_HD int64_t pixels() const { return (int64_t)W * H; }
+    // fetches side s; returns how many pieces it has
+    WO_IMP_HD int vertices(const int32_t* triangles, const int32_t* halfedges, int64_t s, Side& v) const {
+        LonLat ll[3];
+        side_vertices(triangles, halfedges, t_ll, r_ll, s, ll);
+        return side_triangles(ll, v);
+    }
+    // piece k of a side: its triangle, tri_area2 of it and its clipped box; false where nothing is drawn.  The map has one face, 0.
+    WO_IMP_HD bool piece(const Side& v, int k, Tri& t, double& area2, Box& b, int32_t& f) const {
+        t = v[k];
+        area2 = tri_area2(t);
+        f = 0;
+        return tri_box(t, area2, W, H, b);
+    }
+    WO_IMP_HD void center(int32_t i, int32_t j, double& xc, double& yc) const { xc = pixel_xc(i, W); yc = pixel_yc(j, H); }
+    WO_IMP_HD int64_t index(int32_t, int32_t i, int32_t j) const { return (int64_t)j * W + i; }      // in the side map
+};
 
 // ---- colours ----------------------------------------------------------------------------------------------------------------
 struct Rgb { float r, g, b; };

@@ -1,14 +1,13 @@
 // Relief export on the device: a smooth height per pixel of the equirectangular map or of the cube map, its 16-bit encoding and the
 // normals of the displaced surface.  The per-pixel bodies and the contract are in relief_ops.h.
 //
-// wo_relief_raster and wo_relief_raster_cube run the rasters of map.hip and cube.hip launch for launch (map_block.h: map_raster,
-// cube_raster), so the region map and its counts are those of wo_map_raster_centered and wo_map_raster_cube; after k_map_resolve,
-// while the side map and the vertex tables still live, they add
+// wo_relief_raster (map.hip) and wo_relief_raster_cube (cube.hip) run the raster of raster.hip launch for launch, so the region map
+// and its counts are those of wo_map_raster_centered and wo_map_raster_cube; after k_map_resolve, while the side map and the
+// projection's tables still live, relief_heights adds
 //   k_relief_tri_elevation [1]   the elevation of every triangle centre (globe::triangle_elevation), 4 bytes per triangle
-//   k_relief_heights_map [1]  or
-//   k_relief_heights_cube [1]    one pixel per thread: the side from the side map, its triangle rebuilt with the very functions the
+//   k_relief_heights<P> [1]      one pixel per thread: the side from the side map, its triangle rebuilt with the very functions the
 //                                raster used, the interpolated elevation into the block's height map (f32 per pixel).  Bound by its
-//                                gathers, as k_map_sides is: three vertex records and three elevations per pixel.
+//                                gathers, as k_raster_sides is: three vertex records and three elevations per pixel.
 // wo_relief_height16: k_relief_height16 [1], the height map to u16, four pixels per thread.
 // wo_relief_normals: k_relief_tables [1] for the map (cos / sin of every row's latitude and every column's longitude), then
 //   k_relief_normals_map or k_relief_normals_cube [1], a stencil over the height map: five height loads per pixel, a 4-byte store.
@@ -41,23 +40,14 @@ __global__ __launch_bounds__(WO_BLOCK) void k_relief_tri_elevation(const int32_t
     if (t < numTriangles) t_elevation[t] = globe::triangle_elevation(triangles, r_elevation, t);
 }
 
-__global__ __launch_bounds__(WO_BLOCK) void k_relief_heights_map(const uint32_t* __restrict__ sideMap, const int32_t* __restrict__ triangles, const int32_t* __restrict__ halfedges,
-                                                                 const M::LonLat* __restrict__ t_ll, const M::LonLat* __restrict__ r_ll, const float* __restrict__ t_elevation,
-                                                                 const float* __restrict__ r_elevation, int32_t W, int32_t H, float* __restrict__ heights) {
-    const int64_t pixels = (int64_t)W * H;
+template <class P>
+__global__ __launch_bounds__(WO_BLOCK) void k_relief_heights(const P proj, const uint32_t* __restrict__ sideMap, const int32_t* __restrict__ triangles,
+                                                             const int32_t* __restrict__ halfedges, const float* __restrict__ t_elevation, const float* __restrict__ r_elevation,
+                                                             float* __restrict__ heights) {
+    const int64_t pixels = proj.pixels();
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < pixels; q += (int64_t)gridDim.x * blockDim.x) {
         const uint32_t s = sideMap[q];
-        heights[q] = s == M::NO_SIDE ? R::quiet_nan() : R::map_pixel_height(triangles, halfedges, t_ll, r_ll, t_elevation, r_elevation, s, q, W, H);
-    }
-}
-
-__global__ __launch_bounds__(WO_BLOCK) void k_relief_heights_cube(const uint32_t* __restrict__ sideMap, const int32_t* __restrict__ triangles, const int32_t* __restrict__ halfedges,
-                                                                  const float* __restrict__ t_xyz, const float* __restrict__ r_xyz, const float* __restrict__ t_elevation,
-                                                                  const float* __restrict__ r_elevation, int32_t S, float* __restrict__ heights) {
-    const int64_t pixels = (int64_t)Q::FACE_COUNT * S * S;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < pixels; q += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t s = sideMap[q];
-        heights[q] = s == M::NO_SIDE ? R::quiet_nan() : R::cube_pixel_height(triangles, halfedges, t_xyz, r_xyz, t_elevation, r_elevation, s, q, S);
+        heights[q] = s == M::NO_SIDE ? R::quiet_nan() : R::pixel_height(proj, triangles, halfedges, t_elevation, r_elevation, s, q);
     }
 }
 
@@ -101,36 +91,20 @@ __global__ __launch_bounds__(WO_BLOCK) void k_relief_normals_cube(const float* _
     }
 }
 
-// what both height passes do first: the block's height map, the field and the triangle elevations
-static const float* relief_prepare(wo_planet* p, DeviceArena& T, wo_map_block* B, const ReliefRequest& q, const int32_t* d_tri, int32_t numTriangles, const float*& r_elevation) {
+template <class P>
+void relief_heights(wo_planet* p, DeviceArena& T, wo_map_block* B, const ReliefRequest& q, const P& proj, const int32_t* d_tri, const int32_t* d_he, int32_t numTriangles,
+                    const uint32_t* sideMap) {
     if (!B->height) B->height = B->mem.dev<float>((size_t)B->W * (size_t)B->H);
-    r_elevation = stage_elevation(p, T, q.r_elevation);
+    const float* r_elevation = stage_elevation(p, T, q.r_elevation);
     float* t_elevation = T.dev<float>((size_t)numTriangles);
     launch(p, FAM_RELIEF_TRI_ELEVATION, k_relief_tri_elevation, blocks_for(numTriangles), WO_BLOCK, d_tri, r_elevation, t_elevation, numTriangles);
-    return t_elevation;
-}
-
-static void relief_copy_out(wo_planet* p, wo_map_block* B, const ReliefRequest& q) {
+    launch(p, FAM_RELIEF_HEIGHTS, k_relief_heights<P>, blocks_for((int64_t)B->W * B->H, 1 << 16), WO_BLOCK, proj, sideMap, d_tri, d_he, (const float*)t_elevation, r_elevation,
+           B->height);
     if (q.heightOut) WO_HIP(hipMemcpyAsync(q.heightOut, B->height, (size_t)B->W * (size_t)B->H * 4, hipMemcpyDeviceToHost, p->ctx->stream));
 }
 
-void relief_heights_map(wo_planet* p, DeviceArena& T, wo_map_block* B, const ReliefRequest& q, const int32_t* d_tri, const int32_t* d_he, int32_t numTriangles,
-                        const M::LonLat* t_ll, const M::LonLat* r_ll, const uint32_t* sideMap) {
-    const float* r_elevation;
-    const float* t_elevation = relief_prepare(p, T, B, q, d_tri, numTriangles, r_elevation);
-    launch(p, FAM_RELIEF_HEIGHTS, k_relief_heights_map, blocks_for((int64_t)B->W * B->H, 1 << 16), WO_BLOCK, sideMap, d_tri, d_he, t_ll, r_ll, t_elevation, r_elevation, B->W, B->H,
-           B->height);
-    relief_copy_out(p, B, q);
-}
-
-void relief_heights_cube(wo_planet* p, DeviceArena& T, wo_map_block* B, const ReliefRequest& q, const int32_t* d_tri, const int32_t* d_he, int32_t numTriangles, const float* t_xyz,
-                         const uint32_t* sideMap) {
-    const float* r_elevation;
-    const float* t_elevation = relief_prepare(p, T, B, q, d_tri, numTriangles, r_elevation);
-    launch(p, FAM_RELIEF_HEIGHTS, k_relief_heights_cube, blocks_for((int64_t)B->W * B->H, 1 << 16), WO_BLOCK, sideMap, d_tri, d_he, t_xyz, (const float*)p->d_xyz, t_elevation,
-           r_elevation, B->W, B->height);
-    relief_copy_out(p, B, q);
-}
+template void relief_heights(wo_planet*, DeviceArena&, wo_map_block*, const ReliefRequest&, const M::Projection&, const int32_t*, const int32_t*, int32_t, const uint32_t*);
+template void relief_heights(wo_planet*, DeviceArena&, wo_map_block*, const ReliefRequest&, const Q::Projection&, const int32_t*, const int32_t*, int32_t, const uint32_t*);
 
 }  // namespace wo
 
@@ -148,18 +122,6 @@ static wo_map_block* relief_block(wo_planet* p, const char* fn, const void* out,
 }
 
 extern "C" {
-
-int wo_relief_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, double centerLon, const float* r_elevation,
-                     float* heightOut, int64_t counts[2]) {
-    const ReliefRequest q{r_elevation, heightOut};
-    return map_raster(p, "wo_relief_raster", numSides, triangles, halfedges, width, true, centerLon, nullptr, counts, &q);
-}
-
-int wo_relief_raster_cube(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t faceSize, const float* r_elevation, float* heightOut,
-                          int64_t counts[2]) {
-    const ReliefRequest q{r_elevation, heightOut};
-    return cube_raster(p, "wo_relief_raster_cube", numSides, triangles, halfedges, faceSize, nullptr, counts, &q);
-}
 
 int wo_relief_download(wo_planet* p, float* out, int64_t outBytes) {
     const char* fn = "wo_relief_download";

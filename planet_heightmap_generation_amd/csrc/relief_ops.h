@@ -6,7 +6,7 @@
 //
 // The surface.  The globe mesh (globe_ops.h) is one flat triangle per side s between v0 = t_xyz[s / 3], v1 = t_xyz[halfedges[s] / 3]
 //   and v2 = r_xyz[triangles[s]], with the elevations E0 = t_elevation[s / 3], E1 = t_elevation[halfedges[s] / 3] (globe::
-//   triangle_elevation, stored f32) and E2 = r_elevation[triangles[s]].  The rasters of map.hip and cube.hip decide which side
+//   triangle_elevation, stored f32) and E2 = r_elevation[triangles[s]].  The raster (raster.hip) decides which side
 //   covers a pixel (the side map); the height of the pixel is that side's elevation interpolated at the pixel centre.
 // Height, equirectangular.  t is the map::Tri of the winning side that was rastered: side_triangles' k = 0, or for a wrapping side
 //   k = 0 if that triangle has a usable area2 and covers the centre, else k = 1.  With area2 = tri_area2(t) and e0, e1, e2 the edge
@@ -136,6 +136,16 @@ WO_IMP_HD inline float cube_pixel_height(const int32_t* triangles, const int32_t
     float E[3];
     side_elevations(triangles, halfedges, t_elevation, r_elevation, s, E);
     return height_perspective(a, b, Q::pixel_c(r % S, S), Q::pixel_c(r / S, S), ma, E);
+}
+
+// the two bodies above under one name, for the height pass that takes its projection as a type (relief.hip: k_relief_heights)
+WO_IMP_HD inline float pixel_height(const M::Projection& P, const int32_t* triangles, const int32_t* halfedges, const float* t_elevation, const float* r_elevation, int64_t s,
+                                    int64_t q) {
+    return map_pixel_height(triangles, halfedges, P.t_ll, P.r_ll, t_elevation, r_elevation, s, q, P.W, P.H);
+}
+WO_IMP_HD inline float pixel_height(const Q::Projection& P, const int32_t* triangles, const int32_t* halfedges, const float* t_elevation, const float* r_elevation, int64_t s,
+                                    int64_t q) {
+    return cube_pixel_height(triangles, halfedges, P.t_xyz, P.r_xyz, t_elevation, r_elevation, s, q, P.S);
 }
 
 // ---- 16 bit ---------------------------------------------------------------------------------------------------------------------

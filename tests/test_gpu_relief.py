@@ -62,8 +62,9 @@ def _compare(tag, got, want, uncovered):
 
 
 # 256 and 250 (odd boxes, a height that is no power of two) and a centre meridian are the small route with the seam and the pole fan
-# in every one; at 2048 x 1024 every triangle of the 256-cell planet takes the large-box route and has thousands of pixels
-MAP_CASES = [("N10000", 256, 0.0), ("N10000", 250, 0.0), ("N10000", 256, 1.0), ("N256", 2048, 0.0)]
+# in every one; at 2048 x 1024 every triangle of the 256-cell planet takes the large-box route and has thousands of pixels, plain
+# and around a centre meridian
+MAP_CASES = [("N10000", 256, 0.0), ("N10000", 250, 0.0), ("N10000", 256, 1.0), ("N256", 2048, 0.0), ("N256", 2048, 1.0)]
 # 64 and 50 are the small route; S = 1 is six pixels whose four neighbours all lie on other faces; 2 000 cells at 1024 is the list
 CUBE_CASES = [("N10000", 64), ("N10000", 50), ("N10000", 1), ("N2000", 1024)]
 
