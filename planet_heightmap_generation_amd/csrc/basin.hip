@@ -30,7 +30,7 @@
 
 #include <string>
 
-#include "device.h"
+#include "erode_block.h"
 
 namespace wo {
 
@@ -380,56 +380,55 @@ __global__ __launch_bounds__(64 * NW, (NW <= 4 ? 4 : 2)) void k_solve_flowing(Fi
 
 }  // namespace
 
-// Group-major store order for this pass (d_basinSlot) and the sorted group keys (d_keys[1]).  Call after the receivers
+// Group-major store order for this pass (basin.slot) and the sorted group keys (scratch.keys[1]).  Call after the receivers
 // pass (F.tr) and before k_solve_setup; everything is enqueued on the planet's stream, no host sync.
 void basin_alloc(wo_planet* p) {
     const int32_t N = p->N;
     hipStream_t s = cur_stream(p);
-    if (!p->d_basinJ) {
-        // built in an arena of its own and handed to the planet's whole; basinJ, assigned last, says that the buffers are there
-        DeviceArena a;
-        int32_t* J = a.dev<int32_t>(N);
-        p->d_basinSlot = a.dev<int32_t>(N);
-        p->d_basinKey = a.dev<uint32_t>(N);
-        p->d_basinVals[0] = a.dev<int32_t>(N); p->d_basinVals[1] = a.dev<int32_t>(N);   // own buffers: the layout runs beside the flow accumulation, whose rounds use the planet's lists
-        p->d_basinRange = a.dev<int32_t>((size_t)N / 64 + 8 + WO_LONG_MAX);        // range starts, then {count, long ranges}
-        p->d_basinLong = a.dev<uint8_t>((size_t)N / 64 + 8);
-        p->mem.adopt(a); p->d_basinJ = J;
-        WO_HIP(hipMemsetAsync(p->d_basinSlot, 0xff, (size_t)N * 4, s));
-    }
+    wo_erode_block& B = *p->erode; auto& G = B.basin;
+    build_group(B, G, [&](DeviceArena& a) {
+        G.J = a.dev<int32_t>(N);
+        G.slot = a.dev<int32_t>(N);
+        G.key = a.dev<uint32_t>(N);
+        G.vals[0] = a.dev<int32_t>(N); G.vals[1] = a.dev<int32_t>(N);   // own buffers: the layout runs beside the flow accumulation, whose rounds use the planet's lists
+        G.range = a.dev<int32_t>((size_t)N / 64 + 8 + WO_LONG_MAX);        // range starts, then {count, long ranges}
+        G.isLong = a.dev<uint8_t>((size_t)N / 64 + 8);
+        WO_HIP(hipMemsetAsync(G.slot, 0xff, (size_t)N * 4, s));
+    });
 }
 
 // J already holds the start state (k_receivers_flow_init, Fields::basinJ; pairs of cells draining into each other are rings of
 // two there, which the search cuts like any ring: at the smaller slot).  slotIdentity: a land
 // cell's Morton slot is its id (land-first mirror).
 void basin_layout(wo_planet* p, bool slotIdentity) {
-    const int32_t L = p->L;
-    basin_alloc(p);
+    wo_erode_block& B = *p->erode; auto& S = B.scratch; const int32_t L = B.L;
     int bitsL = 1;
     while (((int64_t)1 << bitsL) < (int64_t)L) ++bitsL;
     const int shift = bitsL > WO_BASIN_KEY_BITS ? bitsL - WO_BASIN_KEY_BITS : 0;
     const int grid = blocks_for(L, 1 << 16);
-    launch(p, FAM_BASIN, k_basin_jump, grid, WO_BLOCK, slotIdentity ? (const int32_t*)nullptr : (const int32_t*)p->d_patchOrder, p->d_basinJ, L, (int32_t)shift, p->d_basinKey);
+    launch(p, FAM_BASIN, k_basin_jump, grid, WO_BLOCK, slotIdentity ? (const int32_t*)nullptr : (const int32_t*)S.patchOrder, B.basin.J, L, (int32_t)shift, B.basin.key);
     const int rangeT = WO_BASIN_RANGE;
     const int nRanges = (int)(((int64_t)L + rangeT - 1) / rangeT);
-    launch(p, FAM_BASIN, k_basin_keys, grid, WO_BLOCK, (const int32_t*)p->d_land[p->landCur], (const uint32_t*)p->d_basinKey, L, p->d_keys[0], p->d_basinVals[0],
-           (int32_t)(p->opt.basinScramble ? 1 : 0), p->d_basinRange, (int32_t)(nRanges + 1));
+    launch(p, FAM_BASIN, k_basin_keys, grid, WO_BLOCK, (const int32_t*)S.land[S.cur], (const uint32_t*)B.basin.key, L, S.keys[0], B.basin.vals[0],
+           (int32_t)(p->opt.basinScramble ? 1 : 0), B.basin.range, (int32_t)(nRanges + 1));
     // the in-tree sort (radix.hip); its last pass also writes slotOf[cell] = position
-    uint32_t* const kb[2] = {p->d_keys[0], p->d_keys[1]};
-    int32_t* const vb[2] = {p->d_basinVals[0], p->d_basinVals[1]};
-    const int sorted = radix_sort_pairs(p, FAM_BASIN_SORT, kb, vb, L, 0, 16 /* always two digits: the sort's two group-total buffers swap roles every pass and only stay consistent over an even number of passes; key bits above bitsL - shift are zero */, p->d_basinSlot, radix_scratch(p, 1), p->N, p->rsFlip[1]);
-    launch(p, FAM_BASIN, k_basin_slots, blocks_for(L, 4096), WO_BLOCK, (const int32_t*)p->d_basinVals[sorted], (const uint32_t*)p->d_keys[sorted], (int32_t*)nullptr, L, p->d_basinRange, (int32_t)rangeT);
-    launch(p, FAM_BASIN, k_basin_long, blocks_for(nRanges), WO_BLOCK, (const int32_t*)p->d_basinRange, (int32_t)nRanges, L, p->d_basinRange + nRanges + 1, p->d_basinLong);
+    uint32_t* const kb[2] = {S.keys[0], S.keys[1]};
+    int32_t* const vb[2] = {B.basin.vals[0], B.basin.vals[1]};
+    auto& R = radix_scratch(p, 1);
+    const int sorted = radix_sort_pairs(p, FAM_BASIN_SORT, kb, vb, L, 0, 16 /* always two digits: the sort's two group-total buffers swap roles every pass and only stay consistent over an even number of passes; key bits above bitsL - shift are zero */, B.basin.slot, R.words, p->N, R.flip);
+    launch(p, FAM_BASIN, k_basin_slots, blocks_for(L, 4096), WO_BLOCK, (const int32_t*)B.basin.vals[sorted], (const uint32_t*)S.keys[sorted], (int32_t*)nullptr, L, B.basin.range, (int32_t)rangeT);
+    launch(p, FAM_BASIN, k_basin_long, blocks_for(nRanges), WO_BLOCK, (const int32_t*)B.basin.range, (int32_t)nRanges, L, B.basin.range + nRanges + 1, B.basin.isLong);
 }
 
-// the one launch of the pass; F.slotOf must be d_basinSlot, patchPending zeroed
+// the one launch of the pass; F.slotOf must be basin.slot, patchPending zeroed
 void basin_solve_launch(wo_planet* p, const Fields& F, int32_t launchTag, int32_t* totalPending) {
-    const int nRanges = (int)(((int64_t)p->L + WO_BASIN_RANGE - 1) / WO_BASIN_RANGE);
-    ++p->basinLaunches;
-    const int32_t* big = (const int32_t*)(p->d_basinRange + nRanges + 1);
-    const uint8_t* flag = (const uint8_t*)p->d_basinLong;
+    wo_erode_block& B = *p->erode; auto& S = B.scratch;
+    const int nRanges = (int)(((int64_t)B.L + WO_BASIN_RANGE - 1) / WO_BASIN_RANGE);
+    ++B.basin.launches;
+    const int32_t* big = (const int32_t*)(B.basin.range + nRanges + 1);
+    const uint8_t* flag = (const uint8_t*)B.basin.isLong;
     const int grid = nRanges + WO_LONG_MAX;
-    launch(p, FAM_SOLVE_BASIN, k_solve_flowing<2, false>, grid, 128, F, p->L, (const int32_t*)p->d_basinRange, (int32_t)nRanges, launchTag, p->d_patchPending, totalPending, big, flag, (unsigned long long*)nullptr);
+    launch(p, FAM_SOLVE_BASIN, k_solve_flowing<2, false>, grid, 128, F, B.L, (const int32_t*)B.basin.range, (int32_t)nRanges, launchTag, S.patchPending, totalPending, big, flag, (unsigned long long*)nullptr);
     // (k_solve_flowing<2, true>: the same kernel with phase clocks and the depth of the slowest range's dependency DAG written to its last argument — the
     // diagnostic build behind DESIGN.md's "clocks per level" figures, profiles/r04c_*; not instantiated in the product)
 }

@@ -9,6 +9,7 @@
 #include "climate_ops.h"
 #include "common_kernels.h"
 #include "device.h"
+#include "erode_block.h"
 
 namespace wo {
 
@@ -46,7 +47,7 @@ using namespace wo;
 // smoothField (js/climate-util.js:5-25) on a device-resident field, no host round trip: `passes` Jacobi passes from a into b and
 // back; returns the buffer that holds the result (wind.hip)
 float* wo::smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passes) {
-    Fields F = p->fields();
+    Fields F = fields(p);
     for (int32_t pass = 0; pass < passes; ++pass) {
         launch(p, FAM_SMOOTH_FIELD, k_smooth_field, xcd_grid(p->N), WO_BLOCK, F, (const float*)a, b);
         std::swap(a, b);
@@ -56,7 +57,7 @@ float* wo::smooth_field_resident(wo_planet* p, float* a, float* b, int32_t passe
 
 // diffuseOceanWarmth (js/temperature.js:19-54) of one season on device-resident fields (temp.hip, the split form of its diffusion)
 float* wo::diffuse_warmth_resident(wo_planet* p, const float* warmth, const uint8_t* isLand, const float* plateCont, int32_t passes, float* a, float* b) {
-    const Fields F = p->fields(); const ClimateMesh M = climate_mesh(p);
+    const Fields F = fields(p); const ClimateMesh M = climate_mesh(p);
     launch(p, FAM_CLIMATE, k_warmth_seed, blocks_for(p->N, 4096), WO_BLOCK, warmth, isLand, a, p->N);
     for (int32_t pass = 0; pass < passes; ++pass) { launch(p, FAM_CLIMATE, k_warmth_diffuse, xcd_grid(p->N), WO_BLOCK, F, M, (const float*)a, plateCont, b); std::swap(a, b); }
     return a;
@@ -65,11 +66,11 @@ float* wo::diffuse_warmth_resident(wo_planet* p, const float* warmth, const uint
 // computeWindConvergence and advectMoisture (js/precipitation.js:19-52, :59-182) on device-resident fields (precip.hip); the
 // advection returns the buffer that holds the result
 void wo::wind_convergence_resident(wo_planet* p, const float* wx, const float* wy, const float* wz, float* out) {
-    launch(p, FAM_CLIMATE, k_wind_convergence, xcd_grid(p->N), WO_BLOCK, p->fields(), climate_mesh(p), wx, wy, wz, out);
+    launch(p, FAM_CLIMATE, k_wind_convergence, xcd_grid(p->N), WO_BLOCK, fields(p), climate_mesh(p), wx, wy, wz, out);
 }
 float* wo::advect_moisture_resident(wo_planet* p, const float* heightKm, const uint8_t* isLand, const float* windE, const float* windN, const float* wx, const float* wy,
                                     const float* wz, const float* warmth, const int32_t* coastDist, int32_t maxHops, double depletionBase, float* a, float* b) {
-    const Fields F = p->fields(); const ClimateMesh M = climate_mesh(p);
+    const Fields F = fields(p); const ClimateMesh M = climate_mesh(p);
     launch(p, FAM_CLIMATE, k_moisture_seed, xcd_grid(p->N), WO_BLOCK, F, M, isLand, wx, wy, wz, warmth, coastDist, a);
     for (int32_t it = 0; it < maxHops; ++it) {
         launch(p, FAM_CLIMATE, k_moisture_advect, xcd_grid(p->N), WO_BLOCK, F, M, (const float*)a, heightKm, isLand, windE, windN, wx, wy, wz, maxHops, depletionBase, b);

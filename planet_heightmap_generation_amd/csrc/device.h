@@ -13,7 +13,6 @@
 #include "device_mem.h"
 #include "host_util.h"
 
-#include "erode_ops.h"
 #include "flood_ops.h"
 #include "wo_internal.h"
 
@@ -127,8 +126,6 @@ struct wo_planet {
     bool h_ocean_valid = false;
     float* h_pinned = nullptr;          // N floats, pinned
     int32_t* h_count = nullptr;         // pinned scalar(s) for round-count read-back
-    // erode_composite_checked: the field at entry, tasks any basin launch of the call left pending, calls that had to run again
-    float* d_redoE = nullptr; int32_t* d_pendingEver = nullptr; int64_t redoCalls = 0;
     // host-mapped {serial, value} word the host polls (read_count)
     unsigned long long *h_word = nullptr, *d_word = nullptr; uint32_t wordSerial = 0;
     wo::FloodScratch flood;
@@ -147,49 +144,11 @@ struct wo_planet {
     bool hot_valid = false;
     float* d_savedE = nullptr; uint8_t* d_savedOcean = nullptr; bool saved = false;
     uint8_t* d_tables = nullptr;        // perm[512] + pm12[512]
-    // erode scratch (allocated on first erodeComposite)
-    bool scratch = false;
-    bool landIdentity = false;          // erode_composite under the land-first mirror: landIdx[i] == i
+    int64_t oceanVersion = 0;            // counts the changes of the mask h_ocean describes (the flood tables' and the land lists' cache key)
     int64_t floodPrefixMirror = -1, floodPrefixStatic = -1;      // (mirror version, flood static version) for which the mirror's first L ids were checked to be the flood's land order
     bool floodPrefixOk = false;
-    int32_t *d_landIdx = nullptr, *d_land[2] = {nullptr, nullptr}, *d_rank = nullptr;
-    // the initial land list (ascending r, js/terrain-post.js:384-390) and the index-order list are functions of the ocean mask alone: kept while it stays
-    int32_t* d_landInit = nullptr; int64_t oceanVersion = 0, landListsOcean = -1; bool landListsMirror = false; int32_t landListsL = -1;
-    uint32_t* d_keys[2] = {nullptr, nullptr};
-    float *d_cellDist = nullptr, *d_flow = nullptr;
-    wo::SolveTask* d_task = nullptr; wo::SolveOut* d_out = nullptr;
     // banded Jacobi passes
     int32_t *d_haloSend = nullptr, *d_haloRecv = nullptr; float *d_haloBuf = nullptr, *h_haloBuf = nullptr; int32_t nHaloSend = 0, nHaloRecv = 0;
-    int32_t* d_flowCnt = nullptr; wo::TargetRank* d_tr = nullptr; wo::EventList* d_ev = nullptr; float* d_me = nullptr;
-    // carve dependency lists
-    int32_t *d_carveSlot = nullptr, *d_carveDeps = nullptr, *d_carveDepCnt = nullptr, *d_carveDepPos = nullptr;
-    // radix.hip scratch: elevation sort, basin sort
-    uint32_t* d_rs[2] = {nullptr, nullptr}; int rsFlip[2] = {0, 0};
-    // k_carve_granules: expected tags per task, height granules per cell
-    wo::CarveRec* d_carveRecs = nullptr; wo::CarveExpect* d_carveExpect = nullptr; unsigned long long* d_carveG = nullptr;
-    int32_t* d_carveSlotDone = nullptr; int64_t carveCap = 0;
-    unsigned long long* d_accCnt = nullptr;
-    // two-level flow accumulation (kernels_impl.h: FlowTiles)
-    int32_t *d_ftLr = nullptr, *d_ftParent = nullptr, *d_ftExtCnt = nullptr; uint32_t* d_ftInflow = nullptr; unsigned long long* d_ftRootAcc = nullptr;
-    int32_t *d_jump = nullptr, *d_nj = nullptr;
-    int32_t* d_doneAt = nullptr;
-    double* d_totalExcess = nullptr;
-    float *d_glac = nullptr, *d_iceFlow = nullptr;
-    int32_t *d_iceTarget = nullptr, *d_arank = nullptr;
-    uint8_t* d_iceUp = nullptr;
-    int32_t *d_patchOrder = nullptr, *d_slotOf = nullptr, *d_patchPending = nullptr, *d_patchTotals = nullptr, *d_patchBlk = nullptr;
-    int64_t patchVersion = -1; bool patchMirror = false; int32_t numPatches = 0; int64_t lastPatchLaunches = 1; int64_t solveCalls = 0;
-    hipStream_t side = nullptr; hipEvent_t evFork = nullptr, evJoin = nullptr; bool onSide = false;
-    // basin.hip: component roots (Morton slot space), group-major store order of the pass
-    uint32_t* d_basinKey = nullptr; int32_t* d_basinVals[2] = {nullptr, nullptr}; int32_t *d_basinJ = nullptr, *d_basinSlot = nullptr, *d_basinRange = nullptr;
-    uint8_t* d_basinLong = nullptr; int64_t basinLaunches = 0;
-    wo::Affine* d_affine[2] = {nullptr, nullptr};      // relaxed mode: the affine recurrence, ping-pong
-    int64_t solvePassSerial = 0;                       // unchecked basin passes so far (their output tag: erode.hip, passTag)
-    int32_t* h_patchTotals = nullptr;      // pinned: the pending totals of a burst of k_solve_patch launches (run_solve_patches)
-    int32_t *d_listA = nullptr, *d_listB = nullptr, *d_counters = nullptr;   // round lists + 4 counters
-    void* d_sortTemp = nullptr; size_t sortTempBytes = 0;
-    int landCur = 0;                    // which of d_land[] holds the current order
-    int32_t L = 0;
 
     // heightmap import scratch (heightmap.hip), allocated on first use and grown when needed
     struct Import {
@@ -226,6 +185,9 @@ struct wo_planet {
     // rivers and lakes (rivers.hip; rivers_block.h): the rivers block — the five results of wo_compute_rivers (24 bytes per cell),
     // allocated on its first call; deleted by wo_planet_destroy (rivers_free)
     struct wo_rivers_block* rivers = nullptr;
+    // erodeComposite (erode.hip, basin.hip, sort.hip, radix.hip; erode_block.h): the erosion block — land lists, sort, flow, solve,
+    // ice and carve state, built group by group from the planet's first erodeComposite call on; deleted by wo_planet_destroy (erode_free)
+    struct wo_erode_block* erode = nullptr;
 
     // Patch-major mirror of the mesh for erodeComposite (mirror.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
@@ -257,8 +219,6 @@ struct wo_planet {
     struct StageBracket { std::string name; hipEvent_t a, b; };
     std::vector<StageBracket> stageBrackets; std::vector<std::pair<std::string, std::pair<int64_t, int64_t>>> stageSeen; bool stagePending = false;
     std::vector<std::pair<std::string, double>> erodeStats;
-
-    wo::Fields fields() const;
 };
 
 namespace wo {
@@ -267,51 +227,28 @@ namespace wo {
 hipEvent_t profile_event(wo_planet* p);
 void profile_resolve(wo_planet* p);
 
-// the stream launches of this planet currently go to (its context's stream, or the planet's side stream while onSide is set)
-inline hipStream_t cur_stream(const wo_planet* p) { return (p->onSide && p->side) ? p->side : p->ctx->stream; }
+// planet.hip: the stream launches of this planet currently go to (its context's stream, or the erosion block's side stream while that is on)
+hipStream_t cur_stream(const wo_planet* p);
 
-template <class... KArgs, class... Args>
-inline void launch(wo_planet* p, int fam, void (*kernel)(KArgs...), int grid, int block, Args... args) {
-    hipStream_t s = cur_stream(p);
-    if (p->profiling) {
-        hipEvent_t a = profile_event(p), b = profile_event(p);
-        WO_HIP(hipEventRecord(a, s));
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, args...);
-        WO_HIP(hipGetLastError());                 // a launch that cannot be configured would otherwise be a silent no-op
-        WO_HIP(hipEventRecord(b, s));
-        p->pending.push_back({fam, a, b});
-        if (p->pending.size() >= 4096) profile_resolve(p);
-    } else {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, args...);
-        WO_HIP(hipGetLastError());
-    }
-}
-
+// shmem: bytes of dynamic LDS
 template <class... KArgs, class... Args>
 inline void launch_shmem(wo_planet* p, int fam, void (*kernel)(KArgs...), int grid, int block, size_t shmem, Args... args) {
-    hipStream_t s = p->ctx->stream;
+    hipStream_t s = cur_stream(p);
     hipEvent_t a = nullptr, b = nullptr;
     if (p->profiling) { a = profile_event(p); b = profile_event(p); WO_HIP(hipEventRecord(a, s)); }
     if (shmem > (size_t)(64 << 10)) WO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), shmem, s, args...);
-    WO_HIP(hipGetLastError());
+    WO_HIP(hipGetLastError());                     // a launch that cannot be configured would otherwise be a silent no-op
     if (p->profiling) { WO_HIP(hipEventRecord(b, s)); p->pending.push_back({fam, a, b}); if (p->pending.size() >= 4096) profile_resolve(p); }
 }
+template <class... KArgs, class... Args>
+inline void launch(wo_planet* p, int fam, void (*kernel)(KArgs...), int grid, int block, Args... args) { launch_shmem(p, fam, kernel, grid, block, (size_t)0, args...); }
 
-// sort.hip: stable descending sort of the land list by current elevation + rank scatter
-void sort_land_by_elevation(wo_planet* p);
-size_t sort_temp_bytes(int32_t n);
-void rank_from_land(wo_planet* p);
-// radix.hip: the in-tree stable radix sort (scratch: radix_scratch_words(nMax) u32, zero before the first use; flip: call parity kept by the caller)
+// radix.hip: the in-tree stable radix sort, shared by the erosion's sorts and the wind stage (scratch: radix_scratch_words(nMax) u32, zero
+// before the first use; flip: call parity kept by the caller)
 size_t radix_scratch_words(int32_t nMax);
 int radix_sort_pairs(wo_planet* p, int family, uint32_t* const keys[2], int32_t* const vals[2], int32_t n, int beginBit, int endBit, int32_t* posOut,
                      uint32_t* scratch, int32_t nMax, int& flip);
-uint32_t* radix_scratch(wo_planet* p, int which);      // 0: elevation sort, 1: basin sort (allocated and cleared on first use)
-void select_active_by_rank(wo_planet* p, const int32_t* arank, int32_t* out, int32_t* outCount);   // carve tasks in landCells order
-// basin.hip: group-major store order of the solve (d_basinSlot, sorted group keys in d_keys[1]) and the one-launch solve over it
-void basin_alloc(wo_planet* p);
-void basin_layout(wo_planet* p, bool slotIdentity);
-void basin_solve_launch(wo_planet* p, const Fields& F, int32_t launchTag, int32_t* totalPending);
 // wind.hip, ocean.hip: drop the wind block / the ocean block (and with it its memory)
 void wind_free(wo_planet* p);
 void ocean_free(wo_planet* p);

@@ -9,7 +9,7 @@
 #include <cmath>
 
 #include "../../include/worogen.h"
-#include "device.h"
+#include "erode_block.h"
 #include "flood.h"
 #include "kernels_impl.h"
 #include "mirror.h"
@@ -21,34 +21,30 @@ __global__ __launch_bounds__(WO_BLOCK) void k_fill_i32(int32_t* a, int32_t v, in
 
 constexpr int WO_PATCH_TOTAL_SLOTS = 4096;         // pending-total slots of the patch solve (one per launch, reused modulo)
 
-// Failure-safe by construction: the scratch is built in an arena of its own, which the planet's arena takes over once every buffer is
-// there; a failure on the way frees what was built, `scratch` stays false (the members are then not looked at) and the next call starts afresh.
+// What every call needs of the erosion block
 static void ensure_scratch(wo_planet* p) {
-    if (p->scratch) return;
-    const size_t N = (size_t)p->N;
-    DeviceArena a;
-    p->d_landIdx = a.dev<int32_t>(N); p->d_land[0] = a.dev<int32_t>(N); p->d_land[1] = a.dev<int32_t>(N);
-    p->d_keys[0] = a.dev<uint32_t>(N); p->d_keys[1] = a.dev<uint32_t>(N);
-    p->d_rank = a.dev<int32_t>(N);
-    p->d_cellDist = a.dev<float>(N); p->d_flow = a.dev<float>(N); p->d_task = a.dev<SolveTask>(N);
-    // tags of the unchecked basin passes count up from here: no stale tag may look like a coming one
-    p->d_out = a.dev<SolveOut>(N); WO_HIP(hipMemset(p->d_out, 0, N * sizeof(SolveOut)));
-    p->d_flowCnt = a.dev<int32_t>(N); WO_HIP(hipMemset(p->d_flowCnt, 0, (size_t)N * 4));
-    p->d_tr = a.dev<TargetRank>(N); p->d_ev = a.dev<EventList>(N); p->d_me = a.dev<float>(N); p->d_carveSlot = a.dev<int32_t>(N);
-    p->d_accCnt = a.dev<unsigned long long>(N); p->d_jump = a.dev<int32_t>(N); p->d_nj = a.dev<int32_t>(N);
-    p->d_doneAt = a.dev<int32_t>(N);
-    p->d_totalExcess = a.dev<double>(N);
-    p->d_glac = a.dev<float>(N); p->d_iceFlow = a.dev<float>(N); p->d_iceTarget = a.dev<int32_t>(N); p->d_arank = a.dev<int32_t>(N);
-    p->d_iceUp = a.dev<uint8_t>(N);
-    p->d_listA = a.dev<int32_t>(N); p->d_listB = a.dev<int32_t>(N); p->d_counters = a.dev<int32_t>(8);
-    p->d_patchOrder = a.dev<int32_t>(N); p->d_slotOf = a.dev<int32_t>(N); p->d_patchPending = a.dev<int32_t>(N / WO_PATCH + 2);
-    p->d_patchTotals = a.dev<int32_t>(WO_PATCH_TOTAL_SLOTS); p->d_patchBlk = a.dev<int32_t>(N);
-    p->h_patchTotals = a.pinned<int32_t>(WO_PATCH_TOTAL_SLOTS);          // read-back buffer of run_solve_patches
-    p->sortTempBytes = sort_temp_bytes(p->N);
-    p->d_sortTemp = a.dev<uint8_t>(std::max<size_t>(p->sortTempBytes, 16));
-    WO_HIP(hipMemsetAsync(p->d_glac, 0, N * sizeof(float), p->ctx->stream));
-    p->mem.adopt(a);
-    p->scratch = true;
+    wo_erode_block& B = *p->erode; auto& S = B.scratch; const size_t N = (size_t)p->N;
+    build_group(B, S, [&](DeviceArena& a) {
+        S.landIdx = a.dev<int32_t>(N); S.land[0] = a.dev<int32_t>(N); S.land[1] = a.dev<int32_t>(N);
+        S.keys[0] = a.dev<uint32_t>(N); S.keys[1] = a.dev<uint32_t>(N);
+        S.rank = a.dev<int32_t>(N);
+        S.cellDist = a.dev<float>(N); S.flow = a.dev<float>(N); S.task = a.dev<SolveTask>(N);
+        // tags of the unchecked basin passes count up from here: no stale tag may look like a coming one
+        S.out = a.dev<SolveOut>(N); WO_HIP(hipMemset(S.out, 0, N * sizeof(SolveOut)));
+        S.flowCnt = a.dev<int32_t>(N); WO_HIP(hipMemset(S.flowCnt, 0, (size_t)N * 4));
+        S.tr = a.dev<TargetRank>(N); S.ev = a.dev<EventList>(N); S.me = a.dev<float>(N); S.carveSlot = a.dev<int32_t>(N);
+        S.accCnt = a.dev<unsigned long long>(N); S.jump = a.dev<int32_t>(N); S.nj = a.dev<int32_t>(N);
+        S.doneAt = a.dev<int32_t>(N);
+        S.totalExcess = a.dev<double>(N);
+        S.glac = a.dev<float>(N); S.iceFlow = a.dev<float>(N); S.iceTarget = a.dev<int32_t>(N); S.arank = a.dev<int32_t>(N);
+        S.iceUp = a.dev<uint8_t>(N);
+        S.listA = a.dev<int32_t>(N); S.listB = a.dev<int32_t>(N); S.counters = a.dev<int32_t>(8);
+        S.patchOrder = a.dev<int32_t>(N); S.slotOf = a.dev<int32_t>(N); S.patchPending = a.dev<int32_t>(N / WO_PATCH + 2);
+        S.patchTotals = a.dev<int32_t>(WO_PATCH_TOTAL_SLOTS); S.patchBlk = a.dev<int32_t>(N);
+        S.h_patchTotals = a.pinned<int32_t>(WO_PATCH_TOTAL_SLOTS);          // read-back buffer of run_solve_patches
+        S.sortTemp = a.dev<uint8_t>(std::max<size_t>(sort_temp_bytes(p->N), 16));
+        WO_HIP(hipMemsetAsync(S.glac, 0, N * sizeof(float), p->ctx->stream));
+    });
 }
 
 // Basin solve driver (basin.hip): the first launch of the pass is k_solve_basin on the group-major store order of basin_layout(), which
@@ -56,16 +52,17 @@ static void ensure_scratch(wo_planet* p) {
 // is pending.  Returns the number of launches.  The pass's setup launch (k_solve_setup_batched) has cleared the patch counters and the
 // pending totals: one slot per launch, cleared once per pass (a memset per launch was 13.6 k fill kernels per step).
 static int64_t run_solve_patches(wo_planet* p, const Fields& F, double K, double m, double dt, bool deferCheck, int32_t passTag) {
+    wo_erode_block& B = *p->erode; auto& S = B.scratch;
     hipStream_t s = p->ctx->stream;
-    const int np = p->numPatches;
+    const int np = S.numPatches;
     if (deferCheck) {
         // the one launch of the basin solve, and no look at what it left: tasks left pending are counted into a word that is not
         // cleared during the call and looked at where the host synchronises anyway (erode_composite: RedoWithChecks)
-        basin_solve_launch(p, F, passTag, p->d_pendingEver);
-        p->lastPatchLaunches = 1;
+        basin_solve_launch(p, F, passTag, B.redo.pendingEver);
+        S.lastPatchLaunches = 1;
         return 1;
     }
-    int32_t* tot = p->d_patchTotals;
+    int32_t* tot = S.patchTotals;
     int64_t launches = 0;
     // polling passes per visit (kernels_impl.h); launches from lateFrom on (few patches still open: no queue of visits behind a
     // long one) may poll longer
@@ -76,7 +73,7 @@ static int64_t run_solve_patches(wo_planet* p, const Fields& F, double K, double
         // changes from one erosion iteration to the next, so the first burst is the previous need plus one; then small bursts.
         // Launches after the one that emptied the list find nothing pending and return at once.
         const int32_t first = tag;
-        const int burst = (tag == 1) ? std::max<int>(1, (int)std::min<int64_t>(p->lastPatchLaunches, WO_PATCH_TOTAL_SLOTS / 2)) : 3;
+        const int burst = (tag == 1) ? std::max<int>(1, (int)std::min<int64_t>(S.lastPatchLaunches, WO_PATCH_TOTAL_SLOTS / 2)) : 3;
         for (int b = 0; b < burst; ++b, ++tag) {
             // A burst never spans a wrap of the slot ring: the wrap's memset would clear the slots of the burst's earlier
             // tags before they are read back (they would read as 0 = "nothing pending").  The wrap starts the next burst.
@@ -88,8 +85,8 @@ static int64_t run_solve_patches(wo_planet* p, const Fields& F, double K, double
             else {
                 // the first k_solve_patch launch after a lean setup: its blocker hints are made from the records now (only tasks the basin
                 // launch left pending get one; normally there is no such launch at all)
-                if (tag == 2 && F.solveLean) launch(p, FAM_MISC, k_solve_blk_init, blocks_for(p->L, 4096), WO_BLOCK, F, p->L);
-                launch(p, FAM_SOLVE_PATCH, k_solve_patch, np, WO_PATCH_THREADS, F, p->L, tag, p->d_patchPending, tot + (tag % WO_PATCH_TOTAL_SLOTS), K, m, dt,
+                if (tag == 2 && F.solveLean) launch(p, FAM_MISC, k_solve_blk_init, blocks_for(B.L, 4096), WO_BLOCK, F, B.L);
+                launch(p, FAM_SOLVE_PATCH, k_solve_patch, np, WO_PATCH_THREADS, F, B.L, tag, S.patchPending, tot + (tag % WO_PATCH_TOTAL_SLOTS), K, m, dt,
                        (int32_t*)nullptr, (int32_t)(tag >= lateFrom ? lateCap : spinCap));
             }
             ++launches;
@@ -97,26 +94,35 @@ static int64_t run_solve_patches(wo_planet* p, const Fields& F, double K, double
         if (first == 1 && tag == 2) {                     // the usual case: the one launch of the basin solve, one total to look at
             if (read_count(p, tot + 1) == 0) need = 1;
         } else {
-            WO_HIP(hipMemcpyAsync(p->h_patchTotals, tot, (size_t)WO_PATCH_TOTAL_SLOTS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            WO_HIP(hipMemcpyAsync(S.h_patchTotals, tot, (size_t)WO_PATCH_TOTAL_SLOTS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
             WO_HIP(hipStreamSynchronize(s));
-            for (int32_t t = first; t < tag && !need; ++t) if (p->h_patchTotals[t % WO_PATCH_TOTAL_SLOTS] == 0) need = t;
+            for (int32_t t = first; t < tag && !need; ++t) if (S.h_patchTotals[t % WO_PATCH_TOTAL_SLOTS] == 0) need = t;
         }
         if (need) break;
         if (launches > 4 * (int64_t)p->N + 1024) throw HipError{"patch solve does not converge"};
     }
-    p->lastPatchLaunches = need;      // the first burst is exactly what the last pass needed (its first launch is the basin one)
+    S.lastPatchLaunches = need;      // the first burst is exactly what the last pass needed (its first launch is the basin one)
     return need;
 }
 
-// The planet's side stream (the basin layout beside the flow accumulation).
+// The planet's side stream (the basin layout beside the flow accumulation).  No arena owns a stream or an event: side_destroy drops them
+static void side_destroy(wo_erode_block::Side& S) {
+    if (S.stream) { (void)hipStreamSynchronize(S.stream); (void)hipStreamDestroy(S.stream); }
+    if (S.fork) (void)hipEventDestroy(S.fork);
+    if (S.join) (void)hipEventDestroy(S.join);
+    S = wo_erode_block::Side{};
+}
 static void ensure_side_stream(wo_planet* p) {
-    if (p->side) return;
+    auto& S = p->erode->side;
+    if (S.built) return;
+    side_destroy(S);                       // (what an attempt that failed half-way left)
     // the layout's chain of short launches is the longer of the two: at equal priority its workgroups queue behind the thousands of
     // the flow kernels' (a 22 us scatter pass took 108 us beside k_flow_final), so the side stream gets the highest priority
     int prLeast = 0, prGreatest = 0;
     WO_HIP(hipDeviceGetStreamPriorityRange(&prLeast, &prGreatest));
-    WO_HIP(hipStreamCreateWithPriority(&p->side, hipStreamNonBlocking, prGreatest));
-    WO_HIP(hipEventCreateWithFlags(&p->evFork, hipEventDisableTiming)); WO_HIP(hipEventCreateWithFlags(&p->evJoin, hipEventDisableTiming));
+    WO_HIP(hipStreamCreateWithPriority(&S.stream, hipStreamNonBlocking, prGreatest));
+    WO_HIP(hipEventCreateWithFlags(&S.fork, hipEventDisableTiming)); WO_HIP(hipEventCreateWithFlags(&S.join, hipEventDisableTiming));
+    S.built = true;
 }
 
 // erodeComposite on the resident field (js/terrain-post.js:369-707)
@@ -141,11 +147,12 @@ struct ErodeCall {
         gCarve = 0.02 * gScale; gConv = 0.01 * gScale; gDep = 0.005 * gScale; gFjord = 0.015 * gScale;
     }
     void stats(bool mirrored) const {
-        p->erodeStats = {{"land_cells", (double)p->L}, {"mirror_layout", mirrored ? 1.0 : 0.0}, {"iterations", (double)total}, {"sorts", (double)sorts},
+        const wo_erode_block& B = *p->erode; const auto& S = B.scratch;
+        p->erodeStats = {{"land_cells", (double)B.L}, {"mirror_layout", mirrored ? 1.0 : 0.0}, {"iterations", (double)total}, {"sorts", (double)sorts},
                          {"solve_launches_max_per_pass", (double)maxSolve}, {"solve_patch_launches_total", (double)patchLaunches},
                          {"solve_basin_passes", (double)basinPasses}, {"solve_basin_passes_with_leftovers", (double)basinLeftoverPasses},
-                         {"flow_two_level", (p->d_ftLr && p->landIdentity && hIters > 0) ? 1.0 : 0.0}, {"ice_rounds_total", (double)iceRounds},
-                         {"carve_rounds_total", (double)carveRounds}, {"carve_active_total", (double)carveActive}, {"carve_flow_launches_with_leftovers", (double)carveFlowLeft}, {"solve_check_every_pass", checkEveryPass ? 1.0 : 0.0}, {"calls_run_again_with_checks", (double)p->redoCalls}, {"flood_stage_ms", floodHostMs},
+                         {"flow_two_level", (B.tiles.built && S.identity && hIters > 0) ? 1.0 : 0.0}, {"ice_rounds_total", (double)iceRounds},
+                         {"carve_rounds_total", (double)carveRounds}, {"carve_active_total", (double)carveActive}, {"carve_flow_launches_with_leftovers", (double)carveFlowLeft}, {"solve_check_every_pass", checkEveryPass ? 1.0 : 0.0}, {"calls_run_again_with_checks", (double)B.redo.calls}, {"flood_stage_ms", floodHostMs},
                          {"flood_device_pass1_ms", floodRun.deviceMs}, {"flood_device_rounds", (double)floodRun.rounds}, {"flood_device_epochs", (double)floodRun.epochs},
                          {"flood_device_evaluations", (double)floodRun.evals}, {"flood_equal_key_decisions", (double)floodRun.ties}, {"flood_pass1_on_host", (floodRun.usedDevice && !floodRun.fellBack) ? 0.0 : 1.0},
                          {"flood_host_calls", (double)floodRun.host.calls}, {"flood_host_serial_pass1", (double)floodRun.host.serialPass1}, {"flood_host_tie_groups", (double)floodRun.host.tieGroups}, {"flood_host_contested", (double)floodRun.host.contested},
@@ -181,88 +188,88 @@ static void erode_without_land(ErodeCall& c) {
 // The "setup" stage: the field into the land-first mirror, the land lists, the ranks, the solve's patch order and the ocean cells'
 // constants.  Returns false for a share without land (the call is over then).
 static bool erode_setup(ErodeCall& c) {
-    wo_planet* p = c.p; hipStream_t s = p->ctx->stream;
+    wo_planet* p = c.p; hipStream_t s = p->ctx->stream; wo_erode_block& B = *p->erode; auto& S = B.scratch;
     const int32_t N = p->N;
     c.clk.begin("setup");
     refresh_host_ocean(p);          // the planet's own mask, before the pointers move
     c.mir.enter(p->h_ocean.data());          // land first (mirror_build)
-    p->landIdentity = c.mir.on && p->mirror.h_mask.size() == (size_t)N;      // land cells are the ids 0 .. L-1: the index-order passes skip the land list
+    S.identity = c.mir.on && p->mirror.h_mask.size() == (size_t)N;      // land cells are the ids 0 .. L-1: the index-order passes skip the land list
     coast_flags(p);
     // landCells in ascending r (js/terrain-post.js:384-390): host-side compaction of the ocean mask
     int32_t* hl = reinterpret_cast<int32_t*>(p->h_pinned);
     const uint8_t* oc = p->h_ocean.data();
     // both lists only depend on the mask (and on whether the call runs on the mirror): a call with the mask of the previous one takes them as they are
-    const bool listsKept = p->d_landInit && p->landListsOcean == p->oceanVersion && p->landListsMirror == c.mir.on && p->landListsL >= 0;
-    const int32_t L = listsKept ? p->landListsL : compact_land(N, oc, [](int64_t r) { return r; }, hl);
-    p->L = L;
+    const bool listsKept = B.lists.built && B.lists.ocean == p->oceanVersion && B.lists.mirror == c.mir.on && B.lists.L >= 0;
+    const int32_t L = listsKept ? B.lists.L : compact_land(N, oc, [](int64_t r) { return r; }, hl);
+    B.L = L;
     if (L == 0) { erode_without_land(c); return false; }
     if (listsKept) {
-        WO_HIP(hipMemcpyAsync(p->d_land[0], p->d_landInit, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        WO_HIP(hipMemcpyAsync(S.land[0], B.lists.init, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     } else if (c.mir.on) {
         // initial landCells: the same cells in the same (ascending-r) order, under their mirror names
-        WO_HIP(hipMemcpyAsync(p->d_listA, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        mirror_map_i32(p, p->d_listA, p->d_land[0], L);
+        WO_HIP(hipMemcpyAsync(S.listA, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        mirror_map_i32(p, S.listA, S.land[0], L);
         WO_HIP(hipStreamSynchronize(s));
         // the list the index-order passes iterate: land cells in ascending mirror id
         const int32_t* perm = p->mirror.h_perm.data();
         compact_land(N, oc, [perm](int64_t i) { return perm[i]; }, hl);
-        WO_HIP(hipMemcpyAsync(p->d_landIdx, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        WO_HIP(hipMemcpyAsync(S.landIdx, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
     } else {
-        WO_HIP(hipMemcpyAsync(p->d_landIdx, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        WO_HIP(hipMemcpyAsync(p->d_land[0], p->d_landIdx, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        WO_HIP(hipMemcpyAsync(S.landIdx, hl, (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        WO_HIP(hipMemcpyAsync(S.land[0], S.landIdx, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     }
     if (!listsKept) {
-        if (!p->d_landInit) p->d_landInit = p->mem.dev<int32_t>((size_t)N);
-        WO_HIP(hipMemcpyAsync(p->d_landInit, p->d_land[0], (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        p->landListsOcean = p->oceanVersion; p->landListsMirror = c.mir.on; p->landListsL = L;
+        build_group(B, B.lists, [&](DeviceArena& a) { B.lists.init = a.dev<int32_t>((size_t)N); });
+        WO_HIP(hipMemcpyAsync(B.lists.init, S.land[0], (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        B.lists.ocean = p->oceanVersion; B.lists.mirror = c.mir.on; B.lists.L = L;
     }
     WO_HIP(hipStreamSynchronize(s));       // h_pinned is reused by the flood stage
-    p->landCur = 0;
-    launch(p, FAM_MISC, k_init_rank, c.gridN, WO_BLOCK, p->d_rank, N);
+    S.cur = 0;
+    launch(p, FAM_MISC, k_init_rank, c.gridN, WO_BLOCK, S.rank, N);
     rank_from_land(p);      // thermal-only runs never sort: landCells stays in ascending-r order
     // spatial patches for the patch-local solve: land cells in Morton order (shared with the host flood's layout)
     if (c.hIters > 0) {
         ensure_flood_static(p);
-        if (p->patchVersion != p->flood.staticVersion || p->patchMirror != c.mir.on) {
-            p->patchMirror = c.mir.on;
-            if (c.mir.on) WO_HIP(hipMemcpyAsync(p->d_patchOrder, p->d_landIdx, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));   // ascending mirror id IS Morton order
-            else WO_HIP(hipMemcpyAsync(p->d_patchOrder, p->flood.landCell.data(), (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            launch(p, FAM_MISC, k_fill_i32, c.gridN, WO_BLOCK, p->d_slotOf, -1, N);
-            launch(p, FAM_MISC, k_slot_scatter, blocks_for(L, 4096), WO_BLOCK, (const int32_t*)p->d_patchOrder, p->d_slotOf, L);
+        if (S.patchVersion != p->flood.staticVersion || S.patchMirror != c.mir.on) {
+            S.patchMirror = c.mir.on;
+            if (c.mir.on) WO_HIP(hipMemcpyAsync(S.patchOrder, S.landIdx, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));   // ascending mirror id IS Morton order
+            else WO_HIP(hipMemcpyAsync(S.patchOrder, p->flood.landCell.data(), (size_t)L * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            launch(p, FAM_MISC, k_fill_i32, c.gridN, WO_BLOCK, S.slotOf, -1, N);
+            launch(p, FAM_MISC, k_slot_scatter, blocks_for(L, 4096), WO_BLOCK, (const int32_t*)S.patchOrder, S.slotOf, L);
             WO_HIP(hipStreamSynchronize(s));
-            p->patchVersion = p->flood.staticVersion;
-            p->lastPatchLaunches = 1;
-            p->numPatches = (L + WO_PATCH - 1) / WO_PATCH;
+            S.patchVersion = p->flood.staticVersion;
+            S.lastPatchLaunches = 1;
+            S.numPatches = (L + WO_PATCH - 1) / WO_PATCH;
         }
-    } else p->patchVersion = -1;
+    } else S.patchVersion = -1;
     c.gridL = xcd_grid(L);
     if (c.hIters > 0 || c.tIters > 0) {
         // ocean cells keep these values through the whole call: both elevation buffers hold them, and the per-ocean-cell
         // constants of the land passes are written once
         WO_HIP(hipMemcpyAsync(p->d_e2, p->d_e, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));
-        launch(p, FAM_MISC, k_erode_ocean_init, blocks_for(N, 4096), WO_BLOCK, p->fields());
+        launch(p, FAM_MISC, k_erode_ocean_init, blocks_for(N, 4096), WO_BLOCK, fields(p));
     }
     c.clk.end();
     return true;
 }
 // The host is about to read the field: an unchecked basin launch of this call that left tasks pending sends the call back to run again with checks
 static void leftovers_so_far(ErodeCall& c) {
-    wo_planet* p = c.p;
-    if (c.checkEveryPass || !p->d_pendingEver || read_count(p, p->d_pendingEver) == 0) return;
+    wo_planet* p = c.p; wo_erode_block& B = *p->erode;
+    if (c.checkEveryPass || !B.redo.built || read_count(p, B.redo.pendingEver) == 0) return;
     if (p->opt.floodTiming) {          // (diagnostic runs only) which of the two reasons: a splitter-sort bucket that did not fit, or a basin launch with leftovers
         int32_t h[8] = {0};
-        WO_HIP(hipMemcpy(h, p->d_pendingEver, sizeof(h), hipMemcpyDeviceToHost));
+        WO_HIP(hipMemcpy(h, B.redo.pendingEver, sizeof(h), hipMemcpyDeviceToHost));
         std::fprintf(stderr, "[erode] call runs again with checks: %d basin-solve tasks were left pending\n", h[0]);
     }
     throw RedoWithChecks{};
 }
 static void erode_flood(ErodeCall& c, double carveStrength) {
-    wo_planet* p = c.p;
+    wo_planet* p = c.p; auto& S = p->erode->scratch;
     leftovers_so_far(c);
     c.clk.begin("priority_flood");
     const auto t0 = std::chrono::steady_clock::now();
     // inside the land-first mirror, with the mask and the flood's tables in place: the land heights straight from the mirrored field
-    const bool landOnly = c.mir.on && p->landIdentity && !p->floodX.on && !p->opt.floodDevice && p->h_ocean_valid && p->flood.staticValid &&
+    const bool landOnly = c.mir.on && S.identity && !p->floodX.on && !p->opt.floodDevice && p->h_ocean_valid && p->flood.staticValid &&
                           p->flood.staticN == p->N && p->flood.L > 0 && flood_land_is_mirror_prefix(p);
     if (landOnly) flood_stage_land(p, carveStrength, c.floodRun);
     else { c.mir.suspend(); flood_stage(p, carveStrength, c.floodRun); c.mir.resume(); }
@@ -279,25 +286,23 @@ static void ice_flow(ErodeCall& c, const Fields& F) {
 static void glacial_step_relaxed(ErodeCall& c) {
     wo_planet* p = c.p;
     c.clk.begin("glacial");
-    const Fields F = p->fields();
+    const Fields F = fields(p);
     ice_flow(c, F);
     launch(p, FAM_CARVE_ROUND, k_carve_jacobi, c.gridL, WO_BLOCK, F, (const float*)p->d_e, p->d_e2, c.gCarve, c.gConv, c.gStrength);
     swap_elev(p);
-    launch(p, FAM_MORAINE, k_moraine_fjord, c.gridN, WO_BLOCK, p->fields(), c.gDep, c.gFjord);
+    launch(p, FAM_MORAINE, k_moraine_fjord, c.gridN, WO_BLOCK, fields(p), c.gDep, c.gFjord);
     c.clk.end();
 }
 // the carve's per-task buffers, for at least `active` tasks
 static void ensure_carve_capacity(wo_planet* p, int32_t active) {
-    if ((int64_t)active <= p->carveCap) return;
-    // the old buffers go first; the capacity is set once every new one is there (a failure on the way: the next call releases them and starts again)
-    DeviceArena& a = p->mem;
-    a.release(p->d_carveDeps); a.release(p->d_carveDepCnt); a.release(p->d_carveDepPos); a.release(p->d_carveRecs); a.release(p->d_carveSlotDone); a.release(p->d_carveExpect);
-    p->carveCap = 0;
+    wo_erode_block& B = *p->erode; auto& C = B.carve;
+    if ((int64_t)active <= C.cap) return;
     const size_t cap = (size_t)active + active / 4 + 1024;
-    p->d_carveDeps = a.dev<int32_t>(cap * WO_CARVE_DEPS);
-    p->d_carveDepCnt = a.dev<int32_t>(cap); p->d_carveDepPos = a.dev<int32_t>(cap);
-    p->d_carveRecs = a.dev<CarveRec>(cap); p->d_carveSlotDone = a.dev<int32_t>(cap); p->d_carveExpect = a.dev<CarveExpect>(cap);
-    p->carveCap = (int64_t)cap;
+    regrow_group(B, C, (int64_t)cap, [&](DeviceArena& a) {
+        C.deps = a.dev<int32_t>(cap * WO_CARVE_DEPS);
+        C.depCnt = a.dev<int32_t>(cap); C.depPos = a.dev<int32_t>(cap);
+        C.recs = a.dev<CarveRec>(cap); C.slotDone = a.dev<int32_t>(cap); C.expect = a.dev<CarveExpect>(cap);
+    });
 }
 // k_carve_granules' grid, every task in one launch: what is certainly resident at once, the occupancy query's blocks per CU less one
 // (the query is known to answer one too many near register-file edges).  Asked once per process.
@@ -316,50 +321,50 @@ static int carve_granule_blocks() {
 // number of finished tasks is read back after a burst.  Returns the number of carve launches.  (Round 2 also tried all rounds in ONE cooperative
 // launch with a grid barrier: slower, profiles/r02f_*; the done-word form of the one launch, k_carve_flow, and the rounds-only route were removed in round 6.)
 static int64_t carve_launches(ErodeCall& c, const Fields& F, int32_t active) {
-    wo_planet* p = c.p;
-    const int32_t* const count = p->d_counters + 3; int32_t* const done = p->d_counters + 4;
+    wo_planet* p = c.p; wo_erode_block& B = *p->erode; auto& S = B.scratch;
+    const int32_t* const count = S.counters + 3; int32_t* const done = S.counters + 4;
     // (the dependency lists — a two-hop walk per task — are for the rounds: the granule launch waits on the heights themselves and the lists are only
     // made if it leaves tasks to the rounds)
-    launch(p, FAM_CARVE_SETUP, k_carve_records, blocks_for(active), WO_BLOCK, F, (const int32_t*)p->d_listB, count, p->d_carveRecs, p->d_carveSlotDone, c.gCarve, c.gConv, c.gStrength,
+    launch(p, FAM_CARVE_SETUP, k_carve_records, blocks_for(active), WO_BLOCK, F, (const int32_t*)S.listB, count, B.carve.recs, B.carve.slotDone, c.gCarve, c.gConv, c.gStrength,
            (int32_t)0, (int32_t)1);
     WO_HIP(hipMemsetAsync(done, 0, sizeof(int32_t), p->ctx->stream));
     const int grid = blocks_for(active);
     // hook carve_blocks=<n>: at most n workgroups, so that every thread takes many tasks in turn
     const int blocksNow = p->opt.carveBlocks > 0 ? std::max(1, std::min(carve_granule_blocks(), p->opt.carveBlocks)) : carve_granule_blocks();
     const long long flowBudget = p->opt.carveBudgetMs * 100000ll;   // 100 MHz ticks
-    if (!p->d_carveG) p->d_carveG = p->mem.dev<unsigned long long>((size_t)p->N);
-    launch(p, FAM_CARVE_SETUP, k_carve_expect, grid, WO_BLOCK, F, (const CarveRec*)p->d_carveRecs, count, p->d_carveExpect);
-    launch(p, FAM_CARVE_SETUP, k_carve_pack, blocks_for(p->N, 4096), WO_BLOCK, (const float*)F.e, p->d_carveG, p->N);
-    launch(p, FAM_CARVE_ROUND, k_carve_granules, std::min(grid, blocksNow), WO_BLOCK, F, (const CarveRec*)p->d_carveRecs, (const CarveExpect*)p->d_carveExpect, p->d_carveG,
-           p->d_carveSlotDone, count, done, flowBudget);
-    launch(p, FAM_CARVE_SETUP, k_carve_unpack, blocks_for(p->N, 4096), WO_BLOCK, (const unsigned long long*)p->d_carveG, F.e, p->N);
+    build_group(B, B.granules, [&](DeviceArena& a) { B.granules.g = a.dev<unsigned long long>((size_t)p->N); });
+    launch(p, FAM_CARVE_SETUP, k_carve_expect, grid, WO_BLOCK, F, (const CarveRec*)B.carve.recs, count, B.carve.expect);
+    launch(p, FAM_CARVE_SETUP, k_carve_pack, blocks_for(p->N, 4096), WO_BLOCK, (const float*)F.e, B.granules.g, p->N);
+    launch(p, FAM_CARVE_ROUND, k_carve_granules, std::min(grid, blocksNow), WO_BLOCK, F, (const CarveRec*)B.carve.recs, (const CarveExpect*)B.carve.expect, B.granules.g,
+           B.carve.slotDone, count, done, flowBudget);
+    launch(p, FAM_CARVE_SETUP, k_carve_unpack, blocks_for(p->N, 4096), WO_BLOCK, (const unsigned long long*)B.granules.g, F.e, p->N);
     int64_t k = 2;          // the number of the next launch
     if (read_count(p, done) >= active) return k - 1;
     // the rounds want the dependency lists after all
     ++c.carveFlowLeft;
-    launch(p, FAM_CARVE_SETUP, k_carve_deps, grid, WO_BLOCK, F, (const int32_t*)p->d_listB, count, p->d_carveSlot);
-    launch(p, FAM_CARVE_SETUP, k_carve_records, grid, WO_BLOCK, F, (const int32_t*)p->d_listB, count, p->d_carveRecs, p->d_carveSlotDone, c.gCarve, c.gConv, c.gStrength, (int32_t)1, (int32_t)0);
+    launch(p, FAM_CARVE_SETUP, k_carve_deps, grid, WO_BLOCK, F, (const int32_t*)S.listB, count, S.carveSlot);
+    launch(p, FAM_CARVE_SETUP, k_carve_records, grid, WO_BLOCK, F, (const int32_t*)S.listB, count, B.carve.recs, B.carve.slotDone, c.gCarve, c.gConv, c.gStrength, (int32_t)1, (int32_t)0);
     // the depth of the carve DAG falls from one glacial iteration to the next (the ice smooths its bed), so the count of
     // finished tasks is read back every 32 rounds (a read-back costs about as much as three empty rounds)
     constexpr int burst = 32;
     for (;;) {
         for (int b = 0; b < burst; ++b, ++k)
-            launch(p, FAM_CARVE_ROUND, k_carve_round_static, grid, WO_BLOCK, F, (const CarveRec*)p->d_carveRecs, p->d_carveSlotDone, count, (int32_t)k, c.gCarve, c.gConv, c.gStrength, done);
+            launch(p, FAM_CARVE_ROUND, k_carve_round_static, grid, WO_BLOCK, F, (const CarveRec*)B.carve.recs, B.carve.slotDone, count, (int32_t)k, c.gCarve, c.gConv, c.gStrength, done);
         if (read_count(p, done) >= active) return k - 1;
         if (k > 4 * (int64_t)p->N + 1024) throw HipError{"carve rounds do not converge"};
     }
 }
 // Exact glacial step: ice accumulation, the active carve tasks in landCells order, their carve, moraines and fjords
 static void glacial_step_exact(ErodeCall& c) {
-    wo_planet* p = c.p;
+    wo_planet* p = c.p; wo_erode_block& B = *p->erode; auto& S = B.scratch;
     c.clk.begin("glacial");
-    Fields F = p->fields();
+    Fields F = fields(p);
     ice_flow(c, F);
     launch(p, FAM_CARVE_SETUP, k_carve_setup_cells, c.gridN, WO_BLOCK, F);
-    select_active_by_rank(p, F.arank, p->d_listB, p->d_counters + 3);     // the active tasks in landCells order
-    const int32_t active = read_count(p, p->d_counters + 3);
+    select_active_by_rank(p, F.arank, S.listB, S.counters + 3);     // the active tasks in landCells order
+    const int32_t active = read_count(p, S.counters + 3);
     c.carveActive += active; ensure_carve_capacity(p, active);
-    F.carveDeps = p->d_carveDeps; F.carveDepCnt = p->d_carveDepCnt; F.carveDepPos = p->d_carveDepPos;
+    F.carveDeps = B.carve.deps; F.carveDepCnt = B.carve.depCnt; F.carveDepPos = B.carve.depPos;
     if (active > 0) c.carveRounds += carve_launches(c, F, active);
     launch(p, FAM_MORAINE, k_moraine_fjord, c.gridN, WO_BLOCK, F, c.gDep, c.gFjord);
     c.clk.end();
@@ -367,25 +372,20 @@ static void glacial_step_exact(ErodeCall& c) {
 // The two-level flow accumulation's buffers (k_flow_tiles)
 static FlowTiles flow_tiles_buffers(wo_planet* p) {
     const size_t N = (size_t)p->N;
-    if (!p->d_ftLr) {
-        // (lr, which says that the buffers are there, last)
-        DeviceArena& a = p->mem;
-        if (!p->d_ftParent) p->d_ftParent = a.dev<int32_t>(N);
-        if (!p->d_ftExtCnt) p->d_ftExtCnt = a.dev<int32_t>(N);
-        if (!p->d_ftInflow) p->d_ftInflow = a.dev<uint32_t>(N);
-        if (!p->d_ftRootAcc) p->d_ftRootAcc = a.dev<unsigned long long>(N);
-        p->d_ftLr = a.dev<int32_t>(N);
-        WO_HIP(hipMemsetAsync(p->d_ftInflow, 0, N * 4, p->ctx->stream)); WO_HIP(hipMemsetAsync(p->d_ftExtCnt, 0, N * 4, p->ctx->stream));
-    }
+    wo_erode_block& B = *p->erode; auto& T = B.tiles;
+    build_group(B, T, [&](DeviceArena& a) {
+        T.parent = a.dev<int32_t>(N); T.extCnt = a.dev<int32_t>(N); T.inflow = a.dev<uint32_t>(N); T.rootAcc = a.dev<unsigned long long>(N); T.lr = a.dev<int32_t>(N);
+        WO_HIP(hipMemsetAsync(T.inflow, 0, N * 4, p->ctx->stream)); WO_HIP(hipMemsetAsync(T.extCnt, 0, N * 4, p->ctx->stream));
+    });
     FlowTiles FT{};
-    FT.lr = p->d_ftLr; FT.parent = p->d_ftParent; FT.rootAcc = p->d_ftRootAcc; FT.inflow = p->d_ftInflow; FT.extCnt = p->d_ftExtCnt;
+    FT.lr = T.lr; FT.parent = T.parent; FT.rootAcc = T.rootAcc; FT.inflow = T.inflow; FT.extCnt = T.extCnt;
     return FT;
 }
 static int flow_tile_count(int32_t L) { return (int)(((int64_t)L + FT_CELLS - 1) / FT_CELLS); }
 // The receivers pass (+ the flow's start state and donor counts, + the start state of the basin layout's search), then the layout's fork
 static void erode_receivers(ErodeCall& c, const Fields& F, const FlowTiles& FT, int32_t* donorCnt, bool basin, bool slotIdentity, bool tilesBeforeFork) {
-    wo_planet* p = c.p; hipStream_t s = p->ctx->stream;
-    Fields Fr = F; if (basin) Fr.basinJ = p->d_basinJ;          // (the layout's start state)
+    wo_planet* p = c.p; hipStream_t s = p->ctx->stream; wo_erode_block& B = *p->erode;
+    Fields Fr = F; if (basin) Fr.basinJ = B.basin.J;          // (the layout's start state)
     c.clk.begin("receivers");
     launch(p, FAM_RECEIVERS, k_receivers_flow_init, c.gridL, WO_BLOCK, Fr, donorCnt);
     c.clk.end();
@@ -398,88 +398,87 @@ static void erode_receivers(ErodeCall& c, const Fields& F, const FlowTiles& FT, 
     ensure_side_stream(p);
     if (tilesBeforeFork) {
         // (the root links too before the fork: beside the layout's first kernel — high-priority stream — they took 33 us instead of 15; flow stage 45.9 -> 43.8 ms per step, profiles/r05h_*)
-        launch(p, FAM_FLOW_TILES, k_flow_tiles<false>, flow_tile_count(p->L), FT_THREADS, F, FT);
-        launch(p, FAM_FLOW_TILES, k_flow_root_links, blocks_for(p->L, 4096), WO_BLOCK, F, FT);
+        launch(p, FAM_FLOW_TILES, k_flow_tiles<false>, flow_tile_count(B.L), FT_THREADS, F, FT);
+        launch(p, FAM_FLOW_TILES, k_flow_root_links, blocks_for(B.L, 4096), WO_BLOCK, F, FT);
     }
-    WO_HIP(hipEventRecord(p->evFork, s));
-    WO_HIP(hipStreamWaitEvent(p->side, p->evFork, 0));
-    p->onSide = true;
-    try { basin_layout(p, slotIdentity); } catch (...) { p->onSide = false; throw; }
-    p->onSide = false;
-    WO_HIP(hipEventRecord(p->evJoin, p->side));
+    WO_HIP(hipEventRecord(B.side.fork, s));
+    WO_HIP(hipStreamWaitEvent(B.side.stream, B.side.fork, 0));
+    B.side.on = true;
+    try { basin_layout(p, slotIdentity); } catch (...) { B.side.on = false; throw; }
+    B.side.on = false;
+    WO_HIP(hipEventRecord(B.side.join, B.side.stream));
 }
 // Flow accumulation = subtree sizes of the forward forest (integers: any order of the additions is exact): in two levels under the mirror
 // (kernels_impl.h: k_flow_tiles), else one launch in which every leaf hands its total to its receiver and the thread that completes a
 // receiver carries on with it (k_flow_climb).  Every cell with a forward receiver is retired either way; k_flow_final reads the packed totals.
 // (10 M cells, flow stage per step: round 2's rake rounds + pointer doubling 108 ms, the climb 45, two levels 29: profiles/r02r_*, r05g_*.)
 static void erode_flow(ErodeCall& c, const Fields& F, const FlowTiles& FT, int32_t* donorCnt, bool flowTiles, bool tilesBeforeFork, bool clearOut) {
-    wo_planet* p = c.p;
+    wo_planet* p = c.p; wo_erode_block& B = *p->erode; auto& S = B.scratch;
     c.clk.begin("flow");
     if (flowTiles) {
-        const int tiles = flow_tile_count(p->L);
+        const int tiles = flow_tile_count(B.L);
         if (!tilesBeforeFork) {
             launch(p, FAM_FLOW_TILES, k_flow_tiles<false>, tiles, FT_THREADS, F, FT);
-            launch(p, FAM_FLOW_TILES, k_flow_root_links, blocks_for(p->L, 4096), WO_BLOCK, F, FT);
+            launch(p, FAM_FLOW_TILES, k_flow_root_links, blocks_for(B.L, 4096), WO_BLOCK, F, FT);
         }
-        launch(p, FAM_FLOW_TILES, k_flow_root_climb, blocks_for(p->L, 4096), WO_BLOCK, F, FT);
+        launch(p, FAM_FLOW_TILES, k_flow_root_climb, blocks_for(B.L, 4096), WO_BLOCK, F, FT);
         launch(p, FAM_FLOW_TILES, k_flow_tiles<true>, tiles, FT_THREADS, F, FT);
     } else
-        launch(p, FAM_FLOW_SNAP, k_flow_climb, c.gridL, WO_BLOCK, F, (const int32_t*)p->d_flowCnt, (int32_t)0x7fffffff);
+        launch(p, FAM_FLOW_SNAP, k_flow_climb, c.gridL, WO_BLOCK, F, (const int32_t*)S.flowCnt, (int32_t)0x7fffffff);
     Fields Ff = F;
     if (p->opt.relaxedFull) Ff.ev = nullptr;                // (no event lists: the relaxed solve has no order)
     // the solve's outputs are cleared (tags 0) only for a pass whose result is checked on the spot (k_solve_patch / k_solve_final read
     // the tags as launch numbers); the unchecked pass stamps them with a tag of its own instead (erode_solve_basin): 16 B per land cell less to write
-    launch(p, FAM_FLOW_FINAL, k_flow_final, c.gridL, WO_BLOCK, Ff, donorCnt, clearOut ? p->d_out : (SolveOut*)nullptr);
+    launch(p, FAM_FLOW_FINAL, k_flow_final, c.gridL, WO_BLOCK, Ff, donorCnt, clearOut ? S.out : (SolveOut*)nullptr);
     c.clk.end();
 }
 // Exact mode: the basin-local solve, once the layout on the side stream has joined
 static void erode_solve_basin(ErodeCall& c, Fields F, int32_t iter) {
-    wo_planet* p = c.p; hipStream_t s = p->ctx->stream;
-    WO_HIP(hipStreamWaitEvent(s, p->evJoin, 0));
-    F.slotOf = p->d_basinSlot; F.solveLean = 1;
+    wo_planet* p = c.p; hipStream_t s = p->ctx->stream; wo_erode_block& B = *p->erode; auto& S = B.scratch;
+    WO_HIP(hipStreamWaitEvent(s, B.side.join, 0));
+    F.slotOf = B.basin.slot; F.solveLean = 1;
     // (the outputs' tags were cleared by k_flow_final: one coalesced sweep instead of one scattered 16-byte write per task)
     // an unchecked pass: the solve launch writes the final heights itself (SolveTask finality flags) and no k_solve_final then
     const bool unchecked = !c.checkEveryPass; F.solveFinals = unchecked ? 1 : 0;
     // (the setup launch also clears the counters and pending totals of the solve launches: run_solve_patches)
-    launch(p, FAM_SOLVE_SETUP, k_solve_setup_batched<true>, c.gridL, WO_BLOCK, F, p->d_patchPending, (int32_t)p->numPatches, p->d_patchTotals, (int32_t)WO_PATCH_TOTAL_SLOTS);
+    launch(p, FAM_SOLVE_SETUP, k_solve_setup_batched<true>, c.gridL, WO_BLOCK, F, S.patchPending, (int32_t)S.numPatches, S.patchTotals, (int32_t)WO_PATCH_TOTAL_SLOTS);
     // the unchecked pass's one launch tags what it produces with a number no earlier pass of this planet used
     int32_t passTag = 1;
     if (unchecked) {
-        if (p->solvePassSerial >= 0x3ff00000) { WO_HIP(hipMemsetAsync(p->d_out, 0, (size_t)p->N * sizeof(SolveOut), s)); p->solvePassSerial = 0; }
-        passTag = (1 << 20) + (int32_t)(++p->solvePassSerial);
+        if (S.solvePassSerial >= 0x3ff00000) { WO_HIP(hipMemsetAsync(S.out, 0, (size_t)p->N * sizeof(SolveOut), s)); S.solvePassSerial = 0; }
+        passTag = (1 << 20) + (int32_t)(++S.solvePassSerial);
     }
     const int64_t r = run_solve_patches(p, F, c.K, c.m, c.dt, unchecked, passTag);
     ++c.basinPasses; if (r > 1) ++c.basinLeftoverPasses;
     c.patchLaunches += r; c.maxSolve = std::max(c.maxSolve, r);
-    if (!unchecked) launch(p, FAM_SOLVE_FINAL, k_solve_final, c.gridL, WO_BLOCK, F, p->d_e2, (iter < c.tIters) ? p->d_me : (float*)nullptr);
+    if (!unchecked) launch(p, FAM_SOLVE_FINAL, k_solve_final, c.gridL, WO_BLOCK, F, p->d_e2, (iter < c.tIters) ? S.me : (float*)nullptr);
 }
 // RELAXED: h' = a + b h'(receiver) composed by pointer jumping (12 doublings cover chains of 4 096 cells), then heights + deposits in one sweep
 static void erode_solve_affine(ErodeCall& c, const Fields& F) {
-    wo_planet* p = c.p;
-    if (!p->d_affine[1]) p->d_affine[1] = p->mem.dev<Affine>((size_t)p->N);
-    if (!p->d_affine[0]) p->d_affine[0] = p->mem.dev<Affine>((size_t)p->N);
-    launch(p, FAM_SOLVE_SETUP, k_affine_init, c.gridL, WO_BLOCK, F, p->d_affine[0]);
+    wo_planet* p = c.p; wo_erode_block& B = *p->erode;
+    build_group(B, B.affine, [&](DeviceArena& a) { B.affine.buf[1] = a.dev<Affine>((size_t)p->N); B.affine.buf[0] = a.dev<Affine>((size_t)p->N); });
+    launch(p, FAM_SOLVE_SETUP, k_affine_init, c.gridL, WO_BLOCK, F, B.affine.buf[0]);
     int cur = 0;
-    for (int q = 0; q < 12; ++q, cur ^= 1) launch(p, FAM_SOLVE_ROUND, k_affine_jump, c.gridL, WO_BLOCK, F, (const Affine*)p->d_affine[cur], p->d_affine[cur ^ 1]);
-    launch(p, FAM_SOLVE_FINAL, k_affine_apply, c.gridL, WO_BLOCK, F, (const Affine*)p->d_affine[cur], p->d_e2);
+    for (int q = 0; q < 12; ++q, cur ^= 1) launch(p, FAM_SOLVE_ROUND, k_affine_jump, c.gridL, WO_BLOCK, F, (const Affine*)B.affine.buf[cur], B.affine.buf[cur ^ 1]);
+    launch(p, FAM_SOLVE_FINAL, k_affine_apply, c.gridL, WO_BLOCK, F, (const Affine*)B.affine.buf[cur], p->d_e2);
 }
 // The hydraulic step: receivers, flow accumulation, the implicit solve (exact: basin-local, basin.hip; relaxed: the affine recurrence)
 static void hydraulic_step(ErodeCall& c, int32_t iter) {
-    wo_planet* p = c.p;
-    Fields F = p->fields();
+    wo_planet* p = c.p; wo_erode_block& B = *p->erode; auto& S = B.scratch;
+    Fields F = fields(p);
     F.solveK = c.K; F.solveM = c.m; F.solveDt = c.dt;
     const bool basin = !p->opt.relaxedFull;
     const bool slotIdentity = c.mir.on && p->mirror.h_mask.size() == (size_t)p->N;          // land-first mirror: a land cell's Morton slot is its id
-    if (basin) { basin_alloc(p); F.basinMslot = slotIdentity ? nullptr : p->d_slotOf; }
+    if (basin) { basin_alloc(p); F.basinMslot = slotIdentity ? nullptr : S.slotOf; }
     // two-level accumulation (k_flow_tiles): needs the land cells to be the ids 0 .. L-1 in Morton order (land-first mirror); on the planet's
     // own cell order (WO_LAYOUT=index) the one-launch climb over all cells (k_flow_climb)
-    const bool flowTiles = p->landIdentity;
+    const bool flowTiles = S.identity;
     FlowTiles FT = flowTiles ? flow_tiles_buffers(p) : FlowTiles{};
     // the two-level accumulation's first kernel also shortens the layout's start state inside every tile (k_flow_tiles<false>: J[c] <- an
     // ancestor at most a tile away), so it runs before the fork and the layout's component search starts from chains of tiles instead of cells
     const bool tilesBeforeFork = basin && flowTiles && slotIdentity;
-    if (tilesBeforeFork) FT.basinJ = p->d_basinJ;
-    int32_t* const donorCnt = flowTiles ? (int32_t*)nullptr : p->d_flowCnt;
+    if (tilesBeforeFork) FT.basinJ = B.basin.J;
+    int32_t* const donorCnt = flowTiles ? (int32_t*)nullptr : S.flowCnt;
     erode_receivers(c, F, FT, donorCnt, basin, slotIdentity, tilesBeforeFork);
     erode_flow(c, F, FT, donorCnt, flowTiles, tilesBeforeFork, basin && c.checkEveryPass);
     c.clk.begin("solve");
@@ -490,7 +489,7 @@ static void hydraulic_step(ErodeCall& c, int32_t iter) {
 static void thermal_step(ErodeCall& c, bool afterSolve) {
     wo_planet* p = c.p;
     c.clk.begin("thermal");
-    const Fields F = p->fields();
+    const Fields F = fields(p);
     if (!afterSolve) launch(p, FAM_THERMAL_EXCESS, k_masked_elev, c.gridL, WO_BLOCK, F);      // else written by the solve
     launch(p, FAM_THERMAL_EXCESS, k_thermal_excess, c.gridL, WO_BLOCK, F, c.talus);
     if (p->maxDeg <= 12) launch(p, FAM_THERMAL_APPLY, k_thermal_apply_reg<12>, c.gridL, WO_BLOCK, F, p->d_e2, c.talus, c.kThermal);
@@ -508,14 +507,15 @@ static void erode_composite(wo_planet* p, int32_t hIters, double K, double m, do
     p->floodX.calls = 0; p->floodX.gathers = 0; p->floodX.globalFloods = 0; p->floodX.received = 0;       // per call (the stats of a step, not of the planet's life)
     if (c.total <= 0) return;
     ensure_scratch(p);
+    wo_erode_block& B = *p->erode; auto& S = B.scratch;
     hipStream_t s = p->ctx->stream;
-    if (hIters > 0) WO_HIP(hipMemsetAsync(p->d_flowCnt, 0, (size_t)p->N * sizeof(int32_t), s));   // k_flow_final keeps it zero between iterations; a call that was cut short may not have
-    if (hIters > 0 && p->d_ftInflow) { WO_HIP(hipMemsetAsync(p->d_ftInflow, 0, (size_t)p->N * 4, s)); WO_HIP(hipMemsetAsync(p->d_ftExtCnt, 0, (size_t)p->N * 4, s)); }   // (k_flow_tiles<true> keeps them zero)
+    if (hIters > 0) WO_HIP(hipMemsetAsync(S.flowCnt, 0, (size_t)p->N * sizeof(int32_t), s));   // k_flow_final keeps it zero between iterations; a call that was cut short may not have
+    if (hIters > 0 && B.tiles.built) { WO_HIP(hipMemsetAsync(B.tiles.inflow, 0, (size_t)p->N * 4, s)); WO_HIP(hipMemsetAsync(B.tiles.extCnt, 0, (size_t)p->N * 4, s)); }   // (k_flow_tiles<true> keeps them zero)
     if (!erode_setup(c)) return;
     if (hIters > 0) erode_flood(c, 0.5);
 
     const bool glacial = c.gIters > 0 && c.gStrength > 0;
-    if (glacial) launch(p, FAM_GLAC_INDEX, k_glac_index, c.gridN, WO_BLOCK, p->fields(), c.gStrength);
+    if (glacial) launch(p, FAM_GLAC_INDEX, k_glac_index, c.gridN, WO_BLOCK, fields(p), c.gStrength);
     // (round 2's river-aligned patch lists, WO_RIVER_PATCHES, were measured and dropped: profiles/r02c_river_patch_experiment.txt)
     // (one composite iteration as a hipGraph — captured once per call, replayed 167 times — was built and measured in round 4: 499.5 ms per step against 384.1 with
     // plain launches, profiles/r04j_*: a graph launch costs more than the ~25 stream launches it replaces; removed in round 6)
@@ -542,7 +542,7 @@ static void erode_composite(wo_planet* p, int32_t hIters, double K, double m, do
     leftovers_so_far(c);
     if (glacial) {
         c.clk.begin("glacial_blend");
-        launch(p, FAM_GLAC_BLEND, k_glacial_blend, c.gridN, WO_BLOCK, p->fields(), (const float*)p->d_e, p->d_e2);
+        launch(p, FAM_GLAC_BLEND, k_glacial_blend, c.gridN, WO_BLOCK, fields(p), (const float*)p->d_e, p->d_e2);
         swap_elev(p);
         c.clk.end();
     }
@@ -563,21 +563,27 @@ static void erode_composite_checked(wo_planet* p, int32_t hIters, double K, doub
     // collectives with its peers: a rank that ran the call a second time would repeat them alone (its peers are past them and no longer hold
     // that call's heights).  Such a call is therefore checked pass by pass from the start — pending tasks are finished where they arise and
     // nothing is ever run again.
+    if (!p->erode) p->erode = new wo_erode_block();          // made by the planet's first call
     if (hIters <= 0 || p->floodX.on) { erode_composite(p, hIters, K, m, dt, tIters, talus, kThermal, gIters, gStrength, true); return; }
     hipStream_t s = p->ctx->stream;
-    if (!p->d_redoE) p->d_redoE = p->mem.dev<float>((size_t)p->N);
-    if (!p->d_pendingEver) p->d_pendingEver = p->mem.dev<int32_t>(16);
-    WO_HIP(hipMemcpyAsync(p->d_redoE, p->d_e, (size_t)p->N * sizeof(float), hipMemcpyDeviceToDevice, s));
-    WO_HIP(hipMemsetAsync(p->d_pendingEver, 0, 16 * sizeof(int32_t), s));
+    wo_erode_block& B = *p->erode;
+    build_group(B, B.redo, [&](DeviceArena& a) { B.redo.e = a.dev<float>((size_t)p->N); B.redo.pendingEver = a.dev<int32_t>(16); });
+    WO_HIP(hipMemcpyAsync(B.redo.e, p->d_e, (size_t)p->N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    WO_HIP(hipMemsetAsync(B.redo.pendingEver, 0, 16 * sizeof(int32_t), s));
     try {
         erode_composite(p, hIters, K, m, dt, tIters, talus, kThermal, gIters, gStrength, false);
     } catch (const RedoWithChecks&) {
         WO_HIP(hipStreamSynchronize(s));
-        if (p->side) WO_HIP(hipStreamSynchronize(p->side));
-        WO_HIP(hipMemcpyAsync(p->d_e, p->d_redoE, (size_t)p->N * sizeof(float), hipMemcpyDeviceToDevice, s));
-        ++p->redoCalls;
+        if (B.side.built) WO_HIP(hipStreamSynchronize(B.side.stream));
+        WO_HIP(hipMemcpyAsync(p->d_e, B.redo.e, (size_t)p->N * sizeof(float), hipMemcpyDeviceToDevice, s));
+        ++B.redo.calls;
         erode_composite(p, hIters, K, m, dt, tIters, talus, kThermal, gIters, gStrength, true);
     }
+}
+
+void erode_free(wo_planet* p) {
+    if (p->erode) side_destroy(p->erode->side);
+    delete p->erode; p->erode = nullptr;
 }
 
 }  // namespace wo

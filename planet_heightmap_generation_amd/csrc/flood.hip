@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "device.h"
+#include "erode_block.h"
 #include "flood.h"
 #include "flood_kernels.h"
 #include "stage_clock.h"
@@ -171,7 +172,7 @@ bool flood_land_is_mirror_prefix(wo_planet* p) {
     const FloodScratch& S = p->flood;
     if (p->floodPrefixMirror != M.version || p->floodPrefixStatic != S.staticVersion) {
         p->floodPrefixMirror = M.version; p->floodPrefixStatic = S.staticVersion;
-        p->floodPrefixOk = S.L == p->L && M.h_perm.size() == (size_t)p->N && (size_t)S.L <= M.h_perm.size() &&
+        p->floodPrefixOk = p->erode && S.L == p->erode->L && M.h_perm.size() == (size_t)p->N && (size_t)S.L <= M.h_perm.size() &&
                            std::memcmp(M.h_perm.data(), S.landCell.data(), sizeof(int32_t) * (size_t)S.L) == 0;
     }
     return p->floodPrefixOk;

@@ -16,6 +16,7 @@
 
 #include "common_kernels.h"
 #include "device.h"
+#include "erode_ops.h"
 #include "mirror.h"
 #include "stage_clock.h"
 

@@ -11,18 +11,24 @@
 #include "../../include/worogen.h"
 #include "common_kernels.h"
 #include "device.h"
-
-wo::Fields wo_planet::fields() const {
-    wo::Fields F{};
-    F.N = N; F.xcdTile = wo::xcd_tile(N); F.tileLds = opt.tileLds ? 1 : 0; F.off = d_off; F.adj = d_adj; F.dist = d_dist; F.xyz = d_xyz; F.ocean = d_ocean; F.coast = d_coast;
-    F.e = d_e; F.e2 = d_e2; F.L = L; F.land = d_land[landCur]; F.landIdx = landIdentity ? nullptr : d_landIdx; F.xcdTileL = wo::xcd_tile(L > 0 ? L : 1); F.rank = d_rank; F.target = nullptr; F.tr = d_tr; F.ev = d_ev; F.me = d_me; F.carveSlot = d_carveSlot; F.carveDeps = nullptr; F.carveDepCnt = d_carveDepCnt; F.carveDepPos = d_carveDepPos; F.cellDist = d_cellDist;
-    F.flow = d_flow; F.accA = nullptr; F.accB = nullptr; F.accCnt = d_accCnt; F.jumpA = d_jump; F.jumpB = nullptr;
-    F.task = d_task; F.out = d_out; F.slotOf = (patchVersion >= 0) ? d_slotOf : nullptr; F.blk = d_patchBlk; F.doneAt = d_doneAt;
-    F.totalExcess = d_totalExcess; F.glac = d_glac; F.iceTarget = d_iceTarget; F.iceFlow = d_iceFlow; F.iceUp = d_iceUp; F.arank = d_arank; F.blocker = d_nj;
-    return F;
-}
+#include "erode_block.h"
 
 namespace wo {
+
+hipStream_t cur_stream(const wo_planet* p) { return (p->erode && p->erode->side.on && p->erode->side.stream) ? p->erode->side.stream : p->ctx->stream; }
+
+Fields fields(const wo_planet* p) {
+    Fields F{};
+    F.N = p->N; F.xcdTile = xcd_tile(p->N); F.tileLds = p->opt.tileLds ? 1 : 0; F.off = p->d_off; F.adj = p->d_adj; F.dist = p->d_dist; F.xyz = p->d_xyz; F.ocean = p->d_ocean; F.coast = p->d_coast;
+    F.e = p->d_e; F.e2 = p->d_e2; F.xcdTileL = xcd_tile(1);
+    if (!p->erode) return F;                 // (a planet that never eroded: the Jacobi and warp kernels read the mesh and the field only)
+    const wo_erode_block& B = *p->erode; const auto& S = B.scratch;
+    F.L = B.L; F.land = S.land[S.cur]; F.landIdx = S.identity ? nullptr : S.landIdx; F.xcdTileL = xcd_tile(B.L > 0 ? B.L : 1); F.rank = S.rank; F.tr = S.tr; F.ev = S.ev; F.me = S.me; F.carveSlot = S.carveSlot; F.carveDepCnt = B.carve.depCnt; F.carveDepPos = B.carve.depPos; F.cellDist = S.cellDist;
+    F.flow = S.flow; F.accCnt = S.accCnt; F.jumpA = S.jump;
+    F.task = S.task; F.out = S.out; F.slotOf = (S.patchVersion >= 0) ? S.slotOf : nullptr; F.blk = S.patchBlk; F.doneAt = S.doneAt;
+    F.totalExcess = S.totalExcess; F.glac = S.glac; F.iceTarget = S.iceTarget; F.iceFlow = S.iceFlow; F.iceUp = S.iceUp; F.arank = S.arank; F.blocker = S.nj;
+    return F;
+}
 
 __global__ __launch_bounds__(WO_BLOCK) void k_ocean_from_elev(const float* e, uint8_t* ocean, int32_t N) {
     WO_GRID_STRIDE(r, N) ocean[r] = (e[r] <= 0.0f) ? 1 : 0;
@@ -236,15 +242,13 @@ void wo_planet_destroy(wo_planet* p) {
     if (!p) return;
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
-    if (p->side) { (void)hipStreamSynchronize(p->side); (void)hipStreamDestroy(p->side); p->side = nullptr; }
-    if (p->evFork) { (void)hipEventDestroy(p->evFork); p->evFork = nullptr; }
-    if (p->evJoin) { (void)hipEventDestroy(p->evJoin); p->evJoin = nullptr; }
     if (p->floodLink && p->floodLinkFree) p->floodLinkFree(p->floodLink);
     p->floodLink = nullptr;
     highlight_free(p);
     map_free(p);
     temp_free(p);
     rivers_free(p);
+    erode_free(p);
     precip_free(p);
     ocean_free(p);
     wind_free(p);

@@ -4,6 +4,7 @@
 
 #include "../../include/worogen.h"
 #include "device.h"
+#include "erode_block.h"
 
 namespace wo {
 
@@ -28,7 +29,7 @@ hipEvent_t profile_event(wo_planet* p) {
 void profile_resolve(wo_planet* p) {
     if (p->pending.empty()) return;
     WO_HIP(hipStreamSynchronize(p->ctx->stream));
-    if (p->side) WO_HIP(hipStreamSynchronize(p->side));
+    if (p->erode && p->erode->side.built) WO_HIP(hipStreamSynchronize(p->erode->side.stream));
     for (auto& pe : p->pending) {
         float ms = 0; WO_HIP(hipEventElapsedTime(&ms, pe.a, pe.b));
         p->famMs[pe.fam] += ms; p->famLaunches[pe.fam] += 1;

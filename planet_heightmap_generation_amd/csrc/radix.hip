@@ -25,7 +25,7 @@
 #include <cstdint>
 #include <cstdlib>
 
-#include "device.h"
+#include "erode_block.h"
 
 namespace wo {
 
@@ -197,40 +197,32 @@ int radix_sort_pairs(wo_planet* p, int family, uint32_t* const keys[2], int32_t*
     // let a later, larger sort start on totals a smaller one left behind
     if (passes & 1) throw HipError{"radix_sort_pairs: the number of digits must be even"};
     if (n > nMax) throw HipError{"radix_sort_pairs: more pairs than the scratch was sized for"};
-    hipStream_t s = cur_stream(p);
     const int tiles = rs_tiles(n), groups = rs_groups(n);
     const size_t gtWords = (size_t)rs_groups(nMax) * RS_DIGITS;
     uint32_t* counts = scratch + 2 * gtWords;
-    // profiled runs bracket every kernel on its own (as wo::launch does): a family's time is then the sum of its kernels' durations, comparable
-    // with a rocprofv3 kernel trace, and not the length of the whole sort with the gaps a side stream waits in
-    auto bracketed = [&](auto&& launchIt) {
-        hipEvent_t a = nullptr, b = nullptr;
-        if (p->profiling) { a = profile_event(p); b = profile_event(p); WO_HIP(hipEventRecord(a, s)); }
-        launchIt();
-        if (p->profiling) { WO_HIP(hipEventRecord(b, s)); p->pending.push_back({family, a, b}); if (p->pending.size() >= 4096) profile_resolve(p); }
-    };
+    // (profiled runs bracket every kernel on its own: a family's time is then the sum of its kernels' durations, comparable with a
+    // rocprofv3 kernel trace, and not the length of the whole sort with the gaps a side stream waits in)
     int cur = 0;
     for (int q = 0; q < passes; ++q, ++flip) {
         uint32_t* gt = scratch + (size_t)(flip & 1) * gtWords;
         uint32_t* gtOther = scratch + (size_t)((flip + 1) & 1) * gtWords;
-        bracketed([&] { hipLaunchKernelGGL(k_rs_count, dim3(tiles), dim3(RS_THREADS), 0, s, (const uint32_t*)keys[cur], n, beginBit + 8 * q, counts, gt); });
-        bracketed([&] { hipLaunchKernelGGL(k_rs_scatter, dim3(tiles), dim3(RS_THREADS), 0, s, (const uint32_t*)keys[cur], (const int32_t*)vals[cur], keys[cur ^ 1], vals[cur ^ 1], n,
-                           beginBit + 8 * q, (const uint32_t*)counts, (const uint32_t*)gt, (int32_t)groups, gtOther, (q == passes - 1) ? posOut : (int32_t*)nullptr); });
+        launch(p, family, k_rs_count, tiles, RS_THREADS, (const uint32_t*)keys[cur], n, beginBit + 8 * q, counts, gt);
+        launch(p, family, k_rs_scatter, tiles, RS_THREADS, (const uint32_t*)keys[cur], (const int32_t*)vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, beginBit + 8 * q,
+               (const uint32_t*)counts, (const uint32_t*)gt, (int32_t)groups, gtOther, (q == passes - 1) ? posOut : (int32_t*)nullptr);
         cur ^= 1;
     }
-    WO_HIP(hipGetLastError());
     return cur;
 }
 
-uint32_t* radix_scratch(wo_planet* p, int which) {
-    if (!p->d_rs[which]) {
+wo_erode_block::Radix& radix_scratch(wo_planet* p, int which) {
+    wo_erode_block& B = *p->erode; auto& R = B.radix[which];
+    build_group(B, R, [&](DeviceArena& a) {
         const size_t words = radix_scratch_words(p->N);
-        uint32_t* rs = p->mem.dev<uint32_t>(words);
-        WO_HIP(hipMemsetAsync(rs, 0, words * 4, cur_stream(p)));
-        p->d_rs[which] = rs;
-        p->rsFlip[which] = 0;
-    }
-    return p->d_rs[which];
+        R.words = a.dev<uint32_t>(words);
+        WO_HIP(hipMemsetAsync(R.words, 0, words * 4, cur_stream(p)));
+        R.flip = 0;
+    });
+    return R;
 }
 
 }  // namespace wo

@@ -4,12 +4,7 @@
 // in the previous order reproduces that exactly; keys map -0 and +0 to the same value (erode_ops.h).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdio>
-#include <string>
-#include <cstdlib>
-
-#include "device.h"
+#include "erode_block.h"
 
 namespace wo {
 
@@ -26,7 +21,8 @@ __global__ __launch_bounds__(WO_BLOCK) void k_rank_scatter(const int32_t* __rest
 
 // rank[] for the current (e.g. initial ascending-r) order without sorting
 void rank_from_land(wo_planet* p) {
-    launch(p, FAM_RANK, k_rank_scatter, blocks_for(p->L, 4096), WO_BLOCK, (const int32_t*)p->d_land[p->landCur], p->d_rank, p->L);
+    wo_erode_block& B = *p->erode; auto& S = B.scratch;
+    launch(p, FAM_RANK, k_rank_scatter, blocks_for(B.L, 4096), WO_BLOCK, (const int32_t*)S.land[S.cur], S.rank, B.L);
 }
 
 // The active carve tasks in landCells order: the cells of the current order whose arank is set, order kept (stable selection).
@@ -83,10 +79,10 @@ __global__ __launch_bounds__(WO_BLOCK) void k_sel_scatter(const int32_t* __restr
     for (int q = 0; q < WO_SEL_PER_THREAD; ++q) if (on[q]) out[at++] = cell[q];
 }
 void select_active_by_rank(wo_planet* p, const int32_t* arank, int32_t* out, int32_t* outCount) {
-    const int32_t L = p->L;
+    wo_erode_block& B = *p->erode; auto& S = B.scratch; const int32_t L = B.L;
     const int nTiles = (int)(((int64_t)L + WO_SEL_TILE - 1) / WO_SEL_TILE);
-    int32_t* tileCnt = reinterpret_cast<int32_t*>(p->d_sortTemp);
-    const int32_t* land = p->d_land[p->landCur];
+    int32_t* tileCnt = reinterpret_cast<int32_t*>(S.sortTemp);
+    const int32_t* land = S.land[S.cur];
     launch(p, FAM_CARVE_SETUP, k_sel_count, nTiles, WO_BLOCK, land, arank, L, tileCnt);
     launch(p, FAM_CARVE_SETUP, k_sel_scan, 1, WO_BLOCK, tileCnt, (int32_t)nTiles, outCount);
     launch(p, FAM_CARVE_SETUP, k_sel_scatter, nTiles, WO_BLOCK, land, arank, L, (const int32_t*)tileCnt, out);
@@ -96,19 +92,20 @@ void select_active_by_rank(wo_planet* p, const int32_t* arank, int32_t* out, int
 size_t sort_temp_bytes(int32_t n) { return ((size_t)n / WO_SEL_TILE + 2) * sizeof(int32_t); }
 
 void sort_land_by_elevation(wo_planet* p) {
-    const int32_t L = p->L;
-    const int cur = p->landCur;
+    wo_erode_block& B = *p->erode; auto& S = B.scratch; const int32_t L = B.L;
+    const int cur = S.cur;
     // (measured in round 4: the keys made inside the first counting pass of the sort instead of by a launch of their own — sort stage 34.6 ms per step against
     // 33.1: the counting pass's 679 workgroups gather the heights more slowly than this grid does.  Round 5: the keys written by the thermal step of the
     // previous iteration, keys[rank[cell]] — sort 33.1 -> 28.3 ms per step, thermal 37.6 -> 44.2: profiles/r05z_*; removed.  The library sort
     // (hipcub::DeviceRadixSort, 253 us per sort against 150) was a cross-check route until round 6; 11-bit digits with rocPRIM's onesweep: 180 us per pass
     // against 32, profiles/r03aj_*.)
-    launch(p, FAM_SORT_KEYS, k_sort_keys, blocks_for(L, 4096), WO_BLOCK, (const float*)p->d_e, (const int32_t*)p->d_land[cur], p->d_keys[0], L);
+    launch(p, FAM_SORT_KEYS, k_sort_keys, blocks_for(L, 4096), WO_BLOCK, (const float*)p->d_e, (const int32_t*)S.land[cur], S.keys[0], L);
     // the in-tree stable sort (radix.hip); its last pass also writes rank[cell] = position
-    uint32_t* const kb[2] = {p->d_keys[0], p->d_keys[1]};
-    int32_t* const vb[2] = {p->d_land[cur], p->d_land[cur ^ 1]};
-    const int r = radix_sort_pairs(p, FAM_SORT_RADIX, kb, vb, L, 0, 32, p->d_rank, radix_scratch(p, 0), p->N, p->rsFlip[0]);
-    p->landCur = r == 0 ? cur : (cur ^ 1);
+    uint32_t* const kb[2] = {S.keys[0], S.keys[1]};
+    int32_t* const vb[2] = {S.land[cur], S.land[cur ^ 1]};
+    auto& R = radix_scratch(p, 0);
+    const int r = radix_sort_pairs(p, FAM_SORT_RADIX, kb, vb, L, 0, 32, S.rank, R.words, p->N, R.flip);
+    S.cur = r == 0 ? cur : (cur ^ 1);
 }
 
 }  // namespace wo

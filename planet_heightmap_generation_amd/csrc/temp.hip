@@ -23,6 +23,7 @@
 
 #include "../../include/worogen.h"
 #include "device.h"
+#include "erode_block.h"
 #include "ocean_block.h"
 #include "precip_block.h"
 #include "temp_ops.h"
@@ -170,7 +171,7 @@ static void temp_run(wo_planet* p, const float* r_elevation, double temperatureO
     float* raw[2] = {T.dev<float>(n), T.dev<float>(n)};
     const TempArgs A{Wb->lat, Wb->lon, e, Wb->cont, Wb->plateCont, Wb->isLand, {Pb->out[PF_PRECIP0], Pb->out[PF_PRECIP0 + 1]}, {warm[0], warm[1]}, {speed[0], speed[1]}, coastal, {raw[0], raw[1]}};
     launch(p, FAM_CLIMATE, k_temp_cell, g, WO_BLOCK, A, (const float*)itcz, temperatureOffset, N);
-    launch(p, FAM_CLIMATE, k_temp_smooth, xg, WO_BLOCK, p->fields(), (const float*)raw[0], (const float*)raw[1], B->out[TF_SUMMER], B->out[TF_WINTER]);
+    launch(p, FAM_CLIMATE, k_temp_smooth, xg, WO_BLOCK, fields(p), (const float*)raw[0], (const float*)raw[1], B->out[TF_SUMMER], B->out[TF_WINTER]);
     WO_HIP(hipStreamSynchronize(s));                          // before T frees the temporaries
     B->info = wo_temperature_info{passes, Tm::SMOOTH_PASSES, launches + 2, 0};
     B->have = kTempBlock.all();

@@ -5,6 +5,7 @@
 #include "../../include/worogen.h"
 #include "common_kernels.h"
 #include "device.h"
+#include "erode_block.h"
 #include "mirror.h"
 #include "noise.h"
 
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(WO_BLOCK) void k_warp(Fields F, const uint8_t* tabl
 }
 
 void coast_flags(wo_planet* p) {
-    launch(p, FAM_COAST, k_coast, xcd_grid(p->N), WO_BLOCK, p->fields(), p->d_coast);
+    launch(p, FAM_COAST, k_coast, xcd_grid(p->N), WO_BLOCK, fields(p), p->d_coast);
 }
 
 static void jacobi(wo_planet* p, int kind, int32_t iterations, double strength) {
@@ -76,7 +77,7 @@ static void jacobi(wo_planet* p, int kind, int32_t iterations, double strength) 
     hipStream_t s = p->ctx->stream;
     if (kind == 1) WO_HIP(hipMemcpyAsync(p->d_orig, p->d_e, (size_t)p->N * sizeof(float), hipMemcpyDeviceToDevice, s));
     for (int32_t it = 0; it < iterations; ++it) {
-        Fields F = p->fields();
+        Fields F = fields(p);
         if (kind == 0) launch(p, FAM_SMOOTH, k_smooth, gridN, WO_BLOCK, F, (const float*)p->d_e, p->d_e2, strength);
         else if (kind == 1) launch(p, FAM_SHARPEN, k_sharpen, gridN, WO_BLOCK, F, (const float*)p->d_e, (const float*)p->d_orig, p->d_e2, strength);
         else launch(p, FAM_CREEP, k_creep, gridN, WO_BLOCK, F, (const float*)p->d_e, p->d_e2, strength);
@@ -107,7 +108,7 @@ static void warp(wo_planet* p, double seed, double strength, bool useHot) {
         mirror_gather_f32(p, p->d_hot, M.hot);
         hot = M.hot;
     }
-    launch(p, FAM_WARP, k_warp, xcd_grid(p->N), WO_BLOCK, p->fields(), (const uint8_t*)p->d_tables, (const float*)p->d_e, p->d_e2,
+    launch(p, FAM_WARP, k_warp, xcd_grid(p->N), WO_BLOCK, fields(p), (const uint8_t*)p->d_tables, (const float*)p->d_e, p->d_e2,
            maxAmp, bias, hot);
     swap_elev(p);
     mir.finish();
