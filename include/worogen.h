@@ -606,6 +606,50 @@ int wo_relief_raster_cube(wo_planet* p, int32_t numSides, const int32_t* triangl
 int wo_relief_download(wo_planet* p, float* out, int64_t outBytes);
 int wo_relief_height16(wo_planet* p, int32_t kind, uint16_t* out, int64_t outBytes);
 int wo_relief_normals(wo_planet* p, int32_t space, double strength, int32_t flags, uint8_t* rgbaOut, int64_t outBytes);
+/* The globe view: the displaced globe mesh of wo_globe_mesh seen through a camera, with a depth per pixel and a Lambert term per
+ *   facet (ours: the reference draws this picture with three.js, whose rasteriser, lighting and tone pipeline are not reproduced;
+ *   csrc/view.hip, the bodies and the whole contract are in csrc/view_ops.h).
+ *   Camera: eye in double, finite and not the origin, looking at the origin; z = eye / |eye|, x = (0, 1, 0) x z normalised ((1, 0, 0)
+ *   where that product is shorter than 1e-12: the view from a pole), y = z x x.  0 < fovY < 180 (degrees) is a perspective camera:
+ *   d = v - eye, a = f (x . d) / zc, b = -f (y . d) / zc with zc = -(z . d) and f = 1 / tan(fovY / 2).  fovY == 0 is an orthographic one
+ *   of half height halfHeight > 0: d = v - 10 z, a = (x . d) / halfHeight, b = -(y . d) / halfHeight.  Positions are stored as f32.  The
+ *   centre of pixel (i, j) of the width x height image is a = (2 (i + 0.5) - width) / height, b = (2 (j + 0.5) - height) / height; row 0
+ *   is the top.  width and height are each from 1 to 16384, odd sizes allowed.
+ *   Vertices are wo_globe_mesh's f32 positions with 0.04 * exaggeration in the place of 0.04 (1: the mesh's bits, 0: the smooth
+ *   sphere; finite and >= 0) from r_elevation (NULL: the planet's resident field).  A side is drawn iff all three zc > 0 (it is
+ *   neither clipped nor split), it faces the camera (n = (v1 - v0) x (v2 - v0) in the mesh's winding; perspective n . (eye - v0) > 0,
+ *   orthographic n . z > 0) and its projected triangle has an area.  Coverage is wo_map_raster's rule (centres, closed edges).  The
+ *   depth of a covered centre is the side's zc there as f32, perspective-correct; the smallest depth wins, among equal depths the
+ *   lowest side; a depth that is not > 0 is not written.  Region: triangles[side], -1 where nothing covers.  Depth: the quiet NaN
+ *   0x7FC00000 where nothing covers.
+ *   wo_view_raster leaves the region map in the planet's map block as a width x height map: wo_map_color, wo_map_color_rivers,
+ *   wo_map_color_layer (outBytes: width * height * 4), wo_map_download, wo_map_dims, wo_map_free and the tints of wo_highlight_set
+ *   serve it, and the next raster of any kind replaces it.  On this block the pixels nothing covers take backgroundRgba (R | G << 8
+ *   | B << 16 | A << 24 as it stands; WO_VIEW_BACKGROUND is the reference's scene colour 0x030308, opaque; 0 is transparent), and with
+ *   shade != 0 each of R, G, B of a covered pixel becomes min(255, floor(c * (ambient + diffuse * lambert) + 0.5)), lambert =
+ *   max(0, nhat . lhat) of the pixel's facet as f32, light the direction towards the light in world space (finite, not zero; the
+ *   reference's sun is (5, 3, 4)), ambient and diffuse finite and >= 0 (0.55 and 0.45 let a facet that faces the light keep its
+ *   colour).  regionMapOut, depthOut (may be NULL): width * height int32 / float; counts (may be NULL): covered and uncovered
+ *   pixels.  The other checks and their messages are wo_map_raster's: otherwise status 1 and the planet keeps what it had.
+ *   wo_view_depth_download copies the depth map (outBytes: width * height * 4); without a view raster as the block's last, status 1,
+ *   "no view raster".  wo_view_lambert_download copies the Lambert terms the shade pass reads (f32 per pixel, 0 where nothing covers;
+ *   the same outBytes); without a raster with shade != 0 as the block's last, status 1, "no shaded view raster". */
+#define WO_VIEW_BACKGROUND 0xFF080303u
+typedef struct wo_view_request {
+    double eye[3];
+    double fovY;                 /* degrees; 0: orthographic                                        */
+    double halfHeight;           /* read when fovY == 0                                             */
+    double exaggeration;
+    const float* r_elevation;    /* numRegions floats, NULL: the resident field                     */
+    int32_t shade;
+    double light[3];             /* read when shade != 0, as are ambient and diffuse                */
+    double ambient, diffuse;
+    uint32_t backgroundRgba;
+} wo_view_request;
+int wo_view_raster(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t width, int32_t height,
+                   const wo_view_request* request, int32_t* regionMapOut, float* depthOut, int64_t counts[2]);
+int wo_view_depth_download(wo_planet* p, float* out, int64_t outBytes);
+int wo_view_lambert_download(wo_planet* p, float* out, int64_t outBytes);
 
 /* ------------------------------------------------ rivers and lakes ---------------------------- */
 /* Rivers and lakes of the final terrain (ours: the reference keeps no drainage beyond the scratch of erodeComposite; csrc/rivers.hip,

@@ -106,6 +106,9 @@ SIGNATURES = {
     "wo_rivers_download": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
     "wo_river_lines": (C.c_int, [_p, _c_f64, _p, _p, _p, _c_i64, _p]),
     "wo_map_color_rivers": (C.c_int, [_p, _c_i32, _p, _c_f64, _p, _c_i64]),
+    "wo_view_raster": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _c_i32, _p, _p, _p, _p]),
+    "wo_view_depth_download": (C.c_int, [_p, _p, _c_i64]),
+    "wo_view_lambert_download": (C.c_int, [_p, _p, _c_i64]),
     "wo_globe_mesh": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _c_i32, _p, _p, _p, _p, _c_i64, _p]),
     "wo_globe_mesh_plates": (C.c_int, [_p, _c_i32, _p, _p, _p, _c_i32, _p, _p, _p, _p, _p, _c_i64, _p]),
     "wo_globe_lines": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _p, _p, _p, _c_i64, _p]),

@@ -117,6 +117,7 @@ WO_IMP_HD inline int64_t pixel_index(int32_t f, int32_t i, int32_t j, int32_t S)
 struct Projection {
     static constexpr int PIECES = 3;
     using Side = float[3][3];                                 // a side's vertices: 3 floats each
+    using Word = uint32_t;                                    // the per-pixel word of the side map
     const float* t_xyz;
     const float* r_xyz;
     int32_t S;
@@ -135,6 +136,8 @@ struct Projection {
     }
     WO_IMP_HD void center(int32_t i, int32_t j, double& xc, double& yc) const { xc = pixel_c(i, S); yc = pixel_c(j, S); }
     WO_IMP_HD int64_t index(int32_t f, int32_t i, int32_t j) const { return pixel_index(f, i, j, S); }      // in the side map
+    // what side s leaves, under a minimum, at a pixel centre that its triangle covers: its index
+    WO_IMP_HD Word word(const Side&, const map::Tri&, double, double, double, uint32_t s) const { return s; }
 };
 
 // the direction of the centre of pixel (i, j) of face f: the major axis is +-1, the other two come from ac and bc through the table

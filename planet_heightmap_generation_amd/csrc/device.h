@@ -62,7 +62,8 @@ enum Family : int {
     FAM_PICK, FAM_PICK_REDUCE, FAM_HIGHLIGHT,
     FAM_CUBE_CENTERS, FAM_CUBE_FILL, FAM_CUBE_SIDES, FAM_CUBE_BIG_BOXES, FAM_CUBE_RESOLVE,
     FAM_RELIEF_TRI_ELEVATION, FAM_RELIEF_HEIGHTS, FAM_RELIEF_HEIGHT16, FAM_RELIEF_TABLES, FAM_RELIEF_NORMALS,
-    FAM_RIVERS, FAM_RIVERS_CLIMB, FAM_RIVERS_LINES, FAM_COUNT
+    FAM_RIVERS, FAM_RIVERS_CLIMB, FAM_RIVERS_LINES,
+    FAM_VIEW_TABLES, FAM_VIEW_FILL, FAM_VIEW_SIDES, FAM_VIEW_BIG_BOXES, FAM_VIEW_RESOLVE, FAM_VIEW_SHADE, FAM_COUNT
 };
 extern const char* const kFamilyNames[FAM_COUNT];
 
@@ -260,6 +261,9 @@ void map_free(wo_planet* p);
 // globe.hip: drops the highlight state; its class bytes (on the device), nullptr when no state is set
 void highlight_free(wo_planet* p);
 const uint8_t* highlight_classes(const wo_planet* p);
+// globe.hip: one launch of its k_globe_centers in family fam: the centre records (globe_ops.h) of every triangle from the elevation e
+namespace globe { struct Center; }
+WO_LOCAL void globe_centers(wo_planet* p, int fam, const int32_t* d_tri, const float* e, globe::Center* out, int32_t numTriangles);
 // temp.hip: the class ids of the planet's Koppen block (one byte per cell, on the device), nullptr when it has no Koppen result
 const uint8_t* koppen_classes(const wo_planet* p);
 // planet.hip: the entry points' handle check (refreshes p->opt from the environment, selects the device)

@@ -78,6 +78,11 @@ __global__ __launch_bounds__(WO_BLOCK) void k_globe_centers(const int32_t* __res
     if (t < numTriangles) out[t] = G::center_of(triangles, xyz, e, t);
 }
 
+// view.hip's way to the kernel above: the globe view reads the same records
+void globe_centers(wo_planet* p, int fam, const int32_t* d_tri, const float* e, G::Center* out, int32_t numTriangles) {
+    launch(p, fam, k_globe_centers, blocks_for(numTriangles), WO_BLOCK, d_tri, (const float*)p->d_xyz, e, out, numTriangles);
+}
+
 // the workgroup's `floats` floats of `stage` to out, 16 bytes per lane and turn; out is 16-byte aligned (a workgroup's share is 9216 bytes)
 __device__ inline void globe_flush(const float* stage, float* __restrict__ out, int32_t floats) {
     const int32_t quads = floats / 4;

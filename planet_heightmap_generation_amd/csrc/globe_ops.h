@@ -57,10 +57,16 @@ WO_IMP_HD inline double disp(float elevation, double base) {
     const double e = (double)elevation;
     return base + (e > 0.0 ? e * V : e * V * 0.3);
 }
+// the same with v in the place of V: the globe view's exaggeration (view_ops.h: v = V * exaggeration; v == V gives disp's bits)
+WO_IMP_HD inline double disp(float elevation, double base, double v) {
+    const double e = (double)elevation;
+    return base + (e > 0.0 ? e * v : e * v * 0.3);
+}
 
-// the nine floats of a side from its two centre records and its region; returns whether the winding was swapped
-WO_IMP_HD inline bool side_positions(const Center& a, const Center& b, const float r[3], float re, float out[9]) {
-    const double d0 = disp(a.e, BASE_MESH), d1 = disp(b.e, BASE_MESH), d2 = disp(re, BASE_MESH);
+// the nine floats of a side from its two centre records and its region, displaced with v in the place of V; returns whether the
+// winding was swapped
+WO_IMP_HD inline bool side_positions(const Center& a, const Center& b, const float r[3], float re, double v, float out[9]) {
+    const double d0 = disp(a.e, BASE_MESH, v), d1 = disp(b.e, BASE_MESH, v), d2 = disp(re, BASE_MESH, v);
     const double v0x = (double)a.x * d0, v0y = (double)a.y * d0, v0z = (double)a.z * d0;
     double v1x = (double)b.x * d1, v1y = (double)b.y * d1, v1z = (double)b.z * d1;
     double v2x = (double)r[0] * d2, v2y = (double)r[1] * d2, v2z = (double)r[2] * d2;
@@ -82,6 +88,8 @@ WO_IMP_HD inline bool side_positions(const Center& a, const Center& b, const flo
     out[6] = (float)v2x; out[7] = (float)v2y; out[8] = (float)v2z;
     return swap;
 }
+// the globe mesh's own
+WO_IMP_HD inline bool side_positions(const Center& a, const Center& b, const float r[3], float re, float out[9]) { return side_positions(a, b, r, re, V, out); }
 
 // ---- lines --------------------------------------------------------------------------------------------------------------------
 WO_IMP_HD inline double line_base(int32_t kind) { return kind == LINES_SUPER_PLATE_BORDERS ? BASE_BORDERS : BASE_WIREFRAME; }

@@ -12,7 +12,8 @@
 // wo_relief_raster is wo_map_raster_centered with a request: after k_map_resolve, while the side map and the two tables still live,
 // relief_heights (relief.hip) adds its height pass; the launches above are the same and so are the region map and the counts.
 // Launches of wo_map_color and wo_map_color_layer: the region colours of view_colors.hip, one packed RGBA per region [1-2], then
-// k_map_pixels [1] (region map -> RGBA8, four pixels per thread).
+// k_map_pixels [1] (region map -> RGBA8, four pixels per thread).  On the block of a globe view (view.hip) the uncovered pixels take
+// the view's background word and, after a shaded raster, k_view_shade [1] follows; a map or cube block paints as it always did.
 // Memory (device_mem.h): the region map lives in a block with an arena of its own on the planet (map_block.h; int32 per pixel; a
 // raster at another width or height, wo_map_raster_cube's included, replaces it, wo_map_free and wo_planet_destroy drop it); the
 // colour tables are temporaries of the call, in an arena on its stack.
@@ -85,7 +86,7 @@ wo_map_block* map_block_for(wo_planet* p, int32_t W, int32_t H) {
         block->W = W; block->H = H;
         p->map = block.release();
     }
-    p->map->valid = p->map->heightValid = false;             // any raster, through any entry point, ends the relief of the last
+    p->map->valid = p->map->heightValid = p->map->view = p->map->lambertValid = false;      // any raster, through any entry point, ends the relief and the view of the last
     return p->map;
 }
 
@@ -152,8 +153,9 @@ static int map_paint(wo_planet* p, const char* fn, const char* rasters, const Vi
         uint32_t* out = T.dev<uint32_t>((size_t)pixels);
         view_region_colors(p, T, plan, e, ViewSink{nullptr, regionRgba, d_lut}, families);
         if (riverMinQ) rivers_tint_regions(p, e, *riverMinQ, regionRgba);
-        launch(p, FAM_MAP_PIXELS, k_map_pixels, blocks_for((pixels + 3) / 4, 1 << 14), WO_BLOCK, (const int32_t*)B->region, (const uint32_t*)regionRgba, M::background_rgba(backgroundType, lut), out,
-               pixels);
+        launch(p, FAM_MAP_PIXELS, k_map_pixels, blocks_for((pixels + 3) / 4, 1 << 14), WO_BLOCK, (const int32_t*)B->region, (const uint32_t*)regionRgba,
+               B->view ? B->background : M::background_rgba(backgroundType, lut), out, pixels);
+        if (B->view && B->lambertValid) view_shade(p, B, out);
         WO_HIP(hipMemcpyAsync(rgbaOut, out, (size_t)pixels * 4, hipMemcpyDeviceToHost, s));
         WO_HIP(hipStreamSynchronize(s));                      // before T frees the temporaries; lut is this frame's
         return 0;

@@ -147,6 +147,7 @@ WO_IMP_HD inline void side_vertices(const int32_t* triangles, const int32_t* hal
 struct Projection {
     static constexpr int PIECES = 2;
     using Side = Tri[PIECES];                                 // a side's vertices, as side_triangles leaves them
+    using Word = uint32_t;                                    // the per-pixel word of the side map
     const LonLat* t_ll;
     const LonLat* r_ll;
     int32_t W, H;
@@ -166,6 +167,8 @@ struct Projection {
     }
     WO_IMP_HD void center(int32_t i, int32_t j, double& xc, double& yc) const { xc = pixel_xc(i, W); yc = pixel_yc(j, H); }
     WO_IMP_HD int64_t index(int32_t, int32_t i, int32_t j) const { return (int64_t)j * W + i; }      // in the side map
+    // what side s leaves, under a minimum, at a pixel centre that its triangle covers: its index
+    WO_IMP_HD Word word(const Side&, const Tri&, double, double, double, uint32_t s) const { return s; }
 };
 
 // ---- colours ----------------------------------------------------------------------------------------------------------------

@@ -20,7 +20,8 @@ const char* const kFamilyNames[FAM_COUNT] = {
     "pick", "pick_reduce", "highlight",
     "cube_centers", "cube_fill", "cube_sides", "cube_big_boxes", "cube_resolve",
     "relief_tri_elevation", "relief_heights", "relief_height16", "relief_tables", "relief_normals",
-    "rivers", "rivers_climb", "rivers_lines"};
+    "rivers", "rivers_climb", "rivers_lines",
+    "view_tables", "view_fill", "view_sides", "view_big_boxes", "view_resolve", "view_shade"};
 
 hipEvent_t profile_event(wo_planet* p) {
     if (!p->eventPool.empty()) { hipEvent_t e = p->eventPool.back(); p->eventPool.pop_back(); return e; }

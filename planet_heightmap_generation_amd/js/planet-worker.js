@@ -76,6 +76,14 @@
 //                  `centerLon` (radians, within [-pi, pi]) draws the map around that meridian.  Progress then counts types + layers.
 //                  -> { type: 'exportDone', width, height, maps: [{ type, filename, rgba, png? }],
 //                       _exportTiming: { raster, color, encode, workerTotal } }, the buffers transferred
+//   cmd 'renderGlobe' { type | types, layers?, width, height, camera?, shade?, rivers?, background?, exaggeration?, light?, ambient?,
+//                  diffuse?, png? }   (ours: the picture the reference's page draws with three.js, without a page)
+//                  -> { type: 'renderGlobeDone', width, height, covered, uncovered, maps: [{ type, filename, rgba, png? }], _exportTiming }
+//                  The displaced globe of the retained planet through a camera that looks at its centre (js/view-export.js; the contract
+//                  is in csrc/view_ops.h).  camera: { lon, lat, distance, fov } in degrees (north +Y, longitude 0 at +Z) or { eye, fov };
+//                  fov 0 with halfHeight is orthographic; nothing: the reference's 50 degrees at (0, 0.4, 2.8).  shade (default true):
+//                  one Lambert term per facet from `light` (default the reference's sun).  background: R | G << 8 | B << 16 | A << 24
+//                  for the pixels nothing covers (default 0x030308 opaque, 0: transparent).  types, layers, rivers: exportMap's.
 //   cmd 'exportCubeMap' { type | types, faceSize, png?, layers?, layout? }   (ours: the reference exports no cube map)
 //                  the cube map of the planet's current elevation and Koppen block: six square faces of faceSize x faceSize by
 //                  gnomonic projection, exactly the globe mesh seen from its centre, in the OpenGL order px nx py ny pz nz (north
@@ -167,6 +175,7 @@ import { denseTable, plateDensities, LAYERS } from './plate-table.js';
 import { generateCoarsePlates } from './coarse-plates.js';
 import { SimplexNoise } from './simplex-noise.js';
 import { MAP_TYPES, MAP_LAYERS, CUBE_MAX_FACE_SIZE, exportFilename, layerFilename, cubeFilename, cubeFaces, encodePng, rasterOnPlanet } from './map-export.js';
+import { VIEW_MAX_SIZE, viewFilename, viewParams } from './view-export.js';
 import { RELIEF_KINDS, reliefIs16, reliefFilename, reliefFaces, exportReliefOnPlanet, exportCubeReliefOnPlanet, encodePng16 } from './relief-export.js';
 import { GLOBE_PLATES, GLOBE_TYPE_VIEWS, computePlateColors, exportGlobeOnPlanet, globeFilename } from './globe-export.js';
 import { findNearestRegions, hitDirectionsGlobe, hitDirectionsMap, setHighlight, clearHighlight, PICK_MAX_QUERIES } from './edit-mode.js';
@@ -700,6 +709,54 @@ function handleExportRelief(data) {
     }
 }
 
+// ours: the globe of W.planet's current elevation and Koppen block through a camera: one view raster, one colour pass per type and layer
+function handleRenderGlobe(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for renderGlobe' }); return; }
+    const missing = ['triangles', 'halfedges'].filter((k) => !(W[k] instanceof Int32Array));
+    if (missing.length) {
+        parentPort.postMessage({ type: 'error', message: `renderGlobe: the retained state has no mesh.${missing.join(' and mesh.')} (pass them to retain, or run importHeightmap)` });
+        return;
+    }
+    try {
+        const tTotal0 = performance.now();
+        const { types, layers } = requestedMaps('renderGlobe', data);
+        const width = data.width, height = data.height;
+        for (const [k, v] of [['width', width], ['height', height]])
+            if (!(Number.isInteger(v) && v >= 1 && v <= VIEW_MAX_SIZE)) throw new RangeError(`renderGlobe: ${k} must be an integer from 1 to 16384`);
+        const rivers = data.rivers !== undefined && data.rivers !== null ? checkedMinFlow('renderGlobe', data.rivers) : null;
+        const params = viewParams(data);
+        progress(0, 'Rendering...');
+        let t0 = performance.now();
+        const r = addon.viewRaster(W.planet, W.triangles, W.halfedges, width, height, params, null, false);
+        const tRaster = performance.now() - t0;
+        t0 = performance.now();
+        const maps = [], total = types.length + layers.length;
+        types.forEach((type, k) => {
+            maps.push({ type, filename: viewFilename(type, W.seed), rgba: rivers === null ? addon.mapColor(W.planet, MAP_TYPES.indexOf(type), null)
+                                                                                               : addon.mapColorRivers(W.planet, MAP_TYPES.indexOf(type), null, rivers) });
+            progress(80 * (k + 1) / total, 'Rendering...');
+        });
+        layers.forEach((l, k) => {
+            maps.push({ type: l.name, filename: viewFilename(l.name, W.seed), rgba: addon.mapColorLayer(W.planet, l.id, l.values, null) });
+            progress(80 * (types.length + k + 1) / total, 'Rendering...');
+        });
+        const tColor = performance.now() - t0;
+        let tEncode = 0;
+        if (data.png) {
+            progress(85, 'Encoding PNG...');
+            t0 = performance.now();
+            for (const m of maps) m.png = encodePng(m.rgba, r.width, r.height);
+            tEncode = performance.now() - t0;
+        }
+        const transfer = [];
+        for (const m of maps) { transfer.push(m.rgba.buffer); if (m.png) transfer.push(m.png.buffer); }
+        parentPort.postMessage({ type: 'renderGlobeDone', width: r.width, height: r.height, covered: r.covered, uncovered: r.uncovered, maps,
+                                 _exportTiming: { raster: tRaster, color: tColor, encode: tEncode, workerTotal: performance.now() - tTotal0 } }, transfer);
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
 // ours: the cube map of W.planet's current elevation and Koppen block: one raster of the six faces, one colour pass per type and layer
 function handleExportCubeMap(data) {
     if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for exportCubeMap' }); return; }
@@ -915,6 +972,7 @@ parentPort.on('message', (data) => {
         case 'exportMap': handleExportMap(data); break;
         case 'exportCubeMap': handleExportCubeMap(data); break;
         case 'exportRelief': handleExportRelief(data); break;
+        case 'renderGlobe': handleRenderGlobe(data); break;
         case 'exportGlobe': handleExportGlobe(data); break;
         case 'computeRivers': handleComputeRivers(data); break;
         case 'exportOverlays': handleExportOverlays(data); break;

