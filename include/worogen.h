@@ -724,6 +724,47 @@ int wo_globe_mesh_plates(wo_planet* p, int32_t numSides, const int32_t* triangle
 int wo_globe_lines(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t kind,
                    const float* r_elevation, const float* superPlates, float* segmentsOut, int64_t capacity, int64_t* count);
 
+/* ------------------------------------------------ region outlines (ours) ---------------------- */
+/* Region outlines as ordered closed rings (ours: the reference draws no outline but the loose border segments above;
+ *   csrc/outline.hip, the bodies and the whole contract are in csrc/outline_ops.h).  The line where one class of cells ends and
+ *   another begins: a coastline, a lake shore, a plate, a Koppen zone, an elevation band.  The mesh must be a closed triangulation:
+ *   the checks and messages of wo_globe_lines (numSides a multiple of 3, every corner a region, every half-edge a side), and in
+ *   addition halfedges[halfedges[s]] == s.  Every Voronoi vertex then has exactly three cells around it, and the directed boundary
+ *   sides form a permutation whose cycles are the rings: there are no ambiguous junctions.
+ *   Classes, one int32 per cell, by source: WO_OUTLINE_COAST e > 0 ? 1 : 0 (a NaN is ocean; r_elevation NULL means the resident
+ *   field); WO_OUTLINE_LAKES 1 where the rivers block's r_lake_level is no NaN ("no rivers result" without that block);
+ *   WO_OUTLINE_KOPPEN the resident Koppen class ("no Koppen result" without it); WO_OUTLINE_LEVELS the number of levels[k] <= e for
+ *   numLevels (1 to 32) finite, strictly ascending floats, a NaN elevation class 0; WO_OUTLINE_VALUES the caller's numRegions int32
+ *   in values.  An argument that does not belong to the source (values with COAST, levels without LEVELS, r_elevation with any but
+ *   COAST and LEVELS) is refused.
+ *   Side s, with h = halfedges[s], is a boundary side iff class[triangles[s]] != class[triangles[h]] and, with onlyClass >= 0,
+ *   class[triangles[s]] == onlyClass.  onlyClass -1 traces every class: every undirected boundary edge then appears twice, once per
+ *   class, in opposite directions.  A ring keeps its class on the side of triangles[s] throughout; the successor of a side is an
+ *   O(1) expression in triangles, halfedges and the classes (csrc/outline_ops.h).  The boundary sides in ascending order take the
+ *   slots 0 .. M - 1; a ring's leader is its lowest slot; rings are numbered by ascending leader and run from their leader on.
+ *   wo_outline_build leaves four fields resident in an outline block the planet owns (a second call replaces them; wo_outline_free
+ *   and wo_planet_destroy drop them): sides (int32[M], ring after ring), ring_start (int32[R + 1], the last entry is M),
+ *   ring_class (int32[R]) and ring_of_side (int32[M]).  Everything is integer arithmetic: every word is defined.  The ordering is
+ *   list ranking by pointer doubling in rounds = ceil(log2(max(M, 2))) launches.  info (may be NULL) receives M, R, the longest ring,
+ *   the rounds and the kernel launches of the call.  M == 0 is a valid result: ring_start == {0}.
+ *   wo_outline_download copies one field by its key (outBytes at least its size).
+ *   The vertex of entry k is the centre of triangle sides[k] / 3; a ring is closed implicitly, its first vertex is not repeated.
+ *   wo_outline_positions gives 3 M floats, t_xyz * (base + displacement of t_elevation) exactly as wo_globe_lines displaces its
+ *   centres (base 1.002 over super plates gives the very floats of its border segments); base 0 means t_xyz itself.  r_elevation
+ *   NULL means the resident field; base must be finite.  wo_outline_lonlat gives 2 M doubles, longitude and latitude in radians, of
+ *   the same centres as wo_map_raster places them: outlines lie exactly on the vertices of the exported map.
+ *   Without an outline block the download, positions and lonlat calls answer status 1, "no outline result".
+ *   A refused call returns 1, names the call and the offending value, allocates nothing and leaves the planet what it had. */
+enum { WO_OUTLINE_COAST = 0, WO_OUTLINE_LAKES = 1, WO_OUTLINE_KOPPEN = 2, WO_OUTLINE_LEVELS = 3, WO_OUTLINE_VALUES = 4 };
+typedef struct wo_outline_info { int32_t boundarySides, rings, longestRing, rounds, launches; } wo_outline_info;
+int wo_outline_build(wo_planet* p, int32_t numSides, const int32_t* triangles, const int32_t* halfedges, int32_t source,
+                     const float* r_elevation, const int32_t* values, const float* levels, int32_t numLevels, int32_t onlyClass,
+                     wo_outline_info* info);
+int wo_outline_download(wo_planet* p, const char* field, void* out, int64_t outBytes);
+int wo_outline_positions(wo_planet* p, double base, const float* r_elevation, float* xyzOut, int64_t outFloats);
+int wo_outline_lonlat(wo_planet* p, double* lonLatOut, int64_t outDoubles);
+int wo_outline_free(wo_planet* p);
+
 /* ------------------------------------------------ arrow overlays (js/planet-mesh.js) ---------- */
 /* buildWindArrows, buildOceanCurrentArrows                                        js/planet-mesh.js:1289-1465, :1545-1720
  *   The arrows the reference draws over its wind and ocean-current views, as its own Float32Arrays bit for bit (csrc/overlay.hip;

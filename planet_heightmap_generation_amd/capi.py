@@ -112,7 +112,12 @@ SIGNATURES = {
     "wo_globe_mesh": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _c_i32, _p, _p, _p, _p, _c_i64, _p]),
     "wo_globe_mesh_plates": (C.c_int, [_p, _c_i32, _p, _p, _p, _c_i32, _p, _p, _p, _p, _p, _c_i64, _p]),
     "wo_globe_lines": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _p, _p, _p, _c_i64, _p]),
-    "wo_overlay_bins": (C.c_int, [_p, _c_i32, _p, _p]),
+    "wo_outline_build": (C.c_int, [_p, _c_i32, _p, _p, _c_i32, _p, _p, _p, _c_i32, _c_i32, _p]),
+    "wo_outline_download": (C.c_int, [_p, C.c_char_p, _p, _c_i64]),
+    "wo_outline_positions": (C.c_int, [_p, _c_f64, _p, _p, _c_i64]),
+    "wo_outline_lonlat": (C.c_int, [_p, _p, _c_i64]),
+    "wo_outline_free": (C.c_int, [_p]),
+    "wo_overlay_bins":(C.c_int, [_p, _c_i32, _p, _p]),
     "wo_overlay_arrows": (C.c_int, [_p, _c_i32, _c_i32, _c_f64, _p, _p, _p, _p, _p, _c_i64, _p]),
     "wo_pick_regions": (C.c_int, [_p, _c_i32, _p, _p, _p]),
     "wo_pick_directions_globe": (C.c_int, [_c_i32, _p, _p, _p]),

@@ -63,7 +63,8 @@ enum Family : int {
     FAM_CUBE_CENTERS, FAM_CUBE_FILL, FAM_CUBE_SIDES, FAM_CUBE_BIG_BOXES, FAM_CUBE_RESOLVE,
     FAM_RELIEF_TRI_ELEVATION, FAM_RELIEF_HEIGHTS, FAM_RELIEF_HEIGHT16, FAM_RELIEF_TABLES, FAM_RELIEF_NORMALS,
     FAM_RIVERS, FAM_RIVERS_CLIMB, FAM_RIVERS_LINES,
-    FAM_VIEW_TABLES, FAM_VIEW_FILL, FAM_VIEW_SIDES, FAM_VIEW_BIG_BOXES, FAM_VIEW_RESOLVE, FAM_VIEW_SHADE, FAM_COUNT
+    FAM_VIEW_TABLES, FAM_VIEW_FILL, FAM_VIEW_SIDES, FAM_VIEW_BIG_BOXES, FAM_VIEW_RESOLVE, FAM_VIEW_SHADE,
+    FAM_OUTLINE_CLASSIFY, FAM_OUTLINE_FLAGS, FAM_OUTLINE_SUCC, FAM_OUTLINE_RANK, FAM_OUTLINE_RINGS, FAM_OUTLINE_POSITIONS, FAM_COUNT
 };
 extern const char* const kFamilyNames[FAM_COUNT];
 
@@ -189,6 +190,9 @@ struct wo_planet {
     // erodeComposite (erode.hip, basin.hip, sort.hip, radix.hip; erode_block.h): the erosion block — land lists, sort, flow, solve,
     // ice and carve state, built group by group from the planet's first erodeComposite call on; deleted by wo_planet_destroy (erode_free)
     struct wo_erode_block* erode = nullptr;
+    // region outlines (outline.hip): the outline block — the rings of the last wo_outline_build (8 bytes per boundary side and per
+    // ring, and 12 per side for the corners its vertices are made of); deleted by wo_outline_free and wo_planet_destroy (outline_free)
+    struct wo_outline_block* outline = nullptr;
 
     // Patch-major mirror of the mesh for erodeComposite (mirror.hip, MirrorScope): the same graph with the cells renamed in
     // Morton order of their positions, rows in the reference's order.  While a scope is active the pointers above (mesh, d_e,
@@ -256,6 +260,8 @@ void ocean_free(wo_planet* p);
 void precip_free(wo_planet* p);
 void temp_free(wo_planet* p);
 void rivers_free(wo_planet* p);
+// outline.hip: drops the outline block
+void outline_free(wo_planet* p);
 // map.hip: drops the map block
 void map_free(wo_planet* p);
 // globe.hip: drops the highlight state; its class bytes (on the device), nullptr when no state is set

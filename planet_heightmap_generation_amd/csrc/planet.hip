@@ -245,6 +245,7 @@ void wo_planet_destroy(wo_planet* p) {
     if (p->floodLink && p->floodLinkFree) p->floodLinkFree(p->floodLink);
     p->floodLink = nullptr;
     highlight_free(p);
+    outline_free(p);
     map_free(p);
     temp_free(p);
     rivers_free(p);

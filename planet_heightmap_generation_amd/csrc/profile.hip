@@ -21,7 +21,8 @@ const char* const kFamilyNames[FAM_COUNT] = {
     "cube_centers", "cube_fill", "cube_sides", "cube_big_boxes", "cube_resolve",
     "relief_tri_elevation", "relief_heights", "relief_height16", "relief_tables", "relief_normals",
     "rivers", "rivers_climb", "rivers_lines",
-    "view_tables", "view_fill", "view_sides", "view_big_boxes", "view_resolve", "view_shade"};
+    "view_tables", "view_fill", "view_sides", "view_big_boxes", "view_resolve", "view_shade",
+    "outline_classify", "outline_flags", "outline_succ", "outline_rank", "outline_rings", "outline_positions"};
 
 hipEvent_t profile_event(wo_planet* p) {
     if (!p->eventPool.empty()) { hipEvent_t e = p->eventPool.back(); p->eventPool.pop_back(); return e; }

@@ -30,6 +30,7 @@ LINE_KINDS = ("wireframe", "superPlateBorders")
 # the opacities of the reference's two black line materials (js/planet-mesh.js:792, :573)
 LINE_OPACITY = {"wireframe": 0.12, "superPlateBorders": 0.55}
 GLB_MAX_BYTES = 0xFFFFFFFF                                    # the container's lengths are uint32
+OUTLINE_COLOR = (0.1, 0.1, 0.1)                               # the rings of outline_export in the GLB: our decision
 RIVER_COLOR = (41, 98, 168)                                   # the map tint of the rivers (csrc/rivers_ops.h), over 255 in the GLB
 
 
@@ -253,7 +254,8 @@ def _overlay_part(v, what: str):
     return pos, col
 
 
-def encode_glb(mesh: dict, wireframe=None, super_plate_borders=None, name: str = "globe", wind_arrows=None, ocean_current_arrows=None, itcz=None, grid=None, rivers=None) -> bytes:
+def encode_glb(mesh: dict, wireframe=None, super_plate_borders=None, name: str = "globe", wind_arrows=None, ocean_current_arrows=None, itcz=None, grid=None, rivers=None,
+               outlines=None) -> bytes:
     """A glTF 2.0 binary container of one buffer and one mesh: a TRIANGLES primitive with POSITION (f32 VEC3, min / max from
     mesh['bounds']) and COLOR_0 (f32 VEC3, linear as glTF's vertex colours are), its material the default metallic-roughness one with
     metallic 0 and roughness 1 (our decision: the reference's Lambert shader and its normals are not offered), and a LINES primitive
@@ -261,7 +263,8 @@ def encode_glb(mesh: dict, wireframe=None, super_plate_borders=None, name: str =
     primitives under unlit materials (KHR_materials_unlit, named only when one of them is there): wind_arrows and
     ocean_current_arrows with COLOR_0 at the reference's opacity 0.6, itcz in 0x00ff88 (the hex channels over 255, as glTF takes a
     linear factor: our decision), grid white at 0.12, rivers (the segments of rivers.river_lines) in the map tint's (41, 98, 168) over
-    255; each is the globe form, or a result dict that has one.  Without them the bytes are what they were before the overlays existed.  A planet whose buffers exceed the container's uint32 lengths is refused."""
+    255, outlines (the rings of outline_export as segments, outline_export.ring_segments) in OUTLINE_COLOR; each is the globe form, or
+    a result dict that has one.  Without them the bytes are what they were before the overlays existed.  A planet whose buffers exceed the container's uint32 lengths is refused."""
     from . import overlay_export as OE
     position, color, bounds = mesh["position"], mesh["color"], mesh["bounds"]
     if position is None or color is None or bounds is None:
@@ -275,7 +278,8 @@ def encode_glb(mesh: dict, wireframe=None, super_plate_borders=None, name: str =
     white = [1, 1, 1]
     overlays = []                                             # (name, positions, colours or None, base colour factor)
     for k, v, factor in (("windArrows", wind_arrows, white + [OE.ARROW_OPACITY]), ("oceanCurrentArrows", ocean_current_arrows, white + [OE.ARROW_OPACITY]),
-                         ("itcz", itcz, list(OE.ITCZ_COLOR) + [1]), ("grid", grid, white + [OE.GRID_OPACITY]), ("rivers", rivers, [c / 255 for c in RIVER_COLOR] + [1])):
+                         ("itcz", itcz, list(OE.ITCZ_COLOR) + [1]), ("grid", grid, white + [OE.GRID_OPACITY]), ("rivers", rivers, [c / 255 for c in RIVER_COLOR] + [1]),
+                         ("outlines", outlines, list(OUTLINE_COLOR) + [1])):
         if v is None:
             continue
         pos, col = _overlay_part(v, k)
@@ -345,12 +349,13 @@ def encode_glb(mesh: dict, wireframe=None, super_plate_borders=None, name: str =
 
 
 def export_globe(planet: TP.Planet, mesh, view="color", seed=0, r_elevation=None, values=None, plates=None, wireframe: bool = False, super_plates=None, glb: bool = True,
-                 wind_arrows=None, ocean_current_arrows=None, itcz=None, grid=None, rivers=None) -> dict:
+                 wind_arrows=None, ocean_current_arrows=None, itcz=None, grid=None, rivers=None, outlines=None) -> dict:
     """The globe in one view: build_mesh, the wireframe when asked for, the super-plate borders when super_plates (numRegions floats)
     is given, the overlays of overlay_export when asked for (wind_arrows, ocean_current_arrows, itcz: 'summer' or 'winter'; grid: the
-    spacing in degrees; rivers: a minimum flow, the segments of the planet's rivers block that reach it, see rivers.river_lines), and
+    spacing in degrees; rivers: a minimum flow, the segments of the planet's rivers block that reach it, see rivers.river_lines;
+    outlines: dict(source=..., and the further arguments of outline_export.build_outline), the rings at base 1.002 as segments), and
     the GLB bytes of all of it.
-    -> {filename, position, color, bounds[, wireframe][, superPlateBorders][, windArrows][, oceanCurrentArrows][, itcz][, grid][, rivers][, glb]}"""
+    -> {filename, position, color, bounds[, wireframe][, superPlateBorders][, windArrows][, oceanCurrentArrows][, itcz][, grid][, rivers][, outlines][, glb]}"""
     from . import overlay_export as OE
     res = build_mesh(planet, mesh, view, r_elevation, values, plates)
     res["filename"] = globe_filename(view, seed)
@@ -369,7 +374,12 @@ def export_globe(planet: TP.Planet, mesh, view="color", seed=0, r_elevation=None
     if rivers is not None:
         from . import rivers as RI
         res["rivers"] = RI.river_lines(planet, rivers, r_elevation)["segments"].reshape(-1)
+    if outlines is not None:
+        from . import outline_export as OL
+        kw = dict(outlines)
+        rings = OL.build_outline(planet, mesh, kw.pop("source"), r_elevation=r_elevation, base=OL.GLOBE_BASE, **kw)
+        res["outlines"] = OL.ring_segments(rings)
     if glb:
         res["glb"] = encode_glb(res, res.get("wireframe"), res.get("superPlateBorders"), wind_arrows=res.get("windArrows"), ocean_current_arrows=res.get("oceanCurrentArrows"),
-                                itcz=res.get("itcz"), grid=res.get("grid"), rivers=res.get("rivers"))
+                                itcz=res.get("itcz"), grid=res.get("grid"), rivers=res.get("rivers"), outlines=res.get("outlines"))
     return res

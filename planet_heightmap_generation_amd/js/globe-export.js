@@ -9,6 +9,7 @@ import { MAP_TYPES, MAP_LAYERS } from './map-export.js';
 import { globeFilename, encodeGlb } from './globe-glb.js';
 import { windArrowsOnPlanet, oceanCurrentArrowsOnPlanet, itczLine, globeGrid } from './overlay-export.js';
 import { riverLinesOnPlanet } from './rivers.js';
+import { OUTLINE_GLOBE_BASE, buildOutlineOnPlanet, outlineSegments } from './outline-export.js';
 
 export const GLOBE_PLATES = 'plates';
 export const GLOBE_TYPE_VIEWS = MAP_TYPES.filter((t) => t !== 'landmask');
@@ -54,7 +55,7 @@ export function buildWireframe(mesh, r_xyz, r_elevation) { return wireframeOnPla
 // updateSuperPlateBorders(mesh, r_xyz, r_elevation, superPlates) -> Float32Array(segments * 6): the globe form
 export function updateSuperPlateBorders(mesh, r_xyz, r_elevation, superPlates) { return superPlateBordersOnPlanet(planetFor(mesh, r_xyz), mesh.triangles, mesh.halfedges, r_elevation, superPlates); }
 
-// the globe in one view on a planet handle: { filename, position, color, bounds[, wireframe][, superPlateBorders][, windArrows][, oceanCurrentArrows][, itcz][, grid][, rivers][, glb] }
+// the globe in one view on a planet handle: { filename, position, color, bounds[, wireframe][, superPlateBorders][, windArrows][, oceanCurrentArrows][, itcz][, grid][, rivers][, outlines][, glb] }
 export function exportGlobeOnPlanet(planet, triangles, halfedges, r_elevation, view, seed, opts) {
     const o = opts || {};
     const res = buildMeshOnPlanet(planet, triangles, halfedges, r_elevation, view, o);
@@ -68,13 +69,18 @@ export function exportGlobeOnPlanet(planet, triangles, halfedges, r_elevation, v
     if (o.grid !== undefined && o.grid !== null) res.grid = globeGrid(o.grid);
     // rivers: { minFlow }, the segments of the planet's rivers block that reach it (js/rivers.js)
     if (o.rivers !== undefined && o.rivers !== null) res.rivers = riverLinesOnPlanet(planet, o.rivers.minFlow, r_elevation).segments;
+    // outlines: { source, values, levels, onlyClass }, the rings of js/outline-export.js at base 1.002 as segments
+    if (o.outlines !== undefined && o.outlines !== null) {
+        const rings = buildOutlineOnPlanet(planet, triangles, halfedges, o.outlines.source, Object.assign({}, o.outlines, { r_elevation, base: OUTLINE_GLOBE_BASE, lonlat: false }));
+        res.outlines = outlineSegments(rings);
+    }
     if (o.glb !== false) {
         res.glb = encodeGlb(res, { wireframe: res.wireframe, superPlateBorders: res.superPlateBorders, windArrows: res.windArrows, oceanCurrentArrows: res.oceanCurrentArrows,
-                                   itcz: res.itcz, grid: res.grid, rivers: res.rivers });
+                                   itcz: res.itcz, grid: res.grid, rivers: res.rivers, outlines: res.outlines });
     }
     return res;
 }
-// exportGlobe(mesh, r_xyz, r_elevation, view, seed, { values, plates, wireframe, superPlates, windArrows, oceanCurrentArrows, itcz, grid, rivers, glb })
+// exportGlobe(mesh, r_xyz, r_elevation, view, seed, { values, plates, wireframe, superPlates, windArrows, oceanCurrentArrows, itcz, grid, rivers, outlines, glb })
 export function exportGlobe(mesh, r_xyz, r_elevation, view, seed, opts) {
     return exportGlobeOnPlanet(planetFor(mesh, r_xyz), mesh.triangles, mesh.halfedges, r_elevation, view, seed, opts);
 }

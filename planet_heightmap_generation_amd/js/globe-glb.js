@@ -8,6 +8,7 @@ export const GLB_MAX_BYTES = 0xFFFFFFFF;                    // the container's l
 export const ARROW_OPACITY = 0.6;
 export const ITCZ_COLOR = [0, 1, 0x88 / 255];
 export const RIVER_COLOR = [41 / 255, 98 / 255, 168 / 255];      // the map tint of the rivers (csrc/rivers_ops.h)
+export const OUTLINE_COLOR = [0.1, 0.1, 0.1];                    // the rings of js/outline-export.js in the GLB: our decision
 export const GRID_OPACITY = 0.12;
 
 // ours: the reference exports no globe
@@ -85,8 +86,8 @@ function overlayPart(v, what) {
 // overlays of overlay-export.js follow as further LINES primitives under unlit materials (KHR_materials_unlit, named only when one
 // of them is there): windArrows and oceanCurrentArrows with COLOR_0 at the reference's opacity 0.6, itcz in 0x00ff88 (the hex
 // channels over 255, as glTF takes a linear factor: our decision), grid white at 0.12, rivers (the segments of js/rivers.js) in the
-// map tint's (41, 98, 168) over 255; each is the globe form, or a result that has one.  Without them the bytes are what they were
-// before the overlays existed.
+// map tint's (41, 98, 168) over 255, outlines (the rings of js/outline-export.js as segments: outlineSegments) in OUTLINE_COLOR; each
+// is the globe form, or a result that has one.  Without them the bytes are what they were before the overlays existed.
 export function encodeGlb(mesh, opts) {
     const o = opts || {}, { position, color, bounds } = mesh;
     if (!(position instanceof Float32Array) || !(color instanceof Float32Array) || !(bounds instanceof Float32Array)) throw new TypeError("encodeGlb needs position, color and bounds (buildMesh's result)");
@@ -95,7 +96,8 @@ export function encodeGlb(mesh, opts) {
     for (const [k, a] of lines) if (a.length % 6) throw new RangeError(`${k} has ${a.length} floats, no multiple of 6`);
     const white = [1, 1, 1], overlays = [];                 // [name, positions, colours or null, base colour factor]
     for (const [k, v, factor] of [['windArrows', o.windArrows, white.concat([ARROW_OPACITY])], ['oceanCurrentArrows', o.oceanCurrentArrows, white.concat([ARROW_OPACITY])],
-                                  ['itcz', o.itcz, ITCZ_COLOR.concat([1])], ['grid', o.grid, white.concat([GRID_OPACITY])], ['rivers', o.rivers, RIVER_COLOR.concat([1])]]) {
+                                  ['itcz', o.itcz, ITCZ_COLOR.concat([1])], ['grid', o.grid, white.concat([GRID_OPACITY])], ['rivers', o.rivers, RIVER_COLOR.concat([1])],
+                                  ['outlines', o.outlines, OUTLINE_COLOR.concat([1])]]) {
         if (v === undefined || v === null) continue;
         const [pos, col] = overlayPart(v, k);
         if ((col === null) === k.endsWith('Arrows')) throw new TypeError(`${k} takes ` + (col === null ? '{ position, color }' : 'positions alone'));

@@ -121,7 +121,7 @@
 //                  exportOverlays) as arrays (arrows: { position, color }) or as LINES primitives of the GLB.
 //                  Progress: `Building globe...` at 0, `Done` at 90.
 //                  -> { type: 'globeDone', view, filename, numSides, bounds, glb | position, color[, wireframe][, superPlateBorders][, windArrows]
-//                       [, oceanCurrentArrows][, itcz][, grid],
+//                       [, oceanCurrentArrows][, itcz][, grid][, rivers][, outlines],
 //                       _globeTiming: { workerTotal } }, the buffers transferred
 //   cmd 'computeRivers' { runoff?, download? }   (ours: js/rivers.js, csrc/rivers.hip)
 //                  the rivers and lakes of the planet's current elevation: every land cell drains to its lowest neighbour, depressions
@@ -136,6 +136,21 @@
 //                  exportMap and exportCubeMap take `rivers: { minFlow }`: the types' maps (not the layers') get the river cells whose flow
 //                  reaches minFlow and the lakes painted (41, 98, 168); exportGlobe takes the same and adds the river segments as `rivers`
 //                  (Float32Array, six floats each) or as one more LINES primitive of the GLB.  `no rivers result` before computeRivers.
+//   cmd 'exportOutlines' { source, levels?, values?, onlyClass?, format?, width?, centerLon? }   (ours: js/outline-export.js, csrc/outline.hip)
+//                  the line where one class of cells ends and another begins, traced on the device into ordered closed rings of the
+//                  Voronoi cells' sides.  `source`: 'coast' (elevation > 0 of the planet's current field), 'lakes' (the lake levels of
+//                  computeRivers; `no rivers result` before it), 'koppen' (computeClimate's classes; `no Koppen result` before it),
+//                  'levels' with `levels`: up to 32 ascending elevations, 'values' with `values`: an Int32Array of numRegions classes,
+//                  and the shorthands 'plates' (the retained r_plate) and 'superPlates' (the retained debugLayers.superPlates, a NaN
+//                  cell a class of its own).  `onlyClass`: the rings of that class alone (default: of every class, every boundary
+//                  edge then once per class).  `format`: 'arrays' (the default), 'geojson' or 'svg' (`width`, default 2048, and
+//                  `centerLon` in radians: exportMap's pixel frame); both texts are cut where a ring crosses the map's edge.
+//                  Needs what exportMap needs of the retained state.
+//                  -> { type: 'outlinesDone', source, format, filename, boundarySides, rings, longestRing, rounds, launches,
+//                       sides, ring_start, ring_class, ring_of_side: Int32Array, lonlat: Float64Array (radians) | text,
+//                       _outlineTiming: { workerTotal } }, the buffers transferred
+//                  exportGlobe takes `outlines: { source, levels?, values?, onlyClass? }` and adds the rings, displaced as the super-plate
+//                  borders are (base 1.002), as `outlines` (Float32Array, six floats per segment) or as one more LINES primitive of the GLB.
 //   cmd 'exportOverlays' { windArrows?, oceanCurrentArrows?, itcz?, grid?, centerLon? }   (js/planet-mesh.js:1289-1749, :385-469)
 //                  the line overlays of the reference's views in both forms, globe and map (js/overlay-export.js): `windArrows`,
 //                  `oceanCurrentArrows`: 'summer' | 'winter', the arrows of that season from the blocks computeClimate left on the planet,
@@ -180,6 +195,7 @@ import { RELIEF_KINDS, reliefIs16, reliefFilename, reliefFaces, exportReliefOnPl
 import { GLOBE_PLATES, GLOBE_TYPE_VIEWS, computePlateColors, exportGlobeOnPlanet, globeFilename } from './globe-export.js';
 import { findNearestRegions, hitDirectionsGlobe, hitDirectionsMap, setHighlight, clearHighlight, PICK_MAX_QUERIES } from './edit-mode.js';
 import { computeRiversOnPlanet, checkedMinFlow, RIVER_KEYS } from './rivers.js';
+import { OUTLINE_FIELDS, OUTLINE_SOURCES, buildOutlineOnPlanet, outlineFilename, outlineToGeoJSON, outlineToSvg } from './outline-export.js';
 import { SEASONS, windArrowsOnPlanet, oceanCurrentArrowsOnPlanet, itczLine, grids } from './overlay-export.js';
 
 let W = null;          // retained state (js/planet-worker.js:22)
@@ -878,6 +894,10 @@ function handleExportGlobe(data) {
         if (data.itcz !== undefined && data.itcz !== null) opts.itcz = itczOf('exportGlobe', data.itcz);
         if (data.grid !== undefined && data.grid !== null) opts.grid = data.grid;
         if (data.rivers !== undefined && data.rivers !== null) opts.rivers = { minFlow: checkedMinFlow('exportGlobe', data.rivers) };
+        if (data.outlines !== undefined && data.outlines !== null) {
+            const req = outlineRequest('exportGlobe', data.outlines);
+            opts.outlines = Object.assign({}, req.opts, { source: req.source });
+        }
         progress(0, 'Building globe...');
         const name = data.plates ? GLOBE_PLATES : (data.layer !== undefined && data.layer !== null ? data.layer : view);
         const res = exportGlobeOnPlanet(W.planet, W.triangles, W.halfedges, null, view, W.seed, opts);
@@ -888,10 +908,57 @@ function handleExportGlobe(data) {
         else {
             msg.position = res.position; msg.color = res.color;
             transfer.push(res.position.buffer, res.color.buffer);
-            for (const k of ['wireframe', 'superPlateBorders', 'itcz', 'grid', 'rivers']) if (res[k]) { msg[k] = res[k]; transfer.push(res[k].buffer); }
+            for (const k of ['wireframe', 'superPlateBorders', 'itcz', 'grid', 'rivers', 'outlines']) if (res[k]) { msg[k] = res[k]; transfer.push(res[k].buffer); }
             for (const k of ['windArrows', 'oceanCurrentArrows']) if (res[k]) { msg[k] = res[k]; transfer.push(res[k].position.buffer, res[k].color.buffer); }
         }
         msg._globeTiming = { workerTotal: performance.now() - tTotal0 };
+        parentPort.postMessage(msg, transfer);
+    } catch (err) {
+        parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
+    }
+}
+
+// a command's { source, levels, values, onlyClass } -> what buildOutlineOnPlanet takes; 'plates' and 'superPlates' pass the worker's own arrays as values
+function outlineRequest(fn, data) {
+    if (!data || typeof data !== 'object' || typeof data.source !== 'string') throw new TypeError(`${fn}: outlines take { source, levels?, values?, onlyClass? }`);
+    const req = { name: data.source, source: data.source, opts: { levels: data.levels, values: data.values, onlyClass: data.onlyClass } };
+    if (data.source === 'plates') {
+        if (!(W.r_plate instanceof Int32Array)) throw new Error(`${fn}: the retained state has no r_plate`);
+        req.source = 'values'; req.opts.values = W.r_plate;
+    } else if (data.source === 'superPlates') {
+        const sp = (W.debugLayers || {}).superPlates;
+        if (!(sp instanceof Float32Array)) throw new Error(`${fn}: the retained debugLayers have no superPlates (generate or editRecompute with P >= 8 leaves them)`);
+        // the borders compare floats, a NaN differs from everything: as int32 classes every NaN cell gets a class of its own
+        req.source = 'values'; req.opts.values = Int32Array.from(sp, (v, r) => (Number.isNaN(v) ? -1 - r : v));
+    } else if (OUTLINE_SOURCES.indexOf(data.source) < 0) {
+        throw new RangeError(`${fn}: unknown outline source '${data.source}' (one of ${OUTLINE_SOURCES.concat(['plates', 'superPlates']).join(', ')})`);
+    }
+    return req;
+}
+
+// ours: the outlines of W.planet's current state as rings, as arrays or written out
+function handleExportOutlines(data) {
+    if (!W) { parentPort.postMessage({ type: 'error', message: 'No retained state for exportOutlines' }); return; }
+    const missing = ['triangles', 'halfedges'].filter((k) => !(W[k] instanceof Int32Array));
+    if (missing.length) {
+        parentPort.postMessage({ type: 'error', message: `exportOutlines: the retained state has no mesh.${missing.join(' and mesh.')} (pass them to retain, or run importHeightmap)` });
+        return;
+    }
+    try {
+        const tTotal0 = performance.now();
+        const format = data.format === undefined || data.format === null ? 'arrays' : data.format;
+        if (['arrays', 'geojson', 'svg'].indexOf(format) < 0) throw new RangeError(`exportOutlines: unknown format '${format}' (one of arrays, geojson, svg)`);
+        const req = outlineRequest('exportOutlines', data);
+        progress(0, 'Tracing outlines...');
+        const res = buildOutlineOnPlanet(W.planet, W.triangles, W.halfedges, req.source, Object.assign({}, req.opts, { lonlat: true }));
+        progress(90, 'Done');
+        const msg = { type: 'outlinesDone', source: req.name, format, ...res.info, filename: outlineFilename(req.name, W.seed, format === 'svg' ? 'svg' : 'geojson') };
+        const transfer = [];
+        if (format === 'arrays') {
+            for (const k of OUTLINE_FIELDS.concat(['lonlat'])) { msg[k] = res[k]; transfer.push(res[k].buffer); }
+        } else if (format === 'geojson') msg.text = outlineToGeoJSON(res, { source: req.name });
+        else msg.text = outlineToSvg(res, data.width === undefined || data.width === null ? 2048 : data.width, data.centerLon || 0);
+        msg._outlineTiming = { workerTotal: performance.now() - tTotal0 };
         parentPort.postMessage(msg, transfer);
     } catch (err) {
         parentPort.postMessage({ type: 'error', message: err.message, stack: err.stack });
@@ -975,6 +1042,7 @@ parentPort.on('message', (data) => {
         case 'renderGlobe': handleRenderGlobe(data); break;
         case 'exportGlobe': handleExportGlobe(data); break;
         case 'computeRivers': handleComputeRivers(data); break;
+        case 'exportOutlines': handleExportOutlines(data); break;
         case 'exportOverlays': handleExportOverlays(data); break;
         case 'generate': handleGenerate(data); break;
         case 'pick': handlePick(data); break;

@@ -1069,6 +1069,46 @@ napi_value GlobeLines(napi_env env, napi_callback_info info) {
     return c.copy(seg.data(), count * 6);
 }
 
+// ---- region outlines (include/worogen.h: wo_outline_build / wo_outline_download / wo_outline_positions / wo_outline_lonlat) ----
+// outlineBuild(planet, triangles, halfedges, source 0..4, r_elevation | null, values Int32Array | null, levels Float32Array | null, onlyClass = -1)
+//   -> { boundarySides, rings, longestRing, rounds, launches }; the rings stay in the planet's outline block
+napi_value OutlineBuild(napi_env env, napi_callback_info info) {
+    Call c(env, info, "outlineBuild");
+    int32_t *tri, *he; size_t ns; c.sides(&tri, &he, &ns);
+    wo_planet* p = c.planet();
+    float* e = c.regions<float>(4, p, "r_elevation"); int32_t* values = c.regions<int32_t>(5, p, "values");
+    size_t nl; float* levels = c.opt<float>(6, &nl);
+    if (!c.ok) return nullptr;
+    wo_outline_info I{};
+    if (wo_outline_build(p, (int32_t)ns, tri, he, c.i32(3), e, values, levels, (int32_t)nl, c.has(7) ? c.i32(7) : -1, &I)) return c.fail();
+    napi_value o = c.object();
+    c.set_nums(o, {{"boundarySides", (double)I.boundarySides}, {"rings", (double)I.rings}, {"longestRing", (double)I.longestRing}, {"rounds", (double)I.rounds}, {"launches", (double)I.launches}});
+    return c.done(o);
+}
+// outlineDownload(planet, field, count) -> Int32Array(count): sides and ring_of_side hold boundarySides entries, ring_start rings + 1, ring_class rings
+napi_value OutlineDownload(napi_env env, napi_callback_info info) {
+    Call c(env, info, "outlineDownload");
+    wo_planet* p = c.planet();
+    char key[64];
+    if (!c.key(1, key)) return nullptr;
+    const int64_t count = (int64_t)c.num(2);
+    return c.filled<int32_t>(count, [&](int32_t* d) { return wo_outline_download(p, key, d, count * 4); });
+}
+// outlinePositions(planet, count, base, r_elevation | null) -> Float32Array(count * 3)
+napi_value OutlinePositions(napi_env env, napi_callback_info info) {
+    Call c(env, info, "outlinePositions");
+    wo_planet* p = c.planet(); float* e = c.regions<float>(3, p, "r_elevation");
+    const int64_t count = (int64_t)c.num(1);
+    return c.filled<float>(count * 3, [&](float* d) { return wo_outline_positions(p, c.num(2), e, d, count * 3); });
+}
+// outlineLonLat(planet, count) -> Float64Array(count * 2): longitude and latitude in radians
+napi_value OutlineLonLat(napi_env env, napi_callback_info info) {
+    Call c(env, info, "outlineLonLat");
+    wo_planet* p = c.planet();
+    const int64_t count = (int64_t)c.num(1);
+    return c.filled<double>(count * 2, [&](double* d) { return wo_outline_lonlat(p, d, count * 2); });
+}
+
 // ---- arrow overlays (include/worogen.h: wo_overlay_bins / wo_overlay_arrows) ----------------------------------------------
 // overlayBins(planet, skipLand, r_elevation | null) -> Int32Array(7200): per 3 x 3 degree cell the region closest to its centre, -1 for none
 napi_value OverlayBins(napi_env env, napi_callback_info info) {
@@ -1252,6 +1292,10 @@ napi_value Init(napi_env env, napi_value exports) {
     const napi_property_descriptor later[] = {
         {"viewRaster", nullptr, ViewRaster, nullptr, nullptr, nullptr, (napi_property_attributes)(napi_writable | napi_configurable), nullptr},
         {"viewDepth", nullptr, ViewDepth, nullptr, nullptr, nullptr, (napi_property_attributes)(napi_writable | napi_configurable), nullptr},
+        {"outlineBuild", nullptr, OutlineBuild, nullptr, nullptr, nullptr, (napi_property_attributes)(napi_writable | napi_configurable), nullptr},
+        {"outlineDownload", nullptr, OutlineDownload, nullptr, nullptr, nullptr, (napi_property_attributes)(napi_writable | napi_configurable), nullptr},
+        {"outlinePositions", nullptr, OutlinePositions, nullptr, nullptr, nullptr, (napi_property_attributes)(napi_writable | napi_configurable), nullptr},
+        {"outlineLonLat", nullptr, OutlineLonLat, nullptr, nullptr, nullptr, (napi_property_attributes)(napi_writable | napi_configurable), nullptr},
     };
     if (napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later) != napi_ok) return nullptr;
     napi_value ver; napi_create_int32(env, wo_abi_version(), &ver); napi_set_named_property(env, exports, "abiVersion", ver);
